@@ -8,7 +8,13 @@
 precompute + H2D), the pose upload, the device noise draws, the 20-step loop and the pose write-back are all inside; K calls
 back to back, one device synchronisation at the end, value = K / wall (x world).  One "step" = one complex.
 
-    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5]
+    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5] [--dump-outputs DIR] [--full]
+
+A plain run times the headline bracket alone: set-up, W warm-up calls, ONE pass of exactly K timed calls, the result line.  ``--full`` adds
+everything else below (the median of three passes for K <= 64, the extra brackets, the other conv kernels, the CPU oracle, the boundary-A
+kernel, the 363-complex stream); the --no-* options then skip parts of it.  ``--dump-outputs DIR`` writes what the last timed call returned
+(final poses of its samples; latent poses under configs 3 / 4, confidences under config 4) as DIR/<name>.npy in float32; the inputs of a run
+are seeded, so two builds run with the same arguments can be compared output for output.
 
 configs (BASELINE.json ``configs``; the driver's N = 1 line is config 2):
   2  DiffDock-S score model, 8 synthetic complexes (~30 ligand atoms / 300 C-alpha) per GPU, 40 samples, 20 steps
@@ -20,7 +26,8 @@ rank), config 5 shards SAMPLES (strong scaling); no collective on the data path,
 
 Without torchrun, ``--gpus N`` (N > 1) starts the N ranks itself (re-exec under ``python -m torch.distributed.run --nproc-per-node N``).
 
-Prints ONE JSON line on rank 0, with
+Prints ONE JSON line on rank 0, with (pruning_off, pocket_bound, create_ms, device_loop, the other limb form, the fallback kernel, tp_boundary_A,
+timesplit_stream and cpu_baseline only under --full; null otherwise)
   roofline      fused TP-conv kernel, HIP events around every launch of the timed region: ``achieved`` / ``frac`` = MFMA FLOPs the launches
                 EXECUTED / event time vs the dense f16 matrix peak (the kernel's own roofline fraction); ``fp32_equivalent_TFLOPs`` = the
                 algorithmic fp32 FLOPs of the evaluated edges over the same time; ``reference_equivalent_TFLOPs`` also counts the rec-rec
@@ -214,6 +221,19 @@ def pocket_poses(c, rng, samples, sigma=1.0):
                      for _ in range(samples)]).astype(np.float32)
 
 
+def dump_outputs(d, data_list, confidence, latent):
+    """--dump-outputs: what one sampling() call returned, as float32 .npy files in d - the final ligand poses of its samples, the AR latent
+    picks' positions (latent-conditioned configs) and the confidences (config 4)"""
+    os.makedirs(d, exist_ok=True)
+    arrs = {'poses': torch.stack([g['ligand'].pos for g in data_list])}
+    if latent:
+        arrs['latent_poses'] = torch.stack([g.latent_pos for g in data_list])
+    if confidence is not None:
+        arrs['confidences'] = confidence
+    for name, v in arrs.items():
+        np.save(os.path.join(d, name + '.npy'), v.detach().cpu().numpy().astype(np.float32))
+
+
 def _make_complex(job):
     """one synthetic complex of the workload (top level: the large sets are generated by a process pool)"""
     from disco_diffdock_amd import synthetic
@@ -276,8 +296,8 @@ def timesplit_stream():
     over 363 DISTINCT synthetic complexes with a 10-80-atom ligand spread (a timesplit_test-sized set, reference README.md:20, evaluate.py:221-293), every
     complex streamed ONCE through sampling() - as its own process behind this one's measurements (the GPU is idle by then), the three brackets of the headline."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), '--config', '4', '--complexes', '363', '--steps', '363', '--warmup', '2', '--no-cpu-baseline', '--no-alt',
-           '--no-device-loop', '--no-timesplit']
+    cmd = [sys.executable, os.path.abspath(__file__), '--config', '4', '--complexes', '363', '--steps', '363', '--warmup', '2', '--full', '--no-cpu-baseline',
+           '--no-alt', '--no-device-loop', '--no-timesplit']
     t0 = time.perf_counter()
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
@@ -319,6 +339,11 @@ def main():
     ap.add_argument('--steps', type=int, default=8)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--config', type=int, default=2, choices=[2, 3, 4, 5])
+    ap.add_argument('--full', action='store_true', help='everything beside the headline bracket: three timed passes (K <= 64, the median is reported), the other '
+                    'conv kernels, the pruning-off / pocket-bound brackets, create_ms, the resident loop, the CPU oracle, boundary A and the 363-complex '
+                    'stream (the --no-* options skip parts of it); without it a run is the headline bracket alone, one pass of --steps calls')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='after the timed calls, write what the last one returned (rank 0) as DIR/<name>.npy, '
+                    'float32: poses [samples, ligand atoms, 3]; configs 3 / 4 latent_poses, config 4 confidences')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-alt', action='store_true', help='skip the brackets of the other conv kernels: the three-limb / six-product form (value_six_limb_products) and the fp32-MFMA fallback')
     ap.add_argument('--no-device-loop', action='store_true', help='skip the resident-loop comparison figure')
@@ -333,12 +358,14 @@ def main():
                     'drawn from 10-80 atoms like a PDBBind split - e.g. --complexes 363 --steps 363 streams a timesplit_test-sized set once)')
     ap.add_argument('--fixed-receptor', action='store_true', help='--complexes > 8: keep every receptor at 300 residues (rounds 4 / 5 streamed this set; the default draws '
                     'timesplit-shaped receptor sizes, synthetic.timesplit_shape)')
-    ap.add_argument('--passes', type=int, default=0, help='timed passes over the K calls, the MEDIAN pass is reported (default: 3 for K <= 64, else 1)')
+    ap.add_argument('--passes', type=int, default=0, help='timed passes over the K calls, the MEDIAN pass is reported (default: 1; --full: 3 for K <= 64, else 1)')
     ap.add_argument('--no-tp-boundary', action='store_true', help='skip roofline.tp_boundary_A (FasterTensorProduct.forward at the reference op boundary, 800 000 edges)')
     ap.add_argument('--complex-offset', type=int, default=0, help='first content seed of --complexes (to run a slice of a large set)')
     ap.add_argument('--force-dist', action='store_true', help='N = 1 through the N > 1 code path: a world_size-1 process group on --backend, every '
                     'barrier / all_reduce / all_gather of the path executes (proves that RCCL loads and runs beside libddk.so on a one-GPU box)')
     a = ap.parse_args()
+    if not a.full:      # a plain run: the headline bracket and its result line, nothing that takes a run of its own
+        a.no_cpu_baseline = a.no_alt = a.no_device_loop = a.no_extras = a.no_tp_boundary = a.no_timesplit = True
     if 'WORLD_SIZE' not in os.environ and a.gpus > 1:
         self_launch(a)
     rank, world = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1))
@@ -413,9 +440,10 @@ def main():
             made = pool.map(_make_complex, jobs, chunksize=4)
     else:
         made = [_make_complex(j) for j in jobs]
-    cache_path = os.path.join(tempfile.gettempdir(), f'ddk_bench_cfg{cfg_id}_rank{rank}.ddkg')
-    graph_cache.save_complexes(cache_path, made)
-    complexes = dict(zip(mine, graph_cache.load_complexes(cache_path)))
+    with tempfile.TemporaryDirectory(prefix='ddk_bench_') as td:      # (a directory of this process's own: nothing of another run or user is overwritten or left behind)
+        cache_path = os.path.join(td, f'cfg{cfg_id}_rank{rank}.ddkg')
+        graph_cache.save_complexes(cache_path, made)
+        complexes = dict(zip(mine, graph_cache.load_complexes(cache_path)))      # (the memory map outlives the unlinked file)
 
     # ---- models through the reference's call surface ----------------------------------------------------------------------------
     tsig = partial(t_to_sigma, args=margs)
@@ -481,7 +509,7 @@ def main():
         cdl = [copy.copy(gc) for _ in range(b_local)] if with_conf else None
         return dl, cdl
 
-    n_passes_default = a.passes if a.passes > 0 else (3 if a.steps <= 64 else 1)
+    n_passes_default = a.passes if a.passes > 0 else (3 if a.full and a.steps <= 64 else 1)
 
     def bracket(poses, warmup, prune=True, noise_scale=None, n_passes=None, mdl=None):
         """the reference's bracket (evaluate.py:259,293) over K = a.steps sampling() calls, a NEW complex every call; returns the wall
@@ -524,7 +552,7 @@ def main():
         if ar_ctx is not None:
             ar_ctx.profile_enable(True)
         pool0, mem_peak = ctx.pool_stats(), 0
-        pass_elapsed, pass_calls = [], []
+        pass_elapsed, pass_calls, pass_last = [], [], []
         for pass_id in range(n_passes):
             calls = calls_of_pass[pass_id]
             # every pass: EXACTLY a.steps calls between a barrier + synchronize on both sides; the same complexes, start poses and generator seed
@@ -569,6 +597,7 @@ def main():
                 el_ = float(tmax.item())
             pass_elapsed.append(el_)
             pass_calls.append([round(call_ev[k].elapsed_time(call_ev[k + 1]), 2) for k in range(a.steps)])
+            pass_last.append((out, conf))          # what the pass's last sampling() call returned (--dump-outputs)
         med = sorted(range(n_passes), key=lambda i_: pass_elapsed[i_])[n_passes // 2]      # the MEDIAN pass is the one reported
         elapsed, per_call_ms = pass_elapsed[med], pass_calls[med]
         prof, fw = ctx.profile_read(), ctx.profile_read_forwards()      # (HIP events around the conv launches of ALL passes: means are unaffected)
@@ -596,7 +625,7 @@ def main():
                   'chunk_pool_bytes_parked': pool1['bytes_parked'], 'complex_bytes_owned_peak': pool1['bytes_owned_peak'],
                   'device_memory_in_use_peak_bytes': int(mem_peak)}
         return dict(elapsed=elapsed, prof=prof, fw=fw, per_call_ms=per_call_ms, final=final, confs=confs, order=order[warmup:warmup + a.steps], stream=stream,
-                    passes=n_passes, pass_elapsed_s=[round(v, 5) for v in pass_elapsed], ar_conv_ms=ar_conv_ms)
+                    passes=n_passes, pass_elapsed_s=[round(v, 5) for v in pass_elapsed], ar_conv_ms=ar_conv_ms, last=pass_last[med])
 
     layer_flop = [2 * 72 * (72 + W_LAYER[l]) + TP_FLOP[l] for l in range(5)]
 
@@ -621,6 +650,8 @@ def main():
     else:
         head = bracket(poses_all, a.warmup)
     elapsed, prof, final, confs = head['elapsed'], head['prof'], head['final'], head['confs']
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, *head['last'], latent=disco)
 
     # ---- the one exchange of the path: final poses (and confidences) of every complex to every rank (RCCL over xGMI) ----------
     if big:

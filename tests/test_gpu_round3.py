@@ -45,8 +45,8 @@ def _record_drift(key, value, **extra):
         json.dump(d, f, indent=1, sort_keys=True)
 
 
-def _bench(*args):
-    env = dict(os.environ)
+def _bench(*args, **env_extra):
+    env = dict(os.environ, **env_extra)
     env.pop('WORLD_SIZE', None)
     env.pop('RANK', None)
     env.pop('LOCAL_RANK', None)
@@ -72,7 +72,7 @@ def test_bench_gpus2_launches_two_ranks_by_itself(dev):
 def test_bench_line_reports_executed_work_and_both_floors(dev):
     """roofline.frac is the EXECUTED fraction (<= 1, = flop_per_launch / avg_launch_ms / peak), the pruning-off floor and the
     pocket-bound workload are in the line, and the per-step executed-edge fractions cover the 20 steps."""
-    out = _bench('--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-alt', '--no-device-loop', '--no-timesplit')
+    out = _bench('--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-alt', '--no-device-loop', '--no-timesplit')
     rf = out['roofline']
     # (a suite run with DDK_CONV_KERNEL=1 puts the fp32-MFMA kernel under the bench too: its roofline is priced against the fp32 matrix peak)
     peak = 157.3 if os.environ.get('DDK_CONV_KERNEL') == '1' else 2500.0
@@ -104,7 +104,7 @@ def test_bench_line_carries_the_other_limb_form_of_the_conv_kernel(dev):
     """Round 6: the default conv kernel multiplies two f16 limbs per operand (three products); the line also carries the SAME sampling() bracket with the three-limb /
     six-product form (ddk_config.conv_kernel = 3, the default of rounds 3 - 5) in every context - value_six_limb_products at the top level and under `config` (keys
     the driver's record keeps), the launch time and executed-MFMA fraction under roofline.other_limb_form - and the executed-work accounting follows the form that ran."""
-    out = _bench('--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-device-loop', '--no-timesplit', '--no-tp-boundary')
+    out = _bench('--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-device-loop', '--no-timesplit', '--no-tp-boundary')
     rf, kern = out['roofline'], int(os.environ.get('DDK_CONV_KERNEL', '0'))
     assert out['config']['conv_kernel'] == kern
     if kern == 1:
@@ -121,6 +121,29 @@ def test_bench_line_carries_the_other_limb_form_of_the_conv_kernel(dev):
         assert out['value_six_limb_products'] == out['value']
     assert o['frac_of_f16_matrix_peak'] == pytest.approx(o['mfma_TFLOPs_executed'] / 2500.0)
     assert out['fallback_fp32_kernel']['value'] > 0
+
+
+def test_plain_bench_run_times_the_headline_alone_and_dumps_its_last_call(dev, tmp_path):
+    """A plain ``bench.py --steps K --warmup W`` is the headline bracket alone: ONE pass of exactly K timed calls, none of --full's brackets in the
+    line.  --dump-outputs writes what the last timed sampling() call returned as float32 .npy; the inputs are seeded, so two runs with the same
+    arguments in deterministic mode return the same bits."""
+    outs = []
+    for name in ('a', 'b'):
+        out = _bench('--steps', '2', '--warmup', '1', '--dump-outputs', str(tmp_path / name), DDK_DETERMINISTIC='1')
+        for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+            assert k in out, k
+        hl = out['extra']['headline']
+        assert out['steps'] == 2 and hl['passes'] == 1 and len(hl['pass_elapsed_s']) == 1 and len(out['extra']['per_call_ms']) == 2
+        assert out['ms_per_step'] == pytest.approx(1e3 * hl['pass_elapsed_s'][0] / 2, rel=1e-3)
+        assert out['value'] == pytest.approx(2e3 / (2 * out['ms_per_step']), rel=1e-6)
+        assert out['value_pruning_off'] is None and out['value_pocket_bound'] is None and out['value_six_limb_products'] in (None, out['value'])
+        assert out['cpu_baseline'] is None and 'fallback_fp32_kernel' not in out and out['roofline']['tp_boundary_A'] is None
+        assert out['extra']['device_loop'] is None and out['extra']['create_ms'] is None and 'timesplit_stream' not in out['extra']
+        assert sorted(os.listdir(tmp_path / name)) == ['poses.npy']
+        p = np.load(tmp_path / name / 'poses.npy')
+        assert p.dtype == np.float32 and p.ndim == 3 and p.shape[0] == 40 and p.shape[2] == 3 and np.isfinite(p).all()
+        outs.append(p)
+    assert np.array_equal(outs[0], outs[1])
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------------
