@@ -5,7 +5,7 @@
 #include <cmath>
 #include <string.h>
 
-#include "ddk_internal.h"
+#include "model.h"
 #include "k_conv_common.h"
 
 using namespace ddk;
@@ -75,14 +75,11 @@ int ensure(ddk_ctx* ctx, void** p, size_t* cap, size_t bytes) {
   return DDK_OK;
 }
 
-static const HostTensor* find_w(ddk_ctx* ctx, const std::string& name, std::initializer_list<int64_t> shape) {
+const HostTensor* find_w(ddk_ctx* ctx, const std::string& name, std::initializer_list<int64_t> shape) {
   auto it = ctx->weights.find(name);
-  if (it == ctx->weights.end()) {
-    ctx->err = "missing state_dict key: " + name;
-    return nullptr;
-  }
-  std::vector<int64_t> want(shape);
-  if (it->second.shape != want) {
+  if (it == ctx->weights.end()) { ctx->err = "missing state_dict key: " + name; return nullptr; }
+  const std::vector<int64_t> want(shape);
+  if (it->second.shape != want) {      // the message names both shapes
     std::string s = "shape mismatch for " + name + ": got [";
     for (auto d : it->second.shape) s += std::to_string(d) + ",";
     s += "] want [";
@@ -851,9 +848,7 @@ int ddk_conv_forward(ddk_ctx* ctx, int32_t layer, const float* x, int64_t N, con
   if ((rc = ensure(ctx, (void**)&ws.xpad, &ws.xpad_cap, (size_t)N * XW * 4))) return rc;
   if ((rc = ensure(ctx, (void**)&ws.sum, &ws.sum_cap, (size_t)N * XW * 4))) return rc;
   if ((rc = ensure(ctx, (void**)&ws.deg, &ws.deg_cap, (size_t)N * 4))) return rc;
-  hipError_t e;
   const int64_t E = go[4];
-#define CK(x, what) do { e = (x); if (e != hipSuccess) return hip_fail(ctx, e, what); } while (0)
   CK(launch_pad_rows(x, N, L.din, ws.xpad, s), "pad_rows");
   CK(hipMemsetAsync(ws.sum, 0, (size_t)N * XW * 4, s), "memset sum");
   CK(hipMemsetAsync(ws.deg, 0, (size_t)N * 4, s), "memset deg");
@@ -879,7 +874,6 @@ int ddk_conv_forward(ddk_ctx* ctx, int32_t layer, const float* x, int64_t N, con
     CK(launch_node_finalize(ws.sum, ws.deg, ws.xpad, L.bn_mean, L.bn_scale, L.bn_bias, N, L.dout, L.dout, out, s), "node_finalize");
   else
     CK(launch_node_finalize(ws.sum, ws.deg, ws.xpad, nullptr, nullptr, nullptr, N, 0, L.dout, out, s), "node_finalize");
-#undef CK
   return DDK_OK;
 }
 

@@ -14,6 +14,8 @@ constexpr int MAX_LIG = 256;   // ligand atoms per sample the graph kernels supp
 constexpr int MAX_REC = 8192;  // residues per sample
 constexpr int LIG_CAP = 33;    // radius_graph(max_num_neighbors=32) -> radius(..., 33) including self; an atom with 33 lower-index atoms in range keeps all 33 (self is not among them)
 constexpr int BOND_CAP = 32;   // radius(..., max_num_neighbors=32) of the bond-centre graph
+constexpr int LIG_DIMS[16] = {119, 4, 12, 12, 8, 10, 6, 6, 2, 8, 2, 2, 2, 2, 2, 2};   // categorical ligand-atom features, process_mols.py:62-79
+constexpr int REC_DIM = 38;                                                          // residue types, process_mols.py:88-90
 
 // Layout of the per-complex int32 `info` table written by graph_fill_kernel (write_group_tables; device side; no launch depends on a host read-back).
 // Group 2 (rec-rec) of the merged edge list is stored in four segments ordered by the BACKWARD RECEPTIVE-FIELD LEVEL of the edge's
@@ -282,6 +284,8 @@ void conf_model_destroy(ddk_ctx* ctx);
 struct ConfComplex;
 
 hipError_t launch_graph(const GraphArgs& G, int64_t edge_cap, hipStream_t s);
+// model.hip: the fields every graph build of a complex shares (its static arrays, count / info tables, cut-offs); the caller adds the edge arrays, `deg`, the options
+GraphArgs graph_args(const ddk_ctx* ctx, const ddk_complex* cx, int B, const float* lig_pos, float cross_cutoff);
 int graph_cross_mirror_fits(int n_lig, int n_rec);      // k_graph.hip: does the current device's LDS hold the residue x ligand-atom bit matrix of GraphArgs::cross_mirror?
 hipError_t launch_edge_features(const EdgeFeatArgs& A, int64_t edge_cap, hipStream_t s);
 hipError_t launch_edge_features_node(const EdgeFeatArgs& A, int64_t edge_cap, const NodePreArgs& P, const NodeEmbedArgs& E, hipStream_t s);   // + node embedding and layer-0 node terms
@@ -360,7 +364,16 @@ struct ddk_complex {
   std::vector<float> h_rec_pos;
 };
 
+// inside a function that returns a DDK status and has `ctx` in scope: a failed HIP call ends it through hip_fail, a missing / misshaped tensor with ctx->err set
+#define GET(var, name, ...) const HostTensor* var = find_w(ctx, name, {__VA_ARGS__}); if (!var) return DDK_ERR_INVALID
+#define CK(x, what) do { hipError_t ck_e = (x); if (ck_e != hipSuccess) return hip_fail(ctx, ck_e, what); } while (0)
+
 namespace ddk {
+// state-dict tensor `name` with exactly this shape, or null with ctx->err set (ddk_capi.hip)
+const HostTensor* find_w(ddk_ctx* ctx, const std::string& name, std::initializer_list<int64_t> shape);
+std::vector<float> cols(const HostTensor* t, int c0, int c1);      // columns [c0, c1) of a row-major [rows, cols] matrix (model.hip)
+std::vector<float> transpose_rm(const std::vector<float>& w, int rows, int cols_);      // [rows][cols] -> [cols][rows] (model.hip)
+
 // static per-complex precompute on a few host threads (independent rows; results do not depend on the thread count)
 template <typename F>
 inline void host_parallel_for(int n, F&& body) {
@@ -404,7 +417,7 @@ inline void* cx_alloc(ddk_complex* cx, size_t bytes) {
   cx->chunk_off += need;
   if (cx_canary_on()) {
     char* tail = (char*)r + (need - 4096);
-    hipMemset(tail, 0xA5, 4096);
+    if (hipMemset(tail, 0xA5, 4096) != hipSuccess) { cx->oom = true; return nullptr; }
     cx->canaries.push_back({tail, bytes});
   }
   {      // debugging aid (DDK_TRACE_ALLOC): every array of a complex with its address range, to match a GPU fault address against
@@ -413,5 +426,12 @@ inline void* cx_alloc(ddk_complex* cx, size_t bytes) {
                                         (void*)cx->chunk, cx->chunk_off - need, cx->chunk_cap);
   }
   return r;
+}
+// array of n elements in the complex' arena; src != null: its content follows through the staged upload
+template <typename T>
+inline T* cx_upload(ddk_complex* cx, const T* src, size_t n) {
+  T* p = (T*)cx_alloc(cx, n * sizeof(T));
+  if (!p || (n && src && !cx_put(cx, p, src, n * sizeof(T)))) return nullptr;
+  return p;
 }
 }  // namespace ddk

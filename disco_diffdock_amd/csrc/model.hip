@@ -10,18 +10,7 @@
 
 namespace ddk {
 
-static const int LIG_DIMS[16] = {119, 4, 12, 12, 8, 10, 6, 6, 2, 8, 2, 2, 2, 2, 2, 2};   // process_mols.py:62-79
-static const int REC_DIM = 38;                                                             // process_mols.py:88-90
-
-static const HostTensor* getw(ddk_ctx* ctx, const std::string& name, std::initializer_list<int64_t> shape) {
-  auto it = ctx->weights.find(name);
-  if (it == ctx->weights.end()) { ctx->err = "missing state_dict key: " + name; return nullptr; }
-  if (it->second.shape != std::vector<int64_t>(shape)) { ctx->err = "shape mismatch for " + name; return nullptr; }
-  return &it->second;
-}
-
-// columns [c0, c1) of a row-major [rows, cols] matrix
-static std::vector<float> cols(const HostTensor* t, int c0, int c1) {
+std::vector<float> cols(const HostTensor* t, int c0, int c1) {
   const int rows = (int)t->shape[0], nc = (int)t->shape[1];
   std::vector<float> o((size_t)rows * (c1 - c0));
   for (int r = 0; r < rows; ++r)
@@ -44,7 +33,7 @@ static bool smearing(ddk_ctx* ctx, const char* name, float stop, EdgeMlpDev& m, 
   return m.offset != nullptr;
 }
 
-static std::vector<float> transpose_rm(const std::vector<float>& w, int rows, int cols_) {      // [rows][cols] -> [cols][rows]
+std::vector<float> transpose_rm(const std::vector<float>& w, int rows, int cols_) {      // [rows][cols] -> [cols][rows]
   std::vector<float> t((size_t)rows * cols_);
   for (int r = 0; r < rows; ++r)
     for (int c = 0; c < cols_; ++c) t[(size_t)c * rows + r] = w[(size_t)r * cols_ + c];
@@ -65,7 +54,6 @@ int model_finalize(ddk_ctx* ctx) {
   ModelHost& H = M->host;
   ModelDev& D = M->dev;
   const int lm = c.lm_embedding_dim;
-#define GET(var, name, ...) const HostTensor* var = getw(ctx, name, {__VA_ARGS__}); if (!var) return DDK_ERR_INVALID
   // ---- node encoders -----------------------------------------------------------------------
   int off = 0;
   for (int i = 0; i < 16; ++i) {
@@ -105,10 +93,10 @@ int model_finalize(ddk_ctx* ctx) {
   auto edge_mlp = [&](const char* name, int n_bond, bool sigma_first, EdgeMlpDev& m, std::vector<float>* w1s,
                       std::vector<float>* b1, std::vector<float>* w1d_host, int lat_cols = 0, const char* unc_name = nullptr) -> bool {
     const int in = n_bond + (w1s ? SIG : 0) + DE + lat_cols;
-    const HostTensor* w0 = getw(ctx, std::string(name) + ".0.weight", {NS, in});
-    const HostTensor* b0 = getw(ctx, std::string(name) + ".0.bias", {NS});
-    const HostTensor* w3 = getw(ctx, std::string(name) + ".3.weight", {NS, NS});
-    const HostTensor* b3 = getw(ctx, std::string(name) + ".3.bias", {NS});
+    const HostTensor* w0 = find_w(ctx, std::string(name) + ".0.weight", {NS, in});
+    const HostTensor* b0 = find_w(ctx, std::string(name) + ".0.bias", {NS});
+    const HostTensor* w3 = find_w(ctx, std::string(name) + ".3.weight", {NS, NS});
+    const HostTensor* b3 = find_w(ctx, std::string(name) + ".3.bias", {NS});
     if (!w0 || !b0 || !w3 || !b3) return false;
     int c_sig, c_d;
     if (!w1s) { c_sig = -1; c_d = n_bond; }
@@ -125,7 +113,7 @@ int model_finalize(ddk_ctx* ctx) {
     m.w1l = lat_cols ? dev_upload(ctx, cols(w0, in - lat_cols, in)) : nullptr;   // latent columns are the last ones
     m.unc = nullptr;
     if (unc_name && c.latent_droprate > 0 && LD > 0) {
-      const HostTensor* u = getw(ctx, unc_name, {1, NS});
+      const HostTensor* u = find_w(ctx, unc_name, {1, NS});
       if (!u) return false;
       m.unc = dev_upload(ctx, u->data);
     }
@@ -204,7 +192,6 @@ int model_finalize(ddk_ctx* ctx) {
     D.tf_w0 = dev_upload(ctx, f0->data); D.tf_w3 = dev_upload(ctx, f3->data);
   }
   }      // (!confidence_mode)
-#undef GET
   for (int l = 0; l < c.num_conv_layers; ++l)
     if (!ctx->conv[l].has_weights) return fail(ctx, DDK_ERR_INVALID, "score model checkpoint lacks conv_layers." + std::to_string(l));
   // ---- AR latent model predictors (models/pretrained_score_encoder.py:24-45), present when this context holds the AR checkpoint's
@@ -217,21 +204,21 @@ int model_finalize(ddk_ctx* ctx) {
       return fail(ctx, DDK_ERR_INVALID, "AR predictor: hidden width must be <= 128 and the input 2*ns with ns <= 24 (num_conv_layers >= 3 layout)");
     auto pack = [&](const char* pre, ArMlpDev& D) -> bool {
       const std::string p(pre);
-      const HostTensor* w0 = getw(ctx, p + ".0.weight", {Hd, nin});
-      const HostTensor* b0 = getw(ctx, p + ".0.bias", {Hd});
-      const HostTensor* w4 = getw(ctx, p + ".4.weight", {Hd, Hd});
-      const HostTensor* b4 = getw(ctx, p + ".4.bias", {Hd});
-      const HostTensor* w8 = getw(ctx, p + ".8.weight", {1, Hd});
-      const HostTensor* b8 = getw(ctx, p + ".8.bias", {1});
+      const HostTensor* w0 = find_w(ctx, p + ".0.weight", {Hd, nin});
+      const HostTensor* b0 = find_w(ctx, p + ".0.bias", {Hd});
+      const HostTensor* w4 = find_w(ctx, p + ".4.weight", {Hd, Hd});
+      const HostTensor* b4 = find_w(ctx, p + ".4.bias", {Hd});
+      const HostTensor* w8 = find_w(ctx, p + ".8.weight", {1, Hd});
+      const HostTensor* b8 = find_w(ctx, p + ".8.bias", {1});
       if (!w0 || !b0 || !w4 || !b4 || !w8 || !b8)
         return false;     // (latent_dim of the predictors is 1: model_utils.py:133-139 builds PretrainedScoreEncoder(latent_dim=1))
       std::vector<float> W0 = w0->data, B0 = b0->data, W4 = w4->data, B4 = b4->data;
       auto fold = [&](const char* idx, std::vector<float>& W, std::vector<float>& Bv, int in) -> bool {
         if (ctx->weights.find(p + "." + idx + ".running_var") == ctx->weights.end()) return true;    // latent_no_batchnorm
-        const HostTensor* g = getw(ctx, p + "." + idx + ".weight", {Hd});
-        const HostTensor* be = getw(ctx, p + "." + idx + ".bias", {Hd});
-        const HostTensor* rm = getw(ctx, p + "." + idx + ".running_mean", {Hd});
-        const HostTensor* rv = getw(ctx, p + "." + idx + ".running_var", {Hd});
+        const HostTensor* g = find_w(ctx, p + "." + idx + ".weight", {Hd});
+        const HostTensor* be = find_w(ctx, p + "." + idx + ".bias", {Hd});
+        const HostTensor* rm = find_w(ctx, p + "." + idx + ".running_mean", {Hd});
+        const HostTensor* rv = find_w(ctx, p + "." + idx + ".running_var", {Hd});
         if (!g || !be || !rm || !rv) return false;
         for (int j = 0; j < Hd; ++j) {
           const float sc = g->data[j] / sqrtf(rv->data[j] + 1e-5f);      // nn.BatchNorm1d default eps
@@ -451,27 +438,21 @@ hipError_t cx_wait_ready(ddk_complex* cx, hipStream_t s) {
   return hipStreamWaitEvent(s, cx->ready, 0);
 }
 
-template <typename T>
-static T* cx_upload(ddk_complex* cx, const T* src, size_t n) {
-  T* p = (T*)cx_alloc(cx, n * sizeof(T));
-  if (!p) return nullptr;
-  if (n && src && !cx_put(cx, p, src, n * sizeof(T))) return nullptr;
-  return p;
+GraphArgs graph_args(const ddk_ctx* ctx, const ddk_complex* cx, int B, const float* lig_pos, float cross_cutoff) {
+  GraphArgs G;
+  G.lig_pos = lig_pos; G.rec_pos = cx->rec_pos; G.bond_src = cx->bond_src; G.bond_dst = cx->bond_dst;
+  G.rr_src = cx->rr_src; G.rr_dst = cx->rr_dst; G.rr_outdeg = cx->rr_outdeg; G.rr_start = cx->rr_start;
+  G.B = B; G.n_lig = cx->n_lig; G.n_rec = cx->n_rec; G.M = cx->M; G.E_rr = cx->E_rr;
+  G.lig_r2 = ctx->cfg.lig_max_radius * ctx->cfg.lig_max_radius; G.cross_cutoff = cross_cutoff; G.counts = cx->counts; G.offs = cx->offs; G.info = cx->info; G.levels = cx->levels;
+  return G;
 }
 
 // a6-a8 + the merge of score_model.py:218-225: counts, offsets and the sorted edge list of B poses into the complex' workspace
 static hipError_t build_graph(ddk_ctx* ctx, ddk_complex* cx, int B, const float* lig_pos, float cross_cutoff, bool prune, bool shared_rr,
                               hipStream_t s, int64_t patch_off = -1, int cross_mirror = 0) {
-  const ddk_config& c = ctx->cfg;
-  GraphArgs G;
-  G.cross_mirror = cross_mirror;
-  G.lig_pos = lig_pos; G.rec_pos = cx->rec_pos; G.bond_src = cx->bond_src; G.bond_dst = cx->bond_dst;
-  G.rr_src = cx->rr_src; G.rr_dst = cx->rr_dst; G.rr_outdeg = cx->rr_outdeg; G.rr_start = cx->rr_start;
-  G.prune = prune ? 1 : 0; G.shared_rr = shared_rr ? 1 : 0; G.patch_off = patch_off;
-  G.B = B; G.n_lig = cx->n_lig; G.n_rec = cx->n_rec; G.M = cx->M; G.E_rr = cx->E_rr;
-  G.lig_r2 = c.lig_max_radius * c.lig_max_radius; G.cross_cutoff = cross_cutoff;
-  G.counts = cx->counts; G.offs = cx->offs; G.info = cx->info; G.levels = cx->levels; G.e_src = cx->e_src; G.e_dst = cx->e_dst; G.e_aux = cx->e_aux;
-  G.deg = cx->deg;
+  GraphArgs G = graph_args(ctx, cx, B, lig_pos, cross_cutoff);
+  G.cross_mirror = cross_mirror; G.prune = prune ? 1 : 0; G.shared_rr = shared_rr ? 1 : 0; G.patch_off = patch_off;
+  G.e_src = cx->e_src; G.e_dst = cx->e_dst; G.e_aux = cx->e_aux; G.deg = cx->deg;
   return launch_graph(G, cx->edge_cap, s);
 }
 
@@ -482,8 +463,6 @@ static int score_forward_impl(ddk_ctx* ctx, ddk_complex* cx, int B, const float*
   Model* M = (Model*)ctx->model;
   const int n_lig = cx->n_lig, n_rec = cx->n_rec;
   const int64_t N = (int64_t)B * (n_lig + n_rec);
-  hipError_t e;
-#define CK(x, what) do { e = (x); if (e != hipSuccess) return hip_fail(ctx, e, what); } while (0)
   // layer 0: the receptor's node features and rec-rec edge features are the same for every sample of the batch
   // (no latents) -> evaluate the rec-rec messages once, exact in real arithmetic
   // Latent-conditioned (DisCo) model: the latents are one-hot at a few nodes per sample, so the shared pass (on sample 0's rows) is right
@@ -694,7 +673,6 @@ static int score_forward_impl(ddk_ctx* ctx, ddk_complex* cx, int B, const float*
   }
   if (defer_post) *defer_post = Hd;
   else CK(launch_heads_post(Hd, torsion, s), "heads_post");
-#undef CK
   return DDK_OK;
 }
 

@@ -19,6 +19,11 @@ DEFAULTS = dict(ns=24, nv=6, num_conv_layers=5, sigma_embed_dim=32, distance_emb
                 tor_sigma_min=0.03, tor_sigma_max=3.14, device=0, all_atoms=0, num_confidence_outputs=1, confidence_no_batchnorm=0,
                 conv_kernel=0, deterministic=0, confidence_mode=0)
 
+# the all-atom confidence model's edge groups in the order of its group tables (enum ConfGroup, csrc/conf.hip), and the words of
+# ddk_confidence_status (include/ddk.h): CONF_STATUS_INTS int32, word CONF_OVERFLOW_WORD != 0 after a ligand-atom edge capacity overflow
+CONF_GROUPS = ('ll', 'lr', 'la', 'aa', 'al', 'ar', 'rr', 'rl', 'ra')
+CONF_STATUS_INTS, CONF_OVERFLOW_WORD = 20, 19
+
 
 def config_from_args(args, device=0):
     """model_parameters.yml Namespace -> ddk_config fields, the mapping of get_model
@@ -351,25 +356,26 @@ class Complex:
         return out
 
     def confidence_status_async(self):
-        """-> pinned int32[20] that holds the group table / overflow flag of the last confidence forward once the current stream has
+        """-> pinned int32[CONF_STATUS_INTS] that holds the group table / overflow flag of the last confidence forward once the current stream has
         passed this point (ddk_confidence_status); no synchronisation here"""
-        out = torch.empty(20, dtype=torch.int32, pin_memory=True)
+        out = torch.empty(CONF_STATUS_INTS, dtype=torch.int32, pin_memory=True)
         self.ctx._check(self.ctx.L.ddk_confidence_status(self.ctx.h, self.h, C.c_void_p(out.data_ptr()), _stream()), 'ddk_confidence_status')
         return out
 
     def confidence_counts(self):
-        out = (C.c_int32 * 10)()
+        n = len(CONF_GROUPS)
+        out = (C.c_int32 * (n + 1))()      # the groups' edge counts, then the overflow flag
         self.ctx._check(self.ctx.L.ddk_debug_conf_counts(self.ctx.h, self.h, out), 'ddk_debug_conf_counts')
         v = list(out)
-        if v[9]:
+        if v[n]:
             raise RuntimeError('ddk: ligand-atom edge capacity overflow')
-        return dict(zip(('ll', 'lr', 'la', 'aa', 'al', 'ar', 'rr', 'rl', 'ra'), v[:9]))
+        return dict(zip(CONF_GROUPS, v[:n]))
 
     def confidence_table(self, which):
         """test hook: edges per group of the table layer `which` ran on (0 full, 1 layer 0, 2 level A, 3 level B, 4 layer 1; include/ddk_debug.h)."""
-        out = (C.c_int32 * 9)()
+        out = (C.c_int32 * len(CONF_GROUPS))()
         self.ctx._check(self.ctx.L.ddk_debug_conf_table(self.ctx.h, self.h, which, out), 'ddk_debug_conf_table')
-        return dict(zip(('ll', 'lr', 'la', 'aa', 'al', 'ar', 'rr', 'rl', 'ra'), list(out)))
+        return dict(zip(CONF_GROUPS, list(out)))
 
     def confidence_nodes(self):
         n = self.max_batch * self.n_lig + (self.max_batch + 1) * (self.n_atom + self.n_rec)      # (+ the virtual ligand-free sample)
@@ -379,11 +385,11 @@ class Complex:
 
     def confidence_edges(self):
         """test hook: {group: (src, dst, emb, sh)} of the last confidence forward (node ids in the device numbering)."""
-        gt = (C.c_int32 * 18)()
+        gt = (C.c_int32 * (2 * len(CONF_GROUPS)))()      # first edge of every group, then the end edges
         self.ctx._check(self.ctx.L.ddk_debug_conf_edges(self.ctx.h, self.h, 0, 0, None, None, None, None, gt), 'ddk_debug_conf_edges')
         out = {}
-        for k, name in enumerate(('ll', 'lr', 'la', 'aa', 'al', 'ar', 'rr', 'rl', 'ra')):
-            n = gt[9 + k] - gt[k]
+        for k, name in enumerate(CONF_GROUPS):
+            n = gt[len(CONF_GROUPS) + k] - gt[k]
             src, dst = np.zeros(n, np.int32), np.zeros(n, np.int32)
             emb, sh = np.zeros((n, 24), np.float32), np.zeros((n, 4), np.float32)
             p = lambda a: a.ctypes.data_as(C.c_void_p)

@@ -11,7 +11,7 @@ import torch
 
 from .data import DataLoader
 from .diffusion_utils import set_time
-from .runtime import h2d_async
+from .runtime import CONF_OVERFLOW_WORD, h2d_async
 from .score_model import complex_for_batch
 
 
@@ -115,7 +115,7 @@ class _Bookkeeping:
 
     def _check_conf(self):
         st, self.conf_status = self.conf_status, None
-        if st is not None and int(st[19]) != 0:
+        if st is not None and int(st[CONF_OVERFLOW_WORD]) != 0:
             import warnings
             warnings.warn(f'ddk: ligand-atom edge capacity overflow in a confidence batch of complex {self.name!r}: its confidences were '
                           'returned as -1000 (NaN on the device)', RuntimeWarning)
