@@ -33,6 +33,11 @@ class ddk_atoms_desc(C.Structure):
                 ('atom_edge_index', C.c_void_p), ('atom_rec_index', C.c_void_p)]
 
 
+class ddk_trajectory(C.Structure):
+    # device arrays of ddk_sample_trajectory's record, member order of include/ddk.h (tests/test_trajectory_host.py compares the two)
+    _fields_ = [('pos', C.c_void_p), ('scores', C.c_void_p), ('perturb', C.c_void_p), ('edge_counts', C.c_void_p)]
+
+
 _lib = None
 
 # every symbol include/ddk.h declares (tests check that the library exports all of them)
@@ -41,7 +46,8 @@ SYMBOLS = ['ddk_create', 'ddk_destroy', 'ddk_last_error', 'ddk_version', 'ddk_lo
            'ddk_score_forward', 'ddk_se3_update', 'ddk_sample', 'ddk_last_graph_stats', 'ddk_last_node_features',
            'ddk_profile_enable', 'ddk_profile_read', 'ddk_profile_read_forwards', 'ddk_set_latents', 'ddk_set_guidance',
            'ddk_set_keep_receptor_features', 'ddk_randomize_position', 'ddk_complex_set_atoms',
-           'ddk_confidence_forward', 'ddk_score_confidence', 'ddk_pose_metrics', 'ddk_build_graph', 'ddk_set_receptive_field_pruning', 'ddk_ar_logits', 'ddk_ar_decode', 'ddk_confidence_status']
+           'ddk_confidence_forward', 'ddk_score_confidence', 'ddk_pose_metrics', 'ddk_build_graph', 'ddk_set_receptive_field_pruning', 'ddk_ar_logits', 'ddk_ar_decode', 'ddk_confidence_status',
+           'ddk_sample_trajectory']
 
 # test hooks (include/ddk_debug.h): not part of the drop-in boundary
 DEBUG_SYMBOLS = ['ddk_debug_export', 'ddk_debug_read_edges', 'ddk_debug_conf_counts', 'ddk_debug_conf_table', 'ddk_debug_conf_nodes', 'ddk_debug_conf_edges', 'ddk_debug_kabsch', 'ddk_debug_axis_angle', 'ddk_debug_set_layer0_dedup', 'ddk_debug_read_patch', 'ddk_debug_split3', 'ddk_debug_conv_trace', 'ddk_debug_pool_stats', 'ddk_debug_set_conv_workgroups', 'ddk_debug_set_alloc_limit']
@@ -57,6 +63,10 @@ def lib():
     import torch  # noqa: F401  (first: libddk.so must bind to the HIP runtime PyTorch-ROCm ships; loaded before torch it binds to /opt/rocm's copy,
     #                and two HIP runtimes in one process leave the second without a device: "no ROCm-capable device is detected")
     L = C.CDLL(LIB_PATH)
+    missing = [s for s in SYMBOLS + DEBUG_SYMBOLS if not hasattr(L, s)]
+    if missing:      # a library built from older sources: fail here, not with an AttributeError at the first call of the new entry
+        raise RuntimeError(f'{LIB_PATH} does not export {", ".join(missing)}: it is stale, build the HIP extension again '
+                           '(python -m disco_diffdock_amd.build). disco_diffdock_amd has no CPU fallback.')
     vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
     L.ddk_create.argtypes = [C.POINTER(ddk_config), C.POINTER(vp)]
     L.ddk_destroy.argtypes = [vp]
@@ -80,6 +90,7 @@ def lib():
     L.ddk_score_confidence.argtypes = [vp, vp, i32, vp, C.c_float, C.c_float, C.c_float, vp, vp]
     L.ddk_pose_metrics.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp]
     L.ddk_sample.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.ddk_sample_trajectory.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, C.POINTER(ddk_trajectory), vp]
     L.ddk_last_graph_stats.argtypes = [vp, vp, vp, vp]
     L.ddk_build_graph.argtypes = [vp, vp, C.c_int32, vp, C.c_float, vp, vp, C.c_int64, vp, vp]
     L.ddk_last_node_features.argtypes = [vp, vp, i32, vp, vp, vp]

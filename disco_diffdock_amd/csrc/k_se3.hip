@@ -140,7 +140,9 @@ hipError_t launch_debug_axis_angle(const float* aa, int n, float* R_out, hipStre
 // POST: the workgroup of sample b first finishes the sample's scores from the heads' accumulators - heads_post_kernel's arithmetic (k_heads.hip:
 // tor_bond_conv's mean / BatchNorm / tor_final_layer, final_conv's mean / BatchNorm and the tr / rot magnitude MLPs; same summation orders) - so that
 // a reverse step needs no launch between the head convolutions and the update (ddk_sample without classifier-free guidance)
-template <bool POST>
+// REC: the workgroup also stores what it consumed and produced into the step's rows of a ddk_trajectory (Se3Args::rec_*; ddk_sample_trajectory).  A template
+// flag, not a run-time test: the <POST, false> instantiations are the kernels ddk_sample has always launched, instruction for instruction.
+template <bool POST, bool REC>
 __global__ __launch_bounds__(256) void se3_update_kernel(Se3Args A, HeadArgs H) {
   __shared__ float rig[MAX_LIG * 3], flx_a[MAX_LIG * 3], flx2[MAX_LIG * 3];
   __shared__ float upd[6], ctr[3], Rm[9], cA[3], cB[3], Rk[9], tk[3], rot_th[64];
@@ -207,7 +209,15 @@ __global__ __launch_bounds__(256) void se3_update_kernel(Se3Args A, HeadArgs H) 
   if (tid < 6) {
     const int k = tid / 3;
     const float sc = (tid < 3 ? A.tr : A.rot)[3 * b + tid % 3];
-    upd[tid] = A.sc[k] * sc + (nz ? A.nc[k] * nz[tid] : 0.0f);
+    const float u = A.sc[k] * sc + (nz ? A.nc[k] * nz[tid] : 0.0f);
+    upd[tid] = u;
+    if constexpr (REC) {
+      if (A.rec_scores != nullptr) A.rec_scores[(size_t)b * (6 + R) + tid] = sc;
+      if (A.rec_perturb != nullptr) A.rec_perturb[(size_t)b * (6 + R) + tid] = u;
+    }
+  }
+  if constexpr (REC) {      // batch totals of the four edge groups of the graph this step's forward ran on (ddk_last_graph_stats out[0..3])
+    if (A.rec_edges != nullptr && b == 0 && tid < 4) A.rec_edges[tid] = A.info[I_GO + 1 + tid] - A.info[I_GO + tid];
   }
   __syncthreads();
   if (tid < 3) {
@@ -228,7 +238,15 @@ __global__ __launch_bounds__(256) void se3_update_kernel(Se3Args A, HeadArgs H) 
   }
   __syncthreads();
   if (A.tor == nullptr || R == 0) {
-    for (int i = tid; i < n * 3; i += 256) A.pos_out[(size_t)b * n * 3 + i] = rig[i];
+    for (int i = tid; i < n * 3; i += 256) {
+      A.pos_out[(size_t)b * n * 3 + i] = rig[i];
+      if constexpr (REC) if (A.rec_pos != nullptr) A.rec_pos[(size_t)b * n * 3 + i] = rig[i];
+    }
+    if constexpr (REC)      // no_torsion: the torsion columns of the record's rows are zero
+      for (int r = tid; r < R; r += 256) {
+        if (A.rec_scores != nullptr) A.rec_scores[(size_t)b * (6 + R) + 6 + r] = 0.0f;
+        if (A.rec_perturb != nullptr) A.rec_perturb[(size_t)b * (6 + R) + 6 + r] = 0.0f;
+      }
     return;
   }
   // Sequential torsion rotations, one barrier per rotor: the rotor table (u, v, angle) and every atom's mask bits are fetched for up to 64 rotors at
@@ -241,7 +259,13 @@ __global__ __launch_bounds__(256) void se3_update_kernel(Se3Args A, HeadArgs H) 
     if (tid < chunk) {
       const int r = r0 + tid;
       rot_uv[tid] = make_int2(A.rot_u[r], A.rot_v[r]);
-      rot_th[tid] = A.sc[2] * A.tor[(size_t)b * R + r] + (nz ? A.nc[2] * nz[6 + r] : 0.0f);
+      const float ts = A.tor[(size_t)b * R + r];
+      const float th = A.sc[2] * ts + (nz ? A.nc[2] * nz[6 + r] : 0.0f);
+      rot_th[tid] = th;
+      if constexpr (REC) {
+        if (A.rec_scores != nullptr) A.rec_scores[(size_t)b * (6 + R) + 6 + r] = ts;
+        if (A.rec_perturb != nullptr) A.rec_perturb[(size_t)b * (6 + R) + 6 + r] = th;
+      }
     }
     unsigned long long mbits = 0ull;
     if (tid < n)
@@ -273,9 +297,15 @@ __global__ __launch_bounds__(256) void se3_update_kernel(Se3Args A, HeadArgs H) 
   if (tid < n) {
     const float x = flx[3 * tid], y = flx[3 * tid + 1], z = flx[3 * tid + 2];
     float* o = A.pos_out + ((size_t)b * n + tid) * 3;
-    o[0] = Rk[0] * x + Rk[1] * y + Rk[2] * z + tk[0];
-    o[1] = Rk[3] * x + Rk[4] * y + Rk[5] * z + tk[1];
-    o[2] = Rk[6] * x + Rk[7] * y + Rk[8] * z + tk[2];
+    const float ox = Rk[0] * x + Rk[1] * y + Rk[2] * z + tk[0];
+    const float oy = Rk[3] * x + Rk[4] * y + Rk[5] * z + tk[1];
+    const float oz = Rk[6] * x + Rk[7] * y + Rk[8] * z + tk[2];
+    o[0] = ox; o[1] = oy; o[2] = oz;
+    if constexpr (REC)
+      if (A.rec_pos != nullptr) {
+        float* q = A.rec_pos + ((size_t)b * n + tid) * 3;
+        q[0] = ox; q[1] = oy; q[2] = oz;
+      }
   }
 }
 
@@ -426,8 +456,13 @@ hipError_t launch_cfg_combine(float* score, const float* uncond, float weight, i
 }
 
 hipError_t launch_se3(const Se3Args& A, hipStream_t s, const HeadArgs* post) {
-  if (post) hipLaunchKernelGGL(se3_update_kernel<true>, dim3(A.B), dim3(256), 0, s, A, *post);
-  else { HeadArgs H = {}; hipLaunchKernelGGL(se3_update_kernel<false>, dim3(A.B), dim3(256), 0, s, A, H); }
+  const bool rec = A.rec_pos != nullptr || A.rec_scores != nullptr || A.rec_perturb != nullptr || A.rec_edges != nullptr;
+  HeadArgs H0 = {};
+  const HeadArgs& H = post ? *post : H0;
+  if (post && rec) hipLaunchKernelGGL((se3_update_kernel<true, true>), dim3(A.B), dim3(256), 0, s, A, H);
+  else if (post) hipLaunchKernelGGL((se3_update_kernel<true, false>), dim3(A.B), dim3(256), 0, s, A, H);
+  else if (rec) hipLaunchKernelGGL((se3_update_kernel<false, true>), dim3(A.B), dim3(256), 0, s, A, H);
+  else hipLaunchKernelGGL((se3_update_kernel<false, false>), dim3(A.B), dim3(256), 0, s, A, H);
   return hipGetLastError();
 }
 

@@ -259,6 +259,13 @@ struct Se3Args {
   const uint8_t* mask_rotate;   // [R, n_lig]
   int B, n_lig, R;
   float* pos_out;
+  // trajectory record of this step (ddk_sample_trajectory, include/ddk.h): written by the se3_update_kernel<POST, true> instantiations only, every
+  // destination may be null (= not recorded)
+  float* rec_pos = nullptr;       // [B, n_lig, 3] the poses this step leaves behind (row k + 1 of ddk_trajectory::pos)
+  float* rec_scores = nullptr;    // [B, 6 + R] tr xyz, rot xyz, tor... as read from tr / rot / tor above (torsion columns zero when tor is null)
+  float* rec_perturb = nullptr;   // [B, 6 + R] sc * score + nc * z, the arguments of the conformer update
+  int32_t* rec_edges = nullptr;   // [4] E_ll, E_lr, E_rr, E_rl of the graph in `info`
+  const int32_t* info = nullptr;  // the complex' InfoSlot table (read when rec_edges is set)
 };
 
 struct RandPosArgs {

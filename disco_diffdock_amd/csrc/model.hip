@@ -1014,15 +1014,24 @@ int ddk_pose_metrics(ddk_ctx* ctx, ddk_complex* cx, int32_t B, const float* pos,
   return DDK_OK;
 }
 
-int ddk_sample(ddk_ctx* ctx, ddk_complex* cx, int32_t B, int32_t steps, const float* t, const float* score_coeff,
-               const float* noise_coeff, const float* noise, float* pos, void* stream) {
+}  // extern "C"
+
+// ddk_sample / ddk_sample_trajectory (`what` names the entry point in messages).  rec: the caller's record arrays, every member may be null; the record is
+// written by the se3_update launches themselves (k_se3.hip), so a recorded call enqueues what a plain one does plus ONE copy of the start poses.
+static int sample_impl(ddk_ctx* ctx, ddk_complex* cx, int32_t B, int32_t steps, const float* t, const float* score_coeff, const float* noise_coeff,
+                       const float* noise, float* pos, const ddk_trajectory& rec, void* stream, const char* what) {
   int rc = check_model(ctx, cx, B);
   if (rc) return rc;
   if (((Model*)ctx->model)->confidence_mode) return fail(ctx, DDK_ERR_STATE, "a confidence_mode context has no score heads (ddk_score_confidence)");
   { hipError_t we = cx_wait_ready(cx, (hipStream_t)stream); if (we != hipSuccess) return hip_fail(ctx, we, "wait for the complex upload"); }
-  if (steps < 1 || !t || !score_coeff || !noise_coeff || !pos) return fail(ctx, DDK_ERR_INVALID, "ddk_sample: null argument");
+  if (steps < 1 || !t || !score_coeff || !noise_coeff || !pos) return fail(ctx, DDK_ERR_INVALID, std::string(what) + ": null argument");
   hipStream_t s = (hipStream_t)stream;
   const int R = cx->R;
+  const size_t pos_row = (size_t)B * cx->n_lig * 3, sc_row = (size_t)B * (6 + R);      // one step's row of rec.pos | of rec.scores and rec.perturb
+  if (rec.pos) {      // row 0: the poses before step 0
+    hipError_t e0 = hipMemcpyAsync(rec.pos, pos, pos_row * sizeof(float), hipMemcpyDeviceToDevice, s);
+    if (e0 != hipSuccess) return hip_fail(ctx, e0, "trajectory start-pose copy");
+  }
   float* tr = cx->scores;
   float* rot = tr + (size_t)B * 3;
   float* tor = rot + (size_t)B * 3;
@@ -1054,10 +1063,26 @@ int ddk_sample(ddk_ctx* ctx, ddk_complex* cx, int32_t B, int32_t steps, const fl
     for (int j = 0; j < 3; ++j) { A.sc[j] = score_coeff[3 * k + j]; A.nc[j] = noise_coeff[3 * k + j]; }
     A.rot_u = cx->rot_u; A.rot_v = cx->rot_v; A.mask_rotate = cx->mask_rotate; A.B = B; A.n_lig = cx->n_lig; A.R = R;
     A.pos_out = pos;       // in place: the workgroup of sample b stages pos[b] in LDS before it writes pos[b] (k_se3.hip)
+    if (rec.pos) A.rec_pos = rec.pos + (size_t)(k + 1) * pos_row;
+    if (rec.scores) A.rec_scores = rec.scores + (size_t)k * sc_row;
+    if (rec.perturb) A.rec_perturb = rec.perturb + (size_t)k * sc_row;
+    if (rec.edge_counts) { A.rec_edges = rec.edge_counts + 4 * (size_t)k; A.info = cx->info; }
     hipError_t e = launch_se3(A, s, guided ? nullptr : &post);
     if (e != hipSuccess) return hip_fail(ctx, e, "se3_update launch");
   }
   return DDK_OK;
+}
+
+extern "C" {
+
+int ddk_sample(ddk_ctx* ctx, ddk_complex* cx, int32_t B, int32_t steps, const float* t, const float* score_coeff,
+               const float* noise_coeff, const float* noise, float* pos, void* stream) {
+  return sample_impl(ctx, cx, B, steps, t, score_coeff, noise_coeff, noise, pos, ddk_trajectory{}, stream, "ddk_sample");
+}
+
+int ddk_sample_trajectory(ddk_ctx* ctx, ddk_complex* cx, int32_t B, int32_t steps, const float* t, const float* score_coeff,
+                          const float* noise_coeff, const float* noise, float* pos, const ddk_trajectory* rec, void* stream) {
+  return sample_impl(ctx, cx, B, steps, t, score_coeff, noise_coeff, noise, pos, rec ? *rec : ddk_trajectory{}, stream, "ddk_sample_trajectory");
 }
 
 int ddk_last_graph_stats(ddk_ctx* ctx, ddk_complex* cx, int64_t* out, void* stream) {

@@ -1,5 +1,6 @@
 """Thin Python owner of a ddk context (include/ddk.h): config mapping, checkpoint upload, operator calls.
 PyTorch is used only for device memory and streams; all compute happens in libddk.so."""
+import collections
 import ctypes as C
 import os
 from types import SimpleNamespace
@@ -23,6 +24,12 @@ DEFAULTS = dict(ns=24, nv=6, num_conv_layers=5, sigma_embed_dim=32, distance_emb
 # ddk_confidence_status (include/ddk.h): CONF_STATUS_INTS int32, word CONF_OVERFLOW_WORD != 0 after a ligand-atom edge capacity overflow
 CONF_GROUPS = ('ll', 'lr', 'la', 'aa', 'al', 'ar', 'rr', 'rl', 'ra')
 CONF_STATUS_INTS, CONF_OVERFLOW_WORD = 20, 19
+
+
+# what ``Complex.sample(..., record=...)`` returns: the device arrays of ddk_trajectory (include/ddk.h), None where a member was not recorded.
+#   pos [steps + 1, B, n_lig, 3] (row k: before step k; row steps: final), scores / perturb [steps, B, 6 + n_rot], edge_counts [steps, 4] int32
+TRAJECTORY_FIELDS = ('pos', 'scores', 'perturb', 'edge_counts')
+Trajectory = collections.namedtuple('Trajectory', TRAJECTORY_FIELDS)
 
 
 def config_from_args(args, device=0):
@@ -432,8 +439,11 @@ class Complex:
                    'ddk_randomize_position')
         return out
 
-    def sample(self, pos, t, score_coeff, noise_coeff, noise=None):
-        """in-place reverse diffusion of pos [B,n_lig,3]; t/score_coeff/noise_coeff: [steps,3] host arrays."""
+    def sample(self, pos, t, score_coeff, noise_coeff, noise=None, record=None):
+        """in-place reverse diffusion of pos [B,n_lig,3]; t/score_coeff/noise_coeff: [steps,3] host arrays.
+        record: None / False (default) returns pos; True records the whole trajectory on the device (ddk_sample_trajectory: same launches, no
+        synchronisation) and returns a :data:`Trajectory` of freshly allocated device tensors; a tuple of names out of TRAJECTORY_FIELDS, e.g.
+        ``('pos', 'edge_counts')``, records that subset (the other members of the result are None)."""
         ctx = self.ctx
         assert pos.is_contiguous() and pos.dtype == torch.float32
         B = pos.numel() // (self.n_lig * 3)
@@ -446,8 +456,20 @@ class Complex:
             noise = noise.contiguous().float()
             assert tuple(noise.shape) == (steps, B, 6 + self.R)
         p = lambda a: a.ctypes.data_as(C.c_void_p)
-        ctx._check(ctx.L.ddk_sample(ctx.h, self.h, B, steps, p(t), p(sc), p(nc), _ptr(noise), _ptr(pos), _stream()), 'ddk_sample')
-        return pos
+        if record is None or record is False:
+            ctx._check(ctx.L.ddk_sample(ctx.h, self.h, B, steps, p(t), p(sc), p(nc), _ptr(noise), _ptr(pos), _stream()), 'ddk_sample')
+            return pos
+        names = TRAJECTORY_FIELDS if record is True else tuple(record)
+        if isinstance(record, str) or not names or any(k not in TRAJECTORY_FIELDS for k in names):
+            raise ValueError(f'record: True or a tuple of names out of {TRAJECTORY_FIELDS}, got {record!r}')
+        n = max(steps, 0)      # (steps < 1 is refused by the library, with its message)
+        shapes = dict(pos=(n + 1, B, self.n_lig, 3), scores=(n, B, 6 + self.R), perturb=(n, B, 6 + self.R), edge_counts=(n, 4))
+        rec = Trajectory(*[torch.empty(shapes[k], dtype=torch.int32 if k == 'edge_counts' else torch.float32, device=pos.device) if k in names else None
+                           for k in TRAJECTORY_FIELDS])
+        c_rec = _lib.ddk_trajectory(**{k: (v.data_ptr() if v is not None else None) for k, v in rec._asdict().items()})
+        ctx._check(ctx.L.ddk_sample_trajectory(ctx.h, self.h, B, steps, p(t), p(sc), p(nc), _ptr(noise), _ptr(pos), C.byref(c_rec), _stream()),
+                   'ddk_sample_trajectory')
+        return rec
 
     def build_graph(self, pos, t_tr):
         """score_model.py:310-408 + :218-225 alone: ``(edge_index [2, E] int32, group_offsets [5])`` of the merged graph of the B poses

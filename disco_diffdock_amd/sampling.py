@@ -2,8 +2,10 @@
 (sampling.py:49-54,249) and ``randomize_position`` (:12-46).  The 20-step loop itself - score model forward,
 SDE perturbation, SE(3)/torsion update, Kabsch re-alignment - runs inside libddk.so (``ddk_sample``) without any
 host synchronisation; this file only prepares the per-step host scalars exactly as the reference computes them.
-Options outside the accelerated path (visualisation, the oracle latent encoder)
-raise instead of silently doing something else."""
+``visualization_list`` works as in the reference (:224-228: the poses after every batch), and the extra keyword ``trajectory=[]``
+collects what the loop did step by step - poses, scores, perturbations, edge counts - recorded on the device by the launches the
+sampler makes anyway (``ddk_sample_trajectory``).  The one option outside the accelerated path (the oracle latent encoder) raises
+instead of silently doing something else."""
 import collections
 
 import numpy as np
@@ -259,11 +261,19 @@ def sampling(data_list, model, inference_steps, tr_schedule, rot_schedule, tor_s
              confidence_model_args=None, batch_size=32, no_final_step_noise=False, use_latent=True,
              gumbel_latent_temperature=0.01, ar_model=None, ar_args=None, temp_sampling=1.0, temp_psi=0.0, temp_sigma_data=0.5,
              classifier_free_guidance_weight=0.0, softmax_latent_temperature=1.0, cfg_start=1.0, cfg_end=0.0,
-             compute_ar_accuracy=False, noise=None):
+             compute_ar_accuracy=False, noise=None, trajectory=None):
     """``noise`` (extra, optional): list with one tensor [steps, b, 6+R] per batch of N(0,1) draws (tr xyz, rot xyz,
-    torsions) to replace the device generator - used by the parity tests (the reference never seeds its RNGs)."""
-    if visualization_list is not None:
-        raise RuntimeError('ddk: visualisation is outside the accelerated hot path')
+    torsions) to replace the device generator - used by the parity tests (the reference never seeds its RNGs).
+
+    ``visualization_list`` (utils/sampling.py:224-228; evaluate.py --save_visualisation): the caller's objects, anything with
+    ``.add(coords, part, order)``.  As in the reference the WHOLE list is walked after EVERY batch: with n batches entry ``idx`` receives n calls
+    ``add(data_list[idx]['ligand'].pos.cpu() + data_list[idx].original_center.cpu(), part=1, order=2)``, in batch order and, within a batch, in list order; the
+    calls made before graph ``idx``'s own batch has run carry its start pose, the others its final pose (so the last call always does).  The ``.cpu()``
+    waits for the batch, as it does in the reference; here it comes after the batch's confidence model has been enqueued.
+
+    ``trajectory`` (extra, optional): a list that receives one :data:`runtime.Trajectory` per batch - device tensors ``pos`` [steps + 1, b, n_lig, 3]
+    (row k: before step k, centred coordinates like ``['ligand'].pos``; row ``steps`` = the returned poses), ``scores`` / ``perturb`` [steps, b, 6 + R] and
+    ``edge_counts`` [steps, 4] - recorded by the sampler's own launches; sampling() adds no synchronisation for it."""
     confidence, confidence_loader = None, None
     if confidence_model is not None:      # utils/sampling.py:59-62
         cg_conf = getattr(confidence_model, 'score_model', confidence_model)
@@ -326,7 +336,10 @@ def sampling(data_list, model, inference_steps, tr_schedule, rot_schedule, tor_s
                 z = None
             else:
                 z = draw_noise(inference_steps, b, cx.R, R, nc, device)
-            cx.sample(pos, t_arr, sc, nc, z)
+            if trajectory is not None:
+                trajectory.append(cx.sample(pos, t_arr, sc, nc, z, record=True))
+            else:
+                cx.sample(pos, t_arr, sc, nc, z)
             if confidence_model is not None and cg_conf is not None:
                 # utils/sampling.py:239-240: the score batch itself at the final poses; its times are those of the LAST EXECUTED step
                 # (t_idx = inference_steps - 1, utils/sampling.py:105-111: the reference resets them only in the confidence_data_list branch),
@@ -351,6 +364,10 @@ def sampling(data_list, model, inference_steps, tr_schedule, rot_schedule, tor_s
             graphs = [data_list[batch_id * batch_size + i] for i in range(b)]
             for i, d_i in enumerate(graphs):
                 d_i['ligand'].pos = flat[i * len_lig:len_lig * (i + 1)]
+            if visualization_list is not None:       # utils/sampling.py:224-228: every entry, after every batch
+                for idx, visualization in enumerate(visualization_list):
+                    visualization.add((data_list[idx]['ligand'].pos.detach().cpu() + data_list[idx].original_center.detach().cpu()),
+                                      part=1, order=2)
             if latent_model or conf_checks:
                 # latent bookkeeping of utils/sampling.py:205-221 and the confidence model's capacity flag: ONE read-back, enqueued behind the
                 # sampler and not awaited here (the reference synchronises 6x per pose)

@@ -260,6 +260,30 @@ int ddk_pose_metrics(ddk_ctx* ctx, ddk_complex* cx, int32_t B, const float* pos,
 int ddk_sample(ddk_ctx* ctx, ddk_complex* cx, int32_t B, int32_t steps, const float* t, const float* score_coeff,
                const float* noise_coeff, const float* noise, float* pos, void* stream);
 
+/* ---- ddk_sample that also RECORDS the trajectory on the device: what utils/sampling.py:224-228 hands to the visualisation_list
+ *      per batch (evaluate.py --save_visualisation, evaluate.py:236-247, 344-392) and, per step, the quantities of
+ *      utils/sampling.py:113-135 (scores, after the classifier-free guidance combination on guided steps) and :137-198 (the
+ *      tr / rot / tor perturbations passed to modify_conformer_batch).  The record is written by the launches ddk_sample makes
+ *      anyway: no launch and no copy is added per step (one device-to-device copy of the start poses before the loop), and there
+ *      is still no host synchronisation inside.  Same arguments, arithmetic and refusals as ddk_sample (steps < 1, B above the
+ *      complex's max_batch, a confidence_mode context); the poses come out bit-identical with and without a record.
+ *      rec: caller-owned DEVICE arrays, any member may be NULL (= not recorded); rec == NULL or all members NULL is ddk_sample:
+ *        pos         [steps + 1, B, n_lig, 3]  row k = the poses BEFORE step k, row steps = the final poses (= pos on return)
+ *        scores      [steps, B, 6 + n_rot]     tr xyz, rot xyz, tor... exactly as step k's update consumed them
+ *        perturb     [steps, B, 6 + n_rot]     score_coeff * score + noise_coeff * z of step k
+ *        edge_counts [steps, 4] int32          batch totals E_ll, E_lr, E_rr, E_rl of the graph step k's forward ran on
+ *                                              (ddk_last_graph_stats out[0..3], without its synchronisation)
+ *      The column layout 6 + n_rot is the noise argument's; the torsion columns are zero on a no_torsion context.  The arrays
+ *      must not overlap pos or each other and are complete once the stream has passed the call. */
+typedef struct ddk_trajectory {
+  float* pos;
+  float* scores;
+  float* perturb;
+  int32_t* edge_counts;
+} ddk_trajectory;
+int ddk_sample_trajectory(ddk_ctx* ctx, ddk_complex* cx, int32_t B, int32_t steps, const float* t, const float* score_coeff,
+                          const float* noise_coeff, const float* noise, float* pos, const ddk_trajectory* rec, void* stream);
+
 /* ---- graph construction alone (score_model.py:310-344 build_lig_conv_graph, :346-373 build_rec_conv_graph, :375-408
  *      build_cross_conv_graph, merged as in :218-225): for B poses of the complex at diffusion time t_tr, the ONE edge list the
  *      conv layers consume, in the reference's group order [lig-lig | lig->rec | rec-rec | rec->lig(flipped)], every group sorted
