@@ -52,12 +52,19 @@ typedef struct ddk_config {
   /* how the radial-MLP GEMMs (Linear(72,72) + ReLU + Linear(72,W), tensor_layers.py:140-143) of the fused conv kernel are multiplied.  Inputs, weights,
    * accumulators and outputs are fp32 in every mode; 0 and 3 run on the f16 matrix pipe with every fp32 operand carried as fp16 LIMBS (after an exact
    * power-of-two range scaling per weight group / per edge), 1 on the fp32 matrix pipe.
-   * 0 (default, since ddk 0.8): TWO limbs x = hi + mid (hi = fp16(x), mid = fp16(x - hi), both rounded to nearest: |x - hi - mid| <= 2^-22 |x|) and the
-   *    three limb products hi.hi + hi.mid + mid.hi in one fp32 accumulator (k_conv_x2.hip); mid.mid, <= 2^-22 relative like the operands' own truncation, is dropped.
-   *    Error per product <= 3 * 2^-22 relative, of a K = 72 dot product below the classical fp32 bound 72 * 2^-24 and, restated bit for bit on the host, not above an fp32 FMA
-   *    chain's over the same operands (tests/test_limb_bound.py); measured against the fp64 oracle it is level with mode 1
-   *    and mode 3 (6 - 10e-8 relative on every layer shape, tests/test_gpu_round6.py::test_two_limb_kernel_is_fp32_grade), 14 instead of 27 MFMAs per 32-edge weight tile
-   *    (DESIGN.md 3.3).
+   *    The range-scaling groups: for the weights one whole fc.<g> matrix (W1 [72, 72]; W2 [W, 72] with the tensor product's 1/sqrt(fan-in) folded into its
+   *    rows), scaled at pack time; for the activations one EDGE's 72 values (the GEMM1 inputs, then the hidden vector), scaled in the kernel.  A group's
+   *    maximum lands in [2^14, 2^15).
+   * 0 (default, since ddk 0.8): TWO limbs x = hi + mid (hi = fp16(x), mid = fp16(x - hi), both rounded to nearest) and the three limb products
+   *    hi.hi + hi.mid + mid.hi in one fp32 accumulator (k_conv_x2.hip).  After scaling |x - hi - mid| <= max(2^-22 |x|, 2^-25): RELATIVE 2^-22 for every value
+   *    within 17 binades of its range-scaling group's maximum, an ABSOLUTE 2^-39 of that maximum below (mid is then an fp16 subnormal).  Within the 17 binades
+   *    the dropped mid.mid is <= 2^-22 relative like the operands' own truncation, the error per product <= 3 * 2^-22 relative, of a K = 72 dot product below the
+   *    classical fp32 bound 72 * 2^-24 sum |a_i b_i| and, restated bit for bit on the host, not above an fp32 FMA chain's over the same operands
+   *    (tests/test_limb_bound.py).  An output column whose weights all lie further under the largest weight of its matrix (or an edge whose activations lie further
+   *    under its largest one) gets the absolute term instead: error <= 72 * 2^-24 sum |a_i b_i| + 2^-39 (max|W| sum |h_i| + max|h| sum |W_i|), pinned on
+   *    adversarial operands per weight column by tests/test_gpu_conv_adversarial.py.  On randn operands it is level with mode 1 and mode 3 against the fp64
+   *    oracle (6 - 10e-8 relative on every layer shape, tests/test_gpu_round6.py::test_two_limb_kernel_is_fp32_grade), 14 instead of 27 MFMAs per 32-edge
+   *    weight tile.
    * 3: THREE limbs x = hi + mid + lo (exact for every value within 2^-15 of its range-scaling group's maximum, off by <= 2^-39 of that maximum below), six of the
    *    nine limb products kept (the dropped ones are <= 3 * 2^-33 relative), two fp32 accumulators (k_conv_x.hip): products exact to 2^-33 - the default of
    *    ddk 0.4 - 0.7, ~35 % more conv time than 0.

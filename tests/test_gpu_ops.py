@@ -175,8 +175,13 @@ def test_conv_layer_x3_range(dev, in_scale, w1_scale, w2_scale):
     """The f16-limb products (0: two limbs / three products, the default; 3: three limbs / six products) must not depend on the SCALE of a checkpoint or of
     the features: operands are range-scaled by exact powers of two (weights per group at pack time, activations per edge in the kernel), so operands far outside
     the fp16 range meet the same bar, and the error against the fp64 oracle is not larger than the fp32-MFMA kernel's (VERDICT r02 #3 ii; 2x for the default).
-    (The three scales multiply to 1, so the messages stay O(1) next to the residual and the batch-norm statistics.)"""
+    (The three scales multiply to 1, so the messages stay O(1) next to the residual and the batch-norm statistics.)
+    The additive terms stay: with ~18 edges per node the fp32 atomics of the scatter reorder from run to run, and against the largest output element the
+    ratios to the fp32-MFMA kernel measured in two runs of the same build were 1.42 / 1.51 / 1.00 and 1.42 / 1.11 / 1.00 (default, bar 2.0) but
+    1.91 / 0.95 / 1.00 and 1.14 / 0.95 / 1.00 (three limbs, bar 1.5) over the three cases: the factors alone do not hold run to run.  The ratios are kept in the drift
+    file; the per-column bars without any additive term are tests/test_gpu_conv_adversarial.py's (one edge per node: no atomics noise)."""
     from disco_diffdock_amd.runtime import Context
+    from test_gpu_round3 import _record_drift
     l, N, splits = 3, 300, [0, 700, 2500, 4000, 5555]
     i_irr, o_irr = CFG.conv_irreps(l)
     Pl = smr.random_conv_layer_params(CFG, l, 77, True)
@@ -202,5 +207,7 @@ def test_conv_layer_x3_range(dev, in_scale, w1_scale, w2_scale):
         assert torch.isfinite(out).all()
         err[kernel] = rel_err(out, ref)
     print(f'range test {in_scale:g}/{w1_scale:g}/{w2_scale:g}: two limbs / three products {err[0]:.2e}, fp32 MFMA {err[1]:.2e}, three limbs / six products {err[3]:.2e}')
+    _record_drift(f'conv_layer_x3_range_{in_scale:g}_{w1_scale:g}_{w2_scale:g}', err[0], bar=1e-5, two_limbs_three_products=err[0], fp32_chains=err[1], six_products=err[3],
+                  two_limbs_ratio_to_fp32=err[0] / err[1], six_products_ratio_to_fp32=err[3] / err[1])
     assert err[3] < 1e-5 and err[3] < 1.5 * err[1] + 2e-7, err
     assert err[0] < 1e-5 and err[0] < 2.0 * err[1] + 4e-7, err      # the same per-edge range scaling: no dependence on the magnitude of inputs / weights

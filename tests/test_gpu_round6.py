@@ -303,7 +303,8 @@ def test_two_limb_kernel_is_fp32_grade(dev, l):
     |x - hi - mid| <= 2^-22 |x| (<= 2^-25 absolute after the per-group range scaling for values more than 2^-3 under their group's maximum); the dropped mid.mid is
     <= 2^-22 |x y| as well: a product carries <= 3 * 2^-22 relative error, a K = 72 dot product less than the classical bound 72 * 2^-24 of an fp32 FMA chain.  Measured
     here on 20k edges of every layer shape against the fp64 oracle, beside the three-limb / six-product kernel (3: products exact to 2^-33) and the fp32-MFMA chains (1):
-    the default must stay within 1.5x of the fp32 chains' error (+ 1e-7) and under 1e-5 relative - an order under north_star's 1e-4."""
+    the default must stay within 1.5x of the fp32 chains' error (no additive slack:
+    profiles/r06_parity_drift.json has the ratios at 0.62 - 1.12) and under 1e-5 relative - an order under north_star's 1e-4."""
     from disco_diffdock_amd.runtime import Context
     from test_gpu_ops import _random_case, CFG as OCFG
     from helpers import elem_err
@@ -327,4 +328,4 @@ def test_two_limb_kernel_is_fp32_grade(dev, l):
     _record_drift(f'conv_layer_{l}_20k_edges_vs_fp64_two_limb_default', err[0][0], bar=1e-5,
                   two_limbs_three_products=err[0][0], fp32_chains=err[1][0], six_products=err[3][0], two_limbs_elem=err[0][1], fp32_chains_elem=err[1][1], six_products_elem=err[3][1])
     assert not torch.equal(outs[0], outs[3])                  # (it IS another arithmetic: the mode switch reaches the kernel)
-    assert err[0][0] < 1e-5 and err[0][0] <= 1.5 * err[1][0] + 1e-7 and err[0][1] <= 1.5 * err[1][1] + 1e-6, err
+    assert err[0][0] < 1e-5 and err[0][0] <= 1.5 * err[1][0] and err[0][1] <= 1.5 * err[1][1], err

@@ -5,30 +5,8 @@ the fp64 oracle in tests/test_gpu_round6.py::test_two_limb_kernel_is_fp32_grade.
 import numpy as np
 import pytest
 
-
-def _adversarial(rng, n, binades):
-    """fp32 values with every mantissa bit in play, values one ulp around powers of two and around fp16 rounding boundaries (hi ties, mid ties), mixed signs,
-    spread over `binades` binades below the group's maximum"""
-    m = rng.integers(1 << 23, 1 << 24, size=n).astype(np.float64)
-    m[::7] = (1 << 23) + rng.integers(0, 3, size=m[::7].shape)
-    m[1::7] = (1 << 24) - 1 - rng.integers(0, 3, size=m[1::7].shape)
-    m[2::7] = ((rng.integers(1 << 10, 1 << 11, size=m[2::7].shape) << 13) | (1 << 12)) + rng.integers(-1, 2, size=m[2::7].shape)
-    m[3::7] = (rng.integers(1 << 10, 1 << 11, size=m[3::7].shape) << 13) | ((1 << 12) + (1 << 1) - 1) | (rng.integers(0, 2, size=m[3::7].shape) << 1)
-    e = rng.integers(-binades, 1, size=n)
-    return (rng.choice([-1.0, 1.0], size=n) * m * np.exp2(e.astype(np.float64) - 23)).astype(np.float32)
-
-
-def _range_scale(x, group):
-    """the kernel's exact power-of-two scaling: the maximum of every group of `group` values lands in [2^14, 2^15)"""
-    g = np.abs(x.astype(np.float64)).reshape(-1, group).max(axis=1)
-    e = np.floor(np.log2(np.maximum(g, 2.0 ** -40)))
-    return np.repeat(np.exp2(14 - e), group)
-
-
-def _two_limbs(xs):
-    hi = xs.astype(np.float32).astype(np.float16)
-    mid = (xs.astype(np.float32) - hi.astype(np.float32)).astype(np.float16)          # (the subtraction is exact in fp32: Sterbenz-like, hi is x rounded to 11 bits)
-    return hi.astype(np.float64), mid.astype(np.float64)
+from adversarial_operands import adversarial as _adversarial, range_scale as _range_scale, two_limbs as _two_limbs      # (moved: shared with the GPU test)
+import adversarial_operands as adv
 
 
 @pytest.mark.parametrize('binades', [3, 14, 30])
@@ -105,3 +83,72 @@ def test_emulated_kernel_arithmetic_is_at_least_as_accurate_as_an_fp32_fma_chain
           f'p99 {np.quantile(chain, .99):.2e} max {chain.max():.2e}')
     assert np.median(kern) <= 1.05 * np.median(chain) and np.quantile(kern, .99) <= np.quantile(chain, .99) and kern.max() <= chain.max()
     assert kern.max() < 72 * 2.0 ** -24
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# the CPU companion of tests/test_gpu_conv_adversarial.py: the same layer inputs, the same bars, on the host restatement of the kernel arithmetic
+# ------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('l', range(5))
+def test_adversarial_layer_inputs_observe_every_weight_column_once(l):
+    """What tests/test_gpu_conv_adversarial.py rests on, from the fp64 oracle: with one-hot senders, all-zero receivers with one edge each, a one-hot sh and an
+    identity batch norm every output element of tp_conv_layer is ONE coefficient times ONE column of the radial MLP's output (adv.layout: differentiated AND
+    confirmed by linearity); every one of the W columns is observed in every edge group; no element depends on two; the measures S cover exactly the non-zero
+    elements, so nothing is excluded.  All four groups non-empty, no group size a multiple of 32, E <= 20 000."""
+    L = adv.layout(l)
+    assert all(n > 0 and n % 32 for n in adv.GROUP_SIZES) and sum(adv.GROUP_SIZES) <= 20000
+    for arrangement, cls in (('gemm2', 'spread14'), ('gemm1', 'mixed_signs')):
+        case = adv.make_case(l, arrangement, cls, 0)
+        for g in range(4):
+            obs = case['observed'][g]
+            assert np.array_equal(obs[obs >= 0], np.arange(L['W'])), (l, g, 'a weight column is observed by no output element')
+        ref = adv.oracle_output(case)
+        E = case['splits'][-1]
+        # the closed form (coefficient x one column of the fp64 MLP) IS the oracle's layer output, element for element
+        P = {k: v.double().numpy() for k, v in case['P'].items()}
+        want = np.zeros_like(ref)
+        want[E:, :L['din']] = np.eye(L['din'])
+        bn = (float(np.float32(1.0 - 1e-5)) + 1e-5) ** -0.5
+        for g in range(4):
+            a, b = case['splits'][g], case['splits'][g + 1]
+            h = np.maximum(case['ea'][a:b].double().numpy() @ P[f'fc.{g}.0.weight'].T + P[f'fc.{g}.0.bias'], 0)
+            w = h @ P[f'fc.{g}.4.weight'].T + P[f'fc.{g}.4.bias']
+            c_of = L['col'][case['conf'][a:b]]
+            want[a:b] = np.where(c_of >= 0, L['coef'][case['conf'][a:b]] * np.take_along_axis(w, np.maximum(c_of, 0), 1) * bn, 0.0)
+        assert np.all(np.abs(want - ref) <= 1e-13 * case['S'] + 0.0), (l, arrangement)
+        assert np.all((case['S'] > 0) == (np.pad(L['col'][case['conf']], ((0, L['din']), (0, 0)), constant_values=-1) >= 0))
+        if arrangement == 'gemm2':
+            assert min(case['hits']) == 1.0, case['hits']      # the packed W2 rows carry the class's bit patterns (adv.preimage)
+
+
+@pytest.mark.parametrize('cls', adv.CLASSES)
+@pytest.mark.parametrize('arrangement', ['gemm2', 'gemm1'])
+def test_restated_kernel_meets_the_bars_on_adversarial_layer_inputs(arrangement, cls):
+    """Bars (a) and (b) of adversarial_operands.py - the SAME GAMMA and floor constants the GPU test imports - on the host restatement of the default kernel's two
+    GEMMs (K = 16 steps of three MFMAs plus the packed K = 8 tail, per-matrix / per-edge range scaling), and bar (a) on an fp32 FMA chain, for every operand
+    class in both arrangements and both variants; layers 1 (n_in 30 / 30 / 6: the widest spread of row scales) and 3."""
+    for l in (1, 3):
+        for variant in (0, 1):
+            case = adv.make_case(l, arrangement, cls, variant)
+            assert case['scale_ok']
+            ref = adv.oracle_output(case)
+            f0 = adv.figures(adv.host_restatement(case), ref, case, 0)
+            f1 = adv.figures(adv.host_restatement(case, chain=True), ref, case, 1)
+            print(f'{arrangement} {cls} layer {l} variant {variant}: restated limbs {f0} | fma chain {f1}')
+            assert f0['worst_over_bound'] <= 1.0, (l, variant, f0)
+            assert f1['worst_over_bound'] <= 1.0, (l, variant, f1)
+
+
+def test_the_bars_bite():
+    """Each mutant of the restated arithmetic must break a bar on these operands: the hi.mid product dropped in ONE K step (bar (a), any class); mid converted
+    with truncation (bar (b): the small-column class at 24 binades, where round-to-nearest loses 2^-29 and truncation 2^-24 per term, all of one sign);
+    the range scale one binade up (hi overflows wherever a group's maximum sits one ulp under a power of two)."""
+    def worst(arrangement, cls, mutant, l=3):
+        case = adv.make_case(l, arrangement, cls, 0)
+        return adv.figures(adv.host_restatement(case, mutant=mutant), adv.oracle_output(case), case, 0)['worst_over_bound']
+    for arrangement in ('gemm2', 'gemm1'):
+        assert worst(arrangement, 'spread3', None) <= 1.0
+        assert worst(arrangement, 'spread3', 'drop_hi_mid_in_one_step') > 1.0
+        assert worst(arrangement, 'mixed_signs', 'drop_hi_mid_in_one_step') > 1.0
+        assert worst(arrangement, 'small_column', 'truncate_mid') > 1.0
+        assert worst(arrangement, 'pow2_neighbours', 'scale_one_binade_up') > 1.0
+    assert worst('gemm1', 'dominant_entry', 'truncate_mid') > 1.0
