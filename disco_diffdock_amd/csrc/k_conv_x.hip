@@ -34,25 +34,59 @@
 // chunks of tile t+3 from L2 during its burst of tile t and stores them in its epilogue of tile t into the stage tile t-1 has left - group A
 // between barriers t and t+1, group B one interval later - so tile t+3 is complete at barrier t+2 and each wave fetches the first two K steps of
 // its NEXT tile at the start of its epilogue.
-// Experiment switches.  X3_ABL_* are TIMING-ONLY ablations (results invalid), ONE_ACC / X3_PF2 / X3_CXX_EPI / X_PROLOGUE_TILES are measured-and-dropped
-// alternatives kept for same-box A/Bs (tools/build_variant.sh builds them into ab_libs/, never into libddk.so).  A stray -D cannot reach the product library:
-#if (defined(X3_ABL_NOBARRIER) || defined(X3_ABL_BAR2) || defined(X3_ABL_PRIO_B2) || defined(X3_ABL_NOW1) || defined(X3_ABL_NOGATHER)) && !defined(DDK_TIMING_ONLY_BUILD)
-#error "X3_ABL_* switches give WRONG RESULTS (timing-only ablations): they need -DDDK_TIMING_ONLY_BUILD as well (tools/build_variant.sh adds it)"
-#endif
-#if (defined(ONE_ACC) || defined(X3_PF2) || defined(X3_CXX_EPI) || defined(X_PROLOGUE_TILES) || defined(X3_KEEP_MIDMID)) && !defined(DDK_VARIANT_BUILD) && !defined(DDK_TIMING_ONLY_BUILD)
-#error "experiment switch of k_conv_x.hip outside a variant build: add -DDDK_VARIANT_BUILD (tools/build_variant.sh adds it)"
-#endif
 #include <stdlib.h>
 
 #include "k_conv_common.h"
+
+// Everything that differs between the two forms this file is compiled into.  k_conv_x.hip itself is the THREE-LIMB form described above; k_conv_x2.hip
+// compiles the file a second time with X3_TWO_LIMBS as the TWO-LIMB form (ddk_config.conv_kernel = 0, include/ddk.h: the default), the same kernel
+// under its own names.  The forms differ in: the symbol names; the generated asm epilogue (two accumulators folded / one); the limb products of a K
+// step and of the packed tail (X3_STEP, X3_TAIL3) and how the accumulators are summed (X3_SUM); which limbs of a fragment are read from the ring
+// (X3_FRAG, X3_TAIL_LO); and, with 3 instead of 6 MFMA shadows per K step to hide them in, the instructions pinned behind each MFMA of the burst
+// (X3_RIDERS_0..3, one per K step region, and X3_TAIL_BARES: see X3_PAIR / X3_BARE / X3_BURST_BODY in the kernel).
 #ifdef X3_TWO_LIMBS
-// k_conv_x2.hip compiles this file a second time as the TWO-LIMB form (ddk_config.conv_kernel = 0, include/ddk.h): the same kernel under its own names
 #define conv_x3_kernel conv_x2_kernel
 #define launch_conv_fused_x launch_conv_fused_x2
 #define conv_prepare_device_x conv_prepare_device_x2
-#include "k_conv_x_epi2_gen.inc"     // ... generated with GEN_ONE_ACC=1: one accumulator, nothing to fold
+#include "k_conv_x_epi2_gen.inc"     // the tile epilogue as one asm statement per ring stage, generated with GEN_ONE_ACC=1: one accumulator, nothing to fold
+// TWO limbs per operand (hi = fp16(x), mid = fp16(x - hi): |x - hi - mid| <= 2^-22 |x|) and the three products hi.hi + hi.mid + mid.hi in ONE accumulator: 14 MFMAs per tile.
+// The fourth product mid.mid is <= 2^-22 relative - the size of the operands' own truncation - and is dropped (it rides for free in the packed K = 8 tail, where
+// {W_hi, W_mid} x {h_hi, h_mid} is one MFMA either way); a product is off by <= 3 * 2^-22, a K = 72 dot product by less than the classical fp32 bound 72 * 2^-24
+#define X3_SUM(r) D0[r]                      /* one accumulator: nothing to fold */
+#define X3_TAIL3(a_lh, a_hm) (void)(a_lh); D0 = MFMA16(a_hm, HT.mh, D0); D0 = MFMA16(a_hm, HT.hm, D0);
+#define X3_STEP(MF, ah, am, al, bh, bm, bl)   \
+  (void)(al);                                 \
+  D0 = MF(ah, bm, D0);                        \
+  D0 = MF(am, bh, D0);                        \
+  D0 = MF(ah, bh, D0);
+#define X3_FRAG(f, off) f.h = *reinterpret_cast<const f16x8*>(ringl + (off)); f.m = *reinterpret_cast<const f16x8*>(ringl + W2X_LIMB_BYTES + (off));
+#define X3_TAIL_LO(SO) th      /* (never multiplied: X3_TAIL3 drops a_lh) */
+/* the same riders as the three-limb form (two limbs of every fragment) in three shadows per region: some shadows take two */
+#define X3_TRIO(mask) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(mask, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); }
+#define X3_RIDERS_0 X3_PAIR(0x100) X3_TRIO(0x020) X3_TRIO(0x020)
+#define X3_RIDERS_1 X3_PAIR(0x100) X3_PAIR(0x100) X3_TRIO(0x100)
+#define X3_RIDERS_2 X3_PAIR(0x100) X3_PAIR(0x100) X3_BARE
+#define X3_RIDERS_3 X3_PAIR(0x100) X3_PAIR(0x100) X3_PAIR(0x100)
+#define X3_TAIL_BARES X3_BARE X3_BARE
 #else
 #include "k_conv_x_epi_gen.inc"      // the tile epilogue as one asm statement per ring stage (tools/gen_conv_x_epi.py; round 5)
+// six-term product of one K step into the two accumulators, alternating (D0: hi.hi and the 2^-11 terms, D1: the 2^-22 terms)
+#define X3_SUM(r) (D0[r] + D1[r])
+#define X3_TAIL3(a_lh, a_hm) D0 = MFMA16(a_hm, HT.mh, D0); D1 = MFMA16(a_lh, HT.hl, D1); D0 = MFMA16(a_hm, HT.hm, D0);
+#define X3_STEP(MF, ah, am, al, bh, bm, bl)   \
+  D1 = MF(ah, bl, D1);                        \
+  D0 = MF(ah, bm, D0);                        \
+  D1 = MF(al, bh, D1);                        \
+  D0 = MF(ah, bh, D0);                        \
+  D1 = MF(am, bm, D1);                        \
+  D0 = MF(am, bh, D0);
+#define X3_FRAG(f, off) f.h = *reinterpret_cast<const f16x8*>(ringl + (off)); f.m = *reinterpret_cast<const f16x8*>(ringl + W2X_LIMB_BYTES + (off)); f.l = *reinterpret_cast<const f16x8*>(ringl + 2 * W2X_LIMB_BYTES + (off));
+#define X3_TAIL_LO(SO) *reinterpret_cast<const f16x4*>(ringt + (SO) + 2 * W2X_LIMB_BYTES + 4096)
+#define X3_RIDERS_0 X3_PAIR(0x100) X3_PAIR(0x020) X3_PAIR(0x100) X3_PAIR(0x020) X3_PAIR(0x100) X3_PAIR(0x100)
+#define X3_RIDERS_1 X3_PAIR(0x100) X3_PAIR(0x100) X3_PAIR(0x100) X3_PAIR(0x100) X3_PAIR(0x100) X3_PAIR(0x100)
+#define X3_RIDERS_2 X3_PAIR(0x100) X3_PAIR(0x100) X3_PAIR(0x100) X3_BARE X3_BARE X3_BARE
+#define X3_RIDERS_3 X3_PAIR(0x100) X3_PAIR(0x100) X3_PAIR(0x100) X3_PAIR(0x100) X3_BARE X3_BARE
+#define X3_TAIL_BARES X3_BARE X3_BARE X3_BARE
 #endif
 
 namespace ddk {
@@ -112,18 +146,6 @@ __device__ __forceinline__ void make_limbs(Limbs& L, const float (&v)[36], float
 
 // workgroup barrier that waits for this wave's LDS traffic only: __syncthreads() also drains vmcnt, i.e. the global atomics of a flush and
 // the tile record requests that are meant to stay in flight across the barrier
-#if defined(X3_ABL_NOBARRIER)      // (timing-only ablation: no barrier inside the tile loop - ring races, results invalid)
-#define X3_LOOP_BARRIER(ST) ((void)0)
-#elif defined(X3_ABL_BAR2)         // (timing-only: a barrier every second tile)
-#define X3_LOOP_BARRIER(ST) do { if (((ST) & 1) == 0) lds_barrier(); } while (0)
-#else
-#define X3_LOOP_BARRIER(ST) lds_barrier()
-#endif
-#ifdef X3_ABL_PRIO_B2              // (timing-only: the later-dispatched half bursts at priority 2 - the arbiter prefers the older wave at equal priority)
-#define X3_BURST_PRIO() do { if (grp_s) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(1); } while (0)
-#else
-#define X3_BURST_PRIO() __builtin_amdgcn_s_setprio(1)
-#endif
 __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");      // s_waitcnt lgkmcnt(0)
   __builtin_amdgcn_s_barrier();
@@ -177,46 +199,6 @@ __device__ __forceinline__ void segf_add_n(float* dst, int stride, float (&xv)[N
   }
 }
 #undef SEGF_STEP
-
-// six-term product of one K step into the two accumulators, alternating (D0: hi.hi and the 2^-11 terms, D1: the 2^-22 terms)
-#if defined(X3_TWO_LIMBS)
-// TWO limbs per operand (hi = fp16(x), mid = fp16(x - hi): |x - hi - mid| <= 2^-22 |x|) and the three products hi.hi + hi.mid + mid.hi in ONE accumulator: 14 MFMAs per tile.
-// The fourth product mid.mid is <= 2^-22 relative - the size of the operands' own truncation - and is dropped (it rides for free in the packed K = 8 tail, where
-// {W_hi, W_mid} x {h_hi, h_mid} is one MFMA either way); a product is off by <= 3 * 2^-22, a K = 72 dot product by less than the classical fp32 bound 72 * 2^-24
-#define X3_SUM(r) D0[r]                      /* one accumulator: nothing to fold */
-#define X3_TAIL3(a_lh, a_hm) (void)(a_lh); D0 = MFMA16(a_hm, HT.mh, D0); D0 = MFMA16(a_hm, HT.hm, D0);
-#ifdef X3_KEEP_MIDMID      /* (variant builds, tools/build_variant2.sh: the fourth product mid.mid as well - 18 MFMAs per tile, +10 % conv time, no measurable accuracy) */
-#define X3_MM(MF, am, bm) D0 = MF(am, bm, D0);
-#else
-#define X3_MM(MF, am, bm)
-#endif
-#define X3_STEP(MF, ah, am, al, bh, bm, bl)   \
-  (void)(al);                                 \
-  X3_MM(MF, am, bm)                           \
-  D0 = MF(ah, bm, D0);                        \
-  D0 = MF(am, bh, D0);                        \
-  D0 = MF(ah, bh, D0);
-#elif defined(ONE_ACC)
-#define X3_SUM(r) (D0[r] + D1[r])
-#define X3_TAIL3(a_lh, a_hm) D0 = MFMA16(a_lh, HT.hl, D0); D0 = MFMA16(a_hm, HT.mh, D0); D0 = MFMA16(a_hm, HT.hm, D0);
-#define X3_STEP(MF, ah, am, al, bh, bm, bl)   \
-  D0 = MF(ah, bl, D0);                        \
-  D0 = MF(al, bh, D0);                        \
-  D0 = MF(am, bm, D0);                        \
-  D0 = MF(ah, bm, D0);                        \
-  D0 = MF(am, bh, D0);                        \
-  D0 = MF(ah, bh, D0);
-#else
-#define X3_SUM(r) (D0[r] + D1[r])
-#define X3_TAIL3(a_lh, a_hm) D0 = MFMA16(a_hm, HT.mh, D0); D1 = MFMA16(a_lh, HT.hl, D1); D0 = MFMA16(a_hm, HT.hm, D0);
-#define X3_STEP(MF, ah, am, al, bh, bm, bl)   \
-  D1 = MF(ah, bl, D1);                        \
-  D0 = MF(ah, bm, D0);                        \
-  D1 = MF(al, bh, D1);                        \
-  D0 = MF(ah, bh, D0);                        \
-  D1 = MF(am, bm, D1);                        \
-  D0 = MF(am, bh, D0);
-#endif
 
 // scalar-accumulator tensor-product epilogue of one W2 tile (wave-uniform branch on the tile kind; the f16 pipe does not compete with the VALU
 // for issue: fewer registers beat fewer instructions here).  T_RTS: only rows j = 0,1 belong to the column that is about to be flushed.
@@ -284,9 +266,8 @@ __device__ __forceinline__ void tile_epilogue_s(int w0, const f32x16& D, const f
 // four points of the unit's prologue (slots 4-7: unit start, indices + ring staging done, GEMM1 done, limbs + F rows done); ddk_debug_conv_trace,
 // tools/conv_trace.py.  Every stamp costs the wave ~100 cycles (s_memtime round trip): read the spans as upper bounds.
 // MODE 1: the confidence model's l <= 2 tensor product (a third accumulator set for the 1o(x)2e / 1e(x)2e row groups, nine edge groups, three accumulator slots)
-#ifndef X_PROLOGUE_TILES
-#define X_PROLOGUE_TILES 6.5f
-#endif
+// what a work unit costs before its first tile, in tile periods: the weight of an extra column chunk when the last blocks are split (derived at its use)
+constexpr float UNIT_PROLOGUE_TILES = 6.5f;
 template <bool GATHER, bool SPLIT, bool DET, bool TRACE = false, int MODE = 0>
 __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) {
   static_assert(!SPLIT || GATHER, "the GEMM1 split exists for the gather path");
@@ -301,7 +282,7 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
     }
   };
   bool first_tile = true;
-  auto stamp_epi = [&](int slot) {     // trace mode 2: four stamps INSIDE the epilogue (slots 4-7 of every tile but a unit's first, whose slots hold the prologue)
+  auto stamp_epi = [&](int slot) {     // trace mode 2: one more stamp per tile, behind the epilogue's descriptor read (slot 7 of every tile but a unit's first, whose slots 4-7 hold the prologue)
     if constexpr (TRACE) {
       if (AX.trace_coarse != 2 || first_tile) return;
       if (blockIdx.x == 0 && (threadIdx.x & 63) == 0 && trace_n < CONV_TRACE_TILES)
@@ -355,11 +336,7 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
   const uint32_t fo0 = 16u * tid, fo1 = 16u * min(tid + 64 * WAVES, REC16 - 1);
   // the hot instantiation (score-model conv layers: gather + node terms, atomics) runs its tile epilogue as ONE asm statement (k_conv_x_epi_gen.inc): the
   // accumulators are in/out operands of every tile kind's code alike, so the compiler has nothing to copy or select at a merge (VERDICT r04 #1a)
-#ifdef X3_CXX_EPI          // (A/B switch: the compiler-scheduled epilogue everywhere)
-  constexpr bool ASM_EPI = false;
-#else
-  constexpr bool ASM_EPI = GATHER && SPLIT && !DET && MODE == 0;     // (the trace build too: its stamps 4-6 inside the epilogue exist only under X3_CXX_EPI)
-#endif
+  constexpr bool ASM_EPI = GATHER && SPLIT && !DET && MODE == 0;     // (the trace build too)
   const unsigned ring0_u = (unsigned)(WAVES * 32 * FS * 4), ringb_u = ring0_u + 64u * hh, ringw0_u = ring0_u + fo0, ringw1_u = ring0_u + fo1;
   const unsigned fra_u = (unsigned)((wave * 32 + el) * FS * 4), hh4_u = 4u * hh, hh12_u = 12u * hh;
   int t0_, t1_, t2_, sel_, pk0_, pk1_, pk2_;
@@ -375,10 +352,10 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
   if (rest > 0) {
     float best = 1e30f;
     // rounds of the last blocks' chunks x the length of a chunk in tile periods: its share of the tiles + the unit prologue every chunk repeats
-    // (gathers, GEMM1, limbs: ~17 k cycles = X_PROLOGUE_TILES tile periods; round 3's rule charged 5 % of a block per extra chunk - a third of the
+    // (gathers, GEMM1, limbs: ~17 k cycles = UNIT_PROLOGUE_TILES tile periods; round 3's rule charged 5 % of a block per extra chunk - a third of the
     // real cost at 59 tiles - and cut the small launches of the late reverse steps into too many chunks)
     for (int sp = 1; sp <= A.n_cols; ++sp) {
-      const float cost = (float)((rest * sp + nwg - 1) / nwg) * ((float)n_tiles / (float)sp + X_PROLOGUE_TILES);
+      const float cost = (float)((rest * sp + nwg - 1) / nwg) * ((float)n_tiles / (float)sp + UNIT_PROLOGUE_TILES);
       if (cost < best - 1e-6f) { best = cost; split = sp; }
     }
   }
@@ -440,11 +417,7 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
     float4 mainv[NS / 4];
     float2 pv2[3 * NV / 2];
     {
-#ifdef X3_ABL_NOGATHER      // (timing-only: every lane reads the rows of the wave's FIRST edge - one cache line per request instead of 32: what would hiding the gathers be worth?)
-      const float* xr = A.x + (size_t)__shfl(dn, 0, 32) * XW;
-#else
       const float* xr = A.x + (size_t)dn * XW;
-#endif
 #pragma unroll
       for (int j = 0; j < NS / 4; ++j) mainv[j] = ld4(xr + (hh ? OFF_C : 0) + 4 * j);
 #pragma unroll
@@ -464,13 +437,8 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
         // L2): all 18 requests of a lane go out together, right behind the indices - one exposed memory latency, not one per row tile
         float4 psv[9], pdv[9];
         {
-#ifdef X3_ABL_NOGATHER
-          const float* ps = A.pre + ((size_t)__shfl(sn, 0, 32) * 4 + (gw & 1)) * NE + 36 * hh;
-          const float* pd = A.pre + ((size_t)__shfl(dn, 0, 32) * 4 + 2 + (gw >> 1)) * NE + 36 * hh;
-#else
           const float* ps = A.pre + ((size_t)sn * 4 + (gw & 1)) * NE + 36 * hh;
           const float* pd = A.pre + ((size_t)dn * 4 + 2 + (gw >> 1)) * NE + 36 * hh;
-#endif
 #pragma unroll
           for (int j = 0; j < 9; ++j) { psv[j] = ld4(ps + 4 * j); pdv[j] = ld4(pd + 4 * j); }
         }
@@ -514,25 +482,15 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
           for (int r = 0; r < 16; ++r) D1[r] = 0.0f;
           const char* wt = w1 + (size_t)T * W1X_TILE_BYTES;
           {
-#ifdef X3_ABL_NOW1      // (timing-only ablation: no W1 fragment loads)
-            f16x8 ah, am, al;
-            for (int i = 0; i < 8; ++i) { ah[i] = (_Float16)(float)(lane + T); am[i] = (_Float16)(float)(lane + 2 * T); al[i] = (_Float16)(float)(lane + 3 * T); }
-#else
             const f16x8 ah = *reinterpret_cast<const f16x8*>(wt + lane * 16);
             const f16x8 am = *reinterpret_cast<const f16x8*>(wt + W2X_LIMB_BYTES + lane * 16);
             const f16x8 al = *reinterpret_cast<const f16x8*>(wt + 2 * W2X_LIMB_BYTES + lane * 16);
-#endif
             X3_STEP(MFMA16, ah, am, al, b0h, b0m, b0l)
           }
           {     // registers 8..11: the first half of step 1's fragment
-#ifdef X3_ABL_NOW1
-            f16x4 ah, am, al;
-            for (int i = 0; i < 4; ++i) { ah[i] = (_Float16)(float)(lane + T + 1); am[i] = (_Float16)(float)(lane + 2 * T + 1); al[i] = (_Float16)(float)(lane + 3 * T + 1); }
-#else
             const f16x4 ah = *reinterpret_cast<const f16x4*>(wt + 1024 + lane * 16);
             const f16x4 am = *reinterpret_cast<const f16x4*>(wt + W2X_LIMB_BYTES + 1024 + lane * 16);
             const f16x4 al = *reinterpret_cast<const f16x4*>(wt + 2 * W2X_LIMB_BYTES + 1024 + lane * 16);
-#endif
             // (the K = 8 half step packed like the tile tail: hi.mid + mid.hi, lo.hi + hi.lo, hi.hi + mid.mid as one K = 16 MFMA each: 9 instead of 12 per row tile)
             const f16x8 a_hm = __builtin_shufflevector(ah, am, 0, 1, 2, 3, 4, 5, 6, 7), a_lh = __builtin_shufflevector(al, ah, 0, 1, 2, 3, 4, 5, 6, 7);
             D0 = MFMA16(a_hm, b1_mh, D0);
@@ -695,22 +653,12 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
 #ifndef X3_TWO_LIMBS
     p0.l = *reinterpret_cast<const f16x8*>(ringl + 2 * W2X_LIMB_BYTES);
 #endif
-#ifdef X3_PF2          // (experiment: fragments requested TWO K steps ahead: p0 / p1 of a tile in the previous burst's last two steps, +12 VGPRs across the epilogue)
-    Frag16 p1;
-    p1.h = *reinterpret_cast<const f16x8*>(ringl + 1024); p1.m = *reinterpret_cast<const f16x8*>(ringl + W2X_LIMB_BYTES + 1024); p1.l = *reinterpret_cast<const f16x8*>(ringl + 2 * W2X_LIMB_BYTES + 1024);
-#endif
     int w0, chan0;
     {
       const int2 dq = *reinterpret_cast<const int2*>(ring + W2X_DESC_OFF);
       w0 = __builtin_amdgcn_readfirstlane(dq.x); chan0 = __builtin_amdgcn_readfirstlane(dq.y);
     }
     const bool grp_s = __builtin_amdgcn_readfirstlane(grp) != 0;      // provably wave-uniform: the barrier sits behind a scalar branch
-    const int grp_i = __builtin_amdgcn_readfirstlane(grp); (void)grp_i;
-    // (asm epilogue generated with GEN_DEFER=1 - an experiment, default off) group A's flush runs one tile late, in the interval in which group B flushes the same
-    // column: the column's values, its kind (0 none / 1 scalar / 2 vector) and its channel offset wait here
-    float P_[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    int pend_ = 0, pchan_ = 0;
-    (void)P_; (void)pend_; (void)pchan_;
     // the rare part of an epilogue: the packed extra quad of a 6-channel column and the flush of a column the tile closes
     auto finish_tile = [&](int w0x, int chan0x, const f32x16& D, f32x4 f0x) {
       if (w0x & 0x80) {   // 6-channel column: accumulator quad 3 holds another a / c row quad for channel pair xp
@@ -763,77 +711,7 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
     // one tile: burst + epilogue; ST = the tile's ring stage (compile time)
 #define X3_PAIR(mask) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(mask, 1, 0); }
 #define X3_BARE { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); }
-#ifdef X3_TWO_LIMBS
-#define X3_FRAG(f, off) f.h = *reinterpret_cast<const f16x8*>(ringl + (off)); f.m = *reinterpret_cast<const f16x8*>(ringl + W2X_LIMB_BYTES + (off));
-#define X3_TRIO(mask) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(mask, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); }
-#else
-#define X3_FRAG(f, off) f.h = *reinterpret_cast<const f16x8*>(ringl + (off)); f.m = *reinterpret_cast<const f16x8*>(ringl + W2X_LIMB_BYTES + (off)); f.l = *reinterpret_cast<const f16x8*>(ringl + 2 * W2X_LIMB_BYTES + (off));
-#endif
-#if defined(X3_TWO_LIMBS)
-/* three products per K step + the packed tail: 14 MFMAs; the same riders (two limbs of every fragment), three shadows per region */
-#ifndef X3_KEEP_MIDMID
-#define X3_L2_R0 X3_PAIR(0x100) X3_TRIO(0x020) X3_TRIO(0x020)
-#define X3_L2_R1 X3_PAIR(0x100) X3_PAIR(0x100) X3_TRIO(0x100)
-#define X3_L2_R2 X3_PAIR(0x100) X3_PAIR(0x100) X3_BARE
-#define X3_L2_R3 X3_PAIR(0x100) X3_PAIR(0x100) X3_PAIR(0x100)
-#else
-#define X3_L2_R0 X3_PAIR(0x100) X3_PAIR(0x020) X3_PAIR(0x100) X3_TRIO(0x020)
-#define X3_L2_R1 X3_PAIR(0x100) X3_PAIR(0x100) X3_PAIR(0x100) X3_PAIR(0x100)
-#define X3_L2_R2 X3_PAIR(0x100) X3_PAIR(0x100) X3_BARE X3_BARE
-#define X3_L2_R3 X3_PAIR(0x100) X3_PAIR(0x100) X3_PAIR(0x100) X3_BARE
-#endif
-#define X3_BURST_BODY(ST)                                                                                                                    \
-      Frag16 p1; X3_FRAG(p1, SO + 1024)                                                                                                      \
-      const f32x4 f0 = ldv4(Fp);                                                                                                             \
-      const u32x4 st0 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)fo0, rec_soff, 0);                                                  \
-      const u32x4 st1 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)fo1, rec_soff, 0);                                                  \
-      rec_soff += W2X_TILE_BYTES;                                                                                                            \
-      X3_STEP(MFMA16, p0.h, p0.m, p0.l, H.hi[0], H.mid[0], H.lo[0])                                                                         \
-      X3_L2_R0                                                                                                                               \
-      __builtin_amdgcn_sched_barrier(0);                                                                                                     \
-      Frag16 q2; X3_FRAG(q2, SO + 2048)                                                                                                      \
-      const f16x4 th = *reinterpret_cast<const f16x4*>(ringt + SO + 4096);                                                                   \
-      const f16x4 tm = *reinterpret_cast<const f16x4*>(ringt + SO + W2X_LIMB_BYTES + 4096);                                                  \
-      const f16x4 tl = th;                                                                                                                   \
-      X3_STEP(MFMA16, p1.h, p1.m, p1.l, H.hi[1], H.mid[1], H.lo[1])                                                                         \
-      X3_L2_R1                                                                                                                               \
-      __builtin_amdgcn_sched_barrier(0);                                                                                                     \
-      Frag16 q3; X3_FRAG(q3, SO + 3072)                                                                                                      \
-      X3_STEP(MFMA16, q2.h, q2.m, q2.l, H.hi[2], H.mid[2], H.lo[2])                                                                         \
-      X3_L2_R2                                                                                                                               \
-      __builtin_amdgcn_sched_barrier(0);                                                                                                     \
-      const int2 dq = *reinterpret_cast<const int2*>(ring + SN + W2X_DESC_OFF);                                                              \
-      X3_FRAG(p0, SN)                                                                                                                        \
-      X3_STEP(MFMA16, q3.h, q3.m, q3.l, H.hi[3], H.mid[3], H.lo[3])                                                                         \
-      X3_L2_R3                                                                                                                               \
-      __builtin_amdgcn_sched_barrier(0);
-#elif defined(X3_PF2)
-#define X3_BURST_BODY(ST)                                                                                                                    \
-      Frag16 q2; X3_FRAG(q2, SO + 2048)                                                                                                      \
-      const f32x4 f0 = ldv4(Fp);                                                                                                             \
-      const u32x4 st0 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)fo0, rec_soff, 0);                                                  \
-      const u32x4 st1 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)fo1, rec_soff, 0);                                                  \
-      rec_soff += W2X_TILE_BYTES;                                                                                                            \
-      X3_STEP(MFMA16, p0.h, p0.m, p0.l, H.hi[0], H.mid[0], H.lo[0])                                                                         \
-      X3_PAIR(0x100) X3_PAIR(0x020) X3_PAIR(0x100) X3_PAIR(0x020) X3_PAIR(0x100) X3_PAIR(0x100)                                              \
-      __builtin_amdgcn_sched_barrier(0);                                                                                                     \
-      Frag16 q3; X3_FRAG(q3, SO + 3072)                                                                                                      \
-      const f16x4 th = *reinterpret_cast<const f16x4*>(ringt + SO + 4096);                                                                   \
-      const f16x4 tm = *reinterpret_cast<const f16x4*>(ringt + SO + W2X_LIMB_BYTES + 4096);                                                  \
-      const f16x4 tl = *reinterpret_cast<const f16x4*>(ringt + SO + 2 * W2X_LIMB_BYTES + 4096);                                              \
-      X3_STEP(MFMA16, p1.h, p1.m, p1.l, H.hi[1], H.mid[1], H.lo[1])                                                                         \
-      X3_PAIR(0x100) X3_PAIR(0x100) X3_PAIR(0x100) X3_PAIR(0x100) X3_PAIR(0x100) X3_PAIR(0x100)                                              \
-      __builtin_amdgcn_sched_barrier(0);                                                                                                     \
-      const int2 dq = *reinterpret_cast<const int2*>(ring + SN + W2X_DESC_OFF);                                                              \
-      X3_FRAG(p0, SN)                                                                                                                        \
-      X3_STEP(MFMA16, q2.h, q2.m, q2.l, H.hi[2], H.mid[2], H.lo[2])                                                                         \
-      X3_PAIR(0x100) X3_PAIR(0x100) X3_PAIR(0x100) X3_PAIR(0x100) X3_BARE X3_BARE                                                            \
-      __builtin_amdgcn_sched_barrier(0);                                                                                                     \
-      X3_FRAG(p1, SN + 1024)                                                                                                                 \
-      X3_STEP(MFMA16, q3.h, q3.m, q3.l, H.hi[3], H.mid[3], H.lo[3])                                                                         \
-      X3_PAIR(0x100) X3_PAIR(0x100) X3_PAIR(0x100) X3_BARE X3_BARE X3_BARE                                                                   \
-      __builtin_amdgcn_sched_barrier(0);
-#else
+    // the four K = 16 steps of a burst; behind every step the riders of its region (per form, top of the file): one sched_group_barrier pair per MFMA
 #define X3_BURST_BODY(ST)                                                                                                                    \
       Frag16 p1; X3_FRAG(p1, SO + 1024)                                                                                                      \
       const f32x4 f0 = ldv4(Fp);                                                                                                             \
@@ -842,36 +720,30 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
       const u32x4 st1 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)fo1, rec_soff, 0);                                                  \
       rec_soff += W2X_TILE_BYTES;                                                                                                            \
       X3_STEP(MFMA16, p0.h, p0.m, p0.l, H.hi[0], H.mid[0], H.lo[0])                                                                         \
-      X3_PAIR(0x100) X3_PAIR(0x020) X3_PAIR(0x100) X3_PAIR(0x020) X3_PAIR(0x100) X3_PAIR(0x100)                                              \
+      X3_RIDERS_0                                                                                                                            \
       __builtin_amdgcn_sched_barrier(0);                                                                                                     \
       Frag16 q2; X3_FRAG(q2, SO + 2048)                                                                                                      \
       const f16x4 th = *reinterpret_cast<const f16x4*>(ringt + SO + 4096);                                                                   \
       const f16x4 tm = *reinterpret_cast<const f16x4*>(ringt + SO + W2X_LIMB_BYTES + 4096);                                                  \
-      const f16x4 tl = *reinterpret_cast<const f16x4*>(ringt + SO + 2 * W2X_LIMB_BYTES + 4096);                                              \
+      const f16x4 tl = X3_TAIL_LO(SO);                                                                                                       \
       X3_STEP(MFMA16, p1.h, p1.m, p1.l, H.hi[1], H.mid[1], H.lo[1])                                                                         \
-      X3_PAIR(0x100) X3_PAIR(0x100) X3_PAIR(0x100) X3_PAIR(0x100) X3_PAIR(0x100) X3_PAIR(0x100)                                              \
+      X3_RIDERS_1                                                                                                                            \
       __builtin_amdgcn_sched_barrier(0);                                                                                                     \
       Frag16 q3; X3_FRAG(q3, SO + 3072)                                                                                                      \
       X3_STEP(MFMA16, q2.h, q2.m, q2.l, H.hi[2], H.mid[2], H.lo[2])                                                                         \
-      X3_PAIR(0x100) X3_PAIR(0x100) X3_PAIR(0x100) X3_BARE X3_BARE X3_BARE                                                                   \
+      X3_RIDERS_2                                                                                                                            \
       __builtin_amdgcn_sched_barrier(0);                                                                                                     \
       const int2 dq = *reinterpret_cast<const int2*>(ring + SN + W2X_DESC_OFF);                                                              \
       X3_FRAG(p0, SN)       /* (p0's last use was K step 0 of this burst: the next tile's first K step goes straight into its registers) */    \
       X3_STEP(MFMA16, q3.h, q3.m, q3.l, H.hi[3], H.mid[3], H.lo[3])                                                                         \
-      X3_PAIR(0x100) X3_PAIR(0x100) X3_PAIR(0x100) X3_PAIR(0x100) X3_BARE X3_BARE                                                            \
+      X3_RIDERS_3                                                                                                                            \
       __builtin_amdgcn_sched_barrier(0);
-#endif
-#ifdef X3_TWO_LIMBS
-#define X3_TAIL_BARES X3_BARE X3_BARE
-#else
-#define X3_TAIL_BARES X3_BARE X3_BARE X3_BARE
-#endif
 #define X3_TILE(ST)                                                                                                                          \
     {                                                                                                                                        \
       constexpr int SO = (ST) * W2X_TILE_BYTES, SN = (((ST) + 1) & 3) * W2X_TILE_BYTES, SW = (((ST) + 3) & 3) * W2X_TILE_BYTES;              \
       /* the bursting wave wins issue arbitration against its SIMD partner's epilogue (round 3's static priority for the later-dispatched   \
          half costs 7 % once the half phases are not separated by a barrier; priority during the epilogue instead: +2.5 %) */                \
-      X3_BURST_PRIO();                                                                                                                       \
+      __builtin_amdgcn_s_setprio(1);                                                                                                         \
       stamp(0);                                                                                                                              \
       /* ===== burst: 27 MFMAs; every other instruction rides in an MFMA shadow, pinned region by region (one K step each): the LDS reads    \
          of the fragments one step ahead, the feature rows, this thread's two chunks of record t+3 and - in the tail - the next tile's       \
@@ -889,7 +761,7 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
       __builtin_amdgcn_sched_barrier(0);                                                                                                     \
       __builtin_amdgcn_s_setprio(0);                                                                                                         \
       stamp(1);                                                                                                                              \
-      if (grp_s) X3_LOOP_BARRIER(ST);          /* group B: [epilogue t-1, burst t] | barrier | [epilogue t, burst t+1] */                          \
+      if (grp_s) lds_barrier();                /* group B: [epilogue t-1, burst t] | barrier | [epilogue t, burst t+1] */                    \
       stamp(2);                                                                                                                              \
       /* ===== epilogue (beside the SIMD partner's burst): the tile's bias, then this thread's chunks of tile t+3 into the stage tile t-1     \
          has left (nobody reads it between barriers t and t+2) ===== */                                                                      \
@@ -902,13 +774,11 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
       const float4 bs2 = ld4(reinterpret_cast<const float*>(ringb + SO + W2X_BIAS_OFF + 32)), bs3 = ld4(reinterpret_cast<const float*>(ringb + SO + W2X_BIAS_OFF + 48)); \
       *reinterpret_cast<u32x4*>(ringw0 + SW) = st0;                                                                                          \
       *reinterpret_cast<u32x4*>(ringw1 + SW) = st1;                                                                                          \
-      stamp_epi(4);                                                                                                                          \
       /* the two accumulators and the bias into one */                                                                                       \
       D0[0] = fmaf(bs0.x, bsc2, X3_SUM(0)); D0[1] = fmaf(bs0.y, bsc2, X3_SUM(1)); D0[2] = fmaf(bs0.z, bsc2, X3_SUM(2)); D0[3] = fmaf(bs0.w, bsc2, X3_SUM(3)); \
       D0[4] = fmaf(bs1.x, bsc2, X3_SUM(4)); D0[5] = fmaf(bs1.y, bsc2, X3_SUM(5)); D0[6] = fmaf(bs1.z, bsc2, X3_SUM(6)); D0[7] = fmaf(bs1.w, bsc2, X3_SUM(7)); \
       D0[8] = fmaf(bs2.x, bsc2, X3_SUM(8)); D0[9] = fmaf(bs2.y, bsc2, X3_SUM(9)); D0[10] = fmaf(bs2.z, bsc2, X3_SUM(10)); D0[11] = fmaf(bs2.w, bsc2, X3_SUM(11)); \
       D0[12] = fmaf(bs3.x, bsc2, X3_SUM(12)); D0[13] = fmaf(bs3.y, bsc2, X3_SUM(13)); D0[14] = fmaf(bs3.z, bsc2, X3_SUM(14)); D0[15] = fmaf(bs3.w, bsc2, X3_SUM(15)); \
-      stamp_epi(5);                                                                                                                          \
       if ((w0 & 0x8e) == 0) {        /* the common tile: scalar rows (T_RA / T_RT), no packed quad, no flush */                              \
         if (w0 & 1) {                                                                                                                        \
           _Pragma("unroll") for (int rq = 0; rq < 4; ++rq)                                                                                   \
@@ -917,10 +787,8 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
           _Pragma("unroll") for (int rq = 0; rq < 4; ++rq)                                                                                   \
             accA[rq] = fmaf(f0.x, D0[4 * rq], fmaf(f0.y, D0[4 * rq + 1], fmaf(f0.z, D0[4 * rq + 2], fmaf(f0.w, D0[4 * rq + 3], accA[rq])))); \
         }                                                                                                                                    \
-        stamp_epi(6);                                                                                                                        \
       } else {                                                                                                                               \
         tile_epilogue_s<MODE>(w0, D0, Fp, f0, accA, accV, accX, accY);                                                                       \
-        stamp_epi(6);                                                                                                                        \
         finish_tile(w0, chan0, D0, f0);                                                                                                      \
       }                                                                                                                                      \
       }                                                                                                                                      \
@@ -928,7 +796,7 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
       stamp_epi(7);                                                                                                                          \
       stamp(3);                                                                                                                              \
       first_tile = false;                                                                                                                    \
-      if (!grp_s) X3_LOOP_BARRIER(ST);         /* group A: [burst t, epilogue t] | barrier */                                                      \
+      if (!grp_s) lds_barrier();               /* group A: [burst t, epilogue t] | barrier */                                                \
     }
     for (int t = t_begin;;) {       // unrolled over the ring's four stages: tile t_begin + i sits in stage i & 3
       X3_TILE(0)
@@ -940,10 +808,8 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
       X3_TILE(3)
       if (++t >= t_end) break;
     }
-    if constexpr (ASM_EPI) { X3_EPI_DRAIN(); }      // group A's last column (group B is still in its last epilogue: nobody waits for this)
 #undef X3_PAIR
 #undef X3_BARE
-#undef X3_FRAG
 #undef X3_TILE
 #undef X3_BURST_BODY
     // hand the next unit to the workgroup.  Group A waits here through group B's last epilogue: this barrier also retires the ring

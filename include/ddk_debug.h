@@ -61,9 +61,11 @@ int ddk_debug_axis_angle(ddk_ctx* ctx, int32_t n, const float* aa, float* R_out,
 
 /* Timeline of the default conv kernel (k_conv_x.hip): conv layer `layer` of the following score-model forwards runs the kernel's TRACE
  * instantiation, whose workgroup 0 stamps s_memtime at the four edges of every tile's two half phases into trace (DEVICE,
- * [8 waves][1024 tiles][8] uint32: burst start, burst end, epilogue start, epilogue end, then four stamps inside the burst: before K step 0, 1, 2, 3; tools/conv_trace.py).  trace = NULL: off. */
+ * [8 waves][1024 tiles][8] uint32: burst start, burst end, epilogue start, epilogue end; slots 4-7 of the first tile's record of a unit: four stamps of the unit's prologue - unit start, indices + ring staging done,
+ * GEMM1 done, limbs + F rows done; tools/conv_trace.py).  trace = NULL: off. */
 /* layer = 100 + l: one record per UNIT instead of per tile (slots 4-7 as above, 0 = tile loop done, 1 = tiles of the unit, 2 = unit handed over):
- * no stamp inside the tile loop, undisturbed cycles per tile. */
+ * no stamp inside the tile loop, undisturbed cycles per tile.  layer = 200 + l: the per-tile records with one more stamp in slot 7 of every tile but a unit's first,
+ * behind the descriptor read that ends the epilogue. */
 int ddk_debug_conv_trace(ddk_ctx* ctx, int32_t layer, uint32_t* trace);
 
 /* The default conv kernel's limb split (k_conv_x.hip) on a DEVICE array x [n], cut into groups of `group` consecutive values that share one

@@ -435,5 +435,13 @@ def test_build_stamp_covers_the_public_headers_and_the_product_has_no_variant_ke
     assert any(h.endswith('k_conv_x_epi_gen.inc') for h in hs) and all(os.path.exists(h) for h in hs)
     assert 'k_conv_y.hip' not in build.SOURCES and not os.path.exists(os.path.join(ROOT, 'disco_diffdock_amd', 'csrc', 'k_conv_y.hip'))
     assert os.path.exists(os.path.join(ROOT, 'tools', 'variants', 'k_conv_y.hip'))
-    src = open(os.path.join(ROOT, 'disco_diffdock_amd', 'csrc', 'k_conv_x.hip')).read()
-    assert '#error "X3_ABL_* switches give WRONG RESULTS' in src      # a stray -DX3_ABL_* cannot produce a wrong-answer product library
+    # a stray -D cannot produce a wrong-answer product library: the timing-only ablations and the dropped alternatives are gone from the product sources
+    import re
+    gone = ('X3_ABL_', 'X3_PF2', 'X3_CXX_EPI', 'X3_KEEP_MIDMID', 'X_PROLOGUE_TILES', 'DDK_ABL_', 'DDK_TIMING_ONLY_BUILD', 'DDK_VARIANT_BUILD')
+    csrc = os.path.join(ROOT, 'disco_diffdock_amd', 'csrc')
+    for d, _, files in os.walk(csrc):
+        for f in files:
+            src = open(os.path.join(d, f), 'rb').read().decode('latin-1')
+            for name in gone:
+                assert name not in src, (f, name)
+            assert not re.search(r'(?<!GEN_)\bONE_ACC\b', src), f

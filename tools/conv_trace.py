@@ -12,7 +12,7 @@ from disco_diffdock_amd.runtime import Context, Complex
 ap = argparse.ArgumentParser()
 ap.add_argument('--layer', type=int, default=3)
 ap.add_argument('--t', type=float, default=0.6)
-ap.add_argument('--epi', action='store_true', help='four more stamps inside every epilogue: LDS requests + ring stores | fold | tensor product | packed quad, flush, descriptor')
+ap.add_argument('--epi', action='store_true', help='one more stamp per tile, behind the descriptor read that ends the epilogue (the epilogue itself is one asm statement)')
 ap.add_argument('--samples', type=int, default=40, help='poses in the batch (5: every node row fits every L2)')
 ap.add_argument('--coarse', action='store_true', help='one record per unit (no stamps inside the tile loop): undisturbed cycles per tile')
 a = ap.parse_args()
@@ -46,21 +46,19 @@ if a.coarse:
     sys.exit(0)
 n = int((tr[0, :, 3] != 0).sum())
 if a.epi:
-    print(f'layer {a.layer}: epilogue sub-phases (ticks incl. ~100 per stamp), tiles that are not the first of a unit; by tile class')
+    print(f'layer {a.layer}: epilogue up to its closing stamp (ticks incl. ~100 per stamp), tiles that are not the first of a unit; by tile class')
     for w in (0, 4):
         x = tr[w, :n]
-        ok = x[:, 4] != 0
-        ok[np.nonzero(x[:, 4] != 0)[0]] = True
-        # a unit's first tile carries the prologue stamps in slots 4-7: recognise it by slot 7 < slot 0 (prologue precedes the burst)
-        notfirst = (x[:, 4] > x[:, 2]) & (x[:, 7] > x[:, 4])
+        # a unit's first tile carries the prologue stamps in slots 4-7: there slot 7 precedes the burst (slot 0)
+        notfirst = x[:, 7] > x[:, 2]
         if not notfirst.any():
-            print('no sub-stamps found; first records:'); print(x[:6])
+            print('no epilogue stamps found; first records:'); print(x[:6])
         y = x[notfirst]
         ep = y[:, 3] - y[:, 2]
-        parts = np.stack([y[:, 4] - y[:, 2], y[:, 5] - y[:, 4], y[:, 6] - y[:, 5], y[:, 7] - y[:, 6], y[:, 3] - y[:, 7]], 1)
+        parts = np.stack([y[:, 7] - y[:, 2], y[:, 3] - y[:, 7]], 1)
         for name, m in (('ordinary (epilogue < 1400)', ep < 1400), ('long (>= 1400: flush / vector tiles)', ep >= 1400)):
             if m.any():
-                print(f'wave {w} {name}: {int(m.sum())} tiles, epilogue {ep[m].mean():.0f} = requests+stores {parts[m, 0].mean():.0f} | fold {parts[m, 1].mean():.0f} | tensor product {parts[m, 2].mean():.0f} | quad+flush+descriptor {parts[m, 3].mean():.0f} | close {parts[m, 4].mean():.0f};  burst {(y[m, 1] - y[m, 0]).mean():.0f}')
+                print(f'wave {w} {name}: {int(m.sum())} tiles, epilogue {ep[m].mean():.0f} = asm statement + descriptor {parts[m, 0].mean():.0f} | close {parts[m, 1].mean():.0f};  burst {(y[m, 1] - y[m, 0]).mean():.0f}')
     sys.exit(0)
 print(f'layer {a.layer}: {n} tiles recorded by workgroup 0 (ticks = shader cycles)')
 for w in range(8):

@@ -1,5 +1,5 @@
 """Wall time of whole score-model forwards on FIXED inputs (the SAME 300-residue complex, the SAME 40 poses, four diffusion times), events on the launch
-stream: for A/Bs of the launch structure (tools/build_variant_model.sh), where the conv kernels' own event times say nothing.  DDK_LIB selects the library.
+stream: for A/Bs of the launch structure (another library through DDK_LIB), where the conv kernels' own event times say nothing.  DDK_LIB selects the library.
 
     python tools/forward_time.py [--reps 30] [--pocket]        ms per forward at t = 1.0 / 0.6 / 0.2 / 0.05 and their mean"""
 import argparse, os, sys
