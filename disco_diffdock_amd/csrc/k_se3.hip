@@ -5,6 +5,7 @@
 //   rigid = (pos - centroid) R(rot)^T + tr + centroid
 //   flex  = sequential torsion rotations (in bond order, on already-updated coordinates)
 //   out   = Kabsch-align(flex -> rigid)
+// evaluated on centred coordinates: rigid and flex without "+ tr + centroid", which is added to the aligned pose at the end (same map, see the kernel)
 // The 3x3 SVD of the reference is replaced by Horn's closed form (largest eigenvector of a 4x4 symmetric
 // matrix, Jacobi in fp64 on one lane): same optimal proper rotation, reflection case included.
 #include "model.h"
@@ -18,10 +19,13 @@ __device__ void axis_angle_to_matrix_dev(float ax, float ay, float az, float* R)
   const float half = 0.5f * ang;
   const float s = fabsf(ang) < 1e-6f ? 0.5f - ang * ang / 48.0f : sinf(half) / ang;
   const float qr = cosf(half), qi = ax * s, qj = ay * s, qk = az * s;
-  const float two_s = 2.0f / (qr * qr + qi * qi + qj * qj + qk * qk);
-  R[0] = 1 - two_s * (qj * qj + qk * qk); R[1] = two_s * (qi * qj - qk * qr); R[2] = two_s * (qi * qk + qj * qr);
-  R[3] = two_s * (qi * qj + qk * qr); R[4] = 1 - two_s * (qi * qi + qk * qk); R[5] = two_s * (qj * qk - qi * qr);
-  R[6] = two_s * (qi * qk - qj * qr); R[7] = two_s * (qj * qk + qi * qr); R[8] = 1 - two_s * (qi * qi + qj * qj);
+  // the matrix of the fp32 quaternion assembled in fp64, one rounding per element: in fp32 (three to four roundings per element, as the reference does it)
+  // |R R^T - I| reaches 10 * 2^-24 near a half turn (tests/test_gpu_geometry_adversarial.py), and the rotor loop multiplies such matrices R times per step
+  const double r = qr, i = qi, j = qj, k = qk;
+  const double two_s = 2.0 / (r * r + i * i + j * j + k * k);
+  R[0] = (float)(1 - two_s * (j * j + k * k)); R[1] = (float)(two_s * (i * j - k * r)); R[2] = (float)(two_s * (i * k + j * r));
+  R[3] = (float)(two_s * (i * j + k * r)); R[4] = (float)(1 - two_s * (i * i + k * k)); R[5] = (float)(two_s * (j * k - i * r));
+  R[6] = (float)(two_s * (i * k - j * r)); R[7] = (float)(two_s * (j * k + i * r)); R[8] = (float)(1 - two_s * (i * i + j * j));
 }
 
 // rotation R minimising sum |R a_i - b_i|^2 given S[a][b] = sum a_i[a] b_i[b]  (Horn 1987)
@@ -86,14 +90,27 @@ __device__ void horn_rotation(const double* S, float* R) {
   R[6] = (float)(s2 * (x * z - y * w)); R[7] = (float)(s2 * (y * z + x * w)); R[8] = (float)(1 - s2 * (x * x + y * y));
 }
 
+// Sum of the n points p[3 i + c] per component c in fp64, called by the 64 lanes of the block's first wave: lane t < 48 sums every 16th point of component
+// t % 3, four shuffle steps fold the 16 partial sums, lanes 0..2 return the totals of x, y, z.  fp64 with one rounding at the end because a sequential fp32
+// sum of 256 coordinates near 150 A ends 1e-4 A off, five times the error of the fp32 reference's mean, and the centroid goes into every output atom
+// (tests/test_gpu_geometry_adversarial.py); 16 lanes per component because one lane's chain of n dependent additions was the longest serial piece here.
+__device__ inline double component_sum_wave0(const float* p, int n, int lane) {
+  double s = 0.0;
+  if (lane < 48) {
+    const int c = lane % 3;
+    for (int i = lane / 3; i < n; i += 16) s += (double)p[3 * i + c];
+  }
+  s += __shfl_down(s, 24); s += __shfl_down(s, 12); s += __shfl_down(s, 6); s += __shfl_down(s, 3);
+  return s;
+}
+
 // rigid_transform_Kabsch_3D_torch_batch (utils/geometry.py:126-156) for one point-set pair held in LDS: R, t with R a + t ~ b, proper
 // rotation also in the reflection case.  All threads of the block call it (barriers inside); cA, cB [3], S [9], Rk [9], tk [3] in LDS.
 __device__ void kabsch_block(const float* a, const float* bpts, int n, float* cA, float* cB, double* S, float* Rk, float* tk) {
   const int tid = threadIdx.x;
-  if (tid < 3) {
-    float sa = 0.0f, sb = 0.0f;
-    for (int i = 0; i < n; ++i) { sa += a[3 * i + tid]; sb += bpts[3 * i + tid]; }
-    cA[tid] = sa / (float)n; cB[tid] = sb / (float)n;
+  if (tid < 64) {
+    const double sa = component_sum_wave0(a, n, tid), sb = component_sum_wave0(bpts, n, tid);
+    if (tid < 3) { cA[tid] = (float)(sa / (double)n); cB[tid] = (float)(sb / (double)n); }
   }
   __syncthreads();
   if (tid < 9) {
@@ -220,18 +237,20 @@ __global__ __launch_bounds__(256) void se3_update_kernel(Se3Args A, HeadArgs H) 
     if (A.rec_edges != nullptr && b == 0 && tid < 4) A.rec_edges[tid] = A.info[I_GO + 1 + tid] - A.info[I_GO + tid];
   }
   __syncthreads();
-  if (tid < 3) {
-    float s = 0.0f;
-    for (int i = 0; i < n; ++i) s += rig[3 * i + tid];
-    ctr[tid] = s / (float)n;
+  if (tid < 64) {
+    const double s = component_sum_wave0(rig, n, tid);
+    if (tid < 3) ctr[tid] = (float)(s / (double)n);
   }
-  if (tid == 32) axis_angle_to_matrix_dev(upd[3], upd[4], upd[5], Rm);
+  if (tid == 64) axis_angle_to_matrix_dev(upd[3], upd[4], upd[5], Rm);
   __syncthreads();
   if (tid < n) {
     const float x = rig[3 * tid] - ctr[0], y = rig[3 * tid + 1] - ctr[1], z = rig[3 * tid + 2] - ctr[2];
-    const float rx = Rm[0] * x + Rm[1] * y + Rm[2] * z + upd[0] + ctr[0];
-    const float ry = Rm[3] * x + Rm[4] * y + Rm[5] * z + upd[1] + ctr[1];
-    const float rz = Rm[6] * x + Rm[7] * y + Rm[8] * z + upd[2] + ctr[2];
+    // CENTRED coordinates from here to the last line of the kernel: tr + centroid is added once, to the final pose.  With it added here the rotor
+    // axes (differences of two atoms 1.5 A apart) and every rotated atom carry roundings of the DISTANCE FROM THE ORIGIN, and a chain of rotors amplifies
+    // them by its lever arms: 150 A out a 129-rotor chain ended up to 5e-3 A from fp64 (tests/test_geometry_bound.py), centred it is as exact as at the origin
+    const float rx = Rm[0] * x + Rm[1] * y + Rm[2] * z;
+    const float ry = Rm[3] * x + Rm[4] * y + Rm[5] * z;
+    const float rz = Rm[6] * x + Rm[7] * y + Rm[8] * z;
     // every thread owns its atom: safe to overwrite in place after the barrier above
     rig[3 * tid] = rx; rig[3 * tid + 1] = ry; rig[3 * tid + 2] = rz;
     flx[3 * tid] = rx; flx[3 * tid + 1] = ry; flx[3 * tid + 2] = rz;
@@ -239,8 +258,9 @@ __global__ __launch_bounds__(256) void se3_update_kernel(Se3Args A, HeadArgs H) 
   __syncthreads();
   if (A.tor == nullptr || R == 0) {
     for (int i = tid; i < n * 3; i += 256) {
-      A.pos_out[(size_t)b * n * 3 + i] = rig[i];
-      if constexpr (REC) if (A.rec_pos != nullptr) A.rec_pos[(size_t)b * n * 3 + i] = rig[i];
+      const float v = rig[i] + upd[i % 3] + ctr[i % 3];
+      A.pos_out[(size_t)b * n * 3 + i] = v;
+      if constexpr (REC) if (A.rec_pos != nullptr) A.rec_pos[(size_t)b * n * 3 + i] = v;
     }
     if constexpr (REC)      // no_torsion: the torsion columns of the record's rows are zero
       for (int r = tid; r < R; r += 256) {
@@ -297,9 +317,9 @@ __global__ __launch_bounds__(256) void se3_update_kernel(Se3Args A, HeadArgs H) 
   if (tid < n) {
     const float x = flx[3 * tid], y = flx[3 * tid + 1], z = flx[3 * tid + 2];
     float* o = A.pos_out + ((size_t)b * n + tid) * 3;
-    const float ox = Rk[0] * x + Rk[1] * y + Rk[2] * z + tk[0];
-    const float oy = Rk[3] * x + Rk[4] * y + Rk[5] * z + tk[1];
-    const float oz = Rk[6] * x + Rk[7] * y + Rk[8] * z + tk[2];
+    const float ox = Rk[0] * x + Rk[1] * y + Rk[2] * z + tk[0] + upd[0] + ctr[0];
+    const float oy = Rk[3] * x + Rk[4] * y + Rk[5] * z + tk[1] + upd[1] + ctr[1];
+    const float oz = Rk[6] * x + Rk[7] * y + Rk[8] * z + tk[2] + upd[2] + ctr[2];
     o[0] = ox; o[1] = oy; o[2] = oz;
     if constexpr (REC)
       if (A.rec_pos != nullptr) {
@@ -340,10 +360,9 @@ __global__ __launch_bounds__(256) void randomize_kernel(RandPosArgs A) {
       __syncthreads();
     }
   }
-  if (tid < 3) {
-    float s = 0.0f;
-    for (int i = 0; i < n; ++i) s += p[3 * i + tid];
-    ctr[tid] = s / (float)n;
+  if (tid < 64) {
+    const double s = component_sum_wave0(p, n, tid);
+    if (tid < 3) ctr[tid] = (float)(s / (double)n);
   }
   __syncthreads();
   if (tid < n) {
