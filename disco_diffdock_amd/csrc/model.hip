@@ -1270,17 +1270,29 @@ int ddk_debug_axis_angle(ddk_ctx* ctx, int32_t n, const float* aa, float* R_out,
   return e == hipSuccess ? DDK_OK : hip_fail(ctx, e, "debug axis angle");
 }
 
-// Test hook: copy raw device-side edge arrays of the last forward to host buffers (counts via ddk_last_graph_stats).
-int ddk_debug_read_edges(ddk_ctx* ctx, ddk_complex* cx, int64_t n, int32_t* src, int32_t* dst, float* emb, float* sh, int32_t* deg,
+// Test hook: copy raw device-side edge arrays of the last forward to host buffers: n edges from edge `first` (counts via ddk_last_graph_stats: the
+// four groups are edges [0, E), the shared rec-rec copy of the layer-0 de-duplication [E, E + E_shared), the latent-conditioned model's patch
+// group starts at the edge capacity, out[7]; its per-sample counts via ddk_debug_read_patch)
+int ddk_debug_read_edges(ddk_ctx* ctx, ddk_complex* cx, int64_t first, int64_t n, int32_t* src, int32_t* dst, float* emb, float* sh, int32_t* deg,
                          int64_t n_nodes) {
   if (!ctx || !cx) return DDK_ERR_INVALID;
-  hipDeviceSynchronize();
-  if (src) hipMemcpy(src, cx->e_src, n * 4, hipMemcpyDeviceToHost);
-  if (dst) hipMemcpy(dst, cx->e_dst, n * 4, hipMemcpyDeviceToHost);
-  if (emb) hipMemcpy(emb, cx->e_emb, n * NS * 4, hipMemcpyDeviceToHost);
-  if (sh) hipMemcpy(sh, cx->e_sh, n * 16, hipMemcpyDeviceToHost);
-  if (deg) hipMemcpy(deg, cx->deg, n_nodes * 4, hipMemcpyDeviceToHost);
-  return DDK_OK;
+  const int64_t e_alloc = cx->edge_cap + (cx->patch_off >= 0 ? (int64_t)cx->max_batch * cx->E_rr : 0);
+  if (first < 0 || n < 0 || first + n > e_alloc || n_nodes < 0 || n_nodes > (int64_t)cx->max_batch * (cx->n_lig + cx->n_rec))
+    return fail(ctx, DDK_ERR_INVALID, "ddk_debug_read_edges: range outside the complex' edge / node arrays");
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess && src && n) e = hipMemcpy(src, cx->e_src + first, n * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && dst && n) e = hipMemcpy(dst, cx->e_dst + first, n * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && emb && n) e = hipMemcpy(emb, cx->e_emb + first * NS, n * NS * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && sh && n) e = hipMemcpy(sh, cx->e_sh + first * 4, n * 16, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && deg && n_nodes) e = hipMemcpy(deg, cx->deg, n_nodes * 4, hipMemcpyDeviceToHost);
+  return e == hipSuccess ? DDK_OK : hip_fail(ctx, e, "ddk_debug_read_edges");
+}
+
+// Test hook: 1 when the forwards of `cx` on the current device write the flipped cross edges through the mirror slots (graph_cross_mirror_fits:
+// the pair matrix fits the fill kernel's LDS and DDK_NO_CROSS_MIRROR is not set), 0 when both directions evaluate their own features
+int ddk_debug_cross_mirror(ddk_ctx* ctx, ddk_complex* cx) {
+  if (!ctx || !cx) return DDK_ERR_INVALID;
+  return graph_cross_mirror_fits(cx->n_lig, cx->n_rec) ? 1 : 0;
 }
 
 }  // extern "C"

@@ -507,11 +507,35 @@ class Complex:
         self.ctx._check(self.ctx.L.ddk_last_node_features(self.ctx.h, self.h, B, _ptr(lig), _ptr(rec), _stream()), 'ddk_last_node_features')
         return lig, rec
 
-    def read_edges(self, B):
+    def debug_cross_mirror(self):
+        """test hook: True when this complex' forwards write the rec->lig rows as mirror copies of the lig->rec rows (include/ddk_debug.h)"""
+        rc = self.ctx.L.ddk_debug_cross_mirror(self.ctx.h, self.h)
+        if rc < 0:
+            raise RuntimeError('ddk_debug_cross_mirror failed')
+        return bool(rc)
+
+    def read_edges(self, B, tails=False):
+        """test hook: (graph_stats, src, dst, emb [E, 24], sh [E, 4], deg [B * (n_lig + n_rec)]) of the four edge groups of the last score-model
+        forward.  tails=True appends a dict of the two edge ranges behind them that layer 0 of a de-duplicated forward reads: 'shared' = (src, dst, emb,
+        sh) of the one rec-rec copy in sample 0's numbering, 'patch' = the same for the latent-conditioned model's per-sample patch group, with 'patch_counts'
+        [B + 1] (exclusive prefix per sample) and 'patch_mask' [B, n_rec]; None where the last forward built none."""
         st = self.graph_stats()
         E, N = st['E'], B * (self.n_lig + self.n_rec)
-        src, dst = np.zeros(E, np.int32), np.zeros(E, np.int32)
-        emb, sh, deg = np.zeros((E, 24), np.float32), np.zeros((E, 4), np.float32), np.zeros(N, np.int32)
         p = lambda a: a.ctypes.data_as(C.c_void_p)
-        self.ctx.L.ddk_debug_read_edges(self.ctx.h, self.h, E, p(src), p(dst), p(emb), p(sh), p(deg), N)
-        return st, src, dst, emb, sh, deg
+
+        def rows(first, n, deg=None):
+            src, dst = np.zeros(n, np.int32), np.zeros(n, np.int32)
+            emb, sh = np.zeros((n, 24), np.float32), np.zeros((n, 4), np.float32)
+            self.ctx._check(self.ctx.L.ddk_debug_read_edges(self.ctx.h, self.h, first, n, p(src), p(dst), p(emb), p(sh), None if deg is None else p(deg),
+                                                            0 if deg is None else len(deg)), 'ddk_debug_read_edges')
+            return src, dst, emb, sh
+
+        deg = np.zeros(N, np.int32)
+        out = (st,) + rows(0, E, deg) + (deg,)
+        if not tails:
+            return out
+        tail = dict(shared=rows(E, st['E_shared']) if st['E_shared'] else None, patch=None, patch_counts=None, patch_mask=None)
+        if st['E_shared'] and int(self.ctx.cfg.latent_dim) > 0:
+            cnt, mask = self.debug_read_patch(B)
+            tail.update(patch=rows(st['cap'], int(cnt[B])), patch_counts=cnt, patch_mask=mask)
+        return out + (tail,)

@@ -14,10 +14,16 @@ extern "C" {
  * returns the number of 32-bit words of the item (buf may be NULL to query) or a negative ddk_status. */
 int64_t ddk_debug_export(ddk_ctx* ctx, const char* what, void* buf, int64_t cap_words);
 
-/* Edge arrays of the last score-model forward of `cx` (counts via ddk_last_graph_stats): src/dst [n] int32, emb [n,24],
- * sh [n,4], deg [n_nodes] int32; HOST pointers, any may be NULL. */
-int ddk_debug_read_edges(ddk_ctx* ctx, ddk_complex* cx, int64_t n, int32_t* src, int32_t* dst, float* emb, float* sh, int32_t* deg,
+/* Edge arrays of the last score-model forward of `cx`, n edges from edge `first` (counts via ddk_last_graph_stats: the four groups are edges
+ * [0, out[5]), the shared rec-rec copy of the layer-0 de-duplication the out[4] edges behind them, the patch group of a latent-conditioned model
+ * starts at the edge capacity out[7], ddk_debug_read_patch has its counts): src/dst [n] int32, emb [n,24], sh [n,4], deg [n_nodes] int32;
+ * HOST pointers, any may be NULL.  A range outside the complex' arrays is refused. */
+int ddk_debug_read_edges(ddk_ctx* ctx, ddk_complex* cx, int64_t first, int64_t n, int32_t* src, int32_t* dst, float* emb, float* sh, int32_t* deg,
                          int64_t n_nodes);
+
+/* 1 when the forwards of `cx` write the flipped cross edges (rec->lig) as copies of the lig->rec rows through mirror slots, 0 when both directions
+ * evaluate their own features (the pair matrix does not fit the LDS, or the environment variable DDK_NO_CROSS_MIRROR is set); < 0: a ddk_status. */
+int ddk_debug_cross_mirror(ddk_ctx* ctx, ddk_complex* cx);
 
 /* Confidence model (conf.hip), last ddk_confidence_forward of `cx`:
  *   counts: out[0..8] = edges of the nine groups [ll lr la aa al ar rr rl ra], out[9] = ligand-atom edge capacity overflow flag;
