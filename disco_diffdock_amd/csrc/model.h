@@ -284,6 +284,14 @@ hipError_t launch_debug_kabsch(const float* A, const float* Bp, int B, int n, fl
 hipError_t launch_debug_axis_angle(const float* aa, int n, float* R_out, hipStream_t s);
 hipError_t launch_pose_metrics(const float* pos, const float* ref, const uint8_t* mask, const int32_t* perms, int n_perms, const float* rec_pos,
                                int B, int n_lig, int n_rec, float* out, hipStream_t s);
+// k_pairs.hip: the pairwise RMSD matrix and the clustering on it (ddk_pose_pairwise_rmsd, ddk_pose_cluster)
+constexpr int PAIRS_TJ = 8;            // partner poses j per workgroup of pose_pairs_kernel
+constexpr int PAIRS_WAVES = 16;        // its waves = the permutation rows of one pass
+constexpr int PAIRS_MAX_B = 4096;
+constexpr int CLUSTER_MAX_B = 1024;    // pose_cluster_kernel is one workgroup, one thread per sample
+hipError_t launch_pose_pairs(const float* pos, const uint8_t* mask, const int32_t* perms, int n_perms, int B, int n_lig, float* out, hipStream_t s);
+hipError_t launch_pose_cluster(const float* rmsd, const float* score, float cutoff, int B, int32_t* cluster, int32_t* leaders, int32_t* n_clusters,
+                               hipStream_t s);
 
 int conf_model_finalize(ddk_ctx* ctx);   // conf.hip (all-atom confidence model)
 void conf_complex_free(ddk_complex* cx);

@@ -991,6 +991,30 @@ int ddk_pose_metrics(ddk_ctx* ctx, ddk_complex* cx, int32_t B, const float* pos,
   return DDK_OK;
 }
 
+int ddk_pose_pairwise_rmsd(ddk_ctx* ctx, int32_t B, int32_t n_lig, const float* pos, const uint8_t* atom_mask, const int32_t* perms, int32_t n_perms,
+                           float* out, void* stream) {
+  if (!ctx) return DDK_ERR_INVALID;
+  if (ctx->host_only) return fail(ctx, DDK_ERR_STATE, "host-only context (device < 0) cannot launch kernels");
+  if (B < 1 || B > PAIRS_MAX_B) return fail(ctx, DDK_ERR_INVALID, "ddk_pose_pairwise_rmsd: B must be in [1, " + std::to_string(PAIRS_MAX_B) + "]");
+  if (n_lig < 1 || n_lig > MAX_LIG) return fail(ctx, DDK_ERR_INVALID, "ddk_pose_pairwise_rmsd: n_lig must be in [1, " + std::to_string(MAX_LIG) + "]");
+  if (!pos || !out) return fail(ctx, DDK_ERR_INVALID, "ddk_pose_pairwise_rmsd: null argument");
+  if ((perms != nullptr) != (n_perms > 0)) return fail(ctx, DDK_ERR_INVALID, "ddk_pose_pairwise_rmsd: perms / n_perms come in a pair");
+  hipError_t e = launch_pose_pairs(pos, atom_mask, perms, n_perms, B, n_lig, out, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "pose_pairs launch");
+  return DDK_OK;
+}
+
+int ddk_pose_cluster(ddk_ctx* ctx, int32_t B, const float* rmsd, const float* score, float cutoff, int32_t* cluster, int32_t* leaders,
+                     int32_t* n_clusters, void* stream) {
+  if (!ctx) return DDK_ERR_INVALID;
+  if (ctx->host_only) return fail(ctx, DDK_ERR_STATE, "host-only context (device < 0) cannot launch kernels");
+  if (B < 1 || B > CLUSTER_MAX_B) return fail(ctx, DDK_ERR_INVALID, "ddk_pose_cluster: B must be in [1, " + std::to_string(CLUSTER_MAX_B) + "]");
+  if (!rmsd || !cluster || !leaders || !n_clusters) return fail(ctx, DDK_ERR_INVALID, "ddk_pose_cluster: null argument");
+  hipError_t e = launch_pose_cluster(rmsd, score, cutoff, B, cluster, leaders, n_clusters, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "pose_cluster launch");
+  return DDK_OK;
+}
+
 }  // extern "C"
 
 // ddk_sample / ddk_sample_trajectory (`what` names the entry point in messages).  rec: the caller's record arrays, every member may be null; the record is

@@ -31,6 +31,12 @@ CONF_STATUS_INTS, CONF_OVERFLOW_WORD = 20, 19
 TRAJECTORY_FIELDS = ('pos', 'scores', 'perturb', 'edge_counts')
 Trajectory = collections.namedtuple('Trajectory', TRAJECTORY_FIELDS)
 
+# what ``Context.cluster_poses`` returns, all device tensors (ddk_pose_pairwise_rmsd + ddk_pose_cluster, include/ddk.h): rmsd [B, B] float32; int32 cluster [B]
+# (ordinal per pose, 0 = the cluster of the top-scored pose), leaders [B] (pose index per cluster, -1 after the first n_clusters entries), n_clusters [1]
+PoseClusters = collections.namedtuple('PoseClusters', ('rmsd', 'cluster', 'leaders', 'n_clusters'))
+# the limits of the two calls (csrc/model.h) and the tile shape of pose_pairs_kernel (tests place their shapes on its edges)
+PAIRS_MAX_B, CLUSTER_MAX_B, PAIRS_TJ, PAIRS_ROWS_PER_PASS = 4096, 1024, 8, 16
+
 
 def config_from_args(args, device=0):
     """model_parameters.yml Namespace -> ddk_config fields, the mapping of get_model
@@ -222,6 +228,53 @@ class Context:
         self._check(self.L.ddk_conv_forward(self.h, layer, _ptr(x), N, _ptr(edge_src), _ptr(edge_dst), go, _ptr(edge_attr),
                                             _ptr(sh), _ptr(out), _stream()), 'ddk_conv_forward')
         return out
+
+    # ---- poses -> distinct modes (no complex is involved: poses from any source) ----------------
+    def pairwise_rmsd(self, pos, atom_mask=None, perms=None):
+        """All-pairs symmetry-corrected RMSD of the poses pos [B, n_lig, 3] (device) in their common frame, no alignment: tensor [B, B], symmetric
+        with a zero diagonal.  atom_mask [n_lig]: the atoms that count (filterHs, evaluate.py:297); perms [K, n_lig] (int): the ligand's graph
+        automorphisms, the table of Complex.pose_metrics (None: identity only).  A host table is checked here; a device table is passed as it is (the
+        kernel gives a row with an entry outside the ligand +inf).  Nothing is read back."""
+        pos = _need_cuda(pos)
+        if pos.dim() != 3 or pos.shape[2] != 3:
+            raise RuntimeError('ddk: pairwise_rmsd takes poses [B, n_lig, 3]; got ' + str(tuple(pos.shape)))
+        pos = pos.contiguous().float()
+        B, n_lig = pos.shape[0], pos.shape[1]
+        m = None
+        if atom_mask is not None:
+            m = h2d_async(torch.as_tensor(atom_mask).reshape(-1).ne(0).to(torch.uint8).contiguous(), pos.device)
+            if m.shape[0] != n_lig:
+                raise RuntimeError(f'ddk: atom_mask has {m.shape[0]} entries for {n_lig} ligand atoms')
+        pm = None
+        if perms is not None:
+            pm = torch.as_tensor(perms)
+            if pm.dim() != 2 or pm.shape[0] < 1 or pm.shape[1] != n_lig:
+                raise RuntimeError(f'ddk: the permutation table must be [K >= 1, {n_lig}]; got ' + str(tuple(pm.shape)))
+            if not pm.is_cuda and (int(pm.min()) < 0 or int(pm.max()) >= n_lig):
+                raise RuntimeError('ddk: permutation table entries must be ligand atom indices')
+            pm = h2d_async(pm.to(torch.int32).contiguous(), pos.device)
+        out = torch.empty((B, B), dtype=torch.float32, device=pos.device)
+        self._check(self.L.ddk_pose_pairwise_rmsd(self.h, B, n_lig, _ptr(pos), _ptr(m), _ptr(pm), 0 if pm is None else pm.shape[0], _ptr(out), _stream()),
+                    'ddk_pose_pairwise_rmsd')
+        return out
+
+    def cluster_poses(self, pos, scores=None, cutoff=2.0, atom_mask=None, perms=None):
+        """Which of the poses pos [B, n_lig, 3] are the same binding mode: pairwise_rmsd, then greedy leader clustering by score on the device
+        (scores [B], higher is better, None: index order; ties go to the lower index, NaN ranks last): the best-scored unassigned pose leads the next
+        cluster and every unassigned pose within `cutoff` of it joins.  Returns PoseClusters(rmsd, cluster, leaders, n_clusters), device tensors;
+        nothing is read back.  B <= 1024."""
+        rmsd = self.pairwise_rmsd(pos, atom_mask=atom_mask, perms=perms)
+        B, dev = rmsd.shape[0], rmsd.device
+        sc = None
+        if scores is not None:
+            sc = _need_cuda(scores).to(dev).float().reshape(-1).contiguous()
+            if sc.shape[0] != B:
+                raise RuntimeError(f'ddk: {sc.shape[0]} scores for {B} poses')
+        cluster, leaders = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)
+        n = torch.empty(1, dtype=torch.int32, device=dev)
+        self._check(self.L.ddk_pose_cluster(self.h, B, _ptr(rmsd), _ptr(sc), float(cutoff), _ptr(cluster), _ptr(leaders), _ptr(n), _stream()),
+                    'ddk_pose_cluster')
+        return PoseClusters(rmsd, cluster, leaders, n)
 
 
 class Complex:

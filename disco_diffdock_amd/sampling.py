@@ -388,3 +388,28 @@ def sampling(data_list, model, inference_steps, tr_schedule, rot_schedule, tor_s
     if confidence_model is not None:          # utils/sampling.py:245-247
         confidence = torch.nan_to_num(torch.cat(confidence, dim=0), nan=-1000)
     return data_list, confidence
+
+
+def cluster_poses(data_list, confidence=None, cutoff=2.0, perms=None, heavy_atoms_only=True, ctx=None):
+    """The step every consumer of sampling()'s poses takes next: which of them are the same binding mode.  ``data_list``: the graphs sampling()
+    returned (poses of ONE ligand, on the device, in the common receptor frame); ``confidence``: its second result, [B] or [B, k] (column 0 ranks, as in
+    evaluate.py:317-318), None: list order.  All-pairs RMSD over the heavy atoms (``heavy_atoms_only``: the filterHs mask of evaluate.py:297,
+    ``x[:, 0] != 0``), symmetry-corrected when ``perms`` [K, n_lig] holds the ligand's graph automorphisms, then greedy leader clustering
+    by confidence within ``cutoff`` A.  Returns :data:`runtime.PoseClusters` (rmsd [B, B], cluster [B], leaders [B], n_clusters [1]), device tensors: like
+    sampling() itself this enqueues and reads nothing back.  ``ctx``: a runtime.Context or a model that owns one (default: a weightless context on the
+    poses' device)."""
+    lig0 = data_list[0]['ligand']
+    pos = torch.stack([d['ligand'].pos for d in data_list])
+    if not pos.is_cuda:
+        raise RuntimeError('ddk: cluster_poses takes the device poses sampling() returned (no CPU path exists)')
+    ctx = getattr(ctx, 'ctx', ctx)
+    if ctx is None:
+        from .tensor_layers import _shape_context
+        ctx = _shape_context(pos.device.index if pos.device.index is not None else torch.cuda.current_device())
+    mask = (lig0.x[:, 0] != 0) if heavy_atoms_only else None
+    if confidence is not None:
+        confidence = torch.as_tensor(confidence)
+        if confidence.dim() > 1:
+            confidence = confidence[:, 0]
+        confidence = h2d_async(confidence.float(), pos.device)
+    return ctx.cluster_poses(pos, scores=confidence, cutoff=cutoff, atom_mask=mask, perms=perms)

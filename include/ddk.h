@@ -258,6 +258,31 @@ int ddk_randomize_position(ddk_ctx* ctx, ddk_complex* cx, int32_t B, const float
 int ddk_pose_metrics(ddk_ctx* ctx, ddk_complex* cx, int32_t B, const float* pos, const float* ref_pos, const uint8_t* atom_mask,
                      const int32_t* perms, int32_t n_perms, const float* rec_atom_pos, int32_t n_rec_atoms, float* out, void* stream);
 
+/* ---- poses in -> distinct binding modes out, without a ground truth: the all-pairs form of the RMSD above and a clustering on it.
+ *      Neither call takes a ddk_complex: nothing of a complex is read, so poses from any source can be clustered.  Neither synchronises or allocates.
+ *
+ *      ddk_pose_pairwise_rmsd: pos [B, n_lig, 3] -> out [B, B] fp32 (all DEVICE), one launch:
+ *        out[i][i] = 0;  for i < j:  out[i][j] = out[j][i] = min over k < n_perms of sqrt((1/m) sum over kept a of |pos_i[perms[k][a]] - pos_j[a]|^2)
+ *      The lower-indexed pose is the permuted one: ddk_pose_metrics' convention with pose j as ref.  Only i < j is computed and the value is
+ *      stored twice, so the matrix is symmetric bit for bit.  No alignment: the poses share the receptor frame (evaluate.py:313).
+ *      atom_mask [n_lig] uint8 (NULL = all atoms), m = the number of kept atoms; m = 0 gives a matrix of zeros.  perms [n_perms, n_lig] int32 is
+ *      ddk_pose_metrics' automorphism table (perms = NULL, n_perms = 0: identity only; entries of masked-out atoms are ignored; a row with a kept
+ *      entry outside [0, n_lig) is detected on the device and never wins the minimum; if no row is valid the off-diagonal entries are +inf,
+ *      never NaN).  Coordinate differences are taken first and then squared (exact 150 A from the origin where |a|^2 + |b|^2 - 2ab cancels),
+ *      summed in fp32, one sqrt per pair after the minimum; no float atomics: bit-identical run to run.
+ *      Limits: 1 <= n_lig <= 256, 1 <= B <= 4096; anything else is DDK_ERR_INVALID.
+ *
+ *      ddk_pose_cluster: greedy leader clustering on such a matrix rmsd [B, B], 1 <= B <= 1024 (one workgroup):
+ *        rank the samples by score [B] descending (ties to the lower index; NaN ranks below -inf, NaNs among themselves by index;
+ *        score = NULL: index order); walk the ranking: an unassigned sample becomes the next leader, and every unassigned sample c with
+ *        rmsd[leader][c] <= cutoff joins it.  An entry equal to the cutoff joins; an inf (or NaN) entry never joins, under cutoff = inf too.
+ *      Outputs, int32 DEVICE arrays: cluster [B] the cluster ordinal of each sample in discovery order (0 = the cluster of the top-scored
+ *      pose); leaders [B] the leader's sample index of each cluster in its first n_clusters entries, -1 after them; n_clusters [1]. */
+int ddk_pose_pairwise_rmsd(ddk_ctx* ctx, int32_t B, int32_t n_lig, const float* pos, const uint8_t* atom_mask,
+                           const int32_t* perms, int32_t n_perms, float* out, void* stream);
+int ddk_pose_cluster(ddk_ctx* ctx, int32_t B, const float* rmsd, const float* score, float cutoff,
+                     int32_t* cluster, int32_t* leaders, int32_t* n_clusters, void* stream);
+
 /* ---- a1-a2: the reverse-diffusion loop of sampling()  utils/sampling.py:105-198 for one batch:
  *      per step  perturb = score_coeff*score + noise_coeff*z  (coefficients are the host scalars of
  *      sampling.py:137-192, including the low-temperature variant), then ddk_se3_update.
