@@ -292,6 +292,16 @@ constexpr int CLUSTER_MAX_B = 1024;    // pose_cluster_kernel is one workgroup, 
 hipError_t launch_pose_pairs(const float* pos, const uint8_t* mask, const int32_t* perms, int n_perms, int B, int n_lig, float* out, hipStream_t s);
 hipError_t launch_pose_cluster(const float* rmsd, const float* score, float cutoff, int B, int32_t* cluster, int32_t* leaders, int32_t* n_clusters,
                                hipStream_t s);
+// k_autos.hip: the ligand's graph automorphisms, the table the three calls above read (ddk_ligand_automorphisms)
+constexpr int AUTOS_MAX_CAP = 1 << 20;           // rows of perms_out and of a frontier
+constexpr int AUTOS_WALK_THREADS = 1024;         // autos_walk_kernel: one workgroup
+constexpr int AUTOS_WALK_ITEMS = 1024;           // it walks a level of at most this many (row, candidate) items, one per thread; a larger one goes to the launch pairs
+constexpr int AUTOS_WALK_ONLY_ITEMS = 16384;     // cap * n_lig up to this: no level can be larger, the walk does them all and no pair is enqueued
+constexpr int AUTOS_CHUNK = 256;                 // items per workgroup pass of autos_count_kernel / autos_write_kernel = their workgroup size
+constexpr int AUTOS_GRID = 1024;                 // their fixed grid (the frontier sizes are not known on the host)
+int64_t autos_workspace_bytes(int n_lig, int cap);
+hipError_t launch_ligand_automorphisms(int n_lig, const int32_t* colour, const int32_t* bond_index, int n_bond_edges, const uint8_t* atom_mask,
+                                       int32_t* perms_out, int cap, int32_t* count_out, void* workspace, hipStream_t s);
 
 int conf_model_finalize(ddk_ctx* ctx);   // conf.hip (all-atom confidence model)
 void conf_complex_free(ddk_complex* cx);

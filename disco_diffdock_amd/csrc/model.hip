@@ -1015,6 +1015,25 @@ int ddk_pose_cluster(ddk_ctx* ctx, int32_t B, const float* rmsd, const float* sc
   return DDK_OK;
 }
 
+int64_t ddk_ligand_automorphisms_workspace(int32_t n_lig, int32_t cap) {
+  if (n_lig < 1 || n_lig > MAX_LIG || cap < 1 || cap > AUTOS_MAX_CAP) return -1;
+  return autos_workspace_bytes(n_lig, cap);
+}
+
+int ddk_ligand_automorphisms(ddk_ctx* ctx, int32_t n_lig, const int32_t* colour, const int32_t* bond_index, int32_t n_bond_edges, const uint8_t* atom_mask,
+                             int32_t* perms_out, int32_t cap, int32_t* count_out, void* workspace, void* stream) {
+  if (!ctx) return DDK_ERR_INVALID;
+  if (ctx->host_only) return fail(ctx, DDK_ERR_STATE, "host-only context (device < 0) cannot launch kernels");
+  if (n_lig < 1 || n_lig > MAX_LIG) return fail(ctx, DDK_ERR_INVALID, "ddk_ligand_automorphisms: n_lig must be in [1, " + std::to_string(MAX_LIG) + "]");
+  if (cap < 1 || cap > AUTOS_MAX_CAP) return fail(ctx, DDK_ERR_INVALID, "ddk_ligand_automorphisms: cap must be in [1, " + std::to_string(AUTOS_MAX_CAP) + "]");
+  if (n_bond_edges < 0) return fail(ctx, DDK_ERR_INVALID, "ddk_ligand_automorphisms: n_bond_edges must be >= 0");
+  if (!colour || !perms_out || !count_out || !workspace || (!bond_index && n_bond_edges > 0))
+    return fail(ctx, DDK_ERR_INVALID, "ddk_ligand_automorphisms: null argument (only atom_mask, and bond_index with n_bond_edges = 0, may be null)");
+  hipError_t e = launch_ligand_automorphisms(n_lig, colour, bond_index, n_bond_edges, atom_mask, perms_out, cap, count_out, workspace, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "ligand_automorphisms launch");
+  return DDK_OK;
+}
+
 }  // extern "C"
 
 // ddk_sample / ddk_sample_trajectory (`what` names the entry point in messages).  rec: the caller's record arrays, every member may be null; the record is

@@ -3,6 +3,7 @@ PyTorch is used only for device memory and streams; all compute happens in libdd
 import collections
 import ctypes as C
 import os
+import warnings
 from types import SimpleNamespace
 
 import numpy as np
@@ -36,6 +37,21 @@ Trajectory = collections.namedtuple('Trajectory', TRAJECTORY_FIELDS)
 PoseClusters = collections.namedtuple('PoseClusters', ('rmsd', 'cluster', 'leaders', 'n_clusters'))
 # the limits of the two calls (csrc/model.h) and the tile shape of pose_pairs_kernel (tests place their shapes on its edges)
 PAIRS_MAX_B, CLUSTER_MAX_B, PAIRS_TJ, PAIRS_ROWS_PER_PASS = 4096, 1024, 8, 16
+# ddk_ligand_automorphisms (csrc/k_autos.hip): the largest table, the words of its status, and the sizes at which the search changes its path (csrc/model.h):
+# cap * n_lig <= AUTOS_WALK_ONLY_ITEMS is one workgroup's walk alone; beyond it a level of more than AUTOS_WALK_ITEMS (row, candidate) items takes a pair
+# of launches over workgroups of AUTOS_CHUNK items
+AUTOS_MAX_CAP, AUTOS_WALK_ITEMS, AUTOS_WALK_ONLY_ITEMS, AUTOS_CHUNK = 1 << 20, 1024, 16384, 256
+AUTOS_STATUS = ('complete', 'overflow: a level of the search held more partial maps than cap', 'a bond index outside the ligand')
+
+
+def usable_automorphisms(perms, count, name=None):
+    """(perms, count) of ``Context.ligand_automorphisms`` -> the rows a consumer may read, perms[:count[0]].  The consumers take the row count as a
+    host integer, so this is ONE read-back of ``count`` (8 bytes; the same kind ``PoseClusters.n_clusters`` asks of its reader).  With status 1 or 2 that
+    is the identity alone, the uncorrected fallback of evaluate.py:313, and a warning names the ligand and the status."""
+    rows, status = (int(v) for v in count.tolist())
+    if status != 0:
+        warnings.warn(f'ddk: no automorphism table for ligand {name!r} (status {status}: {AUTOS_STATUS[status]}); its RMSDs are not symmetry-corrected')
+    return perms[:rows]
 
 
 def config_from_args(args, device=0):
@@ -276,6 +292,36 @@ class Context:
                     'ddk_pose_cluster')
         return PoseClusters(rmsd, cluster, leaders, n)
 
+    def ligand_automorphisms(self, colour, bond_index, atom_mask=None, cap=65536):
+        """The automorphism table that pairwise_rmsd, cluster_poses and Complex.pose_metrics take as ``perms``, enumerated on the device
+        (ddk_ligand_automorphisms, include/ddk.h): every bijection of the kept atoms that keeps ``colour`` [n_lig] (int) and the bonds
+        ``bond_index`` [2, E] (either or both directions, duplicates allowed).  ``atom_mask`` [n_lig]: the kept atoms (None: all); masked-out atoms
+        map to themselves.  Returns (perms, count), device tensors: perms is the whole [cap, n_lig] int32 buffer, of which the first count[0] rows are
+        written (row 0 the identity); count [2] int32 = (rows, status), status 0 complete, 1 overflow (the search held more than ``cap`` partial maps
+        at some level), 2 a bond index outside the ligand; with 1 or 2 the identity is the only row.  Nothing is read back: see usable_automorphisms.
+        n_lig <= 256, cap <= 2^20; the call holds about 2 * cap * n_lig bytes of workspace while it runs."""
+        dev = torch.device('cuda', self.device)
+        col = h2d_async(torch.as_tensor(colour).reshape(-1).to(torch.int32).contiguous(), dev)
+        n_lig, cap = col.shape[0], int(cap)
+        bi = torch.as_tensor(bond_index)
+        if bi.numel() and (bi.dim() != 2 or bi.shape[0] != 2):
+            raise RuntimeError('ddk: bond_index must be [2, E]; got ' + str(tuple(bi.shape)))
+        E = bi.numel() // 2
+        bi = h2d_async(bi.to(torch.int32).contiguous(), dev) if E else None
+        m = None
+        if atom_mask is not None:
+            m = h2d_async(torch.as_tensor(atom_mask).reshape(-1).ne(0).to(torch.uint8).contiguous(), dev)
+            if m.shape[0] != n_lig:
+                raise RuntimeError(f'ddk: atom_mask has {m.shape[0]} entries for {n_lig} ligand atoms')
+        nbytes = self.L.ddk_ligand_automorphisms_workspace(n_lig, cap)
+        ok = nbytes >= 0      # a broken limit: the call below says which
+        perms = torch.empty((cap, n_lig) if ok else (1, 1), dtype=torch.int32, device=dev)
+        count = torch.empty(2, dtype=torch.int32, device=dev)
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        self._check(self.L.ddk_ligand_automorphisms(self.h, n_lig, _ptr(col), _ptr(bi), E, _ptr(m), _ptr(perms), cap, _ptr(count), _ptr(ws), _stream()),
+                    'ddk_ligand_automorphisms')
+        return perms, count
+
 
 class Complex:
     """Device-resident static data of one complex (ddk_complex): topology, receptor embedding without its
@@ -294,6 +340,8 @@ class Complex:
         self.n_lig, self.n_rec = a['lig_x'].shape[0], a['rec_pos'].shape[0]
         self.M, self.R, self.E_rr = a['bond_index'].shape[1], a['mask_rotate'].shape[0], a['rec_edge_index'].shape[1]
         self.max_batch = max_batch
+        self.name = c.get('name') if hasattr(c, 'get') else None
+        self._autos = {}
         d = _lib.ddk_complex_desc(n_lig=self.n_lig, n_rec=self.n_rec, n_bond_edges=self.M, n_rot=self.R, n_rec_edges=self.E_rr,
                                   rec_feat_dim=a['rec_x'].shape[1],
                                   **{k: v.ctypes.data_as(C.c_void_p) for k, v in a.items()})
@@ -462,10 +510,28 @@ class Complex:
         self.ctx._check(self.ctx.L.ddk_last_node_features(self.ctx.h, self.h, B, _ptr(lig), None, _stream()), 'ddk_last_node_features')
         return lig
 
-    def pose_metrics(self, pos, ref_pos, atom_mask=None, perms=None, rec_atom_pos=None):
+    def automorphisms(self, atom_mask=None, cap=65536):
+        """This ligand's automorphism table from its own data (Context.ligand_automorphisms): colour = lig_x[:, 0], the bonds = bond_index,
+        ``atom_mask`` [n_lig] the kept atoms, by default the heavy atoms lig_x[:, 0] != 0 (filterHs, evaluate.py:297).  Returns (perms [cap, n_lig],
+        count [2]) on the device, cached per (mask, cap); nothing is read back.  lig_x[:, 0] is the reference's atomic-number INDEX, whose last bucket
+        is 'misc': two different exotic elements in that bucket compare equal here, where spyrmsd compares true atomic numbers."""
+        colour = self.arr['lig_x'][:, 0]
+        mask = (colour != 0) if atom_mask is None else torch.as_tensor(atom_mask).reshape(-1).ne(0).cpu().numpy()
+        key = (mask.tobytes(), int(cap))
+        if key not in self._autos:
+            self._autos[key] = self.ctx.ligand_automorphisms(colour, self.arr['bond_index'], atom_mask=mask, cap=cap)
+        return self._autos[key]
+
+    def pose_metrics(self, pos, ref_pos, atom_mask=None, perms=None, rec_atom_pos=None, auto_cap=65536):
         """evaluate.py:297-338 for B poses: tensor [B,4] = rmsd, centroid distance, min cross distance, min self distance.
         perms [K, n_lig] (int): graph automorphisms of the ligand -> symmetry-corrected RMSD (evaluate.py:308-310); None: uncorrected
-        (:313).  rec_atom_pos [n, 3]: receptor atom coordinates for the cross distance (default: the C-alpha coordinates)."""
+        (:313); 'auto': self.automorphisms(cap=auto_cap) over the atoms this call counts (atom_mask; all atoms if it is None), at the price of one
+        read-back of its row count (usable_automorphisms; the identity alone and a warning if the table did not fit).
+        rec_atom_pos [n, 3]: receptor atom coordinates for the cross distance (default: the C-alpha coordinates)."""
+        if isinstance(perms, str):
+            if perms != 'auto':
+                raise RuntimeError(f"ddk: perms is a table, None or 'auto'; got {perms!r}")
+            perms = usable_automorphisms(*self.automorphisms(np.ones(self.n_lig, bool) if atom_mask is None else atom_mask, cap=auto_cap), name=self.name)
         pos = pos.contiguous().float().reshape(-1, self.n_lig, 3)
         ref = ref_pos.contiguous().float().reshape(self.n_lig, 3).to(pos.device)
         m = None if atom_mask is None else atom_mask.to(pos.device).to(torch.uint8).contiguous()

@@ -390,12 +390,14 @@ def sampling(data_list, model, inference_steps, tr_schedule, rot_schedule, tor_s
     return data_list, confidence
 
 
-def cluster_poses(data_list, confidence=None, cutoff=2.0, perms=None, heavy_atoms_only=True, ctx=None):
+def cluster_poses(data_list, confidence=None, cutoff=2.0, perms=None, heavy_atoms_only=True, ctx=None, auto_cap=65536):
     """The step every consumer of sampling()'s poses takes next: which of them are the same binding mode.  ``data_list``: the graphs sampling()
     returned (poses of ONE ligand, on the device, in the common receptor frame); ``confidence``: its second result, [B] or [B, k] (column 0 ranks, as in
     evaluate.py:317-318), None: list order.  All-pairs RMSD over the heavy atoms (``heavy_atoms_only``: the filterHs mask of evaluate.py:297,
     ``x[:, 0] != 0``), symmetry-corrected when ``perms`` [K, n_lig] holds the ligand's graph automorphisms, then greedy leader clustering
-    by confidence within ``cutoff`` A.  Returns :data:`runtime.PoseClusters` (rmsd [B, B], cluster [B], leaders [B], n_clusters [1]), device tensors: like
+    by confidence within ``cutoff`` A.  ``perms='auto'``: the table is enumerated on the device from the first graph's own ``x[:, 0]`` and bonds over the
+    same atoms (runtime.Context.ligand_automorphisms, at most ``auto_cap`` rows); that costs one read-back of its row count, and a ligand whose table does
+    not fit is clustered uncorrected, with a warning.  Returns :data:`runtime.PoseClusters` (rmsd [B, B], cluster [B], leaders [B], n_clusters [1]), device tensors: like
     sampling() itself this enqueues and reads nothing back.  ``ctx``: a runtime.Context or a model that owns one (default: a weightless context on the
     poses' device)."""
     lig0 = data_list[0]['ligand']
@@ -412,4 +414,10 @@ def cluster_poses(data_list, confidence=None, cutoff=2.0, perms=None, heavy_atom
         if confidence.dim() > 1:
             confidence = confidence[:, 0]
         confidence = h2d_async(confidence.float(), pos.device)
+    if isinstance(perms, str):
+        if perms != 'auto':
+            raise RuntimeError(f"ddk: perms is a table, None or 'auto'; got {perms!r}")
+        from .runtime import usable_automorphisms
+        table = ctx.ligand_automorphisms(lig0.x[:, 0], data_list[0]['ligand', 'lig_bond', 'ligand'].edge_index, atom_mask=mask, cap=auto_cap)
+        perms = usable_automorphisms(*table, name=getattr(data_list[0], 'name', None))
     return ctx.cluster_poses(pos, scores=confidence, cutoff=cutoff, atom_mask=mask, perms=perms)

@@ -283,6 +283,30 @@ int ddk_pose_pairwise_rmsd(ddk_ctx* ctx, int32_t B, int32_t n_lig, const float* 
 int ddk_pose_cluster(ddk_ctx* ctx, int32_t B, const float* rmsd, const float* score, float cutoff,
                      int32_t* cluster, int32_t* leaders, int32_t* n_clusters, void* stream);
 
+/* ---- the automorphism table the three calls above read, enumerated on the device: every colour- and bond-preserving bijection of the ligand's kept
+ *      atoms.  The reference gets it from spyrmsd under time_limit(10) (utils/utils.py:84-98) and falls back to the uncorrected RMSD when that raises
+ *      (evaluate.py:308-313), which is what happens to the ligands with the largest symmetry groups.  Like the two calls above this one takes no
+ *      ddk_complex, allocates nothing and does not synchronise; all pointers are DEVICE pointers.
+ *        colour [n_lig] int32: atoms may map to atoms of the same colour only (the element index, column 0 of lig_x).
+ *        bond_index [2, n_bond_edges] int32: covalent bonds; duplicate columns and the two directions of a bond are one edge, a column with two equal
+ *               ends is ignored.  NULL only with n_bond_edges = 0.
+ *        atom_mask [n_lig] uint8 (NULL = all atoms): the kept atoms.  Masked-out atoms and their bonds are not part of the graph (remove_all_hs).
+ *        perms_out [cap, n_lig] int32: row k maps a kept atom a to its image and a masked-out atom to itself: ddk_pose_metrics' table.  Row 0 is the
+ *               identity.  The rows come in a fixed order (a breadth-first matching order, images ascending): bit-identical run to run.
+ *        count_out [2] int32: [0] the rows written (>= 1), [1] the status: 0 complete; 1 overflow: some level of the search held more than cap
+ *               partial maps (never fewer than the K automorphisms; cap = 2 K is enough for every graph in tests/automorphism_ref.py); 2 a bond index
+ *               outside [0, n_lig), found on the device before it is used as an address.  With status 1 or 2 the identity is the only row (the
+ *               uncorrected fallback, as in the reference) and nothing past it is written.  Overflow is a result, not an error: the call returns DDK_OK.
+ *        workspace: ddk_ligand_automorphisms_workspace(n_lig, cap) bytes of device memory, 16-byte aligned, contents irrelevant before and after
+ *               (about 2 * cap * n_lig bytes; a host function, no context; -1 if a limit is broken).
+ *      The search is level-synchronous over partial maps (csrc/k_autos.hip): one workgroup walks the levels while they are small, larger levels take a
+ *      pair of launches each over a fixed grid; the host enqueues 2 * n_lig launches without knowing the frontier sizes, which stay on the device.
+ *      Limits: 1 <= n_lig <= 256, n_bond_edges >= 0, 1 <= cap <= 2^20; anything else is DDK_ERR_INVALID. */
+int64_t ddk_ligand_automorphisms_workspace(int32_t n_lig, int32_t cap);
+int ddk_ligand_automorphisms(ddk_ctx* ctx, int32_t n_lig, const int32_t* colour, const int32_t* bond_index, int32_t n_bond_edges,
+                             const uint8_t* atom_mask, int32_t* perms_out, int32_t cap, int32_t* count_out /* [2] */,
+                             void* workspace, void* stream);
+
 /* ---- a1-a2: the reverse-diffusion loop of sampling()  utils/sampling.py:105-198 for one batch:
  *      per step  perturb = score_coeff*score + noise_coeff*z  (coefficients are the host scalars of
  *      sampling.py:137-192, including the low-temperature variant), then ddk_se3_update.
