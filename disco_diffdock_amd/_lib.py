@@ -48,7 +48,9 @@ SYMBOLS = ['ddk_create', 'ddk_destroy', 'ddk_last_error', 'ddk_version', 'ddk_lo
            'ddk_set_keep_receptor_features', 'ddk_randomize_position', 'ddk_complex_set_atoms',
            'ddk_confidence_forward', 'ddk_score_confidence', 'ddk_pose_metrics', 'ddk_build_graph', 'ddk_set_receptive_field_pruning', 'ddk_ar_logits', 'ddk_ar_decode', 'ddk_confidence_status',
            'ddk_sample_trajectory', 'ddk_pose_pairwise_rmsd', 'ddk_pose_cluster',
-           'ddk_ligand_automorphisms_workspace', 'ddk_ligand_automorphisms']
+           'ddk_ligand_automorphisms_workspace', 'ddk_ligand_automorphisms',
+           'ddk_receptor_knn_graph_workspace', 'ddk_receptor_knn_graph', 'ddk_radius_graph_workspace', 'ddk_radius_graph',
+           'ddk_ligand_transformation_mask_workspace', 'ddk_ligand_transformation_mask']
 
 # test hooks (include/ddk_debug.h): not part of the drop-in boundary
 DEBUG_SYMBOLS = ['ddk_debug_export', 'ddk_debug_read_edges', 'ddk_debug_conf_counts', 'ddk_debug_conf_table', 'ddk_debug_conf_nodes', 'ddk_debug_conf_edges', 'ddk_debug_kabsch', 'ddk_debug_axis_angle', 'ddk_debug_set_layer0_dedup', 'ddk_debug_read_patch', 'ddk_debug_split3', 'ddk_debug_conv_trace', 'ddk_debug_pool_stats', 'ddk_debug_set_conv_workgroups', 'ddk_debug_set_alloc_limit', 'ddk_debug_cross_mirror']
@@ -95,6 +97,12 @@ def lib():
     L.ddk_ligand_automorphisms_workspace.argtypes = [i32, i32]
     L.ddk_ligand_automorphisms_workspace.restype = i64
     L.ddk_ligand_automorphisms.argtypes = [vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp]
+    for name in ('ddk_receptor_knn_graph_workspace', 'ddk_radius_graph_workspace', 'ddk_ligand_transformation_mask_workspace'):
+        getattr(L, name).argtypes = [i32, i32]
+        getattr(L, name).restype = i64
+    L.ddk_receptor_knn_graph.argtypes = [vp, i32, vp, f32, i32, vp, i32, vp, vp, vp]
+    L.ddk_radius_graph.argtypes = [vp, i32, vp, f32, i32, vp, i32, vp, vp, vp]
+    L.ddk_ligand_transformation_mask.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, vp, vp]
     L.ddk_sample.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.ddk_sample_trajectory.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, C.POINTER(ddk_trajectory), vp]
     L.ddk_last_graph_stats.argtypes = [vp, vp, vp, vp]

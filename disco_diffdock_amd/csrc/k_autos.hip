@@ -23,6 +23,7 @@
 // than cap rows is status 1, a bond index outside [0, n_lig) is status 2 (found before it is used as an address); both emit the identity alone.  Every
 // store of a row is guarded by the row index < cap.
 #include "model.h"
+#include "k_lig_bits.h"
 
 namespace ddk {
 
@@ -143,25 +144,6 @@ __device__ inline void autos_store_child(uint8_t* next, const uint8_t* frontier,
   W[last] = keep | ((uint32_t)c << sh);
 }
 
-// exclusive scan of one flag per thread over the workgroup in thread order (ballot per wave, the wave totals through LDS); *total: the workgroup's sum.
-// Two barriers; wave_sums [blockDim / 64] is free again after the call.
-__device__ inline int autos_block_scan(bool flag, int* wave_sums, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
-  const unsigned long long b = __ballot(flag);
-  const int in_wave = __popcll(b & ((1ull << lane) - 1ull));
-  __syncthreads();      // (the previous call's readers are done with wave_sums)
-  if (lane == 0) wave_sums[wave] = __popcll(b);
-  __syncthreads();
-  int before = 0, all = 0;
-  for (int w = 0; w < n_waves; ++w) {
-    const int s = wave_sums[w];
-    all += s;
-    if (w < wave) before += s;
-  }
-  *total = all;
-  return before + in_wave;
-}
-
 }  // namespace
 
 __global__ __launch_bounds__(AUTOS_WALK_THREADS) void autos_walk_kernel(int n_lig, const int32_t* __restrict__ colour, const int32_t* __restrict__ bond_index,
@@ -188,8 +170,7 @@ __global__ __launch_bounds__(AUTOS_WALK_THREADS) void autos_walk_kernel(int n_li
     if ((unsigned)a >= (unsigned)n_lig || (unsigned)b >= (unsigned)n_lig) {
       bad = 1;      // (every writer writes the same value)
     } else if (a != b && ((T.kept[a >> 5] >> (a & 31)) & 1) && ((T.kept[b >> 5] >> (b & 31)) & 1)) {
-      atomicOr(&T.adj[a][b >> 5], 1u << (b & 31));      // OR: duplicates and the two directions of a bond are one edge, in any arrival order
-      atomicOr(&T.adj[b][a >> 5], 1u << (a & 31));
+      adj256_add(T.adj, a, b);      // OR: duplicates and the two directions of a bond are one edge, in any arrival order
     }
   }
   __syncthreads();
@@ -248,7 +229,7 @@ __global__ __launch_bounds__(AUTOS_WALK_THREADS) void autos_walk_kernel(int n_li
         const int t = t0 + tid;
         int row = 0, c = 0, total;
         const bool flag = t < items && autos_item(T, L, cur, stride, t, &row, &c);
-        const int pos = base + autos_block_scan(flag, wave_sums, &total);
+        const int pos = base + block_scan_flags(flag, wave_sums, &total);
         if (flag && pos < cap) autos_store_child(nxt, cur, stride, d, row, c, pos);
         base += total;
         if (base > cap) break;      // (uniform)
@@ -322,7 +303,7 @@ __global__ __launch_bounds__(AUTOS_CHUNK) void autos_write_kernel(int i, int n_l
     const int t = b * AUTOS_CHUNK + threadIdx.x;
     int row = 0, c = 0, total;
     const bool flag = t < items && autos_item(T, L, cur, stride, t, &row, &c);
-    const int pos = base + autos_block_scan(flag, wave_sums, &total);
+    const int pos = base + block_scan_flags(flag, wave_sums, &total);
     if (flag && pos < cap) autos_store_child(nxt, cur, stride, d, row, c, pos);
     if (b == chunks - 1 && threadIdx.x == 0) {      // the last chunk knows the next level's row count
       const int next = base + total;

@@ -303,6 +303,25 @@ int64_t autos_workspace_bytes(int n_lig, int cap);
 hipError_t launch_ligand_automorphisms(int n_lig, const int32_t* colour, const int32_t* bond_index, int n_bond_edges, const uint8_t* atom_mask,
                                        int32_t* perms_out, int cap, int32_t* count_out, void* workspace, hipStream_t s);
 
+// k_build.hip: the static graph tables of a complex from coordinates and bonds (ddk_receptor_knn_graph, ddk_radius_graph, ddk_ligand_transformation_mask)
+constexpr int BUILD_MAX_POINTS = 65536;          // residues / atoms of one call (build_scan_kernel: 64 rows per thread)
+constexpr int KNN_MAX_NEIGHBOR = 128;            // rows of knn_rows_kernel's selection in LDS
+constexpr int KNN_THREADS = 256;                 // its workgroup = the bins of its radix histogram
+constexpr int RADIUS_MAX_NEIGHBORS = 1024;
+constexpr int BUILD_SCAN_THREADS = 1024;         // build_scan_kernel: one workgroup
+constexpr int BUILD_GRID = 2048;                 // the grid-stride kernels' largest grid
+constexpr int LIG_MASK_MAX_EDGES = 2048;         // directed bond columns: one thread per bond
+constexpr int LIG_MASK_THREADS = 1024;           // lig_mask_kernel: one workgroup
+int64_t knn_graph_workspace_bytes(int n, int max_neighbor);
+int64_t radius_graph_workspace_bytes(int n);
+int64_t lig_mask_workspace_bytes(int M);
+hipError_t launch_receptor_knn_graph(int n, const float* pos, float cutoff, int max_neighbor, int32_t* edge_index_out, int cap, int32_t* count_out,
+                                     void* workspace, hipStream_t s);
+hipError_t launch_radius_graph(int n, const float* pos, float r, int max_num_neighbors, int32_t* edge_index_out, int cap, int32_t* count_out,
+                               void* workspace, hipStream_t s);
+hipError_t launch_ligand_transformation_mask(int n_lig, const int32_t* bond_index, int M, uint8_t* edge_mask_out, uint8_t* mask_rotate_out, int cap_rot,
+                                             int32_t* count_out, void* workspace, hipStream_t s);
+
 int conf_model_finalize(ddk_ctx* ctx);   // conf.hip (all-atom confidence model)
 void conf_complex_free(ddk_complex* cx);
 void conf_model_destroy(ddk_ctx* ctx);

@@ -1034,6 +1034,65 @@ int ddk_ligand_automorphisms(ddk_ctx* ctx, int32_t n_lig, const int32_t* colour,
   return DDK_OK;
 }
 
+int64_t ddk_receptor_knn_graph_workspace(int32_t n, int32_t max_neighbor) {
+  if (n < 2 || n > BUILD_MAX_POINTS || max_neighbor < 1 || max_neighbor > KNN_MAX_NEIGHBOR) return -1;
+  return knn_graph_workspace_bytes(n, max_neighbor);
+}
+
+int ddk_receptor_knn_graph(ddk_ctx* ctx, int32_t n, const float* pos, float cutoff, int32_t max_neighbor, int32_t* edge_index_out, int32_t cap,
+                           int32_t* count_out, void* workspace, void* stream) {
+  if (!ctx) return DDK_ERR_INVALID;
+  if (ctx->host_only) return fail(ctx, DDK_ERR_STATE, "host-only context (device < 0) cannot launch kernels");
+  if (n < 2 || n > BUILD_MAX_POINTS) return fail(ctx, DDK_ERR_INVALID, "ddk_receptor_knn_graph: n must be in [2, " + std::to_string(BUILD_MAX_POINTS) + "]");
+  if (max_neighbor < 1 || max_neighbor > KNN_MAX_NEIGHBOR)
+    return fail(ctx, DDK_ERR_INVALID, "ddk_receptor_knn_graph: max_neighbor must be in [1, " + std::to_string(KNN_MAX_NEIGHBOR) + "]");
+  if ((int64_t)cap < (int64_t)n * max_neighbor)
+    return fail(ctx, DDK_ERR_INVALID, "ddk_receptor_knn_graph: cap must be at least n * max_neighbor = " + std::to_string((int64_t)n * max_neighbor));
+  if (!pos || !edge_index_out || !count_out || !workspace) return fail(ctx, DDK_ERR_INVALID, "ddk_receptor_knn_graph: null argument");
+  hipError_t e = launch_receptor_knn_graph(n, pos, cutoff, max_neighbor, edge_index_out, cap, count_out, workspace, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "receptor_knn_graph launch");
+  return DDK_OK;
+}
+
+int64_t ddk_radius_graph_workspace(int32_t n, int32_t max_num_neighbors) {
+  if (n < 1 || n > BUILD_MAX_POINTS || max_num_neighbors < 1 || max_num_neighbors > RADIUS_MAX_NEIGHBORS) return -1;
+  return radius_graph_workspace_bytes(n);
+}
+
+int ddk_radius_graph(ddk_ctx* ctx, int32_t n, const float* pos, float r, int32_t max_num_neighbors, int32_t* edge_index_out, int32_t cap,
+                     int32_t* count_out, void* workspace, void* stream) {
+  if (!ctx) return DDK_ERR_INVALID;
+  if (ctx->host_only) return fail(ctx, DDK_ERR_STATE, "host-only context (device < 0) cannot launch kernels");
+  if (n < 1 || n > BUILD_MAX_POINTS) return fail(ctx, DDK_ERR_INVALID, "ddk_radius_graph: n must be in [1, " + std::to_string(BUILD_MAX_POINTS) + "]");
+  if (max_num_neighbors < 1 || max_num_neighbors > RADIUS_MAX_NEIGHBORS)
+    return fail(ctx, DDK_ERR_INVALID, "ddk_radius_graph: max_num_neighbors must be in [1, " + std::to_string(RADIUS_MAX_NEIGHBORS) + "]");
+  if (cap < 1) return fail(ctx, DDK_ERR_INVALID, "ddk_radius_graph: cap must be >= 1");
+  if (!pos || !edge_index_out || !count_out || !workspace) return fail(ctx, DDK_ERR_INVALID, "ddk_radius_graph: null argument");
+  hipError_t e = launch_radius_graph(n, pos, r, max_num_neighbors, edge_index_out, cap, count_out, workspace, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "radius_graph launch");
+  return DDK_OK;
+}
+
+int64_t ddk_ligand_transformation_mask_workspace(int32_t n_lig, int32_t M) {
+  if (n_lig < 1 || n_lig > MAX_LIG || M < 0 || M > LIG_MASK_MAX_EDGES || (M & 1)) return -1;
+  return lig_mask_workspace_bytes(M);
+}
+
+int ddk_ligand_transformation_mask(ddk_ctx* ctx, int32_t n_lig, const int32_t* bond_index, int32_t M, uint8_t* edge_mask_out, uint8_t* mask_rotate_out,
+                                   int32_t cap_rot, int32_t* count_out, void* workspace, void* stream) {
+  if (!ctx) return DDK_ERR_INVALID;
+  if (ctx->host_only) return fail(ctx, DDK_ERR_STATE, "host-only context (device < 0) cannot launch kernels");
+  if (n_lig < 1 || n_lig > MAX_LIG) return fail(ctx, DDK_ERR_INVALID, "ddk_ligand_transformation_mask: n_lig must be in [1, " + std::to_string(MAX_LIG) + "]");
+  if (M < 0 || M > LIG_MASK_MAX_EDGES || (M & 1))
+    return fail(ctx, DDK_ERR_INVALID, "ddk_ligand_transformation_mask: M must be even and in [0, " + std::to_string(LIG_MASK_MAX_EDGES) + "]");
+  if (cap_rot < 1) return fail(ctx, DDK_ERR_INVALID, "ddk_ligand_transformation_mask: cap_rot must be >= 1");
+  if (!mask_rotate_out || !count_out || !workspace || ((!bond_index || !edge_mask_out) && M > 0))
+    return fail(ctx, DDK_ERR_INVALID, "ddk_ligand_transformation_mask: null argument (only bond_index and edge_mask_out with M = 0 may be null)");
+  hipError_t e = launch_ligand_transformation_mask(n_lig, bond_index, M, edge_mask_out, mask_rotate_out, cap_rot, count_out, workspace, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "ligand_transformation_mask launch");
+  return DDK_OK;
+}
+
 }  // extern "C"
 
 // ddk_sample / ddk_sample_trajectory (`what` names the entry point in messages).  rec: the caller's record arrays, every member may be null; the record is

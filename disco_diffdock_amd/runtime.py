@@ -42,6 +42,10 @@ PAIRS_MAX_B, CLUSTER_MAX_B, PAIRS_TJ, PAIRS_ROWS_PER_PASS = 4096, 1024, 8, 16
 # of launches over workgroups of AUTOS_CHUNK items
 AUTOS_MAX_CAP, AUTOS_WALK_ITEMS, AUTOS_WALK_ONLY_ITEMS, AUTOS_CHUNK = 1 << 20, 1024, 16384, 256
 AUTOS_STATUS = ('complete', 'overflow: a level of the search held more partial maps than cap', 'a bond index outside the ligand')
+# the three table builders of csrc/k_build.hip (ddk_receptor_knn_graph, ddk_radius_graph, ddk_ligand_transformation_mask): their limits (csrc/model.h)
+BUILD_MAX_POINTS, KNN_MAX_NEIGHBOR, RADIUS_MAX_NEIGHBORS, LIG_MASK_MAX_EDGES = 65536, 128, 1024, 2048
+MASK_STATUS = ('complete', 'more rotatable bonds than rows', 'a bond column that is out of range, unpaired, a self bond or repeated',
+               'the ligand graph is not connected')
 
 
 def usable_automorphisms(perms, count, name=None):
@@ -321,6 +325,82 @@ class Context:
         self._check(self.L.ddk_ligand_automorphisms(self.h, n_lig, _ptr(col), _ptr(bi), E, _ptr(m), _ptr(perms), cap, _ptr(count), _ptr(ws), _stream()),
                     'ddk_ligand_automorphisms')
         return perms, count
+
+    # ---- coordinates + bonds -> the static graph tables of a complex (csrc/k_build.hip) -------------
+    def _count(self, count, what):
+        """the ONE read-back of a builder: count_out [2] -> (count, status) on the host (8 bytes)"""
+        n, status = (int(v) for v in count.tolist())
+        if status == 2:
+            raise ValueError(f'ddk: {what}: ' + ('a coordinate is not finite' if what != 'transformation_mask' else MASK_STATUS[2]))
+        return n, status
+
+    def _points(self, pos, what):
+        dev = torch.device('cuda', self.device)
+        pos = h2d_async(torch.as_tensor(pos).to(torch.float32).contiguous(), dev)
+        if pos.dim() != 2 or pos.shape[1] != 3:
+            raise RuntimeError(f'ddk: {what} takes coordinates [n, 3]; got ' + str(tuple(pos.shape)))
+        return dev, pos
+
+    def receptor_knn_graph(self, pos, cutoff=15.0, max_neighbor=24):
+        """rec_edge_index of the residues pos [n, 3] by the rule of get_calpha_graph (process_mols.py:337-353; ddk_receptor_knn_graph, include/ddk.h):
+        every other residue under ``cutoff`` in ascending index, the ``max_neighbor`` nearest by (distance, index) if there are more, the single nearest
+        if there is none.  -> device tensor [2, E] int32, columns [i; j] grouped by i: what ddk_complex_create takes.  One 8-byte read-back (E).  A
+        coordinate that is not finite is a ValueError.  2 <= n <= 65536, max_neighbor <= 128."""
+        dev, pos = self._points(pos, 'receptor_knn_graph')
+        n, K = pos.shape[0], int(max_neighbor)
+        nbytes = self.L.ddk_receptor_knn_graph_workspace(n, K)
+        cap = n * K if nbytes >= 0 else 1      # a broken limit: the call below says which
+        out = torch.empty((2, cap), dtype=torch.int32, device=dev)
+        count = torch.empty(2, dtype=torch.int32, device=dev)
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        self._check(self.L.ddk_receptor_knn_graph(self.h, n, _ptr(pos), float(cutoff), K, _ptr(out), cap, _ptr(count), _ptr(ws), _stream()),
+                    'ddk_receptor_knn_graph')
+        E, _ = self._count(count, 'receptor_knn_graph')
+        return out[:, :E]
+
+    def radius_graph(self, pos, r=5.0, max_num_neighbors=8):
+        """torch_cluster.radius_graph(pos, r, max_num_neighbors=...) of one graph (atom_edge_index, process_mols.py:471; ddk_radius_graph, include/ddk.h)
+        -> device tensor [2, E] int32, columns [neighbour; centre] grouped by centre, neighbours ascending.  One 8-byte read-back (E).  A coordinate that
+        is not finite is a ValueError.  n <= 65536, max_num_neighbors <= 1024."""
+        dev, pos = self._points(pos, 'radius_graph')
+        n, K = pos.shape[0], int(max_num_neighbors)
+        nbytes = self.L.ddk_radius_graph_workspace(n, K)
+        cap = n * (K + 1) if nbytes >= 0 else 1      # the worst case: the status cannot be 1
+        out = torch.empty((2, cap), dtype=torch.int32, device=dev)
+        count = torch.empty(2, dtype=torch.int32, device=dev)
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        self._check(self.L.ddk_radius_graph(self.h, n, _ptr(pos), float(r), K, _ptr(out), cap, _ptr(count), _ptr(ws), _stream()), 'ddk_radius_graph')
+        E, status = self._count(count, 'radius_graph')
+        if status != 0:
+            raise RuntimeError(f'ddk: radius_graph: status {status} with {E} edges for {cap} columns')
+        return out[:, :E]
+
+    def transformation_mask(self, n_lig, bond_index):
+        """(edge_mask [M], mask_rotate [R, n_lig]), uint8 device tensors, by the rule of get_transformation_mask (utils/torsion.py:15-45;
+        ddk_ligand_transformation_mask, include/ddk.h) from bond_index [2, M], columns 2k / 2k + 1 the two directions of bond k.  One 8-byte read-back
+        (R).  A bond column that is out of range, unpaired, a self bond or repeated is a ValueError; a ligand graph that is not connected gives a warning
+        and no torsion (edge_mask all 0, R = 0).  n_lig <= 256, M <= 2048."""
+        dev = torch.device('cuda', self.device)
+        n_lig = int(n_lig)
+        bi = torch.as_tensor(bond_index)
+        if bi.numel() and (bi.dim() != 2 or bi.shape[0] != 2):
+            raise RuntimeError('ddk: bond_index must be [2, M]; got ' + str(tuple(bi.shape)))
+        M = bi.numel() // 2
+        bi = h2d_async(bi.to(torch.int32).contiguous(), dev) if M else None
+        nbytes = self.L.ddk_ligand_transformation_mask_workspace(n_lig, M)
+        ok = nbytes >= 0
+        cap = max(M // 2, 1)      # a row per bond: the status cannot be 1
+        edge_mask = torch.empty(M if ok else 0, dtype=torch.uint8, device=dev)
+        mask_rotate = torch.empty((cap, n_lig) if ok else (1, 1), dtype=torch.uint8, device=dev)
+        count = torch.empty(2, dtype=torch.int32, device=dev)
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        self._check(self.L.ddk_ligand_transformation_mask(self.h, n_lig, _ptr(bi), M, _ptr(edge_mask) if M else None, _ptr(mask_rotate), cap, _ptr(count),
+                                                          _ptr(ws), _stream()), 'ddk_ligand_transformation_mask')
+        R, status = self._count(count, 'transformation_mask')
+        if status != 0:
+            warnings.warn(f'ddk: transformation_mask: status {status} ({MASK_STATUS[status]}); the ligand gets no torsion')
+            R = 0
+        return edge_mask, mask_rotate[:R]
 
 
 class Complex:

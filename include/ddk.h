@@ -307,6 +307,57 @@ int ddk_ligand_automorphisms(ddk_ctx* ctx, int32_t n_lig, const int32_t* colour,
                              const uint8_t* atom_mask, int32_t* perms_out, int32_t cap, int32_t* count_out /* [2] */,
                              void* workspace, void* stream);
 
+/* ---- coordinates + bonds in -> the static graph tables ddk_complex_create and ddk_complex_set_atoms take, built on the device (csrc/k_build.hip) instead of
+ *      by the host code of the reference's data pipeline (scipy cdist + a Python loop, torch_cluster, networkx).  Like ddk_ligand_automorphisms the three
+ *      calls take no ddk_complex, allocate nothing and do not synchronise; all pointers are DEVICE pointers; the work is enqueued on `stream`; the caller
+ *      owns a workspace of *_workspace(...) bytes (16-byte aligned, contents irrelevant before and after; a host function, no context, -1 if a limit is
+ *      broken); count_out [2] int32 = {count, status}.  A status other than 0 is a result: the call returns DDK_OK.  A broken limit or a NULL argument is
+ *      DDK_ERR_INVALID.  No float atomics and no atomic cursors: the order of the output is fixed and it is bit-identical run to run.
+ *      Distances: the fp32 coordinates are converted to double, subtracted, d2 = dx*dx + dy*dy + dz*dz in double, compared with (double)r * (double)r,
+ *      strictly below.  (On coordinates that are small multiples of 0.5 every step is exact, whatever the contraction.)
+ *
+ *      ddk_receptor_knn_graph: rec_edge_index by the rule of get_calpha_graph, datasets_utils/process_mols.py:337-353.  pos [n, 3].  Row i's candidates
+ *        are the j != i with d(i, j) < cutoff.  At most max_neighbor of them: all are kept, in ascending j (np.where order).  More: the max_neighbor nearest
+ *        of ALL other points, ordered by ascending (d2, j): nearest first, ties to the lower index.  None: the single nearest other point, ties to the
+ *        lower index.  Self is excluded by its INDEX: a coincident residue j != i is a neighbour at distance 0 like any other, where the reference drops
+ *        position 0 of the argsort and its `assert i not in dst` fires.  edge_index_out [2, cap] int32: columns [i; j] grouped by i ascending, the
+ *        order ddk_complex_create demands; row 1 starts at edge_index_out + cap.  count_out[0] = E.  Status 2: a coordinate that is not finite, found
+ *        on the device; E = 0 and nothing is written to edge_index_out.
+ *        Limits: 2 <= n <= 65536, 1 <= max_neighbor <= 128, cap >= n * max_neighbor.  Three launches: one workgroup per row (a radix select on the bits
+ *        of d2 where more than max_neighbor points lie under the cutoff, however many), a scan of the row counts, the stores.
+ *
+ *      ddk_radius_graph: torch_cluster.radius_graph(pos, r, max_num_neighbors) for one graph (atom_edge_index, process_mols.py:471).  For every centre i:
+ *        the first max_num_neighbors + 1 points j in ascending j with d2 < r^2, self included in that scan; then j == i is dropped.  A centre whose own
+ *        index comes after its first max_num_neighbors + 1 in-radius points therefore keeps max_num_neighbors + 1 neighbours (the quirk of LIG_CAP,
+ *        csrc/model.h).  edge_index_out [2, cap] int32: columns [neighbour; centre], grouped by centre ascending, neighbours ascending.  count_out[0] = the
+ *        E the graph needs.  Status 1: E > cap; nothing past cap columns is written and the columns are not to be read.  Status 2: a coordinate that is
+ *        not finite; E = 0, nothing is written.
+ *        Limits: 1 <= n <= 65536, 1 <= max_num_neighbors <= 1024, cap >= 1.  Three launches: one wave per centre sweeps j and stops when its quota is
+ *        full (brute force, no cell list), a scan of the counts, the same sweep again with the stores.
+ *
+ *      ddk_ligand_transformation_mask: edge_mask / mask_rotate by the rule of get_transformation_mask, utils/torsion.py:15-45.  bond_index [2, M] int32,
+ *        columns 2k and 2k + 1 the two directions (u, v), (v, u) of bond k.  Remove bond k; if the graph falls apart, l is the smaller side, on equal
+ *        sizes the side that contains the lowest atom index (networkx's component order under a stable sort).  |l| > 1: the bond is rotatable and the
+ *        marked direction is 2k + 1 if u is on l, else 2k: the head rotates, the tail is fixed, which is the orientation ddk_complex_create checks.
+ *        edge_mask_out [M] uint8: 1 on the marked columns, every other entry is written 0.  mask_rotate_out [cap_rot, n_lig] uint8: one row per marked
+ *        column in ascending column index, 1 on l; rows past R are not touched.  count_out[0] = R.
+ *        Status 1: R > cap_rot; edge_mask_out is all 0 (no torsion: the identity fallback), R is reported and mask_rotate_out is not touched.
+ *        Status 2: a bond index outside [0, n_lig), a column pair that is not (u, v), (v, u), a bond of an atom with itself or a repeated bond, all found
+ *        on the device before an index is used as an address; status 3: the ligand graph is not connected.  With 2 and 3 edge_mask_out is all 0, R = 0
+ *        and mask_rotate_out is not touched.  (For a lone counter-ion next to the ligand that is the reference's result too; with a larger second
+ *        fragment the reference marks bonds whose row ddk_complex_create refuses, so no table is the honest answer.)
+ *        Limits: 1 <= n_lig <= 256, 0 <= M <= 2048 and even, cap_rot >= 1 (bond_index and edge_mask_out may be NULL with M = 0).  One launch of one
+ *        workgroup: a thread per bond walks the side of u over the 256-bit adjacency rows. */
+int64_t ddk_receptor_knn_graph_workspace(int32_t n, int32_t max_neighbor);
+int ddk_receptor_knn_graph(ddk_ctx* ctx, int32_t n, const float* pos, float cutoff, int32_t max_neighbor, int32_t* edge_index_out, int32_t cap,
+                           int32_t* count_out /* [2] */, void* workspace, void* stream);
+int64_t ddk_radius_graph_workspace(int32_t n, int32_t max_num_neighbors);
+int ddk_radius_graph(ddk_ctx* ctx, int32_t n, const float* pos, float r, int32_t max_num_neighbors, int32_t* edge_index_out, int32_t cap,
+                     int32_t* count_out /* [2] */, void* workspace, void* stream);
+int64_t ddk_ligand_transformation_mask_workspace(int32_t n_lig, int32_t M);
+int ddk_ligand_transformation_mask(ddk_ctx* ctx, int32_t n_lig, const int32_t* bond_index, int32_t M, uint8_t* edge_mask_out, uint8_t* mask_rotate_out,
+                                   int32_t cap_rot, int32_t* count_out /* [2] */, void* workspace, void* stream);
+
 /* ---- a1-a2: the reverse-diffusion loop of sampling()  utils/sampling.py:105-198 for one batch:
  *      per step  perturb = score_coeff*score + noise_coeff*z  (coefficients are the host scalars of
  *      sampling.py:137-192, including the low-temperature variant), then ddk_se3_update.
