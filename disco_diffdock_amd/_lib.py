@@ -50,7 +50,8 @@ SYMBOLS = ['ddk_create', 'ddk_destroy', 'ddk_last_error', 'ddk_version', 'ddk_lo
            'ddk_sample_trajectory', 'ddk_pose_pairwise_rmsd', 'ddk_pose_cluster',
            'ddk_ligand_automorphisms_workspace', 'ddk_ligand_automorphisms',
            'ddk_receptor_knn_graph_workspace', 'ddk_receptor_knn_graph', 'ddk_radius_graph_workspace', 'ddk_radius_graph',
-           'ddk_ligand_transformation_mask_workspace', 'ddk_ligand_transformation_mask']
+           'ddk_ligand_transformation_mask_workspace', 'ddk_ligand_transformation_mask',
+           'ddk_rng_noise', 'ddk_rng_initial', 'ddk_rng_uniform']
 
 # test hooks (include/ddk_debug.h): not part of the drop-in boundary
 DEBUG_SYMBOLS = ['ddk_debug_export', 'ddk_debug_read_edges', 'ddk_debug_conf_counts', 'ddk_debug_conf_table', 'ddk_debug_conf_nodes', 'ddk_debug_conf_edges', 'ddk_debug_kabsch', 'ddk_debug_axis_angle', 'ddk_debug_set_layer0_dedup', 'ddk_debug_read_patch', 'ddk_debug_split3', 'ddk_debug_conv_trace', 'ddk_debug_pool_stats', 'ddk_debug_set_conv_workgroups', 'ddk_debug_set_alloc_limit', 'ddk_debug_cross_mirror']
@@ -103,6 +104,10 @@ def lib():
     L.ddk_receptor_knn_graph.argtypes = [vp, i32, vp, f32, i32, vp, i32, vp, vp, vp]
     L.ddk_radius_graph.argtypes = [vp, i32, vp, f32, i32, vp, i32, vp, vp, vp]
     L.ddk_ligand_transformation_mask.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, vp, vp]
+    u64 = C.c_uint64      # (seed, stream_id) of the ddk_rng_* calls: DDK_RNG_LAYOUT of include/ddk.h
+    L.ddk_rng_noise.argtypes = [vp, u64, u64, i32, i32, i32, i32, i32, i32, vp, vp, vp]
+    L.ddk_rng_initial.argtypes = [vp, u64, u64, i32, i32, i32, f32, i32, vp, vp, vp, vp]
+    L.ddk_rng_uniform.argtypes = [vp, u64, u64, i32, i32, i32, vp, vp]
     L.ddk_sample.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.ddk_sample_trajectory.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, C.POINTER(ddk_trajectory), vp]
     L.ddk_last_graph_stats.argtypes = [vp, vp, vp, vp]

@@ -322,6 +322,12 @@ hipError_t launch_radius_graph(int n, const float* pos, float r, int max_num_nei
 hipError_t launch_ligand_transformation_mask(int n_lig, const int32_t* bond_index, int M, uint8_t* edge_mask_out, uint8_t* mask_rotate_out, int cap_rot,
                                              int32_t* count_out, void* workspace, hipStream_t s);
 
+// k_rng.hip: the sampler's draws from the counter-based generator of k_philox.h (ddk_rng_noise, ddk_rng_initial, ddk_rng_uniform); limits in k_philox.h
+hipError_t launch_rng_noise(uint64_t seed, uint64_t stream_id, int sample0, int B, int step0, int steps, int n_cols, int n_active, float* out, hipStream_t s);
+hipError_t launch_rng_initial(uint64_t seed, uint64_t stream_id, int sample0, int B, int n_rot, float tr_sigma, int purpose_rot, float* tor_out, float* rot_out,
+                              float* tr_out, hipStream_t s);
+hipError_t launch_rng_uniform(uint64_t seed, uint64_t stream_id, int sample0, int B, int decoding_idx, float* out, hipStream_t s);
+
 int conf_model_finalize(ddk_ctx* ctx);   // conf.hip (all-atom confidence model)
 void conf_complex_free(ddk_complex* cx);
 void conf_model_destroy(ddk_ctx* ctx);

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <thread>
 
+#include "k_philox.h"
 #include "model.h"
 
 namespace ddk {
@@ -1090,6 +1091,67 @@ int ddk_ligand_transformation_mask(ddk_ctx* ctx, int32_t n_lig, const int32_t* b
     return fail(ctx, DDK_ERR_INVALID, "ddk_ligand_transformation_mask: null argument (only bond_index and edge_mask_out with M = 0 may be null)");
   hipError_t e = launch_ligand_transformation_mask(n_lig, bond_index, M, edge_mask_out, mask_rotate_out, cap_rot, count_out, workspace, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(ctx, e, "ligand_transformation_mask launch");
+  return DDK_OK;
+}
+
+// the argument checks the three ddk_rng_* calls share (include/ddk.h, DDK_RNG_LAYOUT): empty = fine
+static std::string rng_bad_samples(int32_t sample0, int32_t B) {
+  if (B < 1) return "B must be >= 1";
+  if (sample0 < 0) return "sample0 must be >= 0";
+  if ((int64_t)sample0 + B > (int64_t)INT32_MAX) return "sample0 + B must be <= 2^31 - 1";
+  return "";
+}
+
+int ddk_rng_noise(ddk_ctx* ctx, uint64_t seed, uint64_t stream_id, int32_t sample0, int32_t B, int32_t step0, int32_t steps, int32_t n_cols,
+                  int32_t n_active_cols, const float* noise_coeff, float* out, void* stream) {
+  if (!ctx) return DDK_ERR_INVALID;
+  if (ctx->host_only) return fail(ctx, DDK_ERR_STATE, "host-only context (device < 0) cannot launch kernels");
+  const std::string bad = rng_bad_samples(sample0, B);
+  if (!bad.empty()) return fail(ctx, DDK_ERR_INVALID, "ddk_rng_noise: " + bad);
+  if (step0 < 0 || steps < 1 || (int64_t)step0 + steps > RNG_MAX_STEPS)
+    return fail(ctx, DDK_ERR_INVALID, "ddk_rng_noise: need 0 <= step0, 1 <= steps and step0 + steps <= " + std::to_string(RNG_MAX_STEPS));
+  if (n_cols < 1 || n_cols > RNG_MAX_COLS) return fail(ctx, DDK_ERR_INVALID, "ddk_rng_noise: n_cols must be in [1, " + std::to_string(RNG_MAX_COLS) + "]");
+  if (n_active_cols < 0 || n_active_cols > n_cols) return fail(ctx, DDK_ERR_INVALID, "ddk_rng_noise: n_active_cols must be in [0, n_cols]");
+  if (!out) return fail(ctx, DDK_ERR_INVALID, "ddk_rng_noise: null output");
+  // one launch per run of steps that use noise, one memset per run that does not (a step whose three coefficients are all zero draws nothing)
+  const size_t row = (size_t)B * n_cols;
+  auto active = [&](int k) { return !noise_coeff || noise_coeff[3 * k] != 0.f || noise_coeff[3 * k + 1] != 0.f || noise_coeff[3 * k + 2] != 0.f; };
+  for (int k = 0; k < steps;) {
+    int u = k + 1;
+    while (u < steps && active(u) == active(k)) ++u;
+    hipError_t e = active(k) ? launch_rng_noise(seed, stream_id, sample0, B, step0 + k, u - k, n_cols, n_active_cols, out + k * row, (hipStream_t)stream)
+                             : hipMemsetAsync(out + k * row, 0, (u - k) * row * sizeof(float), (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "rng_noise launch");
+    k = u;
+  }
+  return DDK_OK;
+}
+
+int ddk_rng_initial(ddk_ctx* ctx, uint64_t seed, uint64_t stream_id, int32_t sample0, int32_t B, int32_t n_rot, float tr_sigma, int32_t purpose_rot,
+                    float* tor_out, float* rot_out, float* tr_out, void* stream) {
+  if (!ctx) return DDK_ERR_INVALID;
+  if (ctx->host_only) return fail(ctx, DDK_ERR_STATE, "host-only context (device < 0) cannot launch kernels");
+  const std::string bad = rng_bad_samples(sample0, B);
+  if (!bad.empty()) return fail(ctx, DDK_ERR_INVALID, "ddk_rng_initial: " + bad);
+  if (n_rot < 0 || n_rot > RNG_MAX_COLS) return fail(ctx, DDK_ERR_INVALID, "ddk_rng_initial: n_rot must be in [0, " + std::to_string(RNG_MAX_COLS) + "]");
+  if (purpose_rot != (int32_t)RNG_INIT_ROTATION && purpose_rot != (int32_t)RNG_AR_ROTATION)
+    return fail(ctx, DDK_ERR_INVALID, "ddk_rng_initial: purpose_rot must be 2 (initial rotation) or 5 (rotation of ar_pos)");
+  if (!rot_out) return fail(ctx, DDK_ERR_INVALID, "ddk_rng_initial: null output (only tor_out and tr_out may be null)");
+  hipError_t e = launch_rng_initial(seed, stream_id, sample0, B, n_rot, tr_sigma, purpose_rot, tor_out, rot_out, tr_out, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "rng_initial launch");
+  return DDK_OK;
+}
+
+int ddk_rng_uniform(ddk_ctx* ctx, uint64_t seed, uint64_t stream_id, int32_t sample0, int32_t B, int32_t decoding_idx, float* out, void* stream) {
+  if (!ctx) return DDK_ERR_INVALID;
+  if (ctx->host_only) return fail(ctx, DDK_ERR_STATE, "host-only context (device < 0) cannot launch kernels");
+  const std::string bad = rng_bad_samples(sample0, B);
+  if (!bad.empty()) return fail(ctx, DDK_ERR_INVALID, "ddk_rng_uniform: " + bad);
+  if (decoding_idx < 0 || decoding_idx >= RNG_MAX_STEPS)
+    return fail(ctx, DDK_ERR_INVALID, "ddk_rng_uniform: decoding_idx must be in [0, " + std::to_string(RNG_MAX_STEPS) + ")");
+  if (!out) return fail(ctx, DDK_ERR_INVALID, "ddk_rng_uniform: null output");
+  hipError_t e = launch_rng_uniform(seed, stream_id, sample0, B, decoding_idx, out, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "rng_uniform launch");
   return DDK_OK;
 }
 

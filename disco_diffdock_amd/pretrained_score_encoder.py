@@ -11,12 +11,14 @@ from .score_model import complex_for_batch
 
 
 class GenericEncoder(nn.Module):
-    def encode_ar(self, data, sampling_temperature=1.0, choice_fn=None, uniforms=None):
+    def encode_ar(self, data, sampling_temperature=1.0, choice_fn=None, uniforms=None, rng=None):
         """assumes graphs of the same complex as input (model_classes.py:10).  Returns the one-hot latents
         ``(latent_l [B*n_lig, D], latent_r [B*n_rec, D])`` on the device; ``self.last_choices`` [B, D] (int32, device) holds the
         picked node of every graph (ligand atoms first).
         Extras for the parity tests: ``uniforms`` [D, B] replaces the device draws of the inverse-CDF pick;
-        ``choice_fn(idx, logits)`` replaces the pick altogether (host round trip)."""
+        ``choice_fn(idx, logits)`` replaces the pick altogether (host round trip).
+        ``rng`` = (seed, stream id, sample0): the uniforms come from the counter-based generator instead of torch's (``ddk_rng_uniform``: graph b is the
+        global sample sample0 + b, so its picks do not depend on the batch around it)."""
         if self.latent_vocab != 1:
             raise RuntimeError('ddk: AR decoding is implemented for latent_vocab == 1')
         sm = self.pretrained_score_model
@@ -45,7 +47,10 @@ class GenericEncoder(nn.Module):
                     continue
                 u = None
                 if T < 100:
-                    u = uniforms[idx].to(dev).float().contiguous() if uniforms is not None else torch.rand(B, device=dev)
+                    if uniforms is not None:
+                        u = uniforms[idx].to(dev).float().contiguous()
+                    else:
+                        u = torch.rand(B, device=dev) if rng is None else sm.ctx.rng_uniform(rng[0], rng[1], rng[2], B, idx)
                 cx.ar_decode(logits, T, u, idx, latent_l, latent_r, choices)
         finally:
             cx.keep_receptor_features(False)

@@ -48,6 +48,28 @@ MASK_STATUS = ('complete', 'more rotatable bonds than rows', 'a bond column that
                'the ligand graph is not connected')
 
 
+# the ddk_rng_* calls (csrc/k_rng.hip; DDK_RNG_LAYOUT of include/ddk.h): the purposes of the counter's top four bits and the limits (csrc/k_philox.h)
+RNG_LAYOUT = 1
+RNG_PURPOSES = dict(noise=0, initial_torsion=1, initial_rotation=2, initial_translation=3, ar_pick=4, ar_rotation=5)
+RNG_MAX_STEPS, RNG_MAX_COLS = 1 << 20, 1024
+
+
+def stream_id(name):
+    """The 64-bit id of a complex in the generator's counter (``stream_id`` of the ddk_rng_* calls): FNV-1a over the UTF-8 bytes of its name, so that every
+    process, rank and run gives the same complex the same stream without agreeing on an enumeration.  stream_id('a') == 0xaf63dc4c8601ec8c."""
+    h = 0xcbf29ce484222325
+    for byte in str(name).encode('utf-8'):
+        h = ((h ^ byte) * 0x100000001b3) & 0xFFFFFFFFFFFFFFFF
+    return h
+
+
+def _u64(v, what):
+    v = int(v)
+    if not 0 <= v < 1 << 64:
+        raise ValueError(f'ddk: {what} must be an unsigned 64-bit integer, got {v}')
+    return v
+
+
 def usable_automorphisms(perms, count, name=None):
     """(perms, count) of ``Context.ligand_automorphisms`` -> the rows a consumer may read, perms[:count[0]].  The consumers take the row count as a
     host integer, so this is ONE read-back of ``count`` (8 bytes; the same kind ``PoseClusters.n_clusters`` asks of its reader).  With status 1 or 2 that
@@ -325,6 +347,50 @@ class Context:
         self._check(self.L.ddk_ligand_automorphisms(self.h, n_lig, _ptr(col), _ptr(bi), E, _ptr(m), _ptr(perms), cap, _ptr(count), _ptr(ws), _stream()),
                     'ddk_ligand_automorphisms')
         return perms, count
+
+    # ---- the sampler's draws from the counter-based generator (csrc/k_rng.hip; DDK_RNG_LAYOUT of include/ddk.h) -------------
+    def _rng_args(self, seed, stream, ints):
+        for k, v in ints.items():
+            if not -(1 << 31) <= int(v) < 1 << 31:      # (ctypes would wrap it silently)
+                raise ValueError(f'ddk: {k} = {v} does not fit an int32')
+        return C.c_uint64(_u64(seed, 'seed')), C.c_uint64(_u64(stream, 'rng_stream')), torch.device('cuda', self.device)
+
+    def rng_noise(self, seed, stream, sample0, B, steps, n_cols, n_active_cols=None, step0=0, noise_coeff=None):
+        """N(0,1) draws [steps, B, n_cols] (fresh device tensor) for ``Complex.sample``'s ``noise``: row (k, b) belongs to step step0 + k of the GLOBAL sample
+        sample0 + b of complex ``stream`` (:func:`stream_id`) under ``seed``, whatever B, sample0, step0 and steps cut out of the whole.  Columns from
+        ``n_active_cols`` on are 0; with ``noise_coeff`` [steps, 3] (host) a step whose three entries are zero is 0 (draw_noise's rule).  No read-back."""
+        n_active_cols = n_cols if n_active_cols is None else n_active_cols
+        s, st, dev = self._rng_args(seed, stream, dict(sample0=sample0, B=B, step0=step0, steps=steps, n_cols=n_cols, n_active_cols=n_active_cols))
+        nc = None
+        if noise_coeff is not None:
+            nc = np.ascontiguousarray(noise_coeff, dtype=np.float32)
+            if nc.shape != (steps, 3):
+                raise ValueError(f'ddk: noise_coeff must be [steps, 3] = [{steps}, 3], got {nc.shape}')
+        out = torch.empty((max(steps, 0), max(B, 0), max(n_cols, 0)), dtype=torch.float32, device=dev)
+        self._check(self.L.ddk_rng_noise(self.h, s, st, sample0, B, step0, steps, n_cols, n_active_cols, None if nc is None else nc.ctypes.data_as(C.c_void_p),
+                                         _ptr(out), _stream()), 'ddk_rng_noise')
+        return out
+
+    def rng_initial(self, seed, stream, sample0, B, n_rot, tr_sigma=1.0, torsions=True, translations=True, purpose_rot=RNG_PURPOSES['initial_rotation']):
+        """The draws of randomize_position for the global samples sample0 .. sample0 + B - 1: (tor [B, n_rot] uniform in [-pi, pi) or None, rot [B, 3, 3]
+        uniformly random rotation matrices, tr [B, 3] = tr_sigma * N(0,1) or None), fresh device tensors that go straight into
+        ``Complex.randomize_position``.  ``purpose_rot`` 5: the rotation of ``ar_pos`` under ar_args.no_randomness.  No read-back."""
+        s, st, dev = self._rng_args(seed, stream, dict(sample0=sample0, B=B, n_rot=n_rot, purpose_rot=purpose_rot))
+        Bs, Rs = max(B, 0), max(n_rot, 0)
+        tor = torch.empty((Bs, Rs), dtype=torch.float32, device=dev) if torsions else None
+        rot = torch.empty((Bs, 3, 3), dtype=torch.float32, device=dev)
+        tr = torch.empty((Bs, 3), dtype=torch.float32, device=dev) if translations else None
+        self._check(self.L.ddk_rng_initial(self.h, s, st, sample0, B, n_rot, float(tr_sigma), purpose_rot, _ptr(tor), _ptr(rot), _ptr(tr), _stream()),
+                    'ddk_rng_initial')
+        return tor, rot, tr
+
+    def rng_uniform(self, seed, stream, sample0, B, decoding_idx):
+        """The uniforms [B] in [0, 1) of the AR pick of latent dimension ``decoding_idx`` (``Complex.ar_decode``) for the global samples sample0 ..; fresh
+        device tensor, no read-back."""
+        s, st, dev = self._rng_args(seed, stream, dict(sample0=sample0, B=B, decoding_idx=decoding_idx))
+        out = torch.empty(max(B, 0), dtype=torch.float32, device=dev)
+        self._check(self.L.ddk_rng_uniform(self.h, s, st, sample0, B, decoding_idx, _ptr(out), _stream()), 'ddk_rng_uniform')
+        return out
 
     # ---- coordinates + bonds -> the static graph tables of a complex (csrc/k_build.hip) -------------
     def _count(self, count, what):

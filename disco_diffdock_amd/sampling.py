@@ -13,7 +13,7 @@ import torch
 
 from .data import DataLoader
 from .diffusion_utils import set_time
-from .runtime import CONF_OVERFLOW_WORD, h2d_async
+from .runtime import CONF_OVERFLOW_WORD, RNG_PURPOSES, h2d_async, stream_id
 from .score_model import complex_for_batch
 
 
@@ -25,19 +25,45 @@ def is_iterable(arr):
         return False
 
 
-def randomize_position(data_list, no_torsion, no_random, tr_sigma_max, unbatched=False, ar_args=None, device=None):
+def _rng_stream_of(data_list, rng_stream):
+    """the generator's 64-bit complex id of a seeded call: the caller's ``rng_stream``, else runtime.stream_id of the complex name"""
+    if rng_stream is not None:
+        return int(rng_stream)
+    name = getattr(data_list[0], 'name', None)
+    while isinstance(name, (list, tuple)) and len(name):
+        name = name[0]
+    if not isinstance(name, str):
+        raise ValueError('ddk: a seeded call needs rng_stream=... or a complex with a name (its stream id is runtime.stream_id(name))')
+    return stream_id(name)
+
+
+def randomize_position(data_list, no_torsion, no_random, tr_sigma_max, unbatched=False, ar_args=None, device=None, seed=None, rng_stream=None,
+                       sample_offset=0):
     """utils/sampling.py:12-46 with the reference's signature.  The random draws come from the reference's own RNG streams in
     the reference's order; the geometry (torsion rotations, centring, random rotation, translation) runs on the GPU in one
     ``ddk_randomize_position`` launch (:func:`randomize_position_device`).  Limitation (documented in INTEGRATION.md):
     ``data_list`` must hold copies of ONE complex, which is what evaluate.py:232 passes; ``device`` defaults to the current
-    CUDA device."""
-    from scipy.spatial.transform import Rotation as R
+    CUDA device.
+
+    ``seed`` (extra, optional): with a seed every draw is made on the device by the counter-based generator (``ddk_rng_initial``): graph i gets the
+    draws of global sample ``sample_offset + i`` of complex ``rng_stream`` (default: runtime.stream_id of the complex name), whatever the length of the
+    list and whatever was drawn before; no host RNG, scipy or upload is involved."""
     if device is None:
         if not torch.cuda.is_available():
             raise RuntimeError('ddk: randomize_position runs on the GPU only (no CPU fallback)')
         device = torch.device('cuda', torch.cuda.current_device())
-    randomize_position_device(data_list, no_torsion, no_random, tr_sigma_max, device)
-    if ar_args is not None:   # utils/sampling.py:36-46: the pose the AR model sees
+    randomize_position_device(data_list, no_torsion, no_random, tr_sigma_max, device, seed=seed, rng_stream=rng_stream, sample_offset=sample_offset)
+    if ar_args is not None and ar_args.no_randomness and seed is not None:   # utils/sampling.py:36-46 with the rotations of purpose 5
+        from .tensor_layers import _shape_context
+        device = torch.device(device)
+        ctx = _shape_context(device.index if device.index is not None else torch.cuda.current_device())
+        _, rot, _ = ctx.rng_initial(seed, _rng_stream_of(data_list, rng_stream), sample_offset, len(data_list), 0, torsions=False, translations=False,
+                                    purpose_rot=RNG_PURPOSES['ar_rotation'])
+        for i, g in enumerate(data_list):
+            ar = h2d_async(torch.from_numpy(np.asarray(g['ligand'].orig_rdkit_pos[0])).float(), device)
+            g['ligand'].ar_pos = (ar - torch.mean(ar, dim=0, keepdim=True)) @ rot[i].T
+    elif ar_args is not None:   # utils/sampling.py:36-46: the pose the AR model sees
+        from scipy.spatial.transform import Rotation as R
         for g in data_list:
             if ar_args.no_randomness:
                 ar = torch.from_numpy(np.asarray(g['ligand'].orig_rdkit_pos[0])).float()
@@ -48,13 +74,13 @@ def randomize_position(data_list, no_torsion, no_random, tr_sigma_max, unbatched
                 g['ligand'].ar_pos = g['ligand'].pos.clone()
 
 
-def randomize_position_device(data_list, no_torsion, no_random, tr_sigma_max, device):
+def randomize_position_device(data_list, no_torsion, no_random, tr_sigma_max, device, seed=None, rng_stream=None, sample_offset=0):
     """``randomize_position`` (utils/sampling.py:12-34) for the usual case that ``data_list`` holds N copies of ONE complex
     (evaluate.py:232): the random draws are taken on the host from the reference's own RNG streams in the reference's
     order (np.random.uniform per graph, then scipy ``Rotation.random()`` and ``torch.normal`` per graph), the geometry of
     all N copies runs in one ``ddk_randomize_position`` launch, and every ``g['ligand'].pos`` becomes a view of the
-    resulting device tensor."""
-    from scipy.spatial.transform import Rotation as R
+    resulting device tensor.  With ``seed`` the three arrays come from ONE ``ddk_rng_initial`` launch instead (see :func:`randomize_position`) and go
+    straight into ``ddk_randomize_position``: no host loop, no upload of draws."""
     from .data import collate
     from .score_model import complex_for_batch
     if device is None or torch.device(device).type != 'cuda':
@@ -65,6 +91,16 @@ def randomize_position_device(data_list, no_torsion, no_random, tr_sigma_max, de
     if any(g['ligand'].pos.shape[0] != n_lig or getattr(g, 'name', None) != getattr(g0, 'name', None) for g in data_list):
         raise RuntimeError('ddk: randomize_position_device expects copies of one complex')
     n_rot = int(g0['ligand'].edge_mask.sum())
+    if seed is not None:
+        cx, _ = complex_for_batch(collate([g0]), device, need_model=False)
+        tor, rot, tr = cx.ctx.rng_initial(seed, _rng_stream_of(data_list, rng_stream), sample_offset, N, n_rot, tr_sigma=tr_sigma_max,
+                                          torsions=not no_torsion, translations=not no_random)
+        pos = cx.randomize_position(h2d_async(torch.as_tensor(np.asarray(g0['ligand'].pos.cpu(), np.float32)), device), rot,
+                                    tor if n_rot > 0 else None, tr)
+        for b, g in enumerate(data_list):
+            g['ligand'].pos = pos[b]
+        return pos
+    from scipy.spatial.transform import Rotation as R
     tor = None
     if not no_torsion:
         tor = np.stack([np.random.uniform(low=-np.pi, high=np.pi, size=n_rot) for _ in data_list]).astype(np.float32)
@@ -261,9 +297,16 @@ def sampling(data_list, model, inference_steps, tr_schedule, rot_schedule, tor_s
              confidence_model_args=None, batch_size=32, no_final_step_noise=False, use_latent=True,
              gumbel_latent_temperature=0.01, ar_model=None, ar_args=None, temp_sampling=1.0, temp_psi=0.0, temp_sigma_data=0.5,
              classifier_free_guidance_weight=0.0, softmax_latent_temperature=1.0, cfg_start=1.0, cfg_end=0.0,
-             compute_ar_accuracy=False, noise=None, trajectory=None):
+             compute_ar_accuracy=False, noise=None, trajectory=None, seed=None, rng_stream=None, sample_offset=0):
     """``noise`` (extra, optional): list with one tensor [steps, b, 6+R] per batch of N(0,1) draws (tr xyz, rot xyz,
     torsions) to replace the device generator - used by the parity tests (the reference never seeds its RNGs).
+
+    ``seed`` (extra, optional): None draws as above, from torch's device generator.  With a seed every draw of the call - the step noise and the AR picks -
+    is made on the device by the counter-based generator (``ddk_rng_noise`` / ``ddk_rng_uniform``, DDK_RNG_LAYOUT of include/ddk.h) as a pure function of
+    (seed, ``rng_stream``, global sample index, step, column): graph i of ``data_list`` is global sample ``sample_offset + i`` of the complex with the 64-bit id
+    ``rng_stream`` (default: runtime.stream_id of the complex name).  Its draws are then the same bits whatever ``batch_size``, however the samples of the
+    complex are spread over calls or ranks (a rank that holds samples 5..9 passes ``sample_offset=5``) and whatever ran before; the POSES are the same bits
+    when the model's context is also ``deterministic = 1``.  ``noise=`` together with ``seed=`` is a ValueError.
 
     ``visualization_list`` (utils/sampling.py:224-228; evaluate.py --save_visualisation): the caller's objects, anything with
     ``.add(coords, part, order)``.  As in the reference the WHOLE list is walked after EVERY batch: with n batches entry ``idx`` receives n calls
@@ -274,6 +317,10 @@ def sampling(data_list, model, inference_steps, tr_schedule, rot_schedule, tor_s
     ``trajectory`` (extra, optional): a list that receives one :data:`runtime.Trajectory` per batch - device tensors ``pos`` [steps + 1, b, n_lig, 3]
     (row k: before step k, centred coordinates like ``['ligand'].pos``; row ``steps`` = the returned poses), ``scores`` / ``perturb`` [steps, b, 6 + R] and
     ``edge_counts`` [steps, 4] - recorded by the sampler's own launches; sampling() adds no synchronisation for it."""
+    if seed is not None and noise is not None:
+        raise ValueError('ddk: sampling() takes noise= (the draws themselves) or seed= (the generator), not both')
+    if seed is not None:
+        rng_stream = _rng_stream_of(data_list, rng_stream)
     confidence, confidence_loader = None, None
     if confidence_model is not None:      # utils/sampling.py:59-62
         cg_conf = getattr(confidence_model, 'score_model', confidence_model)
@@ -318,7 +365,10 @@ def sampling(data_list, model, inference_steps, tr_schedule, rot_schedule, tor_s
                 temp_lig_pos = batch['ligand'].pos
                 if 'ar_pos' in batch['ligand']:
                     batch['ligand'].pos = batch['ligand'].ar_pos
-                latent_h = ar_model.encode_ar(batch, softmax_latent_temperature)
+                if seed is None:
+                    latent_h = ar_model.encode_ar(batch, softmax_latent_temperature)
+                else:
+                    latent_h = ar_model.encode_ar(batch, softmax_latent_temperature, rng=(seed, rng_stream, sample_offset + batch_id * batch_size))
                 batch['ligand'].pos = temp_lig_pos
                 batch['ligand'].latent_h, batch['receptor'].latent_h = latent_h
                 cx.set_latents(latent_h[0], latent_h[1], 0.0)
@@ -334,6 +384,8 @@ def sampling(data_list, model, inference_steps, tr_schedule, rot_schedule, tor_s
                 z = noise[batch_id].to(device)
             elif no_random or ode:
                 z = None
+            elif seed is not None:
+                z = score_model.ctx.rng_noise(seed, rng_stream, sample_offset + batch_id * batch_size, b, inference_steps, 6 + cx.R, 6 + R, noise_coeff=nc)
             else:
                 z = draw_noise(inference_steps, b, cx.R, R, nc, device)
             if trajectory is not None:

@@ -358,6 +358,55 @@ int64_t ddk_ligand_transformation_mask_workspace(int32_t n_lig, int32_t M);
 int ddk_ligand_transformation_mask(ddk_ctx* ctx, int32_t n_lig, const int32_t* bond_index, int32_t M, uint8_t* edge_mask_out, uint8_t* mask_rotate_out,
                                    int32_t cap_rot, int32_t* count_out /* [2] */, void* workspace, void* stream);
 
+/* ---- the sampler's random draws, made on the device by a counter-based generator: every number is a pure function of
+ *      (seed, complex, sample, step, column), so a pose's draws do not depend on the batch size, on how many ranks share the complex, on the calls made
+ *      before, or on any host or torch generator.  (The reference never seeds its RNGs: utils/sampling.py:22-32, 146-164.)  Like the calls above these
+ *      take no ddk_complex, allocate nothing and do not synchronise; all data pointers are DEVICE pointers; the work is enqueued on `stream`.
+ *
+ *      The layout below is an ABI contract: for a given DDK_RNG_LAYOUT the number stream never changes.
+ *      Generator: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85), csrc/k_philox.h, plain host/device C++.
+ *        key = (seed_lo, seed_hi)                        the low and high words of `seed`
+ *        counter c0 = stream_lo, c1 = stream_hi          the 64-bit id of the complex, `stream_id` (the Python shim: FNV-1a of its name)
+ *                c2 = sample                             the GLOBAL sample index sample0 + b
+ *                c3 = purpose << 28 | step << 8 | block  purpose: 4 bits; step < 2^20; block < 256; every block yields 4 words
+ *        purpose 0  step noise                 step = the reverse step index      column c uses block c / 4
+ *                1  initial torsion uniforms   step = 0                           torsion r uses block r / 4, word r % 4
+ *                2  initial rotation           step = 0                           block 0, four normals
+ *                3  initial translation        step = 0                           block 0, the first three normals
+ *                4  AR pick uniform            step = decoding_idx                block 0, word 0
+ *                5  rotation of ar_pos (ar_args.no_randomness, utils/sampling.py:36-46)   step = 0, as purpose 2
+ *      Words -> draws, in fp32, every operation as written:
+ *        uniform      u = (x >> 8) * 2^-24: in [0, 1), exact
+ *        torsion      (float)pi * (2u - 1): the inner term is exact, one rounding
+ *        normals      a block gives two Box-Muller pairs, from words (0, 1) and (2, 3): u1 = ((x0 >> 8) + 1) * 2^-24 in (0, 1], u2 = (x1 >> 8) * 2^-24,
+ *                     r = sqrtf(-2 * logf(u1)), z0 = r * cospif(2 * u2), z1 = r * sinpif(2 * u2), the accurate library functions (no fast-math
+ *                     intrinsics).  Column c of a row takes normal c % 4 of block c / 4.  |z| <= sqrt(48 ln 2) = 5.768 by construction; u1 = 1 gives a
+ *                     signed zero and never NaN.
+ *        rotation     the four normals are the quaternion (x, y, z, w): normalised, then the row-major matrix of scipy's Rotation.from_quat;
+ *                     |q|^2 < 2^-60: the identity
+ *        translation  tr_sigma * z
+ *      The uniforms and torsions are defined bit for bit; a normal is defined up to the last bits of logf / sinpif / cospif of the device library
+ *      it was built with (the same library gives the same bits on every call, batch size and rank).
+ *
+ *      ddk_rng_noise: out [steps, B, n_cols] = what ddk_sample's `noise` argument reads: row (k, b) is step step0 + k of sample sample0 + b; columns at
+ *        or past n_active_cols are written 0 (torsion columns a no_torsion run does not use); a step whose three noise_coeff entries are all zero is
+ *        written 0 and draws nothing (no_final_step_noise).  noise_coeff: HOST [steps, 3] as ddk_sample takes it, or NULL: every step is active.  One
+ *        launch per run of active steps, one memset per run of inactive ones.
+ *      ddk_rng_initial: the draws ddk_randomize_position takes: tor_out [B, n_rot] (purpose 1; NULL: not drawn), rot_out [B, 3, 3] (purpose_rot: 2, or 5
+ *        for the pose the AR model sees), tr_out [B, 3] = tr_sigma * z (purpose 3; NULL: not drawn).  One launch.
+ *      ddk_rng_uniform: out [B], the `uniforms` argument of ddk_ar_decode for latent dimension decoding_idx.  One launch.
+ *      Limits: 1 <= B, sample0 >= 0, sample0 + B <= 2^31 - 1, 0 <= step0, 1 <= steps, step0 + steps <= 2^20, 1 <= n_cols <= 1024,
+ *      0 <= n_active_cols <= n_cols, 0 <= n_rot <= 1024, 0 <= decoding_idx < 2^20, purpose_rot 2 or 5; anything else, or a NULL output (out, rot_out),
+ *      is DDK_ERR_INVALID with a ddk_last_error text, and nothing is enqueued. */
+#define DDK_RNG_LAYOUT 1
+int ddk_rng_noise(ddk_ctx* ctx, uint64_t seed, uint64_t stream_id, int32_t sample0, int32_t B, int32_t step0, int32_t steps, int32_t n_cols,
+                  int32_t n_active_cols, const float* noise_coeff /* HOST [steps, 3] or NULL */, float* out /* [steps, B, n_cols] */, void* stream);
+int ddk_rng_initial(ddk_ctx* ctx, uint64_t seed, uint64_t stream_id, int32_t sample0, int32_t B, int32_t n_rot, float tr_sigma,
+                    int32_t purpose_rot /* 2 or 5 */, float* tor_out /* [B, n_rot] or NULL */, float* rot_out /* [B, 3, 3] */,
+                    float* tr_out /* [B, 3] or NULL */, void* stream);
+int ddk_rng_uniform(ddk_ctx* ctx, uint64_t seed, uint64_t stream_id, int32_t sample0, int32_t B, int32_t decoding_idx, float* out /* [B] */,
+                    void* stream);
+
 /* ---- a1-a2: the reverse-diffusion loop of sampling()  utils/sampling.py:105-198 for one batch:
  *      per step  perturb = score_coeff*score + noise_coeff*z  (coefficients are the host scalars of
  *      sampling.py:137-192, including the low-temperature variant), then ddk_se3_update.
