@@ -691,7 +691,7 @@ void model_destroy(ddk_ctx* ctx);   // model.hip
 
 extern "C" {
 
-const char* ddk_version(void) { return "ddk 0.8 (gfx950)"; }      // 0.8: conv_kernel = 0 is the two-limb / three-product form of the f16-limb kernel (k_conv_x2.hip), the three-limb / six-product form (the default of 0.4 - 0.7) is conv_kernel = 3; 0.7: conv_kernel = 2 left the library (tools/variants/), ddk_tp_forward walks columns (flat 16-B reads), ddk_debug_set_alloc_limit; 0.6: conv_kernel = 2 (k_conv_y.hip), streaming ddk_tp_forward, confidence edge capacity from geometry; 0.5: ddk_config.confidence_mode + ddk_score_confidence; 0.4: three-limb records carry limbs at their own weight + tile descriptors; conv_f16x3 removed (INTEGRATION.md "ABI notes")
+const char* ddk_version(void) { return "ddk 0.8 (gfx950)"; }      // 0.8: conv_kernel = 0 is the two-limb / three-product form of the f16-limb kernel (k_conv_x2.hip), the three-limb / six-product form (the default of 0.4 - 0.7) is conv_kernel = 3; 0.7: conv_kernel = 2 left the library (the kernel itself was removed later: the last tree carrying it, under tools/variants/, is cd91202), ddk_tp_forward walks columns (flat 16-B reads), ddk_debug_set_alloc_limit; 0.6: conv_kernel = 2 (k_conv_y.hip), streaming ddk_tp_forward, confidence edge capacity from geometry; 0.5: ddk_config.confidence_mode + ddk_score_confidence; 0.4: three-limb records carry limbs at their own weight + tile descriptors; conv_f16x3 removed (INTEGRATION.md "ABI notes")
 
 int ddk_create(const ddk_config* cfg, ddk_ctx** out) {
   if (!cfg || !out) return DDK_ERR_INVALID;
@@ -708,12 +708,8 @@ int ddk_create(const ddk_config* cfg, ddk_ctx** out) {
     return fail(ctx, DDK_ERR_INVALID, "only 32-wide sigma / distance embeddings are compiled in");
   if (cfg->deterministic && cfg->all_atoms)
     return fail(ctx, DDK_ERR_INVALID, "deterministic scatter is implemented for the score model (not with all_atoms)");
-#ifdef DDK_VARIANT_CONV_Y
-  if (cfg->conv_kernel < 0 || cfg->conv_kernel > 3) return fail(ctx, DDK_ERR_INVALID, "conv_kernel must be 0, 1, 2 (variant build) or 3");
-#else
   if (cfg->conv_kernel < 0 || cfg->conv_kernel > 3 || cfg->conv_kernel == 2)
-    return fail(ctx, DDK_ERR_INVALID, "conv_kernel must be 0 (two f16 limbs per operand, three products), 1 (fp32 MFMA) or 3 (three f16 limbs, six products); 2 (round 5's software-pipelined form) lives under tools/variants/ and is not part of libddk.so");
-#endif
+    return fail(ctx, DDK_ERR_INVALID, "conv_kernel must be 0 (two f16 limbs per operand, three products), 1 (fp32 MFMA) or 3 (three f16 limbs, six products); 2 (round 5's software-pipelined form) is retired; the last tree that carries it, under tools/variants/, is cd91202");
   if (cfg->device < 0) {
     ctx->host_only = true;   // packing-only context (CPU tests); every launch entry point refuses to run
     return DDK_OK;

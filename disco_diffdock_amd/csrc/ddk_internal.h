@@ -276,7 +276,6 @@ struct ConvLaunch {
   const int32_t* gend = nullptr;
   uint32_t* trace = nullptr;   // != null (three-limb kernel, split gather path): workgroup 0 records its half-phase time stamps here
   int trace_coarse = 0;        // one record per unit instead of per tile (no stamps inside the tile loop)
-  bool use_y = false;          // variant builds only (DDK_VARIANT_CONV_Y): tools/variants/k_conv_y.hip for the gather launches with node terms
 };
 hipError_t launch_conv_fused(const ConvLayerDev& L, const ConvLaunch& a, int n_cu, hipStream_t s);
 hipError_t launch_conv_fused_x(const ConvLayerDev& L, const ConvLaunch& a, int n_cu, hipStream_t s);   // k_conv_x.hip (three f16 limbs per operand, six products)

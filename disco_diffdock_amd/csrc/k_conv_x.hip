@@ -48,7 +48,7 @@
 #define conv_x3_kernel conv_x2_kernel
 #define launch_conv_fused_x launch_conv_fused_x2
 #define conv_prepare_device_x conv_prepare_device_x2
-#include "k_conv_x_epi2_gen.inc"     // the tile epilogue as one asm statement per ring stage, generated with GEN_ONE_ACC=1: one accumulator, nothing to fold
+#include "k_conv_x_epi2_gen.inc"     // the tile epilogue as one asm statement per ring stage, generated for one accumulator chain: nothing to fold
 // TWO limbs per operand (hi = fp16(x), mid = fp16(x - hi): |x - hi - mid| <= 2^-22 |x|) and the three products hi.hi + hi.mid + mid.hi in ONE accumulator: 14 MFMAs per tile.
 // The fourth product mid.mid is <= 2^-22 relative - the size of the operands' own truncation - and is dropped (it rides for free in the packed K = 8 tail, where
 // {W_hi, W_mid} x {h_hi, h_mid} is one MFMA either way); a product is off by <= 3 * 2^-22, a K = 72 dot product by less than the classical fp32 bound 72 * 2^-24
@@ -889,9 +889,6 @@ hipError_t conv_prepare_device_x() {
   if (e == hipSuccess)
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_x3_kernel<false, false, false, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)CONV_X_LDS_BYTES);
-#if defined(DDK_VARIANT_CONV_Y) && !defined(X3_TWO_LIMBS)
-  if (e == hipSuccess) e = conv_prepare_device_y();
-#endif
   return e;
 }
 
@@ -926,12 +923,6 @@ hipError_t launch_conv_fused_x(const ConvLayerDev& L, const ConvLaunch& a, int n
     conv_det_fix(k, a, L.dout, s);
     return hipGetLastError();
   }
-#if defined(DDK_VARIANT_CONV_Y) && !defined(X3_TWO_LIMBS)      // tools/variants/k_conv_y.hip (round 5's one-wave-per-SIMD form, +9 %): linked by tools/build_variant_y.sh only
-  if (a.gather && a.pre != nullptr && (a.trace == nullptr || a.trace_coarse == 1) && L.epi_ok && a.use_y) {
-    X.trace = a.trace;      // (its TRACE instantiation writes the per-unit records only)
-    return launch_conv_y(X, n_cu, s);
-  }
-#endif
   // the generated asm epilogue of the hot instantiation hard-codes the column shapes of this model family (a scalar flush closes 4 row quads, a vector
   // flush 3, the shared tail sits behind a scalar flush, no l = 2 rows): a tile table outside them must not reach it
   if (a.gather && a.pre != nullptr && !L.epi_ok) return hipErrorInvalidValue;

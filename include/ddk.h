@@ -70,7 +70,7 @@ typedef struct ddk_config {
    *    ddk 0.4 - 0.7, ~35 % more conv time than 0.
    * 1: v_mfma_f32_32x32x2_f32, plain fp32 FMA chains (k_conv.hip) - the stated fallback.  All three apply to the score model, its heads and the all-atom
    *    confidence model's conv layers.
-   *    (Round 5's value 2 - a software-pipelined one-wave-per-SIMD form, measured 9 % slower - is refused: the kernel lives under tools/variants/.) */
+   *    (Round 5's value 2 - a software-pipelined one-wave-per-SIMD form, measured 9 % slower - is refused: the kernel was removed, the last tree carrying it, under tools/variants/, is cd91202.) */
   int32_t conv_kernel;
   /* 1: fixed summation order per node in the score model's conv layers and heads (scatter_mean of tensor_layers.py:159): edges are
    *    sorted by the receiving node, so run tails STORE and the runs that straddle 32-edge tiles are folded in tile order by a second

@@ -2,7 +2,7 @@
 
 * the streaming FasterTensorProduct kernel (k_tp.hip, the BASELINE metric's HBM-bound form) at E = 200 000 against the fp64 oracle, every conv layer's
   shape, and on a weight tensor that is only 4-byte aligned;
-* ddk_config.conv_kernel = 2 (round 5's k_conv_y.hip, now under tools/variants/) is refused by the product library;
+* ddk_config.conv_kernel = 2 (round 5's k_conv_y.hip; removed, the last tree carrying it, under tools/variants/, is cd91202) is refused by the product library;
 * the pocket-bound bracket of bench.py as a 20-step oracle trajectory;
 * ddk_create on a device ordinal the box does not have."""
 import ctypes as C
@@ -78,8 +78,8 @@ def test_tp_stream_kernel_dword_aligned_weights(dev):
 
 
 def test_conv_kernel_2_is_refused_by_the_product_library(dev):
-    """Round 5's ddk_config.conv_kernel = 2 (the one-wave-per-SIMD form, 9 % slower) left libddk.so in round 6 (tools/variants/k_conv_y.hip,
-    tools/build_variant_y.sh): the product library refuses the value with a message instead of silently running kernel 0."""
+    """Round 5's ddk_config.conv_kernel = 2 (the one-wave-per-SIMD form, 9 % slower) left libddk.so in round 6 and was removed later (profiles/r05_conv_kernel_experiments.md
+    keeps its result; the last tree carrying it, under tools/variants/, is cd91202): the library refuses the value with a message instead of silently running kernel 0."""
     from disco_diffdock_amd.runtime import Context
     with pytest.raises(RuntimeError) as ei:
         Context(device=0, conv_kernel=2)

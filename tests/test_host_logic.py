@@ -427,17 +427,19 @@ def test_bench_quotes_pmc_traffic_only_for_the_profiled_kernel(tmp_path, monkeyp
 
 def test_build_stamp_covers_the_public_headers_and_the_product_has_no_variant_kernel():
     """include/ddk.h and ddk_debug.h had dropped out of every object's content stamp (a change of ddk_config would not have
-    recompiled anything); VERDICT r05 #7: round 5's opt-in conv kernel lives under tools/variants/ and is not a source of libddk.so."""
+    recompiled anything); VERDICT r05 #7: round 5's opt-in conv kernel is not a source of libddk.so (it was removed altogether: the last tree carrying it, under
+    tools/variants/, is cd91202)."""
     from disco_diffdock_amd import build
     hs = [os.path.normpath(h) for h in build.stamp_headers()]
     for name in ('ddk.h', 'ddk_debug.h'):
         assert os.path.normpath(os.path.join(ROOT, 'include', name)) in hs, name
     assert any(h.endswith('k_conv_x_epi_gen.inc') for h in hs) and all(os.path.exists(h) for h in hs)
     assert 'k_conv_y.hip' not in build.SOURCES and not os.path.exists(os.path.join(ROOT, 'disco_diffdock_amd', 'csrc', 'k_conv_y.hip'))
-    assert os.path.exists(os.path.join(ROOT, 'tools', 'variants', 'k_conv_y.hip'))
+    assert not os.path.exists(os.path.join(ROOT, 'tools', 'variants'))
     # a stray -D cannot produce a wrong-answer product library: the timing-only ablations and the dropped alternatives are gone from the product sources
     import re
-    gone = ('X3_ABL_', 'X3_PF2', 'X3_CXX_EPI', 'X3_KEEP_MIDMID', 'X_PROLOGUE_TILES', 'DDK_ABL_', 'DDK_TIMING_ONLY_BUILD', 'DDK_VARIANT_BUILD')
+    gone = ('X3_ABL_', 'X3_PF2', 'X3_CXX_EPI', 'X3_KEEP_MIDMID', 'X_PROLOGUE_TILES', 'DDK_ABL_', 'DDK_TIMING_ONLY_BUILD', 'DDK_VARIANT_BUILD',
+            'DDK_VARIANT_CONV_Y', 'launch_conv_y', 'conv_prepare_device_y', 'use_y')
     csrc = os.path.join(ROOT, 'disco_diffdock_amd', 'csrc')
     for d, _, files in os.walk(csrc):
         for f in files:
@@ -445,3 +447,20 @@ def test_build_stamp_covers_the_public_headers_and_the_product_has_no_variant_ke
             for name in gone:
                 assert name not in src, (f, name)
             assert not re.search(r'(?<!GEN_)\bONE_ACC\b', src), f
+
+
+def test_generated_conv_epilogues_are_what_the_generator_emits():
+    """csrc/k_conv_x_epi_gen.inc and k_conv_x_epi2_gen.inc are committed and the build does not run their generator: they must be, byte for byte, what
+    tools/gen_conv_x_epi.py returns, and importing the generator writes nothing."""
+    import importlib.util
+    csrc = os.path.join(ROOT, 'disco_diffdock_amd', 'csrc')
+
+    def snapshot():
+        return {f: open(os.path.join(csrc, f), 'rb').read() for f in sorted(os.listdir(csrc)) if not f.endswith(('.o', '.stamp'))}
+    before = snapshot()
+    spec = importlib.util.spec_from_file_location('gen_conv_x_epi', os.path.join(ROOT, 'tools', 'gen_conv_x_epi.py'))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    assert snapshot() == before
+    assert gen.generate(False).encode() == before['k_conv_x_epi_gen.inc']
+    assert gen.generate(True).encode() == before['k_conv_x_epi2_gen.inc']

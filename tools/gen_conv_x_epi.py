@@ -1,131 +1,255 @@
 #!/usr/bin/env python3
-"""Generator of k_conv_x.hip's tile epilogue as ONE `asm volatile` statement per ring stage  ->  disco_diffdock_amd/csrc/k_conv_x_epi_gen.inc   (round 5)
+"""Generator of k_conv_x.hip's tile epilogue as ONE `asm volatile` statement per ring stage  ->  disco_diffdock_amd/csrc/k_conv_x_epi_gen.inc (two accumulator
+chains, the six-product form) and k_conv_x_epi2_gen.inc (one chain, the default two-limb form): both are committed, the build does not run this script, and
+tests/test_host_logic.py holds them to what generate() returns.
 
-k_conv_x.hip alternates the two waves of a SIMD: one bursts 28 MFMAs while its partner runs the VALU epilogue of its tile; the tile period is the wave-serial
+k_conv_x.hip alternates the two waves of a SIMD: one bursts its MFMAs while its partner runs the VALU epilogue of its tile; the tile period is the wave-serial
 chain burst + epilogue + barrier, and the compiler's epilogue carries ~40 instructions that are not the algorithm's (23-27 v_mov at the merge of the fast and
 the slow path, v_cndmask / v_cmp pairs, conservative lgkmcnt(0) waits: VERDICT r04 #1a).  This statement is the whole epilogue - bias, ring stores, fold,
-tile kind, packed quad, flush - with the accumulators as in/out operands, D0 / D1 / f0 in pinned registers (element access) and scalar branches inside, so every
-tile kind works on the same registers.  The instruction streams are tools/gen_conv_y.py's (same arithmetic, same order as the C++ epilogue it replaces;
-reference models/tensor_layers.py:65-116,147-159)."""
+tile kind, packed quad, flush - with the accumulators as in/out operands, D0 / D1 / f0 in pinned registers (element access) and scalar branches INSIDE the
+statement, so that every tile kind works on the same registers (a C++ switch around per-kind statements made the compiler copy 20-40 registers at every
+merge).  Same arithmetic, same order as the C++ epilogue it replaces (reference models/tensor_layers.py:65-116,147-159).  The compiler does not count the LDS
+operations inside asm: every s_waitcnt below is placed by hand."""
 import os
-import gen_conv_y as G
+from collections import namedtuple
 
 TB, LIMB = 13968, 4608
 BIAS_OFF = 3 * LIMB
-# registers: D0 = v[16:31] (in/out: folded in place), D1 = v[32:47], f0 = v[48:51]; scratch v0..v15 (bias; then f1 v0-3, f2 v4-7, g0 v8-11, R v12-15; flush values v0-8,
-# w = v / sqrt2 in v9-11), v52 packed-quad sum / g0 address, v53 flush address
-G.DBASE['x'] = 16
-G._Y[0] = 'x'
-G.B[:] = [f'v{i}' for i in range(16)]
-F0 = [f'v{48 + i}' for i in range(4)]
-G.F = F0 + [f'v{i}' for i in range(12)]
-G.FQ[:] = [f'v{i}' for i in range(9)]
-G.FO = 'v53'
-G.XQ = 'v52'
-R = ['v12', 'v13', 'v14', 'v15']
-CLOBBER = [f'v{i}' for i in range(16)] + ['v52', 'v53']
+
+# The register assignment.  d: base of D0 (folded in place; D1 follows it); bias: b0..b3; feat: f0, f1, f2, g0; flushv: the flush's out values (the first 9) and
+# w = v / sqrt2 (the last 3); flush_addr: the flush address; quad: packed-quad sum / g0 address; r: the RTS kind's second scalar accumulator (scratch otherwise)
+Regs = namedtuple('Regs', 'd bias feat flushv flush_addr quad r')
 
 
-def fix(lines):
+def vregs(lo, n):
+    return tuple(f'v{lo + i}' for i in range(n))
+
+
+# D0 = v[16:31] (in/out), D1 = v[32:47], f0 = v[48:51]; scratch v0..v15 (bias; then f1 v0-3, f2 v4-7, g0 v8-11, R v12-15; flush values v0-8, w v9-11), v52, v53
+X = Regs(d=16, bias=vregs(0, 16), feat=vregs(48, 4) + vregs(0, 12), flushv=vregs(0, 12), flush_addr='v53', quad='v52', r=vregs(12, 4))
+CLOBBER = list(vregs(0, 16)) + ['v52', 'v53']
+
+
+def aA(rq):
+    return f'%[aA{rq}]'
+
+
+def aV(rq, c):
+    return f'%[aV{rq}{c}]'
+
+
+def aX(rq, c):
+    return f'%[aX{rq}{c}]'
+
+
+def acc_ops():
+    ops = [(f'aA{rq}', '+v', f'accA[{rq}]') for rq in range(4)]
+    for rq in range(4):
+        for c in range(3):
+            ops.append((f'aV{rq}{c}', '+v', f'accV[{rq}][{c}]'))
+            ops.append((f'aX{rq}{c}', '+v', f'accX[{rq}][{c}]'))
+    return ops
+
+
+def main_stream(rg, kind):
+    """the tensor-product FMAs of one tile kind: RA / RT (scalar rows), TV0..TV3 (vector rows; bit 0 / 1: row pair 01 / 23 feeds the cross term), RTS"""
+    f = [rg.feat[0:4], rg.feat[4:8], rg.feat[8:12]]
+    dy = [f'v{rg.d + i}' for i in range(16)]
     out = []
-    for ln in lines:
-        if isinstance(ln, tuple):
-            continue          # ('need', ...) markers: the waits are placed by hand below
-        for k in range(4):
-            ln = ln.replace(f'%[R{k}]', R[k])
-        ln = ln.replace('%[pchan]', '%[chan4]')      # (gen_conv_y's name of the column offset operand)
-        out.append(ln)
+    if kind in ('RA', 'RT'):
+        acc = aA if kind == 'RA' else (lambda rq: aV(rq, 0))
+        for j in (3, 2, 1, 0):          # fmaf(f.x, D0, fmaf(f.y, D1, fmaf(f.z, D2, fmaf(f.w, D3, acc))))
+            for rq in range(4):
+                out.append(f'v_fmac_f32 {acc(rq)}, {f[0][j]}, {dy[4 * rq + j]}')
+    elif kind.startswith('TV'):
+        x = int(kind[2])
+        x01, x23 = bool(x & 1), bool(x & 2)
+        # f0 is an operand; f1 / f2 are read here and waited for in front of their first use (f2 is the youngest LDS operation then)
+        out += [f'ds_read_b128 v[{f[1][0][1:]}:{f[1][3][1:]}], %[fpa] offset:16', f'ds_read_b128 v[{f[2][0][1:]}:{f[2][3][1:]}], %[fpa] offset:32']
+        for c in range(3):
+            if c:
+                out.append(f's_waitcnt lgkmcnt({2 - c})')
+            for j in (1, 0, 3, 2):
+                cross = x01 if j < 2 else x23
+                for rq in range(3):
+                    tgt = aX(rq, c) if cross else aV(rq, c)
+                    out.append(f'v_fmac_f32 {tgt}, {f[c][j]}, {dy[4 * rq + j]}')
+    elif kind == 'RTS':
+        for j in (1, 0):
+            for rq in range(4):
+                out.append(f'v_fmac_f32 {aV(rq, 0)}, {f[0][j]}, {dy[4 * rq + j]}')
+        for rq in range(4):
+            out.append(f'v_mul_f32 {rg.r[rq]}, {f[0][3]}, {dy[4 * rq + 3]}')
+        for rq in range(4):
+            out.append(f'v_fmac_f32 {rg.r[rq]}, {f[0][2]}, {dy[4 * rq + 2]}')
     return out
 
 
-def flush(mode, rts):
-    G.FO, G.XQ = 'v53', 'v52'
-    lines = fix(G.flush_stream(mode))
+def packed_stream(rg):
+    g = rg.feat[12:16]
+    dy = [f'v{rg.d + i}' for i in range(16)]
+    out = [f'v_mul_f32 {rg.quad}, {g[3]}, {dy[15]}', f'v_fmac_f32 {rg.quad}, {g[2]}, {dy[14]}', f'v_fmac_f32 {rg.quad}, {g[1]}, {dy[13]}', f'v_fmac_f32 {rg.quad}, {g[0]}, {dy[12]}']
+    for i in range(3):
+        out.append(f'v_fmac_f32 {aA(i)}, %[pk{i}], {rg.quad}')
+    return out
+
+
+DPP = ['row_shr:1 row_mask:0xf bank_mask:0xf', 'row_shr:2 row_mask:0xf bank_mask:0xf', 'row_shr:4 row_mask:0xf bank_mask:0xf',
+       'row_shr:8 row_mask:0xf bank_mask:0xf', 'row_bcast:15 row_mask:0xa bank_mask:0xf']
+SM = ['sm1', 'sm2', 'sm4', 'sm8', 'sm16']
+
+
+def scan_stream(vals):
+    """segmented scan, the step masks as 0/1 floats: every Hillis-Steele step is ONE v_fmac_f32_dpp"""
+    # a VALU result needs two wait states before a DPP read of it: the other channels' instructions provide them (>= 4 channels interleaved)
+    out = []
+    for step in range(5):
+        for v in vals:
+            out.append(f'v_fmac_f32_dpp {v}, {v}, %[{SM[step]}] {DPP[step]} bound_ctrl:1')
+    return out
+
+
+def atomics(rg, vals, offsets):
+    # ONE item: nothing may come between the two exec writes (run tails only)
+    lines = ['s_mov_b64 %[sv], exec', 's_and_b64 exec, exec, %[tail]']
+    for v, o in zip(vals, offsets):
+        lines.append(f'global_atomic_add_f32 {rg.flush_addr}, {v}, %[sumbase]' + (f' offset:{o}' if o else ''))
+    lines.append('s_mov_b64 exec, %[sv]')
+    return ['\\n\\t'.join(lines)]
+
+
+def flush_stream(rg, mode, rts=False):
+    """the flush of the column this tile closes (k_conv_x.hip finish_tile): out values, resets, segmented scan, atomics.  mode 'S' scalar / 'V' vector column;
+    rts: an RTS column's scalar accumulator restarts from R (R is scratch between tiles here: it is not reset)"""
+    out = []
     if mode == 'S':
-        res = []
-        for ln in lines:
-            if ln.startswith('v_mov_b32 v1') and ln.endswith(', 0') and ln.split()[1].rstrip(',') in R:
-                continue                                              # (R is scratch here: no reset)
-            if not rts:
-                for k in range(4):
-                    ln = ln.replace(f'v_mov_b32 %[aV{k}0], {R[k]}', f'v_mov_b32 %[aV{k}0], 0')
-            res.append(ln)
-        return res
-    pre = ['v_mul_f32 v9, 0x3f3504f3, %[vx]', 'v_mul_f32 v10, 0x3f3504f3, %[vy]', 'v_mul_f32 v11, 0x3f3504f3, %[vz]']
-    return pre + [ln.replace('%[wx]', 'v9').replace('%[wy]', 'v10').replace('%[wz]', 'v11') for ln in lines]
+        m = rg.flushv[0:4]
+        for rq in range(4):
+            out.append(f'v_fma_f32 {m[rq]}, {aA(rq)}, %[s0], {aV(rq, 0)}')
+        for rq in range(4):
+            out.append(f'v_mul_f32 {m[rq]}, %[oscv], {m[rq]}')
+        for rq in range(4):
+            out.append(f'v_mov_b32 {aA(rq)}, 0')
+            out.append(f'v_mov_b32 {aV(rq, 0)}, {rg.r[rq] if rts else 0}')
+        out.append(f'v_add3_u32 {rg.flush_addr}, %[vrow], %[chan4], %[hh4]')
+        out += scan_stream(m)
+        out += atomics(rg, m, [8 * rq for rq in range(4)])
+    else:
+        m, W = rg.flushv[0:9], rg.flushv[9:12]
+        V = ['%[vx]', '%[vy]', '%[vz]']
+        for c in range(3):
+            out.append(f'v_mul_f32 {W[c]}, 0x3f3504f3, {V[c]}')
+        for rq in range(3):
+            for c in range(3):          # osc * fma(X[c+1], w[c+2], fma(-X[c+2], w[c+1], fma(sa, v[c], s0 * accV[c])))
+                c1, c2 = (c + 1) % 3, (c + 2) % 3
+                t = m[3 * rq + c]
+                out.append(f'v_mul_f32 {t}, %[s0], {aV(rq, c)}')
+                out.append(f'v_fmac_f32 {t}, {aA(rq)}, {V[c]}')
+                out.append(f'v_fma_f32 {t}, -{aX(rq, c2)}, {W[c1]}, {t}')
+                out.append(f'v_fmac_f32 {t}, {aX(rq, c1)}, {W[c2]}')
+        for t in m:
+            out.append(f'v_mul_f32 {t}, %[oscv], {t}')
+        for rq in range(3):
+            out.append(f'v_mov_b32 {aA(rq)}, 0')
+            for c in range(3):
+                out.append(f'v_mov_b32 {aV(rq, c)}, 0')
+                out.append(f'v_mov_b32 {aX(rq, c)}, 0')
+        out.append(f'v_mov_b32 {aA(3)}, 0')
+        out.append(f'v_add3_u32 {rg.flush_addr}, %[vrow], %[chan4], %[hh12]')
+        out += scan_stream(m)
+        out += atomics(rg, m, [24 * rq + 4 * c for rq in range(3) for c in range(3)])
+    return out
 
 
-def kind_body(kind):
-    body = []
-    if kind.startswith('TV'):
-        body += [f'ds_read_b128 v[0:3], %[fpa] offset:16', f'ds_read_b128 v[4:7], %[fpa] offset:32']
-        ms = G.main_stream(kind, packed=False)
-        out, seen = [], 0
-        for it in ms:
-            if isinstance(it, tuple):
-                if it[1] == 'f1':
-                    out.append('s_waitcnt lgkmcnt(1)')
-                elif it[1] == 'f2':
-                    out.append('s_waitcnt lgkmcnt(0)')
-                continue
-            out.append(it)
-        return body + fix(out)
-    return fix(G.main_stream(kind, packed=False))
+def dispatch_split(variants, sel, tag):
+    """variants: list of (selector value, lines), the COMMON one first.  Returns (inline, out_of_line): the common variant runs straight through one
+    untaken branch; the others live behind the statement's exit jump and come back to the join label (a taken branch is a bubble in a wave-serial
+    epilogue: the common tile pays for none)"""
+    common_val, common_body = variants[0]
+    inline = [f's_cmp_lg_u32 %[{sel}], {common_val}', f's_cbranch_scc1 .L{tag}rare_%='] + common_body + [f'.L{tag}join_%=:']
+    ool = [f'.L{tag}rare_%=:']
+    rest = variants[1:]
+    for k, (val, _) in enumerate(rest[:-1]):
+        ool.append(f's_cmp_eq_u32 %[{sel}], {val}')
+        ool.append(f's_cbranch_scc1 .L{tag}v{k}_%=')
+    n = len(rest)
+    order = [n - 1] + list(range(n - 1))
+    for k in order:
+        if k != n - 1:
+            ool.append(f'.L{tag}v{k}_%=:')
+        ool += rest[k][1]
+        ool.append(f's_branch .L{tag}join_%=')
+    return inline, ool
 
 
-def epilogue(ST):
+def asm_stmt(name, lines, outs, ins, clobbers):
+    def op(lst):
+        return ', '.join(f'[{n}] "{c}"({e})' for n, c, e in lst)
+    body = ' \\\n    '.join('"' + ln + '\\n\\t"' for ln in lines)
+    cl = ', '.join(f'"{c}"' for c in clobbers)
+    return (f'#define {name}() \\\n  asm volatile( \\\n    {body} \\\n    : {op(outs)} \\\n    : {op(ins)} \\\n    : {cl})\n')
+
+
+def epilogue(rg, ST, one_acc):
     SO, SW = ST * TB, ((ST + 3) & 3) * TB
     L = []
     for j in range(4):
-        L.append(f'ds_read_b128 v[{4 * j}:{4 * j + 3}], %[ringb] offset:{SO + BIAS_OFF + 16 * j}')
+        L.append(f'ds_read_b128 v[{rg.bias[4 * j][1:]}:{rg.bias[4 * j + 3][1:]}], %[ringb] offset:{SO + BIAS_OFF + 16 * j}')
     # this thread's two chunks of record t+3 (requested at the start of the burst) into the stage tile t-1 has left
     L += ['s_waitcnt vmcnt(1)', f'ds_write_b128 %[rw0], %[st0] offset:{SW}', 's_waitcnt vmcnt(0)', f'ds_write_b128 %[rw1], %[st1] offset:{SW}']
-    if not os.environ.get('GEN_ONE_ACC'):      # (the two-limb form has one accumulator chain: nothing to fold)
+    if not one_acc:      # (the two-limb form has one accumulator chain: nothing to fold)
         for r in range(16):
-            L.append(f'v_add_f32 v{16 + r}, v{16 + r}, v{32 + r}')
+            L.append(f'v_add_f32 v{rg.d + r}, v{rg.d + r}, v{rg.d + 16 + r}')
     L.append('s_waitcnt lgkmcnt(2)')      # the bias reads; the two ring stores stay in flight
     for r in range(16):
-        L.append(f'v_fmac_f32 v{16 + r}, v{r}, %[bsc2]')
+        L.append(f'v_fmac_f32 v{rg.d + r}, {rg.bias[r]}, %[bsc2]')
     # tile kind -> selector (1 RA, 2 RT, 3 + cross bits TV, 7 RTS)
     L += ['s_and_b32 %[t0], %[w0], 3', 's_bfe_u32 %[t1], %[w0], 0x2000e', 's_add_i32 %[t1], %[t1], 3', 's_add_i32 %[t2], %[t0], 1',
           's_cmp_eq_u32 %[t0], 2', 's_cselect_b32 %[t2], %[t1], %[t2]', 's_cmp_eq_u32 %[t0], 3', 's_cselect_b32 %[sel], 7, %[t2]']
-    variants = [(1, kind_body('RA')), (2, kind_body('RT'))] + [(3 + x, kind_body(f'TV{x}')) for x in range(4)] + [(7, kind_body('RTS'))]
-    inl, ool_k = G.dispatch_split(variants, 'sel', 'k')
+    kinds = [(1, 'RA'), (2, 'RT')] + [(3 + x, f'TV{x}') for x in range(4)] + [(7, 'RTS')]
+    inl, ool_k = dispatch_split([(val, main_stream(rg, kind)) for val, kind in kinds], 'sel', 'k')
     L += inl
     # packed quad (6-channel columns: accumulator quad 3 carries another a / c row quad for channel pair xp)
+    g0 = rg.feat[12:16]
     L += ['s_bitcmp0_b32 %[w0], 7', 's_cbranch_scc1 .Lnp_%=',
-          's_lshr_b32 %[t0], %[w0], 6', 's_and_b32 %[t0], %[t0], 0xf0', 'v_add_u32 v52, %[t0], %[fra]', 'ds_read_b128 v[8:11], v52',
+          's_lshr_b32 %[t0], %[w0], 6', 's_and_b32 %[t0], %[t0], 0xf0', f'v_add_u32 {rg.quad}, %[t0], %[fra]', f'ds_read_b128 v[{g0[0][1:]}:{g0[3][1:]}], {rg.quad}',
           's_bfe_u32 %[t1], %[w0], 0x20008',
           's_cmp_eq_u32 %[t1], 0', 's_cselect_b32 %[pk0], 1.0, 0', 's_cmp_eq_u32 %[t1], 1', 's_cselect_b32 %[pk1], 1.0, 0', 's_cmp_eq_u32 %[t1], 2', 's_cselect_b32 %[pk2], 1.0, 0',
           's_waitcnt lgkmcnt(0)']
-    L += fix([it for it in G.packed_stream() if not isinstance(it, tuple)])
+    L += packed_stream(rg)
     L.append('.Lnp_%=:')
     # flush of the column this tile closes
     L += ['s_bfe_u32 %[t0], %[w0], 0x20002', 's_cmp_eq_u32 %[t0], 0', 's_cbranch_scc1 .Lnf_%=', 's_cmp_eq_u32 %[t0], 2', 's_cbranch_scc1 .Lfv_%=',
           's_cmp_eq_u32 %[sel], 7', 's_cbranch_scc1 .Lfr_%=']
-    L += flush('S', False) + ['s_branch .Lnf_%=', '.Lfr_%=:'] + flush('S', True) + ['s_branch .Lnf_%=', '.Lfv_%=:'] + flush('V', False)
+    L += flush_stream(rg, 'S') + ['s_branch .Lnf_%=', '.Lfr_%=:'] + flush_stream(rg, 'S', rts=True) + ['s_branch .Lnf_%=', '.Lfv_%=:'] + flush_stream(rg, 'V')
+    # the compiler does not see the LDS operations in here: the statement leaves none in flight
     L += ['.Lnf_%=:', 's_waitcnt lgkmcnt(0)', 's_branch .Lexit_%='] + ool_k + ['.Lexit_%=:']
     return L
 
 
-def main():
+def generate(one_acc):
+    """the text of k_conv_x_epi_gen.inc (one_acc False) or of k_conv_x_epi2_gen.inc (True: one accumulator chain, no D1 operand, nothing to fold)"""
+    rg = X
     out = ['// GENERATED by tools/gen_conv_x_epi.py - do not edit.\n']
-    accs = [o for o in G.acc_ops('') if not o[0].startswith('R')]
-    outs = [('D0', '+{v[16:31]}', 'D0')] + accs + [(n, '=&s', f'{n}_') for n in ('t0', 't1', 't2', 'sel', 'pk0', 'pk1', 'pk2', 'sv')]
-    one_acc = bool(os.environ.get('GEN_ONE_ACC'))      # one accumulator chain (the two-limb form, k_conv_x.hip X3_TWO_LIMBS -> k_conv_x2.hip): no D1 operand, nothing to fold
-    ins = ([] if one_acc else [('D1', '{v[32:47]}', 'D1')]) + [('f0', '{v[48:51]}', 'f0'), ('st0', 'v', 'st0'), ('st1', 'v', 'st1'), ('ringb', 'v', 'ringb_u'), ('rw0', 'v', 'ringw0_u'),
+    d0, d1, f0 = (f'{{v[{lo}:{lo + n - 1}]}}' for lo, n in ((rg.d, 16), (rg.d + 16, 16), (int(rg.feat[0][1:]), 4)))
+    outs = [('D0', '+' + d0, 'D0')] + acc_ops() + [(n, '=&s', f'{n}_') for n in ('t0', 't1', 't2', 'sel', 'pk0', 'pk1', 'pk2', 'sv')]
+    ins = ([] if one_acc else [('D1', d1, 'D1')]) + [('f0', f0, 'f0'), ('st0', 'v', 'st0'), ('st1', 'v', 'st1'), ('ringb', 'v', 'ringb_u'), ('rw0', 'v', 'ringw0_u'),
            ('rw1', 'v', 'ringw1_u'), ('fpa', 'v', 'fpa_u'), ('fra', 'v', 'fra_u'), ('bsc2', 'v', 'bsc2'), ('oscv', 'v', 'oscv'), ('s0', 'v', 's0'), ('vx', 'v', 'vx'),
            ('vy', 'v', 'vy'), ('vz', 'v', 'vz'), ('sm1', 'v', 'seg.m1'), ('sm2', 'v', 'seg.m2'), ('sm4', 'v', 'seg.m4'), ('sm8', 'v', 'seg.m8'), ('sm16', 'v', 'seg.m16'),
            ('vrow', 'v', 'vrow'), ('hh4', 'v', 'hh4_u'), ('hh12', 'v', 'hh12_u'), ('w0', 's', 'w0'), ('chan4', 's', 'chan4_'), ('tail', 's', 'tail_mask'),
            ('sumbase', 's', 'sumbase')]
     for ST in range(4):
-        lines = epilogue(ST)
-        txt = G.asm_stmt(f'X3_EPI_{ST}', lines, outs, ins, CLOBBER + ['memory', 'scc'])
-        out.append(txt)
-    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'disco_diffdock_amd', 'csrc', os.environ.get('GEN_OUT', 'k_conv_x_epi_gen.inc'))
-    with open(path, 'w') as f:
-        f.write('\n'.join(out))
-    print('wrote', os.path.normpath(path), sum(s.count('\n') for s in out), 'lines')
+        out.append(asm_stmt(f'X3_EPI_{ST}', epilogue(rg, ST, one_acc), outs, ins, CLOBBER + ['memory', 'scc']))
+    return '\n'.join(out)
+
+
+def main():
+    csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'disco_diffdock_amd', 'csrc')
+    for one_acc, name in ((False, 'k_conv_x_epi_gen.inc'), (True, 'k_conv_x_epi2_gen.inc')):
+        txt = generate(one_acc)
+        with open(os.path.join(csrc, name), 'w') as f:
+            f.write(txt)
+        print('wrote', os.path.normpath(os.path.join(csrc, name)), txt.count('\n'), 'lines')
 
 
 if __name__ == '__main__':
