@@ -52,6 +52,14 @@ MASK_STATUS = ('complete', 'more rotatable bonds than rows', 'a bond column that
 RNG_LAYOUT = 1
 RNG_PURPOSES = dict(noise=0, initial_torsion=1, initial_rotation=2, initial_translation=3, ar_pick=4, ar_rotation=5)
 RNG_MAX_STEPS, RNG_MAX_COLS = 1 << 20, 1024
+# the purposes of the forward process (ddk_rng_perturbation, csrc/k_noising.hip), in the same counter field; their step field holds the draw index
+RNG_FORWARD_PURPOSES = dict(forward_translation=6, forward_rotation=7, forward_torsion=8)
+# the grids of utils/so3.py and utils/torus.py that ddk_so3_rows and ddk_torus_score evaluate (csrc/k_so3.hip, csrc/k_noising.hip)
+SO3_N_EPS, SO3_X_N, SO3_MAX_ROWS, TORUS_SIGMA_N = 1000, 2000, 4096, 5000
+# what ``Context.rng_perturbation`` returns: the device arrays of ddk_perturbation (include/ddk.h); tor_* are [B, n_rot]
+Perturbation = collections.namedtuple('Perturbation', ('tr_update', 'rot_update', 'tor_update', 'tr_score', 'rot_score', 'tor_score'))
+# the columns of ``Context.score_matching_loss`` (ddk_score_matching_loss)
+LOSS_COLUMNS = ('tr_loss', 'rot_loss', 'tor_loss', 'tr_base_loss', 'rot_base_loss', 'tor_base_loss')
 
 
 def stream_id(name):
@@ -202,6 +210,7 @@ class Context:
         self._check(self.L.ddk_set_score_norm_tables(self.h, so3.ctypes.data_as(C.c_void_p), len(so3),
                                                      torus.ctypes.data_as(C.c_void_p), len(torus)), 'ddk_set_score_norm_tables')
         self._tables_set = True
+        self.score_norm_tables = (so3, torus)      # host copies: training.loss_function looks its two norms up here
 
     def export(self, what, dtype=np.float32):
         n = self.L.ddk_debug_export(self.h, what.encode(), None, 0)
@@ -390,6 +399,78 @@ class Context:
         s, st, dev = self._rng_args(seed, stream, dict(sample0=sample0, B=B, decoding_idx=decoding_idx))
         out = torch.empty(max(B, 0), dtype=torch.float32, device=dev)
         self._check(self.L.ddk_rng_uniform(self.h, s, st, sample0, B, decoding_idx, _ptr(out), _stream()), 'ddk_rng_uniform')
+        return out
+
+    # ---- the forward process and the score-matching loss (csrc/k_so3.hip, csrc/k_noising.hip) -------------
+    def so3_rows(self, eps_idx, cdf=True, score=True, exp_score_norm=True):
+        """Rows ``eps_idx`` (host integers in [0, 1000), duplicates allowed) of the IGSO(3) tables of utils/so3.py, computed in fp64 on the device
+        (ddk_so3_rows, include/ddk.h): (cdf [n, 2000], score [n, 2000], exp_score_norm [n]) float64 device tensors, None where not asked for.  The score
+        rows carry the reference's inf / NaN where the density vanishes.  No read-back."""
+        idx = np.ascontiguousarray(np.atleast_1d(np.asarray(eps_idx)).reshape(-1), dtype=np.int64)
+        if idx.size and (idx.min() < -(1 << 31) or idx.max() >= 1 << 31):
+            raise ValueError('ddk: an eps_idx entry does not fit an int32')
+        idx = idx.astype(np.int32)
+        n, dev = idx.size, torch.device('cuda', self.device)
+        ok = 1 <= n <= SO3_MAX_ROWS      # a broken limit: the call below says which
+        rows = n if ok else 1
+        c = torch.empty((rows, SO3_X_N), dtype=torch.float64, device=dev) if cdf else None
+        sc = torch.empty((rows, SO3_X_N), dtype=torch.float64, device=dev) if score else None
+        e = torch.empty(rows, dtype=torch.float64, device=dev) if exp_score_norm else None
+        self._check(self.L.ddk_so3_rows(self.h, n, idx.ctypes.data_as(C.c_void_p), _ptr(c), _ptr(sc), _ptr(e), _stream()), 'ddk_so3_rows')
+        return c, sc, e
+
+    def torus_score(self, x, sigma_idx):
+        """torus.score(x, sigma) of utils/torus.py:43-52 for the device tensor ``x`` (any shape, fp32) at the table's sigma index ``sigma_idx`` (host
+        integer in [0, 5000]: training.torus_sigma_index), evaluated in fp64 without the table (ddk_torus_score): a fresh fp32 tensor of x's shape."""
+        x = _need_cuda(x).contiguous().float()
+        out = torch.empty_like(x)
+        self._rng_args(0, 0, dict(sigma_idx=sigma_idx))
+        self._check(self.L.ddk_torus_score(self.h, x.numel(), _ptr(x), int(sigma_idx), _ptr(out), _stream()), 'ddk_torus_score')
+        return out
+
+    def rng_perturbation(self, seed, stream, sample0, B, n_rot, tr_sigma, tor_sigma, torus_sigma_idx, so3_cdf_row, so3_score_row=None, draw=0,
+                         scores=True):
+        """One noising of the global samples sample0 .. sample0 + B - 1 of complex ``stream`` under ``seed`` (ddk_rng_perturbation; purposes
+        RNG_FORWARD_PURPOSES, ``draw`` in the step field): :data:`Perturbation` of fresh device tensors, the three updates ``Complex.se3_update`` takes
+        and, with ``scores``, data.tr_score / rot_score / tor_score of apply_noise (None otherwise).  ``so3_cdf_row`` / ``so3_score_row``: one row of
+        :meth:`so3_rows` (float64 device tensors [2000]) for the rotation's noise level.  No read-back."""
+        s, st, dev = self._rng_args(seed, stream, dict(sample0=sample0, B=B, n_rot=n_rot, draw=draw, torus_sigma_idx=torus_sigma_idx))
+        rows = []
+        for name, row in (('so3_cdf_row', so3_cdf_row), ('so3_score_row', so3_score_row)):
+            if row is not None:
+                row = _need_cuda(row).contiguous()
+                if row.dtype != torch.float64 or row.numel() != SO3_X_N:
+                    raise ValueError(f'ddk: {name} must be a float64 tensor of {SO3_X_N} entries (one row of so3_rows)')
+            rows.append(row)
+        Bs, Rs = max(B, 0), max(n_rot, 0)
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        out = Perturbation(new(Bs, 3), new(Bs, 3), new(Bs, Rs), *([new(Bs, 3), new(Bs, 3), new(Bs, Rs)] if scores else [None] * 3))
+        c_out = _lib.ddk_perturbation(**{k: (v.data_ptr() if v is not None and v.numel() else None) for k, v in out._asdict().items()})
+        self._check(self.L.ddk_rng_perturbation(self.h, s, st, sample0, B, draw, n_rot, float(tr_sigma), float(tor_sigma), int(torus_sigma_idx),
+                                                _ptr(rows[0]), _ptr(rows[1]), C.byref(c_out), _stream()), 'ddk_rng_perturbation')
+        return out
+
+    def score_matching_loss(self, tr_pred, rot_pred, tor_pred, tr_score, rot_score, tor_score, tr_sigma, so3_score_norm, torus_score_norm2):
+        """The six per-sample terms of loss_function(..., apply_mean=False) (utils/training.py:21-53; ddk_score_matching_loss): device tensor [B, 6] with
+        the columns LOSS_COLUMNS.  Predictions and targets [B, 3], [B, 3] and [B, n_rot] (flat is fine); ``tor_pred`` None or n_rot = 0: the torsion
+        terms are 0.  The three scalars are host numbers: the translation sigma, so3.score_norm(rot_sigma) and torus.score_norm(tor_sigma)."""
+        f = lambda t, cols: _need_cuda(t).contiguous().float().reshape(-1, cols)
+        tr_pred, rot_pred, tr_score, rot_score = (f(t, 3) for t in (tr_pred, rot_pred, tr_score, rot_score))
+        B = tr_score.shape[0]
+        n_rot = 0
+        if tor_pred is not None and tor_score is not None and tor_score.numel():
+            n_rot = tor_score.numel() // max(B, 1)
+            tor_pred, tor_score = f(tor_pred, n_rot), f(tor_score, n_rot)
+        else:
+            tor_pred = tor_score = None
+        for name, t, shape in (('tr_pred', tr_pred, (B, 3)), ('rot_pred', rot_pred, (B, 3)), ('rot_score', rot_score, (B, 3)),
+                               ('tor_pred', tor_pred, (B, n_rot)), ('tor_score', tor_score, (B, n_rot))):
+            if t is not None and tuple(t.shape) != shape:
+                raise ValueError(f'ddk: {name} must hold {shape} values, got {tuple(t.shape)} (the library reads it through a raw pointer)')
+        out = torch.empty((B, 6), dtype=torch.float32, device=tr_score.device)
+        self._check(self.L.ddk_score_matching_loss(self.h, B, n_rot, _ptr(tr_pred), _ptr(rot_pred), _ptr(tor_pred), _ptr(tr_score), _ptr(rot_score),
+                                                   _ptr(tor_score), float(tr_sigma), float(so3_score_norm), float(torus_score_norm2), _ptr(out),
+                                                   _stream()), 'ddk_score_matching_loss')
         return out
 
     # ---- coordinates + bonds -> the static graph tables of a complex (csrc/k_build.hip) -------------

@@ -375,6 +375,7 @@ int ddk_ligand_transformation_mask(ddk_ctx* ctx, int32_t n_lig, const int32_t* b
  *                3  initial translation        step = 0                           block 0, the first three normals
  *                4  AR pick uniform            step = decoding_idx                block 0, word 0
  *                5  rotation of ar_pos (ar_args.no_randomness, utils/sampling.py:36-46)   step = 0, as purpose 2
+ *                6-8  the forward process (ddk_rng_perturbation below): translation, rotation, torsion; step = the draw index
  *      Words -> draws, in fp32, every operation as written:
  *        uniform      u = (x >> 8) * 2^-24: in [0, 1), exact
  *        torsion      (float)pi * (2u - 1): the inner term is exact, one rounding
@@ -406,6 +407,70 @@ int ddk_rng_initial(ddk_ctx* ctx, uint64_t seed, uint64_t stream_id, int32_t sam
                     float* tr_out /* [B, 3] or NULL */, void* stream);
 int ddk_rng_uniform(ddk_ctx* ctx, uint64_t seed, uint64_t stream_id, int32_t sample0, int32_t B, int32_t decoding_idx, float* out /* [B] */,
                     void* stream);
+
+/* ---- the forward half of the diffusion and the score-matching loss: what the reference's validation pass (test_epoch, utils/training.py) is made of.
+ *      NoiseTransform.apply_noise (datasets_utils/pdbbind.py:40-57) noises the true pose and records the three score targets; loss_function
+ *      (utils/training.py:14-61) sets the model's three scores against them.  Like the ddk_rng_* calls these take no ddk_complex, allocate nothing, do not
+ *      synchronise and enqueue on `stream`; all data pointers are DEVICE pointers unless marked HOST; a broken limit is DDK_ERR_INVALID with a
+ *      ddk_last_error text and nothing is enqueued.  No float atomics: the results are bit-identical run to run.
+ *
+ *      ddk_so3_rows: rows of the IGSO(3) tables of utils/so3.py, computed in fp64 instead of read from a cache (MIN_EPS 0.01, MAX_EPS 2, N_EPS 1000,
+ *        X_N 2000, L = 2000 terms).  Row i of the call has eps = 10 ** linspace(log10 0.01, log10 2, 1000)[eps_idx[i]] (the grid is computed in fp64 on the
+ *        host) on the angles omega_j = pi (j + 1) / 2000.  cdf_out [n_rows, 2000] = _cdf_vals (the cumulative sum of _density(_expansion, marginal) times
+ *        pi / 2000, so3.py:21-30, 56-58), score_out [n_rows, 2000] = _score_norms (_score, so3.py:35-43, 59), exp_score_norm_out [n_rows] =
+ *        _exp_score_norms (so3.py:61).  Every (row, omega) element is accumulated by one thread with l ascending and every term as the reference writes
+ *        it, the order that reproduces the reference's tables bit for bit on the host; the device differs from them by the last bits of its sin, cos and
+ *        exp.  score_out is written as the reference computes it, inf and NaN included: where the density vanishes (pdf below about 1e-9 of the row's
+ *        maximum) the series cancels and both tables are numerical noise, which no reachable draw reads.  exp_score_norm_out sums score^2 pdf over the
+ *        entries whose score is FINITE and whose expansion stands above the rounding noise of its own sum, |f| > 2^-40 sum_l |term_l|, only; sum(pdf)
+ *        runs over all entries.  (score^2 pdf = dSigma^2 (1 - cos omega) / (pi f) is unbounded as a cancelled f comes close to 0: without the second
+ *        condition one entry in a few hundred thousand outweighs 1e-10 of its row, as rows 44 and 55 of the reference's own table show.  The entries
+ *        left out carry less than 1e-10 of the sum; the result is within 1e-9 of the reference's on every row.)
+ *        Limits: 1 <= n_rows <= 4096, every eps_idx in [0, 1000), duplicates allowed, at least one output not NULL.  One launch per 256 rows, one
+ *        workgroup per row.
+ *
+ *      ddk_torus_score: torus.score(x, sigma) (utils/torus.py:43-52) per element without the 5001 x 5001 table: in fp64, x wrapped to [-pi, pi), |x|
+ *        quantised to the grid 10 ** linspace(-5, 0, 5001) * pi as there (natural log, clip to [0, 5000], round half to even), grad / p of torus.py:11-22
+ *        with N = 100 evaluated at that grid point and sigma = 10 ** linspace(log10 3e-3, log10 2, 5001)[sigma_idx] * pi, times -sign(x), rounded once to
+ *        fp32.  x == 0 gives 0; where p underflows to 0 the result is NaN, as in the reference's table (x index 5000 at sigma index 0); an x that is not
+ *        finite gives NaN.  sigma_idx is a HOST quantity (torus.py:49-51 in fp64 on the host's sigma), so a rounding tie cannot differ between host and
+ *        device.  Limits: n >= 0, 0 <= sigma_idx <= 5000.  One launch.
+ *
+ *      ddk_rng_perturbation: one noising of the global samples sample0 .. sample0 + B - 1 at one noise level: the three updates ddk_se3_update takes and
+ *        their score targets, from the generator above (DDK_RNG_LAYOUT 1) with three more purposes; `draw` sits in the step field, so a sample can be
+ *        noised independently up to 2^20 times:
+ *          purpose 6  forward translation   step = draw   block 0, the first three normals z: tr_update = tr_sigma * z
+ *                  7  forward rotation      step = draw   block 0, normals 0..2 = the axis a; block 1, word 0 = the uniform u
+ *                  8  forward torsion       step = draw   torsion r uses normal r % 4 of block r / 4: tor_update = tor_sigma * z
+ *        tr_score = -tr_update / tr_sigma^2 (fp32).  rot_update = a / |a| * omega in fp64, rounded once to fp32, with omega = np.interp(u, so3_cdf_row,
+ *        omegas) (so3.sample, so3.py:69-80), clamped at both ends like NumPy's, the bracket found by bisection for the first cdf[j] >= u; |a|^2 < 2^-60:
+ *        rot_update = rot_score = 0.  rot_score = np.interp(omega, omegas, so3_score_row) * rot_update / omega (so3.score_vec, so3.py:83-88) in fp64,
+ *        rounded once.  tor_score = ddk_torus_score's arithmetic on tor_update at torus_sigma_idx.  so3_cdf_row / so3_score_row [2000]: one row of
+ *        ddk_so3_rows, for so3_eps_index(rot_sigma).  None of the purposes 0-5 is touched: every existing draw keeps its bits.
+ *        out: caller-owned arrays; the updates may not be NULL (tor_update may with n_rot = 0), a score member may be (not computed; so3_score_row may
+ *        then be NULL too).  Limits: those of ddk_rng_initial (1 <= B, sample0 >= 0, sample0 + B <= 2^31 - 1, 0 <= n_rot <= 1024), 0 <= draw < 2^20,
+ *        tr_sigma, tor_sigma > 0, 0 <= torus_sigma_idx <= 5000.  One launch.
+ *
+ *      ddk_score_matching_loss: out [B, 6] = {tr_loss, rot_loss, tor_loss, tr_base_loss, rot_base_loss, tor_base_loss} per sample, the terms of
+ *        loss_function(..., apply_mean=False): tr = mean_3((pred - score)^2 sigma^2), rot = mean_3(((pred - score) / so3_score_norm)^2),
+ *        tor = sum_r((pred - score)^2 / torus_score_norm2) / (n_rot + 1e-4); the base terms are the same expressions with pred = 0.  tor arrays [B, n_rot];
+ *        n_rot = 0 or tor_pred = NULL gives 0 for the two torsion terms.  One wave per sample, fp64 inside, a fixed reduction order, each term rounded
+ *        once to fp32.  Limits: 1 <= B, 0 <= n_rot <= 1024, the three scalars > 0.  One launch. */
+int ddk_so3_rows(ddk_ctx* ctx, int32_t n_rows, const int32_t* eps_idx /* HOST [n_rows], each in [0, 1000) */,
+                 double* cdf_out /* DEVICE [n_rows, 2000] or NULL */, double* score_out /* DEVICE [n_rows, 2000] or NULL */,
+                 double* exp_score_norm_out /* DEVICE [n_rows] or NULL */, void* stream);
+int ddk_torus_score(ddk_ctx* ctx, int64_t n, const float* x /* DEVICE [n] */, int32_t sigma_idx /* in [0, 5000] */, float* score_out /* DEVICE [n] */,
+                    void* stream);
+typedef struct ddk_perturbation {           /* caller-owned DEVICE arrays; updates may not be NULL, a score member may be */
+  float *tr_update, *rot_update, *tor_update;   /* [B,3] [B,3] [B,n_rot]  what ddk_se3_update takes */
+  float *tr_score, *rot_score, *tor_score;      /* [B,3] [B,3] [B,n_rot]  data.tr_score / rot_score / tor_score */
+} ddk_perturbation;
+int ddk_rng_perturbation(ddk_ctx* ctx, uint64_t seed, uint64_t stream_id, int32_t sample0, int32_t B, int32_t draw, int32_t n_rot, float tr_sigma,
+                         float tor_sigma, int32_t torus_sigma_idx, const double* so3_cdf_row, const double* so3_score_row /* DEVICE [2000] each */,
+                         const ddk_perturbation* out, void* stream);
+int ddk_score_matching_loss(ddk_ctx* ctx, int32_t B, int32_t n_rot, const float* tr_pred, const float* rot_pred, const float* tor_pred,
+                            const float* tr_score, const float* rot_score, const float* tor_score, float tr_sigma, float so3_score_norm,
+                            float torus_score_norm2, float* out /* [B, 6] */, void* stream);
 
 /* ---- a1-a2: the reverse-diffusion loop of sampling()  utils/sampling.py:105-198 for one batch:
  *      per step  perturb = score_coeff*score + noise_coeff*z  (coefficients are the host scalars of
