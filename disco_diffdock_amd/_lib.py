@@ -44,6 +44,12 @@ class ddk_perturbation(C.Structure):
                 ('tr_score', C.c_void_p), ('rot_score', C.c_void_p), ('tor_score', C.c_void_p)]
 
 
+class ddk_match_options(C.Structure):
+    # the HOST options of ddk_conformer_match, member order of include/ddk.h
+    _fields_ = [('popsize', C.c_int32), ('maxiter', C.c_int32), ('tol', C.c_float), ('polish_iters', C.c_int32), ('n_islands', C.c_int32),
+                ('seed', C.c_uint64), ('stream_id', C.c_uint64)]
+
+
 _lib = None
 
 # every symbol include/ddk.h declares (tests check that the library exports all of them)
@@ -58,7 +64,8 @@ SYMBOLS = ['ddk_create', 'ddk_destroy', 'ddk_last_error', 'ddk_version', 'ddk_lo
            'ddk_receptor_knn_graph_workspace', 'ddk_receptor_knn_graph', 'ddk_radius_graph_workspace', 'ddk_radius_graph',
            'ddk_ligand_transformation_mask_workspace', 'ddk_ligand_transformation_mask',
            'ddk_rng_noise', 'ddk_rng_initial', 'ddk_rng_uniform',
-           'ddk_so3_rows', 'ddk_torus_score', 'ddk_rng_perturbation', 'ddk_score_matching_loss']
+           'ddk_so3_rows', 'ddk_torus_score', 'ddk_rng_perturbation', 'ddk_score_matching_loss',
+           'ddk_conformer_match_workspace', 'ddk_conformer_rmsd', 'ddk_conformer_match']
 
 # test hooks (include/ddk_debug.h): not part of the drop-in boundary
 DEBUG_SYMBOLS = ['ddk_debug_export', 'ddk_debug_read_edges', 'ddk_debug_conf_counts', 'ddk_debug_conf_table', 'ddk_debug_conf_nodes', 'ddk_debug_conf_edges', 'ddk_debug_kabsch', 'ddk_debug_axis_angle', 'ddk_debug_set_layer0_dedup', 'ddk_debug_read_patch', 'ddk_debug_split3', 'ddk_debug_conv_trace', 'ddk_debug_pool_stats', 'ddk_debug_set_conv_workgroups', 'ddk_debug_set_alloc_limit', 'ddk_debug_cross_mirror']
@@ -119,6 +126,10 @@ def lib():
     L.ddk_torus_score.argtypes = [vp, i64, vp, i32, vp, vp]
     L.ddk_rng_perturbation.argtypes = [vp, u64, u64, i32, i32, i32, i32, f32, f32, i32, vp, vp, C.POINTER(ddk_perturbation), vp]
     L.ddk_score_matching_loss.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, f32, f32, f32, vp, vp]
+    L.ddk_conformer_match_workspace.argtypes = [i32, i32, i32, i32]
+    L.ddk_conformer_match_workspace.restype = i64
+    L.ddk_conformer_rmsd.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
+    L.ddk_conformer_match.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, C.POINTER(ddk_match_options), vp, vp, vp, vp, vp, vp]
     L.ddk_sample.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.ddk_sample_trajectory.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, C.POINTER(ddk_trajectory), vp]
     L.ddk_last_graph_stats.argtypes = [vp, vp, vp, vp]

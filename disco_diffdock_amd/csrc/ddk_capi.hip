@@ -873,6 +873,64 @@ int ddk_conv_forward(ddk_ctx* ctx, int32_t layer, const float* x, int64_t N, con
   return DDK_OK;
 }
 
+// ---- conformer matching (k_match.hip): the limits both calls and the workspace query share; empty = fine
+static std::string match_bad_problem(int32_t n_lig, int32_t n_rot) {
+  if (n_lig < 3 || n_lig > MAX_LIG) return "n_lig must be in [3, " + std::to_string(MAX_LIG) + "]";
+  if (n_rot < 0 || n_rot > MATCH_MAX_ROT) return "n_rot must be in [0, " + std::to_string(MATCH_MAX_ROT) + "]";
+  return "";
+}
+
+static std::string match_bad_population(int32_t n_rot, int32_t popsize, int32_t n_islands) {
+  if (popsize < 1 || popsize > MATCH_MAX_POPSIZE) return "popsize must be in [1, " + std::to_string(MATCH_MAX_POPSIZE) + "]";
+  if (n_islands < 1 || n_islands > MATCH_MAX_ISLANDS) return "n_islands must be in [1, " + std::to_string(MATCH_MAX_ISLANDS) + "]";
+  if (match_members(popsize, n_rot) > MATCH_MAX_MEMBERS)
+    return "max(5, popsize * n_rot) = " + std::to_string(match_members(popsize, n_rot)) + " members per island, at most " + std::to_string(MATCH_MAX_MEMBERS);
+  return "";
+}
+
+int64_t ddk_conformer_match_workspace(int32_t n_lig, int32_t n_rot, int32_t popsize, int32_t n_islands) {
+  if (!match_bad_problem(n_lig, n_rot).empty() || !match_bad_population(n_rot, popsize, n_islands).empty()) return -1;
+  return match_workspace_bytes(n_lig, n_rot, popsize, n_islands);
+}
+
+int ddk_conformer_rmsd(ddk_ctx* ctx, int32_t n_lig, const float* pos0, const float* target, const uint8_t* atom_mask, const int32_t* rot_bonds,
+                       const uint8_t* mask_rotate, int32_t n_rot, int32_t M, const float* torsions, float* rmsd_out, int32_t* status_out, void* stream) {
+  if (!ctx) return DDK_ERR_INVALID;
+  if (ctx->host_only) return fail(ctx, DDK_ERR_STATE, "host-only context (device < 0) cannot launch kernels");
+  const std::string bad = match_bad_problem(n_lig, n_rot);
+  if (!bad.empty()) return fail(ctx, DDK_ERR_INVALID, "ddk_conformer_rmsd: " + bad);
+  if (M < 1 || M > MATCH_MAX_VECTORS) return fail(ctx, DDK_ERR_INVALID, "ddk_conformer_rmsd: M must be in [1, " + std::to_string(MATCH_MAX_VECTORS) + "]");
+  if (!pos0 || !target || !rmsd_out || !status_out || (n_rot > 0 && (!rot_bonds || !mask_rotate || !torsions)))
+    return fail(ctx, DDK_ERR_INVALID, "ddk_conformer_rmsd: null argument (only atom_mask, and the rotor arrays with n_rot = 0, may be null)");
+  const MatchProblem P{n_lig, n_rot, pos0, target, atom_mask, rot_bonds, mask_rotate};
+  hipError_t e = launch_conformer_rmsd(P, M, torsions, rmsd_out, status_out, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "conformer_rmsd launch");
+  return DDK_OK;
+}
+
+int ddk_conformer_match(ddk_ctx* ctx, int32_t n_lig, const float* pos0, const float* target, const uint8_t* atom_mask, const int32_t* rot_bonds,
+                        const uint8_t* mask_rotate, int32_t n_rot, const ddk_match_options* opt, float* torsions_out, float* pos_out, float* rmsd_out,
+                        int32_t* count_out, void* workspace, void* stream) {
+  if (!ctx) return DDK_ERR_INVALID;
+  if (ctx->host_only) return fail(ctx, DDK_ERR_STATE, "host-only context (device < 0) cannot launch kernels");
+  if (!opt) return fail(ctx, DDK_ERR_INVALID, "ddk_conformer_match: null options");
+  std::string bad = match_bad_problem(n_lig, n_rot);
+  if (bad.empty()) bad = match_bad_population(n_rot, opt->popsize, opt->n_islands);
+  if (!bad.empty()) return fail(ctx, DDK_ERR_INVALID, "ddk_conformer_match: " + bad);
+  if (opt->maxiter < 0 || opt->maxiter > MATCH_MAX_ITER)
+    return fail(ctx, DDK_ERR_INVALID, "ddk_conformer_match: maxiter must be in [0, " + std::to_string(MATCH_MAX_ITER) + "]");
+  if (opt->polish_iters < 0 || opt->polish_iters > MATCH_MAX_POLISH)
+    return fail(ctx, DDK_ERR_INVALID, "ddk_conformer_match: polish_iters must be in [0, " + std::to_string(MATCH_MAX_POLISH) + "]");
+  if (!(opt->tol >= 0.0f)) return fail(ctx, DDK_ERR_INVALID, "ddk_conformer_match: tol must be >= 0");
+  if (!pos0 || !target || !pos_out || !rmsd_out || !count_out || !workspace || (n_rot > 0 && (!rot_bonds || !mask_rotate || !torsions_out)))
+    return fail(ctx, DDK_ERR_INVALID, "ddk_conformer_match: null argument (only atom_mask, and the rotor arrays with n_rot = 0, may be null)");
+  const MatchProblem P{n_lig, n_rot, pos0, target, atom_mask, rot_bonds, mask_rotate};
+  const MatchSearch O{opt->popsize, opt->maxiter, opt->polish_iters, opt->n_islands, opt->tol, opt->seed, opt->stream_id};
+  hipError_t e = launch_conformer_match(P, O, torsions_out, pos_out, rmsd_out, count_out, workspace, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "conformer_match launch");
+  return DDK_OK;
+}
+
 // Test hook: copy a packed host-side array out of the context ("conv.<l>.w2p.<g>", "conv.<l>.units", ...).
 // Returns the number of floats (or int32 words) of the item, or a negative status.  buf may be NULL to query.
 int64_t ddk_debug_export(ddk_ctx* ctx, const char* what, void* buf, int64_t cap_words) {

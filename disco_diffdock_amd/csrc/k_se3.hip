@@ -9,86 +9,10 @@
 // The 3x3 SVD of the reference is replaced by Horn's closed form (largest eigenvector of a 4x4 symmetric
 // matrix, Jacobi in fp64 on one lane): same optimal proper rotation, reflection case included.
 #include "model.h"
+#include "k_geom.h"
 
 namespace ddk {
 
-
-__device__ void axis_angle_to_matrix_dev(float ax, float ay, float az, float* R) {
-  // utils/geometry.py:38-85 (quaternion route, small-angle series below 1e-6)
-  const float ang = sqrtf(ax * ax + ay * ay + az * az);
-  const float half = 0.5f * ang;
-  const float s = fabsf(ang) < 1e-6f ? 0.5f - ang * ang / 48.0f : sinf(half) / ang;
-  const float qr = cosf(half), qi = ax * s, qj = ay * s, qk = az * s;
-  // the matrix of the fp32 quaternion assembled in fp64, one rounding per element: in fp32 (three to four roundings per element, as the reference does it)
-  // |R R^T - I| reaches 10 * 2^-24 near a half turn (tests/test_gpu_geometry_adversarial.py), and the rotor loop multiplies such matrices R times per step
-  const double r = qr, i = qi, j = qj, k = qk;
-  const double two_s = 2.0 / (r * r + i * i + j * j + k * k);
-  R[0] = (float)(1 - two_s * (j * j + k * k)); R[1] = (float)(two_s * (i * j - k * r)); R[2] = (float)(two_s * (i * k + j * r));
-  R[3] = (float)(two_s * (i * j + k * r)); R[4] = (float)(1 - two_s * (i * i + k * k)); R[5] = (float)(two_s * (j * k - i * r));
-  R[6] = (float)(two_s * (i * k - j * r)); R[7] = (float)(two_s * (j * k + i * r)); R[8] = (float)(1 - two_s * (i * i + j * j));
-}
-
-// rotation R minimising sum |R a_i - b_i|^2 given S[a][b] = sum a_i[a] b_i[b]  (Horn 1987)
-__device__ void horn_rotation(const double* S, float* R) {
-  double N[4][4] = {
-      {S[0] + S[4] + S[8], S[5] - S[7], S[6] - S[2], S[1] - S[3]},
-      {S[5] - S[7], S[0] - S[4] - S[8], S[1] + S[3], S[6] + S[2]},
-      {S[6] - S[2], S[1] + S[3], -S[0] + S[4] - S[8], S[5] + S[7]},
-      {S[1] - S[3], S[6] + S[2], S[5] + S[7], -S[0] - S[4] + S[8]}};
-  double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-  // Cyclic Jacobi.  A sweep costs six rotations of one sqrt + one rsqrt each on a single lane (the kernel's serial tail), so: the rotation
-  // comes from (c, s) = (|r|, sgn(r) x) / sqrt(r^2 + x^2) with r = d + sgn(d) sqrt(d^2 + x^2), d = (N_qq - N_pp) / 2 - the textbook
-  // t = sgn(theta) / (|theta| + sqrt(theta^2 + 1)) without its three divisions; an off-diagonal element below 2^-60 of its diagonal pair is left
-  // alone (the rotation would be the identity in fp64); the sweeps end when the off-diagonal mass is below 1e-32 of the diagonal's.
-  for (int sweep = 0; sweep < 30; ++sweep) {
-    double off = 0, dg = 0;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      dg += N[p][p] * N[p][p];
-#pragma unroll
-      for (int q = p + 1; q < 4; ++q) off += N[p][q] * N[p][q];
-    }
-    if (off <= 1e-32 * dg || off < 1e-300) break;
-    // (every index below is a compile-time constant after unrolling: N and V stay in registers - with rolled loops they lived in scratch memory)
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-      for (int q = p + 1; q < 4; ++q) {
-        const double x = N[p][q];
-        if (fabs(x) <= 8.7e-19 * (fabs(N[p][p]) + fabs(N[q][q]))) continue;
-        const double d = 0.5 * (N[q][q] - N[p][p]);
-        const double r = d + (d >= 0 ? 1.0 : -1.0) * sqrt(d * d + x * x);
-        const double inv = rsqrt(r * r + x * x);
-        const double c = fabs(r) * inv, s = (r >= 0 ? x : -x) * inv;
-        // N <- G^T N G on the symmetric matrix: the two diagonal elements in closed form, the (p, q) element is zero by construction, the two
-        // other rows / columns once (mirrored)
-        const double app = N[p][p], aqq = N[q][q], cc = c * c, ss = s * s, cs2 = 2.0 * c * s * x;
-        N[p][p] = cc * app - cs2 + ss * aqq;
-        N[q][q] = ss * app + cs2 + cc * aqq;
-        N[p][q] = 0.0; N[q][p] = 0.0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          if (k == p || k == q) continue;
-          const double a = N[k][p], b = N[k][q];
-          const double np_ = c * a - s * b, nq_ = s * a + c * b;
-          N[k][p] = np_; N[p][k] = np_; N[k][q] = nq_; N[q][k] = nq_;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const double a = V[k][p], b = V[k][q];
-          V[k][p] = c * a - s * b; V[k][q] = s * a + c * b;
-        }
-      }
-  }
-  double top = N[0][0], w = V[0][0], x = V[1][0], y = V[2][0], z = V[3][0];
-#pragma unroll
-  for (int k = 1; k < 4; ++k)
-    if (N[k][k] > top) { top = N[k][k]; w = V[0][k]; x = V[1][k]; y = V[2][k]; z = V[3][k]; }
-  const double nn = w * w + x * x + y * y + z * z, s2 = 2.0 / nn;
-  R[0] = (float)(1 - s2 * (y * y + z * z)); R[1] = (float)(s2 * (x * y - z * w)); R[2] = (float)(s2 * (x * z + y * w));
-  R[3] = (float)(s2 * (x * y + z * w)); R[4] = (float)(1 - s2 * (x * x + z * z)); R[5] = (float)(s2 * (y * z - x * w));
-  R[6] = (float)(s2 * (x * z - y * w)); R[7] = (float)(s2 * (y * z + x * w)); R[8] = (float)(1 - s2 * (x * x + y * y));
-}
 
 // Sum of the n points p[3 i + c] per component c in fp64, called by the 64 lanes of the block's first wave: lane t < 48 sums every 16th point of component
 // t % 3, four shuffle steps fold the 16 partial sums, lanes 0..2 return the totals of x, y, z.  fp64 with one rounding at the end because a sequential fp32

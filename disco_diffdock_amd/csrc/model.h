@@ -322,6 +322,31 @@ hipError_t launch_radius_graph(int n, const float* pos, float r, int max_num_nei
 hipError_t launch_ligand_transformation_mask(int n_lig, const int32_t* bond_index, int M, uint8_t* edge_mask_out, uint8_t* mask_rotate_out, int cap_rot,
                                              int32_t* count_out, void* workspace, hipStream_t s);
 
+// k_match.hip: conformer matching, the torsion fit of a conformer to a target pose (ddk_conformer_rmsd, ddk_conformer_match)
+constexpr int MATCH_MAX_ROT = 128;               // rotors of one ligand: the rotor tables live in LDS
+constexpr int MATCH_MAX_POPSIZE = 64;
+constexpr int MATCH_MAX_ITER = 1000;
+constexpr int MATCH_MAX_POLISH = 1024;
+constexpr int MATCH_MAX_ISLANDS = 16;
+constexpr int MATCH_MAX_MEMBERS = 8192;          // NP = max(5, popsize * n_rot) members per island
+constexpr int MATCH_MAX_VECTORS = 65536;         // torsion vectors of one ddk_conformer_rmsd call
+constexpr int MATCH_WAVES = 4;                   // candidates per workgroup of the evaluation kernels, one wave each
+constexpr int MATCH_POLISH_WAVES = 8;            // waves of match_select_kernel's one workgroup (it scans every island's costs)
+constexpr int MATCH_RMSD_GRID = 2048;            // conformer_rmsd_kernel's largest grid
+inline int match_members(int popsize, int n_rot) { return popsize * n_rot > 5 ? popsize * n_rot : 5; }
+struct MatchProblem {      // what both calls share; device pointers as the caller gave them
+  int n_lig, n_rot;
+  const float *pos0, *target;
+  const uint8_t* atom_mask;
+  const int32_t* rot_bonds;
+  const uint8_t* mask_rotate;
+};
+struct MatchSearch { int popsize, maxiter, polish_iters, n_islands; float tol; uint64_t seed, stream_id; };
+int64_t match_workspace_bytes(int n_lig, int n_rot, int popsize, int n_islands);
+hipError_t launch_conformer_rmsd(const MatchProblem& P, int M, const float* torsions, float* rmsd_out, int32_t* status_out, hipStream_t s);
+hipError_t launch_conformer_match(const MatchProblem& P, const MatchSearch& O, float* torsions_out, float* pos_out, float* rmsd_out, int32_t* count_out,
+                                  void* workspace, hipStream_t s);
+
 // k_rng.hip: the sampler's draws from the counter-based generator of k_philox.h (ddk_rng_noise, ddk_rng_initial, ddk_rng_uniform); limits in k_philox.h
 hipError_t launch_rng_noise(uint64_t seed, uint64_t stream_id, int sample0, int B, int step0, int steps, int n_cols, int n_active, float* out, hipStream_t s);
 hipError_t launch_rng_initial(uint64_t seed, uint64_t stream_id, int sample0, int B, int n_rot, float tr_sigma, int purpose_rot, float* tor_out, float* rot_out,

@@ -54,6 +54,10 @@ RNG_PURPOSES = dict(noise=0, initial_torsion=1, initial_rotation=2, initial_tran
 RNG_MAX_STEPS, RNG_MAX_COLS = 1 << 20, 1024
 # the purposes of the forward process (ddk_rng_perturbation, csrc/k_noising.hip), in the same counter field; their step field holds the draw index
 RNG_FORWARD_PURPOSES = dict(forward_translation=6, forward_rotation=7, forward_torsion=8)
+# conformer matching (ddk_conformer_match, csrc/k_match.hip): the purposes of its population and generation draws, its limits (csrc/model.h), the words of its status
+RNG_MATCH_PURPOSES = dict(match_population=9, match_generation=10)
+MATCH_MAX_ROT, MATCH_MAX_POPSIZE, MATCH_MAX_ITER, MATCH_MAX_POLISH, MATCH_MAX_ISLANDS, MATCH_MAX_MEMBERS, MATCH_MAX_VECTORS = 128, 64, 1000, 1024, 16, 8192, 65536
+MATCH_STATUS = ('done', None, 'a rotor table that is out of range or breaks the mask rule, or fewer than 3 kept atoms', 'a coordinate that is not finite')
 # the grids of utils/so3.py and utils/torus.py that ddk_so3_rows and ddk_torus_score evaluate (csrc/k_so3.hip, csrc/k_noising.hip)
 SO3_N_EPS, SO3_X_N, SO3_MAX_ROWS, TORUS_SIGMA_N = 1000, 2000, 4096, 5000
 # what ``Context.rng_perturbation`` returns: the device arrays of ddk_perturbation (include/ddk.h); tor_* are [B, n_rot]
@@ -169,6 +173,7 @@ class Context:
             raise RuntimeError(f'ddk_create: {msg}')
         self.device = device
         self._tables_set = False
+        self._match_ws = {}      # match_conformer's workspace per stream
 
     def _check(self, rc, what):
         if rc != 0:
@@ -356,6 +361,70 @@ class Context:
         self._check(self.L.ddk_ligand_automorphisms(self.h, n_lig, _ptr(col), _ptr(bi), E, _ptr(m), _ptr(perms), cap, _ptr(count), _ptr(ws), _stream()),
                     'ddk_ligand_automorphisms')
         return perms, count
+
+    # ---- conformer matching (csrc/k_match.hip; ddk_conformer_rmsd / ddk_conformer_match of include/ddk.h) -------------
+    def _match_problem(self, pos0, target, rot_bonds, mask_rotate, atom_mask):
+        dev = torch.device('cuda', self.device)
+        f = lambda a: h2d_async(torch.as_tensor(a).to(torch.float32).reshape(-1, 3).contiguous(), dev)
+        pos0, target = f(pos0), f(target)
+        n_lig = pos0.shape[0]
+        if target.shape[0] != n_lig:
+            raise RuntimeError(f'ddk: the target has {target.shape[0]} atoms, the conformer {n_lig}')
+        rb = torch.as_tensor(rot_bonds).reshape(-1, 2)
+        n_rot = rb.shape[0]
+        mr = torch.as_tensor(mask_rotate).reshape(n_rot, -1) if n_rot else None
+        if n_rot and mr.shape[1] != n_lig:
+            raise RuntimeError(f'ddk: mask_rotate must be [{n_rot}, {n_lig}]; got ' + str(tuple(mr.shape)))
+        rb = h2d_async(rb.to(torch.int32).contiguous(), dev) if n_rot else None
+        mr = h2d_async(mr.ne(0).to(torch.uint8).contiguous(), dev) if n_rot else None
+        m = None
+        if atom_mask is not None:
+            m = h2d_async(torch.as_tensor(atom_mask).reshape(-1).ne(0).to(torch.uint8).contiguous(), dev)
+            if m.shape[0] != n_lig:
+                raise RuntimeError(f'ddk: atom_mask has {m.shape[0]} entries for {n_lig} ligand atoms')
+        return dev, n_lig, n_rot, pos0, target, rb, mr, m
+
+    def conformer_rmsd(self, pos0, target, rot_bonds, mask_rotate, torsions, atom_mask=None, return_status=False):
+        """The matching objective alone (ddk_conformer_rmsd): for every row of ``torsions`` [M, n_rot] the RMSD to ``target`` [n_lig, 3], after the optimal
+        rigid fit, of the conformer ``pos0`` [n_lig, 3] with those torsion increments applied (utils/torsion.py:48-68; ``rot_bonds`` [n_rot, 2] = the
+        (u, v) of ``bond_index[:, edge_mask].T``, ``mask_rotate`` [n_rot, n_lig]).  ``atom_mask``: the atoms that count (None: all).  Returns a device
+        tensor [M]; with ``return_status`` also the status word [1] int32 (0; 2 a bad rotor table or fewer than 3 kept atoms; 3 a coordinate that is not
+        finite: the RMSDs are then not written).  Nothing is read back."""
+        dev, n_lig, n_rot, pos0, target, rb, mr, m = self._match_problem(pos0, target, rot_bonds, mask_rotate, atom_mask)
+        tor = torch.as_tensor(torsions).to(torch.float32)
+        tor = h2d_async(tor.reshape(-1, n_rot).contiguous() if n_rot else tor.reshape(tor.shape[0] if tor.dim() else 1, 0), dev)
+        M = tor.shape[0]
+        out = torch.empty(max(M, 1), dtype=torch.float32, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        self._check(self.L.ddk_conformer_rmsd(self.h, n_lig, _ptr(pos0), _ptr(target), _ptr(m), _ptr(rb), _ptr(mr), n_rot, M, _ptr(tor) if n_rot else None,
+                                              _ptr(out), _ptr(status), _stream()), 'ddk_conformer_rmsd')
+        return (out[:M], status) if return_status else out[:M]
+
+    def match_conformer(self, pos0, target, rot_bonds, mask_rotate, atom_mask=None, popsize=15, maxiter=15, polish_iters=128, n_islands=1, seed=0, stream=0,
+                        tol=0.01):
+        """Conformer matching (ddk_conformer_match; datasets_utils/conformer_matching.py): the torsion increments of the conformer ``pos0`` that bring it
+        closest to ``target`` after a rigid fit, by the seeded generation-synchronous differential evolution and compass polish include/ddk.h documents.
+        Returns a dict of device tensors: 'pos' [n_lig, 3] the matched conformer in the target's frame, 'torsions' [n_rot], 'rmsd' [] (rmsd_matching),
+        'rmsd_rigid' [] (all torsions 0; rmsd <= rmsd_rigid always), 'generations' [], 'status' [] (0; 2 / 3 as conformer_rmsd: the other entries are
+        then not written).  ``seed`` and ``stream`` (:func:`stream_id`) select the draws; the result is a pure function of the arguments.  The workspace is
+        kept on the context per stream and grows as needed.  Nothing is read back."""
+        dev, n_lig, n_rot, pos0, target, rb, mr, m = self._match_problem(pos0, target, rot_bonds, mask_rotate, atom_mask)
+        for k, v in dict(popsize=popsize, maxiter=maxiter, polish_iters=polish_iters, n_islands=n_islands).items():
+            if not -(1 << 31) <= int(v) < 1 << 31:
+                raise ValueError(f'ddk: {k} = {v} does not fit an int32')
+        opt = _lib.ddk_match_options(int(popsize), int(maxiter), float(tol), int(polish_iters), int(n_islands), _u64(seed, 'seed'), _u64(stream, 'rng_stream'))
+        nbytes = self.L.ddk_conformer_match_workspace(n_lig, n_rot, int(popsize), int(n_islands))      # -1: a broken limit, the call below says which
+        key = torch.cuda.current_stream(dev).cuda_stream      # (two calls on one stream run in order and may share the workspace)
+        ws = self._match_ws.get(key)
+        if ws is None or ws.numel() < max(nbytes, 16):
+            ws = self._match_ws[key] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        tor = torch.empty(n_rot, dtype=torch.float32, device=dev)
+        pos = torch.empty((n_lig, 3), dtype=torch.float32, device=dev)
+        rmsd = torch.empty(2, dtype=torch.float32, device=dev)
+        count = torch.empty(2, dtype=torch.int32, device=dev)
+        self._check(self.L.ddk_conformer_match(self.h, n_lig, _ptr(pos0), _ptr(target), _ptr(m), _ptr(rb), _ptr(mr), n_rot, C.byref(opt),
+                                               _ptr(tor) if n_rot else None, _ptr(pos), _ptr(rmsd), _ptr(count), _ptr(ws), _stream()), 'ddk_conformer_match')
+        return dict(pos=pos, torsions=tor, rmsd=rmsd[1], rmsd_rigid=rmsd[0], generations=count[0], status=count[1])
 
     # ---- the sampler's draws from the counter-based generator (csrc/k_rng.hip; DDK_RNG_LAYOUT of include/ddk.h) -------------
     def _rng_args(self, seed, stream, ints):

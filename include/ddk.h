@@ -376,6 +376,11 @@ int ddk_ligand_transformation_mask(ddk_ctx* ctx, int32_t n_lig, const int32_t* b
  *                4  AR pick uniform            step = decoding_idx                block 0, word 0
  *                5  rotation of ar_pos (ar_args.no_randomness, utils/sampling.py:36-46)   step = 0, as purpose 2
  *                6-8  the forward process (ddk_rng_perturbation below): translation, rotation, torsion; step = the draw index
+ *                9  conformer matching, the initial population (ddk_conformer_match below)   sample = island * NP + member, step = 0,
+ *                                                                                          torsion r uses block r / 4, word r % 4
+ *                10 conformer matching, generation g   sample = island * NP + member, step = g; block 0: word 0 -> r1, word 1 -> r2,
+ *                                                      word 2 -> the forced crossover index, word 3 OF MEMBER 0 -> the island's mutation factor;
+ *                                                      the crossover uniform of component d is word d % 4 of block 1 + d / 4
  *      Words -> draws, in fp32, every operation as written:
  *        uniform      u = (x >> 8) * 2^-24: in [0, 1), exact
  *        torsion      (float)pi * (2u - 1): the inner term is exact, one rounding
@@ -471,6 +476,75 @@ int ddk_rng_perturbation(ddk_ctx* ctx, uint64_t seed, uint64_t stream_id, int32_
 int ddk_score_matching_loss(ddk_ctx* ctx, int32_t B, int32_t n_rot, const float* tr_pred, const float* rot_pred, const float* tor_pred,
                             const float* tr_score, const float* rot_score, const float* tor_score, float tr_sigma, float so3_score_norm,
                             float torus_score_norm2, float* out /* [B, 6] */, void* stream);
+
+/* ---- conformer matching: fit the torsion angles of a generated conformer so that, after the optimal rigid fit, it lies as close as possible to the true
+ *      pose (datasets_utils/conformer_matching.py, called from get_lig_graph_with_matching, datasets_utils/process_mols.py:280-311; the reference trains and
+ *      validates on matched conformers and reports rmsd_matching per dataset).  Like ddk_ligand_automorphisms these calls take no ddk_complex, allocate
+ *      nothing and do not synchronise; all data pointers are DEVICE pointers; the work is enqueued on `stream`; a status other than 0 is a result (the call
+ *      returns DDK_OK); a broken limit or a NULL required argument is DDK_ERR_INVALID with a ddk_last_error text and nothing is enqueued.  No float atomics:
+ *      the results are bit-identical run to run and a pure function of (ligand, target, options).
+ *
+ *      The objective (ddk_conformer_rmsd evaluates it alone, rmsd_out[m] for the M vectors torsions [M, n_rot]): modify_conformer_torsion_angles
+ *        (utils/torsion.py:48-68) followed by the RMSD after the optimal proper rotation and translation.  For rotor k in order, on the already-updated
+ *        coordinates, the atoms with mask_rotate[k] rotate about pos[v] by the angle theta_k around (pos[u] - pos[v]) / |pos[u] - pos[v]|; a rotor with
+ *        theta_k == 0 is skipped.  rot_bonds [n_rot, 2] = the (u, v) of the rotatable bonds, bond_index[:, edge_mask].T, and mask_rotate [n_rot, n_lig] its
+ *        rows, as ddk_ligand_transformation_mask produces them.  The torsions are RELATIVE increments applied to pos0, where the reference sets absolute
+ *        dihedral angles through RDKit: both reach the same set of shapes, so the minimum is the same, the minimiser differs by the conformer's own angles.
+ *        atom_mask [n_lig] uint8 (NULL = all atoms): the atoms that enter the fit and the RMSD (the reference matches after RemoveHs); masked-out atoms
+ *        are moved like the others and written to pos_out.  The rotor chain runs in fp32 on centred coordinates, the centroids, the covariance and the
+ *        squared norms are fp64 sums, and msd = (sum |a|^2 + sum |b|^2 - 2 lambda_max) / m with lambda_max the top eigenvalue of Horn's 4 x 4 matrix.
+ *      Status (status_out[0] / count_out[1]): 0 done; 2 a bond index outside [0, n_lig), u == v, mask_rotate[k][u] != 0 or mask_rotate[k][v] == 0 (the two
+ *        asserts of the reference), or fewer than 3 kept atoms; 3 a coordinate of pos0 or target that is not finite.  All found on the device before an
+ *        index is used as an address.  With 2 or 3 nothing but status_out / count_out is written (count_out = {0, status}).
+ *
+ *      ddk_conformer_match: the reference's differential_evolution(f, [(-pi, pi)] * n_rot, maxiter, popsize, mutation=(0.5, 1), recombination=0.8)
+ *        (conformer_matching.py:39-41: strategy best1bin, tol 0.01, a polish at the end), with three deliberate differences:
+ *          updating   generation-synchronous: every trial of generation g is built from the population of generation g - 1 (scipy's own
+ *                     updating='deferred'; the reference runs 'immediate')
+ *          bounds     a trial component outside the bounds is wrapped into [-pi, pi): the objective is 2 pi-periodic (scipy redraws the component)
+ *          population independent uniform torsions (purpose 9 above), not a Latin hypercube, and member 0 of island 0 is theta = 0: selection is elitist,
+ *                     so rmsd_out[1] <= rmsd_out[0] always
+ *        n_islands independent populations of NP = max(5, popsize * n_rot) members each (no migration; island j draws the same numbers whatever
+ *        n_islands is, so the search's result BEFORE THE POLISH is never worse with more islands; the polish then starts from a possibly different vector, so
+ *        after it that holds only as a rule); the result is the best member over the islands, ties to the lowest island, then member.
+ *        Generation g = 1 .. maxiter of an island, from the population and costs of generation g - 1:
+ *          stop       mean and standard deviation (population form, / NP) of the NP costs in fp64; std <= tol * |mean| stops the island: this and every later
+ *                     generation leave it unchanged (tested before generation 1 too).  count_out[0] = the largest number of generations an island ran.
+ *          best       the member of the lowest cost, ties to the lowest index
+ *          F          0.5f + 0.5f * u, u the uniform of word 3 of block 0 of the island's member 0: one factor per (island, generation)
+ *          member i   r1 = ((x0 >> 8) * (NP - 1)) >> 24, plus 1 if >= i; r2 = ((x1 >> 8) * (NP - 2)) >> 24, plus 1 if >= min(i, r1), then plus 1 if
+ *                     >= max(i, r1): r1 != r2, both != i, integer arithmetic only; forced = ((x2 >> 8) * n_rot) >> 24
+ *          trial      component d = wrap(fmaf(F, pop[r1][d] - pop[r2][d], pop[best][d])) if d == forced or its uniform < 0.8f, else pop[i][d];
+ *                     wrap(t) = t - 2 pi floor((t + pi) / (2 pi)) in fp32, folded once more if the rounding left it outside [-pi, pi)
+ *          selection  the trial replaces member i if its cost <= the member's (a NaN cost never does)
+ *        Polish (instead of scipy's L-BFGS-B): a compass search from the best vector, h = 0.5: evaluate the 2 n_rot candidates theta +- h e_d (wrapped),
+ *        take the best one (ties to the lowest d, + before -) if it is strictly better, otherwise halve h; stop at h < 1e-4 or after polish_iters
+ *        iterations.  No random numbers.
+ *        Outputs: torsions_out [n_rot] the best vector; pos_out [n_lig, 3] the matched conformer in the target's frame (the AlignMolConformers step of
+ *        process_mols.py:305-307: the pose the reference stores as the ligand's pos); rmsd_out [2] = {the rigid fit with all torsions 0, the matched
+ *        RMSD = rmsd_matching}; count_out [2] = {generations run, status}.  n_rot = 0 is valid: no generation, pos_out = the rigid fit, both RMSDs
+ *        equal (the reference's `if rotable_bonds:`).
+ *        opt: a HOST struct.  workspace: ddk_conformer_match_workspace(...) bytes of device memory, 16-byte aligned, contents irrelevant before and after
+ *        (a host function, no context; -1 if a limit is broken).  Launches: one validation, maxiter + 1 generations over a fixed grid of one wave per
+ *        member (the boundary between two launches is the only ordering between workgroups: no grid barrier, no persistent kernel), one workgroup that
+ *        picks the best member, polish_iters launches of one wave per neighbour (those left after the polish has ended return at once), one workgroup
+ *        for the final fit.
+ *      Limits: 3 <= n_lig <= 256, 0 <= n_rot <= 128, 1 <= popsize <= 64, 0 <= maxiter <= 1000, 0 <= polish_iters <= 1024, 1 <= n_islands <= 16,
+ *      tol >= 0, 1 <= M <= 65536, NP <= 8192. */
+typedef struct ddk_match_options {
+  int32_t popsize, maxiter;
+  float tol;
+  int32_t polish_iters, n_islands;
+  uint64_t seed, stream_id;
+} ddk_match_options;
+int64_t ddk_conformer_match_workspace(int32_t n_lig, int32_t n_rot, int32_t popsize, int32_t n_islands);
+int ddk_conformer_rmsd(ddk_ctx* ctx, int32_t n_lig, const float* pos0, const float* target, const uint8_t* atom_mask,
+                       const int32_t* rot_bonds /* [n_rot, 2] (u, v) */, const uint8_t* mask_rotate /* [n_rot, n_lig] */, int32_t n_rot,
+                       int32_t M, const float* torsions /* [M, n_rot] */, float* rmsd_out /* [M] */, int32_t* status_out /* [1] */, void* stream);
+int ddk_conformer_match(ddk_ctx* ctx, int32_t n_lig, const float* pos0, const float* target, const uint8_t* atom_mask,
+                        const int32_t* rot_bonds, const uint8_t* mask_rotate, int32_t n_rot, const ddk_match_options* opt /* HOST */,
+                        float* torsions_out /* [n_rot] */, float* pos_out /* [n_lig, 3] */, float* rmsd_out /* [2] */, int32_t* count_out /* [2] */,
+                        void* workspace, void* stream);
 
 /* ---- a1-a2: the reverse-diffusion loop of sampling()  utils/sampling.py:105-198 for one batch:
  *      per step  perturb = score_coeff*score + noise_coeff*z  (coefficients are the host scalars of
