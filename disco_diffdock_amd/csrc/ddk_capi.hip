@@ -386,19 +386,31 @@ static int fold_batch_norm(ddk_ctx* ctx, const std::string& pre, const int* out,
 // Exact whenever the last bit of v is a multiple of the fp16 subnormal step 2^-24, i.e. for |v| >= 0.5 after scaling (the group's maximum is
 // scaled into [2^14, 2^15)); smaller values are off by at most 2^-25 = 2^-39 of the maximum.  Checked here for every value.
 // w1all / w2all: the fp32 fragment arrays [.][s/4][lane][s&3] (s = register of the lane half), b2all [t][2][16].
+// A layer is packed in the form it runs: conv_kernel = 3 keeps the three-limb records (W2X_TILE_BYTES, W1X_TILE_BYTES); the default two-limb form
+// (ConvLayerDev::limbs == 2, k_conv_x2.hip) gets the records without the lo limb it never reads (W2X2_TILE_BYTES, W1X2_TILE_BYTES): hi and mid are the same bits at
+// the same offsets.  Two limbs are not exact: |v - hi - mid| <= 2^-22 |v| (mid = fp16(v - hi) rounds a remainder of <= 2^-11 |v| to 11 bits), or <= 2^-25
+// where mid is an fp16 subnormal.  That window is checked here for every value instead of exactness.
 static int pack_x3(ddk_ctx* ctx, ConvLayerDev& L, int NG, const std::vector<float>& w1all, const std::vector<float>& w2all,
                    const std::vector<float>& b2all) {
   const size_t w1sz = 3 * 9 * 64 * 4, w2sz = (size_t)L.n_tiles * 9 * 64 * 4, b2sz = (size_t)L.n_tiles * 32;
+  const int limbs = ctx->cfg.conv_kernel == 3 ? 3 : 2;
+  const int tile_bytes = limbs == 3 ? W2X_TILE_BYTES : W2X2_TILE_BYTES, bias_off = limbs == 3 ? W2X_BIAS_OFF : W2X2_BIAS_OFF,
+            desc_off = limbs == 3 ? W2X_DESC_OFF : W2X2_DESC_OFF, w1_tile_bytes = limbs == 3 ? W1X_TILE_BYTES : W1X2_TILE_BYTES;
   bool exact = true;
-  auto split = [&exact](float v, uint16_t& hi, uint16_t& mid, uint16_t& lo) {
+  auto split = [&exact, limbs](float v, uint16_t& hi, uint16_t& mid, uint16_t& lo) {
     const _Float16 h = (_Float16)v;
     const float r1 = v - (float)h;
     const _Float16 m = (_Float16)r1;
     const _Float16 l = (_Float16)(r1 - (float)m);
     memcpy(&hi, &h, 2); memcpy(&mid, &m, 2); memcpy(&lo, &l, 2);
     // the limbs must reproduce v bit for bit (values below 0.5 - more than 2^-15 under the group's maximum - within 2^-25)
-    const double back = (double)(float)h + (double)(float)m + (double)(float)l;
-    if (std::fabs(v) >= 0.5f ? back != (double)v : std::fabs(back - (double)v) > 0x1p-25) exact = false;
+    if (limbs == 3) {
+      const double back = (double)(float)h + (double)(float)m + (double)(float)l;
+      if (std::fabs(v) >= 0.5f ? back != (double)v : std::fabs(back - (double)v) > 0x1p-25) exact = false;
+    } else {      // two limbs: the window stated above
+      const double back = (double)(float)h + (double)(float)m;
+      if (std::fabs(back - (double)v) > std::max(0x1p-22 * std::fabs((double)v), 0x1p-25)) exact = false;
+    }
   };
   // exact power-of-two range scaling: max|w| of a group is brought into [2^14, 2^15) so that no limb leaves the fp16 range whatever the
   // scale of the checkpoint (the kernel scales the activations per edge the same way)
@@ -411,8 +423,8 @@ static int pack_x3(ddk_ctx* ctx, ConvLayerDev& L, int NG, const std::vector<floa
     return std::ldexp(1.0f, 15 - e);
   };
   // (+ three zero records behind the last group: the kernel requests record t+3 without clamping at a group's last tile)
-  std::vector<uint8_t> w2x((size_t)(NG * L.n_tiles + 4) * W2X_TILE_BYTES, 0), w1x((size_t)NG * 3 * W1X_TILE_BYTES, 0);
-  // one tile of fp32 fragments [9][64][4] -> three limbs x [4 x [64][8] | [64][4]]
+  std::vector<uint8_t> w2x((size_t)(NG * L.n_tiles + 4) * tile_bytes, 0), w1x((size_t)NG * 3 * w1_tile_bytes, 0);
+  // one tile of fp32 fragments [9][64][4] -> the form's limbs x [4 x [64][8] | [64][4]]
   auto frags = [&](const float* src, float sc, uint8_t* dst) {
     for (int r = 0; r < 36; ++r)
       for (int lane = 0; lane < 64; ++lane) {
@@ -421,7 +433,8 @@ static int pack_x3(ddk_ctx* ctx, ConvLayerDev& L, int NG, const std::vector<floa
         const size_t off = s_ < 4 ? (size_t)s_ * 1024 + lane * 16 + 2 * i : (size_t)4096 + lane * 8 + 2 * i;
         uint16_t h, m, l;
         split(v, h, m, l);
-        memcpy(dst + off, &h, 2); memcpy(dst + W2X_LIMB_BYTES + off, &m, 2); memcpy(dst + 2 * W2X_LIMB_BYTES + off, &l, 2);
+        memcpy(dst + off, &h, 2); memcpy(dst + W2X_LIMB_BYTES + off, &m, 2);
+        if (limbs == 3) memcpy(dst + 2 * W2X_LIMB_BYTES + off, &l, 2);
       }
   };
   for (int g = 0; g < NG; ++g) {
@@ -431,26 +444,28 @@ static int pack_x3(ddk_ctx* ctx, ConvLayerDev& L, int NG, const std::vector<floa
     const float sc1 = range_scale(w1, w1sz, nullptr, 0), sc2 = range_scale(w2, w2sz, nullptr, 0);
     L.w1s[g] = sc1; L.w2s[g] = sc2;
     for (int t = 0; t < L.n_tiles; ++t) {
-      uint8_t* rec = w2x.data() + ((size_t)g * L.n_tiles + t) * W2X_TILE_BYTES;
+      uint8_t* rec = w2x.data() + ((size_t)g * L.n_tiles + t) * tile_bytes;
       frags(w2 + (size_t)t * 2304, sc2, rec);
-      memcpy(rec + W2X_BIAS_OFF, b2 + (size_t)t * 32, 128);       // fp32 as is: the kernel scales it like the products
+      memcpy(rec + bias_off, b2 + (size_t)t * 32, 128);       // fp32 as is: the kernel scales it like the products
       const int32_t dq[2] = {x_tile_word(L.h_tiles[t].w0), L.h_tiles[t].chan0};
       if (dq[0] < 0) return fail(ctx, DDK_ERR_INVALID, "internal: a vector tile of the conv layout does not sit on a T1O / T1E row quad");
-      memcpy(rec + W2X_DESC_OFF, dq, 8);
+      memcpy(rec + desc_off, dq, 8);
     }
-    for (int T = 0; T < 3; ++T) frags(w1 + (size_t)T * 2304, sc1, w1x.data() + ((size_t)g * 3 + T) * W1X_TILE_BYTES);
+    for (int T = 0; T < 3; ++T) frags(w1 + (size_t)T * 2304, sc1, w1x.data() + ((size_t)g * 3 + T) * w1_tile_bytes);
   }
-  if (!exact) return fail(ctx, DDK_ERR_INVALID, "internal: the three-limb fp16 split of a conv weight is not exact");
+  if (!exact)
+    return fail(ctx, DDK_ERR_INVALID, limbs == 3 ? "internal: the three-limb fp16 split of a conv weight is not exact"
+                                                 : "internal: the two-limb fp16 split of a conv weight leaves its 2^-22 window");
   L.h_w2x = w2x; L.h_w1x = w1x;
   L.epi_ok = conv_epilogue_shapes_ok(L.h_tiles);      // launch_conv_fused_x refuses the asm-epilogue instantiation otherwise
-  L.limbs = ctx->cfg.conv_kernel == 3 ? 3 : 2;        // the default two-limb form reads the first two limbs of the same records (k_conv_x2.hip); conv_kernel = 3: all three, six products
+  L.limbs = limbs;        // 2: the default two-limb form, three products (k_conv_x2.hip); 3 (conv_kernel = 3): all three limbs, six products
   if (ctx->host_only) return DDK_OK;
   L.w2x = (uint8_t*)dev_alloc(ctx, w2x.size());
   L.w1x = (uint8_t*)dev_alloc(ctx, w1x.size());
-  if (!L.w2x || !L.w1x) return fail(ctx, DDK_ERR_NOMEM, "device allocation failed while packing conv weights (three-limb f16)");
+  if (!L.w2x || !L.w1x) return fail(ctx, DDK_ERR_NOMEM, "device allocation failed while packing conv weights (f16 limbs)");
   if (hipMemcpy(L.w2x, w2x.data(), w2x.size(), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(L.w1x, w1x.data(), w1x.size(), hipMemcpyHostToDevice) != hipSuccess)
-    return fail(ctx, DDK_ERR_HIP, "three-limb weight upload failed");
+    return fail(ctx, DDK_ERR_HIP, "f16-limb weight upload failed");
   return DDK_OK;
 }
 

@@ -34,6 +34,11 @@
 // chunks of tile t+3 from L2 during its burst of tile t and stores them in its epilogue of tile t into the stage tile t-1 has left - group A
 // between barriers t and t+1, group B one interval later - so tile t+3 is complete at barrier t+2 and each wave fetches the first two K steps of
 // its NEXT tile at the start of its epilogue.
+//
+// The TWO-LIMB form (the default) streams records without the lo limb it never reads: 9,360 B = 585 chunks (W2X2_TILE_BYTES), so every thread moves chunk
+// tid and only threads 0..72 a second one (has1 in the kernel): waves 2-7 skip the second load / wait / store behind a wave-uniform scalar branch, wave 1 runs it
+// for nine lanes under exec.  The 4 x 4,608 B the ring gives back hold the node-term split's GEMM1 fragments of the workgroup's current weight group
+// (W1L_BYTES behind the ring: see the unit prologue), which every wave used to fetch from L2 for every unit.
 #include <stdlib.h>
 
 #include "k_conv_common.h"
@@ -49,6 +54,14 @@
 #define launch_conv_fused_x launch_conv_fused_x2
 #define conv_prepare_device_x conv_prepare_device_x2
 #include "k_conv_x_epi2_gen.inc"     // the tile epilogue as one asm statement per ring stage, generated for one accumulator chain: nothing to fold
+// the record this form streams and its LDS budget (ddk_internal.h)
+#define X3_TILE_BYTES W2X2_TILE_BYTES
+#define X3_BIAS_OFF W2X2_BIAS_OFF
+#define X3_DESC_OFF W2X2_DESC_OFF
+#define X3_W1_TILE_BYTES W1X2_TILE_BYTES
+#define X3_LDS_BYTES CONV_X2_LDS_BYTES
+#define X3_W1L_BYTES W1L_BYTES
+#define X3_TWO true                  /* a record is 585 chunks: only threads 0..72 have a second one (has1 / has1_s in the kernel) */
 // TWO limbs per operand (hi = fp16(x), mid = fp16(x - hi): |x - hi - mid| <= 2^-22 |x|) and the three products hi.hi + hi.mid + mid.hi in ONE accumulator: 14 MFMAs per tile.
 // The fourth product mid.mid is <= 2^-22 relative - the size of the operands' own truncation - and is dropped (it rides for free in the packed K = 8 tail, where
 // {W_hi, W_mid} x {h_hi, h_mid} is one MFMA either way); a product is off by <= 3 * 2^-22, a K = 72 dot product by less than the classical fp32 bound 72 * 2^-24
@@ -70,6 +83,13 @@
 #define X3_TAIL_BARES X3_BARE X3_BARE
 #else
 #include "k_conv_x_epi_gen.inc"      // the tile epilogue as one asm statement per ring stage (tools/gen_conv_x_epi.py; round 5)
+#define X3_TILE_BYTES W2X_TILE_BYTES
+#define X3_BIAS_OFF W2X_BIAS_OFF
+#define X3_DESC_OFF W2X_DESC_OFF
+#define X3_W1_TILE_BYTES W1X_TILE_BYTES
+#define X3_LDS_BYTES CONV_X_LDS_BYTES
+#define X3_W1L_BYTES 0               /* (no room beside four three-limb stages: GEMM1's fragments come from global memory) */
+#define X3_TWO false                 /* a record is 873 chunks: every thread has a second one (threads past the record's end move its last chunk again: no branch) */
 // six-term product of one K step into the two accumulators, alternating (D0: hi.hi and the 2^-11 terms, D1: the 2^-22 terms)
 #define X3_SUM(r) (D0[r] + D1[r])
 #define X3_TAIL3(a_lh, a_hm) D0 = MFMA16(a_hm, HT.mh, D0); D1 = MFMA16(a_lh, HT.hl, D1); D0 = MFMA16(a_hm, HT.hm, D0);
@@ -96,6 +116,38 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((vector_size(16)));
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16((a), (b), (c), 0, 0, 0)
 #define MFMA8(a, b, c) __builtin_amdgcn_mfma_f32_32x32x8f16((a), (b), (c), 0, 0, 0)
+
+// GEMM1's A fragments, per form.  w1_lo: the lo limb of a fragment of the W1 records in global memory - the two-limb records have none and the two-limb
+// products never multiply it: the hi limb stands in.  w1_split: K step 0 and the first half of K step 1 (registers 0..11) of row tile T for the node-term
+// split - the two-limb form reads them from the copy in LDS (w1l: ds_read_b128 at lane * 16, ds_read_b64 at lane * 8, conflict free), the three-limb form
+// from the records of weight group gw (w1).
+struct W1Split { f16x8 h, m, l; f16x4 th, tm, tl; };
+#ifdef X3_TWO_LIMBS
+template <class TY> __device__ __forceinline__ TY w1_lo(const char*, const TY& hi) { return hi; }
+__device__ __forceinline__ W1Split w1_split(const char* w1l, const char*, int T, int lane) {
+  const char* wt = w1l + T * (2 * W1L_LIMB_BYTES);
+  W1Split f;
+  f.h = *reinterpret_cast<const f16x8*>(wt + lane * 16);
+  f.m = *reinterpret_cast<const f16x8*>(wt + W1L_LIMB_BYTES + lane * 16);
+  f.th = *reinterpret_cast<const f16x4*>(wt + 1024 + lane * 8);
+  f.tm = *reinterpret_cast<const f16x4*>(wt + W1L_LIMB_BYTES + 1024 + lane * 8);
+  f.l = f.h; f.tl = f.th;
+  return f;
+}
+#else
+template <class TY> __device__ __forceinline__ TY w1_lo(const char* p, const TY&) { return *reinterpret_cast<const TY*>(p); }
+__device__ __forceinline__ W1Split w1_split(const char*, const char* w1, int T, int lane) {
+  const char* wt = w1 + (size_t)T * W1X_TILE_BYTES;
+  W1Split f;
+  f.h = *reinterpret_cast<const f16x8*>(wt + lane * 16);
+  f.m = *reinterpret_cast<const f16x8*>(wt + W2X_LIMB_BYTES + lane * 16);
+  f.l = *reinterpret_cast<const f16x8*>(wt + 2 * W2X_LIMB_BYTES + lane * 16);
+  f.th = *reinterpret_cast<const f16x4*>(wt + 1024 + lane * 16);
+  f.tm = *reinterpret_cast<const f16x4*>(wt + W2X_LIMB_BYTES + 1024 + lane * 16);
+  f.tl = *reinterpret_cast<const f16x4*>(wt + 2 * W2X_LIMB_BYTES + 1024 + lane * 16);
+  return f;
+}
+#endif
 
 // Exact power-of-two range scale: 2^(14 - floor(log2 max(m, 2^-40))) and its inverse (max|x| lands in [2^14, 2^15))
 __device__ __forceinline__ float range_scale(float m, float& inv) {
@@ -302,8 +354,10 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   float* F = lds + wave * (32 * FS);                                   // this wave's 32 F rows
-  char* ring = reinterpret_cast<char*>(lds + WAVES * (32 * FS));       // [W2X_STAGES][W2X_TILE_BYTES]
-  int* blk_slot = reinterpret_cast<int*>(ring + W2X_STAGES * W2X_TILE_BYTES);
+  char* ring = reinterpret_cast<char*>(lds + WAVES * (32 * FS));       // [W2X_STAGES][X3_TILE_BYTES]
+  char* w1l = ring + W2X_STAGES * X3_TILE_BYTES;                       // two-limb form: [W1L_BYTES] GEMM1 fragments of weight group gw_lds
+  int* blk_slot = reinterpret_cast<int*>(w1l + X3_W1L_BYTES);
+  (void)w1l;
   const int el = lane & 31;
   const int hh = lane >> 5;
   const bool g2_shared = A.sum_g2 != nullptr;                 // group 2 is the shared rec-rec copy (layer-0 de-duplication): its own accumulator
@@ -329,11 +383,18 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
   float* Fr = F + el * FS;
   const float inv_s3 = 0.57735026918962576451f, inv_s2 = 0.70710678118654752440f;
   const int n_tiles = A.n_tiles;
-  constexpr int REC16 = W2X_TILE_BYTES / 16;                   // 873 x 16 B per tile record
+  constexpr int REC16 = X3_TILE_BYTES / 16;                    // 873 (two-limb form: 585) x 16 B per tile record
   const int grp = wave >> 2;                                    // half-group: 0 = waves 0-3 (A), 1 = waves 4-7 (B, their SIMD partners)
-  // every thread moves two 16-B chunks of a tile record: chunk tid and chunk tid + 512 (threads past the record's end move its last chunk
-  // again: same bytes to the same place, no branch in the burst)
+  // every thread moves up to two 16-B chunks of a tile record: chunk tid and chunk tid + 512 (three-limb form: threads past the record's end move its
+  // last chunk again, same bytes to the same place, no branch in the burst; two-limb form: threads 0..72 only - has1; has1_s is its wave-uniform
+  // part: waves 2-7 skip the second load / wait / store behind a scalar branch, wave 1 runs them for nine lanes under exec)
   const uint32_t fo0 = 16u * tid, fo1 = 16u * min(tid + 64 * WAVES, REC16 - 1);
+  const bool has1 = !X3_TWO || tid + 64 * WAVES < REC16;
+  const unsigned long long c1_mask = __ballot(has1);                  // (asm epilogue of the two-limb form) the lanes of this wave that have a second chunk
+  const bool has1_s = !X3_TWO || c1_mask != 0;
+  (void)has1; (void)has1_s; (void)c1_mask;
+  int gw_lds = -1;                                                    // the weight group whose GEMM1 fragments sit in w1l
+  (void)gw_lds;
   // the hot instantiation (score-model conv layers: gather + node terms, atomics) runs its tile epilogue as ONE asm statement (k_conv_x_epi_gen.inc): the
   // accumulators are in/out operands of every tile kind's code alike, so the compiler has nothing to copy or select at a merge (VERDICT r04 #1a)
   constexpr bool ASM_EPI = GATHER && SPLIT && !DET && MODE == 0;     // (the trace build too)
@@ -392,21 +453,47 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
 
     // ---- stage the first three W2 tiles of this unit (the ring is idle: the previous unit ended with a barrier) ----
     const int gw = (int)((A.wmap >> (4 * g)) & 15);                 // weight set / node-term roles of this group
-    const char* wrec = reinterpret_cast<const char*>(A.w2x) + (size_t)gw * n_tiles * W2X_TILE_BYTES;
+    const char* wrec = reinterpret_cast<const char*>(A.w2x) + (size_t)gw * n_tiles * X3_TILE_BYTES;
     {
-      const char* wr0 = wrec + (size_t)t_begin * W2X_TILE_BYTES;
-      const char* wr1 = wrec + (size_t)min(t_begin + 1, t_end - 1) * W2X_TILE_BYTES;
-      const char* wr2 = wrec + (size_t)min(t_begin + 2, t_end - 1) * W2X_TILE_BYTES;
-      const float4 r0 = *reinterpret_cast<const float4*>(wr0 + fo0), r1 = *reinterpret_cast<const float4*>(wr0 + fo1);
-      const float4 r2 = *reinterpret_cast<const float4*>(wr1 + fo0), r3 = *reinterpret_cast<const float4*>(wr1 + fo1);
-      const float4 r4 = *reinterpret_cast<const float4*>(wr2 + fo0), r5 = *reinterpret_cast<const float4*>(wr2 + fo1);
+      const char* wr0 = wrec + (size_t)t_begin * X3_TILE_BYTES;
+      const char* wr1 = wrec + (size_t)min(t_begin + 1, t_end - 1) * X3_TILE_BYTES;
+      const char* wr2 = wrec + (size_t)min(t_begin + 2, t_end - 1) * X3_TILE_BYTES;
+      const float4 r0 = *reinterpret_cast<const float4*>(wr0 + fo0);
+      const float4 r2 = *reinterpret_cast<const float4*>(wr1 + fo0);
+      const float4 r4 = *reinterpret_cast<const float4*>(wr2 + fo0);
+      if (has1_s) { if (has1) {
+        const float4 r1 = *reinterpret_cast<const float4*>(wr0 + fo1);
+        const float4 r3 = *reinterpret_cast<const float4*>(wr1 + fo1);
+        const float4 r5 = *reinterpret_cast<const float4*>(wr2 + fo1);
+        *reinterpret_cast<float4*>(ring + fo1) = r1;
+        *reinterpret_cast<float4*>(ring + X3_TILE_BYTES + fo1) = r3;
+        *reinterpret_cast<float4*>(ring + 2 * X3_TILE_BYTES + fo1) = r5;
+      } }
       *reinterpret_cast<float4*>(ring + fo0) = r0;
-      *reinterpret_cast<float4*>(ring + fo1) = r1;
-      *reinterpret_cast<float4*>(ring + W2X_TILE_BYTES + fo0) = r2;
-      *reinterpret_cast<float4*>(ring + W2X_TILE_BYTES + fo1) = r3;
-      *reinterpret_cast<float4*>(ring + 2 * W2X_TILE_BYTES + fo0) = r4;
-      *reinterpret_cast<float4*>(ring + 2 * W2X_TILE_BYTES + fo1) = r5;
+      *reinterpret_cast<float4*>(ring + X3_TILE_BYTES + fo0) = r2;
+      *reinterpret_cast<float4*>(ring + 2 * X3_TILE_BYTES + fo0) = r4;
     }
+#ifdef X3_TWO_LIMBS
+    if constexpr (SPLIT) {
+      // ---- GEMM1's fragments of weight group gw into w1l, when the previous unit of this workgroup ran another group (its first unit; a DisCo patch
+      // group's mapped gw): registers 0..11 of both limbs of the three row tiles, 6 x (1 KB K step 0 + 512 B half step) = W1L_BYTES.  Waves 0-5 copy
+      // one (row tile, limb) each: a 16-B and an 8-B piece per lane.  gw is uniform over the workgroup and so is this branch and its barrier.
+      // Hazard: w1l is read by GEMM1 only; every wave has passed the previous unit's tile-loop barriers (and the unit hand-over barrier), hence its
+      // GEMM1, before any thread gets here, so nobody still reads what is overwritten; the barrier below orders the new bytes before this unit's GEMM1.
+      const int gw_s = __builtin_amdgcn_readfirstlane(gw);
+      if (gw_s != gw_lds) {
+        if (wave < 6) {
+          const char* wsrc = reinterpret_cast<const char*>(A.w1x) + ((size_t)gw_s * 3 + (wave >> 1)) * X3_W1_TILE_BYTES + (wave & 1) * W2X_LIMB_BYTES;
+          const float4 c16 = *reinterpret_cast<const float4*>(wsrc + lane * 16);
+          const float2 c8 = *reinterpret_cast<const float2*>(wsrc + 1024 + lane * 16);
+          *reinterpret_cast<float4*>(w1l + wave * W1L_LIMB_BYTES + lane * 16) = c16;
+          *reinterpret_cast<float2*>(w1l + wave * W1L_LIMB_BYTES + 1024 + lane * 8) = c8;
+        }
+        gw_lds = gw_s;
+        lds_barrier();
+      }
+    }
+#endif
 
     // ---- segmented-scan control words (identical for every output channel of this wave's 32 edges) ----
     const SegF seg = make_segf(make_segctl(sn, el, nvalid, valid));
@@ -430,7 +517,8 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
     float osc, bsc2;      // GEMM2 accumulators hold (s2 h) x (w2s W2): bias goes in times bsc2, flushed sums come out times osc
     {
       float h[36];
-      const char* w1 = reinterpret_cast<const char*>(A.w1x) + (size_t)gw * 3 * W1X_TILE_BYTES;
+      const char* w1 = reinterpret_cast<const char*>(A.w1x) + (size_t)gw * 3 * X3_W1_TILE_BYTES;
+      (void)w1;
       if constexpr (SPLIT) {
         // W1a edge_emb on top of the per-node terms (W1b x[src][:ns] + b1) + W1c x[dst][:ns] (node_finalize_pre_kernel), which arrive in the
         // accumulator's own register order: K = 24 = one step of 16 + one of 8.  The node terms sit at random nodes of a 15 MB array (past the
@@ -480,17 +568,10 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
           }
 #pragma unroll
           for (int r = 0; r < 16; ++r) D1[r] = 0.0f;
-          const char* wt = w1 + (size_t)T * W1X_TILE_BYTES;
-          {
-            const f16x8 ah = *reinterpret_cast<const f16x8*>(wt + lane * 16);
-            const f16x8 am = *reinterpret_cast<const f16x8*>(wt + W2X_LIMB_BYTES + lane * 16);
-            const f16x8 al = *reinterpret_cast<const f16x8*>(wt + 2 * W2X_LIMB_BYTES + lane * 16);
-            X3_STEP(MFMA16, ah, am, al, b0h, b0m, b0l)
-          }
+          const W1Split wf = w1_split(w1l, w1, T, lane);
+          X3_STEP(MFMA16, wf.h, wf.m, wf.l, b0h, b0m, b0l)
           {     // registers 8..11: the first half of step 1's fragment
-            const f16x4 ah = *reinterpret_cast<const f16x4*>(wt + 1024 + lane * 16);
-            const f16x4 am = *reinterpret_cast<const f16x4*>(wt + W2X_LIMB_BYTES + 1024 + lane * 16);
-            const f16x4 al = *reinterpret_cast<const f16x4*>(wt + 2 * W2X_LIMB_BYTES + 1024 + lane * 16);
+            const f16x4 ah = wf.th, am = wf.tm, al = wf.tl;
             // (the K = 8 half step packed like the tile tail: hi.mid + mid.hi, lo.hi + hi.lo, hi.hi + mid.mid as one K = 16 MFMA each: 9 instead of 12 per row tile)
             const f16x8 a_hm = __builtin_shufflevector(ah, am, 0, 1, 2, 3, 4, 5, 6, 7), a_lh = __builtin_shufflevector(al, ah, 0, 1, 2, 3, 4, 5, 6, 7);
             D0 = MFMA16(a_hm, b1_mh, D0);
@@ -548,18 +629,18 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
           }
 #pragma unroll
           for (int r = 0; r < 16; ++r) D1[r] = 0.0f;
-          const char* wt = w1 + (size_t)T * W1X_TILE_BYTES;
+          const char* wt = w1 + (size_t)T * X3_W1_TILE_BYTES;      // (K = 72: 27.6 KB per group, from global memory in both forms)
 #pragma unroll
           for (int s = 0; s < 4; ++s) {
             const f16x8 ah = *reinterpret_cast<const f16x8*>(wt + s * 1024 + lane * 16);
             const f16x8 am = *reinterpret_cast<const f16x8*>(wt + W2X_LIMB_BYTES + s * 1024 + lane * 16);
-            const f16x8 al = *reinterpret_cast<const f16x8*>(wt + 2 * W2X_LIMB_BYTES + s * 1024 + lane * 16);
+            const f16x8 al = w1_lo<f16x8>(wt + 2 * W2X_LIMB_BYTES + s * 1024 + lane * 16, ah);
             X3_STEP(MFMA16, ah, am, al, Bn.hi[s], Bn.mid[s], Bn.lo[s])
           }
           {
             const f16x4 ah = *reinterpret_cast<const f16x4*>(wt + 4096 + lane * 8);
             const f16x4 am = *reinterpret_cast<const f16x4*>(wt + W2X_LIMB_BYTES + 4096 + lane * 8);
-            const f16x4 al = *reinterpret_cast<const f16x4*>(wt + 2 * W2X_LIMB_BYTES + 4096 + lane * 8);
+            const f16x4 al = w1_lo<f16x4>(wt + 2 * W2X_LIMB_BYTES + 4096 + lane * 8, ah);
             X3_STEP(MFMA8, ah, am, al, Bn.thi, Bn.tmid, Bn.tlo)
           }
           const int nr = T < 2 ? 16 : 4;
@@ -637,7 +718,7 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
       if (rq < 3) { accY[rq][0] = 0.0f; accY[rq][1] = 0.0f; accY[rq][2] = 0.0f; }
     }
     // ---- per-lane ring addresses: with the tile loop unrolled over the four ring stages every ring access is ONE base register + an immediate
-    // (the ring spans 4 x 13,968 B < 2^16: the 16-bit ds offset reaches all of it), and the records of tile t+3 come through a buffer
+    // (the ring spans 4 x 13,968 B < 2^16 - two-limb form: 4 x 9,360 B -: the 16-bit ds offset reaches all of it), and the records of tile t+3 come through a buffer
     // descriptor (per-lane offset in a VGPR, the tile's offset in ONE SGPR that advances by a record per tile) ----
     const char* ringl = ring + lane * 16;       // 16-B fragment reads
     const char* ringt = ring + lane * 8;        // 8-B tail-fragment reads
@@ -645,7 +726,7 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
     char* ringw0 = ring + fo0;                  // this thread's two chunks of a record
     char* ringw1 = ring + fo1;
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(wrec), 0, 0x7fffffff, 0x00020000);
-    int rec_soff = (t_begin + 3) * W2X_TILE_BYTES;      // (records past a group's last tile exist: the next group's, or the three pad records)
+    int rec_soff = (t_begin + 3) * X3_TILE_BYTES;      // (records past a group's last tile exist: the next group's, or the three pad records)
     // the first K step of the first tile and its descriptor (the two words ride behind the bias in the ring record: an LDS read, not a scalar
     // load - a scalar load in flight turns every counted LDS wait into a full one); later tiles: fetched in the previous burst's tail
     Frag16 p0;
@@ -655,7 +736,7 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
 #endif
     int w0, chan0;
     {
-      const int2 dq = *reinterpret_cast<const int2*>(ring + W2X_DESC_OFF);
+      const int2 dq = *reinterpret_cast<const int2*>(ring + X3_DESC_OFF);
       w0 = __builtin_amdgcn_readfirstlane(dq.x); chan0 = __builtin_amdgcn_readfirstlane(dq.y);
     }
     const bool grp_s = __builtin_amdgcn_readfirstlane(grp) != 0;      // provably wave-uniform: the barrier sits behind a scalar branch
@@ -715,10 +796,10 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
 #define X3_BURST_BODY(ST)                                                                                                                    \
       Frag16 p1; X3_FRAG(p1, SO + 1024)                                                                                                      \
       const f32x4 f0 = ldv4(Fp);                                                                                                             \
-      /* this thread's two chunks of record t+3, requested first: ~900 cycles until the epilogue stores them */                              \
+      /* this thread's first chunk of record t+3, requested first (the second: X3_TILE): ~900 cycles until the epilogue stores them */      \
       const u32x4 st0 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)fo0, rec_soff, 0);                                                  \
-      const u32x4 st1 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)fo1, rec_soff, 0);                                                  \
-      rec_soff += W2X_TILE_BYTES;                                                                                                            \
+      if constexpr (!X3_TWO) st1 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)fo1, rec_soff, 0);                                      \
+      rec_soff += X3_TILE_BYTES;                                                                                                             \
       X3_STEP(MFMA16, p0.h, p0.m, p0.l, H.hi[0], H.mid[0], H.lo[0])                                                                         \
       X3_RIDERS_0                                                                                                                            \
       __builtin_amdgcn_sched_barrier(0);                                                                                                     \
@@ -733,18 +814,26 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
       X3_STEP(MFMA16, q2.h, q2.m, q2.l, H.hi[2], H.mid[2], H.lo[2])                                                                         \
       X3_RIDERS_2                                                                                                                            \
       __builtin_amdgcn_sched_barrier(0);                                                                                                     \
-      const int2 dq = *reinterpret_cast<const int2*>(ring + SN + W2X_DESC_OFF);                                                              \
+      const int2 dq = *reinterpret_cast<const int2*>(ring + SN + X3_DESC_OFF);                                                               \
       X3_FRAG(p0, SN)       /* (p0's last use was K step 0 of this burst: the next tile's first K step goes straight into its registers) */    \
       X3_STEP(MFMA16, q3.h, q3.m, q3.l, H.hi[3], H.mid[3], H.lo[3])                                                                         \
       X3_RIDERS_3                                                                                                                            \
       __builtin_amdgcn_sched_barrier(0);
 #define X3_TILE(ST)                                                                                                                          \
     {                                                                                                                                        \
-      constexpr int SO = (ST) * W2X_TILE_BYTES, SN = (((ST) + 1) & 3) * W2X_TILE_BYTES, SW = (((ST) + 3) & 3) * W2X_TILE_BYTES;              \
+      constexpr int SO = (ST) * X3_TILE_BYTES, SN = (((ST) + 1) & 3) * X3_TILE_BYTES, SW = (((ST) + 3) & 3) * X3_TILE_BYTES;                 \
       /* the bursting wave wins issue arbitration against its SIMD partner's epilogue (round 3's static priority for the later-dispatched   \
          half costs 7 % once the half phases are not separated by a barrier; priority during the epilogue instead: +2.5 %) */                \
       __builtin_amdgcn_s_setprio(1);                                                                                                         \
       stamp(0);                                                                                                                              \
+      /* the second chunk of record t+3.  Two-limb form: requested here, IN FRONT of the burst's scheduling region (its branch would cut the region in     \
+         two); threads without one never store st1: the empty asm gives it a value without an instruction, so that it lives from here to the epilogue's \
+         store only.  Three-limb form: requested in the burst, behind the first chunk */                                                             \
+      u32x4 st1;                                                                                                                             \
+      if constexpr (X3_TWO) {                                                                                                                \
+        asm volatile("" : "=v"(st1));                                                                                                        \
+        if (has1_s) { if (has1) st1 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)fo1, rec_soff, 0); }                                  \
+      }                                                                                                                                      \
       /* ===== burst: 27 MFMAs; every other instruction rides in an MFMA shadow, pinned region by region (one K step each): the LDS reads    \
          of the fragments one step ahead, the feature rows, this thread's two chunks of record t+3 and - in the tail - the next tile's       \
          descriptor and first K step (complete in the ring since the last barrier) ===== */                                                  \
@@ -770,10 +859,12 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
         const int chan4_ = chan0 * 4;                                                                                                        \
         X3_EPI_##ST();                                                                                                                       \
       } else {                                                                                                                               \
-      const float4 bs0 = ld4(reinterpret_cast<const float*>(ringb + SO + W2X_BIAS_OFF)), bs1 = ld4(reinterpret_cast<const float*>(ringb + SO + W2X_BIAS_OFF + 16)); \
-      const float4 bs2 = ld4(reinterpret_cast<const float*>(ringb + SO + W2X_BIAS_OFF + 32)), bs3 = ld4(reinterpret_cast<const float*>(ringb + SO + W2X_BIAS_OFF + 48)); \
+      /* (two-limb form: the second chunk first - its branch ends a basic block, and behind the bias reads it would keep them live across it) */ \
+      if constexpr (X3_TWO) { if (has1_s) { if (has1) *reinterpret_cast<u32x4*>(ringw1 + SW) = st1; } }                                      \
+      const float4 bs0 = ld4(reinterpret_cast<const float*>(ringb + SO + X3_BIAS_OFF)), bs1 = ld4(reinterpret_cast<const float*>(ringb + SO + X3_BIAS_OFF + 16)); \
+      const float4 bs2 = ld4(reinterpret_cast<const float*>(ringb + SO + X3_BIAS_OFF + 32)), bs3 = ld4(reinterpret_cast<const float*>(ringb + SO + X3_BIAS_OFF + 48)); \
       *reinterpret_cast<u32x4*>(ringw0 + SW) = st0;                                                                                          \
-      *reinterpret_cast<u32x4*>(ringw1 + SW) = st1;                                                                                          \
+      if constexpr (!X3_TWO) *reinterpret_cast<u32x4*>(ringw1 + SW) = st1;                                                                   \
       /* the two accumulators and the bias into one */                                                                                       \
       D0[0] = fmaf(bs0.x, bsc2, X3_SUM(0)); D0[1] = fmaf(bs0.y, bsc2, X3_SUM(1)); D0[2] = fmaf(bs0.z, bsc2, X3_SUM(2)); D0[3] = fmaf(bs0.w, bsc2, X3_SUM(3)); \
       D0[4] = fmaf(bs1.x, bsc2, X3_SUM(4)); D0[5] = fmaf(bs1.y, bsc2, X3_SUM(5)); D0[6] = fmaf(bs1.z, bsc2, X3_SUM(6)); D0[7] = fmaf(bs1.w, bsc2, X3_SUM(7)); \
@@ -848,14 +939,14 @@ hipError_t launch_split3_probe(const float* x, int64_t n, int group, float* hi, 
 
 template <bool GATHER, bool SPLIT, bool DET>
 static hipError_t launch_x_t(const ConvXArgs& k, int n_cu, hipStream_t s) {
-  hipLaunchKernelGGL((conv_x3_kernel<GATHER, SPLIT, DET>), dim3(n_cu), dim3(64 * CONV_WAVES), CONV_X_LDS_BYTES, s, k);
+  hipLaunchKernelGGL((conv_x3_kernel<GATHER, SPLIT, DET>), dim3(n_cu), dim3(64 * CONV_WAVES), X3_LDS_BYTES, s, k);
   return hipGetLastError();
 }
 
 template <bool GATHER, bool SPLIT, bool DET>
 static hipError_t attr_x_t() {
   return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_x3_kernel<GATHER, SPLIT, DET>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)CONV_X_LDS_BYTES);
+                             (int)X3_LDS_BYTES);
 }
 
 #ifndef X3_TWO_LIMBS
@@ -882,13 +973,13 @@ hipError_t conv_prepare_device_x() {
   if (e == hipSuccess) e = attr_x_t<false, false, true>();
   if (e == hipSuccess)
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_x3_kernel<true, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)CONV_X_LDS_BYTES);
+                            (int)X3_LDS_BYTES);
   if (e == hipSuccess)
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_x3_kernel<true, false, false, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)CONV_X_LDS_BYTES);
+                            (int)X3_LDS_BYTES);
   if (e == hipSuccess)
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_x3_kernel<false, false, false, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)CONV_X_LDS_BYTES);
+                            (int)X3_LDS_BYTES);
   return e;
 }
 
@@ -912,8 +1003,8 @@ hipError_t launch_conv_fused_x(const ConvLayerDev& L, const ConvLaunch& a, int n
   X.trace = nullptr; X.trace_coarse = a.trace_coarse;
   if (a.mode == 1) {      // the confidence model: plain gather path (no node-term split, atomics)
     if (a.pre != nullptr || a.part != nullptr || a.trace != nullptr) return hipErrorInvalidValue;
-    if (a.gather) hipLaunchKernelGGL((conv_x3_kernel<true, false, false, false, 1>), dim3(n_cu), dim3(64 * CONV_WAVES), CONV_X_LDS_BYTES, s, X);
-    else hipLaunchKernelGGL((conv_x3_kernel<false, false, false, false, 1>), dim3(n_cu), dim3(64 * CONV_WAVES), CONV_X_LDS_BYTES, s, X);
+    if (a.gather) hipLaunchKernelGGL((conv_x3_kernel<true, false, false, false, 1>), dim3(n_cu), dim3(64 * CONV_WAVES), X3_LDS_BYTES, s, X);
+    else hipLaunchKernelGGL((conv_x3_kernel<false, false, false, false, 1>), dim3(n_cu), dim3(64 * CONV_WAVES), X3_LDS_BYTES, s, X);
     return hipGetLastError();
   }
   if (a.part != nullptr) {       // deterministic scatter
@@ -929,7 +1020,7 @@ hipError_t launch_conv_fused_x(const ConvLayerDev& L, const ConvLaunch& a, int n
   X.trace = a.trace;
   if (a.trace != nullptr) {
     if (!(a.gather && a.pre != nullptr)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((conv_x3_kernel<true, true, false, true>), dim3(n_cu), dim3(64 * CONV_WAVES), CONV_X_LDS_BYTES, s, X);
+    hipLaunchKernelGGL((conv_x3_kernel<true, true, false, true>), dim3(n_cu), dim3(64 * CONV_WAVES), X3_LDS_BYTES, s, X);
     return hipGetLastError();
   }
   if (a.gather && a.pre != nullptr) return launch_x_t<true, true, false>(X, n_cu, s);

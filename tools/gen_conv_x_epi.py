@@ -9,12 +9,16 @@ the slow path, v_cndmask / v_cmp pairs, conservative lgkmcnt(0) waits: VERDICT r
 tile kind, packed quad, flush - with the accumulators as in/out operands, D0 / D1 / f0 in pinned registers (element access) and scalar branches INSIDE the
 statement, so that every tile kind works on the same registers (a C++ switch around per-kind statements made the compiler copy 20-40 registers at every
 merge).  Same arithmetic, same order as the C++ epilogue it replaces (reference models/tensor_layers.py:65-116,147-159).  The compiler does not count the LDS
-operations inside asm: every s_waitcnt below is placed by hand."""
+operations inside asm: every s_waitcnt below is placed by hand.
+
+The two forms move different records through the ring (RECORD).  A three-limb record is 873 16-B chunks: every thread stores two.  A two-limb record is 585
+chunks: every thread stores chunk tid, threads 0..72 a second one, so the ring part of the two-limb epilogue exists per wave class (ring_stores)."""
 import os
 from collections import namedtuple
 
-TB, LIMB = 13968, 4608
-BIAS_OFF = 3 * LIMB
+LIMB = 4608
+# the ring record of a form: tile bytes, offset of the bias (ddk_internal.h: W2X_* three limbs, W2X2_* two limbs)
+RECORD = {False: (3 * LIMB + 128 + 16, 3 * LIMB), True: (2 * LIMB + 128 + 16, 2 * LIMB)}
 
 # The register assignment.  d: base of D0 (folded in place; D1 follows it); bias: b0..b3; feat: f0, f1, f2, g0; flushv: the flush's out values (the first 9) and
 # w = v / sqrt2 (the last 3); flush_addr: the flush address; quad: packed-quad sum / g0 address; r: the RTS kind's second scalar accumulator (scratch otherwise)
@@ -190,17 +194,37 @@ def asm_stmt(name, lines, outs, ins, clobbers):
     return (f'#define {name}() \\\n  asm volatile( \\\n    {body} \\\n    : {op(outs)} \\\n    : {op(ins)} \\\n    : {cl})\n')
 
 
+def ring_stores(SW, two_limb):
+    """this thread's chunks of record t+3 (requested in the burst) into the stage tile t-1 has left, and the wait for the four bias reads issued in front of
+    them.  Returns (inline, out_of_line).  The counted waits follow from what a wave has in flight: vector-memory loads return in order, so vmcnt(n) releases
+    all but the youngest n (older flush atomics only make the wait stricter); LDS operations complete in order, so lgkmcnt(n) with n ring stores behind the
+    four bias reads waits for exactly the reads and leaves the stores in flight."""
+    if not two_limb:
+        # every wave: two loads, st0 requested first -> vmcnt(1) releases st0, vmcnt(0) st1; two stores behind the bias reads -> lgkmcnt(2) (after the fold)
+        return ['s_waitcnt vmcnt(1)', f'ds_write_b128 %[rw0], %[st0] offset:{SW}', 's_waitcnt vmcnt(0)', f'ds_write_b128 %[rw1], %[st1] offset:{SW}'], []
+    # waves 2-7 (%[c1] = 0, six of eight: inline): ONE load in flight -> vmcnt(0); one store behind the bias reads -> lgkmcnt(1).
+    # waves 0 / 1 (out of line): two loads (wave 1: the second one masked down to nine lanes, it still counts as one).  The second chunk is requested in front
+    # of the burst's scheduling region and the first inside it, an order the compiler is free to change: ONE vmcnt(0) for both (they were requested a burst
+    # ago).  st1 is stored by the lanes of %[c1] only; two stores behind the bias reads -> lgkmcnt(2)
+    inline = ['s_cmp_lg_u64 %[c1], 0', 's_cbranch_scc1 .Lr2_%=', 's_waitcnt vmcnt(0)', f'ds_write_b128 %[rw0], %[st0] offset:{SW}', 's_waitcnt lgkmcnt(1)', '.Lrj_%=:']
+    ool = ['.Lr2_%=:', 's_waitcnt vmcnt(0)', f'ds_write_b128 %[rw0], %[st0] offset:{SW}',
+           '\\n\\t'.join(['s_mov_b64 %[sv], exec', 's_and_b64 exec, exec, %[c1]', f'ds_write_b128 %[rw1], %[st1] offset:{SW}', 's_mov_b64 exec, %[sv]']),
+           's_waitcnt lgkmcnt(2)', 's_branch .Lrj_%=']
+    return inline, ool
+
+
 def epilogue(rg, ST, one_acc):
+    TB, BIAS_OFF = RECORD[one_acc]
     SO, SW = ST * TB, ((ST + 3) & 3) * TB
     L = []
     for j in range(4):
         L.append(f'ds_read_b128 v[{rg.bias[4 * j][1:]}:{rg.bias[4 * j + 3][1:]}], %[ringb] offset:{SO + BIAS_OFF + 16 * j}')
-    # this thread's two chunks of record t+3 (requested at the start of the burst) into the stage tile t-1 has left
-    L += ['s_waitcnt vmcnt(1)', f'ds_write_b128 %[rw0], %[st0] offset:{SW}', 's_waitcnt vmcnt(0)', f'ds_write_b128 %[rw1], %[st1] offset:{SW}']
-    if not one_acc:      # (the two-limb form has one accumulator chain: nothing to fold)
+    ring_inl, ool_r = ring_stores(SW, one_acc)
+    L += ring_inl
+    if not one_acc:      # (the two-limb form has one accumulator chain: nothing to fold, and its ring part waits for the bias reads itself)
         for r in range(16):
             L.append(f'v_add_f32 v{rg.d + r}, v{rg.d + r}, v{rg.d + 16 + r}')
-    L.append('s_waitcnt lgkmcnt(2)')      # the bias reads; the two ring stores stay in flight
+        L.append('s_waitcnt lgkmcnt(2)')      # the bias reads; the two ring stores stay in flight
     for r in range(16):
         L.append(f'v_fmac_f32 v{rg.d + r}, {rg.bias[r]}, %[bsc2]')
     # tile kind -> selector (1 RA, 2 RT, 3 + cross bits TV, 7 RTS)
@@ -223,7 +247,7 @@ def epilogue(rg, ST, one_acc):
           's_cmp_eq_u32 %[sel], 7', 's_cbranch_scc1 .Lfr_%=']
     L += flush_stream(rg, 'S') + ['s_branch .Lnf_%=', '.Lfr_%=:'] + flush_stream(rg, 'S', rts=True) + ['s_branch .Lnf_%=', '.Lfv_%=:'] + flush_stream(rg, 'V')
     # the compiler does not see the LDS operations in here: the statement leaves none in flight
-    L += ['.Lnf_%=:', 's_waitcnt lgkmcnt(0)', 's_branch .Lexit_%='] + ool_k + ['.Lexit_%=:']
+    L += ['.Lnf_%=:', 's_waitcnt lgkmcnt(0)', 's_branch .Lexit_%='] + ool_k + ool_r + ['.Lexit_%=:']
     return L
 
 
@@ -237,7 +261,7 @@ def generate(one_acc):
            ('rw1', 'v', 'ringw1_u'), ('fpa', 'v', 'fpa_u'), ('fra', 'v', 'fra_u'), ('bsc2', 'v', 'bsc2'), ('oscv', 'v', 'oscv'), ('s0', 'v', 's0'), ('vx', 'v', 'vx'),
            ('vy', 'v', 'vy'), ('vz', 'v', 'vz'), ('sm1', 'v', 'seg.m1'), ('sm2', 'v', 'seg.m2'), ('sm4', 'v', 'seg.m4'), ('sm8', 'v', 'seg.m8'), ('sm16', 'v', 'seg.m16'),
            ('vrow', 'v', 'vrow'), ('hh4', 'v', 'hh4_u'), ('hh12', 'v', 'hh12_u'), ('w0', 's', 'w0'), ('chan4', 's', 'chan4_'), ('tail', 's', 'tail_mask'),
-           ('sumbase', 's', 'sumbase')]
+           ('sumbase', 's', 'sumbase')] + ([('c1', 's', 'c1_mask')] if one_acc else [])
     for ST in range(4):
         out.append(asm_stmt(f'X3_EPI_{ST}', epilogue(rg, ST, one_acc), outs, ins, CLOBBER + ['memory', 'scc']))
     return '\n'.join(out)
