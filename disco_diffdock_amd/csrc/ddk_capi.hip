@@ -390,8 +390,9 @@ static int fold_batch_norm(ddk_ctx* ctx, const std::string& pre, const int* out,
 // (ConvLayerDev::limbs == 2, k_conv_x2.hip) gets the records without the lo limb it never reads (W2X2_TILE_BYTES, W1X2_TILE_BYTES): hi and mid are the same bits at
 // the same offsets.  Two limbs are not exact: |v - hi - mid| <= 2^-22 |v| (mid = fp16(v - hi) rounds a remainder of <= 2^-11 |v| to 11 bits), or <= 2^-25
 // where mid is an fp16 subnormal.  That window is checked here for every value instead of exactness.
+// sender_k48: also pack the K = 48 GEMM1 records of the node-term split (score-model conv layers in the two-limb form: the only instantiations that read them)
 static int pack_x3(ddk_ctx* ctx, ConvLayerDev& L, int NG, const std::vector<float>& w1all, const std::vector<float>& w2all,
-                   const std::vector<float>& b2all) {
+                   const std::vector<float>& b2all, bool sender_k48 = false) {
   const size_t w1sz = 3 * 9 * 64 * 4, w2sz = (size_t)L.n_tiles * 9 * 64 * 4, b2sz = (size_t)L.n_tiles * 32;
   const int limbs = ctx->cfg.conv_kernel == 3 ? 3 : 2;
   const int tile_bytes = limbs == 3 ? W2X_TILE_BYTES : W2X2_TILE_BYTES, bias_off = limbs == 3 ? W2X_BIAS_OFF : W2X2_BIAS_OFF,
@@ -423,7 +424,7 @@ static int pack_x3(ddk_ctx* ctx, ConvLayerDev& L, int NG, const std::vector<floa
     return std::ldexp(1.0f, 15 - e);
   };
   // (+ three zero records behind the last group: the kernel requests record t+3 without clamping at a group's last tile)
-  std::vector<uint8_t> w2x((size_t)(NG * L.n_tiles + 4) * tile_bytes, 0), w1x((size_t)NG * 3 * w1_tile_bytes, 0);
+  std::vector<uint8_t> w2x((size_t)(NG * L.n_tiles + 4) * tile_bytes, 0), w1x((size_t)NG * 3 * w1_tile_bytes, 0), w1sx(limbs == 2 && sender_k48 ? (size_t)NG * W1L_BYTES : 0, 0);
   // one tile of fp32 fragments [9][64][4] -> the form's limbs x [4 x [64][8] | [64][4]]
   auto frags = [&](const float* src, float sc, uint8_t* dst) {
     for (int r = 0; r < 36; ++r)
@@ -452,17 +453,33 @@ static int pack_x3(ddk_ctx* ctx, ConvLayerDev& L, int NG, const std::vector<floa
       memcpy(rec + desc_off, dq, 8);
     }
     for (int T = 0; T < 3; ++T) frags(w1 + (size_t)T * 2304, sc1, w1x.data() + ((size_t)g * 3 + T) * w1_tile_bytes);
+    // two-limb form: the K = 48 fragments of the node-term split (W1L_BYTES, ddk_internal.h): the edge_emb and x_dst columns of the K = 72 fragments as
+    // three full K steps, under the group's range scale and the same window
+    if (!w1sx.empty())
+      for (int T = 0; T < 3; ++T)
+        for (int r = 0; r < 24; ++r)
+          for (int lane = 0; lane < 64; ++lane) {
+            const int r72 = w1s_k72_register(r);
+            const float v = w1[(size_t)T * 2304 + ((size_t)(r72 / 4) * 64 + lane) * 4 + (r72 & 3)] * sc1;
+            uint8_t* dst = w1sx.data() + (size_t)g * W1L_BYTES + (size_t)T * 2 * W1L_LIMB_BYTES + (size_t)(r / 8) * 1024 + lane * 16 + 2 * (r % 8);
+            uint16_t h, m, l;
+            split(v, h, m, l);
+            memcpy(dst, &h, 2); memcpy(dst + W1L_LIMB_BYTES, &m, 2);
+          }
   }
   if (!exact)
     return fail(ctx, DDK_ERR_INVALID, limbs == 3 ? "internal: the three-limb fp16 split of a conv weight is not exact"
                                                  : "internal: the two-limb fp16 split of a conv weight leaves its 2^-22 window");
-  L.h_w2x = w2x; L.h_w1x = w1x;
+  L.h_w2x = w2x; L.h_w1x = w1x; L.h_w1sx = w1sx;
+  L.sender_in_gemm1 = !w1sx.empty();      // the layer's split launches multiply the sender's columns themselves: its contexts form the receiver roles only
   L.epi_ok = conv_epilogue_shapes_ok(L.h_tiles);      // launch_conv_fused_x refuses the asm-epilogue instantiation otherwise
   L.limbs = limbs;        // 2: the default two-limb form, three products (k_conv_x2.hip); 3 (conv_kernel = 3): all three limbs, six products
   if (ctx->host_only) return DDK_OK;
   L.w2x = (uint8_t*)dev_alloc(ctx, w2x.size());
   L.w1x = (uint8_t*)dev_alloc(ctx, w1x.size());
-  if (!L.w2x || !L.w1x) return fail(ctx, DDK_ERR_NOMEM, "device allocation failed while packing conv weights (f16 limbs)");
+  if (!w1sx.empty()) L.w1sx = (uint8_t*)dev_alloc(ctx, w1sx.size());
+  if (!L.w2x || !L.w1x || (!w1sx.empty() && !L.w1sx)) return fail(ctx, DDK_ERR_NOMEM, "device allocation failed while packing conv weights (f16 limbs)");
+  if (!w1sx.empty() && hipMemcpy(L.w1sx, w1sx.data(), w1sx.size(), hipMemcpyHostToDevice) != hipSuccess) return fail(ctx, DDK_ERR_HIP, "f16-limb weight upload failed");
   if (hipMemcpy(L.w2x, w2x.data(), w2x.size(), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(L.w1x, w1x.data(), w1x.size(), hipMemcpyHostToDevice) != hipSuccess)
     return fail(ctx, DDK_ERR_HIP, "f16-limb weight upload failed");
@@ -566,7 +583,7 @@ static int build_conv_layer(ddk_ctx* ctx, int mode, int l, ConvLayerDev& L) {
     L.h_w2p[g].assign(w2all.begin() + g * w2sz, w2all.begin() + (g + 1) * w2sz);
     L.h_b2p[g].assign(b2all.begin() + g * b2sz, b2all.begin() + (g + 1) * b2sz);
   }
-  if (mode == 0 && c.conv_kernel != 1 && (rc = pack_x3(ctx, L, NG, w1all, w2all, b2all))) return rc;
+  if (mode == 0 && c.conv_kernel != 1 && (rc = pack_x3(ctx, L, NG, w1all, w2all, b2all, true))) return rc;
   if (mode == 1 && c.conv_kernel != 1) {
     // The three-limb kernel keeps the raw p / q rows once ([p0..p5 | q0..q5], quads of four): the l = 2 group of the q rows (T2E), whose two
     // tiles are [q0 q1 q2 q3], [q4 q5 . .] in the table, reads raw quads 1 and 2 = [. . q0 q1], [q2 q3 q4 q5]: move its weight rows accordingly
@@ -973,6 +990,7 @@ int64_t ddk_debug_export(ddk_ctx* ctx, const char* what, void* buf, int64_t cap_
     // three-limb f16 kernel: all groups' records (bytes, padded to words) and the power-of-two range scales [w1s[4] | w2s[4]]
     else if (it == "w1x") { src = L.h_w1x.data(); n = L.h_w1x.size() / 4; }
     else if (it == "w2x") { src = L.h_w2x.data(); n = L.h_w2x.size() / 4; }
+    else if (it == "w1sx") { src = L.h_w1sx.data(); n = L.h_w1sx.size() / 4; }      // two-limb form: the K = 48 GEMM1 fragments of the node-term split (empty for conv_kernel = 3)
     else if (it == "xscale") { static thread_local float sc[8]; for (int k = 0; k < 4; ++k) { sc[k] = L.w1s[k]; sc[4 + k] = L.w2s[k]; } src = sc; n = 8; }
     else return fail(ctx, DDK_ERR_INVALID, "unknown export item");
   } else {

@@ -69,10 +69,14 @@ constexpr int W2X2_BIAS_OFF = 2 * W2X_LIMB_BYTES;                   // 9,216
 constexpr int W2X2_DESC_OFF = W2X2_BIAS_OFF + 128;
 constexpr int W2X2_TILE_BYTES = W2X2_DESC_OFF + 16;                 // 9,360 = 585 x 16 B
 constexpr int W1X2_TILE_BYTES = 2 * W2X_LIMB_BYTES;                 // GEMM1: the two limbs of one 32-row tile
-// ... and what its ring gives back holds the GEMM1 fragments of the node-term split (K = 24: registers 0..11 of a lane half) of the workgroup's current
-// weight group: [3 row tiles][hi | mid][K step 0: [64 lanes][8] | first half of K step 1: [64][4]]
-constexpr int W1L_LIMB_BYTES = 1024 + 512;
-constexpr int W1L_BYTES = 3 * 2 * W1L_LIMB_BYTES;                   // 9,216
+// ... and what its ring gives back holds the GEMM1 fragments of the node-term split of the workgroup's current weight group.  The two-limb split keeps the
+// RECEIVER's node term only (pre[src]); the sender's term W1c x[dst][:ns] is part of the MFMA: K = 48 = [edge_emb (24) | x_dst[:ns] (24)], three full K = 16
+// steps and no tail.  Register r' (0..23) of lane half hh is element r' % 8 of K step r' / 8 and holds edge_emb[12 hh + r'] (r' < 12) or x_dst[12 hh + r' - 12],
+// i.e. register r' < 12 ? r' : r' + 12 of the K = 72 records (w1s_k72_register).  [group][3 row tiles][hi | mid][3 K steps: [64 lanes][8]]: ConvLayerDev::w1sx,
+// copied as it is into LDS
+constexpr int W1L_LIMB_BYTES = 3 * 1024;
+constexpr int W1L_BYTES = 3 * 2 * W1L_LIMB_BYTES;                   // 18,432
+static inline int w1s_k72_register(int r) { return r < 12 ? r : r + 12; }
 constexpr int CONV_TRACE_TILES = 1024;                              // tiles per wave the TRACE instantiation of the kernel records
 // F row of the three-limb kernel (100 floats instead of 132): the vector blocks keep the RAW p / q rows once (12 rows x xyz, component-major inside
 // each quad of rows like T1O / T1E) instead of the four products p*s0, (q x v)/sqrt2, (p x v)/sqrt2, q*s0 - multiplying by s0 and crossing with v
@@ -83,7 +87,7 @@ static_assert(FX_STRIDE == 100 && FX_A == F_A && FX_C == F_C, "F row layout (thr
 constexpr int W2X_STAGES = 4;                                       // LDS ring stages of the three-limb kernel
 constexpr size_t CONV_X_LDS_BYTES = (size_t)CONV_WAVES * 32 * FX_STRIDE * 4 + W2X_STAGES * W2X_TILE_BYTES + 16;
 static_assert(CONV_X_LDS_BYTES <= 160 * 1024 && W2X_TILE_BYTES % 16 == 0, "LDS budget (three-limb f16)");
-constexpr size_t CONV_X2_LDS_BYTES = (size_t)CONV_WAVES * 32 * FX_STRIDE * 4 + W2X_STAGES * W2X2_TILE_BYTES + W1L_BYTES + 16;     // 149,072
+constexpr size_t CONV_X2_LDS_BYTES = (size_t)CONV_WAVES * 32 * FX_STRIDE * 4 + W2X_STAGES * W2X2_TILE_BYTES + W1L_BYTES + 16;     // 158,288
 static_assert(CONV_X2_LDS_BYTES <= 160 * 1024 && W2X2_TILE_BYTES % 16 == 0 && W1L_BYTES % 16 == 0, "LDS budget (two-limb f16)");
 
 // One W2 "tile" = 32 weight rows x 72 hidden units = one burst of 36 v_mfma_f32_32x32x2_f32 per 32 edges.
@@ -151,9 +155,11 @@ struct ConvLayerDev {          // device copies for one TensorProductConvLayer w
   float* b1p[4] = {};          // [3][2][16]
   float* w2r[4] = {};          // [n_tiles][W2_TILE_FLOATS]: per tile the fragments [9][64][4], the bias [2][16], the TileDesc words
   uint8_t* w1x = nullptr;      // f16-limb kernels: [groups][3][W1X_TILE_BYTES] (limbs == 3) or [groups][3][W1X2_TILE_BYTES] (limbs == 2)
+  uint8_t* w1sx = nullptr;     // two-limb form, node-term split: [groups][W1L_BYTES] the K = 48 GEMM1 fragments (edge_emb and x_dst columns), see W1L_BYTES
   uint8_t* w2x = nullptr;      // f16-limb kernels: [groups][n_tiles][W2X_TILE_BYTES] (limbs == 3) or [groups][n_tiles][W2X2_TILE_BYTES] (limbs == 2)
   float w1s[CONV_MAX_GROUPS] = {1, 1, 1, 1, 1, 1, 1, 1, 1}, w2s[CONV_MAX_GROUPS] = {1, 1, 1, 1, 1, 1, 1, 1, 1};   // three-limb f16 kernel: power-of-two range scale of the packed W1 / W2 of each weight set
   int limbs = 2;               // fp16 limbs per fp32 operand in the f16-limb kernel: 2 (three products, k_conv_x2.hip: the default) or 3 (six products, k_conv_x.hip: conv_kernel = 3); set by pack_x3
+  bool sender_in_gemm1 = false;   // two-limb form of a score-model layer (set by pack_x3 with w1sx): the node-term split reads the receiver roles only, GEMM1 runs at K = 48
   bool epi_ok = false;         // the tile table has the column shapes the generated asm epilogue hard-codes (conv_epilogue_shapes_ok): set by pack_x3
   int n_cols = 0;              // flush columns (8 output channels each); col_start[c] = first tile of column c, col_start[n_cols] = n_tiles
   int col_start[17] = {};
@@ -173,7 +179,7 @@ struct ConvLayerDev {          // device copies for one TensorProductConvLayer w
   std::vector<float> h_bn_mean, h_bn_scale, h_bn_bias;          // [n_bn][XW]: one BatchNorm per layer (score) or per conv (confidence)
   int n_groups = 4;
   std::vector<TileDesc> h_tiles;
-  std::vector<uint8_t> h_w1x, h_w2x;     // host copies of the f16-limb records, in the form the layer runs (ddk_debug_export, CPU tests)
+  std::vector<uint8_t> h_w1x, h_w2x, h_w1sx;     // host copies of the f16-limb records, in the form the layer runs (ddk_debug_export, CPU tests)
   // block shapes of the FasterTensorProduct (tensor_layers.py:58-63), order 0e,1o,1e,0o
   int n_in[4] = {}, n_out[4] = {}, blk_off[4] = {};
   int in_mul[4] = {}, out_mul[4] = {};   // 0e,1o,1e,0o multiplicities of the layer's in/out irreps
@@ -270,7 +276,7 @@ struct ConvLaunch {
   int64_t edge_bound = 0;       // host upper bound of the last edge index of the launch (sizes the fix-up grid)
   const int32_t* det_rng = nullptr;   // deterministic mode: sample-aligned ranges of the launch (ConvKArgs::det_rng, det_ranges_kernel) ...
   int det_nr = 0;                     // ... and their number (0: blocks run through the groups)
-  const float* pre = nullptr;   // [N, PRE_W] node terms of GEMM1 (gather mode, score model) or null: GEMM1 over all 72 inputs
+  const float* pre = nullptr;   // [N, PRE_W] node terms of GEMM1 (gather mode, score model; the two-limb f16 kernel reads role slots 0, 1 only) or null: GEMM1 over all 72 inputs
   int gather;                // 1: edge_attr is edge_emb[E,24] and x[src][:24], x[dst][:24] are gathered
   // layer-0 receptor-receptor de-duplication (all samples of a batch share the receptor and, before the first conv,
   // its node/edge features): group 2 of the launch's group table is the shared copy of the receptor edges (sample-0 numbering,

@@ -607,7 +607,7 @@ hipError_t launch_conv_fused(const ConvLayerDev& L, const ConvLaunch& a, int n_c
   if (L.w2x != nullptr && (a.mode == 0 || (a.mode == 1 && a.pre == nullptr)))
     return L.limbs == 2 ? launch_conv_fused_x2(L, a, n_cu, s) : launch_conv_fused_x(L, a, n_cu, s);
   ConvKArgs k;
-  k.w1x = nullptr; k.w2x = nullptr;
+  k.w1x = nullptr; k.w1sx = nullptr; k.w2x = nullptr;
   for (int g = 0; g < CONV_MAX_GROUPS; ++g) { k.w1s[g] = 1.0f; k.w1u[g] = 1.0f; k.w2s[g] = 1.0f; k.w2u[g] = 1.0f; }
   k.x = a.x; k.src = a.src; k.dst = a.dst; k.edge_attr = a.edge_attr; k.sh = a.sh; k.sum = a.sum;
   k.counter = a.counter;

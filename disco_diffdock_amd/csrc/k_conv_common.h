@@ -12,13 +12,14 @@ struct ConvKArgs {
   const int32_t* dst;
   const float* edge_attr;
   const float* sh;
-  const float* pre;   // [N, PRE_W] per-node terms of GEMM1 (SPLIT kernels)
+  const float* pre;   // [N, PRE_W] per-node terms of GEMM1 (SPLIT kernels; the two-limb f16 form reads the receiver roles, slots 0 and 1, only)
   float* sum;
   int32_t* counter;
   const float* w1p;   // [4][3][9][64][4]
   const float* b1p;   // [4][3][2][16]
   const float* w2r;   // [4][n_tiles][W2_TILE_FLOATS]
   const uint8_t* w1x;    // f16-limb kernels: [groups][3][W1X_TILE_BYTES] GEMM1 fragments (two-limb form: W1X2_TILE_BYTES)
+  const uint8_t* w1sx;   // two-limb form, SPLIT: [groups][W1L_BYTES] K = 48 GEMM1 fragments (ConvLayerDev::w1sx)
   const uint8_t* w2x;    // f16-limb kernels: [groups][n_tiles][W2X_TILE_BYTES] tile records (two-limb form: W2X2_TILE_BYTES)
   float w1s[CONV_MAX_GROUPS], w1u[CONV_MAX_GROUPS], w2s[CONV_MAX_GROUPS], w2u[CONV_MAX_GROUPS];   // three-limb f16 kernel: weight range scales of GEMM1 / GEMM2 per weight set and their inverses
   int n_tiles;

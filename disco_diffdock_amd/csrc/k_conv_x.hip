@@ -38,7 +38,9 @@
 // The TWO-LIMB form (the default) streams records without the lo limb it never reads: 9,360 B = 585 chunks (W2X2_TILE_BYTES), so every thread moves chunk
 // tid and only threads 0..72 a second one (has1 in the kernel): waves 2-7 skip the second load / wait / store behind a wave-uniform scalar branch, wave 1 runs it
 // for nine lanes under exec.  The 4 x 4,608 B the ring gives back hold the node-term split's GEMM1 fragments of the workgroup's current weight group
-// (W1L_BYTES behind the ring: see the unit prologue), which every wave used to fetch from L2 for every unit.
+// (W1L_BYTES behind the ring: see the unit prologue).  In this form the split keeps only the RECEIVER's node term pre[src] (one row per run of lanes: edges are
+// sorted by edge_src); the sender's term W1c x[dst][:ns] - a row per EDGE when it is gathered - is formed by GEMM1 itself from the 96 B of the x[dst] row the
+// F row needs anyway: K = 48 = [edge_emb | x_dst[:ns]], three full K steps, 27 MFMAs per wave and unit.
 #include <stdlib.h>
 
 #include "k_conv_common.h"
@@ -118,25 +120,15 @@ typedef unsigned int u32x4 __attribute__((vector_size(16)));
 #define MFMA8(a, b, c) __builtin_amdgcn_mfma_f32_32x32x8f16((a), (b), (c), 0, 0, 0)
 
 // GEMM1's A fragments, per form.  w1_lo: the lo limb of a fragment of the W1 records in global memory - the two-limb records have none and the two-limb
-// products never multiply it: the hi limb stands in.  w1_split: K step 0 and the first half of K step 1 (registers 0..11) of row tile T for the node-term
-// split - the two-limb form reads them from the copy in LDS (w1l: ds_read_b128 at lane * 16, ds_read_b64 at lane * 8, conflict free), the three-limb form
-// from the records of weight group gw (w1).
+// products never multiply it: the hi limb stands in.  w1_split (three-limb form): K step 0 and the first half of K step 1 (registers 0..11) of row tile T
+// for the node-term split, from the records of weight group gw (w1).  The two-limb form's split reads its own K = 48 fragments from the copy in LDS
+// (w1l: ds_read_b128 at lane * 16, conflict free; see the unit prologue).
 struct W1Split { f16x8 h, m, l; f16x4 th, tm, tl; };
 #ifdef X3_TWO_LIMBS
 template <class TY> __device__ __forceinline__ TY w1_lo(const char*, const TY& hi) { return hi; }
-__device__ __forceinline__ W1Split w1_split(const char* w1l, const char*, int T, int lane) {
-  const char* wt = w1l + T * (2 * W1L_LIMB_BYTES);
-  W1Split f;
-  f.h = *reinterpret_cast<const f16x8*>(wt + lane * 16);
-  f.m = *reinterpret_cast<const f16x8*>(wt + W1L_LIMB_BYTES + lane * 16);
-  f.th = *reinterpret_cast<const f16x4*>(wt + 1024 + lane * 8);
-  f.tm = *reinterpret_cast<const f16x4*>(wt + W1L_LIMB_BYTES + 1024 + lane * 8);
-  f.l = f.h; f.tl = f.th;
-  return f;
-}
 #else
 template <class TY> __device__ __forceinline__ TY w1_lo(const char* p, const TY&) { return *reinterpret_cast<const TY*>(p); }
-__device__ __forceinline__ W1Split w1_split(const char*, const char* w1, int T, int lane) {
+__device__ __forceinline__ W1Split w1_split(const char* w1, int T, int lane) {
   const char* wt = w1 + (size_t)T * W1X_TILE_BYTES;
   W1Split f;
   f.h = *reinterpret_cast<const f16x8*>(wt + lane * 16);
@@ -476,19 +468,23 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
 #ifdef X3_TWO_LIMBS
     if constexpr (SPLIT) {
       // ---- GEMM1's fragments of weight group gw into w1l, when the previous unit of this workgroup ran another group (its first unit; a DisCo patch
-      // group's mapped gw): registers 0..11 of both limbs of the three row tiles, 6 x (1 KB K step 0 + 512 B half step) = W1L_BYTES.  Waves 0-5 copy
-      // one (row tile, limb) each: a 16-B and an 8-B piece per lane.  gw is uniform over the workgroup and so is this branch and its barrier.
+      // group's mapped gw): the group's K = 48 record [3 row tiles][hi | mid][3 K steps] as it lies in global memory, W1L_BYTES = 1152 16-B chunks: chunks
+      // tid and tid + 512 by every thread, tid + 1024 by waves 0 and 1 (a wave-uniform branch).  gw is uniform over the workgroup and so is the outer branch
+      // and its barrier.
       // Hazard: w1l is read by GEMM1 only; every wave has passed the previous unit's tile-loop barriers (and the unit hand-over barrier), hence its
       // GEMM1, before any thread gets here, so nobody still reads what is overwritten; the barrier below orders the new bytes before this unit's GEMM1.
+      static_assert(W1L_BYTES / 16 == 2 * 64 * CONV_WAVES + 128, "the copy below moves 1152 chunks");
       const int gw_s = __builtin_amdgcn_readfirstlane(gw);
       if (gw_s != gw_lds) {
-        if (wave < 6) {
-          const char* wsrc = reinterpret_cast<const char*>(A.w1x) + ((size_t)gw_s * 3 + (wave >> 1)) * X3_W1_TILE_BYTES + (wave & 1) * W2X_LIMB_BYTES;
-          const float4 c16 = *reinterpret_cast<const float4*>(wsrc + lane * 16);
-          const float2 c8 = *reinterpret_cast<const float2*>(wsrc + 1024 + lane * 16);
-          *reinterpret_cast<float4*>(w1l + wave * W1L_LIMB_BYTES + lane * 16) = c16;
-          *reinterpret_cast<float2*>(w1l + wave * W1L_LIMB_BYTES + 1024 + lane * 8) = c8;
+        const char* wsrc = reinterpret_cast<const char*>(A.w1sx) + (size_t)gw_s * W1L_BYTES;
+        const float4 c0 = *reinterpret_cast<const float4*>(wsrc + 16 * tid);
+        const float4 c1 = *reinterpret_cast<const float4*>(wsrc + 16 * (tid + 64 * WAVES));
+        if (wave < 2) {
+          const float4 c2 = *reinterpret_cast<const float4*>(wsrc + 16 * (tid + 128 * WAVES));
+          *reinterpret_cast<float4*>(w1l + 16 * (tid + 128 * WAVES)) = c2;
         }
+        *reinterpret_cast<float4*>(w1l + 16 * tid) = c0;
+        *reinterpret_cast<float4*>(w1l + 16 * (tid + 64 * WAVES)) = c1;
         gw_lds = gw_s;
         lds_barrier();
       }
@@ -499,12 +495,16 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
     const SegF seg = make_segf(make_segctl(sn, el, nvalid, valid));
     stamp(5);
 
-    // ---- the F row's inputs (x[dst] row, sh), requested here so that their latency runs under GEMM1 ----
-    const float4 shv = ld4(A.sh + (size_t)e * 4);
+    // ---- the F row's inputs (x[dst] row, sh), requested here so that their latency runs under GEMM1.  SENDK (the two-limb split): GEMM1 multiplies
+    // x[dst][:ns] itself, so the lane halves share the a and the c block (12 floats of each per half: mainv[0..2] = a[12 hh ..], mainv[3..5] = c[12 hh ..]) and
+    // the a part goes out in front of GEMM1 with its other inputs; sh, c, p, q follow them (below) ----
+    constexpr bool SENDK = SPLIT && X3_TWO;
+    float4 shv;
     float4 mainv[NS / 4];
     float2 pv2[3 * NV / 2];
-    {
-      const float* xr = A.x + (size_t)dn * XW;
+    const float* xr = A.x + (size_t)dn * XW;
+    if constexpr (!SENDK) {
+      shv = ld4(A.sh + (size_t)e * 4);
 #pragma unroll
       for (int j = 0; j < NS / 4; ++j) mainv[j] = ld4(xr + (hh ? OFF_C : 0) + 4 * j);
 #pragma unroll
@@ -520,6 +520,73 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
       const char* w1 = reinterpret_cast<const char*>(A.w1x) + (size_t)gw * 3 * X3_W1_TILE_BYTES;
       (void)w1;
       if constexpr (SPLIT) {
+#ifdef X3_TWO_LIMBS
+        // (W1a edge_emb + W1c x[dst][:ns]) on top of the RECEIVER's node term W1b x[src][:ns] + b1 (node_finalize_pre_kernel), which arrives in the
+        // accumulator's own register order and is the same row for a whole run of lanes (edges are sorted by src).  K = 48 = three steps of 16: register
+        // r' < 12 of a lane half is edge_emb[12 hh + r'], register 12 + i is x_dst[12 hh + i] (W1L_BYTES, ddk_internal.h).  All requests of a lane go out
+        // together, right behind the indices, GEMM1's in front: one exposed memory latency
+        float4 psv[9];
+        {
+          const float* ps = A.pre + ((size_t)sn * 4 + (gw & 1)) * NE + 36 * hh;
+#pragma unroll
+          for (int j = 0; j < 9; ++j) psv[j] = ld4(ps + 4 * j);
+        }
+        float bin[24];
+        {
+          const float* pe = A.edge_attr + (size_t)e * NS + 12 * hh;
+#pragma unroll
+          for (int j = 0; j < 3; ++j) {
+            const float4 a = ld4(pe + 4 * j);
+            bin[4 * j + 0] = a.x; bin[4 * j + 1] = a.y; bin[4 * j + 2] = a.z; bin[4 * j + 3] = a.w;
+          }
+#pragma unroll
+          for (int j = 0; j < 3; ++j) mainv[j] = ld4(xr + 12 * hh + 4 * j);
+        }
+        // ... and the rest of the F row's inputs behind them: their latency runs under GEMM1
+        shv = ld4(A.sh + (size_t)e * 4);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) mainv[3 + j] = ld4(xr + OFF_C + 12 * hh + 4 * j);
+#pragma unroll
+        for (int j = 0; j < 3 * NV / 2; ++j) pv2[j] = ld2(xr + (hh ? OFF_Q : OFF_P) + 2 * j);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { bin[12 + 4 * j + 0] = mainv[j].x; bin[12 + 4 * j + 1] = mainv[j].y; bin[12 + 4 * j + 2] = mainv[j].z; bin[12 + 4 * j + 3] = mainv[j].w; }
+        // ONE power-of-two range scale per edge over its 48 inputs (the non-split path does the same over its 72)
+        float m1 = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 24; ++j) m1 = fmaxf(m1, fabsf(bin[j]));
+        m1 = fmaxf(m1, __shfl_xor(m1, 32));          // both lane halves hold K slices of the same edge
+        float inv1;
+        const float s1 = range_scale(m1, inv1);
+        f16x8 bh[3], bm[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+          for (int i = 0; i < 8; ++i) { const Limb3 q = split3(bin[8 * k + i] * s1); bh[k][i] = q.h; bm[k][i] = q.m; }
+        const float bsc = s1 * A.w1s[gw], usc = inv1 * A.w1u[gw];
+#pragma unroll
+        for (int T = 0; T < 3; ++T) {
+          f32x16 D0;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if (T < 2 || j == 0) {
+              const float4 u = psv[4 * T + j];
+              D0[4 * j + 0] = u.x * bsc; D0[4 * j + 1] = u.y * bsc; D0[4 * j + 2] = u.z * bsc; D0[4 * j + 3] = u.w * bsc;
+            } else {
+              D0[4 * j + 0] = 0.0f; D0[4 * j + 1] = 0.0f; D0[4 * j + 2] = 0.0f; D0[4 * j + 3] = 0.0f;
+            }
+          }
+          const char* wt = w1l + T * (2 * W1L_LIMB_BYTES) + lane * 16;
+#pragma unroll
+          for (int k = 0; k < 3; ++k) {
+            const f16x8 ah = *reinterpret_cast<const f16x8*>(wt + k * 1024), am = *reinterpret_cast<const f16x8*>(wt + W1L_LIMB_BYTES + k * 1024);
+            X3_STEP(MFMA16, ah, am, ah, bh[k], bm[k], bh[k])
+          }
+          const int nr = T < 2 ? 16 : 4;
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if (r < nr) h[16 * T + r] = fmaxf(D0[r], 0.0f) * usc;
+        }
+#else
         // W1a edge_emb on top of the per-node terms (W1b x[src][:ns] + b1) + W1c x[dst][:ns] (node_finalize_pre_kernel), which arrive in the
         // accumulator's own register order: K = 24 = one step of 16 + one of 8.  The node terms sit at random nodes of a 15 MB array (past the
         // L2): all 18 requests of a lane go out together, right behind the indices - one exposed memory latency, not one per row tile
@@ -568,18 +635,14 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
           }
 #pragma unroll
           for (int r = 0; r < 16; ++r) D1[r] = 0.0f;
-          const W1Split wf = w1_split(w1l, w1, T, lane);
+          const W1Split wf = w1_split(w1, T, lane);
           X3_STEP(MFMA16, wf.h, wf.m, wf.l, b0h, b0m, b0l)
           {     // registers 8..11: the first half of step 1's fragment
             const f16x4 ah = wf.th, am = wf.tm, al = wf.tl;
             // (the K = 8 half step packed like the tile tail: hi.mid + mid.hi, lo.hi + hi.lo, hi.hi + mid.mid as one K = 16 MFMA each: 9 instead of 12 per row tile)
             const f16x8 a_hm = __builtin_shufflevector(ah, am, 0, 1, 2, 3, 4, 5, 6, 7), a_lh = __builtin_shufflevector(al, ah, 0, 1, 2, 3, 4, 5, 6, 7);
             D0 = MFMA16(a_hm, b1_mh, D0);
-#ifndef X3_TWO_LIMBS
             D1 = MFMA16(a_lh, b1_hl, D1);
-#else
-            (void)a_lh; (void)b1_hl;
-#endif
             D0 = MFMA16(a_hm, b1_hm, D0);
           }
           const int nr = T < 2 ? 16 : 4;
@@ -587,6 +650,7 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
           for (int r = 0; r < 16; ++r)
             if (r < nr) h[16 * T + r] = fmaxf(X3_SUM(r), 0.0f) * usc;
         }
+#endif
       } else {
         float bin[36];
         {
@@ -666,9 +730,13 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void conv_x3_kernel(ConvXArgs AX) 
     const float s0 = shv.x, vx = shv.y, vy = shv.z, vz = shv.w;
     {
       // half 0: a -> FX_A, p: (p.v)/sqrt3 -> FX_PQ, raw p -> rows 0..nv-1 of FX_R;  half 1: c -> FX_C, q: (q.v)/sqrt3 -> FX_PQ, raw q -> rows nv..
+      // (SENDK: each half holds 12 floats of a and 12 of c)
       const int o_main_dst = hh ? FX_C : FX_A, r0 = hh ? NV : 0;
 #pragma unroll
-      for (int j = 0; j < NS / 4; ++j) *reinterpret_cast<float4*>(Fr + o_main_dst + 4 * j) = mainv[j];
+      for (int j = 0; j < NS / 4; ++j) {
+        if constexpr (SENDK) *reinterpret_cast<float4*>(Fr + (j < 3 ? FX_A : FX_C - 12) + 12 * hh + 4 * j) = mainv[j];
+        else *reinterpret_cast<float4*>(Fr + o_main_dst + 4 * j) = mainv[j];
+      }
       float pv[3 * NV];
 #pragma unroll
       for (int j = 0; j < 3 * NV / 2; ++j) { pv[2 * j] = pv2[j].x; pv[2 * j + 1] = pv2[j].y; }
@@ -987,11 +1055,12 @@ void conv_det_fix(const ConvKArgs& k, const ConvLaunch& a, int dout, hipStream_t
 
 hipError_t launch_conv_fused_x(const ConvLayerDev& L, const ConvLaunch& a, int n_cu, hipStream_t s) {
   if (a.mode != 0 && a.mode != 1) return hipErrorInvalidValue;
+  if (X3_TWO && a.gather && a.pre != nullptr && (!L.sender_in_gemm1 || L.w1sx == nullptr)) return hipErrorInvalidValue;      // the two-limb split reads the K = 48 records
   ConvXArgs X;
   ConvKArgs& k = X.k;
   k.x = a.x; k.src = a.src; k.dst = a.dst; k.edge_attr = a.edge_attr; k.sh = a.sh; k.sum = a.sum;
   k.counter = a.counter;
-  k.w1p = nullptr; k.b1p = L.b1p[0]; k.w2r = nullptr; k.w1x = L.w1x; k.w2x = L.w2x; k.n_tiles = L.n_tiles;
+  k.w1p = nullptr; k.b1p = L.b1p[0]; k.w2r = nullptr; k.w1x = L.w1x; k.w1sx = L.w1sx; k.w2x = L.w2x; k.n_tiles = L.n_tiles;
   for (int g = 0; g < CONV_MAX_GROUPS; ++g) { k.w1s[g] = L.w1s[g]; k.w1u[g] = 1.0f / L.w1s[g]; k.w2s[g] = L.w2s[g]; k.w2u[g] = 1.0f / L.w2s[g]; }
   k.n_cols = L.n_cols;
   for (int c = 0; c <= L.n_cols; ++c) k.col_start[c] = L.col_start[c];

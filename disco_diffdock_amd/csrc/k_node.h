@@ -8,7 +8,8 @@ namespace ddk {
 
 // node_finalize of one layer (FINALIZE) + the per-node terms of the NEXT layer's GEMM1 (ConvLayerDev::wn): one workgroup = PRE_TILE nodes
 // of one node type, thread t = (role slot t / 72, hidden position t % 72) with its 24 weights in registers; the node scalars are read
-// from LDS as broadcast 16-B words (one LDS instruction per four FMAs).  Bound by the 1152 B per node it writes.
+// from LDS as broadcast 16-B words (one LDS instruction per four FMAs).  Bound by the 1152 B per node it writes (576 B for the two-limb f16 conv kernel,
+// which reads the two receiver roles only: NodePreArgs::lig_roles / rec_roles).
 #ifndef PRE_TILE_N
 #define PRE_TILE_N 16      // nodes per workgroup: 16 -> 10.2 us, 32 -> 12.5 us, 64 -> 17.9 us, 8 -> 9.7 us per launch at 13 200 nodes (the phase-2 loop is a serial chain per thread)
 #endif
@@ -117,7 +118,9 @@ __device__ __forceinline__ void node_finalize_pre_body(const NodePreArgs& A, con
   }
   if (A.pre == nullptr) return;
   __syncthreads();
-  if (!(((lig ? A.lig_roles : A.rec_roles) >> (tid / NE)) & 1)) return;      // a role the next layer does not evaluate (its last layer: ligand side only)
+  // a role the next layer does not evaluate (its last layer: ligand side only), or one its kernel does not read at all (the two-limb f16 kernel multiplies
+  // the sender's columns itself: its contexts clear the bits of role slots 2, 3)
+  if (!(((lig ? A.lig_roles : A.rec_roles) >> (tid / NE)) & 1)) return;
   float* out = A.pre + (size_t)node0 * PRE_W + tid;
 #pragma unroll 4
   for (int n = 0; n < cnt; ++n) {

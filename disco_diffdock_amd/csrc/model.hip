@@ -509,10 +509,13 @@ static int score_forward_impl(ddk_ctx* ctx, ddk_complex* cx, int B, const float*
   NE_.lig_unc = M->dev.lig_node_unc; NE_.rec_unc = M->dev.rec_node_unc; NE_.unconditional = cx->unconditional; NE_.latent_dim = c.latent_dim;
   // per-node terms of layer 0's GEMM1 (ConvLayerDev::wn): one launch with the node embedding itself
   const bool split = ctx->conv[0].wn != nullptr && cx->pre != nullptr;
+  // the two-limb f16 kernel (conv_kernel = 0) forms the SENDER's term inside its GEMM1: its contexts need the two receiver roles only (slots 0, 1)
+  const bool recv_only = split && ctx->conv[0].sender_in_gemm1;
+  const int role_mask = recv_only ? 0x3 : 0xF;
   if (split) {
     NodePreArgs PA = {};
     PA.x_out = xin; PA.n_lig_total = B * n_lig; PA.n_rec_total = B * n_rec; PA.n_rec = n_rec;
-    PA.wn = ctx->conv[0].wn; PA.bnp = ctx->conv[0].bnp; PA.pre = cx->pre; PA.n_slots = 1; PA.lig_roles = 15; PA.rec_roles = 15;
+    PA.wn = ctx->conv[0].wn; PA.bnp = ctx->conv[0].bnp; PA.pre = cx->pre; PA.n_slots = 1; PA.lig_roles = role_mask; PA.rec_roles = role_mask;
     // ONE launch: the edge features and, beside them, the node embedding + layer 0's node terms (they depend on t and the latents only)
     CK(launch_edge_features_node(F, feat_cap, PA, NE_, s), "edge features + node embed + node_pre");
   } else {
@@ -589,7 +592,7 @@ static int score_forward_impl(ddk_ctx* ctx, ddk_complex* cx, int B, const float*
       // the last layer evaluates groups 0 and 1 only (unless the receptor rows were asked for): ligand atoms receive in both and send in group 0,
       // residues only send in group 1 -> 3 of 4 resp. 1 of 4 role slots
       const bool next_lig_only = (l + 1 == NL - 1) && !cx->keep_rec;
-      PA.lig_roles = next_lig_only ? 0x7 : 0xF; PA.rec_roles = next_lig_only ? 0x4 : 0xF;
+      PA.lig_roles = (next_lig_only ? 0x7 : 0xF) & role_mask; PA.rec_roles = (next_lig_only ? 0x4 : 0xF) & role_mask;
       PA.levels = prune ? cx->levels : nullptr; PA.max_level = l == NL - 2 ? 0 : (l == NL - 3 ? 1 : (l == NL - 4 ? 2 : 3));
       CK(launch_node_finalize_pre(PA, true, s), "node_finalize_pre");
     } else
