@@ -856,6 +856,21 @@ int ddk_tp_forward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float*
   return DDK_OK;
 }
 
+int ddk_tp_backward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float* sh, const float* w, const float* grad_out, int64_t E,
+                    float* grad_x, float* grad_sh, float* grad_w, void* stream) {
+  int rc = check_launchable(ctx, layer);
+  if (rc) return rc;
+  if (!grad_x && !grad_sh && !grad_w) return fail(ctx, DDK_ERR_INVALID, "ddk_tp_backward: no gradient requested (grad_x, grad_sh and grad_w are all null)");
+  if (E < 0) return fail(ctx, DDK_ERR_INVALID, "ddk_tp_backward: negative edge count");
+  if (E > 0 && (!x_dst || !sh || !grad_out || (!w && (grad_x || grad_sh))))
+    return fail(ctx, DDK_ERR_INVALID, "ddk_tp_backward: null operand (w may be null only when grad_w alone is requested)");
+  hipError_t e = launch_tp_backward(ctx->conv[layer], x_dst, sh, w, grad_out, E, grad_x, grad_sh, grad_w, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue)
+    return fail(ctx, DDK_ERR_INVALID, "ddk_tp_backward: the layer's irreps are not one of the four conv-layer shapes of this model family (24x0e [+ 6x1o [+ 6x1e [+ 24x0o]]] -> the next entry)");
+  if (e != hipSuccess) return hip_fail(ctx, e, "tp_backward launch");
+  return DDK_OK;
+}
+
 int ddk_conv_forward(ddk_ctx* ctx, int32_t layer, const float* x, int64_t N, const int32_t* edge_src,
                      const int32_t* edge_dst, const int64_t* go, const float* edge_attr, const float* sh, float* out,
                      void* stream) {

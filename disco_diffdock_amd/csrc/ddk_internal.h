@@ -327,4 +327,7 @@ hipError_t launch_node_finalize(float* sum, const int32_t* deg, const float* x_i
 // k_tp.hip
 hipError_t launch_tp_forward(const ConvLayerDev& L, const float* x_dst, const float* sh, const float* w, int64_t E,
                              float* out, hipStream_t s);
+// k_tp_bwd.hip: the vector-Jacobian product of launch_tp_forward; a null output is not computed (w is read only for grad_x / grad_sh)
+hipError_t launch_tp_backward(const ConvLayerDev& L, const float* x_dst, const float* sh, const float* w, const float* grad_out, int64_t E,
+                              float* grad_x, float* grad_sh, float* grad_w, hipStream_t s);
 }  // namespace ddk

@@ -275,6 +275,40 @@ class Context:
         self._check(self.L.ddk_tp_forward(self.h, layer, _ptr(x_dst), _ptr(sh), _ptr(w), E, _ptr(out), _stream()), 'ddk_tp_forward')
         return out
 
+    def tp_backward(self, layer, x_dst, sh, w, grad_out, need=(True, True, True)):
+        """The vector-Jacobian product of ``tp_forward`` (ddk_tp_backward): (grad_x | None, grad_sh | None, grad_w | None) for the three flags of
+        ``need``.  ``w`` may be None when grad_w alone is asked for (it does not depend on w, and w is not read then)."""
+        need_x, need_sh, need_w = (bool(n) for n in need)
+        if not (need_x or need_sh or need_w):
+            raise RuntimeError('ddk: tp_backward needs at least one gradient to compute')
+        if w is None and (need_x or need_sh):
+            raise RuntimeError('ddk: tp_backward needs w for grad_x and grad_sh')
+        x_dst, sh, grad_out = (_need_cuda(t).contiguous().float() for t in (x_dst, sh, grad_out))
+        E = x_dst.shape[0]
+        if need_x or need_sh:
+            w = _need_cuda(w).contiguous().float()
+            if w.dim() != 2 or w.shape[0] != E:
+                raise RuntimeError('ddk: tp_backward takes w [E, W]; got ' + str(tuple(w.shape)))
+            W = w.shape[1]
+        else:
+            w, W = None, self.tp_weight_numel(layer)
+        if sh.shape != (E, 4) or grad_out.dim() != 2 or grad_out.shape[0] != E:
+            raise RuntimeError('ddk: tp_backward takes sh [E, 4] and grad_out [E, Dout]')
+        new = lambda cols: torch.empty((E, cols), dtype=torch.float32, device=x_dst.device)
+        gx, gsh, gw = new(x_dst.shape[1]) if need_x else None, new(4) if need_sh else None, new(W) if need_w else None
+        if E == 0:      # (an empty tensor has no address: the entry would see no output at all)
+            return gx, gsh, gw
+        self._check(self.L.ddk_tp_backward(self.h, layer, _ptr(x_dst), _ptr(sh), _ptr(w), _ptr(grad_out), E, _ptr(gx), _ptr(gsh), _ptr(gw), _stream()),
+                    'ddk_tp_backward')
+        return gx, gsh, gw
+
+    def tp_weight_numel(self, layer):
+        """W of conv layer ``layer``: the length of a FasterTensorProduct weight row (tensor_layers.py:56-63)."""
+        ns, nv = self.cfg.ns, self.cfg.nv
+        i, o = [(ns, 0, 0, 0), (ns, nv, 0, 0), (ns, nv, nv, 0), (ns, nv, nv, ns)][min(layer, 3)], [(ns, nv, 0, 0), (ns, nv, nv, 0), (ns, nv, nv, ns)][min(layer, 2)]
+        rows = (i[0] + i[1], i[0] + i[1] + i[2], i[1] + i[2] + i[3], i[2] + i[3])
+        return sum(r * c for r, c in zip(rows, o))
+
     def conv_forward(self, layer, x, edge_src, edge_dst, group_offsets, edge_attr, sh, dout):
         x, edge_attr, sh = x.contiguous().float(), edge_attr.contiguous().float(), sh.contiguous().float()
         edge_src, edge_dst = edge_src.contiguous().int(), edge_dst.contiguous().int()

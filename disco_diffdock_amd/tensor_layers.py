@@ -14,6 +14,7 @@ import math
 
 import torch
 from torch import nn
+from torch.autograd.function import once_differentiable
 
 from .runtime import Context
 
@@ -58,12 +59,43 @@ _shape_ctx = {}
 
 
 def _shape_context(device_index):
-    """Context without weights: enough for ddk_tp_forward (shape-only layers)."""
+    """Context without weights: enough for ddk_tp_forward and ddk_tp_backward (shape-only layers)."""
     if device_index not in _shape_ctx:
         ctx = Context(device=device_index)
         ctx.finalize()
         _shape_ctx[device_index] = ctx
     return _shape_ctx[device_index]
+
+
+def _as_rows(t, cols):
+    """[..., cols] -> contiguous fp32 [E, cols]; the tensor itself when it already is that"""
+    return t.reshape(-1, cols).contiguous().float()
+
+
+class _FasterTPFunction(torch.autograd.Function):
+    """ddk_tp_forward with ddk_tp_backward as its vector-Jacobian product (one launch each way).  Inputs keep their shapes and dtypes: the gradients
+    come back in them."""
+
+    @staticmethod
+    def forward(fctx, in_, sh, weight, layer, weight_numel, out_size):
+        ctx = _shape_context(in_.device.index or 0)
+        x, s, w = _as_rows(in_, in_.shape[-1]), _as_rows(sh, 4), _as_rows(weight, weight_numel)
+        out = ctx.tp_forward(layer, x, s, w, out_size)
+        fctx.save_for_backward(x, s, w if (fctx.needs_input_grad[0] or fctx.needs_input_grad[1]) else None)      # grad_w alone does not read w
+        fctx.layer, fctx.ddk = layer, ctx
+        fctx.meta = [(t.shape, t.dtype) for t in (in_, sh, weight)]
+        return out.reshape(in_.shape[:-1] + (out_size,))
+
+    @staticmethod
+    @once_differentiable
+    def backward(fctx, grad_out):
+        x, s, w = fctx.saved_tensors
+        need = tuple(fctx.needs_input_grad[:3])
+        g = grad_out.reshape(-1, grad_out.shape[-1]).contiguous().float()
+        with torch.cuda.device(x.device):
+            grads = fctx.ddk.tp_backward(fctx.layer, x, s, w, g, need)
+        grads = [None if gr is None else gr.reshape(shape).to(dtype) for gr, (shape, dtype) in zip(grads, fctx.meta)]
+        return grads[0], grads[1], grads[2], None, None, None
 
 
 class FasterTensorProduct(nn.Module):
@@ -82,6 +114,8 @@ class FasterTensorProduct(nn.Module):
     def forward(self, in_, sh, weight):
         if not in_.is_cuda:
             raise RuntimeError('ddk FasterTensorProduct runs on the GPU only (no CPU fallback)')
+        if torch.is_grad_enabled() and (in_.requires_grad or sh.requires_grad or weight.requires_grad):
+            return _FasterTPFunction.apply(in_, sh, weight, self.layer, self.weight_numel, self.out_size)
         lead = in_.shape[:-1]
         ctx = _shape_context(in_.device.index or 0)
         out = ctx.tp_forward(self.layer, in_.reshape(-1, in_.shape[-1]), sh.reshape(-1, 4),

@@ -110,6 +110,11 @@ int ddk_set_score_norm_tables(ddk_ctx* ctx, const double* so3_exp_score_norms, i
 int ddk_tp_forward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float* sh, const float* w,
                    int64_t E, float* out, void* stream);
 
+/* VJP of ddk_tp_forward.  All DEVICE pointers; no allocation, no synchronisation.  grad_x [E,Din], grad_sh [E,4], grad_w [E,W]: each may be NULL (not computed);
+ * all three NULL is DDK_ERR_INVALID.  w may be NULL iff grad_x == grad_sh == NULL.  E == 0: DDK_OK, no launch.  Outputs must not alias inputs. */
+int ddk_tp_backward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float* sh, const float* w, const float* grad_out, int64_t E,
+                    float* grad_x, float* grad_sh, float* grad_w, void* stream);
+
 /* ---- a11: TensorProductConvLayer.forward(node_attr, edge_index, edge_attr, edge_sh)
  *      models/tensor_layers.py:147-168 for conv layer `layer`, fused: radial MLP (fp32 MFMA) +
  *      tensor product + segmented scatter-sum + mean + BatchNorm(eval) + residual, without ever

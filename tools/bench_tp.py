@@ -2,7 +2,12 @@
 weights [E, W] resident in HBM (SURVEY.md 8(d) boundary (A): 8 184 B per edge at layers 3 / 4, 0.7 FLOP/B - HBM-bound).  Times ddk_tp_forward
 (tp_stream_kernel, k_tp.hip) with events on the launch stream and checks a slice against the fp64 restatement below.
 
-    python tools/bench_tp.py [--layer 3] [--edges 800000] [--json out.json]        (run it under rocprofv3 --kernel-trace / --pmc for the profile)"""
+    python tools/bench_tp.py [--layer 3] [--edges 800000] [--json out.json]        (run it under rocprofv3 --kernel-trace / --pmc for the profile)
+
+    python tools/bench_tp.py --backward [--edges 800000] [--json out.json]
+times, for each of the four layer shapes, the forward, ddk_tp_backward (tp_bwd_kernel, k_tp_bwd.hip) with all outputs, with grad_w alone and with
+grad_x + grad_sh alone, and in the same run what a user has without it: PyTorch autograd, forward plus backward, of a plain-torch fp32 restatement.
+Every figure is the median of --repeats passes of --iters calls between two events, after warm-up; GB/s are the algorithmic bytes of each mode."""
 import argparse, json, os, sys
 import torch
 sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), '..')))
@@ -13,9 +18,112 @@ p.add_argument('--layer', type=int, default=3)
 p.add_argument('--edges', type=int, default=800000)
 p.add_argument('--iters', type=int, default=10)
 p.add_argument('--json', default=None)
+p.add_argument('--backward', action='store_true')
+p.add_argument('--repeats', type=int, default=5)
+p.add_argument('--baseline-edges', type=int, default=None, help='edges of the torch baseline (default: --edges; a smaller count is scaled and reported)')
 a = p.parse_args()
 dev = torch.device('cuda:0')
 seq = ['24x0e', '24x0e+6x1o', '24x0e+6x1o+6x1e', '24x0e+6x1o+6x1e+24x0o']
+MULS = [(24, 0, 0, 0), (24, 6, 0, 0), (24, 6, 6, 0), (24, 6, 6, 24)]
+
+
+def tp_torch(x, sh, w, im, om):
+    """tensor_layers.py:65-116 in plain torch, any dtype: the autograd baseline (fp32) and the check (fp64) of --backward"""
+    n, (A, P, Q, C) = x.shape[0], im
+    a_, p_ = x[:, :A], x[:, A:A + 3 * P].reshape(n, P, 3)
+    q_, c_ = x[:, A + 3 * P:A + 3 * P + 3 * Q].reshape(n, Q, 3), x[:, A + 3 * P + 3 * Q:]
+    s0, v = sh[:, :1], sh[:, None, 1:]
+    cross = lambda t: torch.cross(t, v.expand_as(t), dim=-1) / 2 ** 0.5
+    rows = [torch.cat([a_ * s0, (p_ * v).sum(-1) / 3 ** 0.5], 1)[..., None],
+            torch.cat([a_[..., None] * v, p_ * s0[..., None], cross(q_)], 1),
+            torch.cat([cross(p_), q_ * s0[..., None], c_[..., None] * v], 1),
+            torch.cat([(q_ * v).sum(-1) / 3 ** 0.5, c_ * s0], 1)[..., None]]
+    out, off = [], 0
+    for r, n_out in zip(rows, om):
+        n_in = r.shape[1]
+        if n_out == 0 or n_in == 0:
+            continue
+        wk = w[:, off:off + n_in * n_out].reshape(n, n_in, n_out)
+        off += n_in * n_out
+        out.append((torch.einsum('eic,eio->eoc', r, wk) / n_in ** 0.5).reshape(n, -1))
+    return torch.cat(out, 1)
+
+
+def median_ms(fn, iters, repeats):
+    for _ in range(2):
+        fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(repeats):
+        st, en = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        st.record()
+        for _ in range(iters):
+            fn()
+        en.record()
+        torch.cuda.synchronize()
+        times.append(st.elapsed_time(en) / iters)
+    return sorted(times)[len(times) // 2]
+
+
+def bench_backward():
+    from disco_diffdock_amd.tensor_layers import _shape_context
+    ctx = _shape_context(0)
+    E, results = a.edges, []
+    for layer in range(4):
+        im, om = MULS[layer], MULS[min(layer + 1, 3)]
+        tp = FasterTensorProduct(seq[layer], '1x0e+1x1o', seq[min(layer + 1, 3)])
+        W, din, dout = tp.weight_numel, im[0] + 3 * im[1] + 3 * im[2] + im[3], om[0] + 3 * om[1] + 3 * om[2] + om[3]
+        gen = torch.Generator(device=dev).manual_seed(layer)
+        x, sh, w, g = (torch.randn(E, n, device=dev, generator=gen) for n in (din, 4, W, dout))
+        # a slice against fp64 autograd of the restatement
+        n = 2048
+        xs, ss, ws = (t[:n].double().requires_grad_(True) for t in (x, sh, w))
+        want = torch.autograd.grad(tp_torch(xs, ss, ws, im, om), (xs, ss, ws), g[:n].double())
+        got = ctx.tp_backward(layer, x, sh, w, g)
+        err = max(float((a_[:n].double() - b_).abs().max() / b_.abs().max()) for a_, b_ in zip(got, want))
+        assert err < 1e-5, (layer, err)
+        del got, want, xs, ss, ws
+        rd_all, wr_all = 4 * (W + din + dout + 4), 4 * (W + din + 4)
+        modes = {'forward': (lambda: ctx.tp_forward(layer, x, sh, w, dout), 4 * (W + din + 4) + 4 * dout),
+                 'backward_all': (lambda: ctx.tp_backward(layer, x, sh, w, g, (True, True, True)), rd_all + wr_all),
+                 'backward_grad_w': (lambda: ctx.tp_backward(layer, x, sh, None, g, (False, False, True)), 4 * (din + dout + 4) + 4 * W),
+                 'backward_grad_x_sh': (lambda: ctx.tp_backward(layer, x, sh, w, g, (True, True, False)), rd_all + 4 * (din + 4))}
+        res = {'layer_shape': layer, 'edges': E, 'W': W, 'max_rel_err_vs_fp64': err}
+        for name, (fn, nbytes) in modes.items():
+            ms = median_ms(fn, a.iters, a.repeats)
+            gbps = E * nbytes / ms / 1e6
+            res[name] = {'ms': ms, 'bytes_per_edge': nbytes, 'GBps': gbps, 'frac_of_6300': gbps / 6300}
+        for name in ('backward_all', 'backward_grad_w', 'backward_grad_x_sh'):
+            res[name]['ratio_to_forward_ms'] = res[name]['ms'] / res['forward']['ms']
+        # the baseline: torch autograd of the fp32 restatement, forward + backward, with the same inputs asking for a gradient
+        Eb = a.baseline_edges or E
+        xb, sb, wb, gb = x[:Eb], sh[:Eb], w[:Eb], g[:Eb]
+
+        def torch_step(need):
+            ins = [t.detach().requires_grad_(r) for t, r in zip((xb, sb, wb), need)]
+            torch.autograd.grad(tp_torch(*ins, im, om), [t for t, r in zip(ins, need) if r], gb)
+
+        base = {}
+        for name, need in (('backward_all', (True, True, True)), ('backward_grad_w', (False, False, True)), ('backward_grad_x_sh', (True, True, False))):
+            base[name] = median_ms(lambda: torch_step(need), max(1, a.iters // 3), a.repeats) * E / Eb
+        with torch.no_grad():
+            base['forward'] = median_ms(lambda: tp_torch(xb, sb, wb, im, om), max(1, a.iters // 3), a.repeats) * E / Eb
+        res['torch_baseline'] = {'edges': Eb, 'forward_ms': base['forward'], 'forward_plus_backward_ms': {k: v for k, v in base.items() if k != 'forward'}}
+        res['speedup_forward_plus_backward'] = {k: base[k] / (res['forward']['ms'] + res[k]['ms']) for k in ('backward_all', 'backward_grad_w', 'backward_grad_x_sh')}
+        res['speedup_forward'] = base['forward'] / res['forward']['ms']
+        res['faster_than_torch_in_every_mode'] = all(v > 1 for v in res['speedup_forward_plus_backward'].values()) and res['speedup_forward'] > 1
+        print(json.dumps(res), flush=True)
+        results.append(res)
+        del x, sh, w, g, xb, sb, wb, gb
+        torch.cuda.empty_cache()
+    if a.json:
+        json.dump(results, open(a.json, 'w'), indent=1)
+    assert all(r['faster_than_torch_in_every_mode'] for r in results), 'a mode is slower than the torch baseline'
+
+
+if a.backward:
+    bench_backward()
+    sys.exit(0)
 i_irr, o_irr = seq[min(a.layer, 3)], seq[min(a.layer + 1, 3)]
 tp = FasterTensorProduct(i_irr, '1x0e+1x1o', o_irr)
 E, W = a.edges, tp.weight_numel
