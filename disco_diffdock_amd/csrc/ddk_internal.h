@@ -55,7 +55,7 @@ template <> struct ConvTraits<1> { static constexpr int WAVES = 6, FS = F_STRIDE
 template <int MODE> constexpr size_t conv_lds_bytes() { return (size_t)(ConvTraits<MODE>::WAVES * 32 * ConvTraits<MODE>::FS + 2 * W2_TILE_FLOATS + 16) * 4; }
 static_assert(conv_lds_bytes<1>() <= 160 * 1024, "LDS budget (l<=2)");
 constexpr int CONV_MAX_GROUPS = 9;
-// Exact three-limb f16 kernel (k_conv_x.hip, ddk_config.conv_kernel = 0): W2 tile record = three limbs (hi | mid | lo, fp16, each at its own weight) x
+// Exact three-limb f16 kernel (k_conv_x.hip, ddk_config.conv_kernel = 3): W2 tile record = three limbs (hi | mid | lo, fp16, each at its own weight) x
 // [4 fragments [64 lanes][8] of K steps 0..3 | tail fragment [64][4] of the last 8 K values] | bias [2][16] f32 | pad ; element (s, lane, i) of
 // a fragment = weight of tile row lane&31 for the hidden unit held by register 8*s+i of lane half lane>>5 (K = 72 = 4 x 16 + 8)
 constexpr int W2X_LIMB_BYTES = 4 * 1024 + 512;                      // 4,608
@@ -121,7 +121,7 @@ static inline TileDesc make_tile(int kind, int f_off, int flush, int nrq, int ch
 // are cross rows, bit 15: rows j = 2,3; T1O = [p s0 (nv) ; q x v (nv)], T1E = [p x v (nv) ; q s0 (nv)]).  The confidence model's l = 2 row groups
 // (T2O: six p rows, T2E: six q rows, contracted with v^ v^T - |v^|^2 I/3) read the same raw rows and accumulate into a third set (bit 24): T2O quad q
 // = raw quad q (rows 2,3 of its second quad are q0, q1: zero weights), T2E's two tiles = raw quads 1 and 2, i.e. [. . q0 q1] and [q2 q3 q4 q5] -
-// pack_x3 moves the weight rows accordingly.  -1: not representable.
+// t2e_row_remap (conv_pack.hip) moves the weight rows accordingly.  -1: not representable.
 constexpr int32_t X_TILE_L2 = 1 << 24;
 static inline int32_t x_tile_word(int32_t w0) {
   const int kind = w0 & 3, f_off = w0 >> 16;
@@ -299,7 +299,8 @@ hipError_t launch_conv_fused(const ConvLayerDev& L, const ConvLaunch& a, int n_c
 hipError_t launch_conv_fused_x(const ConvLayerDev& L, const ConvLaunch& a, int n_cu, hipStream_t s);   // k_conv_x.hip (three f16 limbs per operand, six products)
 hipError_t launch_conv_fused_x2(const ConvLayerDev& L, const ConvLaunch& a, int n_cu, hipStream_t s);  // k_conv_x2.hip (two limbs, three products: the default)
 hipError_t launch_split3_probe(const float* x, int64_t n, int group, float* hi, float* mid, float* lo, float* scale, hipStream_t s);
-int build_head_layer(ddk_ctx* ctx, int mode, ConvLayerDev& L);      // ddk_capi.hip: mode 2 = tor_bond_conv, 3 = final_conv
+int build_conv_layer(ddk_ctx* ctx, int mode, int l, ConvLayerDev& L);      // conv_pack.hip: mode 0 = score-model layer l, 1 = confidence-model layer l (its 9 convs)
+int build_head_layer(ddk_ctx* ctx, int mode, ConvLayerDev& L);      // conv_pack.hip: mode 2 = tor_bond_conv, 3 = final_conv
 hipError_t conv_prepare_device();     // per-device kernel attributes (dynamic LDS opt-in), called by ddk_create
 hipError_t conv_prepare_device_x();   // k_conv_x.hip
 hipError_t conv_prepare_device_x2();  // k_conv_x2.hip

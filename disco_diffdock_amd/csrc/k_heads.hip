@@ -4,7 +4,7 @@
 //   * torsion convolution (tor_bond_conv: FCTP 84 x [(0e+1o) (x) 2e] -> 24x0o + 24x0e, 72->72->288 MLP) around
 //     every rotatable bond, mean over the bond's <=32 neighbour atoms, BatchNorm, tor_final_layer.
 // Both are tensor-product convolutions and run through the fused conv kernel (k_conv.hip, explicit edge attributes) with their own
-// tile tables (ddk_capi.hip: build_head_layer): tor_bond_conv keeps only the two dot-product parts with the 1o block T of
+// tile tables (conv_pack.hip: build_head_layer): tor_bond_conv keeps only the two dot-product parts with the 1o block T of
 // sh (x) sh_2e(bond axis) in the place of the edge's sh[1:4] (W = 288: 12 tiles), final_conv is the two vector blocks with two output
 // channels each (W = 144, MLP width 48 zero padded to 72).  Here: the kernel that builds both edge sets with their 72-wide edge attributes
 // (heads_pre_kernel) and the one that finishes the two outputs (heads_post_kernel).  A launch with a few thousand edges is spread over

@@ -1,4 +1,4 @@
-"""CPU test of the f16-limb weight records a host-only context packs (ddk_capi.hip: pack_x3; layouts in csrc/ddk_internal.h): the default two-limb form's
+"""CPU test of the f16-limb weight records a host-only context packs (conv_pack.hip: pack_x3; layouts in csrc/ddk_internal.h): the default two-limb form's
 9 360-B W2 records and 9 216-B W1 tiles decoded with the offsets the kernel uses, re-added against the fp32 fragments they were split from, and held against
 the three-limb records of a conv_kernel = 3 context (same hi and mid bits at the same offsets, which stay 13 968 B)."""
 import numpy as np

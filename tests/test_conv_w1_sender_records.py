@@ -1,4 +1,4 @@
-"""CPU test of the K = 48 GEMM1 records a host-only context packs for the default conv kernel's node-term split (ddk_capi.hip: pack_x3; W1L_BYTES in
+"""CPU test of the K = 48 GEMM1 records a host-only context packs for the default conv kernel's node-term split (conv_pack.hip: pack_x3; W1L_BYTES in
 csrc/ddk_internal.h): [group][3 row tiles][hi | mid][3 K steps: [64 lanes][8 fp16]], exported as 'conv.<l>.w1sx'.  The kernel's B operand holds, in register
 r' (0..23) of lane half hh, edge_emb[12 hh + r'] for r' < 12 and x_dst[12 hh + r' - 12] behind it; element i of K step s of lane (row + 32 hh) is register
 8 s + i.  So every element is decoded and held against the column of fc.0.weight ([edge_emb | x_src | x_dst] x 24) its position stands for: first the 24
