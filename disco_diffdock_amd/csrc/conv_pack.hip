@@ -469,7 +469,7 @@ static int pack_x3(ddk_ctx* ctx, ConvLayerDev& L, int NG, const std::vector<floa
                                                    : "internal: the two-limb fp16 split of a conv weight leaves its 2^-22 window");
   L.h_w2x = w2x; L.h_w1x = w1x; L.h_w1sx = w1sx;
   L.sender_in_gemm1 = !w1sx.empty();      // the layer's split launches multiply the sender's columns themselves: its contexts form the receiver roles only
-  L.epi_ok = conv_epilogue_shapes_ok(L.h_tiles);      // launch_conv_fused_x refuses the asm-epilogue instantiation otherwise
+  L.epi_ok = conv_epilogue_shapes_ok(L.h_tiles);      // conv_select (conv_launch.hip) refuses the asm-epilogue instantiation otherwise
   L.limbs = F.limbs;      // 2: the default two-limb form, three products (k_conv_x2.hip); 3 (conv_kernel = 3): all three limbs, six products
   if (ctx->host_only) return DDK_OK;
   L.w2x = (uint8_t*)dev_alloc(ctx, w2x.size());

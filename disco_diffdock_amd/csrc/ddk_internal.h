@@ -262,7 +262,7 @@ void* dev_alloc(ddk_ctx* ctx, size_t bytes);                      // tracked, fr
 float* dev_upload(ddk_ctx* ctx, const std::vector<float>& v);
 int ensure(ddk_ctx* ctx, void** p, size_t* cap, size_t bytes);    // grow-only workspace
 
-// k_conv.hip
+// conv_launch.hip: one conv launch (the kernel is chosen from the layer and these fields: conv_select)
 struct ConvLaunch {
   const float* x;            // [N, XW] padded node features
   const int32_t* src;        // [E]
@@ -292,19 +292,16 @@ struct ConvLaunch {
   uint64_t wmap = 0x876543210ull;   // 4 bits per group: weight set of group g (the DisCo patch group 4 uses the rec-rec weights: 0x23210)
   const int32_t* gbeg = nullptr;
   const int32_t* gend = nullptr;
-  uint32_t* trace = nullptr;   // != null (three-limb kernel, split gather path): workgroup 0 records its half-phase time stamps here
+  uint32_t* trace = nullptr;   // != null (f16-limb kernels, split gather path, atomics): workgroup 0 records its half-phase time stamps here; ignored elsewhere (conv_select)
   int trace_coarse = 0;        // one record per unit instead of per tile (no stamps inside the tile loop)
 };
 hipError_t launch_conv_fused(const ConvLayerDev& L, const ConvLaunch& a, int n_cu, hipStream_t s);
-hipError_t launch_conv_fused_x(const ConvLayerDev& L, const ConvLaunch& a, int n_cu, hipStream_t s);   // k_conv_x.hip (three f16 limbs per operand, six products)
-hipError_t launch_conv_fused_x2(const ConvLayerDev& L, const ConvLaunch& a, int n_cu, hipStream_t s);  // k_conv_x2.hip (two limbs, three products: the default)
-hipError_t launch_split3_probe(const float* x, int64_t n, int group, float* hi, float* mid, float* lo, float* scale, hipStream_t s);
+hipError_t launch_split3_probe(const float* x, int64_t n, int group, float* hi, float* mid, float* lo, float* scale, hipStream_t s);      // k_conv_x.hip (test hook)
 int build_conv_layer(ddk_ctx* ctx, int mode, int l, ConvLayerDev& L);      // conv_pack.hip: mode 0 = score-model layer l, 1 = confidence-model layer l (its 9 convs)
 int build_head_layer(ddk_ctx* ctx, int mode, ConvLayerDev& L);      // conv_pack.hip: mode 2 = tor_bond_conv, 3 = final_conv
-hipError_t conv_prepare_device();     // per-device kernel attributes (dynamic LDS opt-in), called by ddk_create
-hipError_t conv_prepare_device_x();   // k_conv_x.hip
-hipError_t conv_prepare_device_x2();  // k_conv_x2.hip
+hipError_t conv_prepare_device();     // conv_launch.hip, per device: dynamic-LDS opt-in of every conv kernel of the three families, called by ddk_create
 hipError_t graph_prepare_device(int* max_rec);   // k_graph.hip, per device: dynamic-LDS opt-in of the graph kernels, largest receptor their LDS holds
+// conv_launch.hip: the small kernels around a conv launch
 hipError_t launch_conv_setup(int32_t* tile_info, const int64_t* group_offsets_host, hipStream_t s);
 hipError_t launch_conv_one_group(int32_t* gt, int n_groups, int k, int64_t E, hipStream_t s);
 hipError_t launch_pad_rows(const float* x, int64_t n, int din, float* xpad, hipStream_t s);

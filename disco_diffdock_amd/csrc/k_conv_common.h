@@ -1,4 +1,5 @@
-// Device helpers shared by the fused conv kernels (k_conv.hip: fp32 MFMA; k_conv_x.hip: exact three-limb f16 MFMA).
+// Shared by the fused conv kernels (k_conv.hip: fp32 MFMA; k_conv_x.hip / k_conv_x2.hip: three / two f16 limbs per fp32 operand) and their host side
+// (conv_launch.hip): the kernel arguments, the instantiation tables through which the kernels are launched, and the device helpers.
 #pragma once
 #include "ddk_internal.h"
 
@@ -58,6 +59,15 @@ struct ConvXArgs {      // kernel arguments of the three-limb f16 kernels (k_con
   uint32_t* trace;                  // TRACE instantiation: [8 waves][CONV_TRACE_TILES][8] s_memtime stamps of workgroup 0
   int trace_coarse;                 // 1: one record per UNIT (slots 4-7 prologue, 0 = tile loop done, 1 = tiles, 2 = unit handed over): no stamp inside the tile loop
 };
+// One instantiation of a conv kernel: its key, and what it takes to opt it in to its dynamic LDS and to launch it.  Each kernel file ends in the table of
+// its instantiations and exports only the accessor; conv_launch.hip derives the LDS opt-in (all entries) and the launch (lookup by key) from the tables.
+struct ConvKey { bool gather, split, det, trace; int mode; };
+struct ConvVariant { ConvKey key; const void* fn; int threads; size_t lds; };      // fn takes ConvKArgs (fp32 family) or ConvXArgs (f16 families)
+struct ConvTable { const ConvVariant* v; int n; };
+ConvTable conv_f32_table();     // k_conv.hip:    conv_fused_kernel<GATHER, MODE, SPLIT, DET>
+ConvTable conv_x3_table();      // k_conv_x.hip:  conv_x3_kernel<GATHER, SPLIT, DET, TRACE, MODE>
+ConvTable conv_x2_table();      // k_conv_x2.hip: conv_x2_kernel<...>, the same file in its two-limb form
+
 // every flush of the tile table closes a 4-quad scalar or a 3-quad vector column, the shared tail sits behind a scalar flush, no l = 2 rows: the column
 // shapes the generated asm epilogue of k_conv_x.hip hard-codes.  Checked by pack_x3 (ConvLayerDev::epi_ok)
 bool conv_epilogue_shapes_ok(const std::vector<TileDesc>& tiles);

@@ -41,20 +41,22 @@
 // (W1L_BYTES behind the ring: see the unit prologue).  In this form the split keeps only the RECEIVER's node term pre[src] (one row per run of lanes: edges are
 // sorted by edge_src); the sender's term W1c x[dst][:ns] - a row per EDGE when it is gathered - is formed by GEMM1 itself from the 96 B of the x[dst] row the
 // F row needs anyway: K = 48 = [edge_emb | x_dst[:ns]], three full K steps, 27 MFMAs per wave and unit.
+//
+// This file holds the kernel, the table of its instantiations (conv_x3_table, at the end) and two host helpers of the packer and the tests
+// (conv_epilogue_shapes_ok, launch_split3_probe); every conv launch goes through conv_launch.hip.
 #include <stdlib.h>
 
 #include "k_conv_common.h"
 
 // Everything that differs between the two forms this file is compiled into.  k_conv_x.hip itself is the THREE-LIMB form described above; k_conv_x2.hip
 // compiles the file a second time with X3_TWO_LIMBS as the TWO-LIMB form (ddk_config.conv_kernel = 0, include/ddk.h: the default), the same kernel
-// under its own names.  The forms differ in: the symbol names; the generated asm epilogue (two accumulators folded / one); the limb products of a K
+// under its own names.  The forms differ in: the names of the kernel and of its table; the generated asm epilogue (two accumulators folded / one); the limb products of a K
 // step and of the packed tail (X3_STEP, X3_TAIL3) and how the accumulators are summed (X3_SUM); which limbs of a fragment are read from the ring
 // (X3_FRAG, X3_TAIL_LO); and, with 3 instead of 6 MFMA shadows per K step to hide them in, the instructions pinned behind each MFMA of the burst
 // (X3_RIDERS_0..3, one per K step region, and X3_TAIL_BARES: see X3_PAIR / X3_BARE / X3_BURST_BODY in the kernel).
 #ifdef X3_TWO_LIMBS
 #define conv_x3_kernel conv_x2_kernel
-#define launch_conv_fused_x launch_conv_fused_x2
-#define conv_prepare_device_x conv_prepare_device_x2
+#define conv_x3_table conv_x2_table
 #include "k_conv_x_epi2_gen.inc"     // the tile epilogue as one asm statement per ring stage, generated for one accumulator chain: nothing to fold
 // the record this form streams and its LDS budget (ddk_internal.h)
 #define X3_TILE_BYTES W2X2_TILE_BYTES
@@ -1005,18 +1007,6 @@ hipError_t launch_split3_probe(const float* x, int64_t n, int group, float* hi, 
 
 #endif      // !X3_TWO_LIMBS
 
-template <bool GATHER, bool SPLIT, bool DET>
-static hipError_t launch_x_t(const ConvXArgs& k, int n_cu, hipStream_t s) {
-  hipLaunchKernelGGL((conv_x3_kernel<GATHER, SPLIT, DET>), dim3(n_cu), dim3(64 * CONV_WAVES), X3_LDS_BYTES, s, k);
-  return hipGetLastError();
-}
-
-template <bool GATHER, bool SPLIT, bool DET>
-static hipError_t attr_x_t() {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_x3_kernel<GATHER, SPLIT, DET>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)X3_LDS_BYTES);
-}
-
 #ifndef X3_TWO_LIMBS
 bool conv_epilogue_shapes_ok(const std::vector<TileDesc>& tiles) {
   if (tiles.empty()) return false;
@@ -1033,67 +1023,15 @@ bool conv_epilogue_shapes_ok(const std::vector<TileDesc>& tiles) {
 }
 #endif      // !X3_TWO_LIMBS
 
-hipError_t conv_prepare_device_x() {
-  hipError_t e = attr_x_t<true, true, false>();
-  if (e == hipSuccess) e = attr_x_t<true, false, false>();
-  if (e == hipSuccess) e = attr_x_t<false, false, false>();
-  if (e == hipSuccess) e = attr_x_t<true, true, true>();
-  if (e == hipSuccess) e = attr_x_t<false, false, true>();
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_x3_kernel<true, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)X3_LDS_BYTES);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_x3_kernel<true, false, false, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)X3_LDS_BYTES);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_x3_kernel<false, false, false, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)X3_LDS_BYTES);
-  return e;
+// Every instantiation of the kernel (of this form), named once: conv_launch.hip opts each entry in to its dynamic LDS and launches it by key.
+#define X3_VARIANT(GATHER, SPLIT, DET, TRACE, MODE)                                                                                  \
+  {{GATHER, SPLIT, DET, TRACE, MODE}, reinterpret_cast<const void*>(&conv_x3_kernel<GATHER, SPLIT, DET, TRACE, MODE>), 64 * CONV_WAVES, \
+   X3_LDS_BYTES}
+ConvTable conv_x3_table() {
+  static const ConvVariant t[] = {X3_VARIANT(1, 1, 0, 0, 0), X3_VARIANT(1, 0, 0, 0, 0), X3_VARIANT(0, 0, 0, 0, 0), X3_VARIANT(1, 1, 1, 0, 0),
+                                  X3_VARIANT(0, 0, 1, 0, 0), X3_VARIANT(1, 1, 0, 1, 0), X3_VARIANT(1, 0, 0, 0, 1), X3_VARIANT(0, 0, 0, 0, 1)};
+  return {t, (int)(sizeof(t) / sizeof(t[0]))};
 }
-
-void conv_det_fix(const ConvKArgs& k, const ConvLaunch& a, int dout, hipStream_t s);   // k_conv.hip
-
-hipError_t launch_conv_fused_x(const ConvLayerDev& L, const ConvLaunch& a, int n_cu, hipStream_t s) {
-  if (a.mode != 0 && a.mode != 1) return hipErrorInvalidValue;
-  if (X3_TWO && a.gather && a.pre != nullptr && (!L.sender_in_gemm1 || L.w1sx == nullptr)) return hipErrorInvalidValue;      // the two-limb split reads the K = 48 records
-  ConvXArgs X;
-  ConvKArgs& k = X.k;
-  k.x = a.x; k.src = a.src; k.dst = a.dst; k.edge_attr = a.edge_attr; k.sh = a.sh; k.sum = a.sum;
-  k.counter = a.counter;
-  k.w1p = nullptr; k.b1p = L.b1p[0]; k.w2r = nullptr; k.w1x = L.w1x; k.w1sx = L.w1sx; k.w2x = L.w2x; k.n_tiles = L.n_tiles;
-  for (int g = 0; g < CONV_MAX_GROUPS; ++g) { k.w1s[g] = L.w1s[g]; k.w1u[g] = 1.0f / L.w1s[g]; k.w2s[g] = L.w2s[g]; k.w2u[g] = 1.0f / L.w2s[g]; }
-  k.n_cols = L.n_cols;
-  for (int c = 0; c <= L.n_cols; ++c) k.col_start[c] = L.col_start[c];
-  k.sum_g2 = a.sum_g2; k.g2_node_off = a.g2_node_off;
-  k.n_groups = a.n_groups; k.n_active = a.n_active; k.n_slots = a.n_slots; k.slots = a.slots; k.wmap = a.wmap;
-  if (a.gbeg) { k.gbeg = a.gbeg; k.gend = a.gend; }
-  else { k.gbeg = a.tile_info + 5; k.gend = a.tile_info + 6; }   // 4 contiguous groups go[g] .. go[g+1] (explicit-boundary entry point)
-  k.pre = a.pre; k.part = a.part; k.det_rng = a.det_rng; k.det_nr = a.det_nr;
-  X.trace = nullptr; X.trace_coarse = a.trace_coarse;
-  if (a.mode == 1) {      // the confidence model: plain gather path (no node-term split, atomics)
-    if (a.pre != nullptr || a.part != nullptr || a.trace != nullptr) return hipErrorInvalidValue;
-    if (a.gather) hipLaunchKernelGGL((conv_x3_kernel<true, false, false, false, 1>), dim3(n_cu), dim3(64 * CONV_WAVES), X3_LDS_BYTES, s, X);
-    else hipLaunchKernelGGL((conv_x3_kernel<false, false, false, false, 1>), dim3(n_cu), dim3(64 * CONV_WAVES), X3_LDS_BYTES, s, X);
-    return hipGetLastError();
-  }
-  if (a.part != nullptr) {       // deterministic scatter
-    hipError_t e = (a.gather && a.pre != nullptr) ? launch_x_t<true, true, true>(X, n_cu, s)
-                                                  : (!a.gather ? launch_x_t<false, false, true>(X, n_cu, s) : hipErrorInvalidValue);
-    if (e != hipSuccess) return e;
-    conv_det_fix(k, a, L.dout, s);
-    return hipGetLastError();
-  }
-  // the generated asm epilogue of the hot instantiation hard-codes the column shapes of this model family (a scalar flush closes 4 row quads, a vector
-  // flush 3, the shared tail sits behind a scalar flush, no l = 2 rows): a tile table outside them must not reach it
-  if (a.gather && a.pre != nullptr && !L.epi_ok) return hipErrorInvalidValue;
-  X.trace = a.trace;
-  if (a.trace != nullptr) {
-    if (!(a.gather && a.pre != nullptr)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((conv_x3_kernel<true, true, false, true>), dim3(n_cu), dim3(64 * CONV_WAVES), X3_LDS_BYTES, s, X);
-    return hipGetLastError();
-  }
-  if (a.gather && a.pre != nullptr) return launch_x_t<true, true, false>(X, n_cu, s);
-  return a.gather ? launch_x_t<true, false, false>(X, n_cu, s) : launch_x_t<false, false, false>(X, n_cu, s);
-}
+#undef X3_VARIANT
 
 }  // namespace ddk
