@@ -243,6 +243,60 @@ int ddk_tp_backward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float
   return DDK_OK;
 }
 
+// the checks the two radial-tensor-product entries share: layer, group table, edge count
+static int rtp_check(ddk_ctx* ctx, const char* who, int32_t layer, const int64_t* go, int32_t n_groups, int64_t E) {
+  int rc = check_launchable(ctx, layer);
+  if (rc) return rc;
+  const std::string w(who);
+  if (layer > 4) return fail(ctx, DDK_ERR_INVALID, w + ": layer out of range (0..4)");
+  if (n_groups < 1 || n_groups > 4) return fail(ctx, DDK_ERR_INVALID, w + ": n_groups must be in 1..4");
+  if (E < 0 || E >= (int64_t)1 << 31) return fail(ctx, DDK_ERR_INVALID, w + ": edge count out of range");
+  if (!go) return fail(ctx, DDK_ERR_INVALID, w + ": null group_offsets");
+  if (go[0] != 0) return fail(ctx, DDK_ERR_INVALID, w + ": group_offsets must start at 0");
+  for (int g = 0; g < n_groups; ++g)
+    if (go[g + 1] < go[g]) return fail(ctx, DDK_ERR_INVALID, w + ": group_offsets are not monotone");
+  if (go[n_groups] != E) return fail(ctx, DDK_ERR_INVALID, w + ": the last group offset is not E");
+  return DDK_OK;
+}
+
+static const char* const RTP_SHAPES = ": the layer's irreps are not one of the four conv-layer shapes of this model family (24x0e [+ 6x1o [+ 6x1e [+ 24x0o]]] -> the next entry)";
+
+int ddk_rtp_forward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float* sh, const float* h, const int64_t* group_offsets, int32_t n_groups,
+                    const float* w2, const float* b2, int64_t E, float* out, void* stream) {
+  int rc = rtp_check(ctx, "ddk_rtp_forward", layer, group_offsets, n_groups, E);
+  if (rc) return rc;
+  if (E == 0) return DDK_OK;
+  if (!x_dst || !sh || !h || !w2 || !b2 || !out) return fail(ctx, DDK_ERR_INVALID, "ddk_rtp_forward: null operand");
+  hipError_t e = launch_rtp_forward(ctx->conv[layer], x_dst, sh, h, group_offsets, n_groups, w2, b2, out, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(ctx, DDK_ERR_INVALID, std::string("ddk_rtp_forward") + RTP_SHAPES);
+  if (e != hipSuccess) return hip_fail(ctx, e, "rtp_forward launch");
+  return DDK_OK;
+}
+
+int ddk_rtp_backward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float* sh, const float* h, const int64_t* group_offsets, int32_t n_groups,
+                     const float* w2, const float* b2, const float* grad_out, int64_t E, float* grad_x, float* grad_sh, float* grad_h, float* grad_w2,
+                     float* grad_b2, void* workspace, void* stream) {
+  int rc = rtp_check(ctx, "ddk_rtp_backward", layer, group_offsets, n_groups, E);
+  if (rc) return rc;
+  if (!grad_x && !grad_sh && !grad_h && !grad_w2 && !grad_b2)
+    return fail(ctx, DDK_ERR_INVALID, "ddk_rtp_backward: no gradient requested (grad_x, grad_sh, grad_h, grad_w2 and grad_b2 are all null)");
+  const bool per_edge = grad_x || grad_sh || grad_h, params = grad_w2 || grad_b2;
+  if (E > 0) {
+    if (!x_dst || !sh || !h || !grad_out) return fail(ctx, DDK_ERR_INVALID, "ddk_rtp_backward: null operand");
+    if (per_edge && !w2) return fail(ctx, DDK_ERR_INVALID, "ddk_rtp_backward: null w2 (it may be null only when grad_x, grad_sh and grad_h are all null)");
+    if ((grad_x || grad_sh) && !b2) return fail(ctx, DDK_ERR_INVALID, "ddk_rtp_backward: null b2 (grad_x and grad_sh need w = w2 h + b2)");
+    if (params && !workspace) return fail(ctx, DDK_ERR_INVALID, "ddk_rtp_backward: grad_w2 / grad_b2 need the workspace of ddk_rtp_backward_workspace");
+  }
+  if (E == 0 && !params) return DDK_OK;
+  hipError_t e = launch_rtp_backward(ctx->conv[layer], x_dst, sh, h, group_offsets, n_groups, w2, b2, grad_out, grad_x, grad_sh, grad_h, grad_w2, grad_b2,
+                                     (float*)workspace, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(ctx, DDK_ERR_INVALID, std::string("ddk_rtp_backward") + RTP_SHAPES);
+  if (e != hipSuccess) return hip_fail(ctx, e, "rtp_backward launch");
+  return DDK_OK;
+}
+
+int64_t ddk_rtp_backward_workspace(int32_t layer, int64_t E, int32_t n_groups) { return rtp_backward_workspace(layer, E, n_groups); }
+
 int ddk_conv_forward(ddk_ctx* ctx, int32_t layer, const float* x, int64_t N, const int32_t* edge_src,
                      const int32_t* edge_dst, const int64_t* go, const float* edge_attr, const float* sh, float* out,
                      void* stream) {

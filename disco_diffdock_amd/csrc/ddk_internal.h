@@ -328,4 +328,12 @@ hipError_t launch_tp_forward(const ConvLayerDev& L, const float* x_dst, const fl
 // k_tp_bwd.hip: the vector-Jacobian product of launch_tp_forward; a null output is not computed (w is read only for grad_x / grad_sh)
 hipError_t launch_tp_backward(const ConvLayerDev& L, const float* x_dst, const float* sh, const float* w, const float* grad_out, int64_t E,
                               float* grad_x, float* grad_sh, float* grad_w, hipStream_t s);
+// k_rtp.hip: the radial tensor product out = TP(x, sh, W2[g] h + b2[g]) and its vector-Jacobian product, the [E, W] weights never stored.  group_offsets is a
+// checked host prefix of n_groups + 1 entries; a null output is not computed; workspace of rtp_backward_workspace bytes where grad_w2 / grad_b2 are asked for
+hipError_t launch_rtp_forward(const ConvLayerDev& L, const float* x_dst, const float* sh, const float* h, const int64_t* group_offsets, int n_groups,
+                              const float* w2, const float* b2, float* out, hipStream_t s);
+hipError_t launch_rtp_backward(const ConvLayerDev& L, const float* x_dst, const float* sh, const float* h, const int64_t* group_offsets, int n_groups,
+                               const float* w2, const float* b2, const float* grad_out, float* grad_x, float* grad_sh, float* grad_h, float* grad_w2,
+                               float* grad_b2, float* workspace, hipStream_t s);
+int64_t rtp_backward_workspace(int32_t layer, int64_t E, int32_t n_groups);
 }  // namespace ddk

@@ -302,6 +302,65 @@ class Context:
                     'ddk_tp_backward')
         return gx, gsh, gw
 
+    def _rtp_operands(self, layer, x_dst, sh, h, group_offsets, w2, b2):
+        """checked operands of the radial tensor product: (x, sh, h, offsets as a ctypes int64 array, G, w2, b2, E, W)"""
+        x_dst, sh, h = (_need_cuda(t).contiguous().float() for t in (x_dst, sh, h))
+        offs = [int(o) for o in group_offsets]
+        G, E, W = len(offs) - 1, x_dst.shape[0], self.tp_weight_numel(layer)
+        if not 1 <= G <= 4:
+            raise RuntimeError(f'ddk: the radial tensor product takes 1..4 edge groups; got {G}')
+        if sh.shape != (E, 4) or h.shape != (E, 72):
+            raise RuntimeError('ddk: the radial tensor product takes sh [E, 4] and h [E, 72]')
+        if w2 is not None:
+            w2 = _need_cuda(w2).contiguous().float()
+            if w2.shape != (G, W, 72):
+                raise RuntimeError(f'ddk: the radial tensor product takes w2 [G, W, 72] = {(G, W, 72)}; got {tuple(w2.shape)}')
+        if b2 is not None:
+            b2 = _need_cuda(b2).contiguous().float()
+            if b2.shape != (G, W):
+                raise RuntimeError(f'ddk: the radial tensor product takes b2 [G, W] = {(G, W)}; got {tuple(b2.shape)}')
+        return x_dst, sh, h, (C.c_int64 * (G + 1))(*offs), G, w2, b2, E, W
+
+    def rtp_forward(self, layer, x_dst, sh, h, group_offsets, w2, b2, dout):
+        """The radial tensor product (ddk_rtp_forward): out [E, dout] = FasterTensorProduct(x_dst, sh, w2[g] h + b2[g]) with the per-edge weights never
+        stored.  ``group_offsets``: G + 1 host integers, edge e belongs to group g iff offsets[g] <= e < offsets[g + 1]."""
+        x_dst, sh, h, offs, G, w2, b2, E, W = self._rtp_operands(layer, x_dst, sh, h, group_offsets, w2, b2)
+        if w2 is None or b2 is None:
+            raise RuntimeError('ddk: rtp_forward needs w2 and b2')
+        out = torch.empty((E, dout), dtype=torch.float32, device=x_dst.device)
+        self._check(self.L.ddk_rtp_forward(self.h, layer, _ptr(x_dst), _ptr(sh), _ptr(h), offs, G, _ptr(w2), _ptr(b2), E, _ptr(out), _stream()), 'ddk_rtp_forward')
+        return out
+
+    def rtp_backward(self, layer, x_dst, sh, h, group_offsets, w2, b2, grad_out, need=(True, True, True, True, True)):
+        """The vector-Jacobian product of ``rtp_forward`` (ddk_rtp_backward): (grad_x, grad_sh, grad_h, grad_w2, grad_b2), None where ``need`` is false.
+        ``w2`` and ``b2`` may be None when only grad_w2 / grad_b2 are asked for; ``b2`` is read for grad_x / grad_sh alone.  The workspace of the
+        parameter gradients comes from torch's allocator and is released on return."""
+        need = tuple(bool(n) for n in need)
+        if not any(need):
+            raise RuntimeError('ddk: rtp_backward needs at least one gradient to compute')
+        if w2 is None and any(need[:3]):
+            raise RuntimeError('ddk: rtp_backward needs w2 for grad_x, grad_sh and grad_h')
+        if b2 is None and any(need[:2]):
+            raise RuntimeError('ddk: rtp_backward needs b2 for grad_x and grad_sh')
+        x_dst, sh, h, offs, G, w2, b2, E, W = self._rtp_operands(layer, x_dst, sh, h, group_offsets, w2, b2)
+        grad_out = _need_cuda(grad_out).contiguous().float()
+        if grad_out.dim() != 2 or grad_out.shape[0] != E:
+            raise RuntimeError('ddk: rtp_backward takes grad_out [E, Dout]')
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x_dst.device)
+        outs = [new(E, x_dst.shape[1]) if need[0] else None, new(E, 4) if need[1] else None, new(E, 72) if need[2] else None,
+                new(G, W, 72) if need[3] else None, new(G, W) if need[4] else None]
+        ws = None
+        if need[3] or need[4]:
+            nbytes = self.L.ddk_rtp_backward_workspace(layer, E, G)
+            if nbytes < 0:
+                raise RuntimeError(f'ddk: rtp_backward: no workspace for layer {layer}, E = {E}, {G} groups')
+            ws = torch.empty(max(int(nbytes), 4) // 4, dtype=torch.float32, device=x_dst.device)
+        elif E == 0:      # (empty tensors have no address: the entry would see no output at all)
+            return tuple(outs)
+        self._check(self.L.ddk_rtp_backward(self.h, layer, _ptr(x_dst), _ptr(sh), _ptr(h), offs, G, _ptr(w2), _ptr(b2), _ptr(grad_out), E,
+                                            *[_ptr(o) for o in outs], _ptr(ws), _stream()), 'ddk_rtp_backward')
+        return tuple(outs)      # (ws goes back to torch's allocator, which orders its reuse after this launch on the current stream)
+
     def tp_weight_numel(self, layer):
         """W of conv layer ``layer``: the length of a FasterTensorProduct weight row (tensor_layers.py:56-63)."""
         ns, nv = self.cfg.ns, self.cfg.nv

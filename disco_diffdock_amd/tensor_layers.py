@@ -6,6 +6,8 @@ parity tests read like tests of the reference modules:
 * ``TensorProductConvLayer(...).forward(node_attr, edge_index, edge_attr, edge_sh, out_nodes=None, reduce='mean')``
                                                                                           tensor_layers.py:119-168
 * ``GaussianSmearing``                                                                   tensor_layers.py:171-181
+* ``fused_radial_tp(tp, fc, x_dst, edge_sh, edge_attr)``: the radial MLP's last Linear, the cat and the tensor product
+  of tensor_layers.py:154-156 as one differentiable op that never stores the per-edge weights (training)
 
 Only the configuration the shipped score models use is implemented on the device (ns=24, nv=6, sh_lmax=1,
 faster=True, edge_groups=4, residual=True, 2-layer ReLU radial MLP, eval mode); anything else raises.
@@ -121,6 +123,65 @@ class FasterTensorProduct(nn.Module):
         out = ctx.tp_forward(self.layer, in_.reshape(-1, in_.shape[-1]), sh.reshape(-1, 4),
                              weight.reshape(-1, self.weight_numel), self.out_size)
         return out.reshape(lead + (self.out_size,))
+
+
+class _RadialTPFunction(torch.autograd.Function):
+    """ddk_rtp_forward with ddk_rtp_backward as its vector-Jacobian product: the tensor product with its weights w2[g] h + b2[g] formed inside the
+    kernels, so that neither the per-edge weights [E, W] nor their gradient exist.  Inputs keep their shapes and dtypes: the gradients come back in them."""
+
+    @staticmethod
+    def forward(fctx, in_, sh, h, w2, b2, layer, offsets, out_size):
+        ctx = _shape_context(in_.device.index or 0)
+        x, s, hh = _as_rows(in_, in_.shape[-1]), _as_rows(sh, 4), _as_rows(h, h.shape[-1])
+        w, b = w2.contiguous().float(), b2.contiguous().float()
+        out = ctx.rtp_forward(layer, x, s, hh, offsets, w, b, out_size)
+        ng = fctx.needs_input_grad
+        fctx.save_for_backward(x, s, hh, w if any(ng[:3]) else None, b if any(ng[:2]) else None)      # the parameter gradients read neither
+        fctx.layer, fctx.ddk, fctx.offsets = layer, ctx, tuple(offsets)
+        fctx.meta = [(t.shape, t.dtype) for t in (in_, sh, h, w2, b2)]
+        return out.reshape(in_.shape[:-1] + (out_size,))
+
+    @staticmethod
+    @once_differentiable
+    def backward(fctx, grad_out):
+        x, s, hh, w, b = fctx.saved_tensors
+        need = tuple(fctx.needs_input_grad[:5])
+        g = grad_out.reshape(-1, grad_out.shape[-1]).contiguous().float()
+        with torch.cuda.device(x.device):
+            grads = fctx.ddk.rtp_backward(fctx.layer, x, s, hh, fctx.offsets, w, b, g, need)
+        grads = [None if gr is None else gr.reshape(shape).to(dtype) for gr, (shape, dtype) in zip(grads, fctx.meta)]
+        return grads[0], grads[1], grads[2], grads[3], grads[4], None, None, None
+
+
+def fused_radial_tp(tp, fc, x_dst, edge_sh, edge_attr):
+    """``tp(x_dst, edge_sh, torch.cat([fc[i](edge_attr[i]) for i in range(G)]))`` of the reference's TensorProductConvLayer.forward
+    (models/tensor_layers.py:154-156) without the per-edge weights: ``fc[i][0..3]`` run in torch, the last Linear of every group runs inside the tensor
+    product's kernels, forward and backward.  ``tp``: a FasterTensorProduct; ``fc``: the layer's ModuleList of FCBlocks, or one FCBlock (edge_groups == 1);
+    ``edge_attr``: the per-group list (a tensor for one FCBlock).  Every parameter of ``fc``, ``x_dst``, ``edge_sh`` and ``edge_attr`` receive the gradients
+    the unfused composition gives them."""
+    if not isinstance(tp, FasterTensorProduct):
+        raise RuntimeError('ddk: fused_radial_tp takes a FasterTensorProduct')
+    if not x_dst.is_cuda:
+        raise RuntimeError('ddk fused_radial_tp runs on the GPU only (no CPU fallback)')
+    if isinstance(fc, nn.Sequential):
+        fc, edge_attr = [fc], ([edge_attr] if torch.is_tensor(edge_attr) else list(edge_attr))
+    fc, edge_attr = list(fc), list(edge_attr)
+    if len(fc) != len(edge_attr) or not 1 <= len(fc) <= 4:
+        raise RuntimeError('ddk: fused_radial_tp takes one edge_attr tensor per FCBlock, 1..4 of them')
+    for blk in fc:
+        if len(blk) != 5 or not isinstance(blk[4], nn.Linear) or blk[4].in_features != 72 or blk[4].out_features != tp.weight_numel or blk[4].bias is None:
+            raise RuntimeError('ddk: fused_radial_tp takes 2-layer FCBlocks whose last Linear maps 72 -> weight_numel')
+    offs = [0]
+    for ea in edge_attr:
+        offs.append(offs[-1] + ea.shape[0])
+    hidden = torch.cat([blk[:4](ea) for blk, ea in zip(fc, edge_attr)], dim=0) if len(fc) > 1 else fc[0][:4](edge_attr[0])
+    w2, b2 = torch.stack([blk[4].weight for blk in fc]), torch.stack([blk[4].bias for blk in fc])
+    if x_dst.dim() != 2 or x_dst.shape[0] != offs[-1]:
+        raise RuntimeError('ddk: fused_radial_tp takes x_dst [E, Din] with E the total of the edge groups')
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (x_dst, edge_sh, hidden, w2, b2)):
+        return _RadialTPFunction.apply(x_dst, edge_sh, hidden, w2, b2, tp.layer, tuple(offs), tp.out_size)
+    ctx = _shape_context(x_dst.device.index or 0)
+    return ctx.rtp_forward(tp.layer, x_dst, edge_sh.reshape(-1, 4), hidden, offs, w2, b2, tp.out_size)
 
 
 def FCBlock(in_dim, hidden_dim, out_dim, layers, dropout, activation='relu', batchnorm=False):

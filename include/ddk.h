@@ -115,6 +115,27 @@ int ddk_tp_forward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float*
 int ddk_tp_backward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float* sh, const float* w, const float* grad_out, int64_t E,
                     float* grad_x, float* grad_sh, float* grad_w, void* stream);
 
+/* ---- The radial tensor product of conv-layer shape `layer` (0..4): out[e] = FasterTensorProduct(x_dst[e], sh[e], w2[g(e)] h[e] + b2[g(e)]), the per-edge
+ *      weights [E, W] never stored (models/tensor_layers.py:154-156 without the last Linear's output and the cat).  x_dst [E, Din], sh [E, 4], h [E, 72] (the
+ *      radial MLP's hidden activation), w2 [n_groups, W, 72] and b2 [n_groups, W] (fc[g][4].weight / .bias stacked), out [E, Dout]: DEVICE pointers, fp32,
+ *      contiguous.  group_offsets: HOST array of n_groups + 1 entries (n_groups in 1..4), 0 = o_0 <= ... <= o_G = E; edge e belongs to group g iff
+ *      o_g <= e < o_{g+1}.  No allocation, no synchronisation.  E == 0: DDK_OK, no launch. */
+int ddk_rtp_forward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float* sh, const float* h, const int64_t* group_offsets, int32_t n_groups,
+                    const float* w2, const float* b2, int64_t E, float* out, void* stream);
+
+/* VJP of ddk_rtp_forward.  grad_x [E, Din], grad_sh [E, 4], grad_h [E, 72], grad_w2 [n_groups, W, 72], grad_b2 [n_groups, W]: each may be NULL (not computed);
+ * all five NULL is DDK_ERR_INVALID.  w2 and b2 may be NULL iff grad_x == grad_sh == grad_h == NULL (b2 is read for grad_x / grad_sh only: they need
+ * w = w2 h + b2).  workspace: ddk_rtp_backward_workspace(layer, E, n_groups) bytes of device memory, needed only when grad_w2 or grad_b2 is asked for.
+ * E == 0 and groups without edges: the grad_w2 / grad_b2 asked for are written as zeros.  Outputs must not alias inputs.  The same bits from call to call,
+ * on every device, and whichever subset of the outputs is asked for. */
+int ddk_rtp_backward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float* sh, const float* h, const int64_t* group_offsets, int32_t n_groups,
+                     const float* w2, const float* b2, const float* grad_out, int64_t E, float* grad_x, float* grad_sh, float* grad_h, float* grad_w2,
+                     float* grad_b2, void* workspace, void* stream);
+
+/* Bytes of ddk_rtp_backward's workspace: a function of its arguments alone (never more than 160 MB); -1 for a layer outside 0..4, n_groups outside 1..4,
+ * E < 0 or E >= 2^31.  Host function, no context. */
+int64_t ddk_rtp_backward_workspace(int32_t layer, int64_t E, int32_t n_groups);
+
 /* ---- a11: TensorProductConvLayer.forward(node_attr, edge_index, edge_attr, edge_sh)
  *      models/tensor_layers.py:147-168 for conv layer `layer`, fused: radial MLP (fp32 MFMA) +
  *      tensor product + segmented scatter-sum + mean + BatchNorm(eval) + residual, without ever

@@ -7,7 +7,12 @@ weights [E, W] resident in HBM (SURVEY.md 8(d) boundary (A): 8 184 B per edge at
     python tools/bench_tp.py --backward [--edges 800000] [--json out.json]
 times, for each of the four layer shapes, the forward, ddk_tp_backward (tp_bwd_kernel, k_tp_bwd.hip) with all outputs, with grad_w alone and with
 grad_x + grad_sh alone, and in the same run what a user has without it: PyTorch autograd, forward plus backward, of a plain-torch fp32 restatement.
-Every figure is the median of --repeats passes of --iters calls between two events, after warm-up; GB/s are the algorithmic bytes of each mode."""
+Every figure is the median of --repeats passes of --iters calls between two events, after warm-up; GB/s are the algorithmic bytes of each mode.
+
+    python tools/bench_tp.py --radial [--edges 200000] [--iters 30] [--json out.json]
+times, for each of the four layer shapes and four equal edge groups, one training step of the op with all gradients two ways in the same run:
+tensor_layers.fused_radial_tp (ddk_rtp_forward / ddk_rtp_backward, k_rtp.hip: the per-edge weights [E, W] never exist) and the composition it replaces
+(the fc Linears, torch.cat, FasterTensorProduct forward and backward, autograd through the Linears), with the peak device memory of each."""
 import argparse, json, os, sys
 import torch
 sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), '..')))
@@ -19,6 +24,7 @@ p.add_argument('--edges', type=int, default=800000)
 p.add_argument('--iters', type=int, default=10)
 p.add_argument('--json', default=None)
 p.add_argument('--backward', action='store_true')
+p.add_argument('--radial', action='store_true')
 p.add_argument('--repeats', type=int, default=5)
 p.add_argument('--baseline-edges', type=int, default=None, help='edges of the torch baseline (default: --edges; a smaller count is scaled and reported)')
 a = p.parse_args()
@@ -121,8 +127,63 @@ def bench_backward():
     assert all(r['faster_than_torch_in_every_mode'] for r in results), 'a mode is slower than the torch baseline'
 
 
+def bench_radial():
+    from disco_diffdock_amd.tensor_layers import FCBlock, _shape_context, fused_radial_tp
+    ctx = _shape_context(0)
+    E, results = a.edges, []
+    offs = [E * k // 4 for k in range(5)]
+    for layer in range(4):
+        im, om = MULS[layer], MULS[min(layer + 1, 3)]
+        tp = FasterTensorProduct(seq[layer], '1x0e+1x1o', seq[min(layer + 1, 3)])
+        W, din, dout = tp.weight_numel, im[0] + 3 * im[1] + 3 * im[2] + im[3], om[0] + 3 * om[1] + 3 * om[2] + om[3]
+        torch.manual_seed(layer)
+        fc = torch.nn.ModuleList([FCBlock(72, 72, W, 2, 0.0) for _ in range(4)]).to(dev)
+        gen = torch.Generator(device=dev).manual_seed(layer)
+        x, sh, ea, g = (torch.randn(E, n, device=dev, generator=gen) for n in (din, 4, 72, dout))
+        X, SH = x.requires_grad_(True), sh.requires_grad_(True)
+        EA = [ea[offs[k]:offs[k + 1]].clone().requires_grad_(True) for k in range(4)]
+
+        def step(fused):
+            for t in [X, SH] + EA + list(fc.parameters()):
+                t.grad = None
+            out = fused_radial_tp(tp, fc, X, SH, EA) if fused else tp(X, SH, torch.cat([fc[k](EA[k]) for k in range(4)]))
+            out.backward(g)
+
+        res = {'layer_shape': layer, 'edges': E, 'W': W, 'one_weight_tensor_bytes': 4 * E * W, 'workspace_bytes': ctx.L.ddk_rtp_backward_workspace(layer, E, 4)}
+        grads = {}
+        for name, fused in (('fused', True), ('unfused', False)):
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            live = torch.cuda.memory_allocated()
+            step(fused)
+            torch.cuda.synchronize()
+            peak = torch.cuda.max_memory_allocated() - live
+            grads[name] = [X.grad.clone()] + [p.grad.clone() for p in fc.parameters()]
+            res[name] = {'ms': median_ms(lambda: step(fused), a.iters, a.repeats), 'peak_bytes': peak, 'peak_over_one_weight_tensor': peak / (4 * E * W)}
+        res['max_rel_diff_of_gradients'] = max(float((u - v).abs().max() / v.abs().max()) for u, v in zip(grads['fused'], grads['unfused']))
+        res['fused_over_unfused_ms'] = res['fused']['ms'] / res['unfused']['ms']
+        # the three device passes on their own (no torch around them)
+        with torch.no_grad():
+            hid = torch.cat([fc[k][:4](EA[k]) for k in range(4)])
+            w2, b2 = torch.stack([b[4].weight for b in fc]), torch.stack([b[4].bias for b in fc])
+            xd, sd = X.detach(), SH.detach()
+            res['kernels_ms'] = {
+                'forward': median_ms(lambda: ctx.rtp_forward(layer, xd, sd, hid, offs, w2, b2, dout), a.iters, a.repeats),
+                'backward_per_edge': median_ms(lambda: ctx.rtp_backward(layer, xd, sd, hid, offs, w2, b2, g, (True, True, True, False, False)), a.iters, a.repeats),
+                'backward_parameters': median_ms(lambda: ctx.rtp_backward(layer, xd, sd, hid, offs, None, None, g, (False, False, False, True, True)), a.iters, a.repeats)}
+        print(json.dumps(res), flush=True)
+        results.append(res)
+        del x, sh, ea, g, X, SH, EA, grads, hid
+        torch.cuda.empty_cache()
+    if a.json:
+        json.dump(results, open(a.json, 'w'), indent=1)
+
+
 if a.backward:
     bench_backward()
+    sys.exit(0)
+if a.radial:
+    bench_radial()
     sys.exit(0)
 i_irr, o_irr = seq[min(a.layer, 3)], seq[min(a.layer + 1, 3)]
 tp = FasterTensorProduct(i_irr, '1x0e+1x1o', o_irr)
