@@ -4,6 +4,7 @@
 #include <string.h>
 
 #include "model.h"
+#include "k_tp_shape.h"
 
 using namespace ddk;
 
@@ -217,35 +218,41 @@ static int check_launchable(ddk_ctx* ctx, int32_t layer) {
   return DDK_OK;
 }
 
-int ddk_tp_forward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float* sh, const float* w, int64_t E,
-                   float* out, void* stream) {
+// what the four tensor-product entries check first: a context that can launch, and a layer that has one of the kernels' shapes (a guard: ddk_create
+// admits ns = 24, nv = 6 only).  Asked BEFORE the launch, so that an invalid-value error of the launch itself is reported as what it is
+static int check_tp_launchable(ddk_ctx* ctx, const char* who, int32_t layer) {
   int rc = check_launchable(ctx, layer);
   if (rc) return rc;
+  if (tp_shape_index(ctx->conv[layer]) < 0)
+    return fail(ctx, DDK_ERR_INVALID, std::string(who) + ": the layer's irreps are not one of the four conv-layer shapes of this model family (24x0e [+ 6x1o [+ 6x1e [+ 24x0o]]] -> the next entry)");
+  return DDK_OK;
+}
+
+int ddk_tp_forward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float* sh, const float* w, int64_t E,
+                   float* out, void* stream) {
+  int rc = check_tp_launchable(ctx, "ddk_tp_forward", layer);
+  if (rc) return rc;
   hipError_t e = launch_tp_forward(ctx->conv[layer], x_dst, sh, w, E, out, (hipStream_t)stream);
-  if (e == hipErrorInvalidValue)      // (say what is wrong instead of a bare HIP error)
-    return fail(ctx, DDK_ERR_INVALID, "ddk_tp_forward: the layer's irreps are not one of the four conv-layer shapes of this model family (24x0e [+ 6x1o [+ 6x1e [+ 24x0o]]] -> the next entry)");
   if (e != hipSuccess) return hip_fail(ctx, e, "tp_forward launch");
   return DDK_OK;
 }
 
 int ddk_tp_backward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float* sh, const float* w, const float* grad_out, int64_t E,
                     float* grad_x, float* grad_sh, float* grad_w, void* stream) {
-  int rc = check_launchable(ctx, layer);
+  int rc = check_tp_launchable(ctx, "ddk_tp_backward", layer);
   if (rc) return rc;
   if (!grad_x && !grad_sh && !grad_w) return fail(ctx, DDK_ERR_INVALID, "ddk_tp_backward: no gradient requested (grad_x, grad_sh and grad_w are all null)");
   if (E < 0) return fail(ctx, DDK_ERR_INVALID, "ddk_tp_backward: negative edge count");
   if (E > 0 && (!x_dst || !sh || !grad_out || (!w && (grad_x || grad_sh))))
     return fail(ctx, DDK_ERR_INVALID, "ddk_tp_backward: null operand (w may be null only when grad_w alone is requested)");
   hipError_t e = launch_tp_backward(ctx->conv[layer], x_dst, sh, w, grad_out, E, grad_x, grad_sh, grad_w, (hipStream_t)stream);
-  if (e == hipErrorInvalidValue)
-    return fail(ctx, DDK_ERR_INVALID, "ddk_tp_backward: the layer's irreps are not one of the four conv-layer shapes of this model family (24x0e [+ 6x1o [+ 6x1e [+ 24x0o]]] -> the next entry)");
   if (e != hipSuccess) return hip_fail(ctx, e, "tp_backward launch");
   return DDK_OK;
 }
 
 // the checks the two radial-tensor-product entries share: layer, group table, edge count
 static int rtp_check(ddk_ctx* ctx, const char* who, int32_t layer, const int64_t* go, int32_t n_groups, int64_t E) {
-  int rc = check_launchable(ctx, layer);
+  int rc = check_tp_launchable(ctx, who, layer);
   if (rc) return rc;
   const std::string w(who);
   if (layer > 4) return fail(ctx, DDK_ERR_INVALID, w + ": layer out of range (0..4)");
@@ -259,8 +266,6 @@ static int rtp_check(ddk_ctx* ctx, const char* who, int32_t layer, const int64_t
   return DDK_OK;
 }
 
-static const char* const RTP_SHAPES = ": the layer's irreps are not one of the four conv-layer shapes of this model family (24x0e [+ 6x1o [+ 6x1e [+ 24x0o]]] -> the next entry)";
-
 int ddk_rtp_forward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float* sh, const float* h, const int64_t* group_offsets, int32_t n_groups,
                     const float* w2, const float* b2, int64_t E, float* out, void* stream) {
   int rc = rtp_check(ctx, "ddk_rtp_forward", layer, group_offsets, n_groups, E);
@@ -268,7 +273,6 @@ int ddk_rtp_forward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float
   if (E == 0) return DDK_OK;
   if (!x_dst || !sh || !h || !w2 || !b2 || !out) return fail(ctx, DDK_ERR_INVALID, "ddk_rtp_forward: null operand");
   hipError_t e = launch_rtp_forward(ctx->conv[layer], x_dst, sh, h, group_offsets, n_groups, w2, b2, out, (hipStream_t)stream);
-  if (e == hipErrorInvalidValue) return fail(ctx, DDK_ERR_INVALID, std::string("ddk_rtp_forward") + RTP_SHAPES);
   if (e != hipSuccess) return hip_fail(ctx, e, "rtp_forward launch");
   return DDK_OK;
 }
@@ -290,7 +294,6 @@ int ddk_rtp_backward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const floa
   if (E == 0 && !params) return DDK_OK;
   hipError_t e = launch_rtp_backward(ctx->conv[layer], x_dst, sh, h, group_offsets, n_groups, w2, b2, grad_out, grad_x, grad_sh, grad_h, grad_w2, grad_b2,
                                      (float*)workspace, (hipStream_t)stream);
-  if (e == hipErrorInvalidValue) return fail(ctx, DDK_ERR_INVALID, std::string("ddk_rtp_backward") + RTP_SHAPES);
   if (e != hipSuccess) return hip_fail(ctx, e, "rtp_backward launch");
   return DDK_OK;
 }

@@ -56,16 +56,11 @@ __host__ __device__ inline int64_t rtp_slice_len(int64_t E) {
 }
 
 template <class S>
-struct RtpT {
-  static constexpr int R(int k) { return k == 0 ? S::R0 : (k == 1 ? S::R1 : (k == 2 ? S::R2 : S::R3)); }
-  static constexpr int O(int k) { return k == 0 ? S::O0 : (k == 1 ? S::O1 : (k == 2 ? S::O2 : S::O3)); }
-  static constexpr int B(int k) { return k == 0 ? S::B0 : (k == 1 ? S::B1 : (k == 2 ? S::B2 : S::B3)); }
-  static constexpr bool vec(int k) { return k == 1 || k == 2; }
-  static constexpr int NRG(int k) { return O(k) ? (R(k) + 3) / 4 : 0; }
-  static constexpr int NCG(int k) { return vec(k) ? 1 : 3; }
+struct RtpT {      // the tiles of a shape: row groups and column groups of block k, its first tile, the number of tiles
+  static constexpr int NRG(int k) { return S::O(k) ? (S::R(k) + 3) / 4 : 0; }
+  static constexpr int NCG(int k) { return S::vec(k) ? 1 : 3; }
   static constexpr int T0(int k) { return k <= 0 ? 0 : T0(k - 1) + NRG(k - 1) * NCG(k - 1); }
   static constexpr int NT = T0(4);
-  static constexpr int GOFF(int k) { return k == 0 ? 0 : (k == 1 ? S::O0 : (k == 2 ? S::O0 + 3 * S::O1 : S::O0 + 3 * S::O1 + 3 * S::O2)); }
   static_assert(S::O0 == 24 && (S::O3 == 0 || S::O3 == 24) && (S::O1 == 0 || S::O1 == 6) && (S::O2 == 0 || S::O2 == 6), "three column groups of 8, or one of 6");
 };
 
@@ -116,13 +111,10 @@ __device__ __forceinline__ RtpRow rtp_row(int k, int r) {
 }
 
 template <class S>
-__device__ __forceinline__ float rtp_rs(int k) {      // tensor_layers.py:89-92
+__device__ __forceinline__ float rtp_rs(int k) {      // of a block index that is a run-time value (the chain is written out: k_tp_shape.h)
   const int Rk = k == 0 ? S::R0 : (k == 1 ? S::R1 : (k == 2 ? S::R2 : S::R3));
-  return 1.0f / sqrtf((float)(Rk > 0 ? Rk : 1));
+  return TP_RS(Rk);
 }
-
-#define RTP_INV_S3 0.57735026918962576451f
-#define RTP_INV_S2 0.70710678118654752440f
 
 // row of U times rs (scalar blocks: u[0] alone)
 __device__ __forceinline__ void rtp_u(int kind, const float* i, float s0, float vx, float vy, float vz, float rs, float* u) {
@@ -130,8 +122,8 @@ __device__ __forceinline__ void rtp_u(int kind, const float* i, float s0, float 
   if (kind == RTP_SS) { u[0] = i[0] * s0; }
   else if (kind == RTP_SV) { u[0] = i[0] * vx; u[1] = i[0] * vy; u[2] = i[0] * vz; }
   else if (kind == RTP_VS) { u[0] = i[0] * s0; u[1] = i[1] * s0; u[2] = i[2] * s0; }
-  else if (kind == RTP_VX) { u[0] = (i[1] * vz - i[2] * vy) * RTP_INV_S2; u[1] = (i[2] * vx - i[0] * vz) * RTP_INV_S2; u[2] = (i[0] * vy - i[1] * vx) * RTP_INV_S2; }
-  else if (kind == RTP_VD) { u[0] = (i[0] * vx + i[1] * vy + i[2] * vz) * RTP_INV_S3; }
+  else if (kind == RTP_VX) { u[0] = (i[1] * vz - i[2] * vy) * TP_INV_S2; u[1] = (i[2] * vx - i[0] * vz) * TP_INV_S2; u[2] = (i[0] * vy - i[1] * vx) * TP_INV_S2; }
+  else if (kind == RTP_VD) { u[0] = (i[0] * vx + i[1] * vy + i[2] * vz) * TP_INV_S3; }
   u[0] *= rs; u[1] *= rs; u[2] *= rs;
 }
 
@@ -142,10 +134,10 @@ __device__ __forceinline__ void rtp_fold(const RtpRow& rk, const float* i, const
   else if (rk.kind == RTP_SV) { d0 = vx * G[0] + vy * G[1] + vz * G[2]; gs[1] += i[0] * G[0]; gs[2] += i[0] * G[1]; gs[3] += i[0] * G[2]; }
   else if (rk.kind == RTP_VS) { d0 = s0 * G[0]; d1 = s0 * G[1]; d2 = s0 * G[2]; gs[0] += i[0] * G[0] + i[1] * G[1] + i[2] * G[2]; }
   else if (rk.kind == RTP_VX) {
-    d0 = (vy * G[2] - vz * G[1]) * RTP_INV_S2; d1 = (vz * G[0] - vx * G[2]) * RTP_INV_S2; d2 = (vx * G[1] - vy * G[0]) * RTP_INV_S2;
-    gs[1] += (G[1] * i[2] - G[2] * i[1]) * RTP_INV_S2; gs[2] += (G[2] * i[0] - G[0] * i[2]) * RTP_INV_S2; gs[3] += (G[0] * i[1] - G[1] * i[0]) * RTP_INV_S2;
+    d0 = (vy * G[2] - vz * G[1]) * TP_INV_S2; d1 = (vz * G[0] - vx * G[2]) * TP_INV_S2; d2 = (vx * G[1] - vy * G[0]) * TP_INV_S2;
+    gs[1] += (G[1] * i[2] - G[2] * i[1]) * TP_INV_S2; gs[2] += (G[2] * i[0] - G[0] * i[2]) * TP_INV_S2; gs[3] += (G[0] * i[1] - G[1] * i[0]) * TP_INV_S2;
   } else if (rk.kind == RTP_VD) {
-    const float k3 = G[0] * RTP_INV_S3;
+    const float k3 = G[0] * TP_INV_S3;
     d0 = vx * k3; d1 = vy * k3; d2 = vz * k3;
     gs[1] += i[0] * k3; gs[2] += i[1] * k3; gs[3] += i[2] * k3;
   }
@@ -210,8 +202,8 @@ struct RtpEdge {
 
   template <int K>
   __device__ __forceinline__ void block() {
-    constexpr int Ok = TT::O(K), Rk = TT::R(K), NCG = TT::NCG(K), NRG = TT::NRG(K);
-    constexpr bool VEC = TT::vec(K);
+    constexpr int Ok = S::O(K), Rk = S::R(K), NCG = TT::NCG(K), NRG = TT::NRG(K);
+    constexpr bool VEC = S::vec(K);
     constexpr int NO = VEC ? 3 * Ok : Ok;      // floats of the block in an out / grad_out row
     const float rs = rtp_rs<S>(K);
     float o[FWD && NO > 0 ? NO : 1];
@@ -221,7 +213,7 @@ struct RtpEdge {
       for (int c = 0; c < NO; ++c) o[c] = 0.f;
     } else {
 #pragma unroll
-      for (int c = 0; c < NO; ++c) gr[c] = ev ? a.g[e * S::DOUT + TT::GOFF(K) + c] : 0.f;
+      for (int c = 0; c < NO; ++c) gr[c] = ev ? a.g[e * S::DOUT + S::OUT_OFF(K) + c] : 0.f;
     }
     for (int rg = 0; rg < NRG; ++rg) {
       // the lane's two rows of the tile
@@ -303,7 +295,7 @@ struct RtpEdge {
 #pragma unroll
       for (int c = 0; c < NO; ++c) {
         const float tot = o[c] + __shfl_xor(o[c], 32);
-        if (ev && (c & 1) == hh) a.out[e * S::DOUT + TT::GOFF(K) + c] = tot;
+        if (ev && (c & 1) == hh) a.out[e * S::DOUT + S::OUT_OFF(K) + c] = tot;
       }
     }
   }
@@ -360,9 +352,9 @@ struct RtpEdge {
     park();
     __syncthreads();
     block<0>();
-    if constexpr (TT::O(1) > 0) block<1>();
-    if constexpr (TT::O(2) > 0) block<2>();
-    if constexpr (TT::O(3) > 0) block<3>();
+    if constexpr (S::O(1) > 0) block<1>();
+    if constexpr (S::O(2) > 0) block<2>();
+    if constexpr (S::O(3) > 0) block<3>();
     if (NH && wave_on) {
       // D of GEMM 2: column = lane & 31 (hidden unit 32 n + j), row = edge (t & 3) + 8 (t >> 2) + 4 (lane >> 5) of the wave's 32
 #pragma unroll
@@ -435,9 +427,9 @@ __global__ __launch_bounds__(256) void rtp_param_kernel(RtpArgs a) {
   const int T = 4 * chunk + wave;
   const bool active = T < TT::NT;
   const RtpSlot sl = rtp_slot<S>(active ? T : 0, j);
-  const bool vec = sl.blk == 1 || sl.blk == 2;
+  const bool vec = S::vec(sl.blk);
   const RtpRow rk = (active && sl.valid) ? rtp_row<S>(sl.blk, sl.r) : RtpRow{RTP_NONE, 0, 0};
-  const int goff = (sl.blk == 0 ? TT::GOFF(0) : (sl.blk == 1 ? TT::GOFF(1) : (sl.blk == 2 ? TT::GOFF(2) : TT::GOFF(3)))) + (sl.valid ? (vec ? 3 * sl.c : sl.c) : 0);
+  const int goff = S::OUT_OFF(sl.blk) + (sl.valid ? (vec ? 3 * sl.c : sl.c) : 0);
   const int gstep = (vec && sl.valid) ? 1 : 0;
   const float rs = rtp_rs<S>(sl.blk);
   rtp_f16 acc[3];
@@ -553,58 +545,35 @@ static hipError_t rtp_launch(const RtpArgs& a, bool fwd, hipStream_t s) {
   return hipGetLastError();
 }
 
-static int rtp_shape_of(const ConvLayerDev& L) {
-  const int* im = L.in_mul;
-  const int* om = L.out_mul;
-  auto is = [&](int a0, int a1, int a2, int a3, int o0, int o1, int o2, int o3) {
-    return im[0] == a0 && im[1] == a1 && im[2] == a2 && im[3] == a3 && om[0] == o0 && om[1] == o1 && om[2] == o2 && om[3] == o3;
-  };
-  if (is(24, 6, 6, 24, 24, 6, 6, 24)) return 3;
-  if (is(24, 6, 6, 0, 24, 6, 6, 24)) return 2;
-  if (is(24, 6, 0, 0, 24, 6, 6, 0)) return 1;
-  if (is(24, 0, 0, 0, 24, 6, 0, 0)) return 0;
-  return -1;
-}
-
-static const int RTP_W[4] = {TpShape<24, 0, 0, 0, 24, 6, 0, 0>::W, TpShape<24, 6, 0, 0, 24, 6, 6, 0>::W, TpShape<24, 6, 6, 0, 24, 6, 6, 24>::W,
-                             TpShape<24, 6, 6, 24, 24, 6, 6, 24>::W};
-
 int64_t rtp_backward_workspace(int32_t layer, int64_t E, int32_t n_groups) {
   if (layer < 0 || layer > 4 || E < 0 || E >= (int64_t)1 << 31 || n_groups < 1 || n_groups > 4) return -1;
   const int64_t slices = E / rtp_slice_len(E) + n_groups;      // sum_g ceil(n_g / L) <= floor(E / L) + G
-  return slices * RTP_W[layer < 3 ? layer : 3] * RTP_IMG * (int64_t)sizeof(float);
+  return slices * TP_LAYER_W[layer < 3 ? layer : 3] * RTP_IMG * (int64_t)sizeof(float);
 }
 
-static hipError_t rtp_dispatch(const ConvLayerDev& L, const RtpArgs& a, bool fwd, hipStream_t s) {
-  switch (rtp_shape_of(L)) {
-    case 3: return rtp_launch<TpShape<24, 6, 6, 24, 24, 6, 6, 24>>(a, fwd, s);
-    case 2: return rtp_launch<TpShape<24, 6, 6, 0, 24, 6, 6, 24>>(a, fwd, s);
-    case 1: return rtp_launch<TpShape<24, 6, 0, 0, 24, 6, 6, 0>>(a, fwd, s);
-    case 0: return rtp_launch<TpShape<24, 0, 0, 0, 24, 6, 0, 0>>(a, fwd, s);
-  }
-  return hipErrorInvalidValue;      // not a FasterTensorProduct of this model family
+// what the forward and the backward both read: operands, group table, slice length
+static RtpArgs rtp_args(const float* x_dst, const float* sh, const float* h, const int64_t* group_offsets, int n_groups, const float* w2, const float* b2) {
+  RtpArgs a{};
+  a.x = x_dst; a.sh = sh; a.h = h; a.w2 = w2; a.b2 = b2;
+  for (int q = 0; q <= n_groups; ++q) a.off[q] = group_offsets[q];
+  a.n_groups = n_groups;
+  a.L = rtp_slice_len(group_offsets[n_groups]);
+  return a;
 }
 
 hipError_t launch_rtp_forward(const ConvLayerDev& L, const float* x_dst, const float* sh, const float* h, const int64_t* group_offsets, int n_groups,
                               const float* w2, const float* b2, float* out, hipStream_t s) {
-  RtpArgs a{};
-  a.x = x_dst; a.sh = sh; a.h = h; a.w2 = w2; a.b2 = b2; a.out = out;
-  for (int q = 0; q <= n_groups; ++q) a.off[q] = group_offsets[q];
-  a.n_groups = n_groups;
-  a.L = rtp_slice_len(group_offsets[n_groups]);
-  return rtp_dispatch(L, a, true, s);
+  RtpArgs a = rtp_args(x_dst, sh, h, group_offsets, n_groups, w2, b2);
+  a.out = out;
+  return tp_dispatch(L, [&](auto shape) { return rtp_launch<decltype(shape)>(a, true, s); });
 }
 
 hipError_t launch_rtp_backward(const ConvLayerDev& L, const float* x_dst, const float* sh, const float* h, const int64_t* group_offsets, int n_groups,
                                const float* w2, const float* b2, const float* grad_out, float* grad_x, float* grad_sh, float* grad_h, float* grad_w2,
                                float* grad_b2, float* workspace, hipStream_t s) {
-  RtpArgs a{};
-  a.x = x_dst; a.sh = sh; a.h = h; a.w2 = w2; a.b2 = b2; a.g = grad_out;
-  a.gx = grad_x; a.gsh = grad_sh; a.gh = grad_h; a.gw2 = grad_w2; a.gb2 = grad_b2; a.ws = workspace;
-  for (int q = 0; q <= n_groups; ++q) a.off[q] = group_offsets[q];
-  a.n_groups = n_groups;
-  a.L = rtp_slice_len(group_offsets[n_groups]);
-  return rtp_dispatch(L, a, false, s);
+  RtpArgs a = rtp_args(x_dst, sh, h, group_offsets, n_groups, w2, b2);
+  a.g = grad_out; a.gx = grad_x; a.gsh = grad_sh; a.gh = grad_h; a.gw2 = grad_w2; a.gb2 = grad_b2; a.ws = workspace;
+  return tp_dispatch(L, [&](auto shape) { return rtp_launch<decltype(shape)>(a, false, s); });
 }
 
 }  // namespace ddk

@@ -34,26 +34,17 @@ template <class S> struct TpRow { float4 w[S::NV]; float x0, x1; float4 sh; };
 
 template <class S>
 __device__ __forceinline__ void tpf_request(const TpFArgs& a, int64_t e, int lane, TpRow<S>& R) {
-  const float4* wr = reinterpret_cast<const float4*>(a.w + e * S::W);
-#pragma unroll
-  for (int t = 0; t < S::NV; ++t) {
-    const int f = 64 * t + lane;
-    if ((t + 1) * 64 <= S::W / 4 || f < S::W / 4) {
-      const tp_f4* pw = reinterpret_cast<const tp_f4*>(wr + f);
-      const tp_f4 q = *pw;      // (default cache policy: non-temporal loads measured 1-3 % slower on this stream)
-      R.w[t] = make_float4(q.x, q.y, q.z, q.w);
-    }
-  }
+  tp_read_row<S>(a.w + e * S::W, lane, R.w);
   const float* xr = a.x + e * S::DIN;
   R.x0 = lane < S::DIN ? xr[lane] : 0.f;
   R.x1 = lane + 64 < S::DIN ? xr[lane + 64] : 0.f;
   R.sh = *reinterpret_cast<const float4*>(a.sh + e * 4);
 }
 
-template <class S>
-__device__ __forceinline__ float tp_xval(float x0, float x1, int k) {      // x[k] of the node row as a wave-uniform value (k is a compile-time constant)
-  return tp_rl(k < 64 ? x0 : x1, k < 64 ? k : k - 64);
-}
+// Rows in flight per wave and waves per SIMD as measured on MI355X (profiles/r06_tp_boundary_kernel_stats.md): the W = 1872 row (8 16-B pieces per
+// lane) wants its registers (2 waves per SIMD requested, 3 fit), the shorter rows want the occupancy
+template <class S> constexpr int TP_COL_WPE = S::NV >= 8 ? 2 : 4;
+
 template <class S, int D, int WPE>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void tp_col_kernel(TpFArgs a) {
   __shared__ float4 Wst[S::NV * 64];
@@ -73,9 +64,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
   const int wB0 = onB ? 4 * (bbase + (blk == 2 ? 0 : S::A) * nout + col) : 0;
   const int wC0 = onC ? 4 * (bbase + (blk == 1 ? S::A + S::P : (blk == 2 ? S::P : 0)) * nout + col) : 0;
   const int nrow = blk == 0 ? S::R0 : (blk == 1 ? S::R1 : (blk == 2 ? S::R2 : (blk == 3 ? S::R3 : 1)));
-  const float rs = 1.0f / sqrtf((float)(nrow > 0 ? nrow : 1));                   // tensor_layers.py:89-92
+  const float rs = TP_RS(nrow);
   const int ooff = blk == 0 ? col : (blk == 1 ? S::O0 + 3 * col : (blk == 2 ? S::O0 + 3 * S::O1 + 3 * col : S::O0 + 3 * S::O1 + 3 * S::O2 + col));
-  const float inv_s3 = 0.57735026918962576451f, inv_s2 = 0.70710678118654752440f;
+  const float inv_s3 = TP_INV_S3, inv_s2 = TP_INV_S2;
   constexpr int NA = S::A > S::C ? S::A : S::C;
   // which component of v multiplies this lane's node-row value in the (p . v), (q . v) sums: lanes A .. A + 3P + 3Q - 1 of x0 hold p then q, xyz interleaved
   static_assert(S::A + 3 * S::P + 3 * S::Q <= 64 && NA % 2 == 0, "the vector inputs of the node row sit in the first 64 lanes");
@@ -116,8 +107,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
       for (int i = 0; i < HA; ++i) { wb[i] = *reinterpret_cast<const float*>(Wb + ad); ad += sA; asm volatile("" : "+v"(ad)); }
 #pragma unroll
       for (int i = 0; i < HA; ++i) {
-        if (i < S::A) accA = fmaf(tp_xval<S>(x0, x1, i), wa[i], accA);
-        if (i < S::C) accC = fmaf(tp_xval<S>(x0, x1, S::XC + i), wa[i], accC);
+        if (i < S::A) accA = fmaf(tp_row_val(x0, x1, i), wa[i], accA);
+        if (i < S::C) accC = fmaf(tp_row_val(x0, x1, S::XC + i), wa[i], accC);
       }
       __builtin_amdgcn_sched_barrier(0);
       ad = wB0;
@@ -130,23 +121,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
       for (int i = 0; i < S::Q; ++i) { wq[i] = *reinterpret_cast<const float*>(Wb + ad); ad += sC; asm volatile("" : "+v"(ad)); }
 #pragma unroll
       for (int i = 0; i < HA; ++i) {
-        if (HA + i < S::A) accA = fmaf(tp_xval<S>(x0, x1, HA + i), wb[i], accA);
-        if (HA + i < S::C) accC = fmaf(tp_xval<S>(x0, x1, S::XC + HA + i), wb[i], accC);
+        if (HA + i < S::A) accA = fmaf(tp_row_val(x0, x1, HA + i), wb[i], accA);
+        if (HA + i < S::C) accC = fmaf(tp_row_val(x0, x1, S::XC + HA + i), wb[i], accC);
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int i = 0; i < S::P; ++i) {
         bs = fmaf(tp_rl(pvq, S::A + 3 * i), wp[i], bs);
-        bx = fmaf(tp_xval<S>(x0, x1, S::A + 3 * i), wp[i], bx);
-        by = fmaf(tp_xval<S>(x0, x1, S::A + 3 * i + 1), wp[i], by);
-        bz = fmaf(tp_xval<S>(x0, x1, S::A + 3 * i + 2), wp[i], bz);
+        bx = fmaf(tp_row_val(x0, x1, S::A + 3 * i), wp[i], bx);
+        by = fmaf(tp_row_val(x0, x1, S::A + 3 * i + 1), wp[i], by);
+        bz = fmaf(tp_row_val(x0, x1, S::A + 3 * i + 2), wp[i], bz);
       }
 #pragma unroll
       for (int i = 0; i < S::Q; ++i) {
         cs = fmaf(tp_rl(pvq, S::A + 3 * S::P + 3 * i), wq[i], cs);
-        cx = fmaf(tp_xval<S>(x0, x1, S::A + 3 * S::P + 3 * i), wq[i], cx);
-        cy = fmaf(tp_xval<S>(x0, x1, S::A + 3 * S::P + 3 * i + 1), wq[i], cy);
-        cz = fmaf(tp_xval<S>(x0, x1, S::A + 3 * S::P + 3 * i + 2), wq[i], cz);
+        cx = fmaf(tp_row_val(x0, x1, S::A + 3 * S::P + 3 * i), wq[i], cx);
+        cy = fmaf(tp_row_val(x0, x1, S::A + 3 * S::P + 3 * i + 1), wq[i], cy);
+        cz = fmaf(tp_row_val(x0, x1, S::A + 3 * S::P + 3 * i + 2), wq[i], cz);
       }
       __builtin_amdgcn_sched_barrier(0);
       const float sa = onA ? (lowblk ? accA : accC) : 0.f;
@@ -176,23 +167,11 @@ hipError_t launch_tp_forward(const ConvLayerDev& L, const float* x_dst, const fl
                              float* out, hipStream_t s) {
   if (E == 0) return hipSuccess;
   const TpFArgs a{x_dst, sh, w, out, E};
-  // persistent waves, one per workgroup: 16 per CU cover the occupancy of every instantiation (3 .. 5 waves per SIMD), each with one row in hand and two in flight
-  const int64_t cap = 256 * 16;
-  const dim3 g((unsigned)(E < cap ? E : cap)), b(64);
-  const int* im = L.in_mul;
-  const int* om = L.out_mul;
-  auto is = [&](int a0, int a1, int a2, int a3, int o0, int o1, int o2, int o3) {
-    return im[0] == a0 && im[1] == a1 && im[2] == a2 && im[3] == a3 && om[0] == o0 && om[1] == o1 && om[2] == o2 && om[3] == o3;
-  };
-  // the conv layers of the score model (tensor_layers.py:12-27): in = 24x0e [+ 6x1o [+ 6x1e [+ 24x0o]]], out = the next entry of the sequence.  Rows in
-  // flight per wave and waves per SIMD as measured on MI355X (profiles/r06_tp_boundary_kernel_stats.md): the W = 1872 row wants its registers (2 waves
-  // per SIMD requested, 3 fit), the shorter rows want the occupancy
-  if (is(24, 6, 6, 24, 24, 6, 6, 24)) hipLaunchKernelGGL((tp_col_kernel<TpShape<24, 6, 6, 24, 24, 6, 6, 24>, 2, 2>), g, b, 0, s, a);
-  else if (is(24, 6, 6, 0, 24, 6, 6, 24)) hipLaunchKernelGGL((tp_col_kernel<TpShape<24, 6, 6, 0, 24, 6, 6, 24>, 2, 4>), g, b, 0, s, a);
-  else if (is(24, 6, 0, 0, 24, 6, 6, 0)) hipLaunchKernelGGL((tp_col_kernel<TpShape<24, 6, 0, 0, 24, 6, 6, 0>, 2, 4>), g, b, 0, s, a);
-  else if (is(24, 0, 0, 0, 24, 6, 0, 0)) hipLaunchKernelGGL((tp_col_kernel<TpShape<24, 0, 0, 0, 24, 6, 0, 0>, 2, 4>), g, b, 0, s, a);
-  else return hipErrorInvalidValue;      // not a FasterTensorProduct of this model family (ddk_create refuses other ns / nv)
-  return hipGetLastError();
+  return tp_dispatch(L, [&](auto shape) {
+    using S = decltype(shape);
+    hipLaunchKernelGGL((tp_col_kernel<S, 2, TP_COL_WPE<S>>), tp_persistent_grid(E), dim3(64), 0, s, a);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace ddk

@@ -59,17 +59,7 @@ struct TpbLane {
 
 template <class S, bool NW, bool NX>
 __device__ __forceinline__ void tpb_request(const TpBArgs& a, int64_t e, int lane, const TpbLane<S>& ln, TpbRow<S, NX>& R) {
-  if (NX) {
-    const float4* wr = reinterpret_cast<const float4*>(a.w + e * S::W);
-#pragma unroll
-    for (int t = 0; t < S::NV; ++t) {
-      const int f = 64 * t + lane;
-      if ((t + 1) * 64 <= S::W / 4 || f < S::W / 4) {
-        const tp_f4 q = *reinterpret_cast<const tp_f4*>(wr + f);
-        R.w[t] = make_float4(q.x, q.y, q.z, q.w);
-      }
-    }
-  }
+  if (NX) tp_read_row<S>(a.w + e * S::W, lane, R.w);
   const float* xr = a.x + e * S::DIN;
 #pragma unroll
   for (int k = 0; k < 3; ++k) R.xi[k] = ln.role < 4 ? xr[ln.xoff + k * ln.xstep] : 0.f;      // a scalar input three times over
@@ -82,11 +72,6 @@ __device__ __forceinline__ void tpb_request(const TpBArgs& a, int64_t e, int lan
 #pragma unroll
     for (int k = 0; k < 3; ++k) R.gc[k] = lane < S::O1 + S::O2 ? gr[S::O0 + 3 * lane + k] : 0.f;      // vector column `lane` of g
   }
-}
-
-template <class S>
-__device__ __forceinline__ float tpb_gval(float g0, float g1, int k) {      // g[k] as a wave-uniform value (k is a compile-time constant)
-  return tp_rl(k < 64 ? g0 : g1, k < 64 ? k : k - 64);
 }
 
 template <class S, int D, bool NW, bool NX>
@@ -104,9 +89,8 @@ __global__ __launch_bounds__(64) void tp_bwd_kernel(TpBArgs a) {
   int64_t e = blockIdx.x;
   const TpbLane<S> ln(lane);
   const int role = ln.role;
-  const float inv_s3 = 0.57735026918962576451f, inv_s2 = 0.70710678118654752440f;
-  const float rs0 = 1.0f / sqrtf((float)(S::R0 > 0 ? S::R0 : 1)), rs1 = 1.0f / sqrtf((float)(S::R1 > 0 ? S::R1 : 1));      // tensor_layers.py:89-92
-  const float rs2 = 1.0f / sqrtf((float)(S::R2 > 0 ? S::R2 : 1)), rs3 = 1.0f / sqrtf((float)(S::R3 > 0 ? S::R3 : 1));
+  const float inv_s3 = TP_INV_S3, inv_s2 = TP_INV_S2;
+  const float rs0 = TP_RS(S::R0), rs1 = TP_RS(S::R1), rs2 = TP_RS(S::R2), rs3 = TP_RS(S::R3);
   const float rss = lane < S::R0 ? rs0 : rs3;      // the lane's row of TS belongs to block 0e or 0o
 
   // grad_w: (row address) | (column address) << 16 of the lane's 4 NV elements, and which of its 16-B pieces lie in a vector block
@@ -219,8 +203,8 @@ __global__ __launch_bounds__(64) void tp_bwd_kernel(TpBArgs a) {
           for (int c2 = 0; c2 < S::O1 / 2; ++c2) {
             const float2 wv = *reinterpret_cast<const float2*>(sm + w1 + 8 * c2);
             const int k0 = S::O0 + 6 * c2;
-            ax = fmaf(wv.x, tpb_gval<S>(g0, g1, k0), ax); ay = fmaf(wv.x, tpb_gval<S>(g0, g1, k0 + 1), ay); az = fmaf(wv.x, tpb_gval<S>(g0, g1, k0 + 2), az);
-            ax = fmaf(wv.y, tpb_gval<S>(g0, g1, k0 + 3), ax); ay = fmaf(wv.y, tpb_gval<S>(g0, g1, k0 + 4), ay); az = fmaf(wv.y, tpb_gval<S>(g0, g1, k0 + 5), az);
+            ax = fmaf(wv.x, tp_row_val(g0, g1, k0), ax); ay = fmaf(wv.x, tp_row_val(g0, g1, k0 + 1), ay); az = fmaf(wv.x, tp_row_val(g0, g1, k0 + 2), az);
+            ax = fmaf(wv.y, tp_row_val(g0, g1, k0 + 3), ax); ay = fmaf(wv.y, tp_row_val(g0, g1, k0 + 4), ay); az = fmaf(wv.y, tp_row_val(g0, g1, k0 + 5), az);
           }
           if (on1) { G1x = ax * rs1; G1y = ay * rs1; G1z = az * rs1; }
         }
@@ -230,8 +214,8 @@ __global__ __launch_bounds__(64) void tp_bwd_kernel(TpBArgs a) {
           for (int c2 = 0; c2 < S::O2 / 2; ++c2) {
             const float2 wv = *reinterpret_cast<const float2*>(sm + w2 + 8 * c2);
             const int k0 = S::O0 + 3 * S::O1 + 6 * c2;
-            ax = fmaf(wv.x, tpb_gval<S>(g0, g1, k0), ax); ay = fmaf(wv.x, tpb_gval<S>(g0, g1, k0 + 1), ay); az = fmaf(wv.x, tpb_gval<S>(g0, g1, k0 + 2), az);
-            ax = fmaf(wv.y, tpb_gval<S>(g0, g1, k0 + 3), ax); ay = fmaf(wv.y, tpb_gval<S>(g0, g1, k0 + 4), ay); az = fmaf(wv.y, tpb_gval<S>(g0, g1, k0 + 5), az);
+            ax = fmaf(wv.x, tp_row_val(g0, g1, k0), ax); ay = fmaf(wv.x, tp_row_val(g0, g1, k0 + 1), ay); az = fmaf(wv.x, tp_row_val(g0, g1, k0 + 2), az);
+            ax = fmaf(wv.y, tp_row_val(g0, g1, k0 + 3), ax); ay = fmaf(wv.y, tp_row_val(g0, g1, k0 + 4), ay); az = fmaf(wv.y, tp_row_val(g0, g1, k0 + 5), az);
           }
           if (on2) { G2x = ax * rs2; G2y = ay * rs2; G2z = az * rs2; }
         }
@@ -285,34 +269,20 @@ __global__ __launch_bounds__(64) void tp_bwd_kernel(TpBArgs a) {
   }
 }
 
-template <class S>
-static hipError_t tpb_launch(const TpBArgs& a, hipStream_t s) {
-  // persistent waves, one per workgroup, as many as the forward's: each with one edge in hand and two in flight
-  const int64_t cap = 256 * 16;
-  const dim3 g((unsigned)(a.E < cap ? a.E : cap)), b(64);
-  const bool nw = a.gw != nullptr, nx = a.gx != nullptr || a.gsh != nullptr;
-  if (nw && nx) hipLaunchKernelGGL((tp_bwd_kernel<S, 2, true, true>), g, b, 0, s, a);
-  else if (nw) hipLaunchKernelGGL((tp_bwd_kernel<S, 2, true, false>), g, b, 0, s, a);
-  else if (nx) hipLaunchKernelGGL((tp_bwd_kernel<S, 2, false, true>), g, b, 0, s, a);
-  else return hipErrorInvalidValue;
-  return hipGetLastError();
-}
-
 hipError_t launch_tp_backward(const ConvLayerDev& L, const float* x_dst, const float* sh, const float* w, const float* grad_out, int64_t E,
                               float* grad_x, float* grad_sh, float* grad_w, hipStream_t s) {
   if (E == 0) return hipSuccess;
-  const int* im = L.in_mul;
-  const int* om = L.out_mul;
-  auto is = [&](int a0, int a1, int a2, int a3, int o0, int o1, int o2, int o3) {
-    return im[0] == a0 && im[1] == a1 && im[2] == a2 && im[3] == a3 && om[0] == o0 && om[1] == o1 && om[2] == o2 && om[3] == o3;
-  };
   const TpBArgs a{x_dst, sh, w, grad_out, grad_x, grad_sh, grad_w, E};
-  // the same four shapes as launch_tp_forward
-  if (is(24, 6, 6, 24, 24, 6, 6, 24)) return tpb_launch<TpShape<24, 6, 6, 24, 24, 6, 6, 24>>(a, s);
-  if (is(24, 6, 6, 0, 24, 6, 6, 24)) return tpb_launch<TpShape<24, 6, 6, 0, 24, 6, 6, 24>>(a, s);
-  if (is(24, 6, 0, 0, 24, 6, 6, 0)) return tpb_launch<TpShape<24, 6, 0, 0, 24, 6, 6, 0>>(a, s);
-  if (is(24, 0, 0, 0, 24, 6, 0, 0)) return tpb_launch<TpShape<24, 0, 0, 0, 24, 6, 0, 0>>(a, s);
-  return hipErrorInvalidValue;      // not a FasterTensorProduct of this model family (ddk_create refuses other ns / nv)
+  const bool nw = grad_w != nullptr, nx = grad_x != nullptr || grad_sh != nullptr;
+  if (!nw && !nx) return hipErrorInvalidValue;
+  return tp_dispatch(L, [&](auto shape) {
+    using S = decltype(shape);
+    const dim3 g = tp_persistent_grid(E), b(64);      // as many waves as the forward's
+    if (nw && nx) hipLaunchKernelGGL((tp_bwd_kernel<S, 2, true, true>), g, b, 0, s, a);
+    else if (nw) hipLaunchKernelGGL((tp_bwd_kernel<S, 2, true, false>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((tp_bwd_kernel<S, 2, false, true>), g, b, 0, s, a);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace ddk

@@ -140,6 +140,17 @@ def h2d_async(t, device):
     return d
 
 
+def tp_layer_shape(layer, ns=24, nv=6):
+    """The FasterTensorProduct of conv layer ``layer`` (get_irrep_seq and FasterTensorProduct.__init__, tensor_layers.py:12-27, 56-63; the table of
+    csrc/k_tp_shape.h): input multiplicities A, P, Q, C of 0e, 1o, 1e, 0o, output multiplicities O, the weight blocks' rows R (0 where the block has no
+    columns) and offsets B in the weight row of W floats, the widths din and dout of a node row.  Layers 3 and later share a shape."""
+    seq = [(ns, 0, 0, 0), (ns, nv, 0, 0), (ns, nv, nv, 0), (ns, nv, nv, ns)]
+    (A, P, Q, C), O = seq[min(layer, 3)], seq[min(layer + 1, 3)]
+    R = [r if o else 0 for r, o in zip((A + P, A + P + Q, P + Q + C, Q + C), O)]
+    B = [sum(r * o for r, o in zip(R[:k], O)) for k in range(5)]
+    return dict(A=A, P=P, Q=Q, C=C, O=O, R=R, B=B, W=B[4], din=A + 3 * P + 3 * Q + C, dout=O[0] + 3 * O[1] + 3 * O[2] + O[3])
+
+
 def _need_cuda(t):
     if not t.is_cuda:
         raise RuntimeError('ddk: device tensors only (no CPU path exists); got a tensor on ' + str(t.device))
@@ -363,10 +374,7 @@ class Context:
 
     def tp_weight_numel(self, layer):
         """W of conv layer ``layer``: the length of a FasterTensorProduct weight row (tensor_layers.py:56-63)."""
-        ns, nv = self.cfg.ns, self.cfg.nv
-        i, o = [(ns, 0, 0, 0), (ns, nv, 0, 0), (ns, nv, nv, 0), (ns, nv, nv, ns)][min(layer, 3)], [(ns, nv, 0, 0), (ns, nv, nv, 0), (ns, nv, nv, ns)][min(layer, 2)]
-        rows = (i[0] + i[1], i[0] + i[1] + i[2], i[1] + i[2] + i[3], i[2] + i[3])
-        return sum(r * c for r, c in zip(rows, o))
+        return tp_layer_shape(layer, self.cfg.ns, self.cfg.nv)['W']
 
     def conv_forward(self, layer, x, edge_src, edge_dst, group_offsets, edge_attr, sh, dout):
         x, edge_attr, sh = x.contiguous().float(), edge_attr.contiguous().float(), sh.contiguous().float()

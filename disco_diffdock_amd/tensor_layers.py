@@ -18,7 +18,7 @@ import torch
 from torch import nn
 from torch.autograd.function import once_differentiable
 
-from .runtime import Context
+from .runtime import Context, tp_layer_shape
 
 _ORDER = ('0e', '1o', '1e', '0o')
 _DIM = {'0e': 1, '1o': 3, '1e': 3, '0o': 1}
@@ -49,10 +49,10 @@ def irrep_to_size(irreps):
 
 def layer_index(in_irreps, out_irreps, ns=24, nv=6):
     """Which conv layer of the score model has these irreps (get_irrep_seq, tensor_layers.py:12-27)."""
-    seq = [dict(zip(_ORDER, m)) for m in ((ns, 0, 0, 0), (ns, nv, 0, 0), (ns, nv, nv, 0), (ns, nv, nv, ns))]
-    i, o = parse_irreps(in_irreps), parse_irreps(out_irreps)
+    i, o = tuple(parse_irreps(in_irreps).values()), tuple(parse_irreps(out_irreps).values())
     for l in range(4):
-        if seq[min(l, 3)] == i and seq[min(l + 1, 3)] == o:
+        s = tp_layer_shape(l, ns, nv)
+        if (s['A'], s['P'], s['Q'], s['C']) == i and s['O'] == o:
             return l
     raise RuntimeError(f'ddk: no fused kernel for irreps {in_irreps} -> {out_irreps} (ns={ns}, nv={nv})')
 
@@ -67,6 +67,11 @@ def _shape_context(device_index):
         ctx.finalize()
         _shape_ctx[device_index] = ctx
     return _shape_ctx[device_index]
+
+
+def _grads_like(grads, meta):
+    """each gradient in the shape and dtype of its input (meta: their (shape, dtype)); None stays None"""
+    return tuple(None if g is None else g.reshape(shape).to(dtype) for g, (shape, dtype) in zip(grads, meta))
 
 
 def _as_rows(t, cols):
@@ -96,8 +101,7 @@ class _FasterTPFunction(torch.autograd.Function):
         g = grad_out.reshape(-1, grad_out.shape[-1]).contiguous().float()
         with torch.cuda.device(x.device):
             grads = fctx.ddk.tp_backward(fctx.layer, x, s, w, g, need)
-        grads = [None if gr is None else gr.reshape(shape).to(dtype) for gr, (shape, dtype) in zip(grads, fctx.meta)]
-        return grads[0], grads[1], grads[2], None, None, None
+        return _grads_like(grads, fctx.meta) + (None, None, None)
 
 
 class FasterTensorProduct(nn.Module):
@@ -106,12 +110,10 @@ class FasterTensorProduct(nn.Module):
         if parse_irreps(sh_irreps) != {'0e': 1, '1o': 1, '1e': 0, '0o': 0}:
             raise AssertionError("sh_irreps don't look like 1st order spherical harmonics")
         self.in_irreps, self.out_irreps = str(in_irreps), str(out_irreps)
-        i, o = parse_irreps(in_irreps), parse_irreps(out_irreps)
-        self.weight_shapes = {'0e': (i['0e'] + i['1o'], o['0e']), '1o': (i['0e'] + i['1o'] + i['1e'], o['1o']),
-                              '1e': (i['1o'] + i['1e'] + i['0o'], o['1e']), '0o': (i['1e'] + i['0o'], o['0o'])}
-        self.weight_numel = sum(a * b for a, b in self.weight_shapes.values())
         self.layer = layer_index(in_irreps, out_irreps)
-        self.out_size = irrep_to_size(out_irreps)
+        s = tp_layer_shape(self.layer)
+        self.weight_shapes = dict(zip(_ORDER, zip(s['R'], s['O'])))      # (every block of these layers that has rows has columns)
+        self.weight_numel, self.out_size = s['W'], s['dout']
 
     def forward(self, in_, sh, weight):
         if not in_.is_cuda:
@@ -149,8 +151,7 @@ class _RadialTPFunction(torch.autograd.Function):
         g = grad_out.reshape(-1, grad_out.shape[-1]).contiguous().float()
         with torch.cuda.device(x.device):
             grads = fctx.ddk.rtp_backward(fctx.layer, x, s, hh, fctx.offsets, w, b, g, need)
-        grads = [None if gr is None else gr.reshape(shape).to(dtype) for gr, (shape, dtype) in zip(grads, fctx.meta)]
-        return grads[0], grads[1], grads[2], grads[3], grads[4], None, None, None
+        return _grads_like(grads, fctx.meta) + (None, None, None)
 
 
 def fused_radial_tp(tp, fc, x_dst, edge_sh, edge_attr):

@@ -19,7 +19,7 @@ from test_gpu_round3 import _record_drift      # the suite's record of measured 
 pytestmark = pytest.mark.gpu
 CFG = smr.ScoreModelConfig()
 BAR = 1e-5
-GRID = 4096      # the kernel's persistent grid (csrc/k_tp_bwd.hip tpb_launch)
+GRID = 4096      # the kernel's persistent grid (csrc/k_tp_shape.h tp_persistent_grid)
 
 
 @pytest.fixture(scope='module')

@@ -60,3 +60,16 @@ def test_host_only_context_refuses_backward(built):
     with pytest.raises(RuntimeError, match='at least one gradient'):
         ctx.tp_backward(3, None, None, None, None, need=(False, False, False))
     assert [ctx.tp_weight_numel(l) for l in range(5)] == [ref.shape(l)['W'] for l in range(5)]
+
+
+@pytest.mark.parametrize('l', range(5))
+def test_one_shape_table(built, l):
+    """the package's statement of a layer's shape (runtime.tp_layer_shape), this suite's (tp_backward_ref.shape) and the kernels' (csrc/k_tp_shape.h,
+    read through the workspace size of one slice of one group: W rows of 72 + 1 floats) are the same table"""
+    from disco_diffdock_amd import _lib
+    from disco_diffdock_amd.runtime import tp_layer_shape
+    got, want = tp_layer_shape(l), ref.shape(l)
+    assert sorted(got) == sorted(want)
+    for k in want:
+        assert got[k] == want[k], k
+    assert _lib.lib().ddk_rtp_backward_workspace(l, 0, 1) == want['W'] * 73 * 4
