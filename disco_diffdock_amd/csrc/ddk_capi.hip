@@ -300,6 +300,61 @@ int ddk_rtp_backward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const floa
 
 int64_t ddk_rtp_backward_workspace(int32_t layer, int64_t E, int32_t n_groups) { return rtp_backward_workspace(layer, E, n_groups); }
 
+// the checks the two radial-conv entries share on top of rtp_check: node counts, and with edges the graph tables and the per-edge operands
+static int rconv_check(ddk_ctx* ctx, const char* who, int32_t layer, const int64_t* go, int32_t n_groups, int64_t E, const RconvGraph& gr, bool backward,
+                       const float* x_nodes, const float* sh, const float* h, const void* workspace) {
+  int rc = rtp_check(ctx, who, layer, go, n_groups, E);
+  if (rc) return rc;
+  const std::string w(who);
+  const int64_t lim = (int64_t)1 << 31;
+  if (gr.n_in < 0 || gr.n_in >= lim || gr.n_out < 0 || gr.n_out >= lim) return fail(ctx, DDK_ERR_INVALID, w + ": node count out of range");
+  if (E == 0) return DDK_OK;
+  if (gr.n_in == 0 || gr.n_out == 0) return fail(ctx, DDK_ERR_INVALID, w + ": edges without nodes");
+  if (!gr.src || !gr.dst || !gr.src_order || !gr.src_ptr || (backward && (!gr.dst_order || !gr.dst_ptr)))
+    return fail(ctx, DDK_ERR_INVALID, w + ": null graph table (edge_src, edge_dst, the orderings and their pointer tables)");
+  if (!x_nodes || !sh || !h) return fail(ctx, DDK_ERR_INVALID, w + ": null operand");
+  if (!workspace) return fail(ctx, DDK_ERR_INVALID, w + ": null workspace (ddk_rconv_workspace bytes)");
+  return DDK_OK;
+}
+
+int ddk_rconv_forward(ddk_ctx* ctx, int32_t layer, const float* x_nodes, int64_t n_in, int64_t n_out, const int32_t* edge_src, const int32_t* edge_dst,
+                      const int32_t* src_order, const int64_t* src_ptr, const float* sh, const float* h, const int64_t* group_offsets, int32_t n_groups,
+                      const float* w2, const float* b2, int64_t E, float* out_nodes, void* workspace, void* stream) {
+  const RconvGraph gr{n_in, n_out, edge_src, edge_dst, src_order, src_ptr, nullptr, nullptr};
+  int rc = rconv_check(ctx, "ddk_rconv_forward", layer, group_offsets, n_groups, E, gr, false, x_nodes, sh, h, workspace);
+  if (rc) return rc;
+  if (n_out > 0 && !out_nodes) return fail(ctx, DDK_ERR_INVALID, "ddk_rconv_forward: null out_nodes");
+  if (E > 0 && (!w2 || !b2)) return fail(ctx, DDK_ERR_INVALID, "ddk_rconv_forward: null w2 or b2");
+  hipError_t e = launch_rconv_forward(ctx->conv[layer], gr, x_nodes, sh, h, group_offsets, n_groups, w2, b2, out_nodes, (float*)workspace, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "rconv_forward launch");
+  return DDK_OK;
+}
+
+int ddk_rconv_backward(ddk_ctx* ctx, int32_t layer, const float* x_nodes, int64_t n_in, int64_t n_out, const int32_t* edge_src, const int32_t* edge_dst,
+                       const int32_t* src_order, const int64_t* src_ptr, const int32_t* dst_order, const int64_t* dst_ptr, const float* sh, const float* h,
+                       const int64_t* group_offsets, int32_t n_groups, const float* w2, const float* b2, const float* grad_out_nodes, int64_t E,
+                       float* grad_x_nodes, float* grad_sh, float* grad_h, float* grad_w2, float* grad_b2, void* workspace, void* stream) {
+  const RconvGraph gr{n_in, n_out, edge_src, edge_dst, src_order, src_ptr, dst_order, dst_ptr};
+  int rc = rconv_check(ctx, "ddk_rconv_backward", layer, group_offsets, n_groups, E, gr, true, x_nodes, sh, h, workspace);
+  if (rc) return rc;
+  if (!grad_x_nodes && !grad_sh && !grad_h && !grad_w2 && !grad_b2)
+    return fail(ctx, DDK_ERR_INVALID, "ddk_rconv_backward: no gradient requested (grad_x_nodes, grad_sh, grad_h, grad_w2 and grad_b2 are all null)");
+  if (E > 0) {
+    if (!grad_out_nodes) return fail(ctx, DDK_ERR_INVALID, "ddk_rconv_backward: null grad_out_nodes");
+    if ((grad_x_nodes || grad_sh || grad_h) && !w2)
+      return fail(ctx, DDK_ERR_INVALID, "ddk_rconv_backward: null w2 (it may be null only when grad_x_nodes, grad_sh and grad_h are all null)");
+    if ((grad_x_nodes || grad_sh) && !b2) return fail(ctx, DDK_ERR_INVALID, "ddk_rconv_backward: null b2 (grad_x_nodes and grad_sh need w = w2 h + b2)");
+  }
+  hipError_t e = launch_rconv_backward(ctx->conv[layer], gr, x_nodes, sh, h, group_offsets, n_groups, w2, b2, grad_out_nodes, grad_x_nodes, grad_sh, grad_h,
+                                       grad_w2, grad_b2, (float*)workspace, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "rconv_backward launch");
+  return DDK_OK;
+}
+
+int64_t ddk_rconv_workspace(int32_t layer, int64_t E, int32_t n_groups, int64_t n_in, int64_t n_out, int32_t backward) {
+  return rconv_workspace(layer, E, n_groups, n_in, n_out, backward);
+}
+
 int ddk_conv_forward(ddk_ctx* ctx, int32_t layer, const float* x, int64_t N, const int32_t* edge_src,
                      const int32_t* edge_dst, const int64_t* go, const float* edge_attr, const float* sh, float* out,
                      void* stream) {

@@ -336,4 +336,16 @@ hipError_t launch_rtp_backward(const ConvLayerDev& L, const float* x_dst, const 
                                const float* w2, const float* b2, const float* grad_out, float* grad_x, float* grad_sh, float* grad_h, float* grad_w2,
                                float* grad_b2, float* workspace, hipStream_t s);
 int64_t rtp_backward_workspace(int32_t layer, int64_t E, int32_t n_groups);
+// k_rtp.hip: the radial conv, node rows to aggregated node rows (include/ddk.h: ddk_rconv_forward / ddk_rconv_backward).  The graph of a call: trusted device
+// tables, dst_order / dst_ptr read by the backward alone
+struct RconvGraph {
+  int64_t n_in, n_out;
+  const int32_t* src; const int32_t* dst; const int32_t* src_order; const int64_t* src_ptr; const int32_t* dst_order; const int64_t* dst_ptr;
+};
+hipError_t launch_rconv_forward(const ConvLayerDev& L, const RconvGraph& gr, const float* x_nodes, const float* sh, const float* h, const int64_t* group_offsets,
+                                int n_groups, const float* w2, const float* b2, float* out_nodes, float* workspace, hipStream_t s);
+hipError_t launch_rconv_backward(const ConvLayerDev& L, const RconvGraph& gr, const float* x_nodes, const float* sh, const float* h, const int64_t* group_offsets,
+                                 int n_groups, const float* w2, const float* b2, const float* grad_out_nodes, float* grad_x_nodes, float* grad_sh, float* grad_h,
+                                 float* grad_w2, float* grad_b2, float* workspace, hipStream_t s);
+int64_t rconv_workspace(int32_t layer, int64_t E, int32_t n_groups, int64_t n_in, int64_t n_out, int32_t backward);
 }  // namespace ddk

@@ -28,6 +28,13 @@
 // column 72, against ones, is grad_b2.  Each workgroup stores its partial image [W][73] with plain stores; the second kernel adds the slices of a group in
 // slice order.  The slice length depends on E alone (rtp_slice_len: 512 edges, longer once E > 122 880 so that there are never more than 240 + G slices:
 // at most 133 MB of workspace for W = 1872), so the bits do not depend on the device.
+//
+// THE RADIAL CONV (launch_rconv_forward / launch_rconv_backward: node rows to aggregated node rows, lines 153-159 of TensorProductConvLayer.forward).  The same
+// two kernels instantiated on RtpIdx<shape>: x and g are node tables, the lane (edge kernel) or the staging loop (parameter kernel) reads row xi[e] = edge_dst[e]
+// of x and row gi[e] = edge_src[e] of g; sh, h and all output rows stay per edge.  Around them rtp_seg_kernel adds a node's rows in ascending edge id from a
+// node-sorted edge list, one thread per (node, column): the scatter-mean of the forward ([E, Dout] rows over src) and the backward of the gather ([E, Din]
+// rows of grad_x over dst); rtp_node_scale_kernel makes gn = grad_out / max(count, 1) once per node, so that the backward gathers plain rows.  No atomics
+// here either.  The indices, orderings and pointer tables are trusted: Context.conv_graph (Python) builds and range-checks them.
 #include <stdlib.h>
 
 #include "ddk_internal.h"
@@ -48,6 +55,7 @@ struct RtpArgs {
   int64_t off[5];
   int n_groups;
   int64_t L;      // edges per slice (pass 3)
+  const int32_t* xi; const int32_t* gi;      // the indexed kernels (the radial conv): edge e reads row xi[e] of x and row gi[e] of g
 };
 
 __host__ __device__ inline int64_t rtp_slice_len(int64_t E) {
@@ -148,9 +156,19 @@ __device__ __forceinline__ void rtp_fold(const RtpRow& rk, const float* i, const
 }
 
 // ---- forward and backward pass 2 ---------------------------------------------------------------------------------------------------------------------------
+// The compile-time flag IDX of the edge and parameter kernels, carried by the shape type so that the kernels of the plain shapes keep their symbols and
+// their code: with S = RtpIdx<shape>, x and g are NODE tables and edge e reads rows a.xi[e] / a.gi[e] of them (the radial conv); sh, h and every output row
+// stay per edge
+template <class S> struct RtpIdx : S {};
+template <class S> struct RtpIsIdx { static constexpr bool value = false; };
+template <class S> struct RtpIsIdx<RtpIdx<S>> { static constexpr bool value = true; };
+template <class S> struct RtpPlain { using type = S; };      // the shape itself (rtp_reduce_kernel reads no x or g: one instantiation per shape)
+template <class S> struct RtpPlain<RtpIdx<S>> { using type = S; };
+
 template <class S, bool FWD, bool NX, bool NH>
 struct RtpEdge {
   using TT = RtpT<S>;
+  static constexpr bool IDX = RtpIsIdx<S>::value;
   static constexpr bool G1 = FWD || NX;      // GEMM 1 (w_tile) runs
 
   const RtpArgs& a;
@@ -158,6 +176,7 @@ struct RtpEdge {
   const float* w2g; const float* b2g;
   int tid, lane, j, hh;
   int64_t e; bool ev, wave_on;
+  int64_t ex, eg;      // IDX: the lane's rows of x and g
   float hreg[G1 ? 36 : 1];
   float s0, vx, vy, vz;
   rtp_f16 accH[NH ? 3 : 1];
@@ -166,6 +185,8 @@ struct RtpEdge {
   int T;
 
   __device__ __forceinline__ RtpEdge(const RtpArgs& a_) : a(a_) {}
+  __device__ __forceinline__ int64_t xrow() const { if constexpr (IDX) return ex; else return e; }
+  __device__ __forceinline__ int64_t grow() const { if constexpr (IDX) return eg; else return e; }
 
   __device__ __forceinline__ void fetch(int Tn) {      // global -> registers
 #pragma unroll
@@ -213,7 +234,7 @@ struct RtpEdge {
       for (int c = 0; c < NO; ++c) o[c] = 0.f;
     } else {
 #pragma unroll
-      for (int c = 0; c < NO; ++c) gr[c] = ev ? a.g[e * S::DOUT + S::OUT_OFF(K) + c] : 0.f;
+      for (int c = 0; c < NO; ++c) gr[c] = ev ? a.g[grow() * S::DOUT + S::OUT_OFF(K) + c] : 0.f;
     }
     for (int rg = 0; rg < NRG; ++rg) {
       // the lane's two rows of the tile
@@ -224,7 +245,7 @@ struct RtpEdge {
         const int r = 4 * rg + hh + 2 * m;
         rk[m] = r < Rk ? rtp_row<S>(K, r) : RtpRow{RTP_NONE, 0, 0};
 #pragma unroll
-        for (int k = 0; k < 3; ++k) in[m][k] = (ev && rk[m].kind != RTP_NONE) ? a.x[e * S::DIN + rk[m].xoff + k * rk[m].xstep] : 0.f;
+        for (int k = 0; k < 3; ++k) in[m][k] = (ev && rk[m].kind != RTP_NONE) ? a.x[xrow() * S::DIN + rk[m].xoff + k * rk[m].xstep] : 0.f;
         if constexpr (FWD || NH) rtp_u(rk[m].kind, in[m], s0, vx, vy, vz, rs, u[m]);
         G[m][0] = 0.f; G[m][1] = 0.f; G[m][2] = 0.f;
       }
@@ -335,6 +356,13 @@ struct RtpEdge {
       const tp_f4 v = *reinterpret_cast<const tp_f4*>(a.sh + e * 4);
       s0 = v.x; vx = v.y; vy = v.z; vz = v.w;
     }
+    if constexpr (IDX) {
+      ex = 0; eg = 0;
+      if (ev) {
+        ex = a.xi[e];
+        if (!FWD) eg = a.gi[e];
+      }
+    }
     gs[0] = 0.f; gs[1] = 0.f; gs[2] = 0.f; gs[3] = 0.f;
     float* img = gx_img + wave * (S::DIN * 32);
     gxl = img + j;
@@ -404,6 +432,7 @@ __global__ __launch_bounds__(256) void rtp_edge_kernel(RtpArgs a) {
 template <class S>
 __global__ __launch_bounds__(256) void rtp_param_kernel(RtpArgs a) {
   using TT = RtpT<S>;
+  constexpr bool IDX = RtpIsIdx<S>::value;
   constexpr int NCH = (TT::NT + 3) / 4;
   __shared__ float xs[32 * S::DIN];
   __shared__ float gsm[32 * S::DOUT];
@@ -437,11 +466,40 @@ __global__ __launch_bounds__(256) void rtp_param_kernel(RtpArgs a) {
   for (int n = 0; n < 3; ++n)
 #pragma unroll
     for (int t = 0; t < 16; ++t) acc[n][t] = 0.f;
+  // IDX: the rows of x (entries 0..31) and g (32..63) of the 32 staged edges, loaded one step ahead into two alternating LDS buffers, so that the staging
+  // loops below issue one global load per element, as without the index
+  [[maybe_unused]] int* idx_s = nullptr;
+  [[maybe_unused]] int step = 0;
+  if constexpr (IDX) {
+    __shared__ int idx_buf[128];
+    idx_s = idx_buf;
+    if (tid < 64) {
+      const int64_t en = es + (tid & 31);
+      idx_s[tid] = en < ee ? (tid < 32 ? a.xi[en] : a.gi[en]) : 0;
+    }
+  }
   for (int64_t eb = es; eb < ee; eb += 32) {
     const int n_e = ee - eb < 32 ? (int)(ee - eb) : 32;
     __syncthreads();
-    for (int f = tid; f < 32 * S::DIN; f += 256) xs[f] = f < n_e * S::DIN ? a.x[eb * S::DIN + f] : 0.f;
-    for (int f = tid; f < 32 * S::DOUT; f += 256) gsm[f] = f < n_e * S::DOUT ? a.g[eb * S::DOUT + f] : 0.f;
+    if constexpr (IDX) {      // row f / DIN of the 32 staged edges comes from the node table
+      const int* cur = idx_s + 64 * (step & 1);
+      for (int f = tid; f < 32 * S::DIN; f += 256) {
+        const int r = f / S::DIN;
+        xs[f] = r < n_e ? a.x[(int64_t)cur[r] * S::DIN + (f - r * S::DIN)] : 0.f;
+      }
+      for (int f = tid; f < 32 * S::DOUT; f += 256) {
+        const int r = f / S::DOUT;
+        gsm[f] = r < n_e ? a.g[(int64_t)cur[32 + r] * S::DOUT + (f - r * S::DOUT)] : 0.f;
+      }
+      ++step;
+      if (tid < 64) {      // the next step's rows, visible after the barrier below; the buffer they go to was last read before the barrier above
+        const int64_t en = eb + 32 + (tid & 31);
+        idx_s[64 * (step & 1) + tid] = en < ee ? (tid < 32 ? a.xi[en] : a.gi[en]) : 0;
+      }
+    } else {
+      for (int f = tid; f < 32 * S::DIN; f += 256) xs[f] = f < n_e * S::DIN ? a.x[eb * S::DIN + f] : 0.f;
+      for (int f = tid; f < 32 * S::DOUT; f += 256) gsm[f] = f < n_e * S::DOUT ? a.g[eb * S::DOUT + f] : 0.f;
+    }
     for (int f = tid; f < 32 * RTP_H; f += 256) hs[f] = f < n_e * RTP_H ? a.h[eb * RTP_H + f] : 0.f;
     if (tid < 128) shs[tid] = tid < n_e * 4 ? a.sh[eb * 4 + tid] : 0.f;
     __syncthreads();
@@ -506,6 +564,39 @@ __global__ __launch_bounds__(256) void rtp_reduce_kernel(RtpArgs a) {
   }
 }
 
+// ---- the radial conv's node side: a fixed-order segmented sum, and the scaled node gradient ----------------------------------------------------------------
+// nodes[n, :] = rows[order[ptr[n]], :] + rows[order[ptr[n] + 1], :] + ... added in that order, one thread per (node, column), columns along lanes (a row is
+// read as one coalesced piece, order[k] is the same address for the lanes of a node); MEAN: divided by max(ptr[n + 1] - ptr[n], 1), a true division as
+// torch_scatter's.  A node without edges: exact zeros.  Plain stores, no atomics: the bits do not depend on the run or the device.
+template <bool MEAN>
+__global__ __launch_bounds__(256) void rtp_seg_kernel(const float* __restrict__ rows, const int32_t* __restrict__ order, const int64_t* __restrict__ ptr,
+                                                      float* __restrict__ nodes, int64_t N, int D) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= N * D) return;
+  const int64_t n = idx / D;
+  const int c = (int)(idx - n * D);
+  const int64_t k0 = ptr[n], k1 = ptr[n + 1];
+  float sum = 0.f;
+  int64_t k = k0;
+  if (k < k1) sum = rows[(int64_t)order[k++] * D + c];      // (not 0 + row: a -0 stays what it is)
+  for (; k + 4 <= k1; k += 4) {      // four loads in flight, added in order
+    const float v0 = rows[(int64_t)order[k] * D + c], v1 = rows[(int64_t)order[k + 1] * D + c];
+    const float v2 = rows[(int64_t)order[k + 2] * D + c], v3 = rows[(int64_t)order[k + 3] * D + c];
+    sum += v0; sum += v1; sum += v2; sum += v3;
+  }
+  for (; k < k1; ++k) sum += rows[(int64_t)order[k] * D + c];
+  if (MEAN) sum = sum / (float)(k1 - k0 > 1 ? k1 - k0 : 1);
+  nodes[idx] = sum;
+}
+
+// gn[n, :] = g[n, :] / max(ptr[n + 1] - ptr[n], 1): the backward of the mean, once per node, so that the indexed kernels gather plain rows
+__global__ __launch_bounds__(256) void rtp_node_scale_kernel(const float* __restrict__ g, const int64_t* __restrict__ ptr, float* __restrict__ gn, int64_t N, int D) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= N * D) return;
+  const int64_t n = idx / D, cnt = ptr[n + 1] - ptr[n];
+  gn[idx] = g[idx] / (float)(cnt > 1 ? cnt : 1);
+}
+
 // ---- host ----------------------------------------------------------------------------------------------------------------------------------------------------
 static int64_t rtp_units(const RtpArgs& a, int64_t per) {      // sum over the groups of ceil(n / per)
   int64_t n = 0;
@@ -513,7 +604,7 @@ static int64_t rtp_units(const RtpArgs& a, int64_t per) {      // sum over the g
   return n;
 }
 
-template <class S>
+template <class S>      // S: a shape, or RtpIdx<shape>
 static hipError_t rtp_launch(const RtpArgs& a, bool fwd, hipStream_t s) {
   const int64_t E = a.off[a.n_groups];
   const int64_t nwg = rtp_units(a, RTP_EPB);
@@ -540,7 +631,7 @@ static hipError_t rtp_launch(const RtpArgs& a, bool fwd, hipStream_t s) {
       if (e != hipSuccess) return e;
     }
     const int64_t n = (int64_t)S::W * RTP_IMG * a.n_groups;
-    hipLaunchKernelGGL((rtp_reduce_kernel<S>), dim3((unsigned)((n + 255) / 256)), b, 0, s, a);
+    hipLaunchKernelGGL((rtp_reduce_kernel<typename RtpPlain<S>::type>), dim3((unsigned)((n + 255) / 256)), b, 0, s, a);
   }
   return hipGetLastError();
 }
@@ -574,6 +665,78 @@ hipError_t launch_rtp_backward(const ConvLayerDev& L, const float* x_dst, const 
   RtpArgs a = rtp_args(x_dst, sh, h, group_offsets, n_groups, w2, b2);
   a.g = grad_out; a.gx = grad_x; a.gsh = grad_sh; a.gh = grad_h; a.gw2 = grad_w2; a.gb2 = grad_b2; a.ws = workspace;
   return tp_dispatch(L, [&](auto shape) { return rtp_launch<decltype(shape)>(a, false, s); });
+}
+
+// ---- the radial conv ---------------------------------------------------------------------------------------------------------------------------------------------
+static int64_t rconv_pad(int64_t n) { return (n + 3) / 4 * 4; }      // floats of a workspace part: the next part starts on 16 bytes
+
+int64_t rconv_workspace(int32_t layer, int64_t E, int32_t n_groups, int64_t n_in, int64_t n_out, int32_t backward) {
+  const int64_t lim = (int64_t)1 << 31;
+  if (layer < 0 || layer > 4 || E < 0 || E >= lim || n_groups < 1 || n_groups > 4 || n_in < 0 || n_in >= lim || n_out < 0 || n_out >= lim) return -1;
+  const int l = layer < 3 ? layer : 3;
+  int din = 0, dout = 0;
+  switch (l) {
+    case 0: din = TpLayerShape<0>::DIN; dout = TpLayerShape<0>::DOUT; break;
+    case 1: din = TpLayerShape<1>::DIN; dout = TpLayerShape<1>::DOUT; break;
+    case 2: din = TpLayerShape<2>::DIN; dout = TpLayerShape<2>::DOUT; break;
+    default: din = TpLayerShape<3>::DIN; dout = TpLayerShape<3>::DOUT; break;
+  }
+  if (!backward) return rconv_pad(E * dout) * (int64_t)sizeof(float);      // the tensor product's rows
+  // gn [n_out, Dout], the per-edge rows of grad_x [E, Din], the parameter images
+  return (rconv_pad(n_out * dout) + rconv_pad(E * din)) * (int64_t)sizeof(float) + rtp_backward_workspace(layer, E, n_groups);
+}
+
+template <bool MEAN>
+static hipError_t rtp_seg_launch(const float* rows, const int32_t* order, const int64_t* ptr, float* nodes, int64_t N, int D, hipStream_t s) {
+  const int64_t nb = (N * D + 255) / 256;      // N < 2^31 and D <= 128: fewer than 2^31 workgroups
+  if (nb > 0) hipLaunchKernelGGL((rtp_seg_kernel<MEAN>), dim3((unsigned)nb), dim3(256), 0, s, rows, order, ptr, nodes, N, D);
+  return hipGetLastError();
+}
+
+static hipError_t rconv_zero(float* p, int64_t n, hipStream_t s) {
+  return (p && n > 0) ? hipMemsetAsync(p, 0, (size_t)n * sizeof(float), s) : hipSuccess;
+}
+
+hipError_t launch_rconv_forward(const ConvLayerDev& L, const RconvGraph& gr, const float* x_nodes, const float* sh, const float* h, const int64_t* group_offsets,
+                                int n_groups, const float* w2, const float* b2, float* out_nodes, float* workspace, hipStream_t s) {
+  return tp_dispatch(L, [&](auto shape) {
+    using S = decltype(shape);
+    if (group_offsets[n_groups] == 0) return rconv_zero(out_nodes, gr.n_out * S::DOUT, s);
+    RtpArgs a = rtp_args(x_nodes, sh, h, group_offsets, n_groups, w2, b2);
+    a.xi = gr.dst;
+    a.out = workspace;
+    hipError_t e = rtp_launch<RtpIdx<S>>(a, true, s);
+    if (e != hipSuccess) return e;
+    return rtp_seg_launch<true>(workspace, gr.src_order, gr.src_ptr, out_nodes, gr.n_out, S::DOUT, s);
+  });
+}
+
+hipError_t launch_rconv_backward(const ConvLayerDev& L, const RconvGraph& gr, const float* x_nodes, const float* sh, const float* h, const int64_t* group_offsets,
+                                 int n_groups, const float* w2, const float* b2, const float* grad_out_nodes, float* grad_x_nodes, float* grad_sh, float* grad_h,
+                                 float* grad_w2, float* grad_b2, float* workspace, hipStream_t s) {
+  return tp_dispatch(L, [&](auto shape) {
+    using S = decltype(shape);
+    const int64_t E = group_offsets[n_groups];
+    if (E == 0) {
+      hipError_t e = rconv_zero(grad_x_nodes, gr.n_in * S::DIN, s);
+      if (e == hipSuccess) e = rconv_zero(grad_w2, (int64_t)n_groups * S::W * RTP_H, s);
+      if (e == hipSuccess) e = rconv_zero(grad_b2, (int64_t)n_groups * S::W, s);
+      return e;
+    }
+    float* gn = workspace;
+    float* gx_rows = gn + rconv_pad(gr.n_out * S::DOUT);
+    float* images = gx_rows + rconv_pad(E * S::DIN);
+    const int64_t nb = (gr.n_out * S::DOUT + 255) / 256;
+    hipLaunchKernelGGL(rtp_node_scale_kernel, dim3((unsigned)nb), dim3(256), 0, s, grad_out_nodes, gr.src_ptr, gn, gr.n_out, (int)S::DOUT);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    RtpArgs a = rtp_args(x_nodes, sh, h, group_offsets, n_groups, w2, b2);
+    a.xi = gr.dst; a.gi = gr.src; a.g = gn;
+    a.gx = grad_x_nodes ? gx_rows : nullptr; a.gsh = grad_sh; a.gh = grad_h; a.gw2 = grad_w2; a.gb2 = grad_b2; a.ws = images;
+    e = rtp_launch<RtpIdx<S>>(a, false, s);
+    if (e != hipSuccess || !grad_x_nodes) return e;
+    return rtp_seg_launch<false>(gx_rows, gr.dst_order, gr.dst_ptr, grad_x_nodes, gr.n_in, S::DIN, s);
+  });
 }
 
 }  // namespace ddk

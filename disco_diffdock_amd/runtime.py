@@ -151,6 +151,18 @@ def tp_layer_shape(layer, ns=24, nv=6):
     return dict(A=A, P=P, Q=Q, C=C, O=O, R=R, B=B, W=B[4], din=A + 3 * P + 3 * Q + C, dout=O[0] + 3 * O[1] + 3 * O[2] + O[3])
 
 
+class ConvGraph:
+    """The graph of the radial conv, made and checked by ``Context.conv_graph``: ``src`` / ``dst`` int32 [E]; ``src_order`` / ``dst_order`` int32 [E], the
+    edge ids sorted by node, ascending within a node; ``src_ptr`` [n_out + 1] / ``dst_ptr`` [n_in + 1] int64, node n owns order[ptr[n] : ptr[n + 1]];
+    ``src_count`` [n_out] / ``dst_count`` [n_in] int64, the edges per node.  The kernels trust these tables."""
+    __slots__ = ('src', 'dst', 'src_order', 'dst_order', 'src_ptr', 'dst_ptr', 'src_count', 'dst_count', 'n_in', 'n_out', 'E')
+
+    def __init__(self, src, dst, src_order, dst_order, src_ptr, dst_ptr, src_count, dst_count, n_in, n_out):
+        self.src, self.dst, self.src_order, self.dst_order = src, dst, src_order, dst_order
+        self.src_ptr, self.dst_ptr, self.src_count, self.dst_count = src_ptr, dst_ptr, src_count, dst_count
+        self.n_in, self.n_out, self.E = n_in, n_out, src.shape[0]
+
+
 def _need_cuda(t):
     if not t.is_cuda:
         raise RuntimeError('ddk: device tensors only (no CPU path exists); got a tensor on ' + str(t.device))
@@ -313,11 +325,12 @@ class Context:
                     'ddk_tp_backward')
         return gx, gsh, gw
 
-    def _rtp_operands(self, layer, x_dst, sh, h, group_offsets, w2, b2):
-        """checked operands of the radial tensor product: (x, sh, h, offsets as a ctypes int64 array, G, w2, b2, E, W)"""
+    def _rtp_operands(self, layer, x_dst, sh, h, group_offsets, w2, b2, E=None):
+        """checked operands of the radial tensor product: (x, sh, h, offsets as a ctypes int64 array, G, w2, b2, E, W).  E: the rows of x_dst, unless
+        given (the radial conv, whose x is a node table)"""
         x_dst, sh, h = (_need_cuda(t).contiguous().float() for t in (x_dst, sh, h))
         offs = [int(o) for o in group_offsets]
-        G, E, W = len(offs) - 1, x_dst.shape[0], self.tp_weight_numel(layer)
+        G, E, W = len(offs) - 1, x_dst.shape[0] if E is None else E, self.tp_weight_numel(layer)
         if not 1 <= G <= 4:
             raise RuntimeError(f'ddk: the radial tensor product takes 1..4 edge groups; got {G}')
         if sh.shape != (E, 4) or h.shape != (E, 72):
@@ -371,6 +384,99 @@ class Context:
         self._check(self.L.ddk_rtp_backward(self.h, layer, _ptr(x_dst), _ptr(sh), _ptr(h), offs, G, _ptr(w2), _ptr(b2), _ptr(grad_out), E,
                                             *[_ptr(o) for o in outs], _ptr(ws), _stream()), 'ddk_rtp_backward')
         return tuple(outs)      # (ws goes back to torch's allocator, which orders its reuse after this launch on the current stream)
+
+    # ---- the radial conv: node features to aggregated node features ---------------------------------
+    @staticmethod
+    def conv_graph(edge_src, edge_dst, n_in, n_out):
+        """The checked graph of ``rconv_forward`` / ``rconv_backward`` (a ``ConvGraph``), built once per graph with torch ops on the device of the
+        indices (CPU tensors work too): messages go from node ``edge_dst[e]`` of the ``n_in`` input nodes to node ``edge_src[e]`` of the ``n_out``
+        output nodes (edge_index rows 0 / 1 of the reference).  One read-back, of the extremes of the indices; an index outside its range or
+        E >= 2^31 raises."""
+        src, dst = torch.as_tensor(edge_src).reshape(-1), torch.as_tensor(edge_dst).reshape(-1)
+        n_in, n_out, E = int(n_in), int(n_out), src.shape[0]
+        if dst.shape[0] != E or dst.device != src.device or src.is_floating_point() or dst.is_floating_point():
+            raise RuntimeError('ddk: conv_graph takes two integer index vectors of one length on one device')
+        if E >= 1 << 31 or not (0 <= n_in < 1 << 31 and 0 <= n_out < 1 << 31):
+            raise RuntimeError(f'ddk: conv_graph: E = {E}, n_in = {n_in}, n_out = {n_out}: each must be below 2^31')
+        src, dst = src.long(), dst.long()
+        if E > 0:
+            lo_s, hi_s, lo_d, hi_d = torch.stack([src.min(), src.max(), dst.min(), dst.max()]).tolist()
+            if lo_s < 0 or hi_s >= n_out or lo_d < 0 or hi_d >= n_in:
+                raise RuntimeError(f'ddk: conv_graph: edge_src must be in [0, {n_out}) and edge_dst in [0, {n_in}); got [{lo_s}, {hi_s}] and [{lo_d}, {hi_d}]')
+
+        def table(idx, n):      # the edge ids sorted by node (stable: ascending edge id within a node), the node's range in them, its edge count
+            order = torch.sort(idx, stable=True).indices.to(torch.int32)
+            count = torch.bincount(idx, minlength=n)[:n]
+            ptr = torch.zeros(n + 1, dtype=torch.int64, device=idx.device)
+            ptr[1:] = torch.cumsum(count, 0)
+            return order.contiguous(), ptr, count
+
+        src_order, src_ptr, src_count = table(src, n_out)
+        dst_order, dst_ptr, dst_count = table(dst, n_in)
+        return ConvGraph(src.to(torch.int32).contiguous(), dst.to(torch.int32).contiguous(), src_order, dst_order, src_ptr, dst_ptr, src_count, dst_count,
+                         n_in, n_out)
+
+    def _rconv_operands(self, layer, graph, x_nodes, sh, h, group_offsets, w2, b2):
+        """checked operands of the radial conv: those of ``_rtp_operands`` with x a node table [n_in, Din] and E the graph's"""
+        if not isinstance(graph, ConvGraph):
+            raise RuntimeError('ddk: the radial conv takes a ConvGraph (Context.conv_graph): its kernels trust the indices')
+        ops = self._rtp_operands(layer, x_nodes, sh, h, group_offsets, w2, b2, E=graph.E)
+        x_nodes = ops[0]
+        if x_nodes.dim() != 2 or x_nodes.shape != (graph.n_in, tp_layer_shape(layer, self.cfg.ns, self.cfg.nv)['din']):
+            raise RuntimeError(f'ddk: the radial conv takes x_nodes [n_in, Din] for a graph of {graph.n_in} input nodes; got {tuple(x_nodes.shape)}')
+        if graph.src.device != x_nodes.device:
+            raise RuntimeError('ddk: the radial conv takes a ConvGraph on the device of its operands')
+        if ops[3][ops[4]] != graph.E:
+            raise RuntimeError(f'ddk: the edge groups hold {ops[3][ops[4]]} edges, the graph {graph.E}')
+        return ops
+
+    def rconv_forward(self, layer, graph, x_nodes, sh, h, group_offsets, w2, b2):
+        """The radial conv (ddk_rconv_forward): out_nodes [n_out, Dout] = scatter-mean over ``graph.src`` of FasterTensorProduct(x_nodes[graph.dst], sh,
+        w2[g] h + b2[g]); neither the per-edge weights nor the gathered rows are stored, the mean is a fixed-order sum (no atomics).  The workspace
+        (the tensor product's rows) comes from torch's allocator and is released on return."""
+        x_nodes, sh, h, offs, G, w2, b2, E, W = self._rconv_operands(layer, graph, x_nodes, sh, h, group_offsets, w2, b2)
+        if w2 is None or b2 is None:
+            raise RuntimeError('ddk: rconv_forward needs w2 and b2')
+        dout = tp_layer_shape(layer, self.cfg.ns, self.cfg.nv)['dout']
+        out = torch.empty((graph.n_out, dout), dtype=torch.float32, device=x_nodes.device)
+        ws = self._rconv_workspace(layer, graph, G, False, x_nodes.device)
+        g = graph
+        self._check(self.L.ddk_rconv_forward(self.h, layer, _ptr(x_nodes), g.n_in, g.n_out, _ptr(g.src), _ptr(g.dst), _ptr(g.src_order), _ptr(g.src_ptr),
+                                             _ptr(sh), _ptr(h), offs, G, _ptr(w2), _ptr(b2), E, _ptr(out), _ptr(ws), _stream()), 'ddk_rconv_forward')
+        return out
+
+    def rconv_backward(self, layer, graph, x_nodes, sh, h, group_offsets, w2, b2, grad_out_nodes, need=(True, True, True, True, True)):
+        """The vector-Jacobian product of ``rconv_forward`` (ddk_rconv_backward): (grad_x_nodes [n_in, Din], grad_sh, grad_h, grad_w2, grad_b2), None
+        where ``need`` is false; ``w2`` / ``b2`` may be None as in ``rtp_backward``.  The same bits from call to call.  The workspace comes from torch's
+        allocator and is released on return."""
+        need = tuple(bool(n) for n in need)
+        if not any(need):
+            raise RuntimeError('ddk: rconv_backward needs at least one gradient to compute')
+        if w2 is None and any(need[:3]):
+            raise RuntimeError('ddk: rconv_backward needs w2 for grad_x_nodes, grad_sh and grad_h')
+        if b2 is None and any(need[:2]):
+            raise RuntimeError('ddk: rconv_backward needs b2 for grad_x_nodes and grad_sh')
+        x_nodes, sh, h, offs, G, w2, b2, E, W = self._rconv_operands(layer, graph, x_nodes, sh, h, group_offsets, w2, b2)
+        g = graph
+        grad_out_nodes = _need_cuda(grad_out_nodes).contiguous().float()
+        if grad_out_nodes.dim() != 2 or grad_out_nodes.shape[0] != g.n_out:
+            raise RuntimeError('ddk: rconv_backward takes grad_out_nodes [n_out, Dout]')
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x_nodes.device)
+        outs = [new(g.n_in, x_nodes.shape[1]) if need[0] else None, new(E, 4) if need[1] else None, new(E, 72) if need[2] else None,
+                new(G, W, 72) if need[3] else None, new(G, W) if need[4] else None]
+        if not any(o is not None and o.numel() for o in outs):      # (empty tensors have no address: the entry would see no output at all)
+            return tuple(outs)
+        ws = self._rconv_workspace(layer, graph, G, True, x_nodes.device)
+        self._check(self.L.ddk_rconv_backward(self.h, layer, _ptr(x_nodes), g.n_in, g.n_out, _ptr(g.src), _ptr(g.dst), _ptr(g.src_order), _ptr(g.src_ptr),
+                                              _ptr(g.dst_order), _ptr(g.dst_ptr), _ptr(sh), _ptr(h), offs, G, _ptr(w2), _ptr(b2), _ptr(grad_out_nodes), E,
+                                              *[_ptr(o) for o in outs], _ptr(ws), _stream()), 'ddk_rconv_backward')
+        return tuple(outs)      # (ws goes back to torch's allocator, which orders its reuse after these launches on the current stream)
+
+    def _rconv_workspace(self, layer, graph, G, backward, device):
+        nbytes = self.L.ddk_rconv_workspace(layer, graph.E, G, graph.n_in, graph.n_out, int(backward))
+        if nbytes < 0:
+            raise RuntimeError(f'ddk: no radial-conv workspace for layer {layer}, E = {graph.E}, {G} groups, {graph.n_in} -> {graph.n_out} nodes')
+        return torch.empty(max(int(nbytes), 4) // 4, dtype=torch.float32, device=device)
 
     def tp_weight_numel(self, layer):
         """W of conv layer ``layer``: the length of a FasterTensorProduct weight row (tensor_layers.py:56-63)."""

@@ -8,9 +8,17 @@ parity tests read like tests of the reference modules:
 * ``GaussianSmearing``                                                                   tensor_layers.py:171-181
 * ``fused_radial_tp(tp, fc, x_dst, edge_sh, edge_attr)``: the radial MLP's last Linear, the cat and the tensor product
   of tensor_layers.py:154-156 as one differentiable op that never stores the per-edge weights (training)
+* ``fused_radial_conv(tp, fc, node_attr, edge_index, edge_sh, edge_attr, out_nodes=None, graph=None)``: lines 153-159, from the
+  node features to the scatter-mean, as one differentiable op: the gather inside the kernels, the mean a fixed-order sum,
+  no atomics (the same gradient bits on every run)
 
 Only the configuration the shipped score models use is implemented on the device (ns=24, nv=6, sh_lmax=1,
-faster=True, edge_groups=4, residual=True, 2-layer ReLU radial MLP, eval mode); anything else raises.
+faster=True, edge_groups=4, residual=True, 2-layer ReLU radial MLP); anything else raises.
+
+``TensorProductConvLayer`` trains: in ``.train()`` its forward is ``fused_radial_conv``, e3nn's BatchNorm on the batch
+statistics (plain torch, ``_BatchNormParams.forward``) and the padded residual.  In ``.eval()`` it is the fused inference
+kernel (``ddk_conv_forward``), unchanged.  What still does not train: ``ddk_score_forward`` end to end, the all-atom /
+confidence irreps, any other ns / nv.
 """
 import math
 
@@ -154,35 +162,93 @@ class _RadialTPFunction(torch.autograd.Function):
         return _grads_like(grads, fctx.meta) + (None, None, None)
 
 
+def _radial_operands(who, tp, fc, x, edge_attr):
+    """What fused_radial_tp and fused_radial_conv share: the checks on ``tp`` and ``fc``, then ``fc[i][0..3]`` in torch.  Returns the group offsets, the
+    hidden activation [E, 72] and the last Linears stacked, w2 [G, W, 72] and b2 [G, W]."""
+    if not isinstance(tp, FasterTensorProduct):
+        raise RuntimeError(f'ddk: {who} takes a FasterTensorProduct')
+    if not x.is_cuda:
+        raise RuntimeError(f'ddk {who} runs on the GPU only (no CPU fallback)')
+    if isinstance(fc, nn.Sequential):
+        fc, edge_attr = [fc], ([edge_attr] if torch.is_tensor(edge_attr) else list(edge_attr))
+    fc, edge_attr = list(fc), list(edge_attr)
+    if len(fc) != len(edge_attr) or not 1 <= len(fc) <= 4:
+        raise RuntimeError(f'ddk: {who} takes one edge_attr tensor per FCBlock, 1..4 of them')
+    for blk in fc:
+        if len(blk) != 5 or not isinstance(blk[4], nn.Linear) or blk[4].in_features != 72 or blk[4].out_features != tp.weight_numel or blk[4].bias is None:
+            raise RuntimeError(f'ddk: {who} takes 2-layer FCBlocks whose last Linear maps 72 -> weight_numel')
+    offs = [0]
+    for ea in edge_attr:
+        offs.append(offs[-1] + ea.shape[0])
+    hidden = torch.cat([blk[:4](ea) for blk, ea in zip(fc, edge_attr)], dim=0) if len(fc) > 1 else fc[0][:4](edge_attr[0])
+    w2, b2 = torch.stack([blk[4].weight for blk in fc]), torch.stack([blk[4].bias for blk in fc])
+    return offs, hidden, w2, b2
+
+
 def fused_radial_tp(tp, fc, x_dst, edge_sh, edge_attr):
     """``tp(x_dst, edge_sh, torch.cat([fc[i](edge_attr[i]) for i in range(G)]))`` of the reference's TensorProductConvLayer.forward
     (models/tensor_layers.py:154-156) without the per-edge weights: ``fc[i][0..3]`` run in torch, the last Linear of every group runs inside the tensor
     product's kernels, forward and backward.  ``tp``: a FasterTensorProduct; ``fc``: the layer's ModuleList of FCBlocks, or one FCBlock (edge_groups == 1);
     ``edge_attr``: the per-group list (a tensor for one FCBlock).  Every parameter of ``fc``, ``x_dst``, ``edge_sh`` and ``edge_attr`` receive the gradients
     the unfused composition gives them."""
-    if not isinstance(tp, FasterTensorProduct):
-        raise RuntimeError('ddk: fused_radial_tp takes a FasterTensorProduct')
-    if not x_dst.is_cuda:
-        raise RuntimeError('ddk fused_radial_tp runs on the GPU only (no CPU fallback)')
-    if isinstance(fc, nn.Sequential):
-        fc, edge_attr = [fc], ([edge_attr] if torch.is_tensor(edge_attr) else list(edge_attr))
-    fc, edge_attr = list(fc), list(edge_attr)
-    if len(fc) != len(edge_attr) or not 1 <= len(fc) <= 4:
-        raise RuntimeError('ddk: fused_radial_tp takes one edge_attr tensor per FCBlock, 1..4 of them')
-    for blk in fc:
-        if len(blk) != 5 or not isinstance(blk[4], nn.Linear) or blk[4].in_features != 72 or blk[4].out_features != tp.weight_numel or blk[4].bias is None:
-            raise RuntimeError('ddk: fused_radial_tp takes 2-layer FCBlocks whose last Linear maps 72 -> weight_numel')
-    offs = [0]
-    for ea in edge_attr:
-        offs.append(offs[-1] + ea.shape[0])
-    hidden = torch.cat([blk[:4](ea) for blk, ea in zip(fc, edge_attr)], dim=0) if len(fc) > 1 else fc[0][:4](edge_attr[0])
-    w2, b2 = torch.stack([blk[4].weight for blk in fc]), torch.stack([blk[4].bias for blk in fc])
+    offs, hidden, w2, b2 = _radial_operands('fused_radial_tp', tp, fc, x_dst, edge_attr)
     if x_dst.dim() != 2 or x_dst.shape[0] != offs[-1]:
         raise RuntimeError('ddk: fused_radial_tp takes x_dst [E, Din] with E the total of the edge groups')
     if torch.is_grad_enabled() and any(t.requires_grad for t in (x_dst, edge_sh, hidden, w2, b2)):
         return _RadialTPFunction.apply(x_dst, edge_sh, hidden, w2, b2, tp.layer, tuple(offs), tp.out_size)
     ctx = _shape_context(x_dst.device.index or 0)
     return ctx.rtp_forward(tp.layer, x_dst, edge_sh.reshape(-1, 4), hidden, offs, w2, b2, tp.out_size)
+
+
+class _RadialConvFunction(torch.autograd.Function):
+    """ddk_rconv_forward with ddk_rconv_backward as its vector-Jacobian product: node features to aggregated node features.  Saved for the backward: the
+    node table, sh, h, the graph, and w2 / b2 where a requested gradient reads them; never the gathered rows [E, Din], the tensor product's rows [E, Dout]
+    or the per-edge weights.  No atomics: the gradients have the same bits on every run."""
+
+    @staticmethod
+    def forward(fctx, node_attr, sh, h, w2, b2, layer, offsets, graph):
+        ctx = _shape_context(node_attr.device.index or 0)
+        x, s, hh = _as_rows(node_attr, node_attr.shape[-1]), _as_rows(sh, 4), _as_rows(h, h.shape[-1])
+        w, b = w2.contiguous().float(), b2.contiguous().float()
+        out = ctx.rconv_forward(layer, graph, x, s, hh, offsets, w, b)
+        ng = fctx.needs_input_grad
+        fctx.save_for_backward(x, s, hh, w if any(ng[:3]) else None, b if any(ng[:2]) else None)      # the parameter gradients read neither
+        fctx.layer, fctx.ddk, fctx.offsets, fctx.graph = layer, ctx, tuple(offsets), graph
+        fctx.meta = [(t.shape, t.dtype) for t in (node_attr, sh, h, w2, b2)]
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(fctx, grad_out):
+        x, s, hh, w, b = fctx.saved_tensors
+        need = tuple(fctx.needs_input_grad[:5])
+        g = grad_out.reshape(-1, grad_out.shape[-1]).contiguous().float()
+        with torch.cuda.device(x.device):
+            grads = fctx.ddk.rconv_backward(fctx.layer, fctx.graph, x, s, hh, fctx.offsets, w, b, g, need)
+        return _grads_like(grads, fctx.meta) + (None, None, None)
+
+
+def fused_radial_conv(tp, fc, node_attr, edge_index, edge_sh, edge_attr, out_nodes=None, graph=None):
+    """Lines 153-159 of the reference's TensorProductConvLayer.forward with reduce='mean' (models/tensor_layers.py) as one differentiable op:
+    ``scatter(tp(node_attr[edge_dst], edge_sh, torch.cat([fc[i](edge_attr[i]) ...])), edge_src, dim_size=out_nodes, reduce='mean')``.  ``fc[i][0..3]``
+    (Dropout included) run in torch; the last Linear, the gather, the tensor product and the mean run in the kernels of the radial tensor product and a
+    fixed-order segmented sum, forward and backward: no [E, W] weights, no gathered rows, no atomics, so the gradients of ``node_attr``, ``edge_sh``,
+    ``edge_attr`` and every parameter of ``fc`` have the same bits on every run.  ``graph``: a ``runtime.ConvGraph`` made once for this
+    ``edge_index`` (``Context.conv_graph(edge_index[0], edge_index[1], n_in=node_attr.shape[0], n_out=out_nodes)``); built here otherwise, which
+    costs two sorts and one read-back per call.  [out_nodes or N, Dout], fp32."""
+    offs, hidden, w2, b2 = _radial_operands('fused_radial_conv', tp, fc, node_attr, edge_attr)
+    if node_attr.dim() != 2:
+        raise RuntimeError('ddk: fused_radial_conv takes node_attr [N, Din]')
+    n_out = out_nodes or node_attr.shape[0]
+    if graph is None:
+        graph = Context.conv_graph(edge_index[0], edge_index[1], node_attr.shape[0], n_out)
+    if graph.n_in != node_attr.shape[0] or graph.n_out != n_out or graph.E != offs[-1]:
+        raise RuntimeError(f'ddk: fused_radial_conv: the graph ({graph.n_in} -> {graph.n_out} nodes, {graph.E} edges) does not fit '
+                           f'{node_attr.shape[0]} -> {n_out} nodes and {offs[-1]} edges in the groups')
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (node_attr, edge_sh, hidden, w2, b2)):
+        return _RadialConvFunction.apply(node_attr, edge_sh, hidden, w2, b2, tp.layer, tuple(offs), graph)
+    ctx = _shape_context(node_attr.device.index or 0)
+    return ctx.rconv_forward(tp.layer, graph, node_attr, edge_sh.reshape(-1, 4), hidden, offs, w2, b2)
 
 
 def FCBlock(in_dim, hidden_dim, out_dim, layers, dropout, activation='relu', batchnorm=False):
@@ -203,6 +269,37 @@ class _BatchNormParams(nn.Module):
         self.register_buffer('running_var', torch.ones(nf))
         self.weight = nn.Parameter(torch.ones(nf))
         self.bias = nn.Parameter(torch.zeros(nsc))
+        self.blocks = [(m[k], _DIM[k], k == '0e') for k in _ORDER if m[k]]      # (mul, d, scalar): 0o is not a scalar for e3nn (no mean, no bias)
+        self.eps, self.momentum = 1e-5, 0.1
+
+    def forward(self, x):
+        """e3nn.nn.BatchNorm.forward with its defaults (affine, reduce='mean', normalization='component', not instance) in plain torch, so that autograd
+        differentiates it: the batch statistics are not detached in the normalisation.  Training updates the running buffers; evaluation reads them."""
+        out, ix, iw, ib = [], 0, 0, 0
+        for mul, d, scalar in self.blocks:
+            field = x[:, ix:ix + mul * d].reshape(-1, mul, d)
+            ix += mul * d
+            if scalar:
+                if self.training:
+                    mean = field.mean(dim=(0, 2))
+                    with torch.no_grad():
+                        self.running_mean[ib:ib + mul] = (1 - self.momentum) * self.running_mean[ib:ib + mul] + self.momentum * mean.detach()
+                else:
+                    mean = self.running_mean[ib:ib + mul]
+                field = field - mean.reshape(1, mul, 1)
+            if self.training:
+                norm = field.pow(2).mean(-1).mean(0)      # the biased estimate, which also feeds the running average
+                with torch.no_grad():
+                    self.running_var[iw:iw + mul] = (1 - self.momentum) * self.running_var[iw:iw + mul] + self.momentum * norm.detach()
+            else:
+                norm = self.running_var[iw:iw + mul]
+            field = field * ((norm + self.eps).pow(-0.5) * self.weight[iw:iw + mul]).reshape(1, mul, 1)
+            if scalar:
+                field = field + self.bias[ib:ib + mul].reshape(1, mul, 1)
+                ib += mul
+            iw += mul
+            out.append(field.reshape(-1, mul * d))
+        return torch.cat(out, dim=-1)
 
 
 class TensorProductConvLayer(nn.Module):
@@ -234,7 +331,7 @@ class TensorProductConvLayer(nn.Module):
 
     def forward(self, node_attr, edge_index, edge_attr, edge_sh, out_nodes=None, reduce='mean'):
         if self.training:
-            raise RuntimeError('ddk: inference (eval mode) only')
+            return self._forward_training(node_attr, edge_index, edge_attr, edge_sh, out_nodes, reduce)
         if reduce != 'mean' or (out_nodes is not None and out_nodes != node_attr.shape[0]):
             raise RuntimeError("ddk: conv layers aggregate with reduce='mean' onto all nodes")
         if not node_attr.is_cuda:
@@ -245,6 +342,22 @@ class TensorProductConvLayer(nn.Module):
         ea = torch.cat(list(edge_attr), dim=0)
         ctx = self._context(node_attr.device)
         return ctx.conv_forward(self.layer, node_attr, edge_index[0], edge_index[1], offs, ea, edge_sh, self.out_size)
+
+
+    def _forward_training(self, node_attr, edge_index, edge_attr, edge_sh, out_nodes, reduce):
+        """The reference's forward (models/tensor_layers.py:147-168) in training: fused_radial_conv, BatchNorm on the batch statistics, the padded
+        residual.  Without edges: zeros and no BatchNorm, as there."""
+        if reduce != 'mean':
+            raise RuntimeError("ddk: conv layers aggregate with reduce='mean'")
+        if not node_attr.is_cuda:
+            raise RuntimeError('ddk TensorProductConvLayer runs on the GPU only (no CPU fallback)')
+        if edge_index.shape[1] == 0:
+            out = torch.zeros((node_attr.shape[0], self.out_size), dtype=node_attr.dtype, device=node_attr.device)
+        else:
+            out = fused_radial_conv(self.tp, self.fc, node_attr, edge_index, edge_sh, edge_attr, out_nodes=out_nodes)
+            if self.batch_norm is not None:
+                out = self.batch_norm(out)
+        return out + torch.nn.functional.pad(node_attr, (0, out.shape[-1] - node_attr.shape[-1]))
 
 
 class GaussianSmearing(nn.Module):

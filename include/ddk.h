@@ -136,6 +136,41 @@ int ddk_rtp_backward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const floa
  * E < 0 or E >= 2^31.  Host function, no context. */
 int64_t ddk_rtp_backward_workspace(int32_t layer, int64_t E, int32_t n_groups);
 
+/* ---- The radial conv of conv-layer shape `layer` (0..4), node features to aggregated node features: lines 153-159 of TensorProductConvLayer.forward with
+ *      reduce='mean' (models/tensor_layers.py), the gather inside the radial tensor product's kernels and the scatter a fixed-order segmented sum:
+ *        out_nodes[n] = (sum over the edges e with edge_src[e] == n, in ascending e, of FasterTensorProduct(x_nodes[edge_dst[e]], sh[e], w2[g(e)] h[e] + b2[g(e)]))
+ *                       / max(number of those edges, 1)                     (a true division; a node without edges: exact zeros)
+ *      x_nodes [n_in, Din], out_nodes [n_out, Dout]; edge_src, edge_dst: int32 [E], 0 <= edge_src < n_out, 0 <= edge_dst < n_in; src_order: int32 [E], the
+ *      edge ids sorted by edge_src, ascending edge id within a node (a stable sort); src_ptr: int64 [n_out + 1], node n owns src_order[src_ptr[n] ..
+ *      src_ptr[n + 1]).  sh, h, group_offsets, n_groups, w2, b2, E: as ddk_rtp_forward.  DEVICE pointers (group_offsets: HOST), fp32, contiguous; no allocation,
+ *      no synchronisation.  The indices, orderings and pointer tables are TRUSTED (an index outside its range reads or writes outside the buffers): they must
+ *      come from a validated graph, Context.conv_graph in Python.
+ *      workspace: ddk_rconv_workspace(layer, E, n_groups, n_in, n_out, 0) bytes of device memory: the [E, Dout] rows of the tensor product and nothing else.
+ *      Never stored: the per-edge weights [E, W], the gathered rows x_nodes[edge_dst] [E, Din].
+ *      E == 0: out_nodes is written as zeros, no kernel of the tensor product is launched.  Outputs must not alias inputs.  No atomics: the same bits from call
+ *      to call. */
+int ddk_rconv_forward(ddk_ctx* ctx, int32_t layer, const float* x_nodes, int64_t n_in, int64_t n_out, const int32_t* edge_src, const int32_t* edge_dst,
+                      const int32_t* src_order, const int64_t* src_ptr, const float* sh, const float* h, const int64_t* group_offsets, int32_t n_groups,
+                      const float* w2, const float* b2, int64_t E, float* out_nodes, void* workspace, void* stream);
+
+/* VJP of ddk_rconv_forward.  The same operands, and dst_order int32 [E] / dst_ptr int64 [n_in + 1] (the edge ids sorted by edge_dst in the same way),
+ * grad_out_nodes [n_out, Dout].  grad_x_nodes [n_in, Din], grad_sh [E, 4], grad_h [E, 72], grad_w2 [n_groups, W, 72], grad_b2 [n_groups, W]: each may be
+ * NULL (not computed); all five NULL is DDK_ERR_INVALID.  w2 and b2 may be NULL exactly when ddk_rtp_backward allows it.
+ * workspace: ddk_rconv_workspace(layer, E, n_groups, n_in, n_out, 1) bytes, always needed when E > 0.  It holds gn = grad_out_nodes / max(count, 1)
+ * [n_out, Dout] (made once per call, so that the kernels gather plain rows of it), the per-edge rows of grad_x [E, Din] (added per node in ascending edge
+ * id, no atomics) and the parameter images of ddk_rtp_backward_workspace.  Never stored: [E, W] or its gradient, x_nodes[edge_dst] [E, Din], the
+ * gathered rows of grad_out [E, Dout].
+ * E == 0: the grad_x_nodes, grad_w2 and grad_b2 asked for are written as zeros, no kernel of the tensor product is launched.  Outputs must not alias
+ * inputs.  The same bits from call to call, on every device, and whichever subset of the outputs is asked for. */
+int ddk_rconv_backward(ddk_ctx* ctx, int32_t layer, const float* x_nodes, int64_t n_in, int64_t n_out, const int32_t* edge_src, const int32_t* edge_dst,
+                       const int32_t* src_order, const int64_t* src_ptr, const int32_t* dst_order, const int64_t* dst_ptr, const float* sh, const float* h,
+                       const int64_t* group_offsets, int32_t n_groups, const float* w2, const float* b2, const float* grad_out_nodes, int64_t E,
+                       float* grad_x_nodes, float* grad_sh, float* grad_h, float* grad_w2, float* grad_b2, void* workspace, void* stream);
+
+/* Bytes of the workspace of ddk_rconv_forward (backward == 0) or ddk_rconv_backward (backward != 0): a function of its arguments alone, whichever outputs
+ * are asked for; -1 for a layer outside 0..4, n_groups outside 1..4, E < 0 or E >= 2^31, n_in or n_out outside 0 .. 2^31 - 1.  Host function, no context. */
+int64_t ddk_rconv_workspace(int32_t layer, int64_t E, int32_t n_groups, int64_t n_in, int64_t n_out, int32_t backward);
+
 /* ---- a11: TensorProductConvLayer.forward(node_attr, edge_index, edge_attr, edge_sh)
  *      models/tensor_layers.py:147-168 for conv layer `layer`, fused: radial MLP (fp32 MFMA) +
  *      tensor product + segmented scatter-sum + mean + BatchNorm(eval) + residual, without ever

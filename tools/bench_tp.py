@@ -12,7 +12,13 @@ Every figure is the median of --repeats passes of --iters calls between two even
     python tools/bench_tp.py --radial [--edges 200000] [--iters 30] [--json out.json]
 times, for each of the four layer shapes and four equal edge groups, one training step of the op with all gradients two ways in the same run:
 tensor_layers.fused_radial_tp (ddk_rtp_forward / ddk_rtp_backward, k_rtp.hip: the per-edge weights [E, W] never exist) and the composition it replaces
-(the fc Linears, torch.cat, FasterTensorProduct forward and backward, autograd through the Linears), with the peak device memory of each."""
+(the fc Linears, torch.cat, FasterTensorProduct forward and backward, autograd through the Linears), with the peak device memory of each.
+
+    python tools/bench_tp.py --conv [--edges 200000] [--nodes 8000] [--layers 0,3] [--iters 10] [--json out.json]
+times one training step, forward + backward with all gradients, of the conv layer's lines 153-159 on one random graph (--nodes: default edges / 25) two
+ways: (a) tensor_layers.fused_radial_conv (ddk_rconv_forward / ddk_rconv_backward: gather inside the kernels, fixed-order mean, no atomics) and (b) the
+composition it replaces, index_select + fused_radial_tp + index_add_ / count.  The two paths alternate pass by pass; medians of --repeats passes, and the
+peak device memory of one step of each."""
 import argparse, json, os, sys
 import torch
 sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), '..')))
@@ -25,6 +31,9 @@ p.add_argument('--iters', type=int, default=10)
 p.add_argument('--json', default=None)
 p.add_argument('--backward', action='store_true')
 p.add_argument('--radial', action='store_true')
+p.add_argument('--conv', action='store_true')
+p.add_argument('--nodes', type=int, default=None, help='--conv: nodes of the graph (default: edges / 25)')
+p.add_argument('--layers', default='0,3', help='--conv: the layer shapes to time')
 p.add_argument('--repeats', type=int, default=5)
 p.add_argument('--baseline-edges', type=int, default=None, help='edges of the torch baseline (default: --edges; a smaller count is scaled and reported)')
 a = p.parse_args()
@@ -179,8 +188,79 @@ def bench_radial():
         json.dump(results, open(a.json, 'w'), indent=1)
 
 
+def bench_conv():
+    from disco_diffdock_amd.tensor_layers import FCBlock, _shape_context, fused_radial_conv, fused_radial_tp
+    ctx = _shape_context(0)
+    E, results = a.edges, []
+    N = a.nodes or max(1, E // 25)
+    offs = [E * k // 4 for k in range(5)]
+    for layer in [int(v) for v in a.layers.split(',')]:
+        im, om = MULS[min(layer, 3)], MULS[min(layer + 1, 3)]
+        tp = FasterTensorProduct(seq[min(layer, 3)], '1x0e+1x1o', seq[min(layer + 1, 3)])
+        W, din, dout = tp.weight_numel, im[0] + 3 * im[1] + 3 * im[2] + im[3], om[0] + 3 * om[1] + 3 * om[2] + om[3]
+        torch.manual_seed(layer)
+        fc = torch.nn.ModuleList([FCBlock(72, 72, W, 2, 0.0) for _ in range(4)]).to(dev)
+        gen = torch.Generator(device=dev).manual_seed(layer)
+        x, sh, ea, g = (torch.randn(n, c, device=dev, generator=gen) for n, c in ((N, din), (E, 4), (E, 72), (N, dout)))
+        ei = torch.randint(0, N, (2, E), device=dev, generator=gen)
+        graph = ctx.conv_graph(ei[0], ei[1], N, N)
+        count = graph.src_count.clamp(min=1).float()[:, None]
+        X, SH = x.requires_grad_(True), sh.requires_grad_(True)
+        EA = [ea[offs[k]:offs[k + 1]].clone().requires_grad_(True) for k in range(4)]
+
+        def step(fused):
+            for t in [X, SH] + EA + list(fc.parameters()):
+                t.grad = None
+            if fused:
+                out = fused_radial_conv(tp, fc, X, ei, SH, EA, graph=graph)
+            else:
+                rows = fused_radial_tp(tp, fc, X.index_select(0, ei[1]), SH, EA)
+                out = torch.zeros(N, dout, device=dev).index_add_(0, ei[0], rows) / count
+            out.backward(g)
+
+        res = {'layer_shape': layer, 'edges': E, 'nodes': N, 'W': W, 'one_row_tensor_bytes': 4 * E * dout,
+               'workspace_bytes': {'forward': ctx.L.ddk_rconv_workspace(layer, E, 4, N, N, 0), 'backward': ctx.L.ddk_rconv_workspace(layer, E, 4, N, N, 1)}}
+        grads = {}
+        for name, fused in (('fused_conv', True), ('composition', False)):
+            step(fused)      # (warm-up: the allocator's blocks, the kernels' code objects)
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            live = torch.cuda.memory_allocated()
+            step(fused)
+            torch.cuda.synchronize()
+            res[name] = {'peak_bytes': torch.cuda.max_memory_allocated() - live}
+            grads[name] = [X.grad.clone(), SH.grad.clone()] + [p.grad.clone() for p in fc.parameters()]
+        res['max_rel_diff_of_gradients'] = max(float((u - v).abs().max() / v.abs().max()) for u, v in zip(grads['fused_conv'], grads['composition']))
+        step(True)
+        again = [X.grad.clone(), SH.grad.clone()] + [p.grad.clone() for p in fc.parameters()]
+        res['fused_conv']['gradients_bit_identical_run_to_run'] = all(torch.equal(u, v) for u, v in zip(again, grads['fused_conv']))
+        times = {'fused_conv': [], 'composition': []}
+        for _ in range(a.repeats):      # the two paths alternate, so that a drift of the clocks meets both
+            for name, fused in (('fused_conv', True), ('composition', False)):
+                st, en = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                st.record()
+                for _ in range(a.iters):
+                    step(fused)
+                en.record()
+                torch.cuda.synchronize()
+                times[name].append(st.elapsed_time(en) / a.iters)
+        for name, t in times.items():
+            res[name]['ms'], res[name]['ms_passes'] = sorted(t)[len(t) // 2], t
+        res['fused_over_composition_ms'] = res['fused_conv']['ms'] / res['composition']['ms']
+        res['fused_over_composition_peak'] = res['fused_conv']['peak_bytes'] / res['composition']['peak_bytes']
+        print(json.dumps(res), flush=True)
+        results.append(res)
+        del x, sh, ea, g, X, SH, EA, grads, again, graph, count
+        torch.cuda.empty_cache()
+    if a.json:
+        json.dump(results, open(a.json, 'w'), indent=1)
+
+
 if a.backward:
     bench_backward()
+    sys.exit(0)
+if a.conv:
+    bench_conv()
     sys.exit(0)
 if a.radial:
     bench_radial()
