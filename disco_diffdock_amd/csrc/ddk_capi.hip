@@ -355,6 +355,67 @@ int64_t ddk_rconv_workspace(int32_t layer, int64_t E, int32_t n_groups, int64_t 
   return rconv_workspace(layer, E, n_groups, n_in, n_out, backward);
 }
 
+// the checks the two radial-hidden entries share: a context that can launch, the group table, the counts, and with edges the operands both read
+static int rhid_check(ddk_ctx* ctx, const char* who, const int64_t* go, int32_t n_groups, int64_t E, int64_t n_nodes, float p, const float* xs,
+                      const int32_t* edge_src, const int32_t* edge_dst, const float* emb) {
+  int rc = check_launchable(ctx, 0);
+  if (rc) return rc;
+  const std::string w(who);
+  if (n_groups < 1 || n_groups > 4) return fail(ctx, DDK_ERR_INVALID, w + ": n_groups must be in 1..4");
+  if (E < 0 || E >= (int64_t)1 << 31) return fail(ctx, DDK_ERR_INVALID, w + ": edge count out of range");
+  if (n_nodes < 0 || n_nodes >= (int64_t)1 << 31) return fail(ctx, DDK_ERR_INVALID, w + ": node count out of range");
+  if (!go) return fail(ctx, DDK_ERR_INVALID, w + ": null group_offsets");
+  if (go[0] != 0) return fail(ctx, DDK_ERR_INVALID, w + ": group_offsets must start at 0");
+  for (int g = 0; g < n_groups; ++g)
+    if (go[g + 1] < go[g]) return fail(ctx, DDK_ERR_INVALID, w + ": group_offsets are not monotone");
+  if (go[n_groups] != E) return fail(ctx, DDK_ERR_INVALID, w + ": the last group offset is not E");
+  if (!(p >= 0.f && p < 1.f)) return fail(ctx, DDK_ERR_INVALID, w + ": the dropout rate p must be in [0, 1)");
+  if (E == 0) return DDK_OK;
+  if (n_nodes == 0) return fail(ctx, DDK_ERR_INVALID, w + ": edges without nodes");
+  if (!xs || !edge_src || !edge_dst || !emb) return fail(ctx, DDK_ERR_INVALID, w + ": null operand (xs, edge_src, edge_dst, emb)");
+  if (((uintptr_t)xs | (uintptr_t)emb) & 15) return fail(ctx, DDK_ERR_INVALID, w + ": xs and emb must be 16-byte aligned");
+  return DDK_OK;
+}
+
+int ddk_rhid_forward(ddk_ctx* ctx, const float* xs, int64_t n_nodes, const int32_t* edge_src, const int32_t* edge_dst, const float* emb,
+                     const int64_t* group_offsets, int32_t n_groups, const float* w1, const float* b1, float p, uint64_t seed, int64_t E, float* h,
+                     void* stream) {
+  int rc = rhid_check(ctx, "ddk_rhid_forward", group_offsets, n_groups, E, n_nodes, p, xs, edge_src, edge_dst, emb);
+  if (rc) return rc;
+  if (E == 0) return DDK_OK;
+  if (!w1 || !b1 || !h) return fail(ctx, DDK_ERR_INVALID, "ddk_rhid_forward: null operand (w1, b1, h)");
+  hipError_t e = launch_rhid_forward(xs, edge_src, edge_dst, emb, group_offsets, n_groups, w1, b1, p, seed, h, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "rhid_forward launch");
+  return DDK_OK;
+}
+
+int ddk_rhid_backward(ddk_ctx* ctx, const float* xs, int64_t n_nodes, const int32_t* edge_src, const int32_t* edge_dst, const int32_t* src_order,
+                      const int64_t* src_ptr, const int32_t* dst_order, const int64_t* dst_ptr, const float* emb, const float* h,
+                      const int64_t* group_offsets, int32_t n_groups, const float* w1, const float* grad_h, float p, int64_t E, float* grad_xs,
+                      float* grad_emb, float* grad_w1, float* grad_b1, void* workspace, void* stream) {
+  int rc = rhid_check(ctx, "ddk_rhid_backward", group_offsets, n_groups, E, n_nodes, p, xs, edge_src, edge_dst, emb);
+  if (rc) return rc;
+  if (!grad_xs && !grad_emb && !grad_w1 && !grad_b1)
+    return fail(ctx, DDK_ERR_INVALID, "ddk_rhid_backward: no gradient requested (grad_xs, grad_emb, grad_w1 and grad_b1 are all null)");
+  if (E > 0) {
+    if (!h || !grad_h) return fail(ctx, DDK_ERR_INVALID, "ddk_rhid_backward: null operand (h, grad_h)");
+    if ((grad_xs || grad_emb) && !w1)
+      return fail(ctx, DDK_ERR_INVALID, "ddk_rhid_backward: null w1 (it may be null only when grad_xs and grad_emb are both null)");
+    if (grad_xs && (!src_order || !src_ptr || !dst_order || !dst_ptr))
+      return fail(ctx, DDK_ERR_INVALID, "ddk_rhid_backward: null graph table (grad_xs needs the orderings and their pointer tables)");
+    if (!workspace) return fail(ctx, DDK_ERR_INVALID, "ddk_rhid_backward: null workspace (ddk_rhid_workspace bytes)");
+    if (((uintptr_t)workspace | (uintptr_t)h | (uintptr_t)grad_h) & 15)
+      return fail(ctx, DDK_ERR_INVALID, "ddk_rhid_backward: h, grad_h and the workspace must be 16-byte aligned");
+  }
+  const RconvGraph gr{n_nodes, n_nodes, edge_src, edge_dst, src_order, src_ptr, dst_order, dst_ptr};
+  hipError_t e = launch_rhid_backward(gr, xs, emb, h, group_offsets, n_groups, w1, grad_h, p, grad_xs, grad_emb, grad_w1, grad_b1, (float*)workspace,
+                                      (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "rhid_backward launch");
+  return DDK_OK;
+}
+
+int64_t ddk_rhid_workspace(int64_t E, int32_t n_groups, int64_t n_nodes) { return rhid_workspace(E, n_groups, n_nodes); }
+
 int ddk_conv_forward(ddk_ctx* ctx, int32_t layer, const float* x, int64_t N, const int32_t* edge_src,
                      const int32_t* edge_dst, const int64_t* go, const float* edge_attr, const float* sh, float* out,
                      void* stream) {

@@ -336,6 +336,12 @@ hipError_t launch_rtp_backward(const ConvLayerDev& L, const float* x_dst, const 
                                const float* w2, const float* b2, const float* grad_out, float* grad_x, float* grad_sh, float* grad_h, float* grad_w2,
                                float* grad_b2, float* workspace, hipStream_t s);
 int64_t rtp_backward_workspace(int32_t layer, int64_t E, int32_t n_groups);
+// edges per slice of a parameter-gradient pass (k_rtp.hip, k_rhid.hip): 512, longer once E > 122 880 so that there are never more than 240 + G slices.
+// A function of E alone: the bits of a parameter gradient do not depend on the device
+__host__ __device__ inline int64_t rtp_slice_len(int64_t E) {
+  const int64_t l = ((E + 239) / 240 + 63) / 64 * 64;
+  return l > 512 ? l : 512;
+}
 // k_rtp.hip: the radial conv, node rows to aggregated node rows (include/ddk.h: ddk_rconv_forward / ddk_rconv_backward).  The graph of a call: trusted device
 // tables, dst_order / dst_ptr read by the backward alone
 struct RconvGraph {
@@ -348,4 +354,15 @@ hipError_t launch_rconv_backward(const ConvLayerDev& L, const RconvGraph& gr, co
                                  int n_groups, const float* w2, const float* b2, const float* grad_out_nodes, float* grad_x_nodes, float* grad_sh, float* grad_h,
                                  float* grad_w2, float* grad_b2, float* workspace, hipStream_t s);
 int64_t rconv_workspace(int32_t layer, int64_t E, int32_t n_groups, int64_t n_in, int64_t n_out, int32_t backward);
+// k_rtp.hip: the radial conv's fixed-order segmented sum without the mean (rtp_seg_kernel<false>): nodes[n, :] = the rows order[ptr[n] .. ptr[n + 1]) of
+// rows [*, D] added in that order; a node without rows: exact zeros
+hipError_t launch_rtp_seg_sum(const float* rows, const int32_t* order, const int64_t* ptr, float* nodes, int64_t N, int D, hipStream_t s);
+// k_rhid.hip: the radial MLP's hidden layer from the edge embedding and the node table, h = dropout(relu(W1[g] [emb | xs[src] | xs[dst]] + b1[g])), and its
+// vector-Jacobian product (include/ddk.h: ddk_rhid_forward / ddk_rhid_backward).  gr: n_in == n_out nodes; a null output is not computed
+hipError_t launch_rhid_forward(const float* xs, const int32_t* src, const int32_t* dst, const float* emb, const int64_t* group_offsets, int n_groups,
+                               const float* w1, const float* b1, float p, uint64_t seed, float* h, hipStream_t s);
+hipError_t launch_rhid_backward(const RconvGraph& gr, const float* xs, const float* emb, const float* h, const int64_t* group_offsets, int n_groups,
+                                const float* w1, const float* grad_h, float p, float* grad_xs, float* grad_emb, float* grad_w1, float* grad_b1,
+                                float* workspace, hipStream_t s);
+int64_t rhid_workspace(int64_t E, int32_t n_groups, int64_t n_nodes);
 }  // namespace ddk

@@ -58,11 +58,6 @@ struct RtpArgs {
   const int32_t* xi; const int32_t* gi;      // the indexed kernels (the radial conv): edge e reads row xi[e] of x and row gi[e] of g
 };
 
-__host__ __device__ inline int64_t rtp_slice_len(int64_t E) {
-  const int64_t l = ((E + 239) / 240 + 63) / 64 * 64;
-  return l > 512 ? l : 512;
-}
-
 template <class S>
 struct RtpT {      // the tiles of a shape: row groups and column groups of block k, its first tile, the number of tiles
   static constexpr int NRG(int k) { return S::O(k) ? (S::R(k) + 3) / 4 : 0; }
@@ -691,6 +686,10 @@ static hipError_t rtp_seg_launch(const float* rows, const int32_t* order, const 
   const int64_t nb = (N * D + 255) / 256;      // N < 2^31 and D <= 128: fewer than 2^31 workgroups
   if (nb > 0) hipLaunchKernelGGL((rtp_seg_kernel<MEAN>), dim3((unsigned)nb), dim3(256), 0, s, rows, order, ptr, nodes, N, D);
   return hipGetLastError();
+}
+
+hipError_t launch_rtp_seg_sum(const float* rows, const int32_t* order, const int64_t* ptr, float* nodes, int64_t N, int D, hipStream_t s) {
+  return rtp_seg_launch<false>(rows, order, ptr, nodes, N, D, s);
 }
 
 static hipError_t rconv_zero(float* p, int64_t n, hipStream_t s) {

@@ -478,6 +478,79 @@ class Context:
             raise RuntimeError(f'ddk: no radial-conv workspace for layer {layer}, E = {graph.E}, {G} groups, {graph.n_in} -> {graph.n_out} nodes')
         return torch.empty(max(int(nbytes), 4) // 4, dtype=torch.float32, device=device)
 
+    # ---- the radial MLP's hidden layer from the edge embedding and the node table ---------------------
+    def _rhid_operands(self, graph, xs, emb, group_offsets, w1, b1, p):
+        """checked operands of the radial hidden layer: (xs, emb, offsets as a ctypes int64 array, G, w1, b1, p)"""
+        if not isinstance(graph, ConvGraph):
+            raise RuntimeError('ddk: the radial hidden layer takes a ConvGraph (Context.conv_graph): its kernels trust the indices')
+        xs, emb = (_need_cuda(t).contiguous().float() for t in (xs, emb))
+        offs = [int(o) for o in group_offsets]
+        G, E = len(offs) - 1, graph.E
+        if not 1 <= G <= 4:
+            raise RuntimeError(f'ddk: the radial hidden layer takes 1..4 edge groups; got {G}')
+        if graph.n_in != graph.n_out or xs.dim() != 2 or xs.shape != (graph.n_in, 24):
+            raise RuntimeError(f'ddk: the radial hidden layer takes xs [n_nodes, 24] and a graph with n_in == n_out == n_nodes; got {tuple(xs.shape)} and a '
+                               f'graph of {graph.n_in} -> {graph.n_out} nodes')
+        if emb.shape != (E, 24):
+            raise RuntimeError(f'ddk: the radial hidden layer takes emb [E, 24] for a graph of {E} edges; got {tuple(emb.shape)}')
+        if graph.src.device != xs.device or emb.device != xs.device:
+            raise RuntimeError('ddk: the radial hidden layer takes a ConvGraph and emb on the device of xs')
+        if offs[-1] != E:
+            raise RuntimeError(f'ddk: the edge groups hold {offs[-1]} edges, the graph {E}')
+        if w1 is not None:
+            w1 = _need_cuda(w1).contiguous().float()
+            if w1.shape != (G, 72, 72) or w1.device != xs.device:
+                raise RuntimeError(f'ddk: the radial hidden layer takes w1 [G, 72, 72] = {(G, 72, 72)} on the device of xs; got {tuple(w1.shape)}')
+        if b1 is not None:
+            b1 = _need_cuda(b1).contiguous().float()
+            if b1.shape != (G, 72) or b1.device != xs.device:
+                raise RuntimeError(f'ddk: the radial hidden layer takes b1 [G, 72] = {(G, 72)} on the device of xs; got {tuple(b1.shape)}')
+        p = float(p)
+        if not 0.0 <= p < 1.0:
+            raise RuntimeError(f'ddk: the dropout rate must be in [0, 1); got {p}')
+        return xs, emb, (C.c_int64 * (G + 1))(*offs), G, w1, b1, p
+
+    def rhid_forward(self, graph, xs, emb, group_offsets, w1, b1, p=0.0, seed=0):
+        """The radial MLP's hidden layer (ddk_rhid_forward): h [E, 72] = dropout_p(relu(w1[g] [emb | xs[graph.src] | xs[graph.dst]] + b1[g])) without the
+        concatenated row.  ``xs`` [n_nodes, 24], ``emb`` [E, 24], ``w1`` [G, 72, 72], ``b1`` [G, 72]; the mask is a pure function of (seed, edge, column)
+        (DDK_RHID_MASK_LAYOUT of include/ddk.h), ``p == 0`` draws nothing."""
+        xs, emb, offs, G, w1, b1, p = self._rhid_operands(graph, xs, emb, group_offsets, w1, b1, p)
+        if w1 is None or b1 is None:
+            raise RuntimeError('ddk: rhid_forward needs w1 and b1')
+        g = graph
+        h = torch.empty((g.E, 72), dtype=torch.float32, device=xs.device)
+        self._check(self.L.ddk_rhid_forward(self.h, _ptr(xs), g.n_in, _ptr(g.src), _ptr(g.dst), _ptr(emb), offs, G, _ptr(w1), _ptr(b1), p,
+                                            _u64(seed, 'seed'), g.E, _ptr(h), _stream()), 'ddk_rhid_forward')
+        return h
+
+    def rhid_backward(self, graph, xs, emb, h, group_offsets, w1, grad_h, p=0.0, need=(True, True, True, True)):
+        """The vector-Jacobian product of ``rhid_forward`` (ddk_rhid_backward): (grad_xs [n_nodes, 24], grad_emb [E, 24], grad_w1 [G, 72, 72], grad_b1
+        [G, 72]), None where ``need`` is false.  ``h``: the forward's output (it carries the pattern of ReLU and Dropout; no seed is needed); ``w1`` may be
+        None when only grad_w1 / grad_b1 are asked for.  No atomics: the same bits from call to call.  The workspace comes from torch's allocator and is
+        released on return."""
+        need = tuple(bool(n) for n in need)
+        if len(need) != 4 or not any(need):
+            raise RuntimeError('ddk: rhid_backward needs at least one of its four gradients to compute')
+        if w1 is None and any(need[:2]):
+            raise RuntimeError('ddk: rhid_backward needs w1 for grad_xs and grad_emb')
+        xs, emb, offs, G, w1, _, p = self._rhid_operands(graph, xs, emb, group_offsets, w1, None, p)
+        g = graph
+        h, grad_h = (_need_cuda(t).contiguous().float() for t in (h, grad_h))
+        if h.shape != (g.E, 72) or grad_h.shape != (g.E, 72) or h.device != xs.device or grad_h.device != xs.device:
+            raise RuntimeError('ddk: rhid_backward takes h and grad_h [E, 72] on the device of xs')
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=xs.device)
+        outs = [new(g.n_in, 24) if need[0] else None, new(g.E, 24) if need[1] else None, new(G, 72, 72) if need[2] else None, new(G, 72) if need[3] else None]
+        if not any(o is not None and o.numel() for o in outs):      # (empty tensors have no address: the entry would see no output at all)
+            return tuple(outs)
+        nbytes = self.L.ddk_rhid_workspace(g.E, G, g.n_in)
+        if nbytes < 0:
+            raise RuntimeError(f'ddk: no radial-hidden workspace for E = {g.E}, {G} groups, {g.n_in} nodes')
+        ws = torch.empty(max(int(nbytes), 4) // 4, dtype=torch.float32, device=xs.device)
+        self._check(self.L.ddk_rhid_backward(self.h, _ptr(xs), g.n_in, _ptr(g.src), _ptr(g.dst), _ptr(g.src_order), _ptr(g.src_ptr), _ptr(g.dst_order),
+                                             _ptr(g.dst_ptr), _ptr(emb), _ptr(h), offs, G, _ptr(w1), _ptr(grad_h), p, g.E, *[_ptr(o) for o in outs],
+                                             _ptr(ws), _stream()), 'ddk_rhid_backward')
+        return tuple(outs)      # (ws goes back to torch's allocator, which orders its reuse after these launches on the current stream)
+
     def tp_weight_numel(self, layer):
         """W of conv layer ``layer``: the length of a FasterTensorProduct weight row (tensor_layers.py:56-63)."""
         return tp_layer_shape(layer, self.cfg.ns, self.cfg.nv)['W']

@@ -10,15 +10,20 @@ parity tests read like tests of the reference modules:
   of tensor_layers.py:154-156 as one differentiable op that never stores the per-edge weights (training)
 * ``fused_radial_conv(tp, fc, node_attr, edge_index, edge_sh, edge_attr, out_nodes=None, graph=None)``: lines 153-159, from the
   node features to the scatter-mean, as one differentiable op: the gather inside the kernels, the mean a fixed-order sum,
-  no atomics (the same gradient bits on every run)
+  no atomics (the same gradient bits on every run); ``hidden=`` takes the hidden activation made by ``fused_radial_hidden``
+* ``fused_radial_hidden(fc, node_attr, edge_emb, group_offsets, graph, seed=None)``: the cat of the embed loop
+  (score_model.py:227-230) and ``fc[g][:4]`` as one differentiable op from the edge embedding [E, ns]: no [E, 72] row, no
+  atomics, a counter-based dropout mask
+* ``TensorProductConvLayer.forward_embedded(...)`` and ``conv_stack(conv_layers, ...)``: one step of that loop, and the loop
 
 Only the configuration the shipped score models use is implemented on the device (ns=24, nv=6, sh_lmax=1,
 faster=True, edge_groups=4, residual=True, 2-layer ReLU radial MLP); anything else raises.
 
 ``TensorProductConvLayer`` trains: in ``.train()`` its forward is ``fused_radial_conv``, e3nn's BatchNorm on the batch
 statistics (plain torch, ``_BatchNormParams.forward``) and the padded residual.  In ``.eval()`` it is the fused inference
-kernel (``ddk_conv_forward``), unchanged.  What still does not train: ``ddk_score_forward`` end to end, the all-atom /
-confidence irreps, any other ns / nv.
+kernel (``ddk_conv_forward``), unchanged.  ``conv_stack`` trains the whole stack of them from the edge embedding with the
+same bits on every run.  What still does not train: the heads, ``ddk_score_forward`` end to end, the all-atom / confidence
+irreps, any other ns / nv.
 """
 import math
 
@@ -162,25 +167,39 @@ class _RadialTPFunction(torch.autograd.Function):
         return _grads_like(grads, fctx.meta) + (None, None, None)
 
 
-def _radial_operands(who, tp, fc, x, edge_attr):
+def _radial_operands(who, tp, fc, x, edge_attr, hidden=None):
     """What fused_radial_tp and fused_radial_conv share: the checks on ``tp`` and ``fc``, then ``fc[i][0..3]`` in torch.  Returns the group offsets, the
-    hidden activation [E, 72] and the last Linears stacked, w2 [G, W, 72] and b2 [G, W]."""
+    hidden activation [E, 72] and the last Linears stacked, w2 [G, W, 72] and b2 [G, W].  With ``hidden`` given (fused_radial_hidden's output)
+    ``fc[i][0..3]`` do not run, and ``edge_attr`` gives the groups alone: G + 1 integer offsets, or one tensor per group whose rows are counted."""
     if not isinstance(tp, FasterTensorProduct):
         raise RuntimeError(f'ddk: {who} takes a FasterTensorProduct')
     if not x.is_cuda:
         raise RuntimeError(f'ddk {who} runs on the GPU only (no CPU fallback)')
-    if isinstance(fc, nn.Sequential):
-        fc, edge_attr = [fc], ([edge_attr] if torch.is_tensor(edge_attr) else list(edge_attr))
-    fc, edge_attr = list(fc), list(edge_attr)
-    if len(fc) != len(edge_attr) or not 1 <= len(fc) <= 4:
+    if hidden is not None and not torch.is_tensor(edge_attr) and len(edge_attr) and not torch.is_tensor(edge_attr[0]):
+        offs = [int(o) for o in edge_attr]
+        fc = [fc] if isinstance(fc, nn.Sequential) else list(fc)
+        if len(offs) != len(fc) + 1 or offs[0] != 0 or any(b < a for a, b in zip(offs, offs[1:])):
+            raise RuntimeError(f'ddk: {who} with hidden= takes G + 1 ascending group offsets that start at 0, G the number of FCBlocks')
+        edge_attr = None
+    else:
+        if isinstance(fc, nn.Sequential):
+            fc, edge_attr = [fc], ([edge_attr] if torch.is_tensor(edge_attr) else list(edge_attr))
+        fc, edge_attr = list(fc), list(edge_attr)
+        if len(fc) != len(edge_attr):
+            raise RuntimeError(f'ddk: {who} takes one edge_attr tensor per FCBlock, 1..4 of them')
+        offs = [0]
+        for ea in edge_attr:
+            offs.append(offs[-1] + ea.shape[0])
+    if not 1 <= len(fc) <= 4:
         raise RuntimeError(f'ddk: {who} takes one edge_attr tensor per FCBlock, 1..4 of them')
     for blk in fc:
         if len(blk) != 5 or not isinstance(blk[4], nn.Linear) or blk[4].in_features != 72 or blk[4].out_features != tp.weight_numel or blk[4].bias is None:
             raise RuntimeError(f'ddk: {who} takes 2-layer FCBlocks whose last Linear maps 72 -> weight_numel')
-    offs = [0]
-    for ea in edge_attr:
-        offs.append(offs[-1] + ea.shape[0])
-    hidden = torch.cat([blk[:4](ea) for blk, ea in zip(fc, edge_attr)], dim=0) if len(fc) > 1 else fc[0][:4](edge_attr[0])
+    if hidden is not None:
+        if hidden.dim() != 2 or hidden.shape != (offs[-1], 72):
+            raise RuntimeError(f'ddk: {who} takes hidden [E, 72] with E = {offs[-1]}, the total of the edge groups; got {tuple(hidden.shape)}')
+    else:
+        hidden = torch.cat([blk[:4](ea) for blk, ea in zip(fc, edge_attr)], dim=0) if len(fc) > 1 else fc[0][:4](edge_attr[0])
     w2, b2 = torch.stack([blk[4].weight for blk in fc]), torch.stack([blk[4].bias for blk in fc])
     return offs, hidden, w2, b2
 
@@ -228,15 +247,16 @@ class _RadialConvFunction(torch.autograd.Function):
         return _grads_like(grads, fctx.meta) + (None, None, None)
 
 
-def fused_radial_conv(tp, fc, node_attr, edge_index, edge_sh, edge_attr, out_nodes=None, graph=None):
+def fused_radial_conv(tp, fc, node_attr, edge_index, edge_sh, edge_attr, out_nodes=None, graph=None, hidden=None):
     """Lines 153-159 of the reference's TensorProductConvLayer.forward with reduce='mean' (models/tensor_layers.py) as one differentiable op:
     ``scatter(tp(node_attr[edge_dst], edge_sh, torch.cat([fc[i](edge_attr[i]) ...])), edge_src, dim_size=out_nodes, reduce='mean')``.  ``fc[i][0..3]``
     (Dropout included) run in torch; the last Linear, the gather, the tensor product and the mean run in the kernels of the radial tensor product and a
     fixed-order segmented sum, forward and backward: no [E, W] weights, no gathered rows, no atomics, so the gradients of ``node_attr``, ``edge_sh``,
     ``edge_attr`` and every parameter of ``fc`` have the same bits on every run.  ``graph``: a ``runtime.ConvGraph`` made once for this
     ``edge_index`` (``Context.conv_graph(edge_index[0], edge_index[1], n_in=node_attr.shape[0], n_out=out_nodes)``); built here otherwise, which
-    costs two sorts and one read-back per call.  [out_nodes or N, Dout], fp32."""
-    offs, hidden, w2, b2 = _radial_operands('fused_radial_conv', tp, fc, node_attr, edge_attr)
+    costs two sorts and one read-back per call.  ``hidden``: the hidden activation [E, 72] made elsewhere (``fused_radial_hidden``); ``fc[i][0..3]`` are
+    skipped then, and ``edge_attr`` only names the groups: G + 1 integer offsets, or per-group tensors whose rows are counted.  [out_nodes or N, Dout], fp32."""
+    offs, hidden, w2, b2 = _radial_operands('fused_radial_conv', tp, fc, node_attr, edge_attr, hidden)
     if node_attr.dim() != 2:
         raise RuntimeError('ddk: fused_radial_conv takes node_attr [N, Din]')
     n_out = out_nodes or node_attr.shape[0]
@@ -249,6 +269,97 @@ def fused_radial_conv(tp, fc, node_attr, edge_index, edge_sh, edge_attr, out_nod
         return _RadialConvFunction.apply(node_attr, edge_sh, hidden, w2, b2, tp.layer, tuple(offs), graph)
     ctx = _shape_context(node_attr.device.index or 0)
     return ctx.rconv_forward(tp.layer, graph, node_attr, edge_sh.reshape(-1, 4), hidden, offs, w2, b2)
+
+
+class _RadialHiddenFunction(torch.autograd.Function):
+    """ddk_rhid_forward with ddk_rhid_backward as its vector-Jacobian product: the hidden activation of the radial MLP from the node scalars and the
+    edge embedding.  Saved for the backward: xs [N, 24], emb [E, 24], h [E, 72] (the output, which carries the ReLU and Dropout pattern), the graph, and
+    w1 where an input gradient reads it; never the concatenated row, the ReLU output or a mask.  No atomics: the same gradient bits on every run."""
+
+    @staticmethod
+    def forward(fctx, xs, emb, w1, b1, offsets, graph, p, seed):
+        ctx = _shape_context(xs.device.index or 0)
+        x, e = _as_rows(xs, 24), _as_rows(emb, 24)
+        w, b = w1.contiguous().float(), b1.contiguous().float()
+        h = ctx.rhid_forward(graph, x, e, offsets, w, b, p, seed)
+        fctx.save_for_backward(x, e, h, w if any(fctx.needs_input_grad[:2]) else None)      # the parameter gradients do not read w1
+        fctx.ddk, fctx.offsets, fctx.graph, fctx.p = ctx, tuple(offsets), graph, p
+        fctx.meta = [(t.shape, t.dtype) for t in (xs, emb, w1, b1)]
+        return h
+
+    @staticmethod
+    @once_differentiable
+    def backward(fctx, grad_h):
+        x, e, h, w = fctx.saved_tensors
+        need = tuple(fctx.needs_input_grad[:4])
+        g = grad_h.reshape(-1, 72).contiguous().float()
+        with torch.cuda.device(x.device):
+            grads = fctx.ddk.rhid_backward(fctx.graph, x, e, h, fctx.offsets, w, g, fctx.p, need)
+        return _grads_like(grads, fctx.meta) + (None, None, None, None)
+
+
+def _draw_seed():
+    """one 63-bit draw from torch's default CPU generator: torch.manual_seed reproduces it, and nothing waits for the device"""
+    return int(torch.randint(0, (1 << 63) - 1, (1,), dtype=torch.int64).item())
+
+
+def fused_radial_hidden(fc, node_attr, edge_emb, group_offsets, graph, seed=None):
+    """``torch.cat([fc[g][:4](edge_attr_[g]) for g in range(G)])`` with ``edge_attr_ = torch.cat([edge_emb, node_attr[edge_index[0], :ns],
+    node_attr[edge_index[1], :ns]], -1)`` cut into the groups (the reference's embed loop, models/score_model.py:227-230, and the first half of the
+    conv layer's radial MLP) as one differentiable op: the hidden activation [E, 72] of all groups.  The gathers, the Linear, the ReLU and the Dropout
+    run in one kernel; the backward adds the gathers' gradients per node in a fixed order (no atomics), so ``node_attr``, ``edge_emb`` and every
+    ``fc[g][0]`` parameter get the same gradient bits on every run.  ``fc``: the layer's FCBlocks (or one); ``group_offsets``: G + 1 integers;
+    ``graph``: the ``ConvGraph`` of ``edge_index`` over ``node_attr``'s rows.  Dropout: rate ``fc[g][3].p`` while that module is in training mode (the
+    same in every group), else none; the mask is a pure function of (``seed``, edge, column), DDK_RHID_MASK_LAYOUT of include/ddk.h.  ``seed=None``
+    takes one draw from torch's default CPU generator, so ``torch.manual_seed`` reproduces a step."""
+    fc = [fc] if isinstance(fc, nn.Sequential) else list(fc)
+    offs = [int(o) for o in group_offsets]
+    if not 1 <= len(fc) <= 4 or len(offs) != len(fc) + 1:
+        raise RuntimeError('ddk: fused_radial_hidden takes 1..4 FCBlocks and one more group offset than blocks')
+    for blk in fc:
+        if (len(blk) != 5 or not isinstance(blk[4], nn.Linear) or blk[4].in_features != 72 or blk[4].bias is None or not isinstance(blk[0], nn.Linear)
+                or blk[0].in_features != 72 or blk[0].out_features != 72 or blk[0].bias is None or not isinstance(blk[2], nn.ReLU)
+                or not isinstance(blk[3], nn.Dropout)):
+            raise RuntimeError('ddk: fused_radial_hidden takes 2-layer FCBlocks: Linear(72, 72) with bias, Identity, ReLU, Dropout, Linear(72, .)')
+    rates = {float(blk[3].p) if blk[3].training else 0.0 for blk in fc}
+    if len(rates) != 1:
+        raise RuntimeError(f'ddk: fused_radial_hidden takes one dropout rate for all groups; got {sorted(rates)}')
+    p = rates.pop()
+    if not 0.0 <= p < 1.0:
+        raise RuntimeError(f'ddk: fused_radial_hidden takes a dropout rate in [0, 1); got {p}')
+    if not node_attr.is_cuda:
+        raise RuntimeError('ddk fused_radial_hidden runs on the GPU only (no CPU fallback)')
+    if node_attr.dim() != 2 or node_attr.shape[1] < 24 or edge_emb.dim() != 2 or edge_emb.shape[1] != 24:
+        raise RuntimeError('ddk: fused_radial_hidden takes node_attr [N, >= 24] and edge_emb [E, 24]')
+    if seed is None:
+        seed = _draw_seed() if p > 0 else 0
+    xs = node_attr[:, :24]      # (torch's slice: its backward pads the gradient back to the node row)
+    w1, b1 = torch.stack([blk[0].weight for blk in fc]), torch.stack([blk[0].bias for blk in fc])
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (xs, edge_emb, w1, b1)):
+        return _RadialHiddenFunction.apply(xs, edge_emb, w1, b1, tuple(offs), graph, p, int(seed))
+    return _shape_context(node_attr.device.index or 0).rhid_forward(graph, xs, edge_emb, offs, w1, b1, p, int(seed))
+
+
+def _layer_seed(seed, l):
+    """the seed of layer ``l`` of a stack: the stack's seed moved by the layer's multiple of the 64-bit golden ratio (distinct Philox keys)"""
+    return (int(seed) + (l + 1) * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+
+
+def conv_stack(conv_layers, node_attr, edge_index, edge_emb, group_sizes, edge_sh, seed=None):
+    """The conv loop of the reference's embed (models/score_model.py:227-230) over ``conv_layers``: every layer sees
+    ``[edge_emb | node_attr[edge_index[0], :ns] | node_attr[edge_index[1], :ns]]`` of the current node features, cut into groups of ``group_sizes`` edges.
+    One ``ConvGraph`` is built for all layers; layer l's dropout seed is derived from ``seed`` (``None``: one draw from torch's default CPU generator).
+    In training the whole stack runs without atomics: two passes from one state and one seed give the same bits.  Returns ``node_attr``."""
+    layers = list(conv_layers)
+    graph = None
+    if any(layer.training for layer in layers) and edge_index.shape[1] > 0:
+        graph = Context.conv_graph(edge_index[0], edge_index[1], node_attr.shape[0], node_attr.shape[0])
+        if seed is None:
+            seed = _draw_seed()
+    for l, layer in enumerate(layers):
+        node_attr = layer.forward_embedded(node_attr, edge_index, edge_emb, group_sizes, edge_sh, graph=graph,
+                                           seed=None if seed is None else _layer_seed(seed, l))
+    return node_attr
 
 
 def FCBlock(in_dim, hidden_dim, out_dim, layers, dropout, activation='relu', batchnorm=False):
@@ -355,6 +466,36 @@ class TensorProductConvLayer(nn.Module):
             out = torch.zeros((node_attr.shape[0], self.out_size), dtype=node_attr.dtype, device=node_attr.device)
         else:
             out = fused_radial_conv(self.tp, self.fc, node_attr, edge_index, edge_sh, edge_attr, out_nodes=out_nodes)
+            if self.batch_norm is not None:
+                out = self.batch_norm(out)
+        return out + torch.nn.functional.pad(node_attr, (0, out.shape[-1] - node_attr.shape[-1]))
+
+    def forward_embedded(self, node_attr, edge_index, edge_emb, group_sizes, edge_sh, graph=None, seed=None):
+        """One step of the reference's embed loop (models/score_model.py:227-230) from the edge EMBEDDING [E, ns]: what ``forward`` returns for
+        ``edge_attr = [edge_emb | node_attr[edge_index[0], :ns] | node_attr[edge_index[1], :ns]]`` cut into groups of ``group_sizes`` edges.  In
+        training the row [E, 72] is never built: ``fused_radial_hidden`` -> ``fused_radial_conv(hidden=...)`` -> BatchNorm -> residual, without
+        atomics.  ``graph``: the ``ConvGraph`` of ``edge_index`` over the nodes, built here otherwise; ``seed``: of the dropout mask
+        (``fused_radial_hidden``).  In evaluation the cat is built and ``forward`` runs the inference kernel, unchanged."""
+        sizes = [int(n) for n in group_sizes]
+        E = edge_index.shape[1]
+        if len(sizes) != self.edge_groups or any(n < 0 for n in sizes) or sum(sizes) != E or edge_emb.shape[0] != E:
+            raise RuntimeError(f'ddk: forward_embedded takes {self.edge_groups} group sizes that add up to the {E} edges of edge_index and edge_emb')
+        if not self.training:
+            ns = edge_emb.shape[1]
+            edge_attr = torch.cat([edge_emb, node_attr[edge_index[0], :ns], node_attr[edge_index[1], :ns]], -1)
+            return self.forward(node_attr, edge_index, list(torch.split(edge_attr, sizes)), edge_sh)
+        if not node_attr.is_cuda:
+            raise RuntimeError('ddk TensorProductConvLayer runs on the GPU only (no CPU fallback)')
+        if E == 0:
+            out = torch.zeros((node_attr.shape[0], self.out_size), dtype=node_attr.dtype, device=node_attr.device)
+        else:
+            offs = [0]
+            for n in sizes:
+                offs.append(offs[-1] + n)
+            if graph is None:
+                graph = Context.conv_graph(edge_index[0], edge_index[1], node_attr.shape[0], node_attr.shape[0])
+            hidden = fused_radial_hidden(self.fc, node_attr, edge_emb, offs, graph, seed=seed)
+            out = fused_radial_conv(self.tp, self.fc, node_attr, edge_index, edge_sh, offs, graph=graph, hidden=hidden)
             if self.batch_norm is not None:
                 out = self.batch_norm(out)
         return out + torch.nn.functional.pad(node_attr, (0, out.shape[-1] - node_attr.shape[-1]))

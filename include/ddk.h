@@ -171,6 +171,53 @@ int ddk_rconv_backward(ddk_ctx* ctx, int32_t layer, const float* x_nodes, int64_
  * are asked for; -1 for a layer outside 0..4, n_groups outside 1..4, E < 0 or E >= 2^31, n_in or n_out outside 0 .. 2^31 - 1.  Host function, no context. */
 int64_t ddk_rconv_workspace(int32_t layer, int64_t E, int32_t n_groups, int64_t n_in, int64_t n_out, int32_t backward);
 
+/* ---- The radial MLP's hidden layer from the edge embedding and the node table: the cat of the reference's embed loop (models/score_model.py:227-230) and
+ *      fc[g][0..3] of the conv layer (Linear 72 -> 72, Identity, ReLU, Dropout; models/tensor_layers.py:154) as one op, the row [E, 72] of the cat never stored.
+ *      For edge e of group g:
+ *        pre[e, :] = b1[g] + w1[g] . [ emb[e, 0:24] | xs[edge_src[e], 0:24] | xs[edge_dst[e], 0:24] ]
+ *        h[e, c]   = keep(e, c) ? max(pre[e, c], 0) * s : 0          s = 1.0f / (1.0f - p) in fp32;  p == 0: s = 1, keep is true everywhere, nothing is drawn
+ *      xs [n_nodes, 24] (the scalar part of the node table, its own contiguous tensor), emb [E, 24], w1 [n_groups, 72, 72] (fc[g][0].weight stacked: columns
+ *      0:24 meet emb, 24:48 the src row, 48:72 the dst row), b1 [n_groups, 72], h [E, 72]: DEVICE pointers, fp32, contiguous, 16-byte aligned.  edge_src,
+ *      edge_dst: int32 [E], both index xs.  group_offsets, n_groups, E: as ddk_rtp_forward (HOST array).  0 <= p < 1, anything else is DDK_ERR_INVALID.
+ *      The index tables are TRUSTED, as in ddk_rconv_forward: they must come from a validated graph (Context.conv_graph in Python).
+ *      Exact fp32 in a fixed order: pre[e, c] is one fmaf chain over the 72 columns in ascending order that starts from b1[g][c].
+ *
+ *      THE DROPOUT MASK is a layout contract like DDK_RNG_LAYOUT: for a given DDK_RHID_MASK_LAYOUT it never changes.  keep(e, c) is a pure function of
+ *      (seed, edge id e, column c); it does not depend on the launch grid, the device, the group table or the call.
+ *        generator  Philox4x32-10 of csrc/k_philox.h (the sampler's)
+ *        key        (seed_lo, seed_hi), the low and high words of `seed`
+ *        counter    c0 = e_lo, c1 = e_hi (the 64-bit edge id), c2 = c / 4, c3 = DDK_RHID_MASK_TAG
+ *        word       c % 4 of the block's four words
+ *        rule       keep iff u >= p with u = (word >> 8) * 2^-24, the generator's uniform in [0, 1), compared in fp32
+ *      No allocation, no synchronisation.  E == 0: DDK_OK, no launch. */
+#define DDK_RHID_MASK_LAYOUT 1
+#define DDK_RHID_MASK_TAG 0x52484944u      /* "RHID" */
+int ddk_rhid_forward(ddk_ctx* ctx, const float* xs, int64_t n_nodes, const int32_t* edge_src, const int32_t* edge_dst, const float* emb,
+                     const int64_t* group_offsets, int32_t n_groups, const float* w1, const float* b1, float p, uint64_t seed, int64_t E, float* h,
+                     void* stream);
+
+/* VJP of ddk_rhid_forward.  h: the forward's output, which carries the pattern of ReLU and Dropout: gpre[e, c] = grad_h[e, c] * (h[e, c] != 0 ? s : 0), so
+ * the backward takes neither the seed nor a mask.  src_order / src_ptr, dst_order / dst_ptr: the node-sorted edge lists of ddk_rconv_backward over
+ * edge_src and edge_dst, both with n_nodes + 1 pointer entries.  grad_xs [n_nodes, 24], grad_emb [E, 24], grad_w1 [n_groups, 72, 72], grad_b1 [n_groups, 72]:
+ * each may be NULL (not computed); all four NULL is DDK_ERR_INVALID.  w1 may be NULL iff grad_xs == grad_emb == NULL.  b1 is not read.
+ *   gin[e, :] = gpre[e, :] . w1[g]: columns 0:24 are grad_emb[e]; grad_xs[n] = (the sum of columns 24:48 over the edges with edge_src == n, in ascending edge
+ *   id) + (the sum of columns 48:72 over the edges with edge_dst == n, in ascending edge id): a node without edges gets exact zeros.
+ *   grad_w1[g] = sum_e gpre[e]^T (x) in[e], grad_b1[g] = sum_e gpre[e]: per slice of rtp-slice-length edges (a function of E alone) a partial image, the
+ *   images added in slice order; a group without edges gets zeros.
+ * workspace: ddk_rhid_workspace(E, n_groups, n_nodes) bytes of device memory, needed when E > 0, 16-byte aligned.  Its content, in this order, every part
+ * padded to a multiple of four floats: the per-edge rows gin[:, 24:48] [E, 24]; the per-edge rows gin[:, 48:72] [E, 24]; the dst sum per node
+ * [n_nodes, 24]; the parameter images [E / slice length + n_groups][72][73] (column 72 is grad_b1's).
+ * E == 0: the grad_xs, grad_w1 and grad_b1 asked for are written as zeros, no kernel is launched.  Outputs must not alias inputs.  No atomics: the same bits
+ * from call to call, on every device, and whichever subset of the outputs is asked for. */
+int ddk_rhid_backward(ddk_ctx* ctx, const float* xs, int64_t n_nodes, const int32_t* edge_src, const int32_t* edge_dst, const int32_t* src_order,
+                      const int64_t* src_ptr, const int32_t* dst_order, const int64_t* dst_ptr, const float* emb, const float* h,
+                      const int64_t* group_offsets, int32_t n_groups, const float* w1, const float* grad_h, float p, int64_t E, float* grad_xs,
+                      float* grad_emb, float* grad_w1, float* grad_b1, void* workspace, void* stream);
+
+/* Bytes of ddk_rhid_backward's workspace: a function of its arguments alone; -1 for n_groups outside 1..4, E < 0 or E >= 2^31, n_nodes outside
+ * 0 .. 2^31 - 1.  Host function, no context. */
+int64_t ddk_rhid_workspace(int64_t E, int32_t n_groups, int64_t n_nodes);
+
 /* ---- a11: TensorProductConvLayer.forward(node_attr, edge_index, edge_attr, edge_sh)
  *      models/tensor_layers.py:147-168 for conv layer `layer`, fused: radial MLP (fp32 MFMA) +
  *      tensor product + segmented scatter-sum + mean + BatchNorm(eval) + residual, without ever

@@ -18,7 +18,13 @@ tensor_layers.fused_radial_tp (ddk_rtp_forward / ddk_rtp_backward, k_rtp.hip: th
 times one training step, forward + backward with all gradients, of the conv layer's lines 153-159 on one random graph (--nodes: default edges / 25) two
 ways: (a) tensor_layers.fused_radial_conv (ddk_rconv_forward / ddk_rconv_backward: gather inside the kernels, fixed-order mean, no atomics) and (b) the
 composition it replaces, index_select + fused_radial_tp + index_add_ / count.  The two paths alternate pass by pass; medians of --repeats passes, and the
-peak device memory of one step of each."""
+peak device memory of one step of each.
+
+    python tools/bench_tp.py --hidden [--edges 200000] [--nodes 8000] [--dropout 0.1] [--iters 10] [--json out.json]
+times one training step, forward + backward with all gradients, of the radial MLP's hidden layer from the edge embedding two ways on one random graph:
+(a) tensor_layers.fused_radial_hidden (ddk_rhid_forward / ddk_rhid_backward, k_rhid.hip: no [E, 72] row, no atomics, a counter-based dropout mask) and
+(b) the composition it replaces, the reference's cat of [edge_emb | node_attr[src, :24] | node_attr[dst, :24]] and fc[g][:4] per group.  Same options,
+alternation and medians as --conv; and the device passes of (a) on their own."""
 import argparse, json, os, sys
 import torch
 sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), '..')))
@@ -32,7 +38,9 @@ p.add_argument('--json', default=None)
 p.add_argument('--backward', action='store_true')
 p.add_argument('--radial', action='store_true')
 p.add_argument('--conv', action='store_true')
-p.add_argument('--nodes', type=int, default=None, help='--conv: nodes of the graph (default: edges / 25)')
+p.add_argument('--hidden', action='store_true')
+p.add_argument('--dropout', type=float, default=0.1, help='--hidden: the dropout rate of the FCBlocks')
+p.add_argument('--nodes', type=int, default=None, help='--conv, --hidden: nodes of the graph (default: edges / 25)')
 p.add_argument('--layers', default='0,3', help='--conv: the layer shapes to time')
 p.add_argument('--repeats', type=int, default=5)
 p.add_argument('--baseline-edges', type=int, default=None, help='edges of the torch baseline (default: --edges; a smaller count is scaled and reported)')
@@ -256,6 +264,79 @@ def bench_conv():
         json.dump(results, open(a.json, 'w'), indent=1)
 
 
+def bench_hidden():
+    from disco_diffdock_amd.tensor_layers import FCBlock, _shape_context, fused_radial_hidden
+    ctx = _shape_context(0)
+    E = a.edges
+    N = a.nodes or max(1, E // 25)
+    offs = [E * k // 4 for k in range(5)]
+    torch.manual_seed(0)
+    fc = torch.nn.ModuleList([FCBlock(72, 72, 72, 2, a.dropout) for _ in range(4)]).to(dev).train()
+    gen = torch.Generator(device=dev).manual_seed(0)
+    x, emb, g = (torch.randn(n, c, device=dev, generator=gen) for n, c in ((N, 48), (E, 24), (E, 72)))
+    ei = torch.randint(0, N, (2, E), device=dev, generator=gen)
+    graph = ctx.conv_graph(ei[0], ei[1], N, N)
+    X, EMB = x.requires_grad_(True), emb.requires_grad_(True)
+    first = [p for blk in fc for p in blk[0].parameters()]
+
+    def step(fused, seed=None):
+        for t in [X, EMB] + first:
+            t.grad = None
+        if fused:
+            h = fused_radial_hidden(fc, X, EMB, offs, graph, seed=seed)
+        else:
+            row = torch.cat([EMB, X[ei[0], :24], X[ei[1], :24]], -1)
+            h = torch.cat([fc[k][:4](row[offs[k]:offs[k + 1]]) for k in range(4)])
+        h.backward(g)
+
+    res = {'edges': E, 'nodes': N, 'dropout': a.dropout, 'one_hidden_tensor_bytes': 4 * E * 72, 'workspace_bytes': ctx.L.ddk_rhid_workspace(E, 4, N)}
+    for name, fused in (('fused_hidden', True), ('composition', False)):
+        step(fused)      # (warm-up: the allocator's blocks, the kernels' code objects)
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        live = torch.cuda.memory_allocated()
+        step(fused)
+        torch.cuda.synchronize()
+        res[name] = {'peak_bytes': torch.cuda.max_memory_allocated() - live}
+    step(True, seed=1)
+    one = [X.grad.clone(), EMB.grad.clone()] + [p.grad.clone() for p in first]
+    step(True, seed=1)
+    res['fused_hidden']['gradients_bit_identical_run_to_run'] = all(torch.equal(u, v) for u, v in zip(one, [X.grad, EMB.grad] + [p.grad for p in first]))
+    if a.dropout == 0:      # (with dropout the two paths draw different masks)
+        step(False)
+        two = [X.grad.clone(), EMB.grad.clone()] + [p.grad.clone() for p in first]
+        res['max_rel_diff_of_gradients'] = max(float((u - v).abs().max() / v.abs().max()) for u, v in zip(one, two))
+    times = {'fused_hidden': [], 'composition': []}
+    for _ in range(a.repeats):      # the two paths alternate, so that a drift of the clocks meets both
+        for name, fused in (('fused_hidden', True), ('composition', False)):
+            st, en = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            st.record()
+            for _ in range(a.iters):
+                step(fused)
+            en.record()
+            torch.cuda.synchronize()
+            times[name].append(st.elapsed_time(en) / a.iters)
+    for name, t in times.items():
+        res[name]['ms'], res[name]['ms_passes'] = sorted(t)[len(t) // 2], t
+    res['fused_over_composition_ms'] = res['fused_hidden']['ms'] / res['composition']['ms']
+    res['fused_over_composition_peak'] = res['fused_hidden']['peak_bytes'] / res['composition']['peak_bytes']
+    # the device passes on their own (no torch around them)
+    with torch.no_grad():
+        w1, b1 = torch.stack([b[0].weight for b in fc]), torch.stack([b[0].bias for b in fc])
+        xs, em = X.detach()[:, :24].contiguous(), EMB.detach()
+        h = ctx.rhid_forward(graph, xs, em, offs, w1, b1, a.dropout, 1)
+        res['kernels_ms'] = {
+            'forward': median_ms(lambda: ctx.rhid_forward(graph, xs, em, offs, w1, b1, a.dropout, 1), a.iters, a.repeats),
+            'backward_per_edge_and_node_sums': median_ms(lambda: ctx.rhid_backward(graph, xs, em, h, offs, w1, g, a.dropout, (True, True, False, False)), a.iters, a.repeats),
+            'backward_parameters': median_ms(lambda: ctx.rhid_backward(graph, xs, em, h, offs, None, g, a.dropout, (False, False, True, True)), a.iters, a.repeats)}
+    print(json.dumps(res), flush=True)
+    if a.json:
+        json.dump([res], open(a.json, 'w'), indent=1)
+
+
+if a.hidden:
+    bench_hidden()
+    sys.exit(0)
 if a.backward:
     bench_backward()
     sys.exit(0)
