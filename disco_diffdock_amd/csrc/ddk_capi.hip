@@ -416,6 +416,74 @@ int ddk_rhid_backward(ddk_ctx* ctx, const float* xs, int64_t n_nodes, const int3
 
 int64_t ddk_rhid_workspace(int64_t E, int32_t n_groups, int64_t n_nodes) { return rhid_workspace(E, n_groups, n_nodes); }
 
+// the checks the two head-conv entries share: a context that can launch, the head, the counts, and with edges the graph tables and the operands both read
+static int hconv_check(ddk_ctx* ctx, const char* who, int32_t head, int64_t E, const RconvGraph& gr, bool backward, const float* x_nodes, const float* sh,
+                       const float* h, const void* workspace) {
+  int rc = check_launchable(ctx, 0);
+  if (rc) return rc;
+  const std::string w(who);
+  const int64_t lim = (int64_t)1 << 31;
+  if (head != DDK_HEAD_CENTER && head != DDK_HEAD_TORSION) return fail(ctx, DDK_ERR_INVALID, w + ": head must be DDK_HEAD_CENTER or DDK_HEAD_TORSION");
+  if (E < 0 || E >= lim) return fail(ctx, DDK_ERR_INVALID, w + ": edge count out of range");
+  if (gr.n_in < 0 || gr.n_in >= lim || gr.n_out < 0 || gr.n_out >= lim) return fail(ctx, DDK_ERR_INVALID, w + ": node count out of range");
+  if (E == 0) return DDK_OK;
+  if (gr.n_in == 0 || gr.n_out == 0) return fail(ctx, DDK_ERR_INVALID, w + ": edges without nodes");
+  if (!gr.src || !gr.dst || !gr.src_order || !gr.src_ptr || (backward && (!gr.dst_order || !gr.dst_ptr)))
+    return fail(ctx, DDK_ERR_INVALID, w + ": null graph table (edge_src, edge_dst, the orderings and their pointer tables)");
+  if (!x_nodes || !sh || !h) return fail(ctx, DDK_ERR_INVALID, w + ": null operand");
+  if (!workspace) return fail(ctx, DDK_ERR_INVALID, w + ": null workspace (ddk_hconv_workspace bytes)");
+  if (((uintptr_t)sh | (uintptr_t)h | (uintptr_t)workspace) & 15) return fail(ctx, DDK_ERR_INVALID, w + ": sh, h and the workspace must be 16-byte aligned");
+  return DDK_OK;
+}
+
+int ddk_hconv_forward(ddk_ctx* ctx, int32_t head, const float* x_nodes, int64_t n_in, int64_t n_out, const int32_t* edge_src, const int32_t* edge_dst,
+                      const int32_t* src_order, const int64_t* src_ptr, const float* sh, const float* h, const float* w2, const float* b2, int64_t E,
+                      float* out_nodes, void* workspace, void* stream) {
+  const RconvGraph gr{n_in, n_out, edge_src, edge_dst, src_order, src_ptr, nullptr, nullptr};
+  int rc = hconv_check(ctx, "ddk_hconv_forward", head, E, gr, false, x_nodes, sh, h, workspace);
+  if (rc) return rc;
+  if (n_out > 0 && !out_nodes) return fail(ctx, DDK_ERR_INVALID, "ddk_hconv_forward: null out_nodes");
+  if (E > 0 && (!w2 || !b2)) return fail(ctx, DDK_ERR_INVALID, "ddk_hconv_forward: null w2 or b2");
+  hipError_t e = launch_hconv_forward(head, gr, x_nodes, sh, h, w2, b2, E, out_nodes, (float*)workspace, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "hconv_forward launch");
+  return DDK_OK;
+}
+
+int ddk_hconv_backward(ddk_ctx* ctx, int32_t head, const float* x_nodes, int64_t n_in, int64_t n_out, const int32_t* edge_src, const int32_t* edge_dst,
+                       const int32_t* src_order, const int64_t* src_ptr, const int32_t* dst_order, const int64_t* dst_ptr, const float* sh, const float* h,
+                       const float* w2, const float* b2, const float* grad_out_nodes, int64_t E, float* grad_x_nodes, float* grad_h, float* grad_w2,
+                       float* grad_b2, void* workspace, void* stream) {
+  const RconvGraph gr{n_in, n_out, edge_src, edge_dst, src_order, src_ptr, dst_order, dst_ptr};
+  int rc = hconv_check(ctx, "ddk_hconv_backward", head, E, gr, true, x_nodes, sh, h, workspace);
+  if (rc) return rc;
+  if (!grad_x_nodes && !grad_h && !grad_w2 && !grad_b2)
+    return fail(ctx, DDK_ERR_INVALID, "ddk_hconv_backward: no gradient requested (grad_x_nodes, grad_h, grad_w2 and grad_b2 are all null)");
+  if (E > 0) {
+    if (!grad_out_nodes) return fail(ctx, DDK_ERR_INVALID, "ddk_hconv_backward: null grad_out_nodes");
+    if ((grad_x_nodes || grad_h) && !w2)
+      return fail(ctx, DDK_ERR_INVALID, "ddk_hconv_backward: null w2 (it may be null only when grad_x_nodes and grad_h are both null)");
+    if (grad_x_nodes && !b2) return fail(ctx, DDK_ERR_INVALID, "ddk_hconv_backward: null b2 (grad_x_nodes needs w = w2 h + b2)");
+  }
+  hipError_t e = launch_hconv_backward(head, gr, x_nodes, sh, h, w2, b2, grad_out_nodes, E, grad_x_nodes, grad_h, grad_w2, grad_b2, (float*)workspace,
+                                       (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "hconv_backward launch");
+  return DDK_OK;
+}
+
+int64_t ddk_hconv_workspace(int32_t head, int64_t E, int64_t n_in, int64_t n_out, int32_t backward) { return hconv_workspace(head, E, n_in, n_out, backward); }
+
+int ddk_seg_sum(ddk_ctx* ctx, const float* rows, const int32_t* order, const int64_t* ptr, float* nodes, int64_t n_nodes, int32_t D, void* stream) {
+  int rc = check_launchable(ctx, 0);
+  if (rc) return rc;
+  if (n_nodes < 0 || n_nodes >= (int64_t)1 << 31) return fail(ctx, DDK_ERR_INVALID, "ddk_seg_sum: node count out of range");
+  if (D < 1 || D > 128) return fail(ctx, DDK_ERR_INVALID, "ddk_seg_sum: D must be in 1..128");
+  if (n_nodes == 0) return DDK_OK;
+  if (!rows || !order || !ptr || !nodes) return fail(ctx, DDK_ERR_INVALID, "ddk_seg_sum: null operand");
+  hipError_t e = launch_rtp_seg_sum(rows, order, ptr, nodes, n_nodes, D, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "seg_sum launch");
+  return DDK_OK;
+}
+
 int ddk_conv_forward(ddk_ctx* ctx, int32_t layer, const float* x, int64_t N, const int32_t* edge_src,
                      const int32_t* edge_dst, const int64_t* go, const float* edge_attr, const float* sh, float* out,
                      void* stream) {

@@ -365,4 +365,12 @@ hipError_t launch_rhid_backward(const RconvGraph& gr, const float* xs, const flo
                                 const float* w1, const float* grad_h, float p, float* grad_xs, float* grad_emb, float* grad_w1, float* grad_b1,
                                 float* workspace, hipStream_t s);
 int64_t rhid_workspace(int64_t E, int32_t n_groups, int64_t n_nodes);
+// k_hconv.hip: the two head convolutions (head 0: final_conv, 1: tor_bond_conv; include/ddk.h: ddk_hconv_forward / ddk_hconv_backward), node rows [n_in, 84]
+// to receiver rows [n_out, 12 or 48] through e3nn's FullyConnectedTensorProduct with the weights W2 h + b2 formed in the kernels; a null output is not computed
+hipError_t launch_hconv_forward(int head, const RconvGraph& gr, const float* x_nodes, const float* sh, const float* h, const float* w2, const float* b2, int64_t E,
+                                float* out_nodes, float* workspace, hipStream_t s);
+hipError_t launch_hconv_backward(int head, const RconvGraph& gr, const float* x_nodes, const float* sh, const float* h, const float* w2, const float* b2,
+                                 const float* grad_out_nodes, int64_t E, float* grad_x_nodes, float* grad_h, float* grad_w2, float* grad_b2, float* workspace,
+                                 hipStream_t s);
+int64_t hconv_workspace(int32_t head, int64_t E, int64_t n_in, int64_t n_out, int32_t backward);
 }  // namespace ddk

@@ -151,6 +151,30 @@ def tp_layer_shape(layer, ns=24, nv=6):
     return dict(A=A, P=P, Q=Q, C=C, O=O, R=R, B=B, W=B[4], din=A + 3 * P + 3 * Q + C, dout=O[0] + 3 * O[1] + 3 * O[2] + O[3])
 
 
+HEAD_CENTER, HEAD_TORSION = 0, 1      # DDK_HEAD_CENTER, DDK_HEAD_TORSION of include/ddk.h
+
+
+def head_tp_shape(head, ns=24, nv=6):
+    """e3nn's FullyConnectedTensorProduct of a score head (tensor_layers.py:137; the table of csrc/k_hconv.hip): ``final_conv`` (``HEAD_CENTER``:
+    in (x) '1x0e + 1x1o' -> '2x1o + 2x1e') or ``tor_bond_conv`` (``HEAD_TORSION``: in (x) '1x1o + 1x2e + 1x2o + 1x3o' -> 'ns x 0o + ns x 0e'), ``in`` the
+    output irreps of conv layer 3.  W: floats of a weight row, K: the radial MLP's width, din / dout: the widths of a node row and an output row, ``blocks``:
+    the weight blocks in e3nn's instruction order as (name, i_in1, i_in2, i_out, offset, (mul_in1, mul_in2, mul_out)), the indices into the three irreps
+    lists, ``out_off``: where output irrep i_out starts in the output row."""
+    if head == HEAD_CENTER:
+        paths = [('A', 0, 1, 0, ns), ('B', 1, 0, 0, nv), ('C', 1, 1, 1, nv), ('D', 2, 0, 1, nv), ('E', 2, 1, 0, nv), ('F', 3, 1, 1, ns)]
+        mulo, K, dout, out_off = 2, 2 * ns, 12, (0, 6)
+    elif head == HEAD_TORSION:
+        paths = [('P', 1, 0, 1, nv), ('Q', 2, 0, 0, nv)]
+        mulo, K, dout, out_off = ns, 3 * ns, 2 * ns, (0, ns)
+    else:
+        raise RuntimeError(f'ddk: head must be HEAD_CENTER (0) or HEAD_TORSION (1); got {head!r}')
+    blocks, off = [], 0
+    for name, i1, i2, io, mul1 in paths:
+        blocks.append((name, i1, i2, io, off, (mul1, 1, mulo)))
+        off += mul1 * mulo
+    return dict(W=off, K=K, din=2 * ns + 6 * nv, dout=dout, blocks=blocks, out_off=out_off)
+
+
 class ConvGraph:
     """The graph of the radial conv, made and checked by ``Context.conv_graph``: ``src`` / ``dst`` int32 [E]; ``src_order`` / ``dst_order`` int32 [E], the
     edge ids sorted by node, ascending within a node; ``src_ptr`` [n_out + 1] / ``dst_ptr`` [n_in + 1] int64, node n owns order[ptr[n] : ptr[n + 1]];
@@ -477,6 +501,94 @@ class Context:
         if nbytes < 0:
             raise RuntimeError(f'ddk: no radial-conv workspace for layer {layer}, E = {graph.E}, {G} groups, {graph.n_in} -> {graph.n_out} nodes')
         return torch.empty(max(int(nbytes), 4) // 4, dtype=torch.float32, device=device)
+
+    # ---- the head convolutions: node features to receiver rows ------------------------------------------
+    def _hconv_operands(self, head, graph, x, sh, h, w2, b2):
+        """checked operands of a head conv: (shape, x, sh, h, w2, b2)"""
+        s = head_tp_shape(head)
+        if not isinstance(graph, ConvGraph):
+            raise RuntimeError('ddk: the head conv takes a ConvGraph (Context.conv_graph): its kernels trust the indices')
+        x, sh, h = (_need_cuda(t).contiguous().float() for t in (x, sh, h))
+        if x.shape != (graph.n_in, s['din']):
+            raise RuntimeError(f'ddk: the head conv takes x [n_in, {s["din"]}] for a graph of {graph.n_in} input nodes; got {tuple(x.shape)}')
+        if sh.shape != (graph.E, 4) or h.shape != (graph.E, s['K']):
+            raise RuntimeError(f'ddk: the head conv takes sh [E, 4] and h [E, {s["K"]}] for a graph of {graph.E} edges; got {tuple(sh.shape)} and {tuple(h.shape)}')
+        if graph.src.device != x.device or sh.device != x.device or h.device != x.device:
+            raise RuntimeError('ddk: the head conv takes a ConvGraph, sh and h on the device of x')
+        if w2 is not None:
+            w2 = _need_cuda(w2).contiguous().float()
+            if w2.shape != (s['W'], s['K']) or w2.device != x.device:
+                raise RuntimeError(f'ddk: the head conv takes w2 [W, K] = {(s["W"], s["K"])} on the device of x; got {tuple(w2.shape)}')
+        if b2 is not None:
+            b2 = _need_cuda(b2).contiguous().float()
+            if b2.shape != (s['W'],) or b2.device != x.device:
+                raise RuntimeError(f'ddk: the head conv takes b2 [W] = {(s["W"],)} on the device of x; got {tuple(b2.shape)}')
+        return s, x, sh, h, w2, b2
+
+    def _hconv_workspace(self, head, graph, backward, device):
+        nbytes = self.L.ddk_hconv_workspace(head, graph.E, graph.n_in, graph.n_out, int(backward))
+        if nbytes < 0:
+            raise RuntimeError(f'ddk: no head-conv workspace for head {head}, E = {graph.E}, {graph.n_in} -> {graph.n_out} nodes')
+        return torch.empty(max(int(nbytes), 4) // 4, dtype=torch.float32, device=device)
+
+    def hconv_forward(self, head, graph, x, sh, h, w2, b2):
+        """A head conv (ddk_hconv_forward): out [n_out, dout] = the mean over ``graph.src`` of e3nn's FullyConnectedTensorProduct of ``head_tp_shape(head)``
+        on (x[graph.dst], sh, w2 h + b2); the per-edge weights and the gathered rows are never stored, the mean is a fixed-order sum (no atomics).  For
+        ``HEAD_TORSION`` ``sh[:, 1:4]`` is the 1o block of the full tensor product of the edge's and the bond's spherical harmonics."""
+        s, x, sh, h, w2, b2 = self._hconv_operands(head, graph, x, sh, h, w2, b2)
+        if w2 is None or b2 is None:
+            raise RuntimeError('ddk: hconv_forward needs w2 and b2')
+        g = graph
+        out = torch.empty((g.n_out, s['dout']), dtype=torch.float32, device=x.device)
+        if out.numel() == 0:
+            return out
+        ws = self._hconv_workspace(head, g, False, x.device)
+        self._check(self.L.ddk_hconv_forward(self.h, head, _ptr(x), g.n_in, g.n_out, _ptr(g.src), _ptr(g.dst), _ptr(g.src_order), _ptr(g.src_ptr), _ptr(sh),
+                                             _ptr(h), _ptr(w2), _ptr(b2), g.E, _ptr(out), _ptr(ws), _stream()), 'ddk_hconv_forward')
+        return out
+
+    def hconv_backward(self, head, graph, x, sh, h, w2, b2, grad_out, need=(True, True, True, True)):
+        """The vector-Jacobian product of ``hconv_forward`` (ddk_hconv_backward): (grad_x [n_in, din], grad_h [E, K], grad_w2 [W, K], grad_b2 [W]), None
+        where ``need`` is false.  ``w2`` may be None when neither grad_x nor grad_h is asked for, ``b2`` unless grad_x is.  There is no grad_sh.  The same
+        bits from call to call.  The workspace comes from torch's allocator and is released on return."""
+        need = tuple(bool(n) for n in need)
+        if len(need) != 4 or not any(need):
+            raise RuntimeError('ddk: hconv_backward needs at least one of its four gradients to compute')
+        if w2 is None and any(need[:2]):
+            raise RuntimeError('ddk: hconv_backward needs w2 for grad_x and grad_h')
+        if b2 is None and need[0]:
+            raise RuntimeError('ddk: hconv_backward needs b2 for grad_x')
+        s, x, sh, h, w2, b2 = self._hconv_operands(head, graph, x, sh, h, w2, b2)
+        g = graph
+        grad_out = _need_cuda(grad_out).contiguous().float()
+        if grad_out.shape != (g.n_out, s['dout']) or grad_out.device != x.device:
+            raise RuntimeError(f'ddk: hconv_backward takes grad_out [n_out, {s["dout"]}] on the device of x')
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x.device)
+        outs = [new(g.n_in, s['din']) if need[0] else None, new(g.E, s['K']) if need[1] else None, new(s['W'], s['K']) if need[2] else None,
+                new(s['W']) if need[3] else None]
+        if not any(o is not None and o.numel() for o in outs):      # (empty tensors have no address: the entry would see no output at all)
+            return tuple(outs)
+        ws = self._hconv_workspace(head, g, True, x.device)
+        self._check(self.L.ddk_hconv_backward(self.h, head, _ptr(x), g.n_in, g.n_out, _ptr(g.src), _ptr(g.dst), _ptr(g.src_order), _ptr(g.src_ptr),
+                                              _ptr(g.dst_order), _ptr(g.dst_ptr), _ptr(sh), _ptr(h), _ptr(w2), _ptr(b2), _ptr(grad_out), g.E,
+                                              *[_ptr(o) for o in outs], _ptr(ws), _stream()), 'ddk_hconv_backward')
+        return tuple(outs)      # (ws goes back to torch's allocator, which orders its reuse after these launches on the current stream)
+
+    def seg_sum(self, rows, order, ptr):
+        """The fixed-order segmented sum (ddk_seg_sum): nodes [N, D] with nodes[n] = the rows ``order[ptr[n] : ptr[n + 1]]`` of ``rows`` [E, D] added in
+        that order; a node without rows gets zeros.  ``order`` int32, ``ptr`` int64 [N + 1]: a node-sorted list as ``ConvGraph`` holds them (trusted).
+        More than 128 columns are summed 128 at a time."""
+        rows = _need_cuda(rows).contiguous().float()
+        N, D = ptr.shape[0] - 1, rows.shape[1]
+        if rows.dim() != 2 or order.dtype != torch.int32 or ptr.dtype != torch.int64 or order.device != rows.device or ptr.device != rows.device:
+            raise RuntimeError('ddk: seg_sum takes rows [E, D], an int32 order and an int64 ptr [N + 1] on the device of rows')
+        if rows.shape[0] == 0 or N == 0 or D == 0:
+            return torch.zeros((N, D), dtype=torch.float32, device=rows.device)
+        if D > 128:
+            return torch.cat([self.seg_sum(rows[:, c:c + 128], order, ptr) for c in range(0, D, 128)], dim=1)
+        nodes = torch.empty((N, D), dtype=torch.float32, device=rows.device)
+        self._check(self.L.ddk_seg_sum(self.h, _ptr(rows), _ptr(order), _ptr(ptr), _ptr(nodes), N, D, _stream()), 'ddk_seg_sum')
+        return nodes
 
     # ---- the radial MLP's hidden layer from the edge embedding and the node table ---------------------
     def _rhid_operands(self, graph, xs, emb, group_offsets, w1, b1, p):

@@ -15,15 +15,19 @@ parity tests read like tests of the reference modules:
   (score_model.py:227-230) and ``fc[g][:4]`` as one differentiable op from the edge embedding [E, ns]: no [E, 72] row, no
   atomics, a counter-based dropout mask
 * ``TensorProductConvLayer.forward_embedded(...)`` and ``conv_stack(conv_layers, ...)``: one step of that loop, and the loop
+* ``fused_head_conv(head, fc, node_attr, edge_index, edge_sh, edge_attr, out_nodes, graph=None, hidden=None)``: lines 153-159 for the two score
+  heads (final_conv, tor_bond_conv: ``faster=False``, e3nn's FullyConnectedTensorProduct, one FCBlock) as one differentiable op, no atomics
+* ``gather_rows(x, index, graph=None, side='dst')``: a gather whose backward is a fixed-order segmented sum
 
-Only the configuration the shipped score models use is implemented on the device (ns=24, nv=6, sh_lmax=1,
-faster=True, edge_groups=4, residual=True, 2-layer ReLU radial MLP); anything else raises.
+Only the configurations the shipped score models use are implemented on the device (ns=24, nv=6, sh_lmax=1, 2-layer ReLU radial MLP): the conv layers
+(faster=True, edge_groups=4, residual=True) and the two heads (faster=False, edge_groups=1, residual=False); anything else raises.
 
 ``TensorProductConvLayer`` trains: in ``.train()`` its forward is ``fused_radial_conv``, e3nn's BatchNorm on the batch
 statistics (plain torch, ``_BatchNormParams.forward``) and the padded residual.  In ``.eval()`` it is the fused inference
 kernel (``ddk_conv_forward``), unchanged.  ``conv_stack`` trains the whole stack of them from the edge embedding with the
-same bits on every run.  What still does not train: the heads, ``ddk_score_forward`` end to end, the all-atom / confidence
-irreps, any other ns / nv.
+same bits on every run.  In a head configuration the layer is ``fused_head_conv`` plus BatchNorm in training and in evaluation
+(``heads.ScoreHeads`` is the module on top).  What still does not train: ``ddk_score_forward`` end to end, the all-atom /
+confidence irreps, any other ns / nv.
 """
 import math
 
@@ -31,7 +35,7 @@ import torch
 from torch import nn
 from torch.autograd.function import once_differentiable
 
-from .runtime import Context, tp_layer_shape
+from .runtime import HEAD_CENTER, HEAD_TORSION, Context, head_tp_shape, tp_layer_shape
 
 _ORDER = ('0e', '1o', '1e', '0o')
 _DIM = {'0e': 1, '1o': 3, '1e': 3, '0o': 1}
@@ -54,6 +58,22 @@ def parse_irreps(irreps):
     if seen != [k for k in _ORDER if k in seen]:
         raise RuntimeError(f'ddk: irreps {irreps!r} are not in 0e,1o,1e,0o order')
     return muls
+
+
+def _irreps_list(irreps):
+    """'24x0o + 24x0e' -> [(24, '0o'), (24, '0e')]: the (mul, irrep) pairs in the order written, entries of multiplicity 0 left out"""
+    out = []
+    for chunk in str(irreps).split('+'):
+        chunk = chunk.strip()
+        if not chunk:
+            continue
+        mul, ir = chunk.split('x') if 'x' in chunk else ('1', chunk)
+        ir = ir.strip()
+        if ir not in _DIM:
+            raise RuntimeError(f'ddk: unsupported irrep {ir!r} (sh_lmax=1 first-order model only)')
+        if int(mul):
+            out.append((int(mul), ir))
+    return out
 
 
 def irrep_to_size(irreps):
@@ -362,6 +382,113 @@ def conv_stack(conv_layers, node_attr, edge_index, edge_emb, group_sizes, edge_s
     return node_attr
 
 
+class _HeadConvFunction(torch.autograd.Function):
+    """ddk_hconv_forward with ddk_hconv_backward as its vector-Jacobian product: node features to receiver rows through a head's
+    FullyConnectedTensorProduct.  Saved for the backward: the node table, sh, h, the graph, and w2 / b2 where a requested gradient reads them; never the
+    gathered rows, the tensor product's rows or the per-edge weights.  No atomics: the gradients have the same bits on every run.  sh gets no gradient."""
+
+    @staticmethod
+    def forward(fctx, node_attr, sh, h, w2, b2, head, graph):
+        ctx = _shape_context(node_attr.device.index or 0)
+        x, s, hh = _as_rows(node_attr, node_attr.shape[-1]), _as_rows(sh, 4), _as_rows(h, h.shape[-1])
+        w, b = w2.contiguous().float(), b2.contiguous().float()
+        out = ctx.hconv_forward(head, graph, x, s, hh, w, b)
+        ng = fctx.needs_input_grad
+        fctx.save_for_backward(x, s, hh, w if (ng[0] or ng[2]) else None, b if ng[0] else None)      # the parameter gradients read neither
+        fctx.head, fctx.ddk, fctx.graph = head, ctx, graph
+        fctx.meta = [(t.shape, t.dtype) for t in (node_attr, h, w2, b2)]
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(fctx, grad_out):
+        x, s, hh, w, b = fctx.saved_tensors
+        ng = fctx.needs_input_grad
+        need = (ng[0], ng[2], ng[3], ng[4])
+        g = grad_out.reshape(-1, grad_out.shape[-1]).contiguous().float()
+        with torch.cuda.device(x.device):
+            gx, gh, gw2, gb2 = _grads_like(fctx.ddk.hconv_backward(fctx.head, fctx.graph, x, s, hh, w, b, g, need), fctx.meta)
+        return gx, None, gh, gw2, gb2, None, None
+
+
+def fused_head_conv(head, fc, node_attr, edge_index, edge_sh, edge_attr, out_nodes, graph=None, hidden=None):
+    """Lines 153-159 of the reference's TensorProductConvLayer.forward (models/tensor_layers.py) for a score head, ``faster=False, edge_groups=1,
+    reduce='mean'``, as one differentiable op: ``scatter(o3.FullyConnectedTensorProduct(...)(node_attr[edge_dst], edge_sh, fc(edge_attr)), edge_src,
+    dim_size=out_nodes, reduce='mean')``.  ``head``: ``runtime.HEAD_CENTER`` (final_conv) or ``runtime.HEAD_TORSION`` (tor_bond_conv); ``fc``: ONE FCBlock
+    whose Linears are K -> K and K -> W of ``runtime.head_tp_shape(head)``.  ``fc[:4]`` (Linear, ReLU, Dropout) runs in torch unless ``hidden`` [E, K] is
+    given; the last Linear, the gather, the tensor product and the mean run in the kernels of csrc/k_hconv.hip, forward and backward: no [E, W] weights,
+    no gathered rows, no atomics, so ``node_attr``, ``edge_attr`` and every parameter of ``fc`` get the same gradient bits on every run.  ``edge_sh``
+    [E, 4]: (1x0e, 1x1o) for the centre head; (anything, T) for the torsion head, T the 1o block of ``FullTensorProduct(sh_irreps, '2e')``.  It gets
+    no gradient (positions carry none in score matching): an ``edge_sh`` that requires one raises.  ``graph``: the ``ConvGraph`` of ``edge_index`` from
+    ``node_attr``'s rows to ``out_nodes`` receivers, built here otherwise.  [out_nodes, dout], fp32."""
+    s = head_tp_shape(head)
+    K, W = s['K'], s['W']
+    if (not isinstance(fc, nn.Sequential) or len(fc) != 5 or not isinstance(fc[0], nn.Linear) or not isinstance(fc[4], nn.Linear)
+            or (fc[0].in_features, fc[0].out_features) != (K, K) or (fc[4].in_features, fc[4].out_features) != (K, W) or fc[4].bias is None):
+        raise RuntimeError(f'ddk: fused_head_conv takes one 2-layer FCBlock whose Linears map {K} -> {K} and {K} -> {W} (edge_groups == 1)')
+    if not node_attr.is_cuda:
+        raise RuntimeError('ddk fused_head_conv runs on the GPU only (no CPU fallback)')
+    if edge_sh.requires_grad:
+        raise RuntimeError('ddk: fused_head_conv has no gradient for edge_sh (positions carry none in score matching); detach it')
+    if node_attr.dim() != 2 or node_attr.shape[1] != s['din']:
+        raise RuntimeError(f'ddk: fused_head_conv takes node_attr [N, {s["din"]}], the output of conv layer 3; got {tuple(node_attr.shape)}')
+    n_out = int(out_nodes)
+    if graph is None:
+        graph = Context.conv_graph(edge_index[0], edge_index[1], node_attr.shape[0], n_out)
+    if graph.n_in != node_attr.shape[0] or graph.n_out != n_out:
+        raise RuntimeError(f'ddk: fused_head_conv: the graph ({graph.n_in} -> {graph.n_out} nodes) does not fit {node_attr.shape[0]} -> {n_out} nodes')
+    if hidden is None:
+        hidden = fc[:4](edge_attr)
+    if hidden.dim() != 2 or hidden.shape != (graph.E, K) or edge_sh.shape != (graph.E, 4):
+        raise RuntimeError(f'ddk: fused_head_conv takes edge_sh [E, 4] and a hidden activation [E, {K}] with E = {graph.E}, the edges of the graph; got '
+                           f'{tuple(edge_sh.shape)} and {tuple(hidden.shape)}')
+    w2, b2 = fc[4].weight, fc[4].bias
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (node_attr, hidden, w2, b2)):
+        return _HeadConvFunction.apply(node_attr, edge_sh, hidden, w2, b2, head, graph)
+    return _shape_context(node_attr.device.index or 0).hconv_forward(head, graph, node_attr, edge_sh, hidden, w2, b2)
+
+
+class _GatherRowsFunction(torch.autograd.Function):
+    """x[index] whose backward adds the rows of a node in ascending position (ddk_seg_sum over the node-sorted list), not with index_add_'s atomics."""
+
+    @staticmethod
+    def forward(fctx, x, index, order, ptr):
+        fctx.save_for_backward(order, ptr)
+        fctx.meta = (x.shape, x.dtype)
+        return x.index_select(0, index)
+
+    @staticmethod
+    @once_differentiable
+    def backward(fctx, grad):
+        order, ptr = fctx.saved_tensors
+        shape, dtype = fctx.meta
+        with torch.cuda.device(grad.device):
+            nodes = _shape_context(grad.device.index or 0).seg_sum(grad.reshape(grad.shape[0], -1), order, ptr)
+        return nodes.reshape(shape).to(dtype), None, None, None
+
+
+def gather_rows(x, index, graph=None, side='dst'):
+    """``x[index]`` ([E, ...] rows of the node table ``x``) with a run-to-run reproducible backward: the gradient rows of a node are added in ascending
+    position from a node-sorted list, where ``index_select``'s backward is ``index_add_`` with float atomics.  ``graph``: a ``ConvGraph`` whose
+    ``side`` ('dst' or 'src') IS ``index`` over ``x``'s rows, so that its sorted list is reused; without it the list is made here (one stable sort).
+    The backward is the device's segmented sum (``Context.seg_sum``): GPU tensors only."""
+    if not x.is_cuda:
+        raise RuntimeError('ddk gather_rows runs on the GPU only (no CPU fallback)')
+    index = index.long()
+    if graph is not None:
+        order, ptr = (graph.dst_order, graph.dst_ptr) if side == 'dst' else (graph.src_order, graph.src_ptr)
+        if order.shape[0] != index.shape[0] or ptr.shape[0] != x.shape[0] + 1:
+            raise RuntimeError(f'ddk: gather_rows: the graph\'s {side} side ({order.shape[0]} edges, {ptr.shape[0] - 1} nodes) does not fit '
+                               f'{index.shape[0]} indices into {x.shape[0]} rows')
+    else:
+        order = torch.sort(index, stable=True).indices.to(torch.int32)
+        ptr = torch.zeros(x.shape[0] + 1, dtype=torch.int64, device=index.device)
+        ptr[1:] = torch.cumsum(torch.bincount(index, minlength=x.shape[0])[:x.shape[0]], 0)
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _GatherRowsFunction.apply(x, index, order, ptr)
+    return x.index_select(0, index)
+
+
 def FCBlock(in_dim, hidden_dim, out_dim, layers, dropout, activation='relu', batchnorm=False):
     """Same Sequential layout (indices 0 and 4 hold the Linears) as the reference models/layers.py:15-22."""
     if layers != 2 or activation != 'relu' or batchnorm:
@@ -374,13 +501,13 @@ class _BatchNormParams(nn.Module):
 
     def __init__(self, irreps):
         super().__init__()
-        m = parse_irreps(irreps)
-        nf, nsc = sum(m.values()), m['0e']
+        listed = _irreps_list(irreps)      # in the order written: the torsion head's '24x0o + 24x0e' puts its scalars second
+        nf, nsc = sum(mul for mul, _ in listed), sum(mul for mul, ir in listed if ir == '0e')
         self.register_buffer('running_mean', torch.zeros(nsc))
         self.register_buffer('running_var', torch.ones(nf))
         self.weight = nn.Parameter(torch.ones(nf))
         self.bias = nn.Parameter(torch.zeros(nsc))
-        self.blocks = [(m[k], _DIM[k], k == '0e') for k in _ORDER if m[k]]      # (mul, d, scalar): 0o is not a scalar for e3nn (no mean, no bias)
+        self.blocks = [(mul, _DIM[ir], ir == '0e') for mul, ir in listed]      # (mul, d, scalar): 0o is not a scalar for e3nn (no mean, no bias)
         self.eps, self.momentum = 1e-5, 0.1
 
     def forward(self, x):
@@ -417,6 +544,16 @@ class TensorProductConvLayer(nn.Module):
     def __init__(self, in_irreps, sh_irreps, out_irreps, n_edge_features, residual=True, batch_norm=True, dropout=0.0,
                  hidden_features=None, faster=False, edge_groups=1, tp_weights_layers=2, activation='relu'):
         super().__init__()
+        self.head = self._head_configuration(in_irreps, sh_irreps, out_irreps, n_edge_features, residual, hidden_features, faster, edge_groups,
+                                             tp_weights_layers, activation)
+        if self.head is not None:
+            # final_conv / tor_bond_conv (models/score_model.py:132-161): e3nn's FullyConnectedTensorProduct, one FCBlock, no residual
+            s = head_tp_shape(self.head)
+            self.in_irreps, self.out_irreps, self.sh_irreps = str(in_irreps), str(out_irreps), sh_irreps
+            self.residual, self.edge_groups, self.out_size = residual, edge_groups, s['dout']
+            self.fc = FCBlock(n_edge_features, s['K'], s['W'], tp_weights_layers, dropout, activation)      # a plain FCBlock: keys fc.0.weight, fc.4.bias
+            self.batch_norm = _BatchNormParams(out_irreps) if batch_norm else None
+            return
         if not faster or edge_groups != 4 or not residual:
             raise RuntimeError('ddk: the fused kernel implements faster=True, edge_groups=4, residual=True conv layers')
         self.in_irreps, self.out_irreps, self.sh_irreps = str(in_irreps), str(out_irreps), sh_irreps
@@ -432,6 +569,42 @@ class TensorProductConvLayer(nn.Module):
         self.batch_norm = _BatchNormParams(out_irreps) if batch_norm else None
         self._ctx, self._ctx_key = None, None
 
+    @staticmethod
+    def _head_configuration(in_irreps, sh_irreps, out_irreps, n_edge_features, residual, hidden_features, faster, edge_groups, tp_weights_layers,
+                            activation):
+        """HEAD_CENTER / HEAD_TORSION when the arguments are those models/score_model.py:132-161 passes to final_conv / tor_bond_conv, else None"""
+        if faster or edge_groups != 1 or residual or tp_weights_layers != 2 or activation != 'relu':
+            return None
+        try:
+            if tuple(parse_irreps(in_irreps).values()) != (24, 6, 6, 24):
+                return None
+            out = _irreps_list(out_irreps)
+        except (RuntimeError, ValueError):
+            return None
+        sh = str(sh_irreps).replace(' ', '').split('+')
+        # the torsion head's sh irreps: the 1o block first (the only one with a path to a scalar), then 2e, 2o, 3o in the order the caller's sort gives
+        for head, sh_want, out_want in ((HEAD_CENTER, ['1x0e', '1x1o'], [(2, '1o'), (2, '1e')]),
+                                        (HEAD_TORSION, ['1x1o', '1x2e', '1x2o', '1x3o'], [(24, '0o'), (24, '0e')])):
+            K = head_tp_shape(head)['K']
+            if sh[0] == sh_want[0] and sorted(sh) == sh_want and out == out_want and n_edge_features == K and hidden_features in (None, K):
+                return head
+        return None
+
+    def _forward_head(self, node_attr, edge_index, edge_attr, edge_sh, out_nodes, reduce, graph=None):
+        """The reference's forward (models/tensor_layers.py:147-168) of a head: fused_head_conv, then BatchNorm (batch statistics in training, the running
+        buffers in evaluation), no residual.  Training and evaluation run the same kernels.  The torsion head takes ``edge_sh`` as the reference passes it,
+        [E, 20] = FullTensorProduct(sh_irreps, '2e') whose first three columns are the 1o block, or as the op does, [E, 4] = (anything, 1o block)."""
+        if reduce != 'mean':
+            raise RuntimeError("ddk: conv layers aggregate with reduce='mean'")
+        if not node_attr.is_cuda:
+            raise RuntimeError('ddk TensorProductConvLayer runs on the GPU only (no CPU fallback)')
+        if edge_index.shape[1] == 0:      # (as there: zeros on all nodes, no BatchNorm)
+            return torch.zeros((node_attr.shape[0], self.out_size), dtype=node_attr.dtype, device=node_attr.device)
+        if self.head == HEAD_TORSION and edge_sh.shape[-1] == 20:
+            edge_sh = torch.nn.functional.pad(edge_sh[:, :3], (1, 0))
+        out = fused_head_conv(self.head, self.fc, node_attr, edge_index, edge_sh, edge_attr, int(out_nodes or node_attr.shape[0]), graph=graph)
+        return self.batch_norm(out) if self.batch_norm is not None else out
+
     def _context(self, device):
         key = (device.index or 0, tuple(int(p._version) for p in self.state_dict().values()))
         if self._ctx is None or self._ctx_key != key:
@@ -441,6 +614,8 @@ class TensorProductConvLayer(nn.Module):
         return self._ctx
 
     def forward(self, node_attr, edge_index, edge_attr, edge_sh, out_nodes=None, reduce='mean'):
+        if self.head is not None:
+            return self._forward_head(node_attr, edge_index, edge_attr, edge_sh, out_nodes, reduce)
         if self.training:
             return self._forward_training(node_attr, edge_index, edge_attr, edge_sh, out_nodes, reduce)
         if reduce != 'mean' or (out_nodes is not None and out_nodes != node_attr.shape[0]):
@@ -476,6 +651,8 @@ class TensorProductConvLayer(nn.Module):
         training the row [E, 72] is never built: ``fused_radial_hidden`` -> ``fused_radial_conv(hidden=...)`` -> BatchNorm -> residual, without
         atomics.  ``graph``: the ``ConvGraph`` of ``edge_index`` over the nodes, built here otherwise; ``seed``: of the dropout mask
         (``fused_radial_hidden``).  In evaluation the cat is built and ``forward`` runs the inference kernel, unchanged."""
+        if self.head is not None:
+            raise RuntimeError('ddk: forward_embedded is a step of the conv stack; a head layer has forward alone')
         sizes = [int(n) for n in group_sizes]
         E = edge_index.shape[1]
         if len(sizes) != self.edge_groups or any(n < 0 for n in sizes) or sum(sizes) != E or edge_emb.shape[0] != E:

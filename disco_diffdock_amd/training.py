@@ -78,6 +78,37 @@ def noise_complex(model, c, t, B, seed, draw=0, sample_offset=0, cx=None, so3_ro
     return pos, Targets(p.tr_score, p.rot_score, tor_score, tr_sigma, rot_sigma, tor_sigma, float(t), p.tr_update, p.rot_update, p.tor_update)
 
 
+class _ScoreMatchingLoss(torch.autograd.Function):
+    """ddk_score_matching_loss for predictions that ask for a gradient: the forward is the kernel, the backward the derivative of its three loss columns
+    (the base columns do not depend on the predictions), written out element-wise: plain torch without reductions, so the same bits on every run.
+      tr_loss[b] = mean_k (tr_pred - tr_score)^2 tr_sigma^2      rot_loss[b] = mean_k ((rot_pred - rot_score) / so3_norm)^2
+      tor_loss[b] = sum_r (tor_pred - tor_score)^2 / torus_norm2 / (n_rot + 1e-4)"""
+
+    @staticmethod
+    def forward(fctx, ctx, tr_pred, rot_pred, tor_pred, tr_score, rot_score, tor_score, tr_sigma, so3_norm, torus_norm2):
+        fctx.save_for_backward(tr_pred, rot_pred, tor_pred, tr_score, rot_score, tor_score)
+        fctx.scalars = (float(tr_sigma), float(so3_norm), float(torus_norm2))
+        return ctx.score_matching_loss(tr_pred, rot_pred, tor_pred, tr_score, rot_score, tor_score, tr_sigma, so3_norm, torus_norm2)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, g):
+        tr_pred, rot_pred, tor_pred, tr_score, rot_score, tor_score = fctx.saved_tensors
+        tr_sigma, so3_norm, torus_norm2 = fctx.scalars
+        B = g.shape[0]
+        like = lambda d, p: d.reshape(p.shape).to(p.dtype)
+        g_tr = g_rot = g_tor = None
+        if fctx.needs_input_grad[1]:
+            g_tr = like((tr_pred.reshape(B, 3).float() - tr_score.reshape(B, 3).float()) * (2.0 * tr_sigma * tr_sigma / 3.0) * g[:, 0:1], tr_pred)
+        if fctx.needs_input_grad[2]:
+            g_rot = like((rot_pred.reshape(B, 3).float() - rot_score.reshape(B, 3).float()) * (2.0 / (so3_norm * so3_norm * 3.0)) * g[:, 1:2], rot_pred)
+        if tor_pred is not None and fctx.needs_input_grad[3]:
+            n_rot = tor_score.numel() // max(B, 1)
+            d = tor_pred.reshape(B, n_rot).float() - tor_score.reshape(B, n_rot).float()
+            g_tor = like(d * (2.0 / (torus_norm2 * (n_rot + 1e-4))) * g[:, 2:3], tor_pred)
+        return None, g_tr, g_rot, g_tor, None, None, None, None, None, None
+
+
 def loss_function(tr_pred, rot_pred, tor_pred, targets, model, apply_mean=True, tr_weight=1, rot_weight=1, tor_weight=1):
     """utils/training.py:14-61 for one batch of ``noise_complex``: the 7-tuple (loss, tr_loss, rot_loss, tor_loss, tr_base_loss, rot_base_loss,
     tor_base_loss) of device tensors, [B] each with ``apply_mean=False`` and [1] (the reference's shapes: 0-d for tr / rot) with it.  The score norms
@@ -88,8 +119,12 @@ def loss_function(tr_pred, rot_pred, tor_pred, targets, model, apply_mean=True, 
     so3_norm = float(np.float32(so3_tab[int(so3_eps_index(targets.rot_sigma))]))
     torus_norm2 = float(np.float32(torus_tab[int(torus_sigma_index(targets.tor_sigma))]))
     no_tor = targets.tor_score is None or tor_pred is None or targets.tor_score.numel() == 0
-    per = ctx.score_matching_loss(tr_pred, rot_pred, None if no_tor else tor_pred, targets.tr_score, targets.rot_score,
-                                  None if no_tor else targets.tor_score, targets.tr_sigma, so3_norm, torus_norm2)
+    args = (tr_pred, rot_pred, None if no_tor else tor_pred, targets.tr_score, targets.rot_score, None if no_tor else targets.tor_score, targets.tr_sigma,
+            so3_norm, torus_norm2)
+    if torch.is_grad_enabled() and any(torch.is_tensor(p) and p.requires_grad for p in args[:3]):      # training: the same kernel, with a backward
+        per = _ScoreMatchingLoss.apply(ctx, *args)
+    else:
+        per = ctx.score_matching_loss(*args)
     cols = [per[:, k] for k in range(len(LOSS_COLUMNS))]
     if apply_mean:
         B = per.shape[0]

@@ -218,6 +218,48 @@ int ddk_rhid_backward(ddk_ctx* ctx, const float* xs, int64_t n_nodes, const int3
  * 0 .. 2^31 - 1.  Host function, no context. */
 int64_t ddk_rhid_workspace(int64_t E, int32_t n_groups, int64_t n_nodes);
 
+/* ---- The head convolutions of the score model, node features to receiver rows: lines 153-159 of TensorProductConvLayer.forward (models/tensor_layers.py) for
+ *      final_conv (head DDK_HEAD_CENTER) and tor_bond_conv (head DDK_HEAD_TORSION), both faster=False (e3nn's FullyConnectedTensorProduct), edge_groups=1,
+ *      reduce='mean':
+ *        out_nodes[r] = (sum over the edges e with edge_src[e] == r, in ascending e, of TP_head(x_nodes[edge_dst[e]], sh[e], w2 h[e] + b2)) / max(count, 1)
+ *      x_nodes [n_in, 84] = [24x0e | 6x1o | 6x1e | 24x0o] (the output irreps of conv layer 3); sh [E, 4]; h [E, K] the radial MLP's hidden activation;
+ *      w2 [W, K], b2 [W] its last Linear, in e3nn's instruction order.
+ *        centre:  sh = (1x0e, 1x1o) of the edge, W = 144, K = 48, out_nodes [n_out, 12] = [2x1o | 2x1e].
+ *        torsion: sh[e, 1:4] = the 1o block of FullTensorProduct(sh(edge), sh_2e(bond axis)) (sh[e, 0] is not read), W = 288, K = 72,
+ *                 out_nodes [n_out, 48] = [24x0o | 24x0e].
+ *      The graph tables are those of ddk_rconv_forward, and TRUSTED in the same way.  DEVICE pointers, fp32, contiguous; sh, h and the workspace 16-byte
+ *      aligned.  workspace: ddk_hconv_workspace(head, E, n_in, n_out, 0) bytes: the [E, Dout] rows of the tensor product.  Never stored: the per-edge weights
+ *      [E, W], the gathered rows [E, 84].  E == 0: out_nodes is written as zeros, no kernel is launched.  A receiver without edges: exact zeros.  No
+ *      allocation, no synchronisation, no atomics: the same bits from call to call. */
+#define DDK_HEAD_CENTER 0
+#define DDK_HEAD_TORSION 1
+int ddk_hconv_forward(ddk_ctx* ctx, int32_t head, const float* x_nodes, int64_t n_in, int64_t n_out, const int32_t* edge_src, const int32_t* edge_dst,
+                      const int32_t* src_order, const int64_t* src_ptr, const float* sh, const float* h, const float* w2, const float* b2, int64_t E,
+                      float* out_nodes, void* workspace, void* stream);
+
+/* VJP of ddk_hconv_forward.  The same operands, dst_order / dst_ptr as ddk_rconv_backward, grad_out_nodes [n_out, Dout].  grad_x_nodes [n_in, 84],
+ * grad_h [E, K], grad_w2 [W, K], grad_b2 [W]: each may be NULL (not computed); all four NULL is DDK_ERR_INVALID.  There is no grad_sh.  w2 may be NULL iff
+ * grad_x_nodes == grad_h == NULL; b2 is read for grad_x_nodes alone.  workspace: ddk_hconv_workspace(head, E, n_in, n_out, 1) bytes, needed when E > 0: the
+ * per-edge rows of grad_x [E, 84] (added per node in ascending edge id) and the parameter images [E / slice length + 1][W][K + 1] (one per slice of
+ * rtp-slice-length edges, a function of E alone, added in slice order).  E == 0: the grad_x_nodes, grad_w2 and grad_b2 asked for are written as zeros.  A node
+ * no edge reads: an exact zero row of grad_x_nodes.  Outputs must not alias inputs.  No atomics: the same bits from call to call, on every device, and
+ * whichever subset of the outputs is asked for. */
+int ddk_hconv_backward(ddk_ctx* ctx, int32_t head, const float* x_nodes, int64_t n_in, int64_t n_out, const int32_t* edge_src, const int32_t* edge_dst,
+                       const int32_t* src_order, const int64_t* src_ptr, const int32_t* dst_order, const int64_t* dst_ptr, const float* sh, const float* h,
+                       const float* w2, const float* b2, const float* grad_out_nodes, int64_t E, float* grad_x_nodes, float* grad_h, float* grad_w2,
+                       float* grad_b2, void* workspace, void* stream);
+
+/* Bytes of the workspace of ddk_hconv_forward (backward == 0) or ddk_hconv_backward (backward != 0): a function of its arguments alone; -1 for a head other
+ * than the two above, E < 0 or E >= 2^31, n_in or n_out outside 0 .. 2^31 - 1.  Host function, no context. */
+int64_t ddk_hconv_workspace(int32_t head, int64_t E, int64_t n_in, int64_t n_out, int32_t backward);
+
+/* The fixed-order segmented sum the radial conv and the head convs add a node's rows with (rtp_seg_kernel of csrc/k_rtp.hip), on its own: the backward of
+ * a gather x[index].  nodes[n, :] = rows[order[ptr[n]], :] + rows[order[ptr[n] + 1], :] + ... + rows[order[ptr[n + 1] - 1], :], added in that order, one
+ * thread per (node, column); a node without rows: exact zeros.  rows [*, D], nodes [n_nodes, D]: DEVICE, fp32, contiguous, 1 <= D <= 128; order: int32,
+ * ptr: int64 [n_nodes + 1], TRUSTED as the graph tables of ddk_rconv_forward (Context.conv_graph makes them).  n_nodes == 0: DDK_OK, no launch.  No
+ * allocation, no synchronisation, no atomics: the same bits from call to call. */
+int ddk_seg_sum(ddk_ctx* ctx, const float* rows, const int32_t* order, const int64_t* ptr, float* nodes, int64_t n_nodes, int32_t D, void* stream);
+
 /* ---- a11: TensorProductConvLayer.forward(node_attr, edge_index, edge_attr, edge_sh)
  *      models/tensor_layers.py:147-168 for conv layer `layer`, fused: radial MLP (fp32 MFMA) +
  *      tensor product + segmented scatter-sum + mean + BatchNorm(eval) + residual, without ever

@@ -24,7 +24,14 @@ peak device memory of one step of each.
 times one training step, forward + backward with all gradients, of the radial MLP's hidden layer from the edge embedding two ways on one random graph:
 (a) tensor_layers.fused_radial_hidden (ddk_rhid_forward / ddk_rhid_backward, k_rhid.hip: no [E, 72] row, no atomics, a counter-based dropout mask) and
 (b) the composition it replaces, the reference's cat of [edge_emb | node_attr[src, :24] | node_attr[dst, :24]] and fc[g][:4] per group.  Same options,
-alternation and medians as --conv; and the device passes of (a) on their own."""
+alternation and medians as --conv; and the device passes of (a) on their own.
+
+    python tools/bench_tp.py --heads [--iters 20] [--json out.json]
+times one training step, forward + backward with all gradients, of the two head convolutions (final_conv, tor_bond_conv) two ways on the shapes of a
+training batch, 1 200 and 12 000 ligand atoms in ligands of 30 atoms with 8 rotatable bonds each (20 neighbours per bond): (a)
+tensor_layers.fused_head_conv (ddk_hconv_forward / ddk_hconv_backward, k_hconv.hip) and (b) a plain-torch restatement of the same composition, the radial
+MLP, index_select, e3nn's FullyConnectedTensorProduct written out per weight block, index_add_ and the division.  Alternation and medians as --conv; the
+device passes of (a) on their own; the launches per direction."""
 import argparse, json, os, sys
 import torch
 sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), '..')))
@@ -39,6 +46,7 @@ p.add_argument('--backward', action='store_true')
 p.add_argument('--radial', action='store_true')
 p.add_argument('--conv', action='store_true')
 p.add_argument('--hidden', action='store_true')
+p.add_argument('--heads', action='store_true')
 p.add_argument('--dropout', type=float, default=0.1, help='--hidden: the dropout rate of the FCBlocks')
 p.add_argument('--nodes', type=int, default=None, help='--conv, --hidden: nodes of the graph (default: edges / 25)')
 p.add_argument('--layers', default='0,3', help='--conv: the layer shapes to time')
@@ -334,6 +342,108 @@ def bench_hidden():
         json.dump([res], open(a.json, 'w'), indent=1)
 
 
+def head_tp_torch(head, xe, sh, w):
+    """e3nn's FullyConnectedTensorProduct of a score head in plain torch, any dtype (the formulas of oracle/e3nn_lite.py written out per weight block,
+    as tests/head_conv_ref.py does in numpy): xe [E, 84] gathered node rows, sh [E, 4], w [E, W] -> [E, 12] (centre) or [E, 48] (torsion)"""
+    E = xe.shape[0]
+    a_, p_, q_, c_ = xe[:, :24], xe[:, 24:42].reshape(E, 6, 3), xe[:, 42:60].reshape(E, 6, 3), xe[:, 60:]
+    s0, v = sh[:, :1, None], sh[:, None, 1:]
+    if head == 0:
+        s6, s72 = (3.0 / 36.0) ** 0.5 / 3.0 ** 0.5, (3.0 / 36.0) ** 0.5 / 6.0 ** 0.5
+        cross = lambda t: torch.cross(t, v.expand_as(t), dim=-1) * s72
+        blocks = ((a_[..., None] * v * s6, 0, 0), (p_ * s0 * s6, 48, 0), (cross(p_), 60, 1), (q_ * s0 * s6, 72, 1), (cross(q_), 84, 0), (c_[..., None] * v * s6, 96, 1))
+        out = [0, 0]
+        for u, off, io in blocks:
+            r = u.shape[1]
+            out[io] = out[io] + torch.einsum('erk,erc->eck', u, w[:, off:off + 2 * r].reshape(E, r, 2))
+        return torch.cat([out[0].reshape(E, 6), out[1].reshape(E, 6)], 1)
+    s18 = (1.0 / 6.0) ** 0.5 / 3.0 ** 0.5
+    up, uq = (p_ * v).sum(-1) * s18, (q_ * v).sum(-1) * s18
+    o0e = torch.einsum('er,erc->ec', up, w[:, :144].reshape(E, 6, 24))
+    o0o = torch.einsum('er,erc->ec', uq, w[:, 144:].reshape(E, 6, 24))
+    return torch.cat([o0o, o0e], 1)
+
+
+def bench_heads():
+    """forward + backward of both head convs on the shapes of a training batch: ligands of 30 atoms with 8 rotatable bonds each"""
+    from disco_diffdock_amd.runtime import head_tp_shape
+    from disco_diffdock_amd.tensor_layers import FCBlock, _shape_context, fused_head_conv
+    ctx = _shape_context(0)
+    results = []
+    for n_atoms in (1200, 12000):
+        n_lig = n_atoms // 30
+        for head, name in ((0, 'centre'), (1, 'torsion')):
+            s = head_tp_shape(head)
+            K, W, dout = s['K'], s['W'], s['dout']
+            gen = torch.Generator(device=dev).manual_seed(head)
+            if head == 0:      # one edge per atom, to its ligand
+                src, dst, n_out = torch.arange(n_atoms, device=dev) // 30, torch.arange(n_atoms, device=dev), n_lig
+            else:      # per bond 20 of its ligand's 30 atoms, ascending
+                n_out = 8 * n_lig
+                pick = torch.rand(n_out, 30, device=dev, generator=gen).argsort(1)[:, :20].sort(1).values
+                src = torch.arange(n_out, device=dev).repeat_interleave(20)
+                dst = (pick + 30 * (torch.arange(n_out, device=dev) // 8)[:, None]).reshape(-1)
+            E = src.shape[0]
+            torch.manual_seed(head)
+            fc = FCBlock(K, K, W, 2, 0.0).to(dev)
+            x, sh, ea, g = (torch.randn(n, c, device=dev, generator=gen) for n, c in ((n_atoms, 84), (E, 4), (E, K), (n_out, dout)))
+            ei = torch.stack([src, dst])
+            graph = ctx.conv_graph(src, dst, n_atoms, n_out)
+            count = graph.src_count.clamp(min=1).float()[:, None]
+            X, EA = x.requires_grad_(True), ea.requires_grad_(True)
+
+            def step(fused):
+                for t in [X, EA] + list(fc.parameters()):
+                    t.grad = None
+                if fused:
+                    out = fused_head_conv(head, fc, X, ei, sh, EA, n_out, graph=graph)
+                else:
+                    rows = head_tp_torch(head, X.index_select(0, dst), sh, fc(EA))
+                    out = torch.zeros(n_out, dout, device=dev).index_add_(0, src, rows) / count
+                out.backward(g)
+
+            res = {'head': name, 'atoms': n_atoms, 'ligands': n_lig, 'receivers': n_out, 'edges': E, 'W': W, 'K': K,
+                   'launches': {'forward': 2, 'backward': 4},
+                   'workspace_bytes': {'forward': ctx.L.ddk_hconv_workspace(head, E, n_atoms, n_out, 0), 'backward': ctx.L.ddk_hconv_workspace(head, E, n_atoms, n_out, 1)}}
+            grads = {}
+            for tag, fused in (('fused', True), ('torch', False)):
+                step(fused)
+                step(fused)
+                torch.cuda.synchronize()
+                grads[tag] = [X.grad.clone(), EA.grad.clone()] + [p.grad.clone() for p in fc.parameters()]
+            res['max_rel_diff_of_gradients'] = max(float((u - v).abs().max() / v.abs().max()) for u, v in zip(grads['fused'], grads['torch']))
+            step(True)
+            again = [X.grad.clone(), EA.grad.clone()] + [p.grad.clone() for p in fc.parameters()]
+            res['gradients_bit_identical_run_to_run'] = all(torch.equal(u, v) for u, v in zip(again, grads['fused']))
+            times = {'fused': [], 'torch': []}
+            for _ in range(a.repeats):      # the two paths alternate, so that a drift of the clocks meets both
+                for tag, fused in (('fused', True), ('torch', False)):
+                    st, en = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    st.record()
+                    for _ in range(a.iters):
+                        step(fused)
+                    en.record()
+                    torch.cuda.synchronize()
+                    times[tag].append(st.elapsed_time(en) / a.iters)
+            for tag, t in times.items():
+                res[tag] = {'ms': sorted(t)[len(t) // 2], 'ms_passes': t}
+            res['fused_over_torch_ms'] = res['fused']['ms'] / res['torch']['ms']
+            with torch.no_grad():      # the device passes on their own (no torch around them)
+                hid, w2, b2, xd = fc[:4](EA), fc[4].weight, fc[4].bias, X.detach()
+                res['kernels_ms'] = {
+                    'forward': median_ms(lambda: ctx.hconv_forward(head, graph, xd, sh, hid, w2, b2), a.iters, a.repeats),
+                    'backward_all': median_ms(lambda: ctx.hconv_backward(head, graph, xd, sh, hid, w2, b2, g), a.iters, a.repeats),
+                    'backward_per_edge': median_ms(lambda: ctx.hconv_backward(head, graph, xd, sh, hid, w2, b2, g, (True, True, False, False)), a.iters, a.repeats),
+                    'backward_parameters': median_ms(lambda: ctx.hconv_backward(head, graph, xd, sh, hid, None, None, g, (False, False, True, True)), a.iters, a.repeats)}
+            print(json.dumps(res), flush=True)
+            results.append(res)
+    if a.json:
+        json.dump(results, open(a.json, 'w'), indent=1)
+
+
+if a.heads:
+    bench_heads()
+    sys.exit(0)
 if a.hidden:
     bench_hidden()
     sys.exit(0)
