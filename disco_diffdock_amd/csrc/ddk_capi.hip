@@ -472,6 +472,63 @@ int ddk_hconv_backward(ddk_ctx* ctx, int32_t head, const float* x_nodes, int64_t
 
 int64_t ddk_hconv_workspace(int32_t head, int64_t E, int64_t n_in, int64_t n_out, int32_t backward) { return hconv_workspace(head, E, n_in, n_out, backward); }
 
+// the checks the two edge-embedding entries share: a context that can launch, the counts and the smearing, and with edges the operands both read
+static int eemb_check(ddk_ctx* ctx, const char* who, const EembOperands& o, int64_t n_a, int64_t n_b, int32_t F, int64_t n_sig, int32_t n_gauss, int64_t E) {
+  int rc = check_launchable(ctx, 0);
+  if (rc) return rc;
+  const std::string w(who);
+  const int64_t lim = (int64_t)1 << 31;
+  if (F != 0 && F != 4) return fail(ctx, DDK_ERR_INVALID, w + ": F must be 0 or 4");
+  if (n_gauss != 32) return fail(ctx, DDK_ERR_INVALID, w + ": n_gauss must be 32");
+  if (E < 0 || E >= lim) return fail(ctx, DDK_ERR_INVALID, w + ": edge count out of range");
+  if (n_a < 0 || n_a >= lim || n_b < 0 || n_b >= lim || n_sig < 0 || n_sig >= lim) return fail(ctx, DDK_ERR_INVALID, w + ": node or graph count out of range");
+  if (!(o.p >= 0.f && o.p < 1.f)) return fail(ctx, DDK_ERR_INVALID, w + ": the dropout rate p must be in [0, 1)");
+  if (!(o.stop > o.start)) return fail(ctx, DDK_ERR_INVALID, w + ": the smearing needs start < stop");
+  if (E == 0) return DDK_OK;
+  if (n_a == 0 || n_b == 0 || n_sig == 0) return fail(ctx, DDK_ERR_INVALID, w + ": edges without nodes or graphs");
+  if (!o.pos_a || !o.pos_b || !o.idx_a || !o.idx_b || !o.sig || !o.sig_index) return fail(ctx, DDK_ERR_INVALID, w + ": null operand (pos, idx, sig, sig_index)");
+  if ((F == 4) != (o.feat != nullptr)) return fail(ctx, DDK_ERR_INVALID, w + ": feat must be given with F == 4 and null with F == 0");
+  if (!o.w1 || !o.b1 || !o.w2) return fail(ctx, DDK_ERR_INVALID, w + ": null parameter (w1, b1, w2)");
+  if (((uintptr_t)o.feat | (uintptr_t)o.sig) & 15) return fail(ctx, DDK_ERR_INVALID, w + ": feat and sig must be 16-byte aligned");
+  return DDK_OK;
+}
+
+int ddk_eemb_forward(ddk_ctx* ctx, const float* pos_a, int64_t n_a, const float* pos_b, int64_t n_b, const int32_t* idx_a, const int32_t* idx_b,
+                     const float* feat, int32_t F, const float* sig, int64_t n_sig, const int32_t* sig_index, float start, float stop, int32_t n_gauss,
+                     const float* w1, const float* b1, const float* w2, const float* b2, float p, uint64_t seed, int64_t E, float* emb, float* sh,
+                     void* stream) {
+  const EembOperands o{pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, b2, p, seed, F};
+  int rc = eemb_check(ctx, "ddk_eemb_forward", o, n_a, n_b, F, n_sig, n_gauss, E);
+  if (rc) return rc;
+  if (E == 0) return DDK_OK;
+  if (!b2 || !emb || !sh) return fail(ctx, DDK_ERR_INVALID, "ddk_eemb_forward: null operand (b2, emb, sh)");
+  if (((uintptr_t)emb | (uintptr_t)sh) & 15) return fail(ctx, DDK_ERR_INVALID, "ddk_eemb_forward: emb and sh must be 16-byte aligned");
+  hipError_t e = launch_eemb_forward(o, E, emb, sh, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "eemb_forward launch");
+  return DDK_OK;
+}
+
+int ddk_eemb_backward(ddk_ctx* ctx, const float* pos_a, int64_t n_a, const float* pos_b, int64_t n_b, const int32_t* idx_a, const int32_t* idx_b,
+                      const float* feat, int32_t F, const float* sig, int64_t n_sig, const int32_t* sig_index, float start, float stop, int32_t n_gauss,
+                      const float* w1, const float* b1, const float* w2, const float* b2, float p, uint64_t seed, const float* grad_emb, int64_t E,
+                      float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2, void* workspace, void* stream) {
+  const EembOperands o{pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, b2, p, seed, F};
+  int rc = eemb_check(ctx, "ddk_eemb_backward", o, n_a, n_b, F, n_sig, n_gauss, E);
+  if (rc) return rc;
+  if (!grad_w1 && !grad_b1 && !grad_w2 && !grad_b2)
+    return fail(ctx, DDK_ERR_INVALID, "ddk_eemb_backward: no gradient requested (grad_w1, grad_b1, grad_w2 and grad_b2 are all null)");
+  if (E > 0) {
+    if (!grad_emb) return fail(ctx, DDK_ERR_INVALID, "ddk_eemb_backward: null grad_emb");
+    if (!workspace) return fail(ctx, DDK_ERR_INVALID, "ddk_eemb_backward: null workspace (ddk_eemb_workspace bytes)");
+    if (((uintptr_t)grad_emb | (uintptr_t)workspace) & 15) return fail(ctx, DDK_ERR_INVALID, "ddk_eemb_backward: grad_emb and the workspace must be 16-byte aligned");
+  }
+  hipError_t e = launch_eemb_backward(o, grad_emb, E, grad_w1, grad_b1, grad_w2, grad_b2, (float*)workspace, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "eemb_backward launch");
+  return DDK_OK;
+}
+
+int64_t ddk_eemb_workspace(int64_t E, int32_t K) { return eemb_workspace(E, K); }
+
 int ddk_seg_sum(ddk_ctx* ctx, const float* rows, const int32_t* order, const int64_t* ptr, float* nodes, int64_t n_nodes, int32_t D, void* stream) {
   int rc = check_launchable(ctx, 0);
   if (rc) return rc;

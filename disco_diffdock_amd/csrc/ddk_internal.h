@@ -373,4 +373,18 @@ hipError_t launch_hconv_backward(int head, const RconvGraph& gr, const float* x_
                                  const float* grad_out_nodes, int64_t E, float* grad_x_nodes, float* grad_h, float* grad_w2, float* grad_b2, float* workspace,
                                  hipStream_t s);
 int64_t hconv_workspace(int32_t head, int64_t E, int64_t n_in, int64_t n_out, int32_t backward);
+// k_eemb.hip: one edge group's embedding in front of the conv stack, emb = W2 dropout(relu(W1 [feat | sig[graph] | smearing(|vec|)] + b1)) + b2 and the edge's
+// first-order spherical harmonics, and its vector-Jacobian product for the four parameter tensors (include/ddk.h: ddk_eemb_forward / ddk_eemb_backward).
+// What both directions read: trusted index tables, feat null for F = 0; a null output of the backward is not computed
+struct EembOperands {
+  const float* pos_a; const float* pos_b; const int32_t* idx_a; const int32_t* idx_b; const float* feat; const float* sig; const int32_t* sig_index;
+  float start, stop;
+  const float* w1; const float* b1; const float* w2; const float* b2;
+  float p; uint64_t seed;
+  int F;      // bond-feature columns: 0 (feat null) or 4
+};
+hipError_t launch_eemb_forward(const EembOperands& o, int64_t E, float* emb, float* sh, hipStream_t s);
+hipError_t launch_eemb_backward(const EembOperands& o, const float* grad_emb, int64_t E, float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2,
+                                float* workspace, hipStream_t s);
+int64_t eemb_workspace(int64_t E, int32_t K);
 }  // namespace ddk

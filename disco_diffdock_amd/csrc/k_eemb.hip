@@ -1,0 +1,366 @@
+// The edge embeddings in front of the conv stack at the op boundary, and their vector-Jacobian product for the four parameter tensors, WITHOUT any per-edge
+// tensor besides the two outputs (models/score_model.py:191-225 of the reference: lig_edge_embedding, cross_edge_embedding, rec_edge_embedding and the
+// first-order spherical harmonics of the edges).  For edge e of ONE edge group:
+//   vec = pos_b[idx_b[e]] - pos_a[idx_a[e]]     d = |vec|     row = [ feat[e] (F = 0 or 4) | sig[sig_index[idx_a[e]]] (32) | exp(coeff (d - offset_j)^2) (32) ]
+//   pre = W1 row + b1     hid = dropout(relu(pre))     emb[e] = W2 hid + b2     sh[e] = [1 | sqrt3 vec / max(d, 1e-12)]
+// Every column of the row is a pure function of two coordinates, a graph index and the bond type: nothing of it carries a gradient, so the backward has the
+// parameters alone to serve and RECOMPUTES row, pre and the mask from the coordinates and the seed; the forward keeps nothing per edge.  Exact fp32: every
+// dot product is ONE fmaf chain in a written-out order (compiled with -ffp-contract=off, so that the only fused operations are the ones spelled fmaf):
+//   pre[e, c]  = fmaf(W1[c, K - 1], row[K - 1], ... fmaf(W1[c, 0], row[0], b1[c]))          k ascending, the bias first (feat, then sig, then the smearing)
+//   emb[e, o]  = fmaf(W2[o, 23], hid[23], ... fmaf(W2[o, 0], hid[0], b2[o]))                c ascending, the bias first
+//   ghid[e, c] = fmaf(g[e, 23], W2[23, c], ... fmaf(g[e, 0], W2[0, c], 0))                  o ascending
+//   d = sqrtf(fmaf(z, z, fmaf(y, y, x * x))), the smearing's argument t = d - offset_j, column = expf(coeff * (t * t))
+// The forward and the backward share these expressions (eemb_geometry, eemb_smear, eemb_hidden): the recomputed hidden layer has the forward's bits.
+//
+// FORWARD.  One LANE owns one EDGE; a workgroup is two waves.  The lane's 24 accumulators start from b1 and a step adds FOUR columns of W1 (24 loads of 16
+// bytes at the same address in every lane: scalar loads through the constant cache, W1 is 6.5 KB, W2 2.3 KB, and v_fmac_f32 takes them from the scalar
+// registers).  The row is never stored: a step's four columns are made where they are used.  emb and sh leave as 16-byte stores of the lane's own row.
+//
+// THE MASK (include/ddk.h, DDK_EEMB_MASK_LAYOUT): keep(e, c) = rng_uniform(word c % 4 of Philox4x32-10(key = seed, counter = (e_lo, e_hi, c / 4,
+// DDK_EEMB_MASK_TAG))) >= p, e the edge's position within the call: a pure function of (seed, edge id, column).
+//
+// BACKWARD.  eemb_param_kernel + eemb_reduce_kernel, as rhid_param_kernel / rhid_reduce_kernel: a workgroup of four waves owns a slice of rtp_slice_len(E)
+// edges and walks it 64 edges at a time.  Per step the four waves share the 64 edges (lane = edge): wave w makes eight columns of sig and of the smearing
+// and six of grad_emb into LDS; then six columns of pre / hid (the forward's chain over the whole row, read back from LDS); then six of
+// gpre = ghid * (hid != 0 ? s : 0).  Then every thread adds the step's 64 edges, in ascending edge order, to its elements of the slice's image, which
+// it holds in registers: grad_w1 [24][K] with grad_b1 as column K, grad_w2 [24][24] with grad_b2 as column 24.  Plain stores of the image; the second
+// kernel adds the images in slice order.  No atomics; the images are the whole workspace, and everything is computed whichever outputs are asked for, so
+// the bits do not depend on the subset, the run or the device.  A row of the LDS tiles has an odd stride: the lanes of an access hit different banks.
+#include "ddk_internal.h"
+#include "k_philox.h"
+
+namespace ddk {
+
+constexpr int EE_H = 24;             // hidden and output width (ns)
+constexpr int EE_S = 32;             // sigma embedding columns
+constexpr int EE_D = 32;             // Gaussians of the distance expansion
+constexpr int EE_KMAX = 4 + EE_S + EE_D;
+constexpr int EE_EPB = 128;          // edges per workgroup of the forward: two waves, one edge per lane
+constexpr int EE_PT = 256;           // threads of eemb_param_kernel: four waves
+constexpr int EE_LDR = EE_KMAX + 1;  // row stride of the LDS tile of rows
+constexpr int EE_LDH = EE_H + 1;     // row stride of the LDS tiles of grad_emb, hid and gpre
+static_assert(EE_H == NS, "the edge embedding of ns = 24");
+
+struct EembArgs {
+  const float* pos_a; const float* pos_b; const int32_t* idx_a; const int32_t* idx_b;
+  const float* feat; const float* sig; const int32_t* sig_index;
+  const float* w1; const float* b1; const float* w2; const float* b2;
+  const float* gemb;
+  float* emb; float* sh; float* img; float* gw1; float* gb1; float* gw2; float* gb2;
+  int64_t E, L;      // edges of the call; edges per slice (parameter pass)
+  int F, K;          // bond-feature columns (0 or 4); K = F + 64
+  float coeff, p, s;
+  uint32_t seed_lo, seed_hi;
+  float offset[EE_D];
+};
+
+struct EembEdge { float x, y, z, d; int64_t sig_row; };
+
+// vec, d and the row of the sigma table of edge e (the indices are trusted)
+__device__ __forceinline__ EembEdge eemb_geometry(const EembArgs& a, int64_t e) {
+  const int64_t ia = a.idx_a[e], ib = a.idx_b[e];
+  EembEdge g;
+  g.x = a.pos_b[3 * ib] - a.pos_a[3 * ia];
+  g.y = a.pos_b[3 * ib + 1] - a.pos_a[3 * ia + 1];
+  g.z = a.pos_b[3 * ib + 2] - a.pos_a[3 * ia + 2];
+  g.d = sqrtf(fmaf(g.z, g.z, fmaf(g.y, g.y, g.x * g.x)));
+  g.sig_row = a.sig_index[ia];
+  return g;
+}
+
+__device__ __forceinline__ float eemb_smear(const EembArgs& a, float d, int j) {
+  const float t = d - a.offset[j];
+  return expf(a.coeff * (t * t));
+}
+
+// hid[c] of the dropout layout from the ReLU of pre[c]: columns c0 .. c0 + n - 1 (c0 a multiple of 2, n <= 8) of edge e
+template <int N>
+__device__ __forceinline__ void eemb_hidden(const EembArgs& a, int64_t e, int c0, float* v) {
+  if (a.p > 0.f) {
+    const uint32_t key[2] = {a.seed_lo, a.seed_hi};
+    const int q0 = c0 >> 2, q1 = (c0 + N - 1) >> 2;
+    for (int q = q0; q <= q1; ++q) {
+      const uint32_t ctr[4] = {(uint32_t)e, (uint32_t)((uint64_t)e >> 32), (uint32_t)q, DDK_EEMB_MASK_TAG};
+      uint32_t w[4];
+      philox4x32_10(ctr, key, w);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int c = 4 * q + i - c0;
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+          if (j == c) {
+            const float r = v[j] < 0.f ? 0.f : v[j];      // (a NaN stays one, as torch's relu leaves it)
+            v[j] = rng_uniform(w[i]) >= a.p ? r * a.s : 0.f;
+          }
+        }
+      }
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < N; ++j) v[j] = v[j] < 0.f ? 0.f : v[j];
+  }
+}
+
+// ---- forward -------------------------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(EE_EPB) void eemb_fwd_kernel(EembArgs a) {
+  const int64_t e = (int64_t)blockIdx.x * EE_EPB + threadIdx.x;
+  const bool ev = e < a.E;
+  const int64_t el = ev ? e : 0;      // a lane past the end works on edge 0 and stores nothing
+  const EembEdge g = eemb_geometry(a, el);
+  float acc[EE_H];
+#pragma unroll
+  for (int c = 0; c < EE_H; ++c) acc[c] = a.b1[c];
+  const int K = a.K;
+  int k0 = 0;
+  if (a.F) {      // the bond features: columns 0 .. 3
+    const float4 f = reinterpret_cast<const float4*>(a.feat)[el];
+    const float x[4] = {f.x, f.y, f.z, f.w};
+#pragma unroll
+    for (int c = 0; c < EE_H; ++c) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) acc[c] = fmaf(a.w1[c * K + i], x[i], acc[c]);
+    }
+    k0 = 4;
+  }
+  const float4* srow = reinterpret_cast<const float4*>(a.sig + g.sig_row * EE_S);
+#pragma unroll 1
+  for (int j = 0; j < EE_S; j += 4) {      // the sigma embedding of the edge's graph
+    const float4 f = srow[j >> 2];
+    const float x[4] = {f.x, f.y, f.z, f.w};
+    const float* w = a.w1 + k0 + j;
+#pragma unroll
+    for (int c = 0; c < EE_H; ++c) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) acc[c] = fmaf(w[c * K + i], x[i], acc[c]);
+    }
+  }
+#pragma unroll 1
+  for (int j = 0; j < EE_D; j += 4) {      // the Gaussian smearing of the edge length
+    float x[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) x[i] = eemb_smear(a, g.d, j + i);
+    const float* w = a.w1 + k0 + EE_S + j;
+#pragma unroll
+    for (int c = 0; c < EE_H; ++c) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) acc[c] = fmaf(w[c * K + i], x[i], acc[c]);
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < EE_H; c += 8) eemb_hidden<8>(a, el, c, acc + c);
+  float out[EE_H];
+#pragma unroll
+  for (int o = 0; o < EE_H; ++o) {
+    float v = a.b2[o];
+#pragma unroll
+    for (int c = 0; c < EE_H; ++c) v = fmaf(a.w2[o * EE_H + c], acc[c], v);
+    out[o] = v;
+  }
+  if (ev) {
+    float4* to = reinterpret_cast<float4*>(a.emb + e * EE_H);
+#pragma unroll
+    for (int q = 0; q < EE_H / 4; ++q) to[q] = make_float4(out[4 * q], out[4 * q + 1], out[4 * q + 2], out[4 * q + 3]);
+    const float r = 1.7320508075688772f / fmaxf(g.d, 1e-12f);
+    reinterpret_cast<float4*>(a.sh)[e] = make_float4(1.f, g.x * r, g.y * r, g.z * r);
+  }
+}
+
+// ---- backward: the slice images ------------------------------------------------------------------------------------------------------------------------------
+// image of a slice: [24][K + 1] (grad_w1, column K grad_b1), then [24][25] (grad_w2, column 24 grad_b2)
+__host__ __device__ inline int eemb_img(int K) { return EE_H * (K + 1) + EE_H * (EE_H + 1); }
+
+__global__ __launch_bounds__(EE_PT) void eemb_param_kernel(EembArgs a) {
+  __shared__ float rows[64 * EE_LDR];
+  __shared__ float gs[64 * EE_LDH];
+  __shared__ float hs[64 * EE_LDH];
+  __shared__ float ps[64 * EE_LDH];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (uniform in the wave: what it indexes W1 and W2 with goes through scalar loads)
+  const int K = a.K, F = a.F;
+  const int64_t slice = blockIdx.x;
+  const int64_t begin = slice * a.L, end = begin + a.L < a.E ? begin + a.L : a.E;
+  // the thread's elements of the image: rows 3 tc .. 3 tc + 2 of columns tk, tk + 32, tk + 64 (< K) of grad_w1; of column tk (< 24) of grad_w2;
+  // tk == 24: of grad_b1; tk == 25: of grad_b2
+  const int tc = tid & 7, tk = tid >> 3;
+  float a1[3][3], a2[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    a2[i] = 0.f;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) a1[i][j] = 0.f;
+  }
+  const bool third = tk + 64 < K;
+  for (int64_t eb = begin; eb < end; eb += 64) {
+    const int64_t e = eb + lane;
+    const bool ev = e < end;
+    const int64_t el = ev ? e : begin;
+    // 1. the wave's columns of the row and of grad_emb; a lane past the end stages zeros, which leave every sum as it is
+    {
+      const EembEdge g = eemb_geometry(a, el);
+      float* r = rows + lane * EE_LDR;
+      if (wave == 0 && F) {
+        const float4 f = reinterpret_cast<const float4*>(a.feat)[el];
+        r[0] = ev ? f.x : 0.f; r[1] = ev ? f.y : 0.f; r[2] = ev ? f.z : 0.f; r[3] = ev ? f.w : 0.f;
+      }
+      const float4* srow = reinterpret_cast<const float4*>(a.sig + g.sig_row * EE_S) + 2 * wave;
+      const float4 s0 = srow[0], s1 = srow[1];
+      const float sv[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        r[F + 8 * wave + i] = ev ? sv[i] : 0.f;
+        const float x = eemb_smear(a, g.d, 8 * wave + i);
+        r[F + EE_S + 8 * wave + i] = ev ? x : 0.f;
+      }
+#pragma unroll
+      for (int i = 0; i < 6; ++i) gs[lane * EE_LDH + 6 * wave + i] = ev ? a.gemb[el * EE_H + 6 * wave + i] : 0.f;
+    }
+    __syncthreads();
+    // 2. six columns of pre and of hid: the forward's chain over the row
+    {
+      const float* r = rows + lane * EE_LDR;
+      const float* w = a.w1 + 6 * wave * K;
+      float v[6];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) v[i] = a.b1[6 * wave + i];
+#pragma unroll 4
+      for (int k = 0; k < K; ++k) {
+        const float x = r[k];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) v[i] = fmaf(w[i * K + k], x, v[i]);
+      }
+      eemb_hidden<6>(a, el, 6 * wave, v);
+#pragma unroll
+      for (int i = 0; i < 6; ++i) hs[lane * EE_LDH + 6 * wave + i] = ev ? v[i] : 0.f;
+      // 3. six columns of gpre = ghid * (hid != 0 ? s : 0)
+      float gh[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int o = 0; o < EE_H; ++o) {
+        const float go = gs[lane * EE_LDH + o];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) gh[i] = fmaf(go, a.w2[o * EE_H + 6 * wave + i], gh[i]);
+      }
+#pragma unroll
+      for (int i = 0; i < 6; ++i) ps[lane * EE_LDH + 6 * wave + i] = ev ? gh[i] * (v[i] != 0.f ? a.s : 0.f) : 0.f;
+    }
+    __syncthreads();
+    // 4. the step's 64 edges, ascending, into the thread's elements of the image
+    if (tk < EE_H) {
+#pragma unroll 4
+      for (int l = 0; l < 64; ++l) {
+        const float hv = hs[l * EE_LDH + tk];
+        const float x0 = rows[l * EE_LDR + tk], x1 = rows[l * EE_LDR + tk + 32], x2 = third ? rows[l * EE_LDR + tk + 64] : 0.f;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          const float gp = ps[l * EE_LDH + 3 * tc + i];
+          a1[i][0] = fmaf(gp, x0, a1[i][0]); a1[i][1] = fmaf(gp, x1, a1[i][1]); a1[i][2] = fmaf(gp, x2, a1[i][2]);
+          a2[i] = fmaf(gs[l * EE_LDH + 3 * tc + i], hv, a2[i]);
+        }
+      }
+    } else {
+      const float* from = tk == EE_H ? ps : gs;      // grad_b1 = the sum of gpre, grad_b2 = the sum of grad_emb (tk == 25; the threads behind add what they never store)
+#pragma unroll 4
+      for (int l = 0; l < 64; ++l) {
+        const float x0 = rows[l * EE_LDR + tk], x1 = rows[l * EE_LDR + tk + 32];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          const float gp = ps[l * EE_LDH + 3 * tc + i];
+          a1[i][0] = fmaf(gp, x0, a1[i][0]); a1[i][1] = fmaf(gp, x1, a1[i][1]);
+          a2[i] += from[l * EE_LDH + 3 * tc + i];
+        }
+      }
+    }
+    __syncthreads();      // (the next step overwrites the tiles)
+  }
+  float* img = a.img + slice * (int64_t)eemb_img(K);
+  float* img2 = img + EE_H * (K + 1);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const int c = 3 * tc + i;
+    img[c * (K + 1) + tk] = a1[i][0];
+    img[c * (K + 1) + tk + 32] = a1[i][1];
+    if (third) img[c * (K + 1) + tk + 64] = a1[i][2];
+    if (tk < EE_H) img2[c * (EE_H + 1) + tk] = a2[i];
+    else if (tk == EE_H) img[c * (K + 1) + K] = a2[i];
+    else if (tk == EE_H + 1) img2[c * (EE_H + 1) + EE_H] = a2[i];
+  }
+}
+
+// the four gradients = the slice images added in slice order
+__global__ __launch_bounds__(256) void eemb_reduce_kernel(EembArgs a, int64_t n_slices) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  const int K = a.K, PER = eemb_img(K), n1 = EE_H * (K + 1);
+  if (idx >= PER) return;
+  float sum = 0.f;
+  for (int64_t s = 0; s < n_slices; ++s) sum += a.img[s * PER + idx];
+  if (idx < n1) {
+    const int c = idx / (K + 1), k = idx - c * (K + 1);
+    if (k < K) {
+      if (a.gw1) a.gw1[c * K + k] = sum;
+    } else if (a.gb1) {
+      a.gb1[c] = sum;
+    }
+  } else {
+    const int r = idx - n1, c = r / (EE_H + 1), k = r - c * (EE_H + 1);
+    if (k < EE_H) {
+      if (a.gw2) a.gw2[c * EE_H + k] = sum;
+    } else if (a.gb2) {
+      a.gb2[c] = sum;
+    }
+  }
+}
+
+// ---- host ----------------------------------------------------------------------------------------------------------------------------------------------------
+int64_t eemb_workspace(int64_t E, int32_t K) {
+  if (E < 0 || E >= (int64_t)1 << 31 || (K != EE_S + EE_D && K != EE_KMAX)) return -1;
+  const int64_t slices = E / rtp_slice_len(E) + 1;      // ceil(E / L) <= floor(E / L) + 1
+  return slices * eemb_img(K) * (int64_t)sizeof(float);
+}
+
+// offset as torch.linspace(start, stop, 32) makes it in fp32 (one fused multiply-add per centre, the upper half counted down from stop), coeff as GaussianSmearing: -0.5 / (offset[1] - offset[0])^2
+static EembArgs eemb_args(const EembOperands& o, int64_t E) {
+  EembArgs a{};
+  a.pos_a = o.pos_a; a.pos_b = o.pos_b; a.idx_a = o.idx_a; a.idx_b = o.idx_b; a.feat = o.feat; a.sig = o.sig; a.sig_index = o.sig_index;
+  a.w1 = o.w1; a.b1 = o.b1; a.w2 = o.w2; a.b2 = o.b2;
+  a.E = E; a.L = rtp_slice_len(E);
+  a.F = o.F; a.K = a.F + EE_S + EE_D;
+  const float step = (o.stop - o.start) / (float)(EE_D - 1);
+  for (int j = 0; j < EE_D; ++j) a.offset[j] = j < EE_D / 2 ? fmaf(step, (float)j, o.start) : fmaf(-step, (float)(EE_D - 1 - j), o.stop);
+  const double gap = (double)(a.offset[1] - a.offset[0]);
+  a.coeff = (float)(-0.5 / (gap * gap));
+  a.p = o.p;
+  a.s = o.p > 0.f ? 1.0f / (1.0f - o.p) : 1.0f;
+  a.seed_lo = (uint32_t)o.seed; a.seed_hi = (uint32_t)(o.seed >> 32);
+  return a;
+}
+
+hipError_t launch_eemb_forward(const EembOperands& o, int64_t E, float* emb, float* sh, hipStream_t s) {
+  if (E == 0) return hipSuccess;
+  EembArgs a = eemb_args(o, E);
+  a.emb = emb; a.sh = sh;
+  hipLaunchKernelGGL(eemb_fwd_kernel, dim3((unsigned)((E + EE_EPB - 1) / EE_EPB)), dim3(EE_EPB), 0, s, a);      // E < 2^31: fewer than 2^31 workgroups
+  return hipGetLastError();
+}
+
+hipError_t launch_eemb_backward(const EembOperands& o, const float* grad_emb, int64_t E, float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2,
+                                float* workspace, hipStream_t s) {
+  const int K = o.F + EE_S + EE_D;
+  if (E == 0) {
+    const struct { float* p; int64_t n; } z[4] = {{grad_w1, (int64_t)EE_H * K}, {grad_b1, EE_H}, {grad_w2, EE_H * EE_H}, {grad_b2, EE_H}};
+    for (const auto& t : z) {
+      if (!t.p) continue;
+      hipError_t e = hipMemsetAsync(t.p, 0, (size_t)t.n * sizeof(float), s);
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  }
+  EembArgs a = eemb_args(o, E);
+  a.gemb = grad_emb; a.img = workspace; a.gw1 = grad_w1; a.gb1 = grad_b1; a.gw2 = grad_w2; a.gb2 = grad_b2;
+  const int64_t n_slices = (E + a.L - 1) / a.L;      // at most 241
+  hipLaunchKernelGGL(eemb_param_kernel, dim3((unsigned)n_slices), dim3(EE_PT), 0, s, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(eemb_reduce_kernel, dim3((unsigned)((eemb_img(K) + 255) / 256)), dim3(256), 0, s, a, n_slices);
+  return hipGetLastError();
+}
+
+}  // namespace ddk

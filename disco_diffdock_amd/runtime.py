@@ -663,6 +663,87 @@ class Context:
                                              _ptr(ws), _stream()), 'ddk_rhid_backward')
         return tuple(outs)      # (ws goes back to torch's allocator, which orders its reuse after these launches on the current stream)
 
+    # ---- the edge embeddings in front of the conv stack -------------------------------------------------
+    def _eemb_operands(self, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, b2, p):
+        """checked operands of the edge embedding: the tensors as the entries take them, (n_a, n_b, F, n_sig, E) and the scalars"""
+        pos_a, pos_b, sig, w1, b1, w2 = (_need_cuda(t).contiguous().float() for t in (pos_a, pos_b, sig, w1, b1, w2))
+        dev = pos_a.device
+        if pos_a.dim() != 2 or pos_a.shape[1] != 3 or pos_b.dim() != 2 or pos_b.shape[1] != 3:
+            raise RuntimeError(f'ddk: the edge embedding takes pos_a [Na, 3] and pos_b [Nb, 3]; got {tuple(pos_a.shape)} and {tuple(pos_b.shape)}')
+        n_a, n_b = pos_a.shape[0], pos_b.shape[0]
+        for name, t in (('idx_a', idx_a), ('idx_b', idx_b), ('sig_index', sig_index)):
+            if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.device != dev:
+                raise RuntimeError(f'ddk: the edge embedding takes {name} as a contiguous int32 vector on the device of pos_a (its kernels trust the indices)')
+        E = idx_a.shape[0]
+        if idx_b.shape[0] != E or sig_index.shape[0] != n_a:
+            raise RuntimeError(f'ddk: the edge embedding takes idx_a and idx_b [E] and sig_index [Na]; got {E}, {idx_b.shape[0]} and {sig_index.shape[0]} for Na = {n_a}')
+        if sig.dim() != 2 or sig.shape[1] != 32 or sig.device != dev:
+            raise RuntimeError(f'ddk: the edge embedding takes sig [T, 32] on the device of pos_a; got {tuple(sig.shape)}')
+        F = 0
+        if feat is not None:
+            feat = _need_cuda(feat).contiguous().float()
+            if feat.shape != (E, 4) or feat.device != dev:
+                raise RuntimeError(f'ddk: the edge embedding takes feat [E, 4] = {(E, 4)} on the device of pos_a; got {tuple(feat.shape)}')
+            F = 4
+        K = F + 64
+        for name, t, shape in (('w1', w1, (24, K)), ('b1', b1, (24,)), ('w2', w2, (24, 24))):
+            if t.shape != shape or t.device != dev:
+                raise RuntimeError(f'ddk: the edge embedding takes {name} {list(shape)} on the device of pos_a; got {tuple(t.shape)}')
+        if b2 is not None:
+            b2 = _need_cuda(b2).contiguous().float()
+            if b2.shape != (24,) or b2.device != dev:
+                raise RuntimeError(f'ddk: the edge embedding takes b2 [24] on the device of pos_a; got {tuple(b2.shape)}')
+        p, start, stop = float(p), float(start), float(stop)
+        if not 0.0 <= p < 1.0:
+            raise RuntimeError(f'ddk: the dropout rate must be in [0, 1); got {p}')
+        if not start < stop:
+            raise RuntimeError(f'ddk: the distance expansion needs start < stop; got {start}, {stop}')
+        if E and (n_a == 0 or n_b == 0 or sig.shape[0] == 0):
+            raise RuntimeError('ddk: the edge embedding has edges without nodes or graphs')
+        return (pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, w1, b1, w2, b2), (n_a, n_b, F, sig.shape[0], E), (start, stop, p)
+
+    def _eemb_call(self, fn, t, n, sc, seed, tail, who):
+        pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, w1, b1, w2, b2 = t
+        n_a, n_b, F, T, E = n
+        start, stop, p = sc
+        self._check(fn(self.h, _ptr(pos_a), n_a, _ptr(pos_b), n_b, _ptr(idx_a), _ptr(idx_b), _ptr(feat), F, _ptr(sig), T, _ptr(sig_index), start, stop, 32,
+                       _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), p, _u64(seed, 'seed'), *tail, _stream()), who)
+
+    def eemb_forward(self, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, b2, p=0.0, seed=0):
+        """One edge group's embedding and spherical harmonics (ddk_eemb_forward): (emb [E, 24], sh [E, 4]) with
+        ``emb = w2 dropout_p(relu(w1 [feat | sig[sig_index[idx_a]] | smearing(|pos_b[idx_b] - pos_a[idx_a]|)] + b1)) + b2`` and ``sh = [1 | sqrt3 unit vector]``.
+        ``idx_a``, ``idx_b`` [E], ``sig_index`` [Na]: int32, trusted; ``feat`` [E, 4] or None; ``start``, ``stop``: of the 32 Gaussians.  The mask is a pure
+        function of (seed, edge position, column) (DDK_EEMB_MASK_LAYOUT of include/ddk.h); nothing per edge is kept for the backward."""
+        t, n, sc = self._eemb_operands(pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, b2, p)
+        if t[-1] is None:
+            raise RuntimeError('ddk: eemb_forward needs b2')
+        E, dev = n[4], t[0].device
+        emb, sh = torch.empty((E, 24), dtype=torch.float32, device=dev), torch.empty((E, 4), dtype=torch.float32, device=dev)
+        if E:
+            self._eemb_call(self.L.ddk_eemb_forward, t, n, sc, seed, (E, _ptr(emb), _ptr(sh)), 'ddk_eemb_forward')
+        return emb, sh
+
+    def eemb_backward(self, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, grad_emb, p=0.0, seed=0, need=(True, True, True, True)):
+        """The vector-Jacobian product of ``eemb_forward`` for its parameters (ddk_eemb_backward): (grad_w1 [24, K], grad_b1 [24], grad_w2 [24, 24],
+        grad_b2 [24]), None where ``need`` is false.  The hidden layer and the mask are recomputed from the coordinates and ``seed``; the workspace holds
+        the slice images alone, comes from torch's allocator and is released on return.  No atomics: the same bits from call to call."""
+        need = tuple(bool(x) for x in need)
+        if len(need) != 4 or not any(need):
+            raise RuntimeError('ddk: eemb_backward needs at least one of its four gradients to compute')
+        t, n, sc = self._eemb_operands(pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, None, p)
+        F, E, dev = n[2], n[4], t[0].device
+        grad_emb = _need_cuda(grad_emb).contiguous().float()
+        if grad_emb.shape != (E, 24) or grad_emb.device != dev:
+            raise RuntimeError(f'ddk: eemb_backward takes grad_emb [E, 24] = {(E, 24)} on the device of pos_a; got {tuple(grad_emb.shape)}')
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        outs = [new(24, F + 64) if need[0] else None, new(24) if need[1] else None, new(24, 24) if need[2] else None, new(24) if need[3] else None]
+        nbytes = self.L.ddk_eemb_workspace(E, F + 64)
+        if nbytes < 0:
+            raise RuntimeError(f'ddk: no edge-embedding workspace for E = {E}, K = {F + 64}')
+        ws = torch.empty(max(int(nbytes), 16) // 4, dtype=torch.float32, device=dev)
+        self._eemb_call(self.L.ddk_eemb_backward, t, n, sc, seed, (_ptr(grad_emb) if E else None, E, *[_ptr(o) for o in outs], _ptr(ws)), 'ddk_eemb_backward')
+        return tuple(outs)      # (ws goes back to torch's allocator, which orders its reuse after these launches on the current stream)
+
     def tp_weight_numel(self, layer):
         """W of conv layer ``layer``: the length of a FasterTensorProduct weight row (tensor_layers.py:56-63)."""
         return tp_layer_shape(layer, self.cfg.ns, self.cfg.nv)['W']

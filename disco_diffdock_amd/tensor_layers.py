@@ -18,6 +18,8 @@ parity tests read like tests of the reference modules:
 * ``fused_head_conv(head, fc, node_attr, edge_index, edge_sh, edge_attr, out_nodes, graph=None, hidden=None)``: lines 153-159 for the two score
   heads (final_conv, tor_bond_conv: ``faster=False``, e3nn's FullyConnectedTensorProduct, one FCBlock) as one differentiable op, no atomics
 * ``gather_rows(x, index, graph=None, side='dst')``: a gather whose backward is a fixed-order segmented sum
+* ``fused_edge_embedding(mlp, expansion, pos_a, pos_b, edge_index, sig, sig_index, feat=None, seed=None)``: one edge group of the embed in front of the
+  conv stack (score_model.py:191-225): the edge embedding [E, ns] and the spherical harmonics from the coordinates, nothing kept per edge
 
 Only the configurations the shipped score models use are implemented on the device (ns=24, nv=6, sh_lmax=1, 2-layer ReLU radial MLP): the conv layers
 (faster=True, edge_groups=4, residual=True) and the two heads (faster=False, edge_groups=1, residual=False); anything else raises.
@@ -26,8 +28,8 @@ Only the configurations the shipped score models use are implemented on the devi
 statistics (plain torch, ``_BatchNormParams.forward``) and the padded residual.  In ``.eval()`` it is the fused inference
 kernel (``ddk_conv_forward``), unchanged.  ``conv_stack`` trains the whole stack of them from the edge embedding with the
 same bits on every run.  In a head configuration the layer is ``fused_head_conv`` plus BatchNorm in training and in evaluation
-(``heads.ScoreHeads`` is the module on top).  What still does not train: ``ddk_score_forward`` end to end, the all-atom /
-confidence irreps, any other ns / nv.
+(``heads.ScoreHeads`` is the module on top); ``train_model.TrainableScoreModel`` assembles the whole model.  What still does not train: the
+latent-conditioned models, the all-atom / confidence irreps, any other ns / nv.
 """
 import math
 
@@ -380,6 +382,94 @@ def conv_stack(conv_layers, node_attr, edge_index, edge_emb, group_sizes, edge_s
         node_attr = layer.forward_embedded(node_attr, edge_index, edge_emb, group_sizes, edge_sh, graph=graph,
                                            seed=None if seed is None else _layer_seed(seed, l))
     return node_attr
+
+
+class _EdgeEmbeddingFunction(torch.autograd.Function):
+    """ddk_eemb_forward with ddk_eemb_backward as its vector-Jacobian product: one edge group's embedding [E, 24] and spherical harmonics [E, 4] from the
+    coordinates.  Saved for the backward: the operands it was given (positions, index tensors, bond features, the sigma table, the four parameters);
+    nothing per edge that the op made itself.  The backward recomputes the hidden layer and the mask from the seed.  Gradients: the four parameters
+    alone, without atomics: the same bits on every run."""
+
+    @staticmethod
+    def forward(fctx, w1, b1, w2, b2, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, p, seed):
+        ctx = _shape_context(pos_a.device.index or 0)
+        emb, sh = ctx.eemb_forward(pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, b2, p, seed)
+        fctx.save_for_backward(w1, b1, w2, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index)      # (b2 is not read by the backward)
+        fctx.ddk, fctx.scalars = ctx, (start, stop, p, seed)
+        fctx.meta = [(t.shape, t.dtype) for t in (w1, b1, w2, b2)]
+        fctx.mark_non_differentiable(sh)
+        return emb, sh
+
+    @staticmethod
+    @once_differentiable
+    def backward(fctx, grad_emb, _grad_sh):
+        w1, b1, w2, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index = fctx.saved_tensors
+        start, stop, p, seed = fctx.scalars
+        need = tuple(fctx.needs_input_grad[:4])
+        with torch.cuda.device(pos_a.device):
+            grads = fctx.ddk.eemb_backward(pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, grad_emb, p, seed, need)
+        return _grads_like(grads, fctx.meta) + (None,) * 11
+
+
+def _smearing_range(expansion):
+    """(start, stop) of a GaussianSmearing of 32 Gaussians whose ``offset`` and ``coeff`` are what the kernels restate from them (include/ddk.h); read
+    back once per buffer and kept on the module"""
+    off = expansion.offset
+    key = (off.data_ptr(), off._version, str(off.device))
+    cached = getattr(expansion, '_ddk_range', None)
+    if cached is None or cached[0] != key:
+        host = off.detach().float().cpu()
+        if host.shape != (32,):
+            raise RuntimeError(f'ddk: fused_edge_embedding takes a distance expansion of 32 Gaussians; got {tuple(host.shape)}')
+        start, stop = float(host[0]), float(host[-1])
+        if not start < stop or not torch.allclose(host, torch.linspace(start, stop, 32), rtol=0, atol=4e-7 * max(abs(start), abs(stop))):
+            raise RuntimeError('ddk: fused_edge_embedding takes a distance expansion whose offset is torch.linspace(start, stop, 32)')
+        coeff = -0.5 / float(host[1] - host[0]) ** 2
+        if abs(float(expansion.coeff) - coeff) > 1e-5 * abs(coeff):
+            raise RuntimeError(f'ddk: fused_edge_embedding takes a distance expansion with coeff = -0.5 / (offset[1] - offset[0])^2 = {coeff}; got {expansion.coeff}')
+        cached = (key, (start, stop))
+        expansion._ddk_range = cached
+    return cached[1]
+
+
+def fused_edge_embedding(mlp, expansion, pos_a, pos_b, edge_index, sig, sig_index, feat=None, seed=None):
+    """One edge group of the reference's embed in front of the conv stack (models/score_model.py:191-225) as one differentiable op:
+    ``edge_emb = mlp(torch.cat([feat, sig[sig_index[edge_index[0]]], expansion(|vec|)], 1))`` and ``edge_sh`` = the first-order spherical harmonics of
+    ``vec = pos_b[edge_index[1]] - pos_a[edge_index[0]]`` (component normalisation: ``[1 | sqrt3 vec / |vec|]``).  ``mlp``: the reference's
+    ``nn.Sequential(Linear(K, 24), ReLU, Dropout, Linear(24, 24))``, K = 64, or 68 with ``feat`` [E, 4]; ``expansion``: a ``GaussianSmearing`` of 32
+    Gaussians; ``sig`` [T, 32]: the sigma embedding per graph, ``sig_index`` [Na] the graph of a node of ``pos_a``.  The positions carry no gradient in
+    score matching: one that requires it raises.  Nothing wider than the outputs is stored per edge, forward or backward; the four parameters of ``mlp``
+    get the same gradient bits on every run (no atomics).  Dropout: rate ``mlp[2].p`` while that module is in training mode, else none; the mask is a
+    pure function of (``seed``, edge position, column), DDK_EEMB_MASK_LAYOUT of include/ddk.h; ``seed=None`` takes one draw from torch's default CPU
+    generator.  Returns (edge_emb [E, 24], edge_sh [E, 4]), fp32."""
+    if (not isinstance(mlp, nn.Sequential) or len(mlp) != 4 or not isinstance(mlp[0], nn.Linear) or not isinstance(mlp[1], nn.ReLU)
+            or not isinstance(mlp[2], nn.Dropout) or not isinstance(mlp[3], nn.Linear) or mlp[0].bias is None or mlp[3].bias is None
+            or mlp[0].out_features != 24 or (mlp[3].in_features, mlp[3].out_features) != (24, 24)):
+        raise RuntimeError('ddk: fused_edge_embedding takes nn.Sequential(Linear(K, 24), ReLU, Dropout, Linear(24, 24)) with biases')
+    K = 64 if feat is None else 68
+    if mlp[0].in_features != K:
+        raise RuntimeError(f'ddk: fused_edge_embedding: the first Linear takes {mlp[0].in_features} columns, the row has {K} (4 bond features with feat, 32 + 32)')
+    if not pos_a.is_cuda:
+        raise RuntimeError('ddk fused_edge_embedding runs on the GPU only (no CPU fallback)')
+    if pos_a.requires_grad or pos_b.requires_grad:
+        raise RuntimeError('ddk: fused_edge_embedding has no gradient for the positions (they carry none in score matching); detach them')
+    if sig.requires_grad or (feat is not None and feat.requires_grad):
+        raise RuntimeError('ddk: fused_edge_embedding has no gradient for sig or feat (times and bond types carry none); detach them')
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise RuntimeError(f'ddk: fused_edge_embedding takes edge_index [2, E]; got {tuple(edge_index.shape)}')
+    p = float(mlp[2].p) if mlp[2].training else 0.0
+    if not 0.0 <= p < 1.0:
+        raise RuntimeError(f'ddk: fused_edge_embedding takes a dropout rate in [0, 1); got {p}')
+    if seed is None:
+        seed = _draw_seed() if p > 0 else 0
+    start, stop = _smearing_range(expansion)
+    idx_a, idx_b = edge_index[0].to(torch.int32).contiguous(), edge_index[1].to(torch.int32).contiguous()
+    operands = (pos_a.detach().float().contiguous(), pos_b.detach().float().contiguous(), idx_a, idx_b, None if feat is None else feat.float().contiguous(),
+                sig.float().contiguous(), sig_index.to(torch.int32).contiguous())
+    w1, b1, w2, b2 = mlp[0].weight, mlp[0].bias, mlp[3].weight, mlp[3].bias
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (w1, b1, w2, b2)):
+        return _EdgeEmbeddingFunction.apply(w1, b1, w2, b2, *operands, start, stop, p, int(seed))
+    return _shape_context(pos_a.device.index or 0).eemb_forward(*operands, start, stop, w1, b1, w2, b2, p, int(seed))
 
 
 class _HeadConvFunction(torch.autograd.Function):

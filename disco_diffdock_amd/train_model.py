@@ -1,0 +1,235 @@
+"""A trainable score model: the reference's ``TensorProductScoreModel`` (models/score_model.py) for the coarse-grained sh_lmax=1 configuration with real
+``nn.Parameter``s under the reference's keys, assembled from the differentiable device ops:
+
+    batch -> graph build (plain torch, no gradient) -> node embeddings (``gather_rows`` + Linear) -> three ``fused_edge_embedding`` calls
+          -> ``conv_stack`` -> ``heads.ScoreHeads`` -> (tr_pred [B, 3], rot_pred [B, 3], tor_pred [sum R])
+
+``state_dict()`` has the keys of ``score_model.TensorProductScoreModel(...).expected_state_dict_spec()`` for the same configuration, so a reference
+checkpoint loads with ``strict=True`` and what was trained here loads into the inference class.  ``.train()`` / ``.eval()`` switch BatchNorm between batch
+statistics and running buffers and switch dropout, as in the layers; in training every parameter gets the same gradient bits on every run for one seed.
+The inference class stays the fast path for sampling: this module is for fine-tuning.
+
+Not covered: the latent-conditioned (``latent_dim > 0``) DisCo and AR models, ``confidence_mode``, the all-atom model, any other ns / nv / sh_lmax."""
+import torch
+from torch import nn
+
+from .diffusion_utils import get_timestep_embedding
+from .heads import ScoreHeads
+from .runtime import DEFAULTS
+from .synthetic import LIG_FEATURE_DIMS, REC_RESIDUE_FEATURE_DIMS
+from .tensor_layers import (GaussianSmearing, TensorProductConvLayer, _draw_seed, _layer_seed, _shape_context, conv_stack, fused_edge_embedding,
+                            gather_rows)
+
+LIG_RADIUS_CAP = 32        # radius_graph's max_num_neighbors default (the self loop rides on top of it)
+CROSS_CAP = 10000          # max_num_neighbors of the cross graph (models/score_model.py:381, 384)
+
+
+def radius(x, y, r, batch_x, batch_y, B, max_num_neighbors=32):
+    """torch_cluster.radius as oracle/cluster_lite.py states it: for every query y_i the x_j of the same graph with |x_j - y_i|^2 < r^2 (strict), in
+    ascending j, the first ``max_num_neighbors`` of them; returns [y index; x index], by y index, then x index.  One window of the query's own graph per
+    query ([Ny, largest graph]), never an Ny x Nx matrix over the batch.  CPU or device tensors."""
+    Nx, Ny = x.shape[0], y.shape[0]
+    if Nx == 0 or Ny == 0:
+        return torch.zeros((2, 0), dtype=torch.long, device=x.device)
+    first, count = ScoreHeads._graph_ranges(batch_x, B)      # (first node, node count) per graph; refuses nodes that are not grouped by graph
+    window = torch.arange(int(count.max()), device=x.device)
+    valid = window[None, :] < count[batch_y][:, None]
+    cand = (first[batch_y][:, None] + window[None, :]).clamp(max=Nx - 1)      # [Ny, largest graph]: the nodes of the query's graph, ascending
+    d2 = ((y[:, None, :] - x[cand]) ** 2).sum(-1)
+    inside = valid & (d2 < float(r) * float(r))
+    keep = inside & (torch.cumsum(inside, 1) <= max_num_neighbors)
+    yy, col = keep.nonzero(as_tuple=True)      # row-major: by query, then by node index
+    return torch.stack([yy, cand[yy, col]])
+
+
+def radius_graph(x, r, batch, B, max_num_neighbors=32):
+    """torch_cluster.radius_graph (flow='source_to_target', no self loops) as oracle/cluster_lite.py states it: [neighbour; centre], by centre, then
+    neighbour; the cap counts the centre itself, so ``max_num_neighbors + 1`` go into ``radius``"""
+    ei = radius(x, x, r, batch, batch, B, max_num_neighbors + 1)
+    row, col = ei[1], ei[0]
+    mask = row != col
+    return torch.stack([row[mask], col[mask]])
+
+
+def build_conv_edges(lig_pos, lig_batch, rec_pos, rec_batch, bond_index, rec_edge_index, B, lig_max_radius, cross_cutoff):
+    """The three edge lists of the reference's embed (models/score_model.py:310-408) for a collated batch, without gradient:
+    ``lig_edge_index`` = [the bonds | radius_graph(lig_pos, lig_max_radius)], ``cross_edge_index`` = radius(rec_pos, lig_pos, cutoff) as [ligand atom;
+    residue] (residue indices NOT yet offset), ``rec_edge_index`` as given.  ``cross_cutoff``: a float, or a [B] tensor of per-graph cutoffs (the
+    reference's dynamic_max_cross: both coordinate sets are divided by their graph's cutoff and the radius is 1).  Returns (lig, cross, rec) edge
+    indices [2, .] (int64) and the number of bond edges in front of the ligand list."""
+    with torch.no_grad():
+        lig_batch, rec_batch = lig_batch.long(), rec_batch.long()
+        radius_edges = radius_graph(lig_pos, lig_max_radius, lig_batch, B, LIG_RADIUS_CAP)
+        lig_ei = torch.cat([bond_index.long(), radius_edges], 1)
+        if torch.is_tensor(cross_cutoff):
+            cut = cross_cutoff.reshape(-1, 1).to(lig_pos.dtype)
+            cross_ei = radius(rec_pos / cut[rec_batch], lig_pos / cut[lig_batch], 1, rec_batch, lig_batch, B, CROSS_CAP)
+        else:
+            cross_ei = radius(rec_pos, lig_pos, cross_cutoff, rec_batch, lig_batch, B, CROSS_CAP)
+        return lig_ei, cross_ei, rec_edge_index.long(), bond_index.shape[1]
+
+
+def combine_edges(lig_ei, cross_ei, rec_ei, n_lig):
+    """the reference's cat order (models/score_model.py:219-225): ligand, cross, receptor, flipped cross over the node table [ligand | receptor];
+    returns (edge_index [2, E], the four group sizes)"""
+    lr = torch.stack([cross_ei[0], cross_ei[1] + n_lig])
+    edge_index = torch.cat([lig_ei, lr, rec_ei + n_lig, torch.flip(lr, dims=[0])], dim=1)
+    return edge_index, (lig_ei.shape[1], lr.shape[1], rec_ei.shape[1], lr.shape[1])
+
+
+class AtomEncoder(nn.Module):
+    """models/layers.py:119-149 (the new AtomEncoder): one embedding table per categorical feature, summed, then a Linear over [sum | scalar features |
+    sigma embedding].  The tables are read through ``gather_rows``: their gradient is a fixed-order segmented sum, not index_add_'s atomics."""
+
+    def __init__(self, emb_dim, feature_dims, sigma_embed_dim, lm_embedding_type=None):
+        super().__init__()
+        self.atom_embedding_list = nn.ModuleList()
+        self.num_categorical_features = len(feature_dims[0])
+        lm = 1280 if lm_embedding_type == 'esm' else 0
+        self.additional_features_dim = feature_dims[1] + sigma_embed_dim + lm
+        for dim in feature_dims[0]:
+            emb = nn.Embedding(dim, emb_dim)
+            nn.init.xavier_uniform_(emb.weight.data)
+            self.atom_embedding_list.append(emb)
+        self.additional_features_embedder = nn.Linear(self.additional_features_dim + emb_dim, emb_dim)
+
+    def forward(self, x_cat, x_scalar):
+        """``x_cat`` [N, categorical features] (integers), ``x_scalar`` [N, additional features] (floats)"""
+        if x_cat.shape[1] != self.num_categorical_features or x_scalar.shape[1] != self.additional_features_dim:
+            raise RuntimeError(f'ddk: AtomEncoder takes {self.num_categorical_features} categorical and {self.additional_features_dim} scalar columns; '
+                               f'got {x_cat.shape[1]} and {x_scalar.shape[1]}')
+        emb = 0
+        for i, table in enumerate(self.atom_embedding_list):
+            emb = emb + gather_rows(table.weight, x_cat[:, i])
+        return self.additional_features_embedder(torch.cat([emb, x_scalar], dim=1))
+
+
+class TrainableScoreModel(nn.Module):
+    """Constructor keywords follow ``score_model.TensorProductScoreModel`` (models/score_model.py:15-24 plus ``embedding_scale`` and ``sigma_limits``).
+    Supported: sh_lmax=1, ns=24, nv=6, latent_dim=0, the new AtomEncoder, 32-wide sigma and distance embeddings, batch_norm / no_torsion /
+    dynamic_max_cross on or off, lm_embedding_type None or 'esm', 3..16 conv layers; anything else raises and names the option."""
+
+    def __init__(self, t_to_sigma=None, device=None, timestep_emb_func=None, in_lig_edge_features=4, sigma_embed_dim=32, sh_lmax=2, ns=16, nv=4,
+                 num_conv_layers=2, lig_max_radius=5, rec_max_radius=30, cross_max_distance=250, center_max_distance=30, distance_embed_dim=32,
+                 cross_distance_embed_dim=32, no_torsion=False, scale_by_sigma=True, use_second_order_repr=False, batch_norm=True,
+                 dynamic_max_cross=False, dropout=0.0, lm_embedding_type=None, confidence_mode=False, use_old_atom_encoder=False, latent_dim=0,
+                 latent_vocab=32, latent_cross_attention=False, latent_droprate=0.0, embedding_scale=1000.0, sigma_limits=None, conv_kernel=None,
+                 confidence_dropout=0, confidence_no_batchnorm=False, num_confidence_outputs=1, new_cross_attention=False, **unused):
+        super().__init__()
+        refused = [('sh_lmax', sh_lmax != 1, 'must be 1'), ('ns', ns != 24, 'must be 24'), ('nv', nv != 6, 'must be 6'),
+                   ('latent_dim', latent_dim != 0, 'must be 0: the latent-conditioned DisCo and AR models are not assembled'),
+                   ('latent_droprate', latent_droprate != 0, 'must be 0'), ('latent_cross_attention', bool(latent_cross_attention), 'is not implemented'),
+                   ('new_cross_attention', bool(new_cross_attention), 'is not implemented'),
+                   ('use_old_atom_encoder', bool(use_old_atom_encoder), 'is not implemented: the new AtomEncoder only'),
+                   ('use_second_order_repr', bool(use_second_order_repr), 'is not implemented'),
+                   ('confidence_mode', bool(confidence_mode), 'is not implemented: the score heads only'),
+                   ('in_lig_edge_features', in_lig_edge_features != 4, 'must be 4'), ('sigma_embed_dim', sigma_embed_dim != 32, 'must be 32'),
+                   ('distance_embed_dim', distance_embed_dim != 32, 'must be 32'), ('cross_distance_embed_dim', cross_distance_embed_dim != 32, 'must be 32'),
+                   ('lm_embedding_type', lm_embedding_type not in (None, 'esm'), "must be None or 'esm'"),
+                   ('num_conv_layers', not 3 <= num_conv_layers <= 16, 'must be in 3..16: the heads read the full 0e + 1o + 1e + 0o rows'),
+                   ('dropout', not 0.0 <= float(dropout) < 1.0, 'must be in [0, 1)'),
+                   ('conv_kernel', conv_kernel is not None, 'selects an inference kernel: it is an option of score_model.TensorProductScoreModel')]
+        for name, bad, why in refused:
+            if bad:
+                raise RuntimeError(f'ddk: TrainableScoreModel: {name} {why}')
+        if unused:
+            raise RuntimeError(f'ddk: TrainableScoreModel: unknown option(s) {sorted(unused)}')
+        keys = ('tr_sigma_min', 'tr_sigma_max', 'rot_sigma_min', 'rot_sigma_max', 'tor_sigma_min', 'tor_sigma_max')
+        lim = {k: float((sigma_limits or DEFAULTS)[k]) for k in keys}
+        self.ns, self.no_torsion, self.dynamic_max_cross = ns, bool(no_torsion), bool(dynamic_max_cross)
+        self.lig_max_radius, self.cross_max_distance = float(lig_max_radius), float(cross_max_distance)
+        self.tr_sigma_min, self.tr_sigma_max = lim['tr_sigma_min'], lim['tr_sigma_max']
+        self.timestep_emb_func = get_timestep_embedding('sinusoidal', sigma_embed_dim, embedding_scale)
+
+        self.lig_node_embedding = AtomEncoder(ns, (LIG_FEATURE_DIMS, 0), sigma_embed_dim)
+        self.lig_edge_embedding = nn.Sequential(nn.Linear(in_lig_edge_features + sigma_embed_dim + distance_embed_dim, ns), nn.ReLU(), nn.Dropout(dropout),
+                                                nn.Linear(ns, ns))
+        self.rec_node_embedding = AtomEncoder(ns, (REC_RESIDUE_FEATURE_DIMS, 0), sigma_embed_dim, lm_embedding_type)
+        self.rec_edge_embedding = nn.Sequential(nn.Linear(sigma_embed_dim + distance_embed_dim, ns), nn.ReLU(), nn.Dropout(dropout), nn.Linear(ns, ns))
+        self.cross_edge_embedding = nn.Sequential(nn.Linear(sigma_embed_dim + cross_distance_embed_dim, ns), nn.ReLU(), nn.Dropout(dropout), nn.Linear(ns, ns))
+        self.rec_distance_expansion = GaussianSmearing(0.0, rec_max_radius, distance_embed_dim)
+        self.cross_distance_expansion = GaussianSmearing(0.0, cross_max_distance, cross_distance_embed_dim)
+
+        seq = [f'{ns}x0e', f'{ns}x0e + {nv}x1o', f'{ns}x0e + {nv}x1o + {nv}x1e', f'{ns}x0e + {nv}x1o + {nv}x1e + {ns}x0o']
+        self.conv_layers = nn.ModuleList([TensorProductConvLayer(in_irreps=seq[min(i, 3)], sh_irreps='1x0e+1x1o', out_irreps=seq[min(i + 1, 3)],
+                                                                 n_edge_features=3 * ns, hidden_features=3 * ns, residual=True, batch_norm=batch_norm,
+                                                                 dropout=dropout, faster=True, edge_groups=4) for i in range(num_conv_layers)])
+
+        # the heads' modules sit at top level, under the reference's keys; the ScoreHeads object that runs them is not a child (no second set of keys)
+        heads = ScoreHeads(ns=ns, nv=nv, sigma_embed_dim=sigma_embed_dim, distance_embed_dim=distance_embed_dim, lig_max_radius=lig_max_radius,
+                           center_max_distance=center_max_distance, dropout=dropout, batch_norm=batch_norm, no_torsion=no_torsion,
+                           scale_by_sigma=scale_by_sigma, embedding_scale=embedding_scale, sigma_limits=lim)
+        for name, module in heads.named_children():
+            setattr(self, name, module)
+        if self.no_torsion:      # (the torsion head owns the ligand's expansion otherwise: one module, one key)
+            self.lig_distance_expansion = GaussianSmearing(0.0, lig_max_radius, distance_embed_dim)
+        object.__setattr__(self, '_heads', heads)
+
+    @property
+    def ctx(self):
+        """the device context the ops run in (what ``training.loss_function`` takes as its ``model``)"""
+        dev = next(self.parameters()).device
+        if dev.type != 'cuda':
+            raise RuntimeError('ddk TrainableScoreModel runs on the GPU only (no CPU fallback)')
+        return _shape_context(dev.index or 0)
+
+    def train(self, mode=True):
+        super().train(mode)
+        self._heads.training = mode      # (its children are this module's children and were switched with them)
+        return self
+
+    def _cross_cutoff(self, complex_t):
+        if not self.dynamic_max_cross:
+            return self.cross_max_distance
+        tr_sigma = self.tr_sigma_min ** (1 - complex_t['tr']) * self.tr_sigma_max ** complex_t['tr']      # diffusion_utils.t_to_sigma
+        return tr_sigma * 3 + 20
+
+    def embed(self, data, seed=None):
+        """models/score_model.py:169-257: (lig_node_attr [N_lig, 84], rec_node_attr [N_rec, 84]) after the conv stack, for a collated batch"""
+        lig, rec = data['ligand'], data['receptor']
+        if not lig.pos.is_cuda:
+            raise RuntimeError('ddk TrainableScoreModel runs on the GPU only (no CPU fallback)')
+        dev, B = lig.pos.device, int(data.num_graphs)
+        complex_t = {k: data.complex_t[k].to(dev).float() for k in ('tr', 'rot', 'tor')}
+        with torch.no_grad():
+            lig_pos, rec_pos = lig.pos.detach().float(), rec.pos.detach().float()
+            lig_batch, rec_batch = lig.batch.to(dev).long(), rec.batch.to(dev).long()
+            sig = self.timestep_emb_func(complex_t['tr'])      # [B, 32]: a node's sigma embedding is its graph's
+            bonds = data['ligand', 'ligand']
+            lig_ei, cross_ei, rec_ei, n_bond = build_conv_edges(lig_pos, lig_batch, rec_pos, rec_batch, bonds.edge_index.to(dev),
+                                                                data['receptor', 'receptor'].edge_index.to(dev), B, self.lig_max_radius,
+                                                                self._cross_cutoff(complex_t))
+            feat = torch.cat([bonds.edge_attr.to(dev).float(), torch.zeros((lig_ei.shape[1] - n_bond, 4), device=dev)], 0)
+            n_lig = lig_pos.shape[0]
+            edge_index, group_sizes = combine_edges(lig_ei, cross_ei, rec_ei, n_lig)
+            lig_idx, rec_idx = lig_batch.to(torch.int32), rec_batch.to(torch.int32)
+            n_cat = self.rec_node_embedding.num_categorical_features
+            rec_x = rec.x.to(dev)
+        if self.training and seed is None:
+            seed = _draw_seed()
+        seeds = [None if seed is None else _layer_seed(seed, len(self.conv_layers) + g) for g in range(3)]      # (the conv layers take 0 .. L - 1)
+
+        lig_node_attr = self.lig_node_embedding(lig.x.to(dev).long(), sig[lig_batch])
+        rec_node_attr = self.rec_node_embedding(rec_x[:, :n_cat].long(), torch.cat([rec_x[:, n_cat:].float(), sig[rec_batch]], 1))
+        lig_emb, lig_sh = fused_edge_embedding(self.lig_edge_embedding, self.lig_distance_expansion, lig_pos, lig_pos, lig_ei, sig, lig_idx, feat=feat,
+                                               seed=seeds[0])
+        lr_emb, lr_sh = fused_edge_embedding(self.cross_edge_embedding, self.cross_distance_expansion, lig_pos, rec_pos, cross_ei, sig, lig_idx, seed=seeds[1])
+        rec_emb, rec_sh = fused_edge_embedding(self.rec_edge_embedding, self.rec_distance_expansion, rec_pos, rec_pos, rec_ei, sig, rec_idx, seed=seeds[2])
+
+        node_attr = torch.cat([lig_node_attr, rec_node_attr], dim=0)
+        edge_emb = torch.cat([lig_emb, lr_emb, rec_emb, lr_emb], dim=0)      # the cross embedding is computed once and serves both directions
+        edge_sh = torch.cat([lig_sh, lr_sh, rec_sh, lr_sh], dim=0)
+        node_attr = conv_stack(self.conv_layers, node_attr, edge_index, edge_emb, group_sizes, edge_sh, seed=seed)
+        return node_attr[:n_lig], node_attr[n_lig:]
+
+    def forward(self, data, seed=None):
+        """``data``: a collated batch in the reference's layout (``data['ligand'].x / .pos / .batch / .edge_mask``, ``data['ligand', 'ligand'].edge_index /
+        .edge_attr``, ``data['receptor'].x / .pos / .batch``, ``data['receptor', 'receptor'].edge_index``, ``data.complex_t`` with the three [B] times,
+        ``data.num_graphs``); the graphs may be different complexes at different times.  ``seed``: of the dropout masks of the device ops (None: one draw
+        from torch's default CPU generator per call in training).  Returns (tr_pred [B, 3], rot_pred [B, 3], tor_pred [sum R])."""
+        lig = data['ligand']
+        lig_node_attr, _ = self.embed(data, seed)
+        dev = lig_node_attr.device
+        complex_t = {k: data.complex_t[k].to(dev).float() for k in ('tr', 'rot', 'tor')}
+        edge_mask = None if self.no_torsion else lig.edge_mask.to(dev)
+        return self._heads(lig_node_attr, lig.pos, lig.batch.to(dev), data['ligand', 'ligand'].edge_index.to(dev), edge_mask, complex_t)

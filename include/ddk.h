@@ -253,6 +253,51 @@ int ddk_hconv_backward(ddk_ctx* ctx, int32_t head, const float* x_nodes, int64_t
  * than the two above, E < 0 or E >= 2^31, n_in or n_out outside 0 .. 2^31 - 1.  Host function, no context. */
 int64_t ddk_hconv_workspace(int32_t head, int64_t E, int64_t n_in, int64_t n_out, int32_t backward);
 
+/* ---- The edge embeddings in front of the conv stack (models/score_model.py:191-225: lig_edge_embedding, cross_edge_embedding, rec_edge_embedding, each
+ *      Linear(K, 24), ReLU, Dropout, Linear(24, 24)) with the edge's first-order spherical harmonics, ONE EDGE GROUP per call, as one op that stores nothing
+ *      per edge besides its two outputs.  For edge e:
+ *        vec       = pos_b[idx_b[e]] - pos_a[idx_a[e]],  d = |vec|
+ *        row       = [ feat[e, 0:F] | sig[sig_index[idx_a[e]], 0:32] | exp(coeff (d - offset_j)^2), j = 0..31 ]            K = F + 64, F = 0 or 4
+ *        hid[e, c] = keep(e, c) ? max(b1[c] + w1[c, :] . row, 0) * s : 0        s = 1.0f / (1.0f - p) in fp32;  p == 0: s = 1, nothing is drawn
+ *        emb[e, :] = b2 + w2 . hid[e, :]                                        sh[e, :] = [1 | sqrt(3) vec / max(d, 1e-12)]
+ *      offset = torch.linspace(start, stop, 32) in fp32 (step = (stop - start) / 31; offset_j = fmaf(step, j, start) for j < 16, fmaf(-step, 31 - j, stop) above) and
+ *      coeff = -0.5 / (offset_1 - offset_0)^2, as GaussianSmearing (models/tensor_layers.py:171-181) states them; n_gauss must be 32.
+ *      pos_a [n_a, 3], pos_b [n_b, 3], feat [E, 4] (NULL with F == 0; F is 0 or 4), sig [n_sig, 32] (the sigma embedding of every graph), w1 [24, K], b1 [24],
+ *      w2 [24, 24], b2 [24], emb [E, 24], sh [E, 4]: DEVICE pointers, fp32, contiguous; feat, sig, emb and sh 16-byte aligned.  idx_a, idx_b: int32 [E];
+ *      sig_index: int32 [n_a], the graph of node a.  The index tables are TRUSTED, as the graph tables of ddk_rconv_forward are.  0 <= p < 1.
+ *      Exact fp32 in a fixed order: the pre-activation is one fmaf chain over the K columns in ascending order that starts from b1[c], emb[e, o] one fmaf
+ *      chain over the 24 hidden columns in ascending order that starts from b2[o].
+ *
+ *      THE DROPOUT MASK is a layout contract like DDK_RHID_MASK_LAYOUT: for a given DDK_EEMB_MASK_LAYOUT it never changes.  keep(e, c) is a pure function of
+ *      (seed, e, c), e the edge's position within the call (callers give every edge group a seed of its own):
+ *        generator  Philox4x32-10 of csrc/k_philox.h;  key (seed_lo, seed_hi);  counter c0 = e_lo, c1 = e_hi, c2 = c / 4, c3 = DDK_EEMB_MASK_TAG
+ *        word       c % 4 of the block's four words;  keep iff u >= p with u = (word >> 8) * 2^-24, compared in fp32
+ *      No allocation, no synchronisation.  E == 0: DDK_OK, no launch. */
+#define DDK_EEMB_MASK_LAYOUT 1
+#define DDK_EEMB_MASK_TAG 0x45454D42u      /* "EEMB" */
+int ddk_eemb_forward(ddk_ctx* ctx, const float* pos_a, int64_t n_a, const float* pos_b, int64_t n_b, const int32_t* idx_a, const int32_t* idx_b,
+                     const float* feat, int32_t F, const float* sig, int64_t n_sig, const int32_t* sig_index, float start, float stop, int32_t n_gauss,
+                     const float* w1, const float* b1, const float* w2, const float* b2, float p, uint64_t seed, int64_t E, float* emb, float* sh,
+                     void* stream);
+
+/* VJP of ddk_eemb_forward for its parameters: the forward's operands (b2 is not read and may be NULL) and grad_emb [E, 24] (16-byte aligned).  There is no
+ * input gradient: positions, times and bond types carry none in score matching.  The forward saves nothing per edge; row, the pre-activation and the mask
+ * are recomputed here from the coordinates and the seed, with the forward's expressions.  grad_w1 [24, K], grad_b1 [24], grad_w2 [24, 24], grad_b2 [24]:
+ * each may be NULL (not computed); all four NULL is DDK_ERR_INVALID.
+ *   ghid[e, c] = fmaf chain over o ascending of grad_emb[e, o] w2[o, c], from 0;  gpre[e, c] = ghid[e, c] * (hid[e, c] != 0 ? s : 0)
+ *   grad_w2 = sum_e grad_emb[e]^T (x) hid[e],  grad_b2 = sum_e grad_emb[e],  grad_w1 = sum_e gpre[e]^T (x) row[e],  grad_b1 = sum_e gpre[e]: per slice of
+ *   rtp-slice-length edges (a function of E alone) a partial image, an fmaf chain over the slice's edges in ascending order, the images added in slice order.
+ * workspace: ddk_eemb_workspace(E, K) bytes of device memory, needed when E > 0: the images [E / slice length + 1][24 (K + 1) + 24 25] and nothing else;
+ * never an [E, .] tensor.  E == 0: the gradients asked for are written as zeros, no kernel is launched.  Outputs must not alias inputs.  No atomics: the
+ * same bits from call to call, on every device, and whichever subset of the outputs is asked for. */
+int ddk_eemb_backward(ddk_ctx* ctx, const float* pos_a, int64_t n_a, const float* pos_b, int64_t n_b, const int32_t* idx_a, const int32_t* idx_b,
+                      const float* feat, int32_t F, const float* sig, int64_t n_sig, const int32_t* sig_index, float start, float stop, int32_t n_gauss,
+                      const float* w1, const float* b1, const float* w2, const float* b2, float p, uint64_t seed, const float* grad_emb, int64_t E,
+                      float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2, void* workspace, void* stream);
+
+/* Bytes of ddk_eemb_backward's workspace: a function of its arguments alone; -1 for K other than 64 and 68, E < 0 or E >= 2^31.  Host function, no context. */
+int64_t ddk_eemb_workspace(int64_t E, int32_t K);
+
 /* The fixed-order segmented sum the radial conv and the head convs add a node's rows with (rtp_seg_kernel of csrc/k_rtp.hip), on its own: the backward of
  * a gather x[index].  nodes[n, :] = rows[order[ptr[n]], :] + rows[order[ptr[n] + 1], :] + ... + rows[order[ptr[n + 1] - 1], :], added in that order, one
  * thread per (node, column); a node without rows: exact zeros.  rows [*, D], nodes [n_nodes, D]: DEVICE, fp32, contiguous, 1 <= D <= 128; order: int32,

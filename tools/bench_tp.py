@@ -31,7 +31,18 @@ times one training step, forward + backward with all gradients, of the two head 
 training batch, 1 200 and 12 000 ligand atoms in ligands of 30 atoms with 8 rotatable bonds each (20 neighbours per bond): (a)
 tensor_layers.fused_head_conv (ddk_hconv_forward / ddk_hconv_backward, k_hconv.hip) and (b) a plain-torch restatement of the same composition, the radial
 MLP, index_select, e3nn's FullyConnectedTensorProduct written out per weight block, index_add_ and the division.  Alternation and medians as --conv; the
-device passes of (a) on their own; the launches per direction."""
+device passes of (a) on their own; the launches per direction.
+
+    python tools/bench_tp.py --embed [--iters 10] [--json out.json]
+times one training step, forward + backward with all four parameter gradients, of one edge group's embedding in front of the conv stack two ways, at
+E = 200 000 and 800 000 edges for K = 64 and K = 68 with dropout 0.1: (a) tensor_layers.fused_edge_embedding (ddk_eemb_forward / ddk_eemb_backward,
+k_eemb.hip: nothing per edge but the outputs, a counter-based mask, no atomics) and (b) the plain-torch composition it replaces (two position gathers,
+the norm, the Gaussian smearing, the gathered sigma embedding, the cat, Linear, ReLU, Dropout, Linear and the spherical harmonics).  Alternation and
+medians as --conv; the peak device memory of one step of each; the device passes of (a) on their own.
+
+    python tools/bench_tp.py --model [--iters 5] [--json out.json]
+times forward + backward of train_model.TrainableScoreModel on a batch of 16 synthetic complexes, and its stages on their own (the graph build, the
+node embeddings, the three edge embeddings, the conv stack, the heads).  Absolute times: there is nothing on the device to compare them with."""
 import argparse, json, os, sys
 import torch
 sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), '..')))
@@ -47,6 +58,8 @@ p.add_argument('--radial', action='store_true')
 p.add_argument('--conv', action='store_true')
 p.add_argument('--hidden', action='store_true')
 p.add_argument('--heads', action='store_true')
+p.add_argument('--embed', action='store_true')
+p.add_argument('--model', action='store_true')
 p.add_argument('--dropout', type=float, default=0.1, help='--hidden: the dropout rate of the FCBlocks')
 p.add_argument('--nodes', type=int, default=None, help='--conv, --hidden: nodes of the graph (default: edges / 25)')
 p.add_argument('--layers', default='0,3', help='--conv: the layer shapes to time')
@@ -441,8 +454,158 @@ def bench_heads():
         json.dump(results, open(a.json, 'w'), indent=1)
 
 
+def bench_embed():
+    import math
+    from disco_diffdock_amd.tensor_layers import GaussianSmearing, _shape_context, fused_edge_embedding
+    ctx = _shape_context(0)
+    results = []
+    for E, K in ((200000, 64), (200000, 68), (800000, 64), (800000, 68)):
+        stop = 5.0 if K == 68 else 30.0
+        n_a, n_b, T = max(1, E // 25), max(1, E // 25), 16
+        torch.manual_seed(0)
+        mlp = torch.nn.Sequential(torch.nn.Linear(K, 24), torch.nn.ReLU(), torch.nn.Dropout(a.dropout), torch.nn.Linear(24, 24)).to(dev).train()
+        expansion = GaussianSmearing(0.0, stop, 32).to(dev)
+        gen = torch.Generator(device=dev).manual_seed(0)
+        pos_a, pos_b = (torch.randn(n, 3, device=dev, generator=gen) * (stop / 4) for n in (n_a, n_b))
+        ei = torch.stack([torch.randint(0, n_a, (E,), device=dev, generator=gen), torch.randint(0, n_b, (E,), device=dev, generator=gen)])
+        sig, sig_index = torch.randn(T, 32, device=dev, generator=gen), torch.randint(0, T, (n_a,), device=dev, generator=gen).to(torch.int32)
+        feat = torch.nn.functional.one_hot(torch.randint(0, 4, (E,), device=dev, generator=gen), 4).float() if K == 68 else None
+        g = torch.randn(E, 24, device=dev, generator=gen)
+        params = list(mlp.parameters())
+
+        def step(fused, seed=None):
+            for t in params:
+                t.grad = None
+            if fused:
+                emb, sh = fused_edge_embedding(mlp, expansion, pos_a, pos_b, ei, sig, sig_index, feat=feat, seed=seed)
+            else:
+                vec = pos_b[ei[1]] - pos_a[ei[0]]
+                d = vec.norm(dim=-1)
+                row = torch.cat(([feat] if feat is not None else []) + [sig[sig_index.long()[ei[0]]], expansion(d)], 1)
+                emb = mlp(row)
+                sh = torch.cat([torch.ones_like(d)[:, None], math.sqrt(3.0) * vec / d.clamp_min(1e-12)[:, None]], 1)
+            emb.backward(g)
+            return sh
+
+        res = {'edges': E, 'K': K, 'dropout': a.dropout, 'outputs_bytes': 4 * E * 28, 'workspace_bytes': ctx.L.ddk_eemb_workspace(E, K)}
+        for name, fused in (('fused_embedding', True), ('composition', False)):
+            step(fused)      # (warm-up: the allocator's blocks, the kernels' code objects)
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            live = torch.cuda.memory_allocated()
+            step(fused)
+            torch.cuda.synchronize()
+            res[name] = {'peak_bytes': torch.cuda.max_memory_allocated() - live}
+        step(True, seed=1)
+        one = [t.grad.clone() for t in params]
+        step(True, seed=1)
+        res['fused_embedding']['gradients_bit_identical_run_to_run'] = all(torch.equal(u, t.grad) for u, t in zip(one, params))
+        times = {'fused_embedding': [], 'composition': []}
+        for _ in range(a.repeats):      # the two paths alternate, so that a drift of the clocks meets both
+            for name, fused in (('fused_embedding', True), ('composition', False)):
+                st, en = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                st.record()
+                for _ in range(a.iters):
+                    step(fused)
+                en.record()
+                torch.cuda.synchronize()
+                times[name].append(st.elapsed_time(en) / a.iters)
+        for name, t in times.items():
+            res[name]['ms'], res[name]['ms_passes'] = sorted(t)[len(t) // 2], t
+        res['fused_over_composition_ms'] = res['fused_embedding']['ms'] / res['composition']['ms']
+        res['fused_over_composition_peak'] = res['fused_embedding']['peak_bytes'] / res['composition']['peak_bytes']
+        with torch.no_grad():      # the device passes on their own (no torch around them)
+            ops = (pos_a, pos_b, ei[0].to(torch.int32), ei[1].to(torch.int32), feat, sig, sig_index, 0.0, stop)
+            w = [t.detach() for t in params]
+            res['kernels_ms'] = {'forward': median_ms(lambda: ctx.eemb_forward(*ops, *w, a.dropout, 1), a.iters, a.repeats),
+                                 'backward': median_ms(lambda: ctx.eemb_backward(*ops, w[0], w[1], w[2], g, a.dropout, 1), a.iters, a.repeats)}
+        print(json.dumps(res), flush=True)
+        results.append(res)
+    if a.json:
+        json.dump(results, open(a.json, 'w'), indent=1)
+
+
+def bench_model():
+    import numpy as np
+    from disco_diffdock_amd import synthetic, train_model
+    from disco_diffdock_amd.data import collate, from_arrays
+    from disco_diffdock_amd.tensor_layers import conv_stack
+    B = 16
+    cs = [synthetic.make_complex(100 + k, n_res=150 + 10 * k) for k in range(B)]
+    b = collate([from_arrays(c) for c in cs]).to(dev)
+    t = torch.linspace(0.1, 0.9, B, device=dev)
+    b.complex_t = {k: t.clone() for k in ('tr', 'rot', 'tor')}
+    torch.manual_seed(0)
+    model = train_model.TrainableScoreModel(sh_lmax=1, ns=24, nv=6, num_conv_layers=5, lig_max_radius=5.0, cross_max_distance=80, dynamic_max_cross=True,
+                                            lm_embedding_type='esm', dropout=a.dropout).to(dev).train()
+    lig, rec = b['ligand'], b['receptor']
+    ct = {k: v.float() for k, v in b.complex_t.items()}
+
+    def edges():
+        return train_model.build_conv_edges(lig.pos, lig.batch, rec.pos, rec.batch, b['ligand', 'ligand'].edge_index, b['receptor', 'receptor'].edge_index, B,
+                                            model.lig_max_radius, model._cross_cutoff(ct))
+
+    lig_ei, cross_ei, rec_ei, _ = edges()
+    edge_index, sizes = train_model.combine_edges(lig_ei, cross_ei, rec_ei, lig.pos.shape[0])
+
+    def full():
+        model.zero_grad(set_to_none=True)
+        tr, rot, tor = model(b, seed=1)
+        (tr.sum() + rot.sum() + tor.sum()).backward()
+
+    def embed_only():
+        model.zero_grad(set_to_none=True)
+        l, r = model.embed(b, seed=1)
+        (l.sum() + r.sum()).backward()
+
+    res = {'complexes': B, 'ligand_atoms': int(lig.pos.shape[0]), 'residues': int(rec.pos.shape[0]), 'edges': dict(zip(('lig', 'cross', 'rec', 'cross_flipped'), sizes)),
+           'dropout': a.dropout, 'parameters': sum(p.numel() for p in model.parameters())}
+    full()
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    live = torch.cuda.memory_allocated()
+    full()
+    torch.cuda.synchronize()
+    res['peak_bytes_of_a_step'] = torch.cuda.max_memory_allocated() - live
+    res['ms'] = {'forward_backward': median_ms(full, a.iters, a.repeats), 'graph_build': median_ms(edges, a.iters, a.repeats),
+                 'embed_forward_backward (graph build, embeddings, conv stack)': median_ms(embed_only, a.iters, a.repeats)}
+    res['ms']['heads_forward_backward (the difference)'] = res['ms']['forward_backward'] - res['ms']['embed_forward_backward (graph build, embeddings, conv stack)']
+    # the edge embeddings and the conv stack on their own, on the batch's graph
+    sig = model.timestep_emb_func(ct['tr'])
+    feat = torch.cat([b['ligand', 'ligand'].edge_attr.float(), torch.zeros((lig_ei.shape[1] - b['ligand', 'ligand'].edge_attr.shape[0], 4), device=dev)], 0)
+    from disco_diffdock_amd.tensor_layers import fused_edge_embedding
+    li, ri = lig.batch.to(torch.int32), rec.batch.to(torch.int32)
+
+    def edge_embeddings():
+        model.zero_grad(set_to_none=True)
+        e0, s0 = fused_edge_embedding(model.lig_edge_embedding, model.lig_distance_expansion, lig.pos, lig.pos, lig_ei, sig, li, feat=feat, seed=1)
+        e1, s1 = fused_edge_embedding(model.cross_edge_embedding, model.cross_distance_expansion, lig.pos, rec.pos, cross_ei, sig, li, seed=2)
+        e2, s2 = fused_edge_embedding(model.rec_edge_embedding, model.rec_distance_expansion, rec.pos, rec.pos, rec_ei, sig, ri, seed=3)
+        (e0.sum() + e1.sum() + e2.sum()).backward()
+        return torch.cat([e0, e1, e2, e1]).detach(), torch.cat([s0, s1, s2, s1])
+
+    emb, sh = edge_embeddings()
+    x0 = torch.randn(lig.pos.shape[0] + rec.pos.shape[0], 24, device=dev)
+
+    def stack():
+        model.zero_grad(set_to_none=True)
+        conv_stack(model.conv_layers, x0, edge_index, emb, sizes, sh, seed=1).sum().backward()
+
+    res['ms']['edge_embeddings_forward_backward'] = median_ms(edge_embeddings, a.iters, a.repeats)
+    res['ms']['conv_stack_forward_backward'] = median_ms(stack, a.iters, a.repeats)
+    print(json.dumps(res), flush=True)
+    if a.json:
+        json.dump(res, open(a.json, 'w'), indent=1)
+
+
 if a.heads:
     bench_heads()
+    sys.exit(0)
+if a.embed:
+    bench_embed()
+    sys.exit(0)
+if a.model:
+    bench_model()
     sys.exit(0)
 if a.hidden:
     bench_hidden()
