@@ -65,7 +65,9 @@ SYMBOLS = ['ddk_create', 'ddk_destroy', 'ddk_last_error', 'ddk_version', 'ddk_lo
            'ddk_ligand_transformation_mask_workspace', 'ddk_ligand_transformation_mask',
            'ddk_rng_noise', 'ddk_rng_initial', 'ddk_rng_uniform',
            'ddk_so3_rows', 'ddk_torus_score', 'ddk_rng_perturbation', 'ddk_score_matching_loss',
-           'ddk_conformer_match_workspace', 'ddk_conformer_rmsd', 'ddk_conformer_match']
+           'ddk_conformer_match_workspace', 'ddk_conformer_rmsd', 'ddk_conformer_match',
+           'ddk_rng_perturbation_batch', 'ddk_rng_forward_times', 'ddk_modify_conformer_batch', 'ddk_score_matching_loss_batch',
+           'ddk_score_matching_loss_batch_backward']
 
 # test hooks (include/ddk_debug.h): not part of the drop-in boundary
 DEBUG_SYMBOLS = ['ddk_debug_export', 'ddk_debug_read_edges', 'ddk_debug_conf_counts', 'ddk_debug_conf_table', 'ddk_debug_conf_nodes', 'ddk_debug_conf_edges', 'ddk_debug_kabsch', 'ddk_debug_axis_angle', 'ddk_debug_set_layer0_dedup', 'ddk_debug_read_patch', 'ddk_debug_split3', 'ddk_debug_conv_trace', 'ddk_debug_pool_stats', 'ddk_debug_set_conv_workgroups', 'ddk_debug_set_alloc_limit', 'ddk_debug_cross_mirror']
@@ -152,6 +154,12 @@ def lib():
     L.ddk_torus_score.argtypes = [vp, i64, vp, i32, vp, vp]
     L.ddk_rng_perturbation.argtypes = [vp, u64, u64, i32, i32, i32, i32, f32, f32, i32, vp, vp, C.POINTER(ddk_perturbation), vp]
     L.ddk_score_matching_loss.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, f32, f32, f32, vp, vp]
+    # the ragged batch forms: ctx, [seed,] G, per-graph device tables ...
+    L.ddk_rng_perturbation_batch.argtypes = [vp, u64, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, C.POINTER(ddk_perturbation), vp]
+    L.ddk_rng_forward_times.argtypes = [vp, u64, i32, vp, i32, i32, vp]
+    L.ddk_modify_conformer_batch.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.ddk_score_matching_loss_batch.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.ddk_score_matching_loss_batch_backward.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.ddk_conformer_match_workspace.argtypes = [i32, i32, i32, i32]
     L.ddk_conformer_match_workspace.restype = i64
     L.ddk_conformer_rmsd.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]

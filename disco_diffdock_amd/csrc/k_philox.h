@@ -24,7 +24,7 @@ constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;      // mul
 constexpr uint32_t PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;      // Weyl constants of the key schedule
 
 // the purposes of DDK_RNG_LAYOUT 1 (bits 28..31 of counter word 3)
-// (6-8 are the forward process, RngForwardPurpose of k_noising.hip; 9 and 10 the conformer matching's search, k_match.hip)
+// (6-8 and 11 are the forward process, RngForwardPurpose of k_noising.hip; 9 and 10 the conformer matching's search, k_match.hip)
 enum RngPurpose : uint32_t { RNG_NOISE = 0, RNG_INIT_TORSION = 1, RNG_INIT_ROTATION = 2, RNG_INIT_TRANSLATION = 3, RNG_AR_PICK = 4, RNG_AR_ROTATION = 5,
                              RNG_MATCH_POPULATION = 9, RNG_MATCH_GENERATION = 10 };
 constexpr int RNG_MAX_STEPS = 1 << 20;      // step < 2^20

@@ -253,6 +253,123 @@ __global__ __launch_bounds__(256) void se3_update_kernel(Se3Args A, HeadArgs H) 
   }
 }
 
+// modify_conformer (utils/diffusion_utils.py) for a RAGGED batch, one workgroup per graph (include/ddk.h: ddk_modify_conformer_batch): graph g has its own
+// atom count, rotor table and mask block, found through node_ptr / tor_ptr / mask_ptr.  From the load of the coordinates on this is se3_update_kernel<false,
+// false> with B = 1, score_coeff = 1 and no noise, expression for expression (the update of component k is `score + 0.0f`, what 1 * score + 0 rounds to), so a
+// graph gets the bits ddk_se3_update gives the same ligand alone; that kernel is not touched.  Before any table entry becomes an address the workgroup
+// checks it; status_out[g]: 0 done; 2 a bond index outside [0, n_g) or u == v; 3 a coordinate that is not finite; 4 a node_ptr / tor_ptr / mask_ptr entry
+// that is no range of the arrays or breaks a limit.  With a status other than 0 the graph's rows of pos_out are not written.
+__global__ __launch_bounds__(256) void modify_conformer_batch_kernel(ConformerBatchArgs A) {
+  __shared__ float rig[MAX_LIG * 3], flx_a[MAX_LIG * 3], flx2[MAX_LIG * 3];
+  __shared__ float upd[6], ctr[3], Rm[9], cA[3], cB[3], Rk[9], tk[3], rot_th[64];
+  __shared__ int2 rot_uv[64];
+  __shared__ double S[9];
+  float* flx = flx_a;
+  const int g = blockIdx.x, tid = threadIdx.x;
+  const int n0 = A.node_ptr[g], n = A.node_ptr[g + 1] - n0;
+  bool tables_ok = n0 >= 0 && n >= 1 && n <= MAX_LIG && n0 <= A.N - n;
+  int R = 0, t0 = 0, m0 = 0;
+  if (A.tor != nullptr) {
+    t0 = A.tor_ptr[g]; R = A.tor_ptr[g + 1] - t0; m0 = A.mask_ptr[g];
+    tables_ok = tables_ok && t0 >= 0 && R >= 0 && R <= NOISE_BATCH_MAX_ROT && t0 <= A.T - R && m0 >= 0 && A.mask_ptr[g + 1] - m0 == R * n &&
+                m0 <= A.mask_bytes - R * n;
+  }
+  if (!tables_ok) {      // (the same in every thread: the block leaves as one)
+    if (tid == 0) A.status_out[g] = 4;
+    return;
+  }
+  const float* pos = A.pos + (size_t)n0 * 3;
+  float* pos_out = A.pos_out + (size_t)n0 * 3;
+  const int32_t* bonds = A.rot_bonds + (size_t)t0 * 2;
+  const uint8_t* mask_rotate = A.mask_rotate + m0;
+  const float* tor = A.tor != nullptr ? A.tor + t0 : nullptr;
+  int bad_pos = 0, bad_bond = 0;
+  for (int i = tid; i < n * 3; i += 256) {
+    const float v = pos[i];
+    rig[i] = v;
+    bad_pos |= !isfinite(v);
+  }
+  for (int r = tid; r < R; r += 256) {
+    const int u = bonds[2 * r], v = bonds[2 * r + 1];
+    bad_bond |= u < 0 || u >= n || v < 0 || v >= n || u == v;
+  }
+  if (tid < 6) upd[tid] = (tid < 3 ? A.tr : A.rot)[3 * g + tid % 3] + 0.0f;
+  bad_pos = __syncthreads_or(bad_pos);
+  bad_bond = __syncthreads_or(bad_bond);
+  if (bad_pos || bad_bond) {
+    if (tid == 0) A.status_out[g] = bad_bond ? 2 : 3;
+    return;
+  }
+  if (tid == 0) A.status_out[g] = 0;
+  if (tid < 64) {
+    const double s = component_sum_wave0(rig, n, tid);
+    if (tid < 3) ctr[tid] = (float)(s / (double)n);
+  }
+  if (tid == 64) axis_angle_to_matrix_dev(upd[3], upd[4], upd[5], Rm);
+  __syncthreads();
+  if (tid < n) {      // centred coordinates from here to the last line (se3_update_kernel says why)
+    const float x = rig[3 * tid] - ctr[0], y = rig[3 * tid + 1] - ctr[1], z = rig[3 * tid + 2] - ctr[2];
+    const float rx = Rm[0] * x + Rm[1] * y + Rm[2] * z;
+    const float ry = Rm[3] * x + Rm[4] * y + Rm[5] * z;
+    const float rz = Rm[6] * x + Rm[7] * y + Rm[8] * z;
+    rig[3 * tid] = rx; rig[3 * tid + 1] = ry; rig[3 * tid + 2] = rz;
+    flx[3 * tid] = rx; flx[3 * tid + 1] = ry; flx[3 * tid + 2] = rz;
+  }
+  __syncthreads();
+  if (tor == nullptr || R == 0) {
+    for (int i = tid; i < n * 3; i += 256) pos_out[i] = rig[i] + upd[i % 3] + ctr[i % 3];
+    return;
+  }
+  float* cur = flx;
+  float* nxt = flx2;
+  for (int r0 = 0; r0 < R; r0 += 64) {
+    const int chunk = min(64, R - r0);
+    if (tid < chunk) {
+      const int r = r0 + tid;
+      rot_uv[tid] = make_int2(bonds[2 * r], bonds[2 * r + 1]);
+      rot_th[tid] = tor[r] + 0.0f;
+    }
+    unsigned long long mbits = 0ull;
+    if (tid < n)
+      for (int k = 0; k < chunk; ++k) mbits |= (unsigned long long)(mask_rotate[(size_t)(r0 + k) * n + tid] != 0) << k;
+    __syncthreads();
+    for (int k = 0; k < chunk; ++k) {
+      if (tid < n) {
+        const int2 uv = rot_uv[k];
+        const float th = rot_th[k];
+        const float px = cur[3 * uv.y], py = cur[3 * uv.y + 1], pz = cur[3 * uv.y + 2];
+        float x = cur[3 * tid], y = cur[3 * tid + 1], z = cur[3 * tid + 2];
+        if ((mbits >> k) & 1ull) {
+          const float ax = cur[3 * uv.x] - px, ay = cur[3 * uv.x + 1] - py, az = cur[3 * uv.x + 2] - pz;
+          const float nn = sqrtf(ax * ax + ay * ay + az * az);
+          float Rl[9];
+          axis_angle_to_matrix_dev(ax / nn * th, ay / nn * th, az / nn * th, Rl);
+          x -= px; y -= py; z -= pz;
+          const float nx = Rl[0] * x + Rl[1] * y + Rl[2] * z + px, ny = Rl[3] * x + Rl[4] * y + Rl[5] * z + py, nz_ = Rl[6] * x + Rl[7] * y + Rl[8] * z + pz;
+          x = nx; y = ny; z = nz_;
+        }
+        nxt[3 * tid] = x; nxt[3 * tid + 1] = y; nxt[3 * tid + 2] = z;
+      }
+      __syncthreads();
+      float* t_ = cur; cur = nxt; nxt = t_;
+    }
+  }
+  flx = cur;
+  kabsch_block(flx, rig, n, cA, cB, S, Rk, tk);
+  if (tid < n) {
+    const float x = flx[3 * tid], y = flx[3 * tid + 1], z = flx[3 * tid + 2];
+    float* o = pos_out + (size_t)tid * 3;
+    o[0] = Rk[0] * x + Rk[1] * y + Rk[2] * z + tk[0] + upd[0] + ctr[0];
+    o[1] = Rk[3] * x + Rk[4] * y + Rk[5] * z + tk[1] + upd[1] + ctr[1];
+    o[2] = Rk[6] * x + Rk[7] * y + Rk[8] * z + tk[2] + upd[2] + ctr[2];
+  }
+}
+
+hipError_t launch_modify_conformer_batch(const ConformerBatchArgs& A, hipStream_t s) {
+  hipLaunchKernelGGL(modify_conformer_batch_kernel, dim3(A.G), dim3(256), 0, s, A);
+  return hipGetLastError();
+}
+
 // randomize_position (utils/sampling.py:12-34) for B copies of one conformer, one workgroup per sample:
 // sequential torsion updates in bond order (utils/torsion.py:48-68: axis pos_u - pos_v, pivot pos_v, zero updates skipped),
 // then (pos - centroid) R^T + tr with the caller's rotation matrix and translation draw.
@@ -410,3 +527,28 @@ hipError_t launch_se3(const Se3Args& A, hipStream_t s, const HeadArgs* post) {
 }
 
 }  // namespace ddk
+
+extern "C" int ddk_modify_conformer_batch(ddk_ctx* ctx, int32_t G, int32_t N, const float* pos, const int32_t* node_ptr, int32_t T, const int32_t* rot_bonds,
+                                          const uint8_t* mask_rotate, const int32_t* mask_ptr, int32_t mask_bytes, const int32_t* tor_ptr,
+                                          const float* tr_update, const float* rot_update, const float* tor_update, float* pos_out, int32_t* status_out,
+                                          void* stream) {
+  using namespace ddk;
+  if (!ctx) return DDK_ERR_INVALID;
+  if (ctx->host_only) return fail(ctx, DDK_ERR_STATE, "host-only context (device < 0) cannot launch kernels");
+  if (G < 1 || G > NOISE_BATCH_MAX_GRAPHS)
+    return fail(ctx, DDK_ERR_INVALID, "ddk_modify_conformer_batch: G must be in [1, " + std::to_string(NOISE_BATCH_MAX_GRAPHS) + "]");
+  if (N < G || (int64_t)N > (int64_t)G * MAX_LIG)
+    return fail(ctx, DDK_ERR_INVALID, "ddk_modify_conformer_batch: N must be in [G, G * " + std::to_string(MAX_LIG) + "] (n_lig of a graph is in [1, " +
+                                          std::to_string(MAX_LIG) + "])");
+  if (T < 0 || (int64_t)T > (int64_t)G * NOISE_BATCH_MAX_ROT)
+    return fail(ctx, DDK_ERR_INVALID, "ddk_modify_conformer_batch: T must be in [0, G * " + std::to_string(NOISE_BATCH_MAX_ROT) + "]");
+  if (mask_bytes < 0) return fail(ctx, DDK_ERR_INVALID, "ddk_modify_conformer_batch: mask_bytes must be >= 0");
+  if (!pos || !node_ptr || !tr_update || !rot_update) return fail(ctx, DDK_ERR_INVALID, "ddk_modify_conformer_batch: null argument (pos, node_ptr, tr_update, rot_update)");
+  if (!pos_out || !status_out) return fail(ctx, DDK_ERR_INVALID, "ddk_modify_conformer_batch: null output (pos_out, status_out)");
+  if (tor_update && (!tor_ptr || !mask_ptr || (T > 0 && (!rot_bonds || !mask_rotate))))
+    return fail(ctx, DDK_ERR_INVALID, "ddk_modify_conformer_batch: tor_update without the rotor tables (tor_ptr, mask_ptr, and with T > 0 rot_bonds, mask_rotate)");
+  ConformerBatchArgs A{pos, node_ptr, tor_ptr, mask_ptr, rot_bonds, mask_rotate, tr_update, rot_update, tor_update, G, N, T, mask_bytes, pos_out, status_out};
+  hipError_t e = launch_modify_conformer_batch(A, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "modify_conformer_batch launch");
+  return DDK_OK;
+}

@@ -353,6 +353,22 @@ hipError_t launch_rng_initial(uint64_t seed, uint64_t stream_id, int sample0, in
                               float* tr_out, hipStream_t s);
 hipError_t launch_rng_uniform(uint64_t seed, uint64_t stream_id, int sample0, int B, int decoding_idx, float* out, hipStream_t s);
 
+// k_noising.hip / k_se3.hip: the ragged batch forms of the forward process (ddk_rng_perturbation_batch, ddk_modify_conformer_batch, ddk_score_matching_loss_batch)
+constexpr int NOISE_BATCH_MAX_GRAPHS = 65536;    // graphs of one call: one workgroup (or wave) each
+constexpr int NOISE_BATCH_MAX_ROWS = 4096;       // rows of the caller's IGSO(3) tables (ddk_so3_rows' own limit)
+constexpr int NOISE_BATCH_MAX_ROT = 1024;        // rotors of one graph = RNG_MAX_COLS of k_philox.h, the limit of ddk_rng_perturbation
+struct ConformerBatchArgs {
+  const float* pos;               // [N, 3]
+  const int32_t *node_ptr, *tor_ptr, *mask_ptr;      // [G + 1] each
+  const int32_t* rot_bonds;       // [T, 2] graph-local (u, v)
+  const uint8_t* mask_rotate;     // the graphs' [R_g, n_g] blocks, graph g at mask_ptr[g]
+  const float *tr, *rot, *tor;    // [G, 3], [G, 3], [T] or null (rigid moves only)
+  int G, N, T, mask_bytes;
+  float* pos_out;                 // [N, 3]
+  int32_t* status_out;            // [G]
+};
+hipError_t launch_modify_conformer_batch(const ConformerBatchArgs& A, hipStream_t s);
+
 int conf_model_finalize(ddk_ctx* ctx);   // conf.hip (all-atom confidence model)
 void conf_complex_free(ddk_complex* cx);
 void conf_model_destroy(ddk_ctx* ctx);

@@ -54,6 +54,11 @@ RNG_PURPOSES = dict(noise=0, initial_torsion=1, initial_rotation=2, initial_tran
 RNG_MAX_STEPS, RNG_MAX_COLS = 1 << 20, 1024
 # the purposes of the forward process (ddk_rng_perturbation, csrc/k_noising.hip), in the same counter field; their step field holds the draw index
 RNG_FORWARD_PURPOSES = dict(forward_translation=6, forward_rotation=7, forward_torsion=8)
+# the diffusion time of a complex for one noising (ddk_rng_forward_times): step = the draw index, block 0, word 0
+RNG_TIME_PURPOSE = 11
+# the ragged batch forms (ddk_rng_perturbation_batch, ddk_modify_conformer_batch, ddk_score_matching_loss_batch): limits (csrc/model.h) and status words
+NOISE_BATCH_MAX_GRAPHS, NOISE_BATCH_MAX_LIG, NOISE_BATCH_MAX_ROT = 65536, 256, 1024
+CONFORMER_BATCH_STATUS = ('done', None, 'a bond index outside the graph, or u == v', 'a coordinate that is not finite', 'a node_ptr / tor_ptr / mask_ptr entry out of range')
 # conformer matching (ddk_conformer_match, csrc/k_match.hip): the purposes of its population and generation draws, its limits (csrc/model.h), the words of its status
 RNG_MATCH_PURPOSES = dict(match_population=9, match_generation=10)
 MATCH_MAX_ROT, MATCH_MAX_POPSIZE, MATCH_MAX_ITER, MATCH_MAX_POLISH, MATCH_MAX_ISLANDS, MATCH_MAX_MEMBERS, MATCH_MAX_VECTORS = 128, 64, 1000, 1024, 16, 8192, 65536
@@ -1014,6 +1019,167 @@ class Context:
                                                    _ptr(tor_score), float(tr_sigma), float(so3_score_norm), float(torus_score_norm2), _ptr(out),
                                                    _stream()), 'ddk_score_matching_loss')
         return out
+
+    # ---- the same for a ragged batch of different complexes at different times (ddk_*_batch of include/ddk.h) -------------
+    def _dev(self, a, dtype):
+        """host array or tensor -> contiguous device tensor of ``dtype`` (a device tensor passes through without a copy when it already is one)"""
+        dev = torch.device('cuda', self.device)
+        t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(np.asarray(a), dtype=np.dtype(str(dtype).replace('torch.', ''))))
+        return h2d_async(t.to(dtype).contiguous(), dev)
+
+    @staticmethod
+    def _check_ptr(name, ptr, total, what):
+        """a prefix table given as a HOST array is checked here (a device tensor is checked by the kernel that reads it): starts at 0, never decreases,
+        ends at the length of the array it cuts"""
+        if torch.is_tensor(ptr) and ptr.is_cuda:
+            return
+        p = np.asarray(ptr.cpu() if torch.is_tensor(ptr) else ptr, dtype=np.int64).reshape(-1)
+        if p.size < 2 or p[0] != 0 or (np.diff(p) < 0).any() or (total is not None and p[-1] != total):
+            raise ValueError(f'ddk: {name} must be a non-decreasing prefix [G + 1] from 0 to {total if total is not None else "its total"} ({what}), got {p.tolist()}')
+
+    def so3_table(self):
+        """The whole IGSO(3) table, (cdf, score) float64 [1000, 2000] on the device (32 MB), computed by ddk_so3_rows on first use and kept on the context: a
+        batch's ``so3_row`` entries are then the eps indices themselves, and a second batch pays nothing for its rows."""
+        if getattr(self, '_so3_table', None) is None:
+            cdf, score, _ = self.so3_rows(np.arange(SO3_N_EPS), exp_score_norm=False)
+            self._so3_table = (cdf, score)
+        return self._so3_table
+
+    def forward_times(self, seed, streams, draw=0, sample=0):
+        """t in [0, 1) of each complex of ``streams`` (:func:`stream_id` values) for noising ``draw`` (ddk_rng_forward_times, purpose RNG_TIME_PURPOSE):
+        a float32 host array; computed on the host, no kernel."""
+        for k, v in dict(draw=draw, sample=sample).items():
+            if not -(1 << 31) <= int(v) < 1 << 31:
+                raise ValueError(f'ddk: {k} = {v} does not fit an int32')
+        st = np.ascontiguousarray([_u64(v, 'rng_stream') for v in streams], dtype=np.uint64)
+        out = np.empty(st.size, dtype=np.float32)
+        self._check(self.L.ddk_rng_forward_times(self.h, C.c_uint64(_u64(seed, 'seed')), st.size, st.ctypes.data_as(C.c_void_p), int(sample), int(draw),
+                                                 out.ctypes.data_as(C.c_void_p)), 'ddk_rng_forward_times')
+        return out
+
+    def rng_perturbation_batch(self, seed, streams, samples, tor_ptr, tr_sigma, tor_sigma, torus_sigma_idx, so3_row, so3_cdf_rows, so3_score_rows=None,
+                               draw=0, scores=True, T=None):
+        """One noising of G graphs, each at its own noise level (ddk_rng_perturbation_batch): :data:`Perturbation` with tr / rot [G, 3] and the torsion
+        members flat [T].  The per-graph tables (``streams`` uint64, ``samples`` / ``tor_ptr`` [G + 1] / ``torus_sigma_idx`` / ``so3_row`` int32, the two
+        sigmas float32) are device tensors, or host arrays that are uploaded; ``T`` = tor_ptr[G] as a host integer (needed when tor_ptr is a device
+        tensor).  ``so3_cdf_rows`` / ``so3_score_rows``: float64 [n_rows, 2000] (:meth:`so3_table` or :meth:`so3_rows`).  No read-back."""
+        if T is None:
+            if torch.is_tensor(tor_ptr) and tor_ptr.is_cuda:
+                raise ValueError('ddk: rng_perturbation_batch needs T (= tor_ptr[G]) as a host integer when tor_ptr is a device tensor')
+            T = int(np.asarray(tor_ptr).reshape(-1)[-1])
+        self._check_ptr('tor_ptr', tor_ptr, T, 'the rotor counts of the graphs')
+        s, _, dev = self._rng_args(seed, 0, dict(draw=draw, T=T))
+        st = self._dev(np.asarray([_u64(v, 'rng_stream') for v in streams], dtype=np.uint64).view(np.int64), torch.int64) if not torch.is_tensor(streams) else streams
+        G = st.numel()
+        i32 = [self._dev(a, torch.int32) for a in (samples, tor_ptr, torus_sigma_idx, so3_row)]
+        f32 = [self._dev(a, torch.float32) for a in (tr_sigma, tor_sigma)]
+        for name, t, n in (('samples', i32[0], G), ('tor_ptr', i32[1], G + 1), ('torus_sigma_idx', i32[2], G), ('so3_row', i32[3], G), ('tr_sigma', f32[0], G),
+                           ('tor_sigma', f32[1], G)):
+            if t.numel() != n:
+                raise ValueError(f'ddk: {name} must hold {n} entries for {G} graphs, got {t.numel()} (the library reads it through a raw pointer)')
+        rows = []
+        for name, t in (('so3_cdf_rows', so3_cdf_rows), ('so3_score_rows', so3_score_rows)):
+            if t is not None:
+                t = _need_cuda(t).contiguous()
+                if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != SO3_X_N:
+                    raise ValueError(f'ddk: {name} must be a float64 tensor [n_rows, {SO3_X_N}] (rows of so3_rows)')
+            rows.append(t)
+        n_rows = rows[0].shape[0] if rows[0] is not None else 0
+        if rows[1] is not None and rows[1].shape[0] != n_rows:
+            raise ValueError('ddk: so3_cdf_rows and so3_score_rows must have the same number of rows')
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        Ts = max(T, 0)
+        out = Perturbation(new(G, 3), new(G, 3), new(Ts), *([new(G, 3), new(G, 3), new(Ts)] if scores else [None] * 3))
+        c_out = _lib.ddk_perturbation(**{k: (v.data_ptr() if v is not None and v.numel() else None) for k, v in out._asdict().items()})
+        self._check(self.L.ddk_rng_perturbation_batch(self.h, s, G, _ptr(st), _ptr(i32[0]), _ptr(i32[1]), T, draw, _ptr(f32[0]), _ptr(f32[1]), _ptr(i32[2]),
+                                                      _ptr(i32[3]), n_rows, _ptr(rows[0]), _ptr(rows[1]), C.byref(c_out), _stream()),
+                    'ddk_rng_perturbation_batch')
+        return out
+
+    def modify_conformer_batch(self, pos, node_ptr, rot_bonds, mask_rotate, mask_ptr, tor_ptr, tr_update, rot_update, tor_update, T=None, return_status=False):
+        """modify_conformer for a ragged batch (ddk_modify_conformer_batch): ``pos`` [N, 3] with graph g's atoms at node_ptr[g] .. node_ptr[g + 1],
+        ``rot_bonds`` [T, 2] graph-local (u, v), ``mask_rotate`` the graphs' [R_g, n_g] byte blocks back to back with graph g's at mask_ptr[g], the updates
+        [G, 3], [G, 3] and flat [T] (None: rigid moves only).  Returns pos_out [N, 3]; with ``return_status`` also the int32 status [G]
+        (CONFORMER_BATCH_STATUS; a graph with a status other than 0 is not written).  Host arrays are uploaded; nothing is read back."""
+        dev = torch.device('cuda', self.device)
+        pos = self._dev(pos, torch.float32).reshape(-1, 3)
+        self._check_ptr('node_ptr', node_ptr, pos.shape[0], 'the nodes must be grouped by graph')
+        node_ptr = self._dev(node_ptr, torch.int32)
+        G, N = node_ptr.numel() - 1, pos.shape[0]
+        tr_update, rot_update = self._dev(tr_update, torch.float32), self._dev(rot_update, torch.float32)
+        for name, t in (('tr_update', tr_update), ('rot_update', rot_update)):
+            if t.numel() != 3 * G:
+                raise ValueError(f'ddk: {name} must be [{G}, 3] for {G} graphs, got {tuple(t.shape)} (the library reads it through a raw pointer)')
+        rb = mr = mp = tp = tor = None
+        mask_bytes = 0
+        if tor_update is not None:
+            tor = self._dev(tor_update, torch.float32).reshape(-1)
+            T = tor.numel() if T is None else int(T)
+            rb = self._dev(rot_bonds, torch.int32).reshape(-1, 2)
+            mr = self._dev(mask_rotate, torch.uint8).reshape(-1)
+            self._check_ptr('tor_ptr', tor_ptr, T, 'the rotor counts of the graphs')
+            self._check_ptr('mask_ptr', mask_ptr, None, 'the mask blocks of the graphs')
+            mp, tp = self._dev(mask_ptr, torch.int32), self._dev(tor_ptr, torch.int32)
+            mask_bytes = mr.numel()
+            for name, t, n in (('tor_update', tor, T), ('rot_bonds', rb, 2 * T), ('mask_ptr', mp, G + 1), ('tor_ptr', tp, G + 1)):
+                if t.numel() != n:
+                    raise ValueError(f'ddk: {name} must hold {n} entries (G = {G}, T = {T}), got {t.numel()} (the library reads it through a raw pointer)')
+        out = torch.empty_like(pos)
+        status = torch.empty(max(G, 1), dtype=torch.int32, device=dev)
+        self._rng_args(0, 0, dict(G=G, N=N, T=T or 0, mask_bytes=mask_bytes))
+        self._check(self.L.ddk_modify_conformer_batch(self.h, G, N, _ptr(pos), _ptr(node_ptr), T or 0, _ptr(rb), _ptr(mr), _ptr(mp), mask_bytes, _ptr(tp),
+                                                      _ptr(tr_update), _ptr(rot_update), _ptr(tor), _ptr(out), _ptr(status), _stream()),
+                    'ddk_modify_conformer_batch')
+        return (out, status) if return_status else out
+
+    def _loss_batch_args(self, tr_pred, rot_pred, tor_pred, tr_score, rot_score, tor_score, tr_sigma, so3_score_norm, torus_score_norm2, tor_ptr, T):
+        f = lambda t, cols: _need_cuda(t).contiguous().float().reshape(-1, cols)
+        tr_pred, rot_pred, tr_score, rot_score = (f(t, 3) for t in (tr_pred, rot_pred, tr_score, rot_score))
+        G = tr_score.shape[0]
+        T = int(T)
+        if tor_pred is not None and tor_score is not None and T > 0:
+            tor_pred, tor_score = f(tor_pred, 1).reshape(-1), f(tor_score, 1).reshape(-1)
+        else:
+            tor_pred = tor_score = None
+        scal = [self._dev(a, torch.float32).reshape(-1) for a in (tr_sigma, so3_score_norm, torus_score_norm2)]
+        self._check_ptr('tor_ptr', tor_ptr, T, 'the rotor counts of the graphs')
+        tor_ptr = self._dev(tor_ptr, torch.int32).reshape(-1)
+        for name, t, n in (('tr_pred', tr_pred, 3 * G), ('rot_pred', rot_pred, 3 * G), ('rot_score', rot_score, 3 * G), ('tor_pred', tor_pred, T),
+                           ('tor_score', tor_score, T), ('tr_sigma', scal[0], G), ('so3_score_norm', scal[1], G), ('torus_score_norm2', scal[2], G),
+                           ('tor_ptr', tor_ptr, G + 1)):
+            if t is not None and t.numel() != n:
+                raise ValueError(f'ddk: {name} must hold {n} values (G = {G}, T = {T}), got {t.numel()} (the library reads it through a raw pointer)')
+        return G, T, tor_ptr, (tr_pred, rot_pred, tor_pred, tr_score, rot_score, tor_score), scal
+
+    def score_matching_loss_batch(self, tr_pred, rot_pred, tor_pred, tr_score, rot_score, tor_score, tr_sigma, so3_score_norm, torus_score_norm2, tor_ptr, T):
+        """The six LOSS_COLUMNS per GRAPH of a ragged batch (ddk_score_matching_loss_batch): device tensor [G, 6].  Predictions and targets [G, 3], [G, 3]
+        and flat [T]; the three scalars and ``tor_ptr`` [G + 1] per graph (device tensors, or host arrays that are uploaded); ``T`` = tor_ptr[G] as a host
+        integer.  ``tor_pred`` None or T = 0: the torsion terms are 0."""
+        G, T, tor_ptr, ops, scal = self._loss_batch_args(tr_pred, rot_pred, tor_pred, tr_score, rot_score, tor_score, tr_sigma, so3_score_norm, torus_score_norm2,
+                                                         tor_ptr, T)
+        out = torch.empty((G, 6), dtype=torch.float32, device=ops[3].device)
+        self._check(self.L.ddk_score_matching_loss_batch(self.h, G, _ptr(tor_ptr), T, *[_ptr(t) for t in ops], *[_ptr(t) for t in scal], _ptr(out), _stream()),
+                    'ddk_score_matching_loss_batch')
+        return out
+
+    def score_matching_loss_batch_backward(self, grad, tr_pred, rot_pred, tor_pred, tr_score, rot_score, tor_score, tr_sigma, so3_score_norm, torus_score_norm2,
+                                           tor_ptr, T, need=(True, True, True)):
+        """The gradients of (tr_pred, rot_pred, tor_pred) from ``grad`` [G, 3], the gradient of the three loss columns
+        (ddk_score_matching_loss_batch_backward): a tuple of fresh device tensors [G, 3], [G, 3], [T], None where ``need`` is false (or there are no
+        torsions)."""
+        G, T, tor_ptr, ops, scal = self._loss_batch_args(tr_pred, rot_pred, tor_pred, tr_score, rot_score, tor_score, tr_sigma, so3_score_norm, torus_score_norm2,
+                                                         tor_ptr, T)
+        grad = _need_cuda(grad).contiguous().float()
+        if grad.numel() != 3 * G:
+            raise ValueError(f'ddk: grad must be [{G}, 3], got {tuple(grad.shape)} (the library reads it through a raw pointer)')
+        dev = grad.device
+        g_tr = torch.empty((G, 3), dtype=torch.float32, device=dev) if need[0] else None
+        g_rot = torch.empty((G, 3), dtype=torch.float32, device=dev) if need[1] else None
+        g_tor = torch.empty(T, dtype=torch.float32, device=dev) if need[2] and ops[2] is not None else None
+        self._check(self.L.ddk_score_matching_loss_batch_backward(self.h, G, _ptr(tor_ptr), T, _ptr(grad), *[_ptr(t) for t in ops], *[_ptr(t) for t in scal],
+                                                                  _ptr(g_tr), _ptr(g_rot), _ptr(g_tor), _stream()),
+                    'ddk_score_matching_loss_batch_backward')
+        return g_tr, g_rot, g_tor
 
     # ---- coordinates + bonds -> the static graph tables of a complex (csrc/k_build.hip) -------------
     def _count(self, count, what):

@@ -1,7 +1,8 @@
-"""The forward half of the diffusion and the score-matching validation loss: the reference's validation pass (test_epoch, utils/training.py) for a
-loaded checkpoint, without training.  ``noise_complex`` is NoiseTransform.apply_noise (datasets_utils/pdbbind.py:40-57) for B copies of a complex at a
-common t, ``loss_function`` is utils/training.py:14-61, ``validation_loss`` runs noise -> score model -> loss over complexes and noise levels.  Every draw
-comes from the counter-based generator (ddk_rng_perturbation), so a validation number is a pure function of (checkpoint, complexes, seed).
+"""The forward half of the diffusion, the score-matching loss and the training loop: the reference's validation pass (test_epoch, utils/training.py) for a
+loaded checkpoint, and its training pass (train_epoch) for a ``train_model.TrainableScoreModel``: ``noise_batch`` is NoiseTransform.apply_noise per complex
+at its own time followed by collation, ``draw_times`` the times, ``train_epoch`` utils/training.py:96-135, ``ExponentialMovingAverage`` utils/utils.py:117-.
+``noise_complex`` is NoiseTransform.apply_noise (datasets_utils/pdbbind.py:40-57) for B copies of a complex at a common t, ``loss_function`` is
+utils/training.py:14-61, ``validation_loss`` runs noise -> score model -> loss over complexes and noise levels.  Every draw comes from the counter-based generator (ddk_rng_perturbation), so a validation number is a pure function of (checkpoint, complexes, seed).
 All compute is in libddk.so (csrc/k_so3.hip, csrc/k_noising.hip and the score model); the host holds scalars."""
 import collections
 import os
@@ -10,7 +11,8 @@ import numpy as np
 import torch
 
 from .diffusion_utils import t_to_sigma
-from .runtime import _DATA, LOSS_COLUMNS, Complex, stream_id
+from . import data as _data
+from .runtime import _DATA, LOSS_COLUMNS, NOISE_BATCH_MAX_LIG, NOISE_BATCH_MAX_ROT, Complex, Context, h2d_async, stream_id
 
 # utils/so3.py and utils/torus.py: the grids of the two noise-level tables
 SO3_MIN_EPS, SO3_MAX_EPS, SO3_N_EPS = 0.01, 2, 1000
@@ -20,6 +22,12 @@ TORUS_SIGMA_MIN, TORUS_SIGMA_MAX, TORUS_SIGMA_N = 3e-3, 2, 5000
 # three sigmas and t (host floats), and the updates that made the poses
 Targets = collections.namedtuple('Targets', ('tr_score', 'rot_score', 'tor_score', 'tr_sigma', 'rot_sigma', 'tor_sigma', 't',
                                              'tr_update', 'rot_update', 'tor_update'))
+
+# what ``noise_batch`` hands to ``loss_function``: G graphs, each at its own time.  tr_score / rot_score / tr_update / rot_update [G, 3]; tor_score / tor_update
+# flat [T] with the prefix tor_ptr [G + 1] (int32) of the rotor counts (tor_score None on a no_torsion model); the three sigmas, t, so3_score_norm =
+# so3.score_norm(rot_sigma) and torus_score_norm2 = torus.score_norm(tor_sigma) float32 [G]: all device tensors.  rotors: the R_g as a HOST tuple (shapes).
+BatchTargets = collections.namedtuple('BatchTargets', ('tr_score', 'rot_score', 'tor_score', 'tr_sigma', 'rot_sigma', 'tor_sigma', 't', 'tor_ptr',
+                                                       'tr_update', 'rot_update', 'tor_update', 'so3_score_norm', 'torus_score_norm2', 'rotors'))
 
 
 def so3_eps_index(eps):
@@ -78,6 +86,186 @@ def noise_complex(model, c, t, B, seed, draw=0, sample_offset=0, cx=None, so3_ro
     return pos, Targets(p.tr_score, p.rot_score, tor_score, tr_sigma, rot_sigma, tor_sigma, float(t), p.tr_update, p.rot_update, p.tor_update)
 
 
+_host_context = None
+
+
+def _host_ctx():
+    """a host-only context for the calls that launch nothing (ddk_rng_forward_times)"""
+    global _host_context
+    if _host_context is None:
+        _host_context = Context(device=-1)
+    return _host_context
+
+
+def draw_times(names, seed, draw, alpha=1, beta=1):
+    """The diffusion time t in [0, 1) of each complex of ``names`` for noising ``draw`` under ``seed``: a float32 host array, a pure function of (name, seed,
+    draw) (generator purpose 11, ddk_rng_forward_times; computed on the host).  NoiseTransform draws t ~ Beta(alpha, beta); only the reference's default
+    alpha = beta = 1, the uniform, is covered."""
+    for option, v in (('alpha', alpha), ('beta', beta)):
+        if float(v) != 1.0:
+            raise NotImplementedError(f'ddk: draw_times covers sampling_{option} = 1 only (t uniform on [0, 1)), got {option} = {v}')
+    return _host_ctx().forward_times(seed, [stream_id(n) for n in names], draw=draw)
+
+
+def _splitmix64(x):
+    x = (x + 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+    z = x
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
+    return x, z ^ (z >> 31)
+
+
+def epoch_permutation(n, seed, epoch):
+    """The order in which ``train_epoch`` visits n complexes: a permutation of range(n) that is a pure function of (n, seed, epoch), in integer arithmetic
+    only (a Fisher-Yates shuffle fed by splitmix64 from the state seed ^ splitmix64(epoch); the modulo bias of 64-bit words is below 2^-40 for any list
+    that fits in memory), so it is the same on every host and library version."""
+    state = (int(seed) ^ _splitmix64(int(epoch) & 0xFFFFFFFFFFFFFFFF)[1]) & 0xFFFFFFFFFFFFFFFF
+    order = list(range(int(n)))
+    for i in range(len(order) - 1, 0, -1):
+        state, word = _splitmix64(state)
+        j = word % (i + 1)
+        order[i], order[j] = order[j], order[i]
+    return order
+
+
+def _pack(arrays):
+    """host arrays -> one uint8 buffer with every array at a multiple of 16 bytes, and their (offset, dtype, shape)"""
+    at, parts, where = 0, [], []
+    for a in arrays:
+        a = np.ascontiguousarray(a)
+        where.append((at, a.dtype, a.shape, a.nbytes))
+        pad = (-a.nbytes) % 16
+        parts.append(a.reshape(-1).view(np.uint8))
+        if pad:
+            parts.append(np.zeros(pad, np.uint8))
+        at += a.nbytes + pad
+    return (np.concatenate(parts) if parts else np.zeros(0, np.uint8)), where
+
+
+_TORCH_OF = {np.dtype(np.float32): torch.float32, np.dtype(np.int32): torch.int32, np.dtype(np.int64): torch.int64, np.dtype(np.uint8): torch.uint8}
+
+
+def noise_batch(model, complexes, t, seed, draw=0, samples=None):
+    """NoiseTransform.apply_noise (datasets_utils/pdbbind.py:35-57) for G DIFFERENT complexes, complex g at its own time ``t[g]``, and their collation:
+    returns (data, :data:`BatchTargets`).  ``complexes``: the dicts ``runtime.Complex`` takes, with 'name', 'lig_pos', 'edge_mask', 'mask_rotate'; ``t``:
+    G host floats in [0, 1]; ``samples``: G global sample indices (default 0).  Graph g is sample ``samples[g]`` of stream ``stream_id(name_g)`` under
+    ``seed`` and ``draw``, so its pose and targets do not depend on the rest of the batch, and a complex may appear twice with different samples.
+    ``data`` is a ``data.collate`` batch on the model's device in the layout ``TrainableScoreModel.forward`` documents, with the noised ``data['ligand'].pos``
+    and ``data.complex_t`` (set_time's graph-level part).  Every per-graph table goes up in ONE copy; then ddk_rng_perturbation_batch and
+    ddk_modify_conformer_batch, one launch each (the IGSO(3) table is computed once per context).  Nothing is read back: what the device would report as a
+    status (a bond outside its ligand, a coordinate that is not finite, a ligand over a limit) is checked here on the host first and raises."""
+    ctx = _ctx_of(model)
+    G = len(complexes)
+    if G < 1:
+        raise ValueError('ddk: noise_batch needs at least one complex')
+    t = np.asarray(t, dtype=np.float64).reshape(-1)
+    if t.size != G:
+        raise ValueError(f'ddk: noise_batch: t must hold one time per complex ({G}), got {t.size}')
+    if not (np.isfinite(t).all() and (t >= 0).all() and (t <= 1).all()):
+        raise ValueError(f'ddk: noise_batch: every t must be in [0, 1], got {t.tolist()}')
+    samples = np.zeros(G, np.int64) if samples is None else np.asarray(samples, dtype=np.int64).reshape(-1)
+    if samples.size != G or (samples < 0).any() or (samples >= (1 << 31) - 1).any():
+        raise ValueError(f'ddk: noise_batch: samples must hold one index in [0, 2^31 - 1) per complex ({G}), got {samples.tolist()}')
+    no_torsion = bool(getattr(model, 'no_torsion', ctx.cfg.no_torsion))      # (a TrainableScoreModel says so itself; its context is shared)
+    so3_tab, torus_tab = _score_norm_tables(ctx)
+    streams, pos, bonds, masks, rotors, atoms, sig, idx, norms = [], [], [], [], [], [], [], [], []
+    for g, c in enumerate(complexes):
+        name = c.get('name') if hasattr(c, 'get') else None
+        if name is None:
+            raise ValueError(f'ddk: noise_batch needs complexes with a name (complex {g} has none; its stream id is runtime.stream_id(name))')
+        p = np.asarray(c['lig_pos'], dtype=np.float32).reshape(-1, 3)
+        n = p.shape[0]
+        if not 1 <= n <= NOISE_BATCH_MAX_LIG:
+            raise ValueError(f'ddk: noise_batch: n_lig of complex {g} ({name!r}) must be in [1, {NOISE_BATCH_MAX_LIG}], got {n}')
+        if not np.isfinite(p).all():
+            raise ValueError(f'ddk: noise_batch: lig_pos of complex {g} ({name!r}) has a coordinate that is not finite')
+        em = np.asarray(c['edge_mask']).astype(bool).reshape(-1)
+        mr = np.asarray(c['mask_rotate']).astype(np.uint8).reshape(-1, n) if np.size(c['mask_rotate']) else np.zeros((0, n), np.uint8)
+        uv = np.asarray(c['bond_index'], dtype=np.int64)[:, em].T.reshape(-1, 2)
+        if mr.shape[0] != uv.shape[0]:
+            raise ValueError(f'ddk: noise_batch: complex {g} ({name!r}) has {uv.shape[0]} rotatable bonds in edge_mask and {mr.shape[0]} rows in mask_rotate')
+        if no_torsion:
+            mr, uv = mr[:0], uv[:0]
+        R = uv.shape[0]
+        if R > NOISE_BATCH_MAX_ROT:
+            raise ValueError(f'ddk: noise_batch: R_g of complex {g} ({name!r}) must be in [0, {NOISE_BATCH_MAX_ROT}], got {R}')
+        if R and ((uv < 0).any() or (uv >= n).any() or (uv[:, 0] == uv[:, 1]).any()):
+            raise ValueError(f'ddk: noise_batch: a rotatable bond of complex {g} ({name!r}) has an atom index outside [0, {n}) or joins an atom to itself')
+        s3 = _sigmas(ctx, float(t[g]))
+        e_idx, t_idx = int(so3_eps_index(s3[1])), int(torus_sigma_index(s3[2]))
+        streams.append(stream_id(name)); pos.append(p); bonds.append(uv.astype(np.int32)); masks.append(mr.reshape(-1)); rotors.append(R); atoms.append(n)
+        sig.append(s3); idx.append((e_idx, t_idx)); norms.append((so3_tab[e_idx], torus_tab[t_idx]))
+    prefix = lambda counts: np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    node_ptr, tor_ptr, mask_ptr = prefix(atoms), prefix(rotors), prefix([r * n for r, n in zip(rotors, atoms)])
+    T = int(tor_ptr[-1])
+    sig, idx, norms = np.asarray(sig, np.float32), np.asarray(idx, np.int32), np.asarray(norms, np.float32)
+    host = [np.asarray(streams, np.uint64).view(np.int64), np.concatenate(pos), node_ptr, tor_ptr, mask_ptr, samples.astype(np.int32), idx[:, 0].copy(),
+            idx[:, 1].copy(), sig[:, 0].copy(), sig[:, 1].copy(), sig[:, 2].copy(), t.astype(np.float32), norms[:, 0].copy(), norms[:, 1].copy(),
+            np.concatenate(bonds).reshape(-1, 2), np.concatenate(masks)]
+    buf, where = _pack(host)
+    dev = torch.device('cuda', ctx.device)
+    dbuf = h2d_async(torch.from_numpy(buf), dev)      # the one copy
+    (d_streams, d_pos, d_node, d_tor, d_mask_ptr, d_samples, d_eps, d_tidx, d_tr_sigma, d_rot_sigma, d_tor_sigma, d_t, d_so3_norm, d_torus_norm2, d_bonds,
+     d_masks) = (dbuf[at:at + nbytes].view(_TORCH_OF[dt]).reshape(shape) for at, dt, shape, nbytes in where)
+    cdf, score = ctx.so3_table()
+    p = ctx.rng_perturbation_batch(seed, d_streams, d_samples, d_tor, d_tr_sigma, d_tor_sigma, d_tidx, d_eps, cdf, score, draw=draw, T=T)
+    noised = ctx.modify_conformer_batch(d_pos, d_node, d_bonds, d_masks, d_mask_ptr, d_tor, p.tr_update, p.rot_update, p.tor_update if T else None, T=T)
+    batch = _data.collate([_data.from_arrays(c) for c in complexes]).to(dev)
+    batch['ligand'].pos = noised
+    batch.complex_t = {k: d_t for k in ('tr', 'rot', 'tor')}
+    targets = BatchTargets(p.tr_score, p.rot_score, None if no_torsion else p.tor_score, d_tr_sigma, d_rot_sigma, d_tor_sigma, d_t, d_tor, p.tr_update,
+                           p.rot_update, p.tor_update, d_so3_norm, d_torus_norm2, tuple(rotors))
+    return batch, targets
+
+
+class _ScoreMatchingLossBatch(torch.autograd.Function):
+    """ddk_score_matching_loss_batch for predictions that ask for a gradient; the backward is ddk_score_matching_loss_batch_backward, element-wise (the
+    base columns do not depend on the predictions)."""
+
+    @staticmethod
+    def forward(fctx, ctx, tg, tr_pred, rot_pred, tor_pred):
+        fctx.save_for_backward(tr_pred, rot_pred, tor_pred)
+        fctx.ddk = (ctx, tg)
+        return ctx.score_matching_loss_batch(tr_pred, rot_pred, tor_pred, tg.tr_score, tg.rot_score, tg.tor_score, tg.tr_sigma, tg.so3_score_norm,
+                                             tg.torus_score_norm2, tg.tor_ptr, sum(tg.rotors))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, g):
+        tr_pred, rot_pred, tor_pred = fctx.saved_tensors
+        ctx, tg = fctx.ddk
+        need = (fctx.needs_input_grad[2], fctx.needs_input_grad[3], tor_pred is not None and fctx.needs_input_grad[4])
+        grads = ctx.score_matching_loss_batch_backward(g[:, :3], tr_pred, rot_pred, tor_pred, tg.tr_score, tg.rot_score, tg.tor_score, tg.tr_sigma,
+                                                       tg.so3_score_norm, tg.torus_score_norm2, tg.tor_ptr, sum(tg.rotors), need=need)
+        like = lambda d, p: None if d is None else d.reshape(p.shape).to(p.dtype)
+        return (None, None) + tuple(like(d, p) for d, p in zip(grads, (tr_pred, rot_pred, tor_pred)))
+
+
+def _loss_function_batch(tr_pred, rot_pred, tor_pred, tg, ctx, apply_mean, tr_weight, rot_weight, tor_weight):
+    """loss_function for a :data:`BatchTargets`: per graph, the torsion term divided by R_g + 1e-4 (the reference's index_add of the per-edge terms and of
+    the counts); with ``apply_mean`` the tr / rot means over (G, 3) and the torsion mean over ALL T torsions of the batch, [1], 0 when T = 0"""
+    T = sum(tg.rotors)
+    no_tor = tg.tor_score is None or tor_pred is None or T == 0
+    args = (tr_pred, rot_pred, None if no_tor else tor_pred)
+    if torch.is_grad_enabled() and any(torch.is_tensor(p) and p.requires_grad for p in args):
+        per = _ScoreMatchingLossBatch.apply(ctx, tg, *args)
+    else:
+        per = ctx.score_matching_loss_batch(*args, tg.tr_score, tg.rot_score, None if no_tor else tg.tor_score, tg.tr_sigma, tg.so3_score_norm,
+                                            tg.torus_score_norm2, tg.tor_ptr, T)
+    cols = [per[:, k] for k in range(len(LOSS_COLUMNS))]
+    if apply_mean:
+        G = per.shape[0]
+        if no_tor:
+            tor = tor_base = torch.zeros(1, dtype=per.dtype, device=per.device)
+        else:      # the per-graph sums were divided by R_g + 1e-4: multiply back, add up over the graphs, divide by the count of all torsions
+            w = (tg.tor_ptr[1:] - tg.tor_ptr[:-1]).to(per.dtype) + 1e-4
+            tor, tor_base = ((cols[2] * w).sum() / T).reshape(1), ((cols[5] * w).sum() / T).reshape(1)
+        cols = [cols[0].sum() / G, cols[1].sum() / G, tor, cols[3].sum() / G, cols[4].sum() / G, tor_base]
+    tr_loss, rot_loss, tor_loss, tr_base, rot_base, tor_base = cols
+    loss = tr_loss * tr_weight + rot_loss * rot_weight + tor_loss * tor_weight
+    return loss, tr_loss, rot_loss, tor_loss, tr_base, rot_base, tor_base
+
+
 class _ScoreMatchingLoss(torch.autograd.Function):
     """ddk_score_matching_loss for predictions that ask for a gradient: the forward is the kernel, the backward the derivative of its three loss columns
     (the base columns do not depend on the predictions), written out element-wise: plain torch without reductions, so the same bits on every run.
@@ -113,8 +301,12 @@ def loss_function(tr_pred, rot_pred, tor_pred, targets, model, apply_mean=True, 
     """utils/training.py:14-61 for one batch of ``noise_complex``: the 7-tuple (loss, tr_loss, rot_loss, tor_loss, tr_base_loss, rot_base_loss,
     tor_base_loss) of device tensors, [B] each with ``apply_mean=False`` and [1] (the reference's shapes: 0-d for tr / rot) with it.  The score norms
     are looked up on the host in the context's tables at the targets' sigmas.  With ``apply_mean`` the torsion term is the mean over ALL torsions of the
-    batch, as in the reference (the per-sample values divide by n_rot + 1e-4; the batch mean divides by the count)."""
+    batch, as in the reference (the per-sample values divide by n_rot + 1e-4; the batch mean divides by the count).
+    With the :data:`BatchTargets` of ``noise_batch`` the batch is ragged: G graphs, each with its own sigmas and its own number of torsions; the tensors are
+    [G] each with ``apply_mean=False`` (ddk_score_matching_loss_batch, the score norms taken from the targets)."""
     ctx = _ctx_of(model)
+    if isinstance(targets, BatchTargets):
+        return _loss_function_batch(tr_pred, rot_pred, tor_pred, targets, ctx, apply_mean, tr_weight, rot_weight, tor_weight)
     so3_tab, torus_tab = _score_norm_tables(ctx)
     so3_norm = float(np.float32(so3_tab[int(so3_eps_index(targets.rot_sigma))]))
     torus_norm2 = float(np.float32(torus_tab[int(torus_sigma_index(targets.tor_sigma))]))
@@ -162,3 +354,86 @@ def validation_loss(model, complexes, t_values=None, samples_per_complex=8, seed
     out = dict(zip(keys, every.mean(axis=0).tolist())) if len(every) else {k: float('nan') for k in keys}
     out.update(per_t=per_t, n=int(len(every)))
     return out
+
+
+class ExponentialMovingAverage:
+    """The moving average of a model's trainable parameters that the reference trains with (utils/utils.py:117-, after score_sde_pytorch's ema.py), in plain
+    torch: shadow <- shadow - (1 - d) (shadow - p) after every optimizer step, with d = min(decay, (1 + k) / (10 + k)) at update k when
+    ``use_num_updates``.  ``store`` / ``copy_to`` / ``restore`` swap the average in for validation and back."""
+
+    def __init__(self, parameters, decay, use_num_updates=True):
+        if not 0.0 <= decay <= 1.0:
+            raise ValueError('Decay must be between 0 and 1')
+        self.decay = decay
+        self.num_updates = 0 if use_num_updates else None
+        self.shadow_params = [p.detach().clone() for p in parameters if p.requires_grad]
+        self.collected_params = []
+
+    def update(self, parameters):
+        d = self.decay
+        if self.num_updates is not None:
+            self.num_updates += 1
+            d = min(d, (1 + self.num_updates) / (10 + self.num_updates))
+        with torch.no_grad():
+            for shadow, p in zip(self.shadow_params, [p for p in parameters if p.requires_grad]):
+                shadow.sub_((1.0 - d) * (shadow - p))
+
+    def copy_to(self, parameters):
+        for shadow, p in zip(self.shadow_params, [p for p in parameters if p.requires_grad]):
+            p.data.copy_(shadow.data)
+
+    def store(self, parameters):
+        self.collected_params = [p.detach().clone() for p in parameters]
+
+    def restore(self, parameters):
+        for kept, p in zip(self.collected_params, parameters):
+            p.data.copy_(kept.data)
+
+    def state_dict(self):
+        return dict(decay=self.decay, num_updates=self.num_updates, shadow_params=self.shadow_params)
+
+    def load_state_dict(self, state_dict, device=None):
+        self.decay, self.num_updates = state_dict['decay'], state_dict['num_updates']
+        self.shadow_params = [v.detach().clone() if device is None else v.to(device) for v in state_dict['shadow_params']]
+
+
+TRAIN_METERS = ('loss',) + LOSS_COLUMNS
+
+
+def _step_seed(seed, epoch, step):
+    """the dropout seed of one training step: distinct 63-bit values for distinct (seed, epoch, step)"""
+    return _splitmix64((_splitmix64((int(seed) ^ _splitmix64(int(epoch) & 0xFFFFFFFFFFFFFFFF)[1]) & 0xFFFFFFFFFFFFFFFF)[1] + int(step)) & 0xFFFFFFFFFFFFFFFF)[1] >> 1
+
+
+def train_epoch(model, complexes, optimizer, batch_size, seed, epoch, ema=None, tr_weight=1, rot_weight=1, tor_weight=1):
+    """One training epoch of a ``TrainableScoreModel`` over ``complexes`` (dicts as ``noise_batch`` takes): utils/training.py:96-135.  The complexes are
+    visited in the order ``epoch_permutation(len(complexes), seed, epoch)`` in batches of ``batch_size``; complex i is noised at ``draw_times(names, seed,
+    draw=epoch)[i]`` with draw = epoch, so every epoch sees every complex at a new time and a new noise, and the whole epoch is a pure function of (the
+    model's state, complexes, seed, epoch).  Per batch: ``noise_batch`` -> ``model(data, seed=...)`` -> ``loss_function`` -> ``backward`` ->
+    ``optimizer.step()`` -> ``ema.update``.  A batch of one graph is skipped, as in the reference (BatchNorm needs two).  The seven meters are added up on
+    the device and read back ONCE at the end; returns the reference's summary, {'loss', 'tr_loss', ...: the mean over the batches run} (NaN if none ran).
+    The reference's out-of-memory loop, which retries a batch at 0.8 of its size, is not reproduced: an out-of-memory error is raised."""
+    ctx = _ctx_of(model)
+    model.train()
+    order = epoch_permutation(len(complexes), seed, epoch)
+    times = draw_times([c.get('name') if hasattr(c, 'get') else None for c in complexes], seed, epoch) if complexes else np.zeros(0, np.float32)
+    total, ran = torch.zeros(len(TRAIN_METERS), dtype=torch.float64, device=torch.device('cuda', ctx.device)), 0
+    for step, at in enumerate(range(0, len(order), int(batch_size))):
+        ids = order[at:at + int(batch_size)]
+        if len(ids) == 1:
+            continue
+        data, targets = noise_batch(model, [complexes[i] for i in ids], times[ids], seed, draw=epoch)
+        optimizer.zero_grad()
+        step_seed = _step_seed(seed, epoch, step)
+        with torch.random.fork_rng(devices=[ctx.device]):      # the heads' nn.Dropout layers draw from torch's generators: seeded per step, then put back
+            torch.manual_seed(step_seed)
+            tr_pred, rot_pred, tor_pred = model(data, seed=step_seed)
+        out = loss_function(tr_pred, rot_pred, tor_pred, targets, model, tr_weight=tr_weight, rot_weight=rot_weight, tor_weight=tor_weight)
+        out[0].sum().backward()
+        optimizer.step()
+        if ema is not None:
+            ema.update(model.parameters())
+        total += torch.stack([v.detach().double().reshape(()) for v in out])
+        ran += 1
+    values = (total / ran).tolist() if ran else [float('nan')] * len(TRAIN_METERS)      # the one read-back
+    return dict(zip(TRAIN_METERS, values))

@@ -576,6 +576,7 @@ int ddk_ligand_transformation_mask(ddk_ctx* ctx, int32_t n_lig, const int32_t* b
  *                10 conformer matching, generation g   sample = island * NP + member, step = g; block 0: word 0 -> r1, word 1 -> r2,
  *                                                      word 2 -> the forced crossover index, word 3 OF MEMBER 0 -> the island's mutation factor;
  *                                                      the crossover uniform of component d is word d % 4 of block 1 + d / 4
+ *                11 forward time (ddk_rng_forward_times below)   step = the draw index, block 0, word 0: t = the uniform u
  *      Words -> draws, in fp32, every operation as written:
  *        uniform      u = (x >> 8) * 2^-24: in [0, 1), exact
  *        torsion      (float)pi * (2u - 1): the inner term is exact, one rounding
@@ -671,6 +672,71 @@ int ddk_rng_perturbation(ddk_ctx* ctx, uint64_t seed, uint64_t stream_id, int32_
 int ddk_score_matching_loss(ddk_ctx* ctx, int32_t B, int32_t n_rot, const float* tr_pred, const float* rot_pred, const float* tor_pred,
                             const float* tr_score, const float* rot_score, const float* tor_score, float tr_sigma, float so3_score_norm,
                             float torus_score_norm2, float* out /* [B, 6] */, void* stream);
+
+/* ---- the same three steps for a RAGGED batch: G graphs that are different complexes, each at its own diffusion time, which is what the reference's
+ *      training loader delivers (NoiseTransform per complex, then collation; train_epoch, utils/training.py:96-135).  Like the calls above these take no
+ *      ddk_complex, allocate nothing, do not synchronise and enqueue on `stream`; a broken limit or a NULL required argument is DDK_ERR_INVALID with a
+ *      ddk_last_error text that names it, and nothing is enqueued.  The per-graph tables ([G] or [G + 1]) are DEVICE arrays the host side of the call never
+ *      reads; the caller (the Python shim checks them on the host before the one copy that uploads them) is responsible for them, and every entry is
+ *      checked on the device before it becomes an address or a table index.  No float atomics; a graph's results do not depend on the other graphs of the
+ *      batch, on its place in it or on G.
+ *      Ragged torsion arrays are flat [T] with the prefix tor_ptr [G + 1] of the rotor counts R_g (tor_ptr[0] = 0, tor_ptr[G] = T, R_g = 0 allowed).
+ *
+ *      ddk_rng_perturbation_batch: one noising (draw index `draw`) of G graphs: graph g is the global sample sample[g] of stream stream_id[g] under `seed`
+ *        at the noise level tr_sigma[g], tor_sigma[g], torus_sigma_idx[g] and row so3_row[g] of the caller's so3_cdf_rows / so3_score_rows [n_rows, 2000]
+ *        (rows of ddk_so3_rows in any order).  DDK_RNG_LAYOUT 1, purposes 6-8 exactly as for ddk_rng_perturbation.  out: tr_update, rot_update, tr_score,
+ *        rot_score [G, 3]; tor_update, tor_score [T]; the score members (and tor_update with T = 0) may be NULL.  The values of graph g are bit for bit
+ *        those of ddk_rng_perturbation(seed, stream_id[g], sample0 = sample[g], B = 1, draw, n_rot = R_g, ...) with g's scalars and rows.  The sigma of a
+ *        torus index is read from a 5001-entry table the FIRST batch call on a device computes on the host and uploads (40 kB, a blocking copy, once per
+ *        process and device), so that it is the host's number as in the single call.  A graph with a broken entry (tor_ptr not a range of [0, T], R_g >
+ *        1024, an index outside its table, a sample < 0, a sigma that is not positive and finite) gets NaN in its tr_update / rot_update rows and nothing
+ *        else.  Limits: 1 <= G <= 65536, 0 <= T <= 1024 G, 0 <= draw < 2^20, 1 <= n_rows <= 4096.  One launch, one workgroup per graph.
+ *
+ *      ddk_rng_forward_times: the diffusion time of each of n complexes for one noising, t_out[i] = the uniform of purpose 11 for (seed, stream_id[i],
+ *        sample, draw): in [0, 1), i.e. NoiseTransform's Beta(alpha, beta) draw for the reference's default alpha = beta = 1.  A HOST function (stream_id and
+ *        t_out are HOST arrays, no kernel, also on a host-only context): the noise levels of a batch are host scalars (the table indices are computed
+ *        from them), the generator is plain integer code and the word -> uniform conversion is exact, so the device has nothing to add.
+ *
+ *      ddk_modify_conformer_batch: modify_conformer (utils/diffusion_utils.py) per graph: the rigid move by (tr_update[g], rot_update[g]) about the
+ *        graph's centroid, the torsion rotations in bond order on the already-updated coordinates, the Kabsch re-alignment of the flexed conformer onto
+ *        the rigid one.  pos / pos_out [N, 3] with the atoms of graph g at node_ptr[g] .. node_ptr[g + 1]; rot_bonds [T, 2] graph-local (u, v) and
+ *        mask_rotate, the graphs' [R_g, n_g] byte blocks back to back with graph g's at mask_ptr[g] (mask_bytes in all), as ddk_conformer_rmsd takes them.
+ *        tor_update = NULL: rigid moves only (the rotor tables may then be NULL).  One workgroup per graph with the arithmetic of ddk_se3_update: centred
+ *        coordinates, fp64 centroid sums, Horn's closed form; pos_out of graph g is bit for bit ddk_se3_update's with B = 1 on a ddk_complex of that ligand
+ *        and the same updates; a graph with R_g = 0 gets the rigid move.  status_out [G]: 0 done; 2 a bond index outside [0, n_g) or u == v; 3 a
+ *        coordinate that is not finite; 4 a node_ptr / tor_ptr / mask_ptr entry that is no range of its array, n_g outside [1, 256], R_g outside [0, 1024]
+ *        or a mask block that is not R_g * n_g bytes: all found before an index is used as an address; with 2, 3 or 4 the graph's rows of pos_out are
+ *        not written.  Limits: 1 <= G <= 65536, G <= N <= 256 G, 0 <= T <= 1024 G, mask_bytes >= 0.  One launch.
+ *
+ *      ddk_score_matching_loss_batch: out [G, 6], row g = ddk_score_matching_loss(B = 1, n_rot = R_g, ...) bit for bit with the graph's own tr_sigma[g],
+ *        so3_score_norm[g], torus_score_norm2[g] (one torus norm per graph: every torsion edge of a graph carries the graph's tor_sigma).  tor_pred = NULL
+ *        or R_g = 0: the graph's torsion terms are 0.  A graph with a tor_ptr pair that is no range of [0, T], R_g > 1024 or a scalar that is not positive
+ *        gets a row of NaN.  One launch, one wave per graph.
+ *      ddk_score_matching_loss_batch_backward: from grad [G, 3], the gradient of the three loss columns, the gradients of the predictions, each written
+ *        only where its destination is not NULL: grad_tr_pred [G, 3] = 2 (pred - score) tr_sigma^2 / 3 * grad[g][0], grad_rot_pred [G, 3] = 2 (pred -
+ *        score) / so3_score_norm^2 / 3 * grad[g][1], grad_tor_pred [T] = 2 (pred - score) / torus_score_norm2 / (R_g + 1e-4) * grad[g][2]; element-wise,
+ *        fp64 inside, one rounding.  One launch (none if nothing is asked for).
+ *      Limits of both: 1 <= G <= 65536, 0 <= T <= 1024 G. */
+int ddk_rng_perturbation_batch(ddk_ctx* ctx, uint64_t seed, int32_t G, const uint64_t* stream_id /* DEVICE [G] */, const int32_t* sample /* DEVICE [G] */,
+                               const int32_t* tor_ptr /* DEVICE [G + 1] */, int32_t T, int32_t draw, const float* tr_sigma, const float* tor_sigma,
+                               const int32_t* torus_sigma_idx, const int32_t* so3_row /* DEVICE [G] each */, int32_t n_rows,
+                               const double* so3_cdf_rows, const double* so3_score_rows /* DEVICE [n_rows, 2000] each */, const ddk_perturbation* out,
+                               void* stream);
+int ddk_rng_forward_times(ddk_ctx* ctx, uint64_t seed, int32_t n, const uint64_t* stream_id /* HOST [n] */, int32_t sample, int32_t draw,
+                          float* t_out /* HOST [n] */);
+int ddk_modify_conformer_batch(ddk_ctx* ctx, int32_t G, int32_t N, const float* pos /* [N, 3] */, const int32_t* node_ptr /* [G + 1] */, int32_t T,
+                               const int32_t* rot_bonds /* [T, 2] */, const uint8_t* mask_rotate /* [mask_bytes] */, const int32_t* mask_ptr /* [G + 1] */,
+                               int32_t mask_bytes, const int32_t* tor_ptr /* [G + 1] */, const float* tr_update, const float* rot_update /* [G, 3] */,
+                               const float* tor_update /* [T] or NULL */, float* pos_out /* [N, 3] */, int32_t* status_out /* [G] */, void* stream);
+int ddk_score_matching_loss_batch(ddk_ctx* ctx, int32_t G, const int32_t* tor_ptr /* [G + 1] */, int32_t T, const float* tr_pred, const float* rot_pred,
+                                  const float* tor_pred, const float* tr_score, const float* rot_score, const float* tor_score,
+                                  const float* tr_sigma, const float* so3_score_norm, const float* torus_score_norm2 /* DEVICE [G] each */,
+                                  float* out /* [G, 6] */, void* stream);
+int ddk_score_matching_loss_batch_backward(ddk_ctx* ctx, int32_t G, const int32_t* tor_ptr, int32_t T, const float* grad /* [G, 3] */, const float* tr_pred,
+                                           const float* rot_pred, const float* tor_pred, const float* tr_score, const float* rot_score,
+                                           const float* tor_score, const float* tr_sigma, const float* so3_score_norm, const float* torus_score_norm2,
+                                           float* grad_tr_pred /* [G, 3] or NULL */, float* grad_rot_pred /* [G, 3] or NULL */,
+                                           float* grad_tor_pred /* [T] or NULL */, void* stream);
 
 /* ---- conformer matching: fit the torsion angles of a generated conformer so that, after the optimal rigid fit, it lies as close as possible to the true
  *      pose (datasets_utils/conformer_matching.py, called from get_lig_graph_with_matching, datasets_utils/process_mols.py:280-311; the reference trains and
