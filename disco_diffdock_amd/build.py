@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libddk.so')
-SOURCES = ['ddk_capi.hip', 'conv_pack.hip', 'conv_launch.hip', 'k_conv.hip', 'k_tp.hip', 'k_tp_bwd.hip', 'k_rtp.hip', 'k_rhid.hip', 'k_hconv.hip', 'k_eemb.hip', 'k_graph.hip', 'k_heads.hip', 'k_se3.hip', 'model.hip', 'conf.hip', 'k_conv_x.hip', 'k_conv_x2.hip', 'k_ar.hip', 'k_pairs.hip', 'k_autos.hip', 'k_build.hip', 'k_rng.hip', 'k_so3.hip', 'k_noising.hip', 'k_match.hip']
+SOURCES = ['ddk_capi.hip', 'conv_pack.hip', 'conv_launch.hip', 'k_conv.hip', 'k_tp.hip', 'k_tp_bwd.hip', 'k_rtp.hip', 'k_rhid.hip', 'k_hconv.hip', 'k_eemb.hip', 'k_reduce.hip', 'k_graph.hip', 'k_heads.hip', 'k_se3.hip', 'model.hip', 'conf.hip', 'k_conv_x.hip', 'k_conv_x2.hip', 'k_ar.hip', 'k_pairs.hip', 'k_autos.hip', 'k_build.hip', 'k_rng.hip', 'k_so3.hip', 'k_noising.hip', 'k_match.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics', '-mllvm', '-amdgpu-mfma-vgpr-form', '-Wall', '-Wno-unused-function', '-Wno-unused-value', '-Wno-unused-result']
 
 
@@ -20,10 +20,10 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-ato
 # kernel is written out, so that its instantiations (one per subset of outputs) give the same bits; k_rtp and k_rhid make the same promise.  k_rhid: its
 # fmaf chains take W1 from scalar registers, which a v_fmac_f32 reads directly and a packed FMA only after a v_mov per element; k_hconv: the same promise
 # and the same chains, with W2 in the scalar registers; k_eemb: the same promise, W1 and W2 in the scalar registers, and a backward that recomputes the
-# forward's hidden layer with the forward's expressions
+# forward's hidden layer with the forward's expressions; k_reduce: the slice reduction and the segmented sum that close these ops, separate adds in a fixed order
 FILE_FLAGS = {'k_conv_x.hip': ['-fno-slp-vectorize'], 'k_conv_x2.hip': ['-fno-slp-vectorize'], 'k_tp_bwd.hip': ['-ffp-contract=off'], 'k_rtp.hip': ['-ffp-contract=off'],
               'k_rhid.hip': ['-ffp-contract=off', '-fno-slp-vectorize'], 'k_hconv.hip': ['-ffp-contract=off', '-fno-slp-vectorize'],
-              'k_eemb.hip': ['-ffp-contract=off', '-fno-slp-vectorize']}
+              'k_eemb.hip': ['-ffp-contract=off', '-fno-slp-vectorize'], 'k_reduce.hip': ['-ffp-contract=off']}
 # sources that are #included by another source (besides the headers): part of that object's content stamp
 INCLUDED_SOURCES = {'k_conv_x2.hip': ['k_conv_x.hip']}
 

@@ -250,12 +250,9 @@ int ddk_tp_backward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float
   return DDK_OK;
 }
 
-// the checks the two radial-tensor-product entries share: layer, group table, edge count
-static int rtp_check(ddk_ctx* ctx, const char* who, int32_t layer, const int64_t* go, int32_t n_groups, int64_t E) {
-  int rc = check_tp_launchable(ctx, who, layer);
-  if (rc) return rc;
+// the group table of a training op and its edge count: 1..4 groups, E below 2^31, a monotone host prefix from 0 to E
+static int check_group_table(ddk_ctx* ctx, const char* who, const int64_t* go, int32_t n_groups, int64_t E) {
   const std::string w(who);
-  if (layer > 4) return fail(ctx, DDK_ERR_INVALID, w + ": layer out of range (0..4)");
   if (n_groups < 1 || n_groups > 4) return fail(ctx, DDK_ERR_INVALID, w + ": n_groups must be in 1..4");
   if (E < 0 || E >= (int64_t)1 << 31) return fail(ctx, DDK_ERR_INVALID, w + ": edge count out of range");
   if (!go) return fail(ctx, DDK_ERR_INVALID, w + ": null group_offsets");
@@ -264,6 +261,26 @@ static int rtp_check(ddk_ctx* ctx, const char* who, int32_t layer, const int64_t
     if (go[g + 1] < go[g]) return fail(ctx, DDK_ERR_INVALID, w + ": group_offsets are not monotone");
   if (go[n_groups] != E) return fail(ctx, DDK_ERR_INVALID, w + ": the last group offset is not E");
   return DDK_OK;
+}
+
+// the graph of a conv op (the radial conv, the head convs): node counts below 2^31, and with edges nodes on both sides and the tables the direction reads
+static int check_conv_graph(ddk_ctx* ctx, const char* who, const RconvGraph& gr, int64_t E, bool backward) {
+  const std::string w(who);
+  const int64_t lim = (int64_t)1 << 31;
+  if (gr.n_in < 0 || gr.n_in >= lim || gr.n_out < 0 || gr.n_out >= lim) return fail(ctx, DDK_ERR_INVALID, w + ": node count out of range");
+  if (E == 0) return DDK_OK;
+  if (gr.n_in == 0 || gr.n_out == 0) return fail(ctx, DDK_ERR_INVALID, w + ": edges without nodes");
+  if (!gr.src || !gr.dst || !gr.src_order || !gr.src_ptr || (backward && (!gr.dst_order || !gr.dst_ptr)))
+    return fail(ctx, DDK_ERR_INVALID, w + ": null graph table (edge_src, edge_dst, the orderings and their pointer tables)");
+  return DDK_OK;
+}
+
+// the checks the two radial-tensor-product entries share: layer, group table, edge count
+static int rtp_check(ddk_ctx* ctx, const char* who, int32_t layer, const int64_t* go, int32_t n_groups, int64_t E) {
+  int rc = check_tp_launchable(ctx, who, layer);
+  if (rc) return rc;
+  if (layer > 4) return fail(ctx, DDK_ERR_INVALID, std::string(who) + ": layer out of range (0..4)");
+  return check_group_table(ctx, who, go, n_groups, E);
 }
 
 int ddk_rtp_forward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float* sh, const float* h, const int64_t* group_offsets, int32_t n_groups,
@@ -304,14 +321,9 @@ int64_t ddk_rtp_backward_workspace(int32_t layer, int64_t E, int32_t n_groups) {
 static int rconv_check(ddk_ctx* ctx, const char* who, int32_t layer, const int64_t* go, int32_t n_groups, int64_t E, const RconvGraph& gr, bool backward,
                        const float* x_nodes, const float* sh, const float* h, const void* workspace) {
   int rc = rtp_check(ctx, who, layer, go, n_groups, E);
-  if (rc) return rc;
+  if (!rc) rc = check_conv_graph(ctx, who, gr, E, backward);
+  if (rc || E == 0) return rc;
   const std::string w(who);
-  const int64_t lim = (int64_t)1 << 31;
-  if (gr.n_in < 0 || gr.n_in >= lim || gr.n_out < 0 || gr.n_out >= lim) return fail(ctx, DDK_ERR_INVALID, w + ": node count out of range");
-  if (E == 0) return DDK_OK;
-  if (gr.n_in == 0 || gr.n_out == 0) return fail(ctx, DDK_ERR_INVALID, w + ": edges without nodes");
-  if (!gr.src || !gr.dst || !gr.src_order || !gr.src_ptr || (backward && (!gr.dst_order || !gr.dst_ptr)))
-    return fail(ctx, DDK_ERR_INVALID, w + ": null graph table (edge_src, edge_dst, the orderings and their pointer tables)");
   if (!x_nodes || !sh || !h) return fail(ctx, DDK_ERR_INVALID, w + ": null operand");
   if (!workspace) return fail(ctx, DDK_ERR_INVALID, w + ": null workspace (ddk_rconv_workspace bytes)");
   return DDK_OK;
@@ -361,14 +373,10 @@ static int rhid_check(ddk_ctx* ctx, const char* who, const int64_t* go, int32_t 
   int rc = check_launchable(ctx, 0);
   if (rc) return rc;
   const std::string w(who);
-  if (n_groups < 1 || n_groups > 4) return fail(ctx, DDK_ERR_INVALID, w + ": n_groups must be in 1..4");
-  if (E < 0 || E >= (int64_t)1 << 31) return fail(ctx, DDK_ERR_INVALID, w + ": edge count out of range");
-  if (n_nodes < 0 || n_nodes >= (int64_t)1 << 31) return fail(ctx, DDK_ERR_INVALID, w + ": node count out of range");
-  if (!go) return fail(ctx, DDK_ERR_INVALID, w + ": null group_offsets");
-  if (go[0] != 0) return fail(ctx, DDK_ERR_INVALID, w + ": group_offsets must start at 0");
-  for (int g = 0; g < n_groups; ++g)
-    if (go[g + 1] < go[g]) return fail(ctx, DDK_ERR_INVALID, w + ": group_offsets are not monotone");
-  if (go[n_groups] != E) return fail(ctx, DDK_ERR_INVALID, w + ": the last group offset is not E");
+  const int64_t lim = (int64_t)1 << 31;
+  // (the node count is refused after n_groups and E and before the offsets, as it always was: the refusal tests hold the order)
+  if (n_groups >= 1 && n_groups <= 4 && E >= 0 && E < lim && (n_nodes < 0 || n_nodes >= lim)) return fail(ctx, DDK_ERR_INVALID, w + ": node count out of range");
+  if ((rc = check_group_table(ctx, who, go, n_groups, E))) return rc;
   if (!(p >= 0.f && p < 1.f)) return fail(ctx, DDK_ERR_INVALID, w + ": the dropout rate p must be in [0, 1)");
   if (E == 0) return DDK_OK;
   if (n_nodes == 0) return fail(ctx, DDK_ERR_INVALID, w + ": edges without nodes");
@@ -422,14 +430,10 @@ static int hconv_check(ddk_ctx* ctx, const char* who, int32_t head, int64_t E, c
   int rc = check_launchable(ctx, 0);
   if (rc) return rc;
   const std::string w(who);
-  const int64_t lim = (int64_t)1 << 31;
   if (head != DDK_HEAD_CENTER && head != DDK_HEAD_TORSION) return fail(ctx, DDK_ERR_INVALID, w + ": head must be DDK_HEAD_CENTER or DDK_HEAD_TORSION");
-  if (E < 0 || E >= lim) return fail(ctx, DDK_ERR_INVALID, w + ": edge count out of range");
-  if (gr.n_in < 0 || gr.n_in >= lim || gr.n_out < 0 || gr.n_out >= lim) return fail(ctx, DDK_ERR_INVALID, w + ": node count out of range");
-  if (E == 0) return DDK_OK;
-  if (gr.n_in == 0 || gr.n_out == 0) return fail(ctx, DDK_ERR_INVALID, w + ": edges without nodes");
-  if (!gr.src || !gr.dst || !gr.src_order || !gr.src_ptr || (backward && (!gr.dst_order || !gr.dst_ptr)))
-    return fail(ctx, DDK_ERR_INVALID, w + ": null graph table (edge_src, edge_dst, the orderings and their pointer tables)");
+  if (E < 0 || E >= (int64_t)1 << 31) return fail(ctx, DDK_ERR_INVALID, w + ": edge count out of range");
+  rc = check_conv_graph(ctx, who, gr, E, backward);
+  if (rc || E == 0) return rc;
   if (!x_nodes || !sh || !h) return fail(ctx, DDK_ERR_INVALID, w + ": null operand");
   if (!workspace) return fail(ctx, DDK_ERR_INVALID, w + ": null workspace (ddk_hconv_workspace bytes)");
   if (((uintptr_t)sh | (uintptr_t)h | (uintptr_t)workspace) & 15) return fail(ctx, DDK_ERR_INVALID, w + ": sh, h and the workspace must be 16-byte aligned");
@@ -536,7 +540,7 @@ int ddk_seg_sum(ddk_ctx* ctx, const float* rows, const int32_t* order, const int
   if (D < 1 || D > 128) return fail(ctx, DDK_ERR_INVALID, "ddk_seg_sum: D must be in 1..128");
   if (n_nodes == 0) return DDK_OK;
   if (!rows || !order || !ptr || !nodes) return fail(ctx, DDK_ERR_INVALID, "ddk_seg_sum: null operand");
-  hipError_t e = launch_rtp_seg_sum(rows, order, ptr, nodes, n_nodes, D, (hipStream_t)stream);
+  hipError_t e = launch_seg_sum(rows, order, ptr, nodes, n_nodes, D, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(ctx, e, "seg_sum launch");
   return DDK_OK;
 }

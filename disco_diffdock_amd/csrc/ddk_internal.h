@@ -342,6 +342,60 @@ __host__ __device__ inline int64_t rtp_slice_len(int64_t E) {
   const int64_t l = ((E + 239) / 240 + 63) / 64 * 64;
   return l > 512 ? l : 512;
 }
+// What the training ops share (k_rtp.hip, k_rhid.hip, k_hconv.hip, k_eemb.hip, k_reduce.hip).  THE GROUP TABLE of a call: edge e belongs to group g iff
+// off[g] <= e < off[g + 1], at most four groups.  A kernel cuts the edges into UNITS of `per` edges (a workgroup's edges, or a slice of the parameter
+// pass): groups in order, ceil(n / per) units each, so that a unit never spans two groups
+struct EdgeGroupTable { int64_t off[5]; int n_groups; };
+struct GroupUnit { int grp; int64_t begin, end; };      // a unit's group and edges; grp < 0: past the last unit
+
+inline EdgeGroupTable group_table(const int64_t* group_offsets, int n_groups) {
+  EdgeGroupTable t{};
+  for (int q = 0; q <= n_groups; ++q) t.off[q] = group_offsets[q];
+  t.n_groups = n_groups;
+  return t;
+}
+inline EdgeGroupTable group_table(int64_t E) { return EdgeGroupTable{{0, E, 0, 0, 0}, 1}; }      // the ops of one group
+
+__host__ __device__ __forceinline__ GroupUnit group_unit(const EdgeGroupTable& t, int64_t b, int64_t per) {      // unit b
+  GroupUnit u{-1, 0, 0};
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    if (q < t.n_groups && u.grp < 0) {
+      const int64_t nb = (t.off[q + 1] - t.off[q] + per - 1) / per;
+      if (b < nb) { u.grp = q; u.begin = t.off[q] + b * per; u.end = u.begin + per < t.off[q + 1] ? u.begin + per : t.off[q + 1]; } else b -= nb;
+    }
+  }
+  return u;
+}
+inline void group_units(const EdgeGroupTable& t, int grp, int64_t per, int64_t& first, int64_t& count) {      // a group's first unit, its unit count
+  first = 0; count = 0;
+  for (int q = 0; q < 4; ++q) {
+    if (q < t.n_groups) {
+      const int64_t n = (t.off[q + 1] - t.off[q] + per - 1) / per;
+      if (q < grp) first += n;
+      if (q == grp) count = n;
+    }
+  }
+}
+inline int64_t group_unit_total(const EdgeGroupTable& t, int64_t per) {
+  int64_t n = 0;
+  for (int q = 0; q < t.n_groups; ++q) n += (t.off[q + 1] - t.off[q] + per - 1) / per;
+  return n;
+}
+// workspace parts: floats rounded up so that the next part starts on 16 bytes; a memset that skips a null or empty output; the slices of a parameter pass
+// over E edges in G groups, sum_g ceil(n_g / L) <= floor(E / L) + G
+inline int64_t ws_pad(int64_t n) { return (n + 3) / 4 * 4; }
+inline hipError_t zero_async(float* p, int64_t n, hipStream_t s) { return (p && n > 0) ? hipMemsetAsync(p, 0, (size_t)n * sizeof(float), s) : hipSuccess; }
+inline int64_t slice_bound(int64_t E, int n_groups) { return E / rtp_slice_len(E) + n_groups; }
+// k_reduce.hip: THE SLICE REDUCTION of every parameter pass, the one place that fixes the bits of a parameter gradient.  A slice image is one or two parts
+// [rows][cols + 1] (rows = 0: no second part); per group the images of its slices (units of L edges) are added in slice order, `float sum = 0; sum += img[s]`
+// with separate adds, and column `cols` of a part goes to b [G][rows], the rest to w [G][rows][cols].  A null output is skipped; a group without edges gets zeros
+struct ReducePart { float* w; float* b; int rows, cols; };
+hipError_t launch_slice_reduce(const float* images, const EdgeGroupTable& t, int64_t L, const ReducePart& p0, const ReducePart& p1, hipStream_t s);
+// k_reduce.hip: the fixed-order segmented sum and mean: nodes[n, :] = the rows order[ptr[n] .. ptr[n + 1]) of rows [*, D] added in that order (the first
+// row starts the sum: a -0 stays what it is), the mean divided by max(ptr[n + 1] - ptr[n], 1); a node without rows: exact zeros.  D <= 128
+hipError_t launch_seg_sum(const float* rows, const int32_t* order, const int64_t* ptr, float* nodes, int64_t N, int D, hipStream_t s);
+hipError_t launch_seg_mean(const float* rows, const int32_t* order, const int64_t* ptr, float* nodes, int64_t N, int D, hipStream_t s);
 // k_rtp.hip: the radial conv, node rows to aggregated node rows (include/ddk.h: ddk_rconv_forward / ddk_rconv_backward).  The graph of a call: trusted device
 // tables, dst_order / dst_ptr read by the backward alone
 struct RconvGraph {
@@ -354,9 +408,6 @@ hipError_t launch_rconv_backward(const ConvLayerDev& L, const RconvGraph& gr, co
                                  int n_groups, const float* w2, const float* b2, const float* grad_out_nodes, float* grad_x_nodes, float* grad_sh, float* grad_h,
                                  float* grad_w2, float* grad_b2, float* workspace, hipStream_t s);
 int64_t rconv_workspace(int32_t layer, int64_t E, int32_t n_groups, int64_t n_in, int64_t n_out, int32_t backward);
-// k_rtp.hip: the radial conv's fixed-order segmented sum without the mean (rtp_seg_kernel<false>): nodes[n, :] = the rows order[ptr[n] .. ptr[n + 1]) of
-// rows [*, D] added in that order; a node without rows: exact zeros
-hipError_t launch_rtp_seg_sum(const float* rows, const int32_t* order, const int64_t* ptr, float* nodes, int64_t N, int D, hipStream_t s);
 // k_rhid.hip: the radial MLP's hidden layer from the edge embedding and the node table, h = dropout(relu(W1[g] [emb | xs[src] | xs[dst]] + b1[g])), and its
 // vector-Jacobian product (include/ddk.h: ddk_rhid_forward / ddk_rhid_backward).  gr: n_in == n_out nodes; a null output is not computed
 hipError_t launch_rhid_forward(const float* xs, const int32_t* src, const int32_t* dst, const float* emb, const int64_t* group_offsets, int n_groups,

@@ -19,7 +19,7 @@
 // THE MASK (include/ddk.h, DDK_EEMB_MASK_LAYOUT): keep(e, c) = rng_uniform(word c % 4 of Philox4x32-10(key = seed, counter = (e_lo, e_hi, c / 4,
 // DDK_EEMB_MASK_TAG))) >= p, e the edge's position within the call: a pure function of (seed, edge id, column).
 //
-// BACKWARD.  eemb_param_kernel + eemb_reduce_kernel, as rhid_param_kernel / rhid_reduce_kernel: a workgroup of four waves owns a slice of rtp_slice_len(E)
+// BACKWARD.  eemb_param_kernel + the slice reduction of k_reduce.hip, as rhid_param_kernel: a workgroup of four waves owns a slice of rtp_slice_len(E)
 // edges and walks it 64 edges at a time.  Per step the four waves share the 64 edges (lane = edge): wave w makes eight columns of sig and of the smearing
 // and six of grad_emb into LDS; then six columns of pre / hid (the forward's chain over the whole row, read back from LDS); then six of
 // gpre = ghid * (hid != 0 ? s : 0).  Then every thread adds the step's 64 edges, in ascending edge order, to its elements of the slice's image, which
@@ -46,7 +46,7 @@ struct EembArgs {
   const float* feat; const float* sig; const int32_t* sig_index;
   const float* w1; const float* b1; const float* w2; const float* b2;
   const float* gemb;
-  float* emb; float* sh; float* img; float* gw1; float* gb1; float* gw2; float* gb2;
+  float* emb; float* sh; float* img;
   int64_t E, L;      // edges of the call; edges per slice (parameter pass)
   int F, K;          // bond-feature columns (0 or 4); K = F + 64
   float coeff, p, s;
@@ -74,6 +74,7 @@ __device__ __forceinline__ float eemb_smear(const EembArgs& a, float d, int j) {
 }
 
 // hid[c] of the dropout layout from the ReLU of pre[c]: columns c0 .. c0 + n - 1 (c0 a multiple of 2, n <= 8) of edge e
+// (mask_keep4 / mask_relu of k_philox.h written out: through the helper eemb_param_kernel measured 1 % slower, with the text below it is the code it was)
 template <int N>
 __device__ __forceinline__ void eemb_hidden(const EembArgs& a, int64_t e, int c0, float* v) {
   if (a.p > 0.f) {
@@ -285,35 +286,10 @@ __global__ __launch_bounds__(EE_PT) void eemb_param_kernel(EembArgs a) {
   }
 }
 
-// the four gradients = the slice images added in slice order
-__global__ __launch_bounds__(256) void eemb_reduce_kernel(EembArgs a, int64_t n_slices) {
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  const int K = a.K, PER = eemb_img(K), n1 = EE_H * (K + 1);
-  if (idx >= PER) return;
-  float sum = 0.f;
-  for (int64_t s = 0; s < n_slices; ++s) sum += a.img[s * PER + idx];
-  if (idx < n1) {
-    const int c = idx / (K + 1), k = idx - c * (K + 1);
-    if (k < K) {
-      if (a.gw1) a.gw1[c * K + k] = sum;
-    } else if (a.gb1) {
-      a.gb1[c] = sum;
-    }
-  } else {
-    const int r = idx - n1, c = r / (EE_H + 1), k = r - c * (EE_H + 1);
-    if (k < EE_H) {
-      if (a.gw2) a.gw2[c * EE_H + k] = sum;
-    } else if (a.gb2) {
-      a.gb2[c] = sum;
-    }
-  }
-}
-
 // ---- host ----------------------------------------------------------------------------------------------------------------------------------------------------
 int64_t eemb_workspace(int64_t E, int32_t K) {
   if (E < 0 || E >= (int64_t)1 << 31 || (K != EE_S + EE_D && K != EE_KMAX)) return -1;
-  const int64_t slices = E / rtp_slice_len(E) + 1;      // ceil(E / L) <= floor(E / L) + 1
-  return slices * eemb_img(K) * (int64_t)sizeof(float);
+  return slice_bound(E, 1) * eemb_img(K) * (int64_t)sizeof(float);
 }
 
 // offset as torch.linspace(start, stop, 32) makes it in fp32 (one fused multiply-add per centre, the upper half counted down from stop), coeff as GaussianSmearing: -0.5 / (offset[1] - offset[0])^2
@@ -345,22 +321,19 @@ hipError_t launch_eemb_backward(const EembOperands& o, const float* grad_emb, in
                                 float* workspace, hipStream_t s) {
   const int K = o.F + EE_S + EE_D;
   if (E == 0) {
-    const struct { float* p; int64_t n; } z[4] = {{grad_w1, (int64_t)EE_H * K}, {grad_b1, EE_H}, {grad_w2, EE_H * EE_H}, {grad_b2, EE_H}};
-    for (const auto& t : z) {
-      if (!t.p) continue;
-      hipError_t e = hipMemsetAsync(t.p, 0, (size_t)t.n * sizeof(float), s);
-      if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    hipError_t e = zero_async(grad_w1, EE_H * K, s);
+    if (e == hipSuccess) e = zero_async(grad_b1, EE_H, s);
+    if (e == hipSuccess) e = zero_async(grad_w2, EE_H * EE_H, s);
+    if (e == hipSuccess) e = zero_async(grad_b2, EE_H, s);
+    return e;
   }
   EembArgs a = eemb_args(o, E);
-  a.gemb = grad_emb; a.img = workspace; a.gw1 = grad_w1; a.gb1 = grad_b1; a.gw2 = grad_w2; a.gb2 = grad_b2;
+  a.gemb = grad_emb; a.img = workspace;
   const int64_t n_slices = (E + a.L - 1) / a.L;      // at most 241
   hipLaunchKernelGGL(eemb_param_kernel, dim3((unsigned)n_slices), dim3(EE_PT), 0, s, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(eemb_reduce_kernel, dim3((unsigned)((eemb_img(K) + 255) / 256)), dim3(256), 0, s, a, n_slices);
-  return hipGetLastError();
+  return launch_slice_reduce(workspace, group_table(E), a.L, ReducePart{grad_w1, grad_b1, EE_H, K}, ReducePart{grad_w2, grad_b2, EE_H, EE_H}, s);
 }
 
 }  // namespace ddk

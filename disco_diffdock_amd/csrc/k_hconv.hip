@@ -21,15 +21,15 @@
 // threads for the centre head, 512 for the torsion head); they share the 64 gathered node rows through LDS (stride 85: no bank conflicts).  The grid is
 // ceil(E / 64) workgroups: a 1 200-edge centre launch is 76 waves on 19 CUs, a torsion launch of 320 bonds about 800 waves.
 //
-// LAUNCHES.  Forward: 2 (hc_edge_kernel writes the per-edge rows [E, Dout], hc_seg_mean_kernel adds a receiver's rows in ascending edge id and divides).
+// LAUNCHES.  Forward: 2 (hc_edge_kernel writes the per-edge rows [E, Dout], seg_kernel<mean> of k_reduce.hip adds a receiver's rows in ascending edge id and divides).
 // Backward: at most 4.  hc_edge_kernel<bwd> (grad_x rows and grad_h; the receiver's gradient row is gathered and divided by its count in the kernel),
-// rtp_seg_kernel of k_rtp.hip (grad_x: a node's rows in ascending edge id), hc_param_kernel + hc_reduce_kernel (grad_w2, grad_b2).  Each is skipped when no
+// seg_kernel of k_reduce.hip (grad_x: a node's rows in ascending edge id), hc_param_kernel + the slice reduction of k_reduce.hip (grad_w2, grad_b2).  Each is skipped when no
 // output needs it.
 //   backward edge kernel: every wave keeps its tile's part of grad_h (K registers) and of the edge's grad_x row (60 / 18 registers), and the waves add them
 //   into one LDS image in tile order, one wave per barrier interval: a fixed order, and the image leaves as coalesced rows.
 //   parameter kernel: a workgroup owns (slice of rtp_slice_len(E) edges, tile).  Per 64 staged edges the 36 x 64 values gw = dL/dw_e[p] go to LDS, then every
 //   thread adds its (p, k) entries of gw^T [h | 1] over the 64 edges in ascending order.  Partial images [W][K + 1] per slice, added in slice order by
-//   hc_reduce_kernel.  The slice length depends on E alone, so the bits do not depend on the device.
+//   slice_reduce_kernel.  The slice length depends on E alone, so the bits do not depend on the device.
 // The indices, orderings and pointer tables are trusted: Context.conv_graph (Python) builds and range-checks them.
 #include "ddk_internal.h"
 
@@ -343,53 +343,13 @@ __global__ __launch_bounds__(256) void hc_param_kernel(HcArgs a) {
   }
 }
 
-// grad_w2 / grad_b2 = the slice images added in slice order
-template <int HEAD>
-__global__ __launch_bounds__(256) void hc_reduce_kernel(HcArgs a, int64_t n_slices) {
-  using S = HcShape<HEAD>;
-  constexpr int K = S::K, K1 = K + 1, PER = S::W * K1;
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= PER) return;
-  const int p = idx / K1, col = idx - p * K1;
-  float sum = 0.f;
-  for (int64_t s = 0; s < n_slices; ++s) sum += a.ws[s * PER + idx];
-  if (col < K) {
-    if (a.gw2) a.gw2[p * K + col] = sum;
-  } else if (a.gb2) {
-    a.gb2[p] = sum;
-  }
-}
-
-// out[r, :] = (rows[order[ptr[r]], :] + rows[order[ptr[r] + 1], :] + ...) / max(ptr[r + 1] - ptr[r], 1): the rows of a receiver added in ascending edge id,
-// one thread per (receiver, column); a receiver without edges: exact zeros.  Plain stores, no atomics
-__global__ __launch_bounds__(256) void hc_seg_mean_kernel(const float* __restrict__ rows, const int32_t* __restrict__ order, const int64_t* __restrict__ ptr,
-                                                          float* __restrict__ out, int64_t N, int D) {
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= N * D) return;
-  const int64_t r = idx / D;
-  const int c = (int)(idx - r * D);
-  const int64_t k0 = ptr[r], k1 = ptr[r + 1];
-  float sum = 0.f;
-  int64_t k = k0;
-  if (k < k1) sum = rows[(int64_t)order[k++] * D + c];
-  for (; k < k1; ++k) sum += rows[(int64_t)order[k] * D + c];
-  out[idx] = sum / (float)(k1 - k0 > 1 ? k1 - k0 : 1);
-}
-
 // ---- host ------------------------------------------------------------------------------------------------------------------------------------------------------
-static int64_t hc_pad(int64_t n) { return (n + 3) / 4 * 4; }      // floats of a workspace part: the next part starts on 16 bytes
-
 int64_t hconv_workspace(int32_t head, int64_t E, int64_t n_in, int64_t n_out, int32_t backward) {
   const int64_t lim = (int64_t)1 << 31;
   if (head < 0 || head > 1 || E < 0 || E >= lim || n_in < 0 || n_in >= lim || n_out < 0 || n_out >= lim) return -1;
   const int64_t W = head ? HcShape<1>::W : HcShape<0>::W, K1 = (head ? HcShape<1>::K : HcShape<0>::K) + 1, dout = head ? HcShape<1>::DOUT : HcShape<0>::DOUT;
-  if (!backward) return hc_pad(E * dout) * (int64_t)sizeof(float);      // the tensor product's rows
-  const int64_t slices = E / rtp_slice_len(E) + 1;      // ceil(E / L) <= floor(E / L) + 1
-  return (hc_pad(E * HC_DIN) + slices * W * K1) * (int64_t)sizeof(float);      // the per-edge rows of grad_x, the parameter images
-}
-
-static hipError_t hc_zero(float* p, int64_t n, hipStream_t s) {
-  return (p && n > 0) ? hipMemsetAsync(p, 0, (size_t)n * sizeof(float), s) : hipSuccess;
+  if (!backward) return ws_pad(E * dout) * (int64_t)sizeof(float);      // the tensor product's rows
+  return (ws_pad(E * HC_DIN) + slice_bound(E, 1) * W * K1) * (int64_t)sizeof(float);      // the per-edge rows of grad_x, the parameter images
 }
 
 static HcArgs hc_args(const RconvGraph& gr, const float* x, const float* sh, const float* h, const float* w2, const float* b2, int64_t E) {
@@ -403,29 +363,27 @@ static HcArgs hc_args(const RconvGraph& gr, const float* x, const float* sh, con
 template <int HEAD>
 static hipError_t hc_forward(const RconvGraph& gr, HcArgs a, float* out_nodes, float* workspace, hipStream_t s) {
   using S = HcShape<HEAD>;
-  if (a.E == 0) return hc_zero(out_nodes, gr.n_out * S::DOUT, s);
+  if (a.E == 0) return zero_async(out_nodes, gr.n_out * S::DOUT, s);
   a.rows = workspace;
   const int64_t nwg = (a.E + 63) / 64;      // E < 2^31
   hipLaunchKernelGGL((hc_edge_kernel<HEAD, true, false, false>), dim3((unsigned)nwg), dim3(64 * S::NT), 0, s, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  const int64_t nb = (gr.n_out * S::DOUT + 255) / 256;      // n_out < 2^31 and Dout <= 48: fewer than 2^31 workgroups
-  if (nb > 0) hipLaunchKernelGGL(hc_seg_mean_kernel, dim3((unsigned)nb), dim3(256), 0, s, workspace, gr.src_order, gr.src_ptr, out_nodes, gr.n_out, (int)S::DOUT);
-  return hipGetLastError();
+  return launch_seg_mean(workspace, gr.src_order, gr.src_ptr, out_nodes, gr.n_out, S::DOUT, s);
 }
 
 template <int HEAD>
 static hipError_t hc_backward(const RconvGraph& gr, HcArgs a, float* grad_x_nodes, float* workspace, hipStream_t s) {
   using S = HcShape<HEAD>;
   if (a.E == 0) {
-    hipError_t e = hc_zero(grad_x_nodes, gr.n_in * HC_DIN, s);
-    if (e == hipSuccess) e = hc_zero(a.gw2, (int64_t)S::W * S::K, s);
-    if (e == hipSuccess) e = hc_zero(a.gb2, S::W, s);
+    hipError_t e = zero_async(grad_x_nodes, gr.n_in * HC_DIN, s);
+    if (e == hipSuccess) e = zero_async(a.gw2, (int64_t)S::W * S::K, s);
+    if (e == hipSuccess) e = zero_async(a.gb2, S::W, s);
     return e;
   }
   float* gx_rows = workspace;
   a.gxr = grad_x_nodes ? gx_rows : nullptr;
-  a.ws = gx_rows + hc_pad(a.E * HC_DIN);
+  a.ws = gx_rows + ws_pad(a.E * HC_DIN);
   const int64_t nwg = (a.E + 63) / 64;
   const dim3 b(64 * S::NT);
   const bool nx = a.gxr != nullptr, nh = a.gh != nullptr;
@@ -436,7 +394,7 @@ static hipError_t hc_backward(const RconvGraph& gr, HcArgs a, float* grad_x_node
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (nx) {
-      e = launch_rtp_seg_sum(gx_rows, gr.dst_order, gr.dst_ptr, grad_x_nodes, gr.n_in, HC_DIN, s);
+      e = launch_seg_sum(gx_rows, gr.dst_order, gr.dst_ptr, grad_x_nodes, gr.n_in, HC_DIN, s);
       if (e != hipSuccess) return e;
     }
   }
@@ -445,7 +403,7 @@ static hipError_t hc_backward(const RconvGraph& gr, HcArgs a, float* grad_x_node
     hipLaunchKernelGGL((hc_param_kernel<HEAD>), dim3((unsigned)nsl, S::NT), dim3(256), 0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((hc_reduce_kernel<HEAD>), dim3((S::W * (S::K + 1) + 255) / 256), dim3(256), 0, s, a, nsl);
+    return launch_slice_reduce(a.ws, group_table(a.E), a.L, ReducePart{a.gw2, a.gb2, S::W, S::K}, ReducePart{}, s);
   }
   return hipGetLastError();
 }

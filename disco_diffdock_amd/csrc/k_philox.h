@@ -57,6 +57,24 @@ DDK_HD inline void rng_block(const RngStream& S, uint32_t sample, uint32_t purpo
 
 DDK_HD inline float rng_uniform(uint32_t x) { return (float)(x >> 8) * 0x1p-24f; }
 
+// The dropout masks of the training ops (include/ddk.h: DDK_RHID_MASK_LAYOUT, DDK_EEMB_MASK_LAYOUT): the keep flags of columns 4 q .. 4 q + 3 of edge e are
+// rng_uniform(word) >= p of the four words of Philox(key = seed, counter = (e_lo, e_hi, q, tag)), and a kept element is relu(v) / (1 - p) = relu(v) * s
+struct MaskKeep4 {      // (keep[i] compares where it is used: flags made ahead of their use cost a kernel vector registers)
+  float u[4], p;
+  DDK_HD bool operator[](int i) const { return u[i] >= p; }
+};
+DDK_HD inline MaskKeep4 mask_keep4(uint32_t seed_lo, uint32_t seed_hi, int64_t e, uint32_t q, uint32_t tag, float p) {
+  const uint32_t ctr[4] = {(uint32_t)e, (uint32_t)((uint64_t)e >> 32), q, tag};
+  const uint32_t key[2] = {seed_lo, seed_hi};
+  uint32_t w[4];
+  philox4x32_10(ctr, key, w);
+  return MaskKeep4{{rng_uniform(w[0]), rng_uniform(w[1]), rng_uniform(w[2]), rng_uniform(w[3])}, p};
+}
+DDK_HD inline float mask_relu(bool keep, float v, float s) {
+  const float r = v < 0.f ? 0.f : v;      // (a NaN stays one, as torch's relu leaves it)
+  return keep ? r * s : 0.f;
+}
+
 DDK_HD inline float rng_torsion(uint32_t x) {
   const float s = 2.0f * rng_uniform(x) - 1.0f;      // exact, contracted or not
   return 3.14159265358979323846f * s;

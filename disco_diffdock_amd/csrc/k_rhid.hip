@@ -1,7 +1,7 @@
 // The first half of a conv layer's radial MLP at the op boundary, and its vector-Jacobian product, WITHOUT the concatenated row [E, 72]:
 //   pre_e = W1[g(e)] [ emb_e | xs[src_e] | xs[dst_e] ] + b1[g(e)]      h_e = dropout(relu(pre_e))      (models/score_model.py:227-230 and fc[g][0..3] of
 // models/tensor_layers.py:154).  The row is gathered inside the kernels; the backward adds the two gathers' gradients per node in ascending edge id (the
-// fixed-order segmented sum of the radial conv, k_rtp.hip), so nothing here uses an atomic and the bits do not depend on the run, the device or the
+// fixed-order segmented sum of k_reduce.hip), so nothing here uses an atomic and the bits do not depend on the run, the device or the
 // subset of gradients asked for.  Exact fp32: every dot product is ONE fmaf chain in a written-out order (compiled with -ffp-contract=off, so that the
 // only fused operations are the ones spelled fmaf):
 //   pre[e, c]   = fmaf(W1[c, 71], in[71], ... fmaf(W1[c, 0], in[0], b1[c]))                     k ascending, the bias first
@@ -21,7 +21,7 @@
 // DDK_RHID_MASK_TAG))) >= p: a pure function of (seed, edge id, column).  One block per four columns of h; drawn after the GEMM, into the lane's row of
 // the tile, whose inputs are used up.  The backward reads the pattern from h itself (h != 0), so it needs neither the seed nor a mask tensor.
 //
-// rhid_param_kernel + rhid_reduce_kernel, as rtp_param_kernel / rtp_reduce_kernel: a workgroup of twelve waves owns an edge slice of a group and keeps the
+// rhid_param_kernel + the slice reduction of k_reduce.hip, as rtp_param_kernel: a workgroup of twelve waves owns an edge slice of a group and keeps the
 // slice's image [72][73] in registers (a half-wave owns three columns, its lane three rows: 3 x 3 accumulators; column 72, the sum of gpre itself, is
 // grad_b1) while 32 edges at a time are staged in LDS, gpre [32][72] and the gathered rows [32][72]: grad_h and h are read once, and a thread loads
 // its elements of the next step into registers before it makes this step's products.  Plain stores; the
@@ -42,28 +42,12 @@ static_assert(RH_W == NE && RH_P == NS, "the radial MLP of ns = 24");
 struct RhidArgs {
   const float* xs; const float* emb; const float* h; const float* gh;
   const int32_t* src; const int32_t* dst;
-  float* out_h; float* gemb; float* rows_src; float* rows_dst; float* img; float* gw1; float* gb1;
-  int64_t off[5];
-  int n_groups;
+  float* out_h; float* gemb; float* rows_src; float* rows_dst; float* img;
+  EdgeGroupTable t;
   int64_t L;      // edges per slice (parameter pass)
   float p, s;
   uint32_t seed_lo, seed_hi;
 };
-
-struct RhidWhere { int grp; int64_t begin, end; };      // a unit's group and edges
-
-// unit b of the units of `per` edges: groups in order, ceil(n / per) units each
-__device__ __forceinline__ RhidWhere rhid_where(const RhidArgs& a, int64_t b, int64_t per) {
-  RhidWhere w{-1, 0, 0};
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    if (q < a.n_groups && w.grp < 0) {
-      const int64_t nb = (a.off[q + 1] - a.off[q] + per - 1) / per;
-      if (b < nb) { w.grp = q; w.begin = a.off[q] + b * per; w.end = w.begin + per < a.off[q + 1] ? w.begin + per : a.off[q + 1]; } else b -= nb;
-    }
-  }
-  return w;
-}
 
 __device__ __forceinline__ void rhid_load24(const float* row, bool on, float* v) {
 #pragma unroll
@@ -81,7 +65,7 @@ __device__ __forceinline__ float rhid_gpre(float gh, float h, float s) { return 
 __global__ __launch_bounds__(RH_EPB) void rhid_fwd_kernel(RhidArgs a, const float* __restrict__ w1, const float* __restrict__ b1) {
   __shared__ float tile[RH_EPB / 64][64 * RH_LD];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const RhidWhere u = rhid_where(a, blockIdx.x, RH_EPB);
+  const GroupUnit u = group_unit(a.t, blockIdx.x, RH_EPB);
   if (u.grp < 0) return;      // (the whole workgroup)
   const int64_t e0 = u.begin + 64 * wave, e = e0 + lane;
   const bool ev = e < u.end;
@@ -112,20 +96,14 @@ __global__ __launch_bounds__(RH_EPB) void rhid_fwd_kernel(RhidArgs a, const floa
     }
   }
   if (a.p > 0.f) {
-    const uint32_t key[2] = {a.seed_lo, a.seed_hi};
 #pragma unroll 1
     for (int q = 0; q < RH_W / 4; ++q) {      // the mask goes to the tile as 1 / 0 (the row's inputs are used up)
-      const uint32_t ctr[4] = {(uint32_t)e, (uint32_t)((uint64_t)e >> 32), (uint32_t)q, DDK_RHID_MASK_TAG};
-      uint32_t w[4];
-      philox4x32_10(ctr, key, w);
+      const MaskKeep4 keep = mask_keep4(a.seed_lo, a.seed_hi, e, q, DDK_RHID_MASK_TAG, a.p);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) t[4 * q + i] = rng_uniform(w[i]) >= a.p ? 1.f : 0.f;
+      for (int i = 0; i < 4; ++i) t[4 * q + i] = keep[i] ? 1.f : 0.f;
     }
 #pragma unroll
-    for (int c = 0; c < RH_W; ++c) {
-      const float r = acc[c] < 0.f ? 0.f : acc[c];      // (a NaN stays one, as torch's relu leaves it)
-      t[c] = t[c] != 0.f ? r * a.s : 0.f;
-    }
+    for (int c = 0; c < RH_W; ++c) t[c] = mask_relu(t[c] != 0.f, acc[c], a.s);
   } else {
 #pragma unroll
     for (int c = 0; c < RH_W; ++c) t[c] = acc[c] < 0.f ? 0.f : acc[c];
@@ -144,7 +122,7 @@ __global__ __launch_bounds__(RH_EPB) void rhid_fwd_kernel(RhidArgs a, const floa
 __global__ __launch_bounds__(RH_EPB) void rhid_bwd_edge_kernel(RhidArgs a, const float* __restrict__ w1) {
   __shared__ float tile[RH_EPB / 64][64 * RH_LD];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const RhidWhere u = rhid_where(a, blockIdx.x, RH_EPB);
+  const GroupUnit u = group_unit(a.t, blockIdx.x, RH_EPB);
   if (u.grp < 0) return;
   const int64_t e0 = u.begin + 64 * wave, e = e0 + lane;
   const bool ev = e < u.end;
@@ -196,7 +174,7 @@ __global__ __launch_bounds__(RH_PT) void rhid_param_kernel(RhidArgs a) {
   __shared__ float ins[32 * RH_W];
   const int tid = threadIdx.x, tc = tid & 31, tk = tid >> 5;      // rows 3 tc .. 3 tc + 2 (tc < 24) x columns 3 tk .. 3 tk + 2
   const int64_t slice = blockIdx.x;
-  const RhidWhere u = rhid_where(a, slice, a.L);
+  const GroupUnit u = group_unit(a.t, slice, a.L);
   if (u.grp < 0) return;
   const bool active = tc < RH_P;
   float acc[3][3], accb[3];
@@ -257,32 +235,6 @@ __global__ __launch_bounds__(RH_PT) void rhid_param_kernel(RhidArgs a) {
   }
 }
 
-// grad_w1[g] / grad_b1[g] = the group's slice images added in slice order (a group without edges: zeros)
-__global__ __launch_bounds__(256) void rhid_reduce_kernel(RhidArgs a) {
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  constexpr int64_t PER = (int64_t)RH_W * RH_IMG;
-  if (idx >= PER * a.n_groups) return;
-  const int grp = (int)(idx / PER);
-  const int rem = (int)(idx - grp * PER);
-  const int c = rem / RH_IMG, col = rem - c * RH_IMG;
-  int64_t first = 0, ns = 0;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    if (q < a.n_groups) {
-      const int64_t n = (a.off[q + 1] - a.off[q] + a.L - 1) / a.L;
-      if (q < grp) first += n;
-      if (q == grp) ns = n;
-    }
-  }
-  float sum = 0.f;
-  for (int64_t s = 0; s < ns; ++s) sum += a.img[(first + s) * PER + rem];
-  if (col < RH_W) {
-    if (a.gw1) a.gw1[((int64_t)grp * RH_W + c) * RH_W + col] = sum;
-  } else if (a.gb1) {
-    a.gb1[(int64_t)grp * RH_W + c] = sum;
-  }
-}
-
 // grad_xs = (the sum over the node's edges as src) + (the sum over its edges as dst), in that order
 __global__ __launch_bounds__(256) void rhid_add_kernel(float* __restrict__ to, const float* __restrict__ add, int64_t n) {
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -290,34 +242,20 @@ __global__ __launch_bounds__(256) void rhid_add_kernel(float* __restrict__ to, c
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------------------------------------
-static int64_t rhid_pad(int64_t n) { return (n + 3) / 4 * 4; }      // floats of a workspace part: the next part starts on 16 bytes
-
-static int64_t rhid_units(const RhidArgs& a, int64_t per) {
-  int64_t n = 0;
-  for (int q = 0; q < a.n_groups; ++q) n += (a.off[q + 1] - a.off[q] + per - 1) / per;
-  return n;
-}
-
 int64_t rhid_workspace(int64_t E, int32_t n_groups, int64_t n_nodes) {
   const int64_t lim = (int64_t)1 << 31;
   if (E < 0 || E >= lim || n_groups < 1 || n_groups > 4 || n_nodes < 0 || n_nodes >= lim) return -1;
-  const int64_t slices = E / rtp_slice_len(E) + n_groups;      // sum_g ceil(n_g / L) <= floor(E / L) + G
-  return (2 * rhid_pad(E * RH_P) + rhid_pad(n_nodes * RH_P) + slices * RH_W * RH_IMG) * (int64_t)sizeof(float);
+  return (2 * ws_pad(E * RH_P) + ws_pad(n_nodes * RH_P) + slice_bound(E, n_groups) * RH_W * RH_IMG) * (int64_t)sizeof(float);
 }
 
 static RhidArgs rhid_args(const float* xs, const int32_t* src, const int32_t* dst, const float* emb, const int64_t* group_offsets, int n_groups, float p) {
   RhidArgs a{};
   a.xs = xs; a.src = src; a.dst = dst; a.emb = emb;
-  for (int q = 0; q <= n_groups; ++q) a.off[q] = group_offsets[q];
-  a.n_groups = n_groups;
+  a.t = group_table(group_offsets, n_groups);
   a.L = rtp_slice_len(group_offsets[n_groups]);
   a.p = p;
   a.s = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
   return a;
-}
-
-static hipError_t rhid_zero(float* p, int64_t n, hipStream_t s) {
-  return (p && n > 0) ? hipMemsetAsync(p, 0, (size_t)n * sizeof(float), s) : hipSuccess;
 }
 
 hipError_t launch_rhid_forward(const float* xs, const int32_t* src, const int32_t* dst, const float* emb, const int64_t* group_offsets, int n_groups,
@@ -326,7 +264,7 @@ hipError_t launch_rhid_forward(const float* xs, const int32_t* src, const int32_
   RhidArgs a = rhid_args(xs, src, dst, emb, group_offsets, n_groups, p);
   a.out_h = h;
   a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
-  const int64_t nwg = rhid_units(a, RH_EPB);      // E < 2^31: fewer than 2^31 workgroups
+  const int64_t nwg = group_unit_total(a.t, RH_EPB);      // E < 2^31: fewer than 2^31 workgroups
   hipLaunchKernelGGL(rhid_fwd_kernel, dim3((unsigned)nwg), dim3(RH_EPB), 0, s, a, w1, b1);
   return hipGetLastError();
 }
@@ -336,36 +274,34 @@ hipError_t launch_rhid_backward(const RconvGraph& gr, const float* xs, const flo
                                 float* workspace, hipStream_t s) {
   const int64_t E = group_offsets[n_groups], N = gr.n_in;
   if (E == 0) {
-    hipError_t e = rhid_zero(grad_xs, N * RH_P, s);
-    if (e == hipSuccess) e = rhid_zero(grad_w1, (int64_t)n_groups * RH_W * RH_W, s);
-    if (e == hipSuccess) e = rhid_zero(grad_b1, (int64_t)n_groups * RH_W, s);
+    hipError_t e = zero_async(grad_xs, N * RH_P, s);
+    if (e == hipSuccess) e = zero_async(grad_w1, (int64_t)n_groups * RH_W * RH_W, s);
+    if (e == hipSuccess) e = zero_async(grad_b1, (int64_t)n_groups * RH_W, s);
     return e;
   }
   float* rows_src = workspace;
-  float* rows_dst = rows_src + rhid_pad(E * RH_P);
-  float* node_dst = rows_dst + rhid_pad(E * RH_P);
+  float* rows_dst = rows_src + ws_pad(E * RH_P);
+  float* node_dst = rows_dst + ws_pad(E * RH_P);
   RhidArgs a = rhid_args(xs, gr.src, gr.dst, emb, group_offsets, n_groups, p);
   a.h = h; a.gh = grad_h;
   a.gemb = grad_emb; a.rows_src = grad_xs ? rows_src : nullptr; a.rows_dst = grad_xs ? rows_dst : nullptr;
-  a.img = node_dst + rhid_pad(N * RH_P); a.gw1 = grad_w1; a.gb1 = grad_b1;
+  a.img = node_dst + ws_pad(N * RH_P);
   hipError_t e = hipSuccess;
   if (grad_emb || grad_xs) {
-    hipLaunchKernelGGL(rhid_bwd_edge_kernel, dim3((unsigned)rhid_units(a, RH_EPB)), dim3(RH_EPB), 0, s, a, w1);
+    hipLaunchKernelGGL(rhid_bwd_edge_kernel, dim3((unsigned)group_unit_total(a.t, RH_EPB)), dim3(RH_EPB), 0, s, a, w1);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   if (grad_xs) {
-    if ((e = launch_rtp_seg_sum(rows_src, gr.src_order, gr.src_ptr, grad_xs, N, RH_P, s)) != hipSuccess) return e;
-    if ((e = launch_rtp_seg_sum(rows_dst, gr.dst_order, gr.dst_ptr, node_dst, N, RH_P, s)) != hipSuccess) return e;
+    if ((e = launch_seg_sum(rows_src, gr.src_order, gr.src_ptr, grad_xs, N, RH_P, s)) != hipSuccess) return e;
+    if ((e = launch_seg_sum(rows_dst, gr.dst_order, gr.dst_ptr, node_dst, N, RH_P, s)) != hipSuccess) return e;
     const int64_t n = N * RH_P;      // N < 2^31: fewer than 2^31 workgroups
     hipLaunchKernelGGL(rhid_add_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, grad_xs, node_dst, n);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   if (grad_w1 || grad_b1) {
-    hipLaunchKernelGGL(rhid_param_kernel, dim3((unsigned)rhid_units(a, a.L)), dim3(RH_PT), 0, s, a);
+    hipLaunchKernelGGL(rhid_param_kernel, dim3((unsigned)group_unit_total(a.t, a.L)), dim3(RH_PT), 0, s, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    const int64_t n = (int64_t)RH_W * RH_IMG * n_groups;
-    hipLaunchKernelGGL(rhid_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
-    e = hipGetLastError();
+    e = launch_slice_reduce(a.img, a.t, a.L, ReducePart{grad_w1, grad_b1, RH_W, RH_W}, ReducePart{}, s);
   }
   return e;
 }

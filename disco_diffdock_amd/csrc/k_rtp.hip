@@ -23,7 +23,7 @@
 // 4 apart are 288 floats = 32 banks apart, so the two half-waves do not meet).  gw_tile is made on the VALU, one element per lane and step.  G rows are
 // folded into grad_x (an LDS image [Din][32] per wave) and grad_sh (registers) as soon as their three column groups are done.
 //
-// rtp_param_kernel (backward pass 3) + rtp_reduce_kernel.  A workgroup owns (edge slice of a group, four tiles): wave w keeps the [32 slots x 96] accumulators
+// rtp_param_kernel (backward pass 3) + the slice reduction of k_reduce.hip.  A workgroup owns (edge slice of a group, four tiles): wave w keeps the [32 slots x 96] accumulators
 // of its tile over the whole slice, gw_tile^T . [h | 1] with K = edges (32 staged in LDS per step; lane = slot makes its gw from the staged x, sh, g rows);
 // column 72, against ones, is grad_b2.  Each workgroup stores its partial image [W][73] with plain stores; the second kernel adds the slices of a group in
 // slice order.  The slice length depends on E alone (rtp_slice_len: 512 edges, longer once E > 122 880 so that there are never more than 240 + G slices:
@@ -31,7 +31,7 @@
 //
 // THE RADIAL CONV (launch_rconv_forward / launch_rconv_backward: node rows to aggregated node rows, lines 153-159 of TensorProductConvLayer.forward).  The same
 // two kernels instantiated on RtpIdx<shape>: x and g are node tables, the lane (edge kernel) or the staging loop (parameter kernel) reads row xi[e] = edge_dst[e]
-// of x and row gi[e] = edge_src[e] of g; sh, h and all output rows stay per edge.  Around them rtp_seg_kernel adds a node's rows in ascending edge id from a
+// of x and row gi[e] = edge_src[e] of g; sh, h and all output rows stay per edge.  Around them seg_kernel of k_reduce.hip adds a node's rows in ascending edge id from a
 // node-sorted edge list, one thread per (node, column): the scatter-mean of the forward ([E, Dout] rows over src) and the backward of the gather ([E, Din]
 // rows of grad_x over dst); rtp_node_scale_kernel makes gn = grad_out / max(count, 1) once per node, so that the backward gathers plain rows.  No atomics
 // here either.  The indices, orderings and pointer tables are trusted: Context.conv_graph (Python) builds and range-checks them.
@@ -52,8 +52,7 @@ constexpr int RTP_IMG = RTP_H + 1;   // columns of a partial image: grad_w2's 72
 struct RtpArgs {
   const float* x; const float* sh; const float* h; const float* w2; const float* b2; const float* g;
   float* out; float* gx; float* gsh; float* gh; float* ws; float* gw2; float* gb2;
-  int64_t off[5];
-  int n_groups;
+  EdgeGroupTable t;
   int64_t L;      // edges per slice (pass 3)
   const int32_t* xi; const int32_t* gi;      // the indexed kernels (the radial conv): edge e reads row xi[e] of x and row gi[e] of g
 };
@@ -157,8 +156,6 @@ __device__ __forceinline__ void rtp_fold(const RtpRow& rk, const float* i, const
 template <class S> struct RtpIdx : S {};
 template <class S> struct RtpIsIdx { static constexpr bool value = false; };
 template <class S> struct RtpIsIdx<RtpIdx<S>> { static constexpr bool value = true; };
-template <class S> struct RtpPlain { using type = S; };      // the shape itself (rtp_reduce_kernel reads no x or g: one instantiation per shape)
-template <class S> struct RtpPlain<RtpIdx<S>> { using type = S; };
 
 template <class S, bool FWD, bool NX, bool NH>
 struct RtpEdge {
@@ -320,14 +317,15 @@ struct RtpEdge {
     Afrag = Afrag_; Wrm = Wrm_; Bt = Bt_;
     tid = threadIdx.x; lane = tid & 63; j = lane & 31; hh = lane >> 5;
     const int wave = tid >> 6;
-    // the workgroup's group and its first edge: groups in order, ceil(n / 128) workgroups each
+    // the workgroup's group and its first edge: groups in order, ceil(n / 128) workgroups each.  (group_unit written out with the GROUP's end for ge: with
+    // the unit's end the backward instantiation for grad_x and grad_h, at 256 vector registers, takes two more accumulation registers)
     int grp = -1;
     int64_t gb = 0, ge = 0, b = blockIdx.x;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      if (q < a.n_groups && grp < 0) {
-        const int64_t nb = (a.off[q + 1] - a.off[q] + RTP_EPB - 1) / RTP_EPB;
-        if (b < nb) { grp = q; gb = a.off[q]; ge = a.off[q + 1]; } else b -= nb;
+      if (q < a.t.n_groups && grp < 0) {
+        const int64_t nb = (a.t.off[q + 1] - a.t.off[q] + RTP_EPB - 1) / RTP_EPB;
+        if (b < nb) { grp = q; gb = a.t.off[q]; ge = a.t.off[q + 1]; } else b -= nb;
       }
     }
     if (grp < 0) return;
@@ -437,17 +435,9 @@ __global__ __launch_bounds__(256) void rtp_param_kernel(RtpArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, hh = lane >> 5;
   const int chunk = blockIdx.x % NCH;
   const int64_t slice = blockIdx.x / NCH;
-  // the slice's group and edges: groups in order, ceil(n / L) slices each
-  int grp = -1;
-  int64_t es = 0, ee = 0, b = slice;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    if (q < a.n_groups && grp < 0) {
-      const int64_t ns = (a.off[q + 1] - a.off[q] + a.L - 1) / a.L;
-      if (b < ns) { grp = q; es = a.off[q] + b * a.L; ee = es + a.L < a.off[q + 1] ? es + a.L : a.off[q + 1]; } else b -= ns;
-    }
-  }
-  if (grp < 0) return;
+  const GroupUnit un = group_unit(a.t, slice, a.L);      // the slice's group and edges
+  if (un.grp < 0) return;
+  const int64_t es = un.begin, ee = un.end;
   const int T = 4 * chunk + wave;
   const bool active = T < TT::NT;
   const RtpSlot sl = rtp_slot<S>(active ? T : 0, j);
@@ -532,58 +522,7 @@ __global__ __launch_bounds__(256) void rtp_param_kernel(RtpArgs a) {
   }
 }
 
-// grad_w2[g] / grad_b2[g] = the group's slice images added in slice order (a group without edges: zeros)
-template <class S>
-__global__ __launch_bounds__(256) void rtp_reduce_kernel(RtpArgs a) {
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  constexpr int64_t PER = (int64_t)S::W * RTP_IMG;
-  if (idx >= PER * a.n_groups) return;
-  const int grp = (int)(idx / PER);
-  const int64_t rem = idx - grp * PER;
-  const int p = (int)(rem / RTP_IMG), col = (int)(rem - (int64_t)p * RTP_IMG);
-  int64_t first = 0, ns = 0;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    if (q < a.n_groups) {
-      const int64_t n = (a.off[q + 1] - a.off[q] + a.L - 1) / a.L;
-      if (q < grp) first += n;
-      if (q == grp) ns = n;
-    }
-  }
-  float sum = 0.f;
-  for (int64_t s = 0; s < ns; ++s) sum += a.ws[(first + s) * PER + rem];
-  if (col < RTP_H) {
-    if (a.gw2) a.gw2[((int64_t)grp * S::W + p) * RTP_H + col] = sum;
-  } else if (a.gb2) {
-    a.gb2[(int64_t)grp * S::W + p] = sum;
-  }
-}
-
-// ---- the radial conv's node side: a fixed-order segmented sum, and the scaled node gradient ----------------------------------------------------------------
-// nodes[n, :] = rows[order[ptr[n]], :] + rows[order[ptr[n] + 1], :] + ... added in that order, one thread per (node, column), columns along lanes (a row is
-// read as one coalesced piece, order[k] is the same address for the lanes of a node); MEAN: divided by max(ptr[n + 1] - ptr[n], 1), a true division as
-// torch_scatter's.  A node without edges: exact zeros.  Plain stores, no atomics: the bits do not depend on the run or the device.
-template <bool MEAN>
-__global__ __launch_bounds__(256) void rtp_seg_kernel(const float* __restrict__ rows, const int32_t* __restrict__ order, const int64_t* __restrict__ ptr,
-                                                      float* __restrict__ nodes, int64_t N, int D) {
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= N * D) return;
-  const int64_t n = idx / D;
-  const int c = (int)(idx - n * D);
-  const int64_t k0 = ptr[n], k1 = ptr[n + 1];
-  float sum = 0.f;
-  int64_t k = k0;
-  if (k < k1) sum = rows[(int64_t)order[k++] * D + c];      // (not 0 + row: a -0 stays what it is)
-  for (; k + 4 <= k1; k += 4) {      // four loads in flight, added in order
-    const float v0 = rows[(int64_t)order[k] * D + c], v1 = rows[(int64_t)order[k + 1] * D + c];
-    const float v2 = rows[(int64_t)order[k + 2] * D + c], v3 = rows[(int64_t)order[k + 3] * D + c];
-    sum += v0; sum += v1; sum += v2; sum += v3;
-  }
-  for (; k < k1; ++k) sum += rows[(int64_t)order[k] * D + c];
-  if (MEAN) sum = sum / (float)(k1 - k0 > 1 ? k1 - k0 : 1);
-  nodes[idx] = sum;
-}
-
+// ---- the radial conv's node side: the scaled node gradient (the fixed-order segmented sums are launch_seg_sum / launch_seg_mean of k_reduce.hip) ------------
 // gn[n, :] = g[n, :] / max(ptr[n + 1] - ptr[n], 1): the backward of the mean, once per node, so that the indexed kernels gather plain rows
 __global__ __launch_bounds__(256) void rtp_node_scale_kernel(const float* __restrict__ g, const int64_t* __restrict__ ptr, float* __restrict__ gn, int64_t N, int D) {
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -593,16 +532,10 @@ __global__ __launch_bounds__(256) void rtp_node_scale_kernel(const float* __rest
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------------------------------------
-static int64_t rtp_units(const RtpArgs& a, int64_t per) {      // sum over the groups of ceil(n / per)
-  int64_t n = 0;
-  for (int q = 0; q < a.n_groups; ++q) n += (a.off[q + 1] - a.off[q] + per - 1) / per;
-  return n;
-}
-
 template <class S>      // S: a shape, or RtpIdx<shape>
 static hipError_t rtp_launch(const RtpArgs& a, bool fwd, hipStream_t s) {
-  const int64_t E = a.off[a.n_groups];
-  const int64_t nwg = rtp_units(a, RTP_EPB);
+  const int64_t E = a.t.off[a.t.n_groups];
+  const int64_t nwg = group_unit_total(a.t, RTP_EPB);
   if (nwg >= (int64_t)1 << 31) return hipErrorInvalidValue;
   const dim3 b(256);
   if (fwd) {
@@ -618,31 +551,28 @@ static hipError_t rtp_launch(const RtpArgs& a, bool fwd, hipStream_t s) {
     if (e != hipSuccess) return e;
   }
   if (a.gw2 || a.gb2) {
-    const int64_t nsl = rtp_units(a, a.L);
+    const int64_t nsl = group_unit_total(a.t, a.L);
     constexpr int NCH = (RtpT<S>::NT + 3) / 4;
     if (nsl > 0) {
       hipLaunchKernelGGL((rtp_param_kernel<S>), dim3((unsigned)(nsl * NCH)), b, 0, s, a);
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) return e;
     }
-    const int64_t n = (int64_t)S::W * RTP_IMG * a.n_groups;
-    hipLaunchKernelGGL((rtp_reduce_kernel<typename RtpPlain<S>::type>), dim3((unsigned)((n + 255) / 256)), b, 0, s, a);
+    return launch_slice_reduce(a.ws, a.t, a.L, ReducePart{a.gw2, a.gb2, S::W, RTP_H}, ReducePart{}, s);
   }
   return hipGetLastError();
 }
 
 int64_t rtp_backward_workspace(int32_t layer, int64_t E, int32_t n_groups) {
   if (layer < 0 || layer > 4 || E < 0 || E >= (int64_t)1 << 31 || n_groups < 1 || n_groups > 4) return -1;
-  const int64_t slices = E / rtp_slice_len(E) + n_groups;      // sum_g ceil(n_g / L) <= floor(E / L) + G
-  return slices * TP_LAYER_W[layer < 3 ? layer : 3] * RTP_IMG * (int64_t)sizeof(float);
+  return slice_bound(E, n_groups) * TP_LAYER_W[layer < 3 ? layer : 3] * RTP_IMG * (int64_t)sizeof(float);
 }
 
 // what the forward and the backward both read: operands, group table, slice length
 static RtpArgs rtp_args(const float* x_dst, const float* sh, const float* h, const int64_t* group_offsets, int n_groups, const float* w2, const float* b2) {
   RtpArgs a{};
   a.x = x_dst; a.sh = sh; a.h = h; a.w2 = w2; a.b2 = b2;
-  for (int q = 0; q <= n_groups; ++q) a.off[q] = group_offsets[q];
-  a.n_groups = n_groups;
+  a.t = group_table(group_offsets, n_groups);
   a.L = rtp_slice_len(group_offsets[n_groups]);
   return a;
 }
@@ -663,8 +593,6 @@ hipError_t launch_rtp_backward(const ConvLayerDev& L, const float* x_dst, const 
 }
 
 // ---- the radial conv ---------------------------------------------------------------------------------------------------------------------------------------------
-static int64_t rconv_pad(int64_t n) { return (n + 3) / 4 * 4; }      // floats of a workspace part: the next part starts on 16 bytes
-
 int64_t rconv_workspace(int32_t layer, int64_t E, int32_t n_groups, int64_t n_in, int64_t n_out, int32_t backward) {
   const int64_t lim = (int64_t)1 << 31;
   if (layer < 0 || layer > 4 || E < 0 || E >= lim || n_groups < 1 || n_groups > 4 || n_in < 0 || n_in >= lim || n_out < 0 || n_out >= lim) return -1;
@@ -676,37 +604,22 @@ int64_t rconv_workspace(int32_t layer, int64_t E, int32_t n_groups, int64_t n_in
     case 2: din = TpLayerShape<2>::DIN; dout = TpLayerShape<2>::DOUT; break;
     default: din = TpLayerShape<3>::DIN; dout = TpLayerShape<3>::DOUT; break;
   }
-  if (!backward) return rconv_pad(E * dout) * (int64_t)sizeof(float);      // the tensor product's rows
+  if (!backward) return ws_pad(E * dout) * (int64_t)sizeof(float);      // the tensor product's rows
   // gn [n_out, Dout], the per-edge rows of grad_x [E, Din], the parameter images
-  return (rconv_pad(n_out * dout) + rconv_pad(E * din)) * (int64_t)sizeof(float) + rtp_backward_workspace(layer, E, n_groups);
-}
-
-template <bool MEAN>
-static hipError_t rtp_seg_launch(const float* rows, const int32_t* order, const int64_t* ptr, float* nodes, int64_t N, int D, hipStream_t s) {
-  const int64_t nb = (N * D + 255) / 256;      // N < 2^31 and D <= 128: fewer than 2^31 workgroups
-  if (nb > 0) hipLaunchKernelGGL((rtp_seg_kernel<MEAN>), dim3((unsigned)nb), dim3(256), 0, s, rows, order, ptr, nodes, N, D);
-  return hipGetLastError();
-}
-
-hipError_t launch_rtp_seg_sum(const float* rows, const int32_t* order, const int64_t* ptr, float* nodes, int64_t N, int D, hipStream_t s) {
-  return rtp_seg_launch<false>(rows, order, ptr, nodes, N, D, s);
-}
-
-static hipError_t rconv_zero(float* p, int64_t n, hipStream_t s) {
-  return (p && n > 0) ? hipMemsetAsync(p, 0, (size_t)n * sizeof(float), s) : hipSuccess;
+  return (ws_pad(n_out * dout) + ws_pad(E * din)) * (int64_t)sizeof(float) + rtp_backward_workspace(layer, E, n_groups);
 }
 
 hipError_t launch_rconv_forward(const ConvLayerDev& L, const RconvGraph& gr, const float* x_nodes, const float* sh, const float* h, const int64_t* group_offsets,
                                 int n_groups, const float* w2, const float* b2, float* out_nodes, float* workspace, hipStream_t s) {
   return tp_dispatch(L, [&](auto shape) {
     using S = decltype(shape);
-    if (group_offsets[n_groups] == 0) return rconv_zero(out_nodes, gr.n_out * S::DOUT, s);
+    if (group_offsets[n_groups] == 0) return zero_async(out_nodes, gr.n_out * S::DOUT, s);
     RtpArgs a = rtp_args(x_nodes, sh, h, group_offsets, n_groups, w2, b2);
     a.xi = gr.dst;
     a.out = workspace;
     hipError_t e = rtp_launch<RtpIdx<S>>(a, true, s);
     if (e != hipSuccess) return e;
-    return rtp_seg_launch<true>(workspace, gr.src_order, gr.src_ptr, out_nodes, gr.n_out, S::DOUT, s);
+    return launch_seg_mean(workspace, gr.src_order, gr.src_ptr, out_nodes, gr.n_out, S::DOUT, s);
   });
 }
 
@@ -717,14 +630,14 @@ hipError_t launch_rconv_backward(const ConvLayerDev& L, const RconvGraph& gr, co
     using S = decltype(shape);
     const int64_t E = group_offsets[n_groups];
     if (E == 0) {
-      hipError_t e = rconv_zero(grad_x_nodes, gr.n_in * S::DIN, s);
-      if (e == hipSuccess) e = rconv_zero(grad_w2, (int64_t)n_groups * S::W * RTP_H, s);
-      if (e == hipSuccess) e = rconv_zero(grad_b2, (int64_t)n_groups * S::W, s);
+      hipError_t e = zero_async(grad_x_nodes, gr.n_in * S::DIN, s);
+      if (e == hipSuccess) e = zero_async(grad_w2, (int64_t)n_groups * S::W * RTP_H, s);
+      if (e == hipSuccess) e = zero_async(grad_b2, (int64_t)n_groups * S::W, s);
       return e;
     }
     float* gn = workspace;
-    float* gx_rows = gn + rconv_pad(gr.n_out * S::DOUT);
-    float* images = gx_rows + rconv_pad(E * S::DIN);
+    float* gx_rows = gn + ws_pad(gr.n_out * S::DOUT);
+    float* images = gx_rows + ws_pad(E * S::DIN);
     const int64_t nb = (gr.n_out * S::DOUT + 255) / 256;
     hipLaunchKernelGGL(rtp_node_scale_kernel, dim3((unsigned)nb), dim3(256), 0, s, grad_out_nodes, gr.src_ptr, gn, gr.n_out, (int)S::DOUT);
     hipError_t e = hipGetLastError();
@@ -734,7 +647,7 @@ hipError_t launch_rconv_backward(const ConvLayerDev& L, const RconvGraph& gr, co
     a.gx = grad_x_nodes ? gx_rows : nullptr; a.gsh = grad_sh; a.gh = grad_h; a.gw2 = grad_w2; a.gb2 = grad_b2; a.ws = images;
     e = rtp_launch<RtpIdx<S>>(a, false, s);
     if (e != hipSuccess || !grad_x_nodes) return e;
-    return rtp_seg_launch<false>(gx_rows, gr.dst_order, gr.dst_ptr, grad_x_nodes, gr.n_in, S::DIN, s);
+    return launch_seg_sum(gx_rows, gr.dst_order, gr.dst_ptr, grad_x_nodes, gr.n_in, S::DIN, s);
   });
 }
 

@@ -202,6 +202,31 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def _need(need, who, four=False):
+    """``need`` of a ``*_backward`` as a tuple of bools; a call that asks for no gradient (``four``: or not for four flags) is refused"""
+    need = tuple(bool(n) for n in need)
+    if four and (len(need) != 4 or not any(need)):
+        raise RuntimeError(f'ddk: {who} needs at least one of its four gradients to compute')
+    if not any(need):
+        raise RuntimeError(f'ddk: {who} needs at least one gradient to compute')
+    return need
+
+
+def _outputs(need, shapes, device):
+    """(outs, live) of a ``*_backward``: a new fp32 tensor of its shape where ``need`` is set and None elsewhere; ``live``: one of them has an element
+    (empty tensors have no address: without one the entry would see no output at all, and the caller returns ``outs`` as they are)"""
+    outs = [torch.empty(shape, dtype=torch.float32, device=device) if n else None for n, shape in zip(need, shapes)]
+    return outs, any(o is not None and o.numel() for o in outs)
+
+
+def _workspace(nbytes, what, device):
+    """``nbytes`` of a workspace query as a tensor from torch's allocator, which orders its reuse after the launches on the current stream when the
+    caller lets go of it; a negative answer is refused as 'ddk: ``what``'"""
+    if nbytes < 0:
+        raise RuntimeError('ddk: ' + what)
+    return torch.empty(max(int(nbytes), 16) // 4, dtype=torch.float32, device=device)
+
+
 class Context:
     """One ddk_ctx (one device).  device=-1 gives a host-only context (weight packing only, for CPU tests)."""
 
@@ -388,9 +413,7 @@ class Context:
         """The vector-Jacobian product of ``rtp_forward`` (ddk_rtp_backward): (grad_x, grad_sh, grad_h, grad_w2, grad_b2), None where ``need`` is false.
         ``w2`` and ``b2`` may be None when only grad_w2 / grad_b2 are asked for; ``b2`` is read for grad_x / grad_sh alone.  The workspace of the
         parameter gradients comes from torch's allocator and is released on return."""
-        need = tuple(bool(n) for n in need)
-        if not any(need):
-            raise RuntimeError('ddk: rtp_backward needs at least one gradient to compute')
+        need = _need(need, 'rtp_backward')
         if w2 is None and any(need[:3]):
             raise RuntimeError('ddk: rtp_backward needs w2 for grad_x, grad_sh and grad_h')
         if b2 is None and any(need[:2]):
@@ -399,17 +422,12 @@ class Context:
         grad_out = _need_cuda(grad_out).contiguous().float()
         if grad_out.dim() != 2 or grad_out.shape[0] != E:
             raise RuntimeError('ddk: rtp_backward takes grad_out [E, Dout]')
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x_dst.device)
-        outs = [new(E, x_dst.shape[1]) if need[0] else None, new(E, 4) if need[1] else None, new(E, 72) if need[2] else None,
-                new(G, W, 72) if need[3] else None, new(G, W) if need[4] else None]
+        outs, live = _outputs(need, ((E, x_dst.shape[1]), (E, 4), (E, 72), (G, W, 72), (G, W)), x_dst.device)
+        if not live:
+            return tuple(outs)
         ws = None
         if need[3] or need[4]:
-            nbytes = self.L.ddk_rtp_backward_workspace(layer, E, G)
-            if nbytes < 0:
-                raise RuntimeError(f'ddk: rtp_backward: no workspace for layer {layer}, E = {E}, {G} groups')
-            ws = torch.empty(max(int(nbytes), 4) // 4, dtype=torch.float32, device=x_dst.device)
-        elif E == 0:      # (empty tensors have no address: the entry would see no output at all)
-            return tuple(outs)
+            ws = _workspace(self.L.ddk_rtp_backward_workspace(layer, E, G), f'rtp_backward: no workspace for layer {layer}, E = {E}, {G} groups', x_dst.device)
         self._check(self.L.ddk_rtp_backward(self.h, layer, _ptr(x_dst), _ptr(sh), _ptr(h), offs, G, _ptr(w2), _ptr(b2), _ptr(grad_out), E,
                                             *[_ptr(o) for o in outs], _ptr(ws), _stream()), 'ddk_rtp_backward')
         return tuple(outs)      # (ws goes back to torch's allocator, which orders its reuse after this launch on the current stream)
@@ -468,8 +486,9 @@ class Context:
             raise RuntimeError('ddk: rconv_forward needs w2 and b2')
         dout = tp_layer_shape(layer, self.cfg.ns, self.cfg.nv)['dout']
         out = torch.empty((graph.n_out, dout), dtype=torch.float32, device=x_nodes.device)
-        ws = self._rconv_workspace(layer, graph, G, False, x_nodes.device)
         g = graph
+        ws = _workspace(self.L.ddk_rconv_workspace(layer, g.E, G, g.n_in, g.n_out, 0),
+                        f'no radial-conv workspace for layer {layer}, E = {g.E}, {G} groups, {g.n_in} -> {g.n_out} nodes', x_nodes.device)
         self._check(self.L.ddk_rconv_forward(self.h, layer, _ptr(x_nodes), g.n_in, g.n_out, _ptr(g.src), _ptr(g.dst), _ptr(g.src_order), _ptr(g.src_ptr),
                                              _ptr(sh), _ptr(h), offs, G, _ptr(w2), _ptr(b2), E, _ptr(out), _ptr(ws), _stream()), 'ddk_rconv_forward')
         return out
@@ -478,9 +497,7 @@ class Context:
         """The vector-Jacobian product of ``rconv_forward`` (ddk_rconv_backward): (grad_x_nodes [n_in, Din], grad_sh, grad_h, grad_w2, grad_b2), None
         where ``need`` is false; ``w2`` / ``b2`` may be None as in ``rtp_backward``.  The same bits from call to call.  The workspace comes from torch's
         allocator and is released on return."""
-        need = tuple(bool(n) for n in need)
-        if not any(need):
-            raise RuntimeError('ddk: rconv_backward needs at least one gradient to compute')
+        need = _need(need, 'rconv_backward')
         if w2 is None and any(need[:3]):
             raise RuntimeError('ddk: rconv_backward needs w2 for grad_x_nodes, grad_sh and grad_h')
         if b2 is None and any(need[:2]):
@@ -490,22 +507,15 @@ class Context:
         grad_out_nodes = _need_cuda(grad_out_nodes).contiguous().float()
         if grad_out_nodes.dim() != 2 or grad_out_nodes.shape[0] != g.n_out:
             raise RuntimeError('ddk: rconv_backward takes grad_out_nodes [n_out, Dout]')
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x_nodes.device)
-        outs = [new(g.n_in, x_nodes.shape[1]) if need[0] else None, new(E, 4) if need[1] else None, new(E, 72) if need[2] else None,
-                new(G, W, 72) if need[3] else None, new(G, W) if need[4] else None]
-        if not any(o is not None and o.numel() for o in outs):      # (empty tensors have no address: the entry would see no output at all)
+        outs, live = _outputs(need, ((g.n_in, x_nodes.shape[1]), (E, 4), (E, 72), (G, W, 72), (G, W)), x_nodes.device)
+        if not live:
             return tuple(outs)
-        ws = self._rconv_workspace(layer, graph, G, True, x_nodes.device)
+        ws = _workspace(self.L.ddk_rconv_workspace(layer, E, G, g.n_in, g.n_out, 1),
+                        f'no radial-conv workspace for layer {layer}, E = {E}, {G} groups, {g.n_in} -> {g.n_out} nodes', x_nodes.device)
         self._check(self.L.ddk_rconv_backward(self.h, layer, _ptr(x_nodes), g.n_in, g.n_out, _ptr(g.src), _ptr(g.dst), _ptr(g.src_order), _ptr(g.src_ptr),
                                               _ptr(g.dst_order), _ptr(g.dst_ptr), _ptr(sh), _ptr(h), offs, G, _ptr(w2), _ptr(b2), _ptr(grad_out_nodes), E,
                                               *[_ptr(o) for o in outs], _ptr(ws), _stream()), 'ddk_rconv_backward')
         return tuple(outs)      # (ws goes back to torch's allocator, which orders its reuse after these launches on the current stream)
-
-    def _rconv_workspace(self, layer, graph, G, backward, device):
-        nbytes = self.L.ddk_rconv_workspace(layer, graph.E, G, graph.n_in, graph.n_out, int(backward))
-        if nbytes < 0:
-            raise RuntimeError(f'ddk: no radial-conv workspace for layer {layer}, E = {graph.E}, {G} groups, {graph.n_in} -> {graph.n_out} nodes')
-        return torch.empty(max(int(nbytes), 4) // 4, dtype=torch.float32, device=device)
 
     # ---- the head convolutions: node features to receiver rows ------------------------------------------
     def _hconv_operands(self, head, graph, x, sh, h, w2, b2):
@@ -530,12 +540,6 @@ class Context:
                 raise RuntimeError(f'ddk: the head conv takes b2 [W] = {(s["W"],)} on the device of x; got {tuple(b2.shape)}')
         return s, x, sh, h, w2, b2
 
-    def _hconv_workspace(self, head, graph, backward, device):
-        nbytes = self.L.ddk_hconv_workspace(head, graph.E, graph.n_in, graph.n_out, int(backward))
-        if nbytes < 0:
-            raise RuntimeError(f'ddk: no head-conv workspace for head {head}, E = {graph.E}, {graph.n_in} -> {graph.n_out} nodes')
-        return torch.empty(max(int(nbytes), 4) // 4, dtype=torch.float32, device=device)
-
     def hconv_forward(self, head, graph, x, sh, h, w2, b2):
         """A head conv (ddk_hconv_forward): out [n_out, dout] = the mean over ``graph.src`` of e3nn's FullyConnectedTensorProduct of ``head_tp_shape(head)``
         on (x[graph.dst], sh, w2 h + b2); the per-edge weights and the gathered rows are never stored, the mean is a fixed-order sum (no atomics).  For
@@ -547,7 +551,8 @@ class Context:
         out = torch.empty((g.n_out, s['dout']), dtype=torch.float32, device=x.device)
         if out.numel() == 0:
             return out
-        ws = self._hconv_workspace(head, g, False, x.device)
+        ws = _workspace(self.L.ddk_hconv_workspace(head, g.E, g.n_in, g.n_out, 0),
+                        f'no head-conv workspace for head {head}, E = {g.E}, {g.n_in} -> {g.n_out} nodes', x.device)
         self._check(self.L.ddk_hconv_forward(self.h, head, _ptr(x), g.n_in, g.n_out, _ptr(g.src), _ptr(g.dst), _ptr(g.src_order), _ptr(g.src_ptr), _ptr(sh),
                                              _ptr(h), _ptr(w2), _ptr(b2), g.E, _ptr(out), _ptr(ws), _stream()), 'ddk_hconv_forward')
         return out
@@ -556,9 +561,7 @@ class Context:
         """The vector-Jacobian product of ``hconv_forward`` (ddk_hconv_backward): (grad_x [n_in, din], grad_h [E, K], grad_w2 [W, K], grad_b2 [W]), None
         where ``need`` is false.  ``w2`` may be None when neither grad_x nor grad_h is asked for, ``b2`` unless grad_x is.  There is no grad_sh.  The same
         bits from call to call.  The workspace comes from torch's allocator and is released on return."""
-        need = tuple(bool(n) for n in need)
-        if len(need) != 4 or not any(need):
-            raise RuntimeError('ddk: hconv_backward needs at least one of its four gradients to compute')
+        need = _need(need, 'hconv_backward', four=True)
         if w2 is None and any(need[:2]):
             raise RuntimeError('ddk: hconv_backward needs w2 for grad_x and grad_h')
         if b2 is None and need[0]:
@@ -568,12 +571,11 @@ class Context:
         grad_out = _need_cuda(grad_out).contiguous().float()
         if grad_out.shape != (g.n_out, s['dout']) or grad_out.device != x.device:
             raise RuntimeError(f'ddk: hconv_backward takes grad_out [n_out, {s["dout"]}] on the device of x')
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x.device)
-        outs = [new(g.n_in, s['din']) if need[0] else None, new(g.E, s['K']) if need[1] else None, new(s['W'], s['K']) if need[2] else None,
-                new(s['W']) if need[3] else None]
-        if not any(o is not None and o.numel() for o in outs):      # (empty tensors have no address: the entry would see no output at all)
+        outs, live = _outputs(need, ((g.n_in, s['din']), (g.E, s['K']), (s['W'], s['K']), (s['W'],)), x.device)
+        if not live:
             return tuple(outs)
-        ws = self._hconv_workspace(head, g, True, x.device)
+        ws = _workspace(self.L.ddk_hconv_workspace(head, g.E, g.n_in, g.n_out, 1),
+                        f'no head-conv workspace for head {head}, E = {g.E}, {g.n_in} -> {g.n_out} nodes', x.device)
         self._check(self.L.ddk_hconv_backward(self.h, head, _ptr(x), g.n_in, g.n_out, _ptr(g.src), _ptr(g.dst), _ptr(g.src_order), _ptr(g.src_ptr),
                                               _ptr(g.dst_order), _ptr(g.dst_ptr), _ptr(sh), _ptr(h), _ptr(w2), _ptr(b2), _ptr(grad_out), g.E,
                                               *[_ptr(o) for o in outs], _ptr(ws), _stream()), 'ddk_hconv_backward')
@@ -645,9 +647,7 @@ class Context:
         [G, 72]), None where ``need`` is false.  ``h``: the forward's output (it carries the pattern of ReLU and Dropout; no seed is needed); ``w1`` may be
         None when only grad_w1 / grad_b1 are asked for.  No atomics: the same bits from call to call.  The workspace comes from torch's allocator and is
         released on return."""
-        need = tuple(bool(n) for n in need)
-        if len(need) != 4 or not any(need):
-            raise RuntimeError('ddk: rhid_backward needs at least one of its four gradients to compute')
+        need = _need(need, 'rhid_backward', four=True)
         if w1 is None and any(need[:2]):
             raise RuntimeError('ddk: rhid_backward needs w1 for grad_xs and grad_emb')
         xs, emb, offs, G, w1, _, p = self._rhid_operands(graph, xs, emb, group_offsets, w1, None, p)
@@ -655,14 +655,10 @@ class Context:
         h, grad_h = (_need_cuda(t).contiguous().float() for t in (h, grad_h))
         if h.shape != (g.E, 72) or grad_h.shape != (g.E, 72) or h.device != xs.device or grad_h.device != xs.device:
             raise RuntimeError('ddk: rhid_backward takes h and grad_h [E, 72] on the device of xs')
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=xs.device)
-        outs = [new(g.n_in, 24) if need[0] else None, new(g.E, 24) if need[1] else None, new(G, 72, 72) if need[2] else None, new(G, 72) if need[3] else None]
-        if not any(o is not None and o.numel() for o in outs):      # (empty tensors have no address: the entry would see no output at all)
+        outs, live = _outputs(need, ((g.n_in, 24), (g.E, 24), (G, 72, 72), (G, 72)), xs.device)
+        if not live:
             return tuple(outs)
-        nbytes = self.L.ddk_rhid_workspace(g.E, G, g.n_in)
-        if nbytes < 0:
-            raise RuntimeError(f'ddk: no radial-hidden workspace for E = {g.E}, {G} groups, {g.n_in} nodes')
-        ws = torch.empty(max(int(nbytes), 4) // 4, dtype=torch.float32, device=xs.device)
+        ws = _workspace(self.L.ddk_rhid_workspace(g.E, G, g.n_in), f'no radial-hidden workspace for E = {g.E}, {G} groups, {g.n_in} nodes', xs.device)
         self._check(self.L.ddk_rhid_backward(self.h, _ptr(xs), g.n_in, _ptr(g.src), _ptr(g.dst), _ptr(g.src_order), _ptr(g.src_ptr), _ptr(g.dst_order),
                                              _ptr(g.dst_ptr), _ptr(emb), _ptr(h), offs, G, _ptr(w1), _ptr(grad_h), p, g.E, *[_ptr(o) for o in outs],
                                              _ptr(ws), _stream()), 'ddk_rhid_backward')
@@ -732,20 +728,14 @@ class Context:
         """The vector-Jacobian product of ``eemb_forward`` for its parameters (ddk_eemb_backward): (grad_w1 [24, K], grad_b1 [24], grad_w2 [24, 24],
         grad_b2 [24]), None where ``need`` is false.  The hidden layer and the mask are recomputed from the coordinates and ``seed``; the workspace holds
         the slice images alone, comes from torch's allocator and is released on return.  No atomics: the same bits from call to call."""
-        need = tuple(bool(x) for x in need)
-        if len(need) != 4 or not any(need):
-            raise RuntimeError('ddk: eemb_backward needs at least one of its four gradients to compute')
+        need = _need(need, 'eemb_backward', four=True)
         t, n, sc = self._eemb_operands(pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, None, p)
         F, E, dev = n[2], n[4], t[0].device
         grad_emb = _need_cuda(grad_emb).contiguous().float()
         if grad_emb.shape != (E, 24) or grad_emb.device != dev:
             raise RuntimeError(f'ddk: eemb_backward takes grad_emb [E, 24] = {(E, 24)} on the device of pos_a; got {tuple(grad_emb.shape)}')
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        outs = [new(24, F + 64) if need[0] else None, new(24) if need[1] else None, new(24, 24) if need[2] else None, new(24) if need[3] else None]
-        nbytes = self.L.ddk_eemb_workspace(E, F + 64)
-        if nbytes < 0:
-            raise RuntimeError(f'ddk: no edge-embedding workspace for E = {E}, K = {F + 64}')
-        ws = torch.empty(max(int(nbytes), 16) // 4, dtype=torch.float32, device=dev)
+        outs, _ = _outputs(need, ((24, F + 64), (24,), (24, 24), (24,)), dev)      # (never empty)
+        ws = _workspace(self.L.ddk_eemb_workspace(E, F + 64), f'no edge-embedding workspace for E = {E}, K = {F + 64}', dev)
         self._eemb_call(self.L.ddk_eemb_backward, t, n, sc, seed, (_ptr(grad_emb) if E else None, E, *[_ptr(o) for o in outs], _ptr(ws)), 'ddk_eemb_backward')
         return tuple(outs)      # (ws goes back to torch's allocator, which orders its reuse after these launches on the current stream)
 

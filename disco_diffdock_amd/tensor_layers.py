@@ -104,6 +104,16 @@ def _shape_context(device_index):
     return _shape_ctx[device_index]
 
 
+def _ctx_of(t):
+    """the shape context of the device of tensor ``t``"""
+    return _shape_context(t.device.index or 0)
+
+
+def _grad_rows(grad):
+    """an incoming gradient [..., cols] as contiguous fp32 rows [E, cols]"""
+    return _as_rows(grad, grad.shape[-1])
+
+
 def _grads_like(grads, meta):
     """each gradient in the shape and dtype of its input (meta: their (shape, dtype)); None stays None"""
     return tuple(None if g is None else g.reshape(shape).to(dtype) for g, (shape, dtype) in zip(grads, meta))
@@ -120,7 +130,7 @@ class _FasterTPFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(fctx, in_, sh, weight, layer, weight_numel, out_size):
-        ctx = _shape_context(in_.device.index or 0)
+        ctx = _ctx_of(in_)
         x, s, w = _as_rows(in_, in_.shape[-1]), _as_rows(sh, 4), _as_rows(weight, weight_numel)
         out = ctx.tp_forward(layer, x, s, w, out_size)
         fctx.save_for_backward(x, s, w if (fctx.needs_input_grad[0] or fctx.needs_input_grad[1]) else None)      # grad_w alone does not read w
@@ -133,7 +143,7 @@ class _FasterTPFunction(torch.autograd.Function):
     def backward(fctx, grad_out):
         x, s, w = fctx.saved_tensors
         need = tuple(fctx.needs_input_grad[:3])
-        g = grad_out.reshape(-1, grad_out.shape[-1]).contiguous().float()
+        g = _grad_rows(grad_out)
         with torch.cuda.device(x.device):
             grads = fctx.ddk.tp_backward(fctx.layer, x, s, w, g, need)
         return _grads_like(grads, fctx.meta) + (None, None, None)
@@ -156,7 +166,7 @@ class FasterTensorProduct(nn.Module):
         if torch.is_grad_enabled() and (in_.requires_grad or sh.requires_grad or weight.requires_grad):
             return _FasterTPFunction.apply(in_, sh, weight, self.layer, self.weight_numel, self.out_size)
         lead = in_.shape[:-1]
-        ctx = _shape_context(in_.device.index or 0)
+        ctx = _ctx_of(in_)
         out = ctx.tp_forward(self.layer, in_.reshape(-1, in_.shape[-1]), sh.reshape(-1, 4),
                              weight.reshape(-1, self.weight_numel), self.out_size)
         return out.reshape(lead + (self.out_size,))
@@ -168,7 +178,7 @@ class _RadialTPFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(fctx, in_, sh, h, w2, b2, layer, offsets, out_size):
-        ctx = _shape_context(in_.device.index or 0)
+        ctx = _ctx_of(in_)
         x, s, hh = _as_rows(in_, in_.shape[-1]), _as_rows(sh, 4), _as_rows(h, h.shape[-1])
         w, b = w2.contiguous().float(), b2.contiguous().float()
         out = ctx.rtp_forward(layer, x, s, hh, offsets, w, b, out_size)
@@ -183,7 +193,7 @@ class _RadialTPFunction(torch.autograd.Function):
     def backward(fctx, grad_out):
         x, s, hh, w, b = fctx.saved_tensors
         need = tuple(fctx.needs_input_grad[:5])
-        g = grad_out.reshape(-1, grad_out.shape[-1]).contiguous().float()
+        g = _grad_rows(grad_out)
         with torch.cuda.device(x.device):
             grads = fctx.ddk.rtp_backward(fctx.layer, x, s, hh, fctx.offsets, w, b, g, need)
         return _grads_like(grads, fctx.meta) + (None, None, None)
@@ -237,7 +247,7 @@ def fused_radial_tp(tp, fc, x_dst, edge_sh, edge_attr):
         raise RuntimeError('ddk: fused_radial_tp takes x_dst [E, Din] with E the total of the edge groups')
     if torch.is_grad_enabled() and any(t.requires_grad for t in (x_dst, edge_sh, hidden, w2, b2)):
         return _RadialTPFunction.apply(x_dst, edge_sh, hidden, w2, b2, tp.layer, tuple(offs), tp.out_size)
-    ctx = _shape_context(x_dst.device.index or 0)
+    ctx = _ctx_of(x_dst)
     return ctx.rtp_forward(tp.layer, x_dst, edge_sh.reshape(-1, 4), hidden, offs, w2, b2, tp.out_size)
 
 
@@ -248,7 +258,7 @@ class _RadialConvFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(fctx, node_attr, sh, h, w2, b2, layer, offsets, graph):
-        ctx = _shape_context(node_attr.device.index or 0)
+        ctx = _ctx_of(node_attr)
         x, s, hh = _as_rows(node_attr, node_attr.shape[-1]), _as_rows(sh, 4), _as_rows(h, h.shape[-1])
         w, b = w2.contiguous().float(), b2.contiguous().float()
         out = ctx.rconv_forward(layer, graph, x, s, hh, offsets, w, b)
@@ -263,7 +273,7 @@ class _RadialConvFunction(torch.autograd.Function):
     def backward(fctx, grad_out):
         x, s, hh, w, b = fctx.saved_tensors
         need = tuple(fctx.needs_input_grad[:5])
-        g = grad_out.reshape(-1, grad_out.shape[-1]).contiguous().float()
+        g = _grad_rows(grad_out)
         with torch.cuda.device(x.device):
             grads = fctx.ddk.rconv_backward(fctx.layer, fctx.graph, x, s, hh, fctx.offsets, w, b, g, need)
         return _grads_like(grads, fctx.meta) + (None, None, None)
@@ -289,7 +299,7 @@ def fused_radial_conv(tp, fc, node_attr, edge_index, edge_sh, edge_attr, out_nod
                            f'{node_attr.shape[0]} -> {n_out} nodes and {offs[-1]} edges in the groups')
     if torch.is_grad_enabled() and any(t.requires_grad for t in (node_attr, edge_sh, hidden, w2, b2)):
         return _RadialConvFunction.apply(node_attr, edge_sh, hidden, w2, b2, tp.layer, tuple(offs), graph)
-    ctx = _shape_context(node_attr.device.index or 0)
+    ctx = _ctx_of(node_attr)
     return ctx.rconv_forward(tp.layer, graph, node_attr, edge_sh.reshape(-1, 4), hidden, offs, w2, b2)
 
 
@@ -300,7 +310,7 @@ class _RadialHiddenFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(fctx, xs, emb, w1, b1, offsets, graph, p, seed):
-        ctx = _shape_context(xs.device.index or 0)
+        ctx = _ctx_of(xs)
         x, e = _as_rows(xs, 24), _as_rows(emb, 24)
         w, b = w1.contiguous().float(), b1.contiguous().float()
         h = ctx.rhid_forward(graph, x, e, offsets, w, b, p, seed)
@@ -359,7 +369,7 @@ def fused_radial_hidden(fc, node_attr, edge_emb, group_offsets, graph, seed=None
     w1, b1 = torch.stack([blk[0].weight for blk in fc]), torch.stack([blk[0].bias for blk in fc])
     if torch.is_grad_enabled() and any(t.requires_grad for t in (xs, edge_emb, w1, b1)):
         return _RadialHiddenFunction.apply(xs, edge_emb, w1, b1, tuple(offs), graph, p, int(seed))
-    return _shape_context(node_attr.device.index or 0).rhid_forward(graph, xs, edge_emb, offs, w1, b1, p, int(seed))
+    return _ctx_of(node_attr).rhid_forward(graph, xs, edge_emb, offs, w1, b1, p, int(seed))
 
 
 def _layer_seed(seed, l):
@@ -392,7 +402,7 @@ class _EdgeEmbeddingFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(fctx, w1, b1, w2, b2, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, p, seed):
-        ctx = _shape_context(pos_a.device.index or 0)
+        ctx = _ctx_of(pos_a)
         emb, sh = ctx.eemb_forward(pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, b2, p, seed)
         fctx.save_for_backward(w1, b1, w2, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index)      # (b2 is not read by the backward)
         fctx.ddk, fctx.scalars = ctx, (start, stop, p, seed)
@@ -469,7 +479,7 @@ def fused_edge_embedding(mlp, expansion, pos_a, pos_b, edge_index, sig, sig_inde
     w1, b1, w2, b2 = mlp[0].weight, mlp[0].bias, mlp[3].weight, mlp[3].bias
     if torch.is_grad_enabled() and any(t.requires_grad for t in (w1, b1, w2, b2)):
         return _EdgeEmbeddingFunction.apply(w1, b1, w2, b2, *operands, start, stop, p, int(seed))
-    return _shape_context(pos_a.device.index or 0).eemb_forward(*operands, start, stop, w1, b1, w2, b2, p, int(seed))
+    return _ctx_of(pos_a).eemb_forward(*operands, start, stop, w1, b1, w2, b2, p, int(seed))
 
 
 class _HeadConvFunction(torch.autograd.Function):
@@ -479,7 +489,7 @@ class _HeadConvFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(fctx, node_attr, sh, h, w2, b2, head, graph):
-        ctx = _shape_context(node_attr.device.index or 0)
+        ctx = _ctx_of(node_attr)
         x, s, hh = _as_rows(node_attr, node_attr.shape[-1]), _as_rows(sh, 4), _as_rows(h, h.shape[-1])
         w, b = w2.contiguous().float(), b2.contiguous().float()
         out = ctx.hconv_forward(head, graph, x, s, hh, w, b)
@@ -495,7 +505,7 @@ class _HeadConvFunction(torch.autograd.Function):
         x, s, hh, w, b = fctx.saved_tensors
         ng = fctx.needs_input_grad
         need = (ng[0], ng[2], ng[3], ng[4])
-        g = grad_out.reshape(-1, grad_out.shape[-1]).contiguous().float()
+        g = _grad_rows(grad_out)
         with torch.cuda.device(x.device):
             gx, gh, gw2, gb2 = _grads_like(fctx.ddk.hconv_backward(fctx.head, fctx.graph, x, s, hh, w, b, g, need), fctx.meta)
         return gx, None, gh, gw2, gb2, None, None
@@ -535,7 +545,7 @@ def fused_head_conv(head, fc, node_attr, edge_index, edge_sh, edge_attr, out_nod
     w2, b2 = fc[4].weight, fc[4].bias
     if torch.is_grad_enabled() and any(t.requires_grad for t in (node_attr, hidden, w2, b2)):
         return _HeadConvFunction.apply(node_attr, edge_sh, hidden, w2, b2, head, graph)
-    return _shape_context(node_attr.device.index or 0).hconv_forward(head, graph, node_attr, edge_sh, hidden, w2, b2)
+    return _ctx_of(node_attr).hconv_forward(head, graph, node_attr, edge_sh, hidden, w2, b2)
 
 
 class _GatherRowsFunction(torch.autograd.Function):
@@ -553,7 +563,7 @@ class _GatherRowsFunction(torch.autograd.Function):
         order, ptr = fctx.saved_tensors
         shape, dtype = fctx.meta
         with torch.cuda.device(grad.device):
-            nodes = _shape_context(grad.device.index or 0).seg_sum(grad.reshape(grad.shape[0], -1), order, ptr)
+            nodes = _ctx_of(grad).seg_sum(grad.reshape(grad.shape[0], -1), order, ptr)
         return nodes.reshape(shape).to(dtype), None, None, None
 
 
