@@ -1,5 +1,6 @@
-// The two pieces of rigid-body arithmetic that the pose update (k_se3.hip) and the conformer matching (k_match.hip) share: the rotation matrix of an
-// axis-angle vector and the optimal rotation of a point-set pair from its 3 x 3 covariance (Horn 1987).
+// The pieces of rigid-body arithmetic that the pose update (k_se3.hip) and the conformer matching (k_match.hip) share: the rotation matrix of an
+// axis-angle vector, the bond rotor step built on it (the update's rotor loop, randomize_kernel and match_eval) and the optimal rotation of a
+// point-set pair from its 3 x 3 covariance (Horn 1987).
 #pragma once
 #include "model.h"
 
@@ -18,6 +19,23 @@ __device__ inline void axis_angle_to_matrix_dev(float ax, float ay, float az, fl
   R[0] = (float)(1 - two_s * (j * j + k * k)); R[1] = (float)(two_s * (i * j - k * r)); R[2] = (float)(two_s * (i * k + j * r));
   R[3] = (float)(two_s * (i * j + k * r)); R[4] = (float)(1 - two_s * (i * i + k * k)); R[5] = (float)(two_s * (j * k - i * r));
   R[6] = (float)(two_s * (i * k - j * r)); R[7] = (float)(two_s * (j * k + i * r)); R[8] = (float)(1 - two_s * (i * i + j * j));
+}
+
+// The bond rotor step (utils/torsion.py:48-68) on the coordinates xyz [3 n]: the rotation by th about the axis xyz[u] - xyz[v] -> M [9], and its
+// pivot xyz[v] -> piv [3].  A caller that skips zero angles tests th itself.
+__device__ inline void bond_rotor(const float* xyz, int u, int v, float th, float* M, float* piv) {
+  const float px = xyz[3 * v], py = xyz[3 * v + 1], pz = xyz[3 * v + 2];
+  const float ax = xyz[3 * u] - px, ay = xyz[3 * u + 1] - py, az = xyz[3 * u + 2] - pz;
+  const float nn = sqrtf(ax * ax + ay * ay + az * az);
+  axis_angle_to_matrix_dev(ax / nn * th, ay / nn * th, az / nn * th, M);
+  piv[0] = px; piv[1] = py; piv[2] = pz;
+}
+
+// (x, y, z) <- M ((x, y, z) - piv) + piv
+__device__ inline void rotate_about(const float* M, const float* piv, float& x, float& y, float& z) {
+  x -= piv[0]; y -= piv[1]; z -= piv[2];
+  const float nx = M[0] * x + M[1] * y + M[2] * z + piv[0], ny = M[3] * x + M[4] * y + M[5] * z + piv[1], nz = M[6] * x + M[7] * y + M[8] * z + piv[2];
+  x = nx; y = ny; z = nz;
 }
 
 // Horn 1987 for the covariance S[a][b] = sum a_i[a] b_i[b] of two centred point sets: the largest eigenvalue of a 4 x 4 symmetric matrix is

@@ -7,11 +7,13 @@
 // tile tables (conv_pack.hip: build_head_layer): tor_bond_conv keeps only the two dot-product parts with the 1o block T of
 // sh (x) sh_2e(bond axis) in the place of the edge's sh[1:4] (W = 288: 12 tiles), final_conv is the two vector blocks with two output
 // channels each (W = 144, MLP width 48 zero padded to 72).  Here: the kernel that builds both edge sets with their 72-wide edge attributes
-// (heads_pre_kernel) and the one that finishes the two outputs (heads_post_kernel).  A launch with a few thousand edges is spread over
-// the CUs by the fused kernel's column split of short work queues.
+// (heads_pre_kernel) and the one that finishes the two outputs (heads_post_kernel; its arithmetic lives in k_head_finish.h, shared with the fused
+// finish inside se3_update_kernel<true, *>).  A launch with a few thousand edges is spread over the CUs by the fused kernel's column split of short
+// work queues.
 // The Clebsch-Gordan constants are e3nn's real-basis wigner 3j (restated in oracle/e3nn_lite.py):
 //   w3j(0,1,1) = w3j(1,0,1) = delta/sqrt3,  w3j(1,1,1) = eps_ijk/sqrt6,  w3j(1,1,0) = delta/sqrt3,  w3j(1,2,1) below.
 #include "model.h"
+#include "k_head_finish.h"
 
 namespace ddk {
 
@@ -180,7 +182,7 @@ __global__ __launch_bounds__(256) void heads_pre_kernel(HeadArgs A, int n_tor_bl
 }
 
 // blocks [0, B*R): tor_bond_conv's mean / BatchNorm / tor_final_layer (score_model.py:302-307); blocks [B*R, B*R + B): final_conv's mean /
-// BatchNorm and the tr / rot magnitude MLPs (:272-286).  Every accumulator that is read is cleared behind the read.
+// BatchNorm and the tr / rot magnitude MLPs (:272-286).  The arithmetic is k_head_finish.h's, which the POST block of se3_update_kernel runs too.
 __global__ __launch_bounds__(64) void heads_post_kernel(HeadArgs A, int n_tor_blocks) {
   __shared__ float v48[2 * NS], hid[NS], g12[12];
   const int tid = threadIdx.x;
@@ -188,47 +190,17 @@ __global__ __launch_bounds__(64) void heads_post_kernel(HeadArgs A, int n_tor_bl
   if ((int)blockIdx.x < n_tor_blocks) {
     float* row = A.h_sum + (size_t)(A.B + blockIdx.x) * XW;
     const int ne = A.h_deg[blockIdx.x];
-    if (tid < 2 * NS) {
-      const float s = row[tid] / (float)(ne > 1 ? ne : 1);
-      row[tid] = 0.0f;
-      v48[tid] = (s - A.md.tb_bn_mean[tid]) * A.md.tb_bn_scale[tid] + A.md.tb_bn_bias[tid];
-    }
+    if (tid < 2 * NS) v48[tid] = tor_bn_element(A, row, ne, tid);
     __syncthreads();
-    if (tid < NS) {   // tor_final_layer: Linear(48,24,no bias) -> tanh -> Linear(24,1,no bias)
-      float a = 0.0f;
-      for (int j = 0; j < 2 * NS; ++j) a += A.md.tf_w0[tid * 2 * NS + j] * v48[j];
-      hid[tid] = A.md.tf_w3[tid] * tanhf(a);
-    }
+    if (tid < NS) hid[tid] = tor_hidden_unit(A, v48, tid);
     __syncthreads();
-    if (tid == 0) {
-      float o = 0.0f;
-      for (int j = 0; j < NS; ++j) o += hid[j];
-      if (A.scale_by_sigma) o *= A.sp.torus_norm_sqrt;
-      A.tor_out[blockIdx.x] = o;          // [b * R + r]
-    }
+    if (tid == 0) A.tor_out[blockIdx.x] = tor_score_sum(A, hid);          // [b * R + r]
     return;
   }
   const int b = blockIdx.x - n_tor_blocks;
-  float* row = A.h_sum + (size_t)b * XW;
-  if (tid < 12) {
-    g12[tid] = (row[tid] / (float)A.n_lig) * A.md.fc_bn_scale[tid / 3];
-    row[tid] = 0.0f;
-  }
+  if (tid < 12) g12[tid] = center_element(A, A.h_sum + (size_t)b * XW, tid);
   __syncthreads();
-  if (tid < 2) {   // tid 0: translation, tid 1: rotation  (score_model.py:274-286)
-    const int o = 3 * tid;
-    const float px = g12[o] + g12[6 + o], py = g12[o + 1] + g12[7 + o], pz = g12[o + 2] + g12[8 + o];
-    const float nrm = sqrtf(px * px + py * py + pz * pz);
-    const float* w0n = tid == 0 ? A.md.tr_w0n : A.md.rot_w0n;
-    const float* w3 = tid == 0 ? A.md.tr_w3 : A.md.rot_w3;
-    const float* sb = tid == 0 ? A.sp.tr_sigb : A.sp.rot_sigb;
-    float s = tid == 0 ? A.md.tr_b3 : A.md.rot_b3;
-    for (int k = 0; k < NS; ++k) s += w3[k] * fmaxf(w0n[k] * nrm + sb[k], 0.0f);
-    float f = s / nrm;
-    if (A.scale_by_sigma) f = tid == 0 ? f / A.sp.tr_sigma : f * A.sp.so3_norm;
-    float* out = (tid == 0 ? A.tr_out : A.rot_out) + 3 * (size_t)b;
-    out[0] = px * f; out[1] = py * f; out[2] = pz * f;
-  }
+  if (tid < 2) tr_rot_score(A, g12, tid, b);   // tid 0: translation, tid 1: rotation
 }
 
 hipError_t launch_heads_pre(const HeadArgs& A, bool torsion, hipStream_t s) {

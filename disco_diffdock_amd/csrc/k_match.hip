@@ -182,18 +182,14 @@ __device__ inline float match_eval(const MatchTables& T, float* xyz, const float
     const float th = theta[k];
     if (th != 0.0f) {      // a rotor with a zero angle is skipped, as in the reference
       const int2 uv = T.uv[k];
-      const float px = xyz[3 * uv.y], py = xyz[3 * uv.y + 1], pz = xyz[3 * uv.y + 2];
-      const float ax = xyz[3 * uv.x] - px, ay = xyz[3 * uv.x + 1] - py, az = xyz[3 * uv.x + 2] - pz;
-      const float nn = sqrtf(ax * ax + ay * ay + az * az);
-      float Rl[9];
-      axis_angle_to_matrix_dev(ax / nn * th, ay / nn * th, az / nn * th, Rl);
+      float Rl[9], piv[3];
+      bond_rotor(xyz, uv.x, uv.y, th, Rl, piv);
       // in place: u is not in the mask and v, the pivot, maps to itself exactly, so the two atoms every lane has just read keep their values
       for (int i = lane; i < n; i += 64)
         if (bit_of(T.bits[k], i)) {
-          const float x = xyz[3 * i] - px, y = xyz[3 * i + 1] - py, z = xyz[3 * i + 2] - pz;
-          xyz[3 * i] = Rl[0] * x + Rl[1] * y + Rl[2] * z + px;
-          xyz[3 * i + 1] = Rl[3] * x + Rl[4] * y + Rl[5] * z + py;
-          xyz[3 * i + 2] = Rl[6] * x + Rl[7] * y + Rl[8] * z + pz;
+          float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
+          rotate_about(Rl, piv, x, y, z);
+          xyz[3 * i] = x; xyz[3 * i + 1] = y; xyz[3 * i + 2] = z;
         }
     }
     wave_lds_sync();

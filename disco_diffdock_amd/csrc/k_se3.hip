@@ -8,8 +8,11 @@
 // evaluated on centred coordinates: rigid and flex without "+ tr + centroid", which is added to the aligned pose at the end (same map, see the kernel)
 // The 3x3 SVD of the reference is replaced by Horn's closed form (largest eigenvector of a 4x4 symmetric
 // matrix, Jacobi in fp64 on one lane): same optimal proper rotation, reflection case included.
+// One body, pose_update_body, runs from the centroid to the last store in se3_update_kernel<POST, REC> (the sampler) and in
+// modify_conformer_batch_kernel (the ragged training batch); the heads' finish of the POST block is k_head_finish.h's, the rotor step k_geom.h's.
 #include "model.h"
 #include "k_geom.h"
+#include "k_head_finish.h"
 
 namespace ddk {
 
@@ -78,18 +81,99 @@ hipError_t launch_debug_axis_angle(const float* aa, int n, float* R_out, hipStre
   return hipGetLastError();
 }
 
-// POST: the workgroup of sample b first finishes the sample's scores from the heads' accumulators - heads_post_kernel's arithmetic (k_heads.hip:
-// tor_bond_conv's mean / BatchNorm / tor_final_layer, final_conv's mean / BatchNorm and the tr / rot magnitude MLPs; same summation orders) - so that
-// a reverse step needs no launch between the head convolutions and the update (ddk_sample without classifier-free guidance)
+// The LDS of one pose update: the rigid pose, the two buffers the rotor loop alternates between, and the small per-sample quantities.
+struct PoseLds {
+  float rig[MAX_LIG * 3], flx[2][MAX_LIG * 3];
+  float upd[6], ctr[3], Rm[9], cA[3], cB[3], Rk[9], tk[3], rot_th[64];
+  int2 rot_uv[64];
+  double S[9];
+};
+
+// The pose update from the centroid to the last store, by all 256 threads of a workgroup (barriers inside).  The caller has filled L.rig with the n atoms
+// of the pose and L.upd with (tr, rot), and has passed a barrier behind those stores.  flexible = the R rotors turn; mask_rotate [R, n] says
+// which atoms.  What differs between the kernels comes in as two inlined callables: rotor(r, u, v, th) gives rotor r's bond (u, v) and angle, called
+// once per rotor by one thread; store(i, x, y, z) puts atom i of the new pose where it belongs.  se3_update_kernel<POST, REC> and
+// modify_conformer_batch_kernel are this one body, which is why a graph of the ragged batch gets the bits of the same ligand alone
+// (tests/test_gpu_noise_batch.py, tests/test_gpu_pose_bits.py).
+template <class Rotor, class Store>
+__device__ __forceinline__ void pose_update_body(PoseLds& L, int n, int R, bool flexible, const uint8_t* mask_rotate, Rotor rotor, Store store) {
+  const int tid = threadIdx.x;
+  if (tid < 64) {
+    const double s = component_sum_wave0(L.rig, n, tid);
+    if (tid < 3) L.ctr[tid] = (float)(s / (double)n);
+  }
+  if (tid == 64) axis_angle_to_matrix_dev(L.upd[3], L.upd[4], L.upd[5], L.Rm);
+  __syncthreads();
+  if (tid < n) {
+    const float x = L.rig[3 * tid] - L.ctr[0], y = L.rig[3 * tid + 1] - L.ctr[1], z = L.rig[3 * tid + 2] - L.ctr[2];
+    // CENTRED coordinates from here to the last line: tr + centroid is added once, to the final pose.  With it added here the rotor
+    // axes (differences of two atoms 1.5 A apart) and every rotated atom carry roundings of the DISTANCE FROM THE ORIGIN, and a chain of rotors amplifies
+    // them by its lever arms: 150 A out a 129-rotor chain ended up to 5e-3 A from fp64 (tests/test_geometry_bound.py), centred it is as exact as at the origin
+    const float rx = L.Rm[0] * x + L.Rm[1] * y + L.Rm[2] * z;
+    const float ry = L.Rm[3] * x + L.Rm[4] * y + L.Rm[5] * z;
+    const float rz = L.Rm[6] * x + L.Rm[7] * y + L.Rm[8] * z;
+    // every thread owns its atom: safe to overwrite in place after the barrier above
+    L.rig[3 * tid] = rx; L.rig[3 * tid + 1] = ry; L.rig[3 * tid + 2] = rz;
+    L.flx[0][3 * tid] = rx; L.flx[0][3 * tid + 1] = ry; L.flx[0][3 * tid + 2] = rz;
+  }
+  __syncthreads();
+  if (!flexible) {
+    if (tid < n) store(tid, L.rig[3 * tid] + L.upd[0] + L.ctr[0], L.rig[3 * tid + 1] + L.upd[1] + L.ctr[1], L.rig[3 * tid + 2] + L.upd[2] + L.ctr[2]);
+    return;
+  }
+  // Sequential torsion rotations, one barrier per rotor: the rotor table (u, v, angle) and every atom's mask bits are fetched for up to 64 rotors at
+  // once (one exposed memory latency per chunk instead of three per rotor), every thread builds the rotor's matrix itself from the CURRENT
+  // coordinates (same instruction sequence on every lane) and writes its atom into the other of two coordinate buffers.
+  float* cur = L.flx[0];
+  float* nxt = L.flx[1];
+  for (int r0 = 0; r0 < R; r0 += 64) {
+    const int chunk = min(64, R - r0);
+    if (tid < chunk) {
+      int u, v;
+      float th;
+      rotor(r0 + tid, u, v, th);
+      L.rot_uv[tid] = make_int2(u, v);
+      L.rot_th[tid] = th;
+    }
+    unsigned long long mbits = 0ull;
+    if (tid < n)
+      for (int k = 0; k < chunk; ++k) mbits |= (unsigned long long)(mask_rotate[(size_t)(r0 + k) * n + tid] != 0) << k;
+    __syncthreads();
+    for (int k = 0; k < chunk; ++k) {
+      if (tid < n) {
+        float x = cur[3 * tid], y = cur[3 * tid + 1], z = cur[3 * tid + 2];
+        if ((mbits >> k) & 1ull) {
+          float Rl[9], piv[3];
+          bond_rotor(cur, L.rot_uv[k].x, L.rot_uv[k].y, L.rot_th[k], Rl, piv);
+          rotate_about(Rl, piv, x, y, z);
+        }
+        nxt[3 * tid] = x; nxt[3 * tid + 1] = y; nxt[3 * tid + 2] = z;
+      }
+      __syncthreads();
+      float* t_ = cur; cur = nxt; nxt = t_;
+    }
+  }
+  kabsch_block(cur, L.rig, n, L.cA, L.cB, L.S, L.Rk, L.tk);
+  if (tid < n) {
+    const float x = cur[3 * tid], y = cur[3 * tid + 1], z = cur[3 * tid + 2];
+    // Rk (x, y, z) + tk + upd + ctr with every multiply-add WRITTEN OUT: left to the compiler's contraction, which product of a row is rounded before
+    // the others are fused onto it comes out differently in the recording and the plain instantiations (one body, two sets of bits).  These chains,
+    // rows 1 and 2 starting from their middle product, are the ones tests/golden/pose_update_bits.json pins: do not reorder them.
+    const float ox = fmaf(L.Rk[2], z, fmaf(L.Rk[1], y, L.Rk[0] * x)) + L.tk[0] + L.upd[0] + L.ctr[0];
+    const float oy = fmaf(L.Rk[5], z, fmaf(L.Rk[3], x, L.Rk[4] * y)) + L.tk[1] + L.upd[1] + L.ctr[1];
+    const float oz = fmaf(L.Rk[8], z, fmaf(L.Rk[6], x, L.Rk[7] * y)) + L.tk[2] + L.upd[2] + L.ctr[2];
+    store(tid, ox, oy, oz);
+  }
+}
+
+// POST: the workgroup of sample b first finishes the sample's scores from the heads' accumulators - heads_post_kernel's arithmetic, through the same
+// functions (k_head_finish.h), on 256 threads over chunks of 64 bonds - so that a reverse step needs no launch between the head convolutions and the
+// update (ddk_sample without classifier-free guidance)
 // REC: the workgroup also stores what it consumed and produced into the step's rows of a ddk_trajectory (Se3Args::rec_*; ddk_sample_trajectory).  A template
-// flag, not a run-time test: the <POST, false> instantiations are the kernels ddk_sample has always launched, instruction for instruction.
+// flag, not a run-time test: the <POST, false> instantiations carry no trace of it.
 template <bool POST, bool REC>
 __global__ __launch_bounds__(256) void se3_update_kernel(Se3Args A, HeadArgs H) {
-  __shared__ float rig[MAX_LIG * 3], flx_a[MAX_LIG * 3], flx2[MAX_LIG * 3];
-  __shared__ float upd[6], ctr[3], Rm[9], cA[3], cB[3], Rk[9], tk[3], rot_th[64];
-  __shared__ int2 rot_uv[64];
-  __shared__ double S[9];
-  float* flx = flx_a;
+  __shared__ PoseLds L;
   const int b = blockIdx.x, tid = threadIdx.x, n = A.n_lig, R = A.R;
   if constexpr (POST) {
     __shared__ float v48[64][2 * NS], hid[64][NS], g12[12];
@@ -100,58 +184,30 @@ __global__ __launch_bounds__(256) void se3_update_kernel(Se3Args A, HeadArgs H) 
         for (int i = tid; i < chunk * 2 * NS; i += 256) {
           const int rr = i / (2 * NS), c = i - rr * 2 * NS;
           const int bond = b * R + r0 + rr;
-          float* row = H.h_sum + (size_t)(H.B + bond) * XW;
-          const int ne = H.h_deg[bond];
-          const float sv = row[c] / (float)(ne > 1 ? ne : 1);
-          row[c] = 0.0f;
-          v48[rr][c] = (sv - H.md.tb_bn_mean[c]) * H.md.tb_bn_scale[c] + H.md.tb_bn_bias[c];
+          v48[rr][c] = tor_bn_element(H, H.h_sum + (size_t)(H.B + bond) * XW, H.h_deg[bond], c);
         }
         __syncthreads();
-        for (int i = tid; i < chunk * NS; i += 256) {      // tor_final_layer: Linear(48,24,no bias) -> tanh -> Linear(24,1,no bias)
+        for (int i = tid; i < chunk * NS; i += 256) {
           const int rr = i / NS, k = i - rr * NS;
-          float a = 0.0f;
-          for (int j = 0; j < 2 * NS; ++j) a += H.md.tf_w0[k * 2 * NS + j] * v48[rr][j];
-          hid[rr][k] = H.md.tf_w3[k] * tanhf(a);
+          hid[rr][k] = tor_hidden_unit(H, v48[rr], k);
         }
         __syncthreads();
-        if (tid < chunk) {
-          float o = 0.0f;
-          for (int j = 0; j < NS; ++j) o += hid[tid][j];
-          if (H.scale_by_sigma) o *= H.sp.torus_norm_sqrt;
-          H.tor_out[(size_t)b * R + r0 + tid] = o;
-        }
+        if (tid < chunk) H.tor_out[(size_t)b * R + r0 + tid] = tor_score_sum(H, hid[tid]);
         __syncthreads();
       }
     }
-    float* row = H.h_sum + (size_t)b * XW;
-    if (tid < 12) {
-      g12[tid] = (row[tid] / (float)H.n_lig) * H.md.fc_bn_scale[tid / 3];
-      row[tid] = 0.0f;
-    }
+    if (tid < 12) g12[tid] = center_element(H, H.h_sum + (size_t)b * XW, tid);
     __syncthreads();
-    if (tid < 2) {   // tid 0: translation, tid 1: rotation  (score_model.py:274-286)
-      const int o = 3 * tid;
-      const float px = g12[o] + g12[6 + o], py = g12[o + 1] + g12[7 + o], pz = g12[o + 2] + g12[8 + o];
-      const float nrm = sqrtf(px * px + py * py + pz * pz);
-      const float* w0n = tid == 0 ? H.md.tr_w0n : H.md.rot_w0n;
-      const float* w3 = tid == 0 ? H.md.tr_w3 : H.md.rot_w3;
-      const float* sb = tid == 0 ? H.sp.tr_sigb : H.sp.rot_sigb;
-      float sv = tid == 0 ? H.md.tr_b3 : H.md.rot_b3;
-      for (int k = 0; k < NS; ++k) sv += w3[k] * fmaxf(w0n[k] * nrm + sb[k], 0.0f);
-      float f = sv / nrm;
-      if (H.scale_by_sigma) f = tid == 0 ? f / H.sp.tr_sigma : f * H.sp.so3_norm;
-      float* out = (tid == 0 ? H.tr_out : H.rot_out) + 3 * (size_t)b;
-      out[0] = px * f; out[1] = py * f; out[2] = pz * f;
-    }
+    if (tid < 2) tr_rot_score(H, g12, tid, b);   // tid 0: translation, tid 1: rotation
     __syncthreads();      // the scores written above are read back through A.tr / A.rot / A.tor below (same workgroup)
   }
   const float* nz = A.noise ? A.noise + (size_t)b * (6 + R) : nullptr;
-  for (int i = tid; i < n * 3; i += 256) rig[i] = A.pos[(size_t)b * n * 3 + i];
+  for (int i = tid; i < n * 3; i += 256) L.rig[i] = A.pos[(size_t)b * n * 3 + i];
   if (tid < 6) {
     const int k = tid / 3;
     const float sc = (tid < 3 ? A.tr : A.rot)[3 * b + tid % 3];
     const float u = A.sc[k] * sc + (nz ? A.nc[k] * nz[tid] : 0.0f);
-    upd[tid] = u;
+    L.upd[tid] = u;
     if constexpr (REC) {
       if (A.rec_scores != nullptr) A.rec_scores[(size_t)b * (6 + R) + tid] = sc;
       if (A.rec_perturb != nullptr) A.rec_perturb[(size_t)b * (6 + R) + tid] = u;
@@ -161,110 +217,43 @@ __global__ __launch_bounds__(256) void se3_update_kernel(Se3Args A, HeadArgs H) 
     if (A.rec_edges != nullptr && b == 0 && tid < 4) A.rec_edges[tid] = A.info[I_GO + 1 + tid] - A.info[I_GO + tid];
   }
   __syncthreads();
-  if (tid < 64) {
-    const double s = component_sum_wave0(rig, n, tid);
-    if (tid < 3) ctr[tid] = (float)(s / (double)n);
-  }
-  if (tid == 64) axis_angle_to_matrix_dev(upd[3], upd[4], upd[5], Rm);
-  __syncthreads();
-  if (tid < n) {
-    const float x = rig[3 * tid] - ctr[0], y = rig[3 * tid + 1] - ctr[1], z = rig[3 * tid + 2] - ctr[2];
-    // CENTRED coordinates from here to the last line of the kernel: tr + centroid is added once, to the final pose.  With it added here the rotor
-    // axes (differences of two atoms 1.5 A apart) and every rotated atom carry roundings of the DISTANCE FROM THE ORIGIN, and a chain of rotors amplifies
-    // them by its lever arms: 150 A out a 129-rotor chain ended up to 5e-3 A from fp64 (tests/test_geometry_bound.py), centred it is as exact as at the origin
-    const float rx = Rm[0] * x + Rm[1] * y + Rm[2] * z;
-    const float ry = Rm[3] * x + Rm[4] * y + Rm[5] * z;
-    const float rz = Rm[6] * x + Rm[7] * y + Rm[8] * z;
-    // every thread owns its atom: safe to overwrite in place after the barrier above
-    rig[3 * tid] = rx; rig[3 * tid + 1] = ry; rig[3 * tid + 2] = rz;
-    flx[3 * tid] = rx; flx[3 * tid + 1] = ry; flx[3 * tid + 2] = rz;
-  }
-  __syncthreads();
-  if (A.tor == nullptr || R == 0) {
-    for (int i = tid; i < n * 3; i += 256) {
-      const float v = rig[i] + upd[i % 3] + ctr[i % 3];
-      A.pos_out[(size_t)b * n * 3 + i] = v;
-      if constexpr (REC) if (A.rec_pos != nullptr) A.rec_pos[(size_t)b * n * 3 + i] = v;
-    }
-    if constexpr (REC)      // no_torsion: the torsion columns of the record's rows are zero
+  const bool flexible = A.tor != nullptr && R > 0;
+  pose_update_body(
+      L, n, R, flexible, A.mask_rotate,
+      [&](int r, int& u, int& v, float& th) {
+        u = A.rot_u[r]; v = A.rot_v[r];
+        const float ts = A.tor[(size_t)b * R + r];
+        th = A.sc[2] * ts + (nz ? A.nc[2] * nz[6 + r] : 0.0f);
+        if constexpr (REC) {
+          if (A.rec_scores != nullptr) A.rec_scores[(size_t)b * (6 + R) + 6 + r] = ts;
+          if (A.rec_perturb != nullptr) A.rec_perturb[(size_t)b * (6 + R) + 6 + r] = th;
+        }
+      },
+      [&](int i, float x, float y, float z) {
+        float* o = A.pos_out + ((size_t)b * n + i) * 3;
+        o[0] = x; o[1] = y; o[2] = z;
+        if constexpr (REC)
+          if (A.rec_pos != nullptr) {
+            float* q = A.rec_pos + ((size_t)b * n + i) * 3;
+            q[0] = x; q[1] = y; q[2] = z;
+          }
+      });
+  if constexpr (REC)      // no_torsion: the torsion columns of the record's rows are zero
+    if (!flexible)
       for (int r = tid; r < R; r += 256) {
         if (A.rec_scores != nullptr) A.rec_scores[(size_t)b * (6 + R) + 6 + r] = 0.0f;
         if (A.rec_perturb != nullptr) A.rec_perturb[(size_t)b * (6 + R) + 6 + r] = 0.0f;
       }
-    return;
-  }
-  // Sequential torsion rotations, one barrier per rotor: the rotor table (u, v, angle) and every atom's mask bits are fetched for up to 64 rotors at
-  // once (one exposed memory latency per chunk instead of three per rotor), every thread builds the rotor's matrix itself from the CURRENT
-  // coordinates (same instruction sequence on every lane) and writes its atom into the other of two coordinate buffers.
-  float* cur = flx;
-  float* nxt = flx2;
-  for (int r0 = 0; r0 < R; r0 += 64) {
-    const int chunk = min(64, R - r0);
-    if (tid < chunk) {
-      const int r = r0 + tid;
-      rot_uv[tid] = make_int2(A.rot_u[r], A.rot_v[r]);
-      const float ts = A.tor[(size_t)b * R + r];
-      const float th = A.sc[2] * ts + (nz ? A.nc[2] * nz[6 + r] : 0.0f);
-      rot_th[tid] = th;
-      if constexpr (REC) {
-        if (A.rec_scores != nullptr) A.rec_scores[(size_t)b * (6 + R) + 6 + r] = ts;
-        if (A.rec_perturb != nullptr) A.rec_perturb[(size_t)b * (6 + R) + 6 + r] = th;
-      }
-    }
-    unsigned long long mbits = 0ull;
-    if (tid < n)
-      for (int k = 0; k < chunk; ++k) mbits |= (unsigned long long)(A.mask_rotate[(size_t)(r0 + k) * n + tid] != 0) << k;
-    __syncthreads();
-    for (int k = 0; k < chunk; ++k) {
-      if (tid < n) {
-        const int2 uv = rot_uv[k];
-        const float th = rot_th[k];
-        const float px = cur[3 * uv.y], py = cur[3 * uv.y + 1], pz = cur[3 * uv.y + 2];
-        float x = cur[3 * tid], y = cur[3 * tid + 1], z = cur[3 * tid + 2];
-        if ((mbits >> k) & 1ull) {
-          const float ax = cur[3 * uv.x] - px, ay = cur[3 * uv.x + 1] - py, az = cur[3 * uv.x + 2] - pz;
-          const float nn = sqrtf(ax * ax + ay * ay + az * az);
-          float Rl[9];
-          axis_angle_to_matrix_dev(ax / nn * th, ay / nn * th, az / nn * th, Rl);
-          x -= px; y -= py; z -= pz;
-          const float nx = Rl[0] * x + Rl[1] * y + Rl[2] * z + px, ny = Rl[3] * x + Rl[4] * y + Rl[5] * z + py, nz_ = Rl[6] * x + Rl[7] * y + Rl[8] * z + pz;
-          x = nx; y = ny; z = nz_;
-        }
-        nxt[3 * tid] = x; nxt[3 * tid + 1] = y; nxt[3 * tid + 2] = z;
-      }
-      __syncthreads();
-      float* t_ = cur; cur = nxt; nxt = t_;
-    }
-  }
-  flx = cur;
-  kabsch_block(flx, rig, n, cA, cB, S, Rk, tk);
-  if (tid < n) {
-    const float x = flx[3 * tid], y = flx[3 * tid + 1], z = flx[3 * tid + 2];
-    float* o = A.pos_out + ((size_t)b * n + tid) * 3;
-    const float ox = Rk[0] * x + Rk[1] * y + Rk[2] * z + tk[0] + upd[0] + ctr[0];
-    const float oy = Rk[3] * x + Rk[4] * y + Rk[5] * z + tk[1] + upd[1] + ctr[1];
-    const float oz = Rk[6] * x + Rk[7] * y + Rk[8] * z + tk[2] + upd[2] + ctr[2];
-    o[0] = ox; o[1] = oy; o[2] = oz;
-    if constexpr (REC)
-      if (A.rec_pos != nullptr) {
-        float* q = A.rec_pos + ((size_t)b * n + tid) * 3;
-        q[0] = ox; q[1] = oy; q[2] = oz;
-      }
-  }
 }
 
 // modify_conformer (utils/diffusion_utils.py) for a RAGGED batch, one workgroup per graph (include/ddk.h: ddk_modify_conformer_batch): graph g has its own
-// atom count, rotor table and mask block, found through node_ptr / tor_ptr / mask_ptr.  From the load of the coordinates on this is se3_update_kernel<false,
-// false> with B = 1, score_coeff = 1 and no noise, expression for expression (the update of component k is `score + 0.0f`, what 1 * score + 0 rounds to), so a
-// graph gets the bits ddk_se3_update gives the same ligand alone; that kernel is not touched.  Before any table entry becomes an address the workgroup
+// atom count, rotor table and mask block, found through node_ptr / tor_ptr / mask_ptr.  From the centroid on this is pose_update_body, as in
+// se3_update_kernel<false, false> with B = 1, score_coeff = 1 and no noise; the update of component k is `score + 0.0f`, what 1 * score + 0 rounds to.  So a
+// graph gets the bits ddk_se3_update gives the same ligand alone.  Before any table entry becomes an address the workgroup
 // checks it; status_out[g]: 0 done; 2 a bond index outside [0, n_g) or u == v; 3 a coordinate that is not finite; 4 a node_ptr / tor_ptr / mask_ptr entry
 // that is no range of the arrays or breaks a limit.  With a status other than 0 the graph's rows of pos_out are not written.
 __global__ __launch_bounds__(256) void modify_conformer_batch_kernel(ConformerBatchArgs A) {
-  __shared__ float rig[MAX_LIG * 3], flx_a[MAX_LIG * 3], flx2[MAX_LIG * 3];
-  __shared__ float upd[6], ctr[3], Rm[9], cA[3], cB[3], Rk[9], tk[3], rot_th[64];
-  __shared__ int2 rot_uv[64];
-  __shared__ double S[9];
-  float* flx = flx_a;
+  __shared__ PoseLds L;
   const int g = blockIdx.x, tid = threadIdx.x;
   const int n0 = A.node_ptr[g], n = A.node_ptr[g + 1] - n0;
   bool tables_ok = n0 >= 0 && n >= 1 && n <= MAX_LIG && n0 <= A.N - n;
@@ -281,19 +270,18 @@ __global__ __launch_bounds__(256) void modify_conformer_batch_kernel(ConformerBa
   const float* pos = A.pos + (size_t)n0 * 3;
   float* pos_out = A.pos_out + (size_t)n0 * 3;
   const int32_t* bonds = A.rot_bonds + (size_t)t0 * 2;
-  const uint8_t* mask_rotate = A.mask_rotate + m0;
   const float* tor = A.tor != nullptr ? A.tor + t0 : nullptr;
   int bad_pos = 0, bad_bond = 0;
   for (int i = tid; i < n * 3; i += 256) {
     const float v = pos[i];
-    rig[i] = v;
+    L.rig[i] = v;
     bad_pos |= !isfinite(v);
   }
   for (int r = tid; r < R; r += 256) {
     const int u = bonds[2 * r], v = bonds[2 * r + 1];
     bad_bond |= u < 0 || u >= n || v < 0 || v >= n || u == v;
   }
-  if (tid < 6) upd[tid] = (tid < 3 ? A.tr : A.rot)[3 * g + tid % 3] + 0.0f;
+  if (tid < 6) L.upd[tid] = (tid < 3 ? A.tr : A.rot)[3 * g + tid % 3] + 0.0f;
   bad_pos = __syncthreads_or(bad_pos);
   bad_bond = __syncthreads_or(bad_bond);
   if (bad_pos || bad_bond) {
@@ -301,68 +289,10 @@ __global__ __launch_bounds__(256) void modify_conformer_batch_kernel(ConformerBa
     return;
   }
   if (tid == 0) A.status_out[g] = 0;
-  if (tid < 64) {
-    const double s = component_sum_wave0(rig, n, tid);
-    if (tid < 3) ctr[tid] = (float)(s / (double)n);
-  }
-  if (tid == 64) axis_angle_to_matrix_dev(upd[3], upd[4], upd[5], Rm);
-  __syncthreads();
-  if (tid < n) {      // centred coordinates from here to the last line (se3_update_kernel says why)
-    const float x = rig[3 * tid] - ctr[0], y = rig[3 * tid + 1] - ctr[1], z = rig[3 * tid + 2] - ctr[2];
-    const float rx = Rm[0] * x + Rm[1] * y + Rm[2] * z;
-    const float ry = Rm[3] * x + Rm[4] * y + Rm[5] * z;
-    const float rz = Rm[6] * x + Rm[7] * y + Rm[8] * z;
-    rig[3 * tid] = rx; rig[3 * tid + 1] = ry; rig[3 * tid + 2] = rz;
-    flx[3 * tid] = rx; flx[3 * tid + 1] = ry; flx[3 * tid + 2] = rz;
-  }
-  __syncthreads();
-  if (tor == nullptr || R == 0) {
-    for (int i = tid; i < n * 3; i += 256) pos_out[i] = rig[i] + upd[i % 3] + ctr[i % 3];
-    return;
-  }
-  float* cur = flx;
-  float* nxt = flx2;
-  for (int r0 = 0; r0 < R; r0 += 64) {
-    const int chunk = min(64, R - r0);
-    if (tid < chunk) {
-      const int r = r0 + tid;
-      rot_uv[tid] = make_int2(bonds[2 * r], bonds[2 * r + 1]);
-      rot_th[tid] = tor[r] + 0.0f;
-    }
-    unsigned long long mbits = 0ull;
-    if (tid < n)
-      for (int k = 0; k < chunk; ++k) mbits |= (unsigned long long)(mask_rotate[(size_t)(r0 + k) * n + tid] != 0) << k;
-    __syncthreads();
-    for (int k = 0; k < chunk; ++k) {
-      if (tid < n) {
-        const int2 uv = rot_uv[k];
-        const float th = rot_th[k];
-        const float px = cur[3 * uv.y], py = cur[3 * uv.y + 1], pz = cur[3 * uv.y + 2];
-        float x = cur[3 * tid], y = cur[3 * tid + 1], z = cur[3 * tid + 2];
-        if ((mbits >> k) & 1ull) {
-          const float ax = cur[3 * uv.x] - px, ay = cur[3 * uv.x + 1] - py, az = cur[3 * uv.x + 2] - pz;
-          const float nn = sqrtf(ax * ax + ay * ay + az * az);
-          float Rl[9];
-          axis_angle_to_matrix_dev(ax / nn * th, ay / nn * th, az / nn * th, Rl);
-          x -= px; y -= py; z -= pz;
-          const float nx = Rl[0] * x + Rl[1] * y + Rl[2] * z + px, ny = Rl[3] * x + Rl[4] * y + Rl[5] * z + py, nz_ = Rl[6] * x + Rl[7] * y + Rl[8] * z + pz;
-          x = nx; y = ny; z = nz_;
-        }
-        nxt[3 * tid] = x; nxt[3 * tid + 1] = y; nxt[3 * tid + 2] = z;
-      }
-      __syncthreads();
-      float* t_ = cur; cur = nxt; nxt = t_;
-    }
-  }
-  flx = cur;
-  kabsch_block(flx, rig, n, cA, cB, S, Rk, tk);
-  if (tid < n) {
-    const float x = flx[3 * tid], y = flx[3 * tid + 1], z = flx[3 * tid + 2];
-    float* o = pos_out + (size_t)tid * 3;
-    o[0] = Rk[0] * x + Rk[1] * y + Rk[2] * z + tk[0] + upd[0] + ctr[0];
-    o[1] = Rk[3] * x + Rk[4] * y + Rk[5] * z + tk[1] + upd[1] + ctr[1];
-    o[2] = Rk[6] * x + Rk[7] * y + Rk[8] * z + tk[2] + upd[2] + ctr[2];
-  }
+  pose_update_body(
+      L, n, R, tor != nullptr && R > 0, A.mask_rotate + m0,
+      [&](int r, int& u, int& v, float& th) { u = bonds[2 * r]; v = bonds[2 * r + 1]; th = tor[r] + 0.0f; },
+      [&](int i, float x, float y, float z) { pos_out[3 * i] = x; pos_out[3 * i + 1] = y; pos_out[3 * i + 2] = z; });
 }
 
 hipError_t launch_modify_conformer_batch(const ConformerBatchArgs& A, hipStream_t s) {
@@ -382,21 +312,16 @@ __global__ __launch_bounds__(256) void randomize_kernel(RandPosArgs A) {
   __syncthreads();
   if (A.tor != nullptr) {
     for (int r = 0; r < R; ++r) {
-      if (tid == 0) {
+      if (tid == 0) {      // thread 0 builds the rotor, all apply it
         const float th = A.tor[(size_t)b * R + r];
         skip = th == 0.0f;
-        const int u = A.rot_u[r], v = A.rot_v[r];
-        const float ax = p[3 * u] - p[3 * v], ay = p[3 * u + 1] - p[3 * v + 1], az = p[3 * u + 2] - p[3 * v + 2];
-        const float nn = sqrtf(ax * ax + ay * ay + az * az);
-        axis_angle_to_matrix_dev(ax / nn * th, ay / nn * th, az / nn * th, Rt);
-        piv[0] = p[3 * v]; piv[1] = p[3 * v + 1]; piv[2] = p[3 * v + 2];
+        bond_rotor(p, A.rot_u[r], A.rot_v[r], th, Rt, piv);
       }
       __syncthreads();
       if (!skip && tid < n && A.mask_rotate[(size_t)r * n + tid]) {
-        const float x = p[3 * tid] - piv[0], y = p[3 * tid + 1] - piv[1], z = p[3 * tid + 2] - piv[2];
-        p[3 * tid] = Rt[0] * x + Rt[1] * y + Rt[2] * z + piv[0];
-        p[3 * tid + 1] = Rt[3] * x + Rt[4] * y + Rt[5] * z + piv[1];
-        p[3 * tid + 2] = Rt[6] * x + Rt[7] * y + Rt[8] * z + piv[2];
+        float x = p[3 * tid], y = p[3 * tid + 1], z = p[3 * tid + 2];
+        rotate_about(Rt, piv, x, y, z);
+        p[3 * tid] = x; p[3 * tid + 1] = y; p[3 * tid + 2] = z;
       }
       __syncthreads();
     }
