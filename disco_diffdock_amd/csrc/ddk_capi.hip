@@ -4,6 +4,7 @@
 #include <string.h>
 
 #include "model.h"
+#include "k_philox.h"
 #include "k_tp_shape.h"
 
 using namespace ddk;
@@ -532,6 +533,123 @@ int ddk_eemb_backward(ddk_ctx* ctx, const float* pos_a, int64_t n_a, const float
 }
 
 int64_t ddk_eemb_workspace(int64_t E, int32_t K) { return eemb_workspace(E, K); }
+
+// what the two latent entries check on top of eemb_check
+static int eemb_latent_check(ddk_ctx* ctx, const char* who, const EembLatent& l, int64_t E) {
+  const std::string w(who);
+  if (l.NL < 1 || l.NL > 4) return fail(ctx, DDK_ERR_INVALID, w + ": L (the latent columns per node) must be in 1..4");
+  if (E == 0) return DDK_OK;
+  if (!l.zero_latent && (!l.lat_a || !l.lat_b)) return fail(ctx, DDK_ERR_INVALID, w + ": null latent table (lat_a, lat_b; they may be null only with zero_latent)");
+  if (!l.zero_latent && (((uintptr_t)l.lat_a | (uintptr_t)l.lat_b) & 15)) return fail(ctx, DDK_ERR_INVALID, w + ": lat_a and lat_b must be 16-byte aligned");
+  if (l.unc_a && !l.uemb) return fail(ctx, DDK_ERR_INVALID, w + ": unc_a without uemb");
+  return DDK_OK;
+}
+
+int ddk_eemb_latent_forward(ddk_ctx* ctx, const float* pos_a, int64_t n_a, const float* pos_b, int64_t n_b, const int32_t* idx_a, const int32_t* idx_b,
+                            const float* feat, int32_t F, const float* sig, int64_t n_sig, const int32_t* sig_index, float start, float stop, int32_t n_gauss,
+                            const float* w1, const float* b1, const float* w2, const float* b2, float p, uint64_t seed, const float* lat_a, const float* lat_b,
+                            int32_t L, int32_t zero_latent, const float* unc_a, const float* uemb, int64_t E, float* emb, float* sh, void* stream) {
+  const EembOperands o{pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, b2, p, seed, F};
+  const EembLatent l{lat_a, lat_b, unc_a, uemb, L, zero_latent != 0};
+  int rc = eemb_check(ctx, "ddk_eemb_latent_forward", o, n_a, n_b, F, n_sig, n_gauss, E);
+  if (!rc) rc = eemb_latent_check(ctx, "ddk_eemb_latent_forward", l, E);
+  if (rc) return rc;
+  if (E == 0) return DDK_OK;
+  if (!b2 || !emb || !sh) return fail(ctx, DDK_ERR_INVALID, "ddk_eemb_latent_forward: null operand (b2, emb, sh)");
+  if (((uintptr_t)emb | (uintptr_t)sh) & 15) return fail(ctx, DDK_ERR_INVALID, "ddk_eemb_latent_forward: emb and sh must be 16-byte aligned");
+  hipError_t e = launch_eemb_latent_forward(o, l, E, emb, sh, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "eemb_latent_forward launch");
+  return DDK_OK;
+}
+
+int ddk_eemb_latent_backward(ddk_ctx* ctx, const float* pos_a, int64_t n_a, const float* pos_b, int64_t n_b, const int32_t* idx_a, const int32_t* idx_b,
+                             const float* feat, int32_t F, const float* sig, int64_t n_sig, const int32_t* sig_index, float start, float stop, int32_t n_gauss,
+                             const float* w1, const float* b1, const float* w2, const float* b2, float p, uint64_t seed, const float* lat_a, const float* lat_b,
+                             int32_t L, int32_t zero_latent, const float* unc_a, const float* uemb, const int32_t* order_a, const int64_t* ptr_a,
+                             const int32_t* order_b, const int64_t* ptr_b, const float* grad_emb, int64_t E, float* grad_w1, float* grad_b1, float* grad_w2,
+                             float* grad_b2, float* grad_uemb, float* grad_lat_a, float* grad_lat_b, void* workspace, void* stream) {
+  const EembOperands o{pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, b2, p, seed, F};
+  const EembLatent l{lat_a, lat_b, unc_a, uemb, L, zero_latent != 0};
+  int rc = eemb_check(ctx, "ddk_eemb_latent_backward", o, n_a, n_b, F, n_sig, n_gauss, E);
+  if (!rc) rc = eemb_latent_check(ctx, "ddk_eemb_latent_backward", l, E);
+  if (rc) return rc;
+  if (!grad_w1 && !grad_b1 && !grad_w2 && !grad_b2 && !grad_uemb && !grad_lat_a && !grad_lat_b)
+    return fail(ctx, DDK_ERR_INVALID, "ddk_eemb_latent_backward: no gradient requested (all seven outputs are null)");
+  if (E > 0) {
+    if (!grad_emb) return fail(ctx, DDK_ERR_INVALID, "ddk_eemb_latent_backward: null grad_emb");
+    if (!workspace) return fail(ctx, DDK_ERR_INVALID, "ddk_eemb_latent_backward: null workspace (ddk_eemb_latent_workspace bytes)");
+    if (((uintptr_t)grad_emb | (uintptr_t)workspace) & 15)
+      return fail(ctx, DDK_ERR_INVALID, "ddk_eemb_latent_backward: grad_emb and the workspace must be 16-byte aligned");
+    if (!zero_latent && ((grad_lat_a && (!order_a || !ptr_a)) || (grad_lat_b && (!order_b || !ptr_b))))
+      return fail(ctx, DDK_ERR_INVALID, "ddk_eemb_latent_backward: null node-sorted edge list (grad_lat_a needs order_a and ptr_a, grad_lat_b order_b and ptr_b)");
+  }
+  const EembLatentGraph gr{n_a, n_b, order_a, ptr_a, order_b, ptr_b};
+  hipError_t e = launch_eemb_latent_backward(o, l, gr, grad_emb, E, grad_w1, grad_b1, grad_w2, grad_b2, grad_uemb, grad_lat_a, grad_lat_b, (float*)workspace,
+                                             (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "eemb_latent_backward launch");
+  return DDK_OK;
+}
+
+int64_t ddk_eemb_latent_workspace(int64_t E, int32_t K, int32_t L) { return eemb_latent_workspace(E, K, L); }
+
+// the checks the two Gumbel-softmax entries share
+static int gumbel_check(ddk_ctx* ctx, const char* who, int32_t G, int32_t D, int64_t n_lig, int64_t n_rec, const int64_t* lig_ptr, const int64_t* rec_ptr, float T) {
+  int rc = check_launchable(ctx, 0);
+  if (rc) return rc;
+  const std::string w(who);
+  if (G < 1 || G > 65536) return fail(ctx, DDK_ERR_INVALID, w + ": G must be in [1, 65536]");
+  if (D < 1 || D > 4) return fail(ctx, DDK_ERR_INVALID, w + ": D must be in 1..4");
+  if (n_lig < 0 || n_rec < 0 || n_lig >= (int64_t)1 << 31 || n_rec >= (int64_t)1 << 31) return fail(ctx, DDK_ERR_INVALID, w + ": node count out of range");
+  if (!(T > 0.f) || !(T < INFINITY)) return fail(ctx, DDK_ERR_INVALID, w + ": the temperature must be positive and finite");
+  if (!lig_ptr || !rec_ptr) return fail(ctx, DDK_ERR_INVALID, w + ": null lig_ptr or rec_ptr");
+  return DDK_OK;
+}
+
+int ddk_gumbel_softmax_batch(ddk_ctx* ctx, int32_t G, int32_t D, const float* logit_l, int64_t n_lig, const float* logit_r, int64_t n_rec,
+                             const int64_t* lig_ptr, const int64_t* rec_ptr, float T, uint64_t seed, const uint64_t* stream_id, int32_t sample, int32_t draw,
+                             float* y_l, float* y_r, float* out_l, float* out_r, void* stream) {
+  int rc = gumbel_check(ctx, "ddk_gumbel_softmax_batch", G, D, n_lig, n_rec, lig_ptr, rec_ptr, T);
+  if (rc) return rc;
+  if (sample < 0) return fail(ctx, DDK_ERR_INVALID, "ddk_gumbel_softmax_batch: sample must be >= 0");
+  if (draw < 0 || draw >= (1 << 20)) return fail(ctx, DDK_ERR_INVALID, "ddk_gumbel_softmax_batch: draw must be in [0, 2^20)");
+  if (!stream_id) return fail(ctx, DDK_ERR_INVALID, "ddk_gumbel_softmax_batch: null stream_id");
+  if ((n_lig > 0 && (!logit_l || !y_l || !out_l)) || (n_rec > 0 && (!logit_r || !y_r || !out_r)))
+    return fail(ctx, DDK_ERR_INVALID, "ddk_gumbel_softmax_batch: null operand (logit, y, out of a side that has nodes)");
+  if (n_lig + n_rec == 0) return DDK_OK;
+  const GumbelOperands o{lig_ptr, rec_ptr, n_lig, n_rec, G, D, T};
+  hipError_t e = launch_gumbel_forward(o, logit_l, logit_r, seed, stream_id, (uint32_t)sample, (uint32_t)draw, y_l, y_r, out_l, out_r, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "gumbel_softmax_batch launch");
+  return DDK_OK;
+}
+
+int ddk_gumbel_softmax_batch_backward(ddk_ctx* ctx, int32_t G, int32_t D, const float* y_l, int64_t n_lig, const float* y_r, int64_t n_rec,
+                                      const int64_t* lig_ptr, const int64_t* rec_ptr, float T, const float* grad_out_l, const float* grad_out_r,
+                                      float* grad_logit_l, float* grad_logit_r, void* stream) {
+  int rc = gumbel_check(ctx, "ddk_gumbel_softmax_batch_backward", G, D, n_lig, n_rec, lig_ptr, rec_ptr, T);
+  if (rc) return rc;
+  if ((n_lig > 0 && (!y_l || !grad_out_l || !grad_logit_l)) || (n_rec > 0 && (!y_r || !grad_out_r || !grad_logit_r)))
+    return fail(ctx, DDK_ERR_INVALID, "ddk_gumbel_softmax_batch_backward: null operand (y, grad_out, grad_logit of a side that has nodes)");
+  if (n_lig + n_rec == 0) return DDK_OK;
+  const GumbelOperands o{lig_ptr, rec_ptr, n_lig, n_rec, G, D, T};
+  hipError_t e = launch_gumbel_backward(o, y_l, y_r, grad_out_l, grad_out_r, grad_logit_l, grad_logit_r, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "gumbel_softmax_batch_backward launch");
+  return DDK_OK;
+}
+
+int ddk_rng_latent_keep(ddk_ctx* ctx, uint64_t seed, int32_t n, const uint64_t* stream_id, int32_t sample, int32_t draw, float rate, float* keep_out) {
+  if (!ctx) return DDK_ERR_INVALID;
+  if (n < 0) return fail(ctx, DDK_ERR_INVALID, "ddk_rng_latent_keep: n must be >= 0");
+  if (sample < 0) return fail(ctx, DDK_ERR_INVALID, "ddk_rng_latent_keep: sample must be >= 0");
+  if (draw < 0 || draw >= RNG_MAX_STEPS) return fail(ctx, DDK_ERR_INVALID, "ddk_rng_latent_keep: draw must be in [0, " + std::to_string(RNG_MAX_STEPS) + ")");
+  if (!(rate >= 0.f && rate <= 1.f)) return fail(ctx, DDK_ERR_INVALID, "ddk_rng_latent_keep: rate must be in [0, 1]");
+  if (n > 0 && (!stream_id || !keep_out)) return fail(ctx, DDK_ERR_INVALID, "ddk_rng_latent_keep: null argument");
+  for (int32_t i = 0; i < n; ++i) {
+    uint32_t w[4];
+    rng_block(rng_stream(seed, stream_id[i]), (uint32_t)sample, 12u /* latent keep: DDK_RNG_LAYOUT 1 */, (uint32_t)draw, 0, w);
+    keep_out[i] = rng_uniform(w[0]) >= rate ? 1.f : 0.f;
+  }
+  return DDK_OK;
+}
 
 int ddk_seg_sum(ddk_ctx* ctx, const float* rows, const int32_t* order, const int64_t* ptr, float* nodes, int64_t n_nodes, int32_t D, void* stream) {
   int rc = check_launchable(ctx, 0);

@@ -438,4 +438,20 @@ hipError_t launch_eemb_forward(const EembOperands& o, int64_t E, float* emb, flo
 hipError_t launch_eemb_backward(const EembOperands& o, const float* grad_emb, int64_t E, float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2,
                                 float* workspace, hipStream_t s);
 int64_t eemb_workspace(int64_t E, int32_t K);
+// the latent variant (include/ddk.h: ddk_eemb_latent_*): node tables lat_a [n_a, NL] / lat_b [n_b, NL] (not read with zero_latent), unc_a [n_a] and uemb [24]
+// (unc_a null: no unconditional term); the node-sorted lists of idx_a and idx_b that the latent's gradient is summed along (trusted, read only for grad_lat_*)
+struct EembLatent { const float* lat_a; const float* lat_b; const float* unc_a; const float* uemb; int NL, zero_latent; };
+struct EembLatentGraph { int64_t n_a, n_b; const int32_t* order_a; const int64_t* ptr_a; const int32_t* order_b; const int64_t* ptr_b; };
+hipError_t launch_eemb_latent_forward(const EembOperands& o, const EembLatent& l, int64_t E, float* emb, float* sh, hipStream_t s);
+hipError_t launch_eemb_latent_backward(const EembOperands& o, const EembLatent& l, const EembLatentGraph& gr, const float* grad_emb, int64_t E, float* grad_w1,
+                                       float* grad_b1, float* grad_w2, float* grad_b2, float* grad_uemb, float* grad_lat_a, float* grad_lat_b,
+                                       float* workspace, hipStream_t s);
+int64_t eemb_latent_workspace(int64_t E, int32_t K, int32_t NL);
+// k_gumbel.hip: the ragged straight-through Gumbel softmax over a graph's ligand and receptor nodes and its vector-Jacobian product (include/ddk.h:
+// ddk_gumbel_softmax_batch / ddk_gumbel_softmax_batch_backward).  lig_ptr / rec_ptr [G + 1]: device tables, range-checked per graph in the kernels
+struct GumbelOperands { const int64_t* lig_ptr; const int64_t* rec_ptr; int64_t n_lig, n_rec; int G, D; float T; };
+hipError_t launch_gumbel_forward(const GumbelOperands& o, const float* logit_l, const float* logit_r, uint64_t seed, const uint64_t* stream_id, uint32_t sample,
+                                 uint32_t draw, float* y_l, float* y_r, float* out_l, float* out_r, hipStream_t s);
+hipError_t launch_gumbel_backward(const GumbelOperands& o, const float* y_l, const float* y_r, const float* gout_l, const float* gout_r, float* grad_l,
+                                  float* grad_r, hipStream_t s);
 }  // namespace ddk

@@ -26,6 +26,16 @@
 // it holds in registers: grad_w1 [24][K] with grad_b1 as column K, grad_w2 [24][24] with grad_b2 as column 24.  Plain stores of the image; the second
 // kernel adds the images in slice order.  No atomics; the images are the whole workspace, and everything is computed whichever outputs are asked for, so
 // the bits do not depend on the subset, the run or the device.  A row of the LDS tiles has an odd stride: the lanes of an access hit different banks.
+//
+// THE LATENT VARIANT (DisCo: latent_dim = NL in 1..4; include/ddk.h, ddk_eemb_latent_*) is a compile-time flag of both kernels, as RtpIdx<S> is of the rtp
+// kernels: the plain instantiations take EembArgs and are the code they were.  The row gains 2 NL columns behind the smearing, [lat_a[idx_a[e]] | lat_b[idx_b[e]]]
+// (zeros with zero_latent: the cross group), the chain of pre runs on over them, and emb[e, o] = fmaf(unc_a[idx_a[e]], uemb[o], emb[e, o]) closes the forward
+// where unc_a is given.  The latent carries a gradient, so the parameter pass has three more things to do per step of 64 edges: the latent columns ride in the
+// row tile (grad_w1 is [24][K] with K up to 76, the tile's stride 77), grad_uemb is one more image column (the threads of grad_b2's row group, edges ascending),
+// and glat[e, j] = fmaf(gpre[e, 23], W1[23, K0 + j], ... fmaf(gpre[e, 0], W1[0, K0 + j], 0)), K0 = F + 64, leaves as two planes [E, NL] of the workspace
+// (idx_a's columns, idx_b's columns) that launch_seg_sum adds per node in ascending edge id from the caller's node-sorted lists.  No atomics.
+#include <type_traits>
+
 #include "ddk_internal.h"
 #include "k_philox.h"
 
@@ -35,9 +45,11 @@ constexpr int EE_H = 24;             // hidden and output width (ns)
 constexpr int EE_S = 32;             // sigma embedding columns
 constexpr int EE_D = 32;             // Gaussians of the distance expansion
 constexpr int EE_KMAX = 4 + EE_S + EE_D;
+constexpr int EE_NLMAX = 4;          // latent columns per side (latent variant)
 constexpr int EE_EPB = 128;          // edges per workgroup of the forward: two waves, one edge per lane
 constexpr int EE_PT = 256;           // threads of eemb_param_kernel: four waves
 constexpr int EE_LDR = EE_KMAX + 1;  // row stride of the LDS tile of rows
+constexpr int EE_LDR_LAT = EE_KMAX + 2 * EE_NLMAX + 1;      // the same with the latent columns: 77, odd
 constexpr int EE_LDH = EE_H + 1;     // row stride of the LDS tiles of grad_emb, hid and gpre
 static_assert(EE_H == NS, "the edge embedding of ns = 24");
 
@@ -53,6 +65,14 @@ struct EembArgs {
   uint32_t seed_lo, seed_hi;
   float offset[EE_D];
 };
+
+// what the latent instantiations take on top (glat_a / glat_b: the planes [E, NL] of the parameter pass, null: not made; img_u: the images [slices][24] of grad_uemb)
+struct EembLatArgs : EembArgs {
+  const float* lat_a; const float* lat_b; const float* unc_a; const float* uemb;
+  float* glat_a; float* glat_b; float* img_u;
+  int NL, zero_latent;
+};
+template <bool LAT> using EembKernelArgs = std::conditional_t<LAT, EembLatArgs, EembArgs>;
 
 struct EembEdge { float x, y, z, d; int64_t sig_row; };
 
@@ -103,7 +123,8 @@ __device__ __forceinline__ void eemb_hidden(const EembArgs& a, int64_t e, int c0
 }
 
 // ---- forward -------------------------------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(EE_EPB) void eemb_fwd_kernel(EembArgs a) {
+template <bool LAT>
+__global__ __launch_bounds__(EE_EPB) void eemb_fwd_kernel(EembKernelArgs<LAT> a) {
   const int64_t e = (int64_t)blockIdx.x * EE_EPB + threadIdx.x;
   const bool ev = e < a.E;
   const int64_t el = ev ? e : 0;      // a lane past the end works on edge 0 and stores nothing
@@ -147,6 +168,16 @@ __global__ __launch_bounds__(EE_EPB) void eemb_fwd_kernel(EembArgs a) {
       for (int i = 0; i < 4; ++i) acc[c] = fmaf(w[c * K + i], x[i], acc[c]);
     }
   }
+  if constexpr (LAT) {      // the latent of the edge's two nodes: columns F + 64 .. K - 1 (zero_latent: the row holds zeros there)
+    const int64_t ia = a.idx_a[el], ib = a.idx_b[el];
+    const float* w = a.w1 + k0 + EE_S + EE_D;
+#pragma unroll 1
+    for (int j = 0; j < 2 * a.NL; ++j) {
+      const float x = a.zero_latent ? 0.f : (j < a.NL ? a.lat_a[ia * a.NL + j] : a.lat_b[ib * a.NL + j - a.NL]);
+#pragma unroll
+      for (int c = 0; c < EE_H; ++c) acc[c] = fmaf(w[c * K + j], x, acc[c]);
+    }
+  }
 #pragma unroll
   for (int c = 0; c < EE_H; c += 8) eemb_hidden<8>(a, el, c, acc + c);
   float out[EE_H];
@@ -156,6 +187,13 @@ __global__ __launch_bounds__(EE_EPB) void eemb_fwd_kernel(EembArgs a) {
 #pragma unroll
     for (int c = 0; c < EE_H; ++c) v = fmaf(a.w2[o * EE_H + c], acc[c], v);
     out[o] = v;
+  }
+  if constexpr (LAT) {
+    if (a.unc_a) {
+      const float u = a.unc_a[a.idx_a[el]];
+#pragma unroll
+      for (int o = 0; o < EE_H; ++o) out[o] = fmaf(u, a.uemb[o], out[o]);
+    }
   }
   if (ev) {
     float4* to = reinterpret_cast<float4*>(a.emb + e * EE_H);
@@ -170,8 +208,11 @@ __global__ __launch_bounds__(EE_EPB) void eemb_fwd_kernel(EembArgs a) {
 // image of a slice: [24][K + 1] (grad_w1, column K grad_b1), then [24][25] (grad_w2, column 24 grad_b2)
 __host__ __device__ inline int eemb_img(int K) { return EE_H * (K + 1) + EE_H * (EE_H + 1); }
 
-__global__ __launch_bounds__(EE_PT) void eemb_param_kernel(EembArgs a) {
-  __shared__ float rows[64 * EE_LDR];
+template <bool LAT>
+__global__ __launch_bounds__(EE_PT) void eemb_param_kernel(EembKernelArgs<LAT> a) {
+  constexpr int LDR = LAT ? EE_LDR_LAT : EE_LDR;
+  __shared__ float rows[64 * LDR];
+  constexpr int UC = EE_LDR_LAT - 1;      // latent variant: the tile's last column (K <= 76 never reaches it) holds unc_a of the edge
   __shared__ float gs[64 * EE_LDH];
   __shared__ float hs[64 * EE_LDH];
   __shared__ float ps[64 * EE_LDH];
@@ -183,10 +224,10 @@ __global__ __launch_bounds__(EE_PT) void eemb_param_kernel(EembArgs a) {
   // the thread's elements of the image: rows 3 tc .. 3 tc + 2 of columns tk, tk + 32, tk + 64 (< K) of grad_w1; of column tk (< 24) of grad_w2;
   // tk == 24: of grad_b1; tk == 25: of grad_b2
   const int tc = tid & 7, tk = tid >> 3;
-  float a1[3][3], a2[3];
+  float a1[3][3], a2[3], au[3];
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
-    a2[i] = 0.f;
+    a2[i] = 0.f; au[i] = 0.f;
 #pragma unroll
     for (int j = 0; j < 3; ++j) a1[i][j] = 0.f;
   }
@@ -198,7 +239,7 @@ __global__ __launch_bounds__(EE_PT) void eemb_param_kernel(EembArgs a) {
     // 1. the wave's columns of the row and of grad_emb; a lane past the end stages zeros, which leave every sum as it is
     {
       const EembEdge g = eemb_geometry(a, el);
-      float* r = rows + lane * EE_LDR;
+      float* r = rows + lane * LDR;
       if (wave == 0 && F) {
         const float4 f = reinterpret_cast<const float4*>(a.feat)[el];
         r[0] = ev ? f.x : 0.f; r[1] = ev ? f.y : 0.f; r[2] = ev ? f.z : 0.f; r[3] = ev ? f.w : 0.f;
@@ -214,11 +255,22 @@ __global__ __launch_bounds__(EE_PT) void eemb_param_kernel(EembArgs a) {
       }
 #pragma unroll
       for (int i = 0; i < 6; ++i) gs[lane * EE_LDH + 6 * wave + i] = ev ? a.gemb[el * EE_H + 6 * wave + i] : 0.f;
+      if constexpr (LAT) {
+        if (wave == 1) {      // the latent columns; wave 2: unc_a of the edge
+          const int64_t ia = a.idx_a[el], ib = a.idx_b[el];
+          for (int j = 0; j < 2 * a.NL; ++j) {
+            const float x = a.zero_latent ? 0.f : (j < a.NL ? a.lat_a[ia * a.NL + j] : a.lat_b[ib * a.NL + j - a.NL]);
+            r[F + EE_S + EE_D + j] = ev ? x : 0.f;
+          }
+        } else if (wave == 2) {
+          rows[lane * LDR + UC] = (ev && a.unc_a) ? a.unc_a[a.idx_a[el]] : 0.f;
+        }
+      }
     }
     __syncthreads();
     // 2. six columns of pre and of hid: the forward's chain over the row
     {
-      const float* r = rows + lane * EE_LDR;
+      const float* r = rows + lane * LDR;
       const float* w = a.w1 + 6 * wave * K;
       float v[6];
 #pragma unroll
@@ -244,12 +296,26 @@ __global__ __launch_bounds__(EE_PT) void eemb_param_kernel(EembArgs a) {
       for (int i = 0; i < 6; ++i) ps[lane * EE_LDH + 6 * wave + i] = ev ? gh[i] * (v[i] != 0.f ? a.s : 0.f) : 0.f;
     }
     __syncthreads();
+    if constexpr (LAT) {      // the latent's per-edge gradient rows: wave w makes columns w and w + 4 of [idx_a's NL | idx_b's NL], one chain over c ascending
+      if (a.glat_a) {
+        for (int j = wave; j < 2 * a.NL; j += 4) {
+          const float* w = a.w1 + F + EE_S + EE_D + j;
+          float v = 0.f;
+#pragma unroll 4
+          for (int c = 0; c < EE_H; ++c) v = fmaf(ps[lane * EE_LDH + c], w[c * K], v);
+          if (ev) {
+            if (j < a.NL) a.glat_a[e * a.NL + j] = v;
+            else a.glat_b[e * a.NL + j - a.NL] = v;
+          }
+        }
+      }
+    }
     // 4. the step's 64 edges, ascending, into the thread's elements of the image
     if (tk < EE_H) {
 #pragma unroll 4
       for (int l = 0; l < 64; ++l) {
         const float hv = hs[l * EE_LDH + tk];
-        const float x0 = rows[l * EE_LDR + tk], x1 = rows[l * EE_LDR + tk + 32], x2 = third ? rows[l * EE_LDR + tk + 64] : 0.f;
+        const float x0 = rows[l * LDR + tk], x1 = rows[l * LDR + tk + 32], x2 = third ? rows[l * LDR + tk + 64] : 0.f;
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
           const float gp = ps[l * EE_LDH + 3 * tc + i];
@@ -261,12 +327,13 @@ __global__ __launch_bounds__(EE_PT) void eemb_param_kernel(EembArgs a) {
       const float* from = tk == EE_H ? ps : gs;      // grad_b1 = the sum of gpre, grad_b2 = the sum of grad_emb (tk == 25; the threads behind add what they never store)
 #pragma unroll 4
       for (int l = 0; l < 64; ++l) {
-        const float x0 = rows[l * EE_LDR + tk], x1 = rows[l * EE_LDR + tk + 32];
+        const float x0 = rows[l * LDR + tk], x1 = rows[l * LDR + tk + 32];
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
           const float gp = ps[l * EE_LDH + 3 * tc + i];
           a1[i][0] = fmaf(gp, x0, a1[i][0]); a1[i][1] = fmaf(gp, x1, a1[i][1]);
           a2[i] += from[l * EE_LDH + 3 * tc + i];
+          if constexpr (LAT) au[i] = fmaf(rows[l * LDR + UC], gs[l * EE_LDH + 3 * tc + i], au[i]);      // grad_uemb (tk == 25 stores it)
         }
       }
     }
@@ -283,6 +350,9 @@ __global__ __launch_bounds__(EE_PT) void eemb_param_kernel(EembArgs a) {
     if (tk < EE_H) img2[c * (EE_H + 1) + tk] = a2[i];
     else if (tk == EE_H) img[c * (K + 1) + K] = a2[i];
     else if (tk == EE_H + 1) img2[c * (EE_H + 1) + EE_H] = a2[i];
+    if constexpr (LAT) {
+      if (tk == EE_H + 1) a.img_u[slice * EE_H + c] = au[i];
+    }
   }
 }
 
@@ -293,8 +363,9 @@ int64_t eemb_workspace(int64_t E, int32_t K) {
 }
 
 // offset as torch.linspace(start, stop, 32) makes it in fp32 (one fused multiply-add per centre, the upper half counted down from stop), coeff as GaussianSmearing: -0.5 / (offset[1] - offset[0])^2
-static EembArgs eemb_args(const EembOperands& o, int64_t E) {
-  EembArgs a{};
+template <class Args = EembArgs>
+static Args eemb_args(const EembOperands& o, int64_t E) {
+  Args a{};
   a.pos_a = o.pos_a; a.pos_b = o.pos_b; a.idx_a = o.idx_a; a.idx_b = o.idx_b; a.feat = o.feat; a.sig = o.sig; a.sig_index = o.sig_index;
   a.w1 = o.w1; a.b1 = o.b1; a.w2 = o.w2; a.b2 = o.b2;
   a.E = E; a.L = rtp_slice_len(E);
@@ -313,7 +384,7 @@ hipError_t launch_eemb_forward(const EembOperands& o, int64_t E, float* emb, flo
   if (E == 0) return hipSuccess;
   EembArgs a = eemb_args(o, E);
   a.emb = emb; a.sh = sh;
-  hipLaunchKernelGGL(eemb_fwd_kernel, dim3((unsigned)((E + EE_EPB - 1) / EE_EPB)), dim3(EE_EPB), 0, s, a);      // E < 2^31: fewer than 2^31 workgroups
+  hipLaunchKernelGGL(eemb_fwd_kernel<false>, dim3((unsigned)((E + EE_EPB - 1) / EE_EPB)), dim3(EE_EPB), 0, s, a);      // E < 2^31: fewer than 2^31 workgroups
   return hipGetLastError();
 }
 
@@ -330,10 +401,72 @@ hipError_t launch_eemb_backward(const EembOperands& o, const float* grad_emb, in
   EembArgs a = eemb_args(o, E);
   a.gemb = grad_emb; a.img = workspace;
   const int64_t n_slices = (E + a.L - 1) / a.L;      // at most 241
-  hipLaunchKernelGGL(eemb_param_kernel, dim3((unsigned)n_slices), dim3(EE_PT), 0, s, a);
+  hipLaunchKernelGGL(eemb_param_kernel<false>, dim3((unsigned)n_slices), dim3(EE_PT), 0, s, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   return launch_slice_reduce(workspace, group_table(E), a.L, ReducePart{grad_w1, grad_b1, EE_H, K}, ReducePart{grad_w2, grad_b2, EE_H, EE_H}, s);
+}
+
+// ---- host: the latent variant ------------------------------------------------------------------------------------------------------------------------------
+// workspace: [slices][eemb_img(K)] | [slices][24] (grad_uemb) | glat_a [E][NL] | glat_b [E][NL], every part on 16 bytes
+int64_t eemb_latent_workspace(int64_t E, int32_t K, int32_t NL) {
+  if (E < 0 || E >= (int64_t)1 << 31 || NL < 1 || NL > EE_NLMAX || (K != EE_S + EE_D + 2 * NL && K != EE_KMAX + 2 * NL)) return -1;
+  const int64_t ns = slice_bound(E, 1);
+  return (ws_pad(ns * eemb_img(K)) + ws_pad(ns * EE_H) + 2 * ws_pad(E * NL)) * (int64_t)sizeof(float);
+}
+
+static EembLatArgs eemb_latent_args(const EembOperands& o, const EembLatent& l, int64_t E) {
+  EembLatArgs a = eemb_args<EembLatArgs>(o, E);
+  a.K += 2 * l.NL;
+  a.lat_a = l.lat_a; a.lat_b = l.lat_b; a.unc_a = l.unc_a; a.uemb = l.uemb;
+  a.NL = l.NL; a.zero_latent = l.zero_latent;
+  return a;
+}
+
+hipError_t launch_eemb_latent_forward(const EembOperands& o, const EembLatent& l, int64_t E, float* emb, float* sh, hipStream_t s) {
+  if (E == 0) return hipSuccess;
+  EembLatArgs a = eemb_latent_args(o, l, E);
+  a.emb = emb; a.sh = sh;
+  hipLaunchKernelGGL(eemb_fwd_kernel<true>, dim3((unsigned)((E + EE_EPB - 1) / EE_EPB)), dim3(EE_EPB), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_eemb_latent_backward(const EembOperands& o, const EembLatent& l, const EembLatentGraph& gr, const float* grad_emb, int64_t E, float* grad_w1,
+                                       float* grad_b1, float* grad_w2, float* grad_b2, float* grad_uemb, float* grad_lat_a, float* grad_lat_b,
+                                       float* workspace, hipStream_t s) {
+  const int K = o.F + EE_S + EE_D + 2 * l.NL;
+  const bool nodes = !l.zero_latent && E > 0 && (grad_lat_a || grad_lat_b);
+  hipError_t e = hipSuccess;
+  if (!nodes) {      // no edges, or the cross group: the latent gets zeros
+    e = zero_async(grad_lat_a, gr.n_a * l.NL, s);
+    if (e == hipSuccess) e = zero_async(grad_lat_b, gr.n_b * l.NL, s);
+  }
+  if (E == 0) {
+    if (e == hipSuccess) e = zero_async(grad_w1, EE_H * K, s);
+    if (e == hipSuccess) e = zero_async(grad_b1, EE_H, s);
+    if (e == hipSuccess) e = zero_async(grad_w2, EE_H * EE_H, s);
+    if (e == hipSuccess) e = zero_async(grad_b2, EE_H, s);
+    if (e == hipSuccess) e = zero_async(grad_uemb, EE_H, s);
+    return e;
+  }
+  if (e != hipSuccess) return e;
+  EembLatArgs a = eemb_latent_args(o, l, E);
+  const int64_t ns = slice_bound(E, 1);
+  a.gemb = grad_emb; a.img = workspace;
+  a.img_u = workspace + ws_pad(ns * eemb_img(K));
+  float* glat_a = a.img_u + ws_pad(ns * EE_H);
+  float* glat_b = glat_a + ws_pad(E * l.NL);
+  a.glat_a = nodes ? glat_a : nullptr; a.glat_b = nodes ? glat_b : nullptr;
+  const int64_t n_slices = (E + a.L - 1) / a.L;      // at most 241
+  hipLaunchKernelGGL(eemb_param_kernel<true>, dim3((unsigned)n_slices), dim3(EE_PT), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  const EdgeGroupTable t = group_table(E);
+  if (grad_w1 || grad_b1 || grad_w2 || grad_b2)
+    e = launch_slice_reduce(workspace, t, a.L, ReducePart{grad_w1, grad_b1, EE_H, K}, ReducePart{grad_w2, grad_b2, EE_H, EE_H}, s);
+  if (e == hipSuccess && grad_uemb) e = launch_slice_reduce(a.img_u, t, a.L, ReducePart{nullptr, grad_uemb, EE_H, 0}, ReducePart{nullptr, nullptr, 0, 0}, s);
+  if (e == hipSuccess && nodes && grad_lat_a) e = launch_seg_sum(glat_a, gr.order_a, gr.ptr_a, grad_lat_a, gr.n_a, l.NL, s);
+  if (e == hipSuccess && nodes && grad_lat_b) e = launch_seg_sum(glat_b, gr.order_b, gr.ptr_b, grad_lat_b, gr.n_b, l.NL, s);
+  return e;
 }
 
 }  // namespace ddk

@@ -1,0 +1,215 @@
+// The ragged straight-through Gumbel softmax in front of the latent-conditioned score model (include/ddk.h: ddk_gumbel_softmax_batch, DDK_GUMBEL_LAYOUT) and
+// its vector-Jacobian product: the reference's per-graph loop (latent_encoder.py:328-335, pretrained_score_encoder.py:74-81 over models/layers.py:152-181) for a
+// whole collated batch in one launch.  ONE WORKGROUP per (graph g, latent dimension d); the class axis is the graph's ligand nodes, then its receptor nodes,
+// position p = 0 .. n_lig_g + n_rec_g - 1.  Exact fp32 in a written-out order (compiled with -ffp-contract=off):
+//   u    = (word >> 8) * 2^-24                               the word of position p: see THE NOISE below
+//   gum  = -logf(-logf(u + 1e-20f) + 1e-20f)                 the accurate library logf
+//   z    = (logit + gum) / T                                  a true division
+//   y    = expf(z - max z) / sum                              the sum: thread t adds its positions (quads t, t + 256, ... of four positions, ascending) to a
+//                                                             partial that starts from 0, then the 256 partials are added by the fixed halving tree
+//   out  = (hard - y) + y                                     two operations as written; hard = 1 at the LOWEST position that holds the maximum of y, else 0
+// and backward, from the saved y:  grad_logit = y * (g - sum g y) / T, the sum in the same order.  No atomics; y's buffer holds z and the exponentials between the
+// passes (a thread reads back only what it wrote itself), so there is no limit on the number of nodes.
+//
+// THE NOISE (DDK_GUMBEL_LAYOUT 1): generator purpose 13 of DDK_RNG_LAYOUT 1, rng_block(seed, stream_id[g], sample, 13, draw, d), yields four words; words 0 and 1
+// are the key of a second Philox4x32-10 whose counter (p / 4, 0, 0, DDK_GUMBEL_TAG) gives position p the word p % 4.  A graph's noise is a pure function of
+// (seed, complex, sample, draw, d, position): the batch it sits in and its place there do not matter.
+#include "ddk_internal.h"
+#include "k_philox.h"
+
+namespace ddk {
+
+constexpr int GUM_T = 256;
+constexpr uint32_t RNG_GUMBEL = 13;      // DDK_RNG_LAYOUT 1, beside RngPurpose
+
+struct GumbelArgs {      // the forward
+  const float* logit_l; const float* logit_r;
+  const int64_t* lig_ptr; const int64_t* rec_ptr; const uint64_t* stream_id;
+  float* y_l; float* y_r; float* out_l; float* out_r;
+  int64_t n_lig, n_rec;
+  int D;
+  float T;
+  uint32_t seed_lo, seed_hi, sample, draw;
+};
+struct GumbelBwdArgs {      // the backward: the saved y and grad_out in, grad_logit out
+  const float* y_l; const float* y_r; const float* gout_l; const float* gout_r;
+  const int64_t* lig_ptr; const int64_t* rec_ptr;
+  float* grad_l; float* grad_r;
+  int64_t n_lig, n_rec;
+  int D;
+  float T;
+};
+
+// the graph's nodes on both sides, or n < 0 where a pointer pair is no range of its table (the graph is then left alone)
+struct GumbelGraph { int64_t l0, r0, nl, n; };
+template <class Args>
+__device__ __forceinline__ GumbelGraph gumbel_graph(const Args& a, int g) {
+  const int64_t l0 = a.lig_ptr[g], l1 = a.lig_ptr[g + 1], r0 = a.rec_ptr[g], r1 = a.rec_ptr[g + 1];
+  const bool ok = l0 >= 0 && l0 <= l1 && l1 <= a.n_lig && r0 >= 0 && r0 <= r1 && r1 <= a.n_rec;
+  return GumbelGraph{l0, r0, l1 - l0, ok ? (l1 - l0) + (r1 - r0) : -1};
+}
+// element (position p, column d) of a pair of node tables
+__device__ __forceinline__ int64_t gumbel_at(const GumbelGraph& G, int64_t p, int D, int d, bool& lig) {
+  lig = p < G.nl;
+  return (lig ? G.l0 + p : G.r0 + (p - G.nl)) * D + d;
+}
+
+__device__ __forceinline__ float gumbel_tree_sum(float* red, float v) {
+  const int t = threadIdx.x;
+  __syncthreads();      // (the tile may still be read from the reduction before)
+  red[t] = v;
+  __syncthreads();
+  for (int s = GUM_T / 2; s > 0; s >>= 1) {
+    if (t < s) red[t] = red[t] + red[t + s];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+__global__ __launch_bounds__(GUM_T) void gumbel_fwd_kernel(GumbelArgs a) {
+  __shared__ float red[GUM_T];
+  __shared__ int64_t redi[GUM_T];
+  const int g = blockIdx.x, d = blockIdx.y, t = threadIdx.x;
+  const GumbelGraph G = gumbel_graph(a, g);
+  if (G.n <= 0) return;
+  uint32_t key[4];
+  rng_block(rng_stream(((uint64_t)a.seed_hi << 32) | a.seed_lo, a.stream_id[g]), a.sample, RNG_GUMBEL, a.draw, (uint32_t)d, key);
+  const int64_t quads = (G.n + 3) >> 2;
+  bool lig;
+  // 1. z into y's buffer, the thread's maximum
+  float m = -INFINITY;
+  for (int64_t q = t; q < quads; q += GUM_T) {
+    const uint32_t ctr[4] = {(uint32_t)q, 0u, 0u, DDK_GUMBEL_TAG};
+    uint32_t w[4];
+    philox4x32_10(ctr, key, w);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int64_t p = 4 * q + i;
+      if (p < G.n) {
+        const int64_t at = gumbel_at(G, p, a.D, d, lig);
+        const float u = rng_uniform(w[i]);
+        const float gum = -logf(-logf(u + 1e-20f) + 1e-20f);
+        const float z = ((lig ? a.logit_l : a.logit_r)[at] + gum) / a.T;
+        (lig ? a.y_l : a.y_r)[at] = z;
+        m = fmaxf(m, z);
+      }
+    }
+  }
+  __syncthreads();
+  red[t] = m;
+  __syncthreads();
+  for (int s = GUM_T / 2; s > 0; s >>= 1) {
+    if (t < s) red[t] = fmaxf(red[t], red[t + s]);
+    __syncthreads();
+  }
+  m = red[0];
+  // 2. the exponentials and their sum
+  float part = 0.f;
+  for (int64_t q = t; q < quads; q += GUM_T) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int64_t p = 4 * q + i;
+      if (p < G.n) {
+        const int64_t at = gumbel_at(G, p, a.D, d, lig);
+        float* y = lig ? a.y_l : a.y_r;
+        const float e = expf(y[at] - m);
+        y[at] = e;
+        part += e;
+      }
+    }
+  }
+  const float sum = gumbel_tree_sum(red, part);
+  // 3. y and the lowest position of its maximum
+  float best = -INFINITY;
+  int64_t where = INT64_MAX;
+  for (int64_t q = t; q < quads; q += GUM_T) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int64_t p = 4 * q + i;
+      if (p < G.n) {
+        const int64_t at = gumbel_at(G, p, a.D, d, lig);
+        float* y = lig ? a.y_l : a.y_r;
+        const float v = y[at] / sum;
+        y[at] = v;
+        if (v > best) { best = v; where = p; }      // (ascending p: the first of equals stays)
+      }
+    }
+  }
+  __syncthreads();
+  red[t] = best; redi[t] = where;
+  __syncthreads();
+  for (int s = GUM_T / 2; s > 0; s >>= 1) {
+    if (t < s) {
+      const float o = red[t + s];
+      const int64_t oi = redi[t + s];
+      if (o > red[t] || (o == red[t] && oi < redi[t])) { red[t] = o; redi[t] = oi; }
+    }
+    __syncthreads();
+  }
+  where = redi[0];
+  // 4. the straight-through output
+  for (int64_t q = t; q < quads; q += GUM_T) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int64_t p = 4 * q + i;
+      if (p < G.n) {
+        const int64_t at = gumbel_at(G, p, a.D, d, lig);
+        const float y = (lig ? a.y_l : a.y_r)[at];
+        const float hard = p == where ? 1.f : 0.f;
+        (lig ? a.out_l : a.out_r)[at] = (hard - y) + y;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(GUM_T) void gumbel_bwd_kernel(GumbelBwdArgs a) {
+  __shared__ float red[GUM_T];
+  const int g = blockIdx.x, d = blockIdx.y, t = threadIdx.x;
+  const GumbelGraph G = gumbel_graph(a, g);
+  if (G.n <= 0) return;
+  const int64_t quads = (G.n + 3) >> 2;
+  bool lig;
+  float part = 0.f;
+  for (int64_t q = t; q < quads; q += GUM_T) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int64_t p = 4 * q + i;
+      if (p < G.n) {
+        const int64_t at = gumbel_at(G, p, a.D, d, lig);
+        part += (lig ? a.gout_l : a.gout_r)[at] * (lig ? a.y_l : a.y_r)[at];
+      }
+    }
+  }
+  const float dot = gumbel_tree_sum(red, part);
+  for (int64_t q = t; q < quads; q += GUM_T) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int64_t p = 4 * q + i;
+      if (p < G.n) {
+        const int64_t at = gumbel_at(G, p, a.D, d, lig);
+        const float y = (lig ? a.y_l : a.y_r)[at], go = (lig ? a.gout_l : a.gout_r)[at];
+        (lig ? a.grad_l : a.grad_r)[at] = y * (go - dot) / a.T;
+      }
+    }
+  }
+}
+
+hipError_t launch_gumbel_forward(const GumbelOperands& o, const float* logit_l, const float* logit_r, uint64_t seed, const uint64_t* stream_id, uint32_t sample,
+                                 uint32_t draw, float* y_l, float* y_r, float* out_l, float* out_r, hipStream_t s) {
+  GumbelArgs a{};
+  a.logit_l = logit_l; a.logit_r = logit_r; a.lig_ptr = o.lig_ptr; a.rec_ptr = o.rec_ptr; a.stream_id = stream_id;
+  a.y_l = y_l; a.y_r = y_r; a.out_l = out_l; a.out_r = out_r;
+  a.n_lig = o.n_lig; a.n_rec = o.n_rec; a.D = o.D; a.T = o.T;
+  a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.sample = sample; a.draw = draw;
+  hipLaunchKernelGGL(gumbel_fwd_kernel, dim3((unsigned)o.G, (unsigned)o.D), dim3(GUM_T), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_gumbel_backward(const GumbelOperands& o, const float* y_l, const float* y_r, const float* gout_l, const float* gout_r, float* grad_l,
+                                  float* grad_r, hipStream_t s) {
+  const GumbelBwdArgs a{y_l, y_r, gout_l, gout_r, o.lig_ptr, o.rec_ptr, grad_l, grad_r, o.n_lig, o.n_rec, o.D, o.T};
+  hipLaunchKernelGGL(gumbel_bwd_kernel, dim3((unsigned)o.G, (unsigned)o.D), dim3(GUM_T), 0, s, a);
+  return hipGetLastError();
+}
+
+}  // namespace ddk

@@ -56,6 +56,9 @@ RNG_MAX_STEPS, RNG_MAX_COLS = 1 << 20, 1024
 RNG_FORWARD_PURPOSES = dict(forward_translation=6, forward_rotation=7, forward_torsion=8)
 # the diffusion time of a complex for one noising (ddk_rng_forward_times): step = the draw index, block 0, word 0
 RNG_TIME_PURPOSE = 11
+# the latent of the DisCo score model: the keep flag of a complex (ddk_rng_latent_keep) and the Gumbel noise (DDK_GUMBEL_LAYOUT: step = the draw index, block = d)
+RNG_LATENT_KEEP_PURPOSE, RNG_GUMBEL_PURPOSE = 12, 13
+GUMBEL_LAYOUT, GUMBEL_TAG = 1, 0x47554D42
 # the ragged batch forms (ddk_rng_perturbation_batch, ddk_modify_conformer_batch, ddk_score_matching_loss_batch): limits (csrc/model.h) and status words
 NOISE_BATCH_MAX_GRAPHS, NOISE_BATCH_MAX_LIG, NOISE_BATCH_MAX_ROT = 65536, 256, 1024
 CONFORMER_BATCH_STATUS = ('done', None, 'a bond index outside the graph, or u == v', 'a coordinate that is not finite', 'a node_ptr / tor_ptr / mask_ptr entry out of range')
@@ -738,6 +741,162 @@ class Context:
         ws = _workspace(self.L.ddk_eemb_workspace(E, F + 64), f'no edge-embedding workspace for E = {E}, K = {F + 64}', dev)
         self._eemb_call(self.L.ddk_eemb_backward, t, n, sc, seed, (_ptr(grad_emb) if E else None, E, *[_ptr(o) for o in outs], _ptr(ws)), 'ddk_eemb_backward')
         return tuple(outs)      # (ws goes back to torch's allocator, which orders its reuse after these launches on the current stream)
+
+    # ---- the edge embeddings of the latent-conditioned (DisCo) model ------------------------------------
+    def _eemb_latent_operands(self, ops, lat_a, lat_b, zero_latent, unc_a, uemb, b2=None):
+        """checked operands of the latent edge embedding: those of ``_eemb_operands`` (``ops``: its arguments with w1 [24, F + 64 + 2 L]) and
+        (lat_a, lat_b, L, zero_latent, unc_a, uemb)"""
+        pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, p = ops
+        if not torch.is_tensor(w1) or w1.dim() != 2:
+            raise RuntimeError('ddk: the latent edge embedding takes w1 [24, F + 64 + 2 L]')
+        F = 0 if feat is None else 4
+        L2 = w1.shape[1] - F - 64
+        if L2 not in (2, 4, 6, 8):
+            raise RuntimeError(f'ddk: the latent edge embedding takes w1 [24, {F + 64} + 2 L] with L in 1..4; got {tuple(w1.shape)}')
+        L = L2 // 2
+        w1 = _need_cuda(w1).contiguous().float()
+        t, n, sc = self._eemb_operands(pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1[:, :F + 64], b1, w2, b2, p)
+        t = t[:7] + (w1,) + t[8:]
+        dev, n_a, n_b = t[0].device, n[0], n[1]
+        zero_latent = bool(zero_latent)
+        if zero_latent:
+            lat_a = lat_b = None
+        else:
+            if lat_a is None or lat_b is None:
+                raise RuntimeError('ddk: the latent edge embedding takes lat_a and lat_b unless zero_latent is set')
+            lat_a, lat_b = (_need_cuda(x).contiguous().float() for x in (lat_a, lat_b))
+            if lat_a.shape != (n_a, L) or lat_b.shape != (n_b, L) or lat_a.device != dev or lat_b.device != dev:
+                raise RuntimeError(f'ddk: the latent edge embedding takes lat_a [Na, L] = {(n_a, L)} and lat_b [Nb, L] = {(n_b, L)} on the device of pos_a; got '
+                                   f'{tuple(lat_a.shape)} and {tuple(lat_b.shape)}')
+        if (unc_a is None) != (uemb is None):
+            raise RuntimeError('ddk: the latent edge embedding takes unc_a and uemb together')
+        if unc_a is not None:
+            unc_a, uemb = _need_cuda(unc_a).contiguous().float().reshape(-1), _need_cuda(uemb).contiguous().float().reshape(-1)
+            if unc_a.shape != (n_a,) or uemb.shape != (24,) or unc_a.device != dev or uemb.device != dev:
+                raise RuntimeError(f'ddk: the latent edge embedding takes unc_a [Na] = {(n_a,)} and uemb [24] on the device of pos_a; got {tuple(unc_a.shape)} and '
+                                   f'{tuple(uemb.shape)}')
+        return t, n, sc, (lat_a, lat_b, L, zero_latent, unc_a, uemb)
+
+    def _eemb_latent_call(self, fn, t, n, sc, seed, lat, tail, who):
+        pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, w1, b1, w2, b2 = t
+        n_a, n_b, F, T, E = n
+        start, stop, p = sc
+        lat_a, lat_b, L, zero, unc_a, uemb = lat
+        self._check(fn(self.h, _ptr(pos_a), n_a, _ptr(pos_b), n_b, _ptr(idx_a), _ptr(idx_b), _ptr(feat), F, _ptr(sig), T, _ptr(sig_index), start, stop, 32,
+                       _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), p, _u64(seed, 'seed'), _ptr(lat_a), _ptr(lat_b), L, int(zero), _ptr(unc_a), _ptr(uemb),
+                       *tail, _stream()), who)
+
+    def eemb_latent_forward(self, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, b2, lat_a, lat_b, zero_latent=False, unc_a=None,
+                            uemb=None, p=0.0, seed=0):
+        """``eemb_forward`` with the latent columns (ddk_eemb_latent_forward): the row is ``[feat | sig | smearing | lat_a[idx_a] | lat_b[idx_b]]``, ``w1``
+        [24, F + 64 + 2 L], and ``emb += unc_a[idx_a][:, None] * uemb`` where ``unc_a`` [Na] and ``uemb`` [24] are given.  ``zero_latent``: the 2 L columns
+        hold zeros and the tables are not read (the cross group).  Returns (emb [E, 24], sh [E, 4])."""
+        t, n, sc, lat = self._eemb_latent_operands((pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, p), lat_a, lat_b, zero_latent,
+                                                   unc_a, uemb, b2)
+        if t[-1] is None:
+            raise RuntimeError('ddk: eemb_latent_forward needs b2')
+        E, dev = n[4], t[0].device
+        emb, sh = torch.empty((E, 24), dtype=torch.float32, device=dev), torch.empty((E, 4), dtype=torch.float32, device=dev)
+        if E:
+            self._eemb_latent_call(self.L.ddk_eemb_latent_forward, t, n, sc, seed, lat, (E, _ptr(emb), _ptr(sh)), 'ddk_eemb_latent_forward')
+        return emb, sh
+
+    def eemb_latent_backward(self, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, lat_a, lat_b, grad_emb, zero_latent=False,
+                             unc_a=None, uemb=None, p=0.0, seed=0, graph=None, need=(True,) * 7):
+        """The vector-Jacobian product of ``eemb_latent_forward`` (ddk_eemb_latent_backward): (grad_w1 [24, K], grad_b1 [24], grad_w2 [24, 24], grad_b2 [24],
+        grad_uemb [24], grad_lat_a [Na, L], grad_lat_b [Nb, L]), None where ``need`` is false.  ``graph``: ``Context.conv_graph(idx_a, idx_b, Nb, Na)``, the
+        node-sorted edge lists the latent's gradient is summed along (needed for grad_lat_a / grad_lat_b unless ``zero_latent``).  Per-edge rows [E, 2 L] and
+        the slice images are the whole workspace; no atomics: the same bits from call to call and for every subset of ``need``."""
+        need = tuple(bool(x) for x in need)
+        if len(need) != 7 or not any(need):
+            raise RuntimeError('ddk: eemb_latent_backward needs at least one of its seven gradients to compute')
+        t, n, sc, lat = self._eemb_latent_operands((pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, p), lat_a, lat_b, zero_latent,
+                                                   unc_a, uemb)
+        n_a, n_b, F, _, E = n
+        dev, L = t[0].device, lat[2]
+        K = F + 64 + 2 * L
+        grad_emb = _need_cuda(grad_emb).contiguous().float()
+        if grad_emb.shape != (E, 24) or grad_emb.device != dev:
+            raise RuntimeError(f'ddk: eemb_latent_backward takes grad_emb [E, 24] = {(E, 24)} on the device of pos_a; got {tuple(grad_emb.shape)}')
+        tables = (None,) * 4
+        if E and not lat[3] and (need[5] or need[6]):
+            if not isinstance(graph, ConvGraph) or graph.E != E or graph.n_out != n_a or graph.n_in != n_b or graph.src.device != dev:
+                raise RuntimeError('ddk: eemb_latent_backward takes graph = Context.conv_graph(idx_a, idx_b, Nb, Na) on the device of pos_a for the latent gradients')
+            tables = (graph.src_order, graph.src_ptr, graph.dst_order, graph.dst_ptr)
+        outs, live = _outputs(need, ((24, K), (24,), (24, 24), (24,), (24,), (n_a, L), (n_b, L)), dev)
+        if not live:
+            return tuple(outs)
+        outs = [o if o is None or o.numel() else None for o in outs]      # (an empty node table has no address)
+        ws = _workspace(self.L.ddk_eemb_latent_workspace(E, K, L), f'no latent edge-embedding workspace for E = {E}, K = {K}, L = {L}', dev)
+        self._eemb_latent_call(self.L.ddk_eemb_latent_backward, t, n, sc, seed, lat,
+                               (*[_ptr(x) for x in tables], _ptr(grad_emb) if E else None, E, *[_ptr(o) for o in outs], _ptr(ws)), 'ddk_eemb_latent_backward')
+        shapes = ((24, K), (24,), (24, 24), (24,), (24,), (n_a, L), (n_b, L))
+        return tuple(torch.zeros(s, dtype=torch.float32, device=dev) if (on and o is None) else o for on, o, s in zip(need, outs, shapes))
+
+    # ---- the ragged straight-through Gumbel softmax ------------------------------------------------------
+    @staticmethod
+    def _gumbel_operands(a_l, a_r, lig_ptr, rec_ptr, temperature, who):
+        a_l, a_r = (_need_cuda(x).contiguous().float() for x in (a_l, a_r))
+        dev = a_l.device
+        if a_l.dim() != 2 or a_r.dim() != 2 or a_l.shape[1] != a_r.shape[1] or not 1 <= a_l.shape[1] <= 4 or a_r.device != dev:
+            raise RuntimeError(f'ddk: {who} takes two tables [N_lig, D] and [N_rec, D] with D in 1..4 on one device; got {tuple(a_l.shape)} and {tuple(a_r.shape)}')
+        for name, t in (('lig_ptr', lig_ptr), ('rec_ptr', rec_ptr)):
+            if not torch.is_tensor(t) or t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous() or t.device != dev or t.shape != lig_ptr.shape:
+                raise RuntimeError(f'ddk: {who} takes {name} as a contiguous int64 vector [G + 1] on the device of the tables')
+        G = lig_ptr.shape[0] - 1
+        if not 1 <= G <= 65536:
+            raise RuntimeError(f'ddk: {who} takes 1..65536 graphs; got {G}')
+        T = float(temperature)
+        if not (T > 0 and T < float('inf')):
+            raise RuntimeError(f'ddk: {who} takes a positive finite temperature; got {temperature}')
+        return a_l, a_r, G, a_l.shape[1], T
+
+    def gumbel_softmax(self, logit_l, logit_r, lig_ptr, rec_ptr, temperature, seed, stream_ids, sample=0, draw=0):
+        """The straight-through Gumbel softmax of every graph and latent dimension over the graph's ligand nodes followed by its receptor nodes
+        (ddk_gumbel_softmax_batch; the noise is DDK_GUMBEL_LAYOUT of include/ddk.h): (out_l, out_r, y_l, y_r), ``out`` the one-hot sample carrying the soft
+        ``y``'s gradient, ``y`` what ``gumbel_softmax_backward`` reads.  ``lig_ptr`` / ``rec_ptr``: int64 [G + 1] on the device; ``stream_ids``: uint64-valued
+        [G] (a device int64 tensor holding the bit patterns, or host integers)."""
+        logit_l, logit_r, G, D, T = self._gumbel_operands(logit_l, logit_r, lig_ptr, rec_ptr, temperature, 'gumbel_softmax')
+        dev = logit_l.device
+        if torch.is_tensor(stream_ids):
+            st = stream_ids.to(dev).contiguous()
+            if st.dtype != torch.int64 or st.shape != (G,):
+                raise RuntimeError(f'ddk: gumbel_softmax takes stream_ids as {G} 64-bit integers')
+        else:
+            st = h2d_async(torch.from_numpy(np.ascontiguousarray([_u64(v, 'rng_stream') for v in stream_ids], dtype=np.uint64).view(np.int64)), dev)
+            if st.shape != (G,):
+                raise RuntimeError(f'ddk: gumbel_softmax takes {G} stream ids; got {st.shape[0]}')
+        for k, v in dict(draw=draw, sample=sample).items():
+            if not 0 <= int(v) < 1 << 31:
+                raise RuntimeError(f'ddk: gumbel_softmax: {k} = {v} must be a non-negative int32')
+        y_l, y_r, out_l, out_r = torch.empty_like(logit_l), torch.empty_like(logit_r), torch.empty_like(logit_l), torch.empty_like(logit_r)
+        self._check(self.L.ddk_gumbel_softmax_batch(self.h, G, D, _ptr(logit_l), logit_l.shape[0], _ptr(logit_r), logit_r.shape[0], _ptr(lig_ptr), _ptr(rec_ptr), T,
+                                                    C.c_uint64(_u64(seed, 'seed')), _ptr(st), int(sample), int(draw), _ptr(y_l), _ptr(y_r), _ptr(out_l),
+                                                    _ptr(out_r), _stream()), 'ddk_gumbel_softmax_batch')
+        return out_l, out_r, y_l, y_r
+
+    def gumbel_softmax_backward(self, y_l, y_r, lig_ptr, rec_ptr, temperature, grad_out_l, grad_out_r):
+        """(grad_logit_l, grad_logit_r) = y (g - sum g y) / T per graph and latent dimension from the saved ``y`` (ddk_gumbel_softmax_batch_backward)"""
+        y_l, y_r, G, D, T = self._gumbel_operands(y_l, y_r, lig_ptr, rec_ptr, temperature, 'gumbel_softmax_backward')
+        g_l, g_r = (_need_cuda(x).contiguous().float() for x in (grad_out_l, grad_out_r))
+        if g_l.shape != y_l.shape or g_r.shape != y_r.shape or g_l.device != y_l.device or g_r.device != y_l.device:
+            raise RuntimeError('ddk: gumbel_softmax_backward takes grad_out of the shapes of y on its device')
+        out_l, out_r = torch.empty_like(y_l), torch.empty_like(y_r)
+        self._check(self.L.ddk_gumbel_softmax_batch_backward(self.h, G, D, _ptr(y_l), y_l.shape[0], _ptr(y_r), y_r.shape[0], _ptr(lig_ptr), _ptr(rec_ptr), T,
+                                                             _ptr(g_l), _ptr(g_r), _ptr(out_l), _ptr(out_r), _stream()), 'ddk_gumbel_softmax_batch_backward')
+        return out_l, out_r
+
+    def latent_keep(self, seed, streams, rate, draw=0, sample=0):
+        """keep flag (1.0 / 0.0, float32 host array) of each complex of ``streams`` for noising ``draw``: the uniform of purpose RNG_LATENT_KEEP_PURPOSE
+        is at or above ``rate`` (ddk_rng_latent_keep; computed on the host, no kernel)"""
+        for k, v in dict(draw=draw, sample=sample).items():
+            if not -(1 << 31) <= int(v) < 1 << 31:
+                raise ValueError(f'ddk: {k} = {v} does not fit an int32')
+        st = np.ascontiguousarray([_u64(v, 'rng_stream') for v in streams], dtype=np.uint64)
+        out = np.empty(st.size, dtype=np.float32)
+        self._check(self.L.ddk_rng_latent_keep(self.h, C.c_uint64(_u64(seed, 'seed')), st.size, st.ctypes.data_as(C.c_void_p), int(sample), int(draw), float(rate),
+                                               out.ctypes.data_as(C.c_void_p)), 'ddk_rng_latent_keep')
+        return out
 
     def tp_weight_numel(self, layer):
         """W of conv layer ``layer``: the length of a FasterTensorProduct weight row (tensor_layers.py:56-63)."""

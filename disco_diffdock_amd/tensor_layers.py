@@ -28,11 +28,13 @@ Only the configurations the shipped score models use are implemented on the devi
 statistics (plain torch, ``_BatchNormParams.forward``) and the padded residual.  In ``.eval()`` it is the fused inference
 kernel (``ddk_conv_forward``), unchanged.  ``conv_stack`` trains the whole stack of them from the edge embedding with the
 same bits on every run.  In a head configuration the layer is ``fused_head_conv`` plus BatchNorm in training and in evaluation
-(``heads.ScoreHeads`` is the module on top); ``train_model.TrainableScoreModel`` assembles the whole model.  What still does not train: the
-latent-conditioned models, the all-atom / confidence irreps, any other ns / nv.
+(``heads.ScoreHeads`` is the module on top); ``train_model.TrainableScoreModel`` assembles the whole model.  The latent-conditioned (DisCo) score model trains
+through ``fused_edge_embedding``'s latent columns and ``ragged_gumbel_softmax``.  What still does not train: the AR predictor, the all-atom / confidence
+irreps, any other ns / nv.
 """
 import math
 
+import numpy as np
 import torch
 from torch import nn
 from torch.autograd.function import once_differentiable
@@ -421,6 +423,36 @@ class _EdgeEmbeddingFunction(torch.autograd.Function):
         return _grads_like(grads, fctx.meta) + (None,) * 11
 
 
+class _LatentEdgeEmbeddingFunction(torch.autograd.Function):
+    """ddk_eemb_latent_forward with ddk_eemb_latent_backward as its vector-Jacobian product: ``_EdgeEmbeddingFunction`` with the latent columns and the
+    unconditional embedding.  Saved for the backward: the operands it was given, the two latent tables and the node-sorted edge lists among them; nothing
+    per edge that the op made itself.  Gradients: the four parameters, ``uemb`` and the two latent tables (where both are one tensor the caller adds the
+    two), all without atomics: the same bits on every run."""
+
+    @staticmethod
+    def forward(fctx, w1, b1, w2, b2, uemb, lat_a, lat_b, unc_a, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, p, seed, zero_latent, graph):
+        ctx = _ctx_of(pos_a)
+        emb, sh = ctx.eemb_latent_forward(pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, b2, lat_a, lat_b, zero_latent, unc_a,
+                                          uemb, p, seed)
+        fctx.save_for_backward(w1, b1, w2, uemb, lat_a, lat_b, unc_a, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index)      # (b2 is not read by the backward)
+        fctx.ddk, fctx.scalars, fctx.graph = ctx, (start, stop, p, seed, zero_latent), graph
+        fctx.meta = [None if t is None else (t.shape, t.dtype) for t in (w1, b1, w2, b2, uemb, lat_a, lat_b)]
+        fctx.mark_non_differentiable(sh)
+        return emb, sh
+
+    @staticmethod
+    @once_differentiable
+    def backward(fctx, grad_emb, _grad_sh):
+        w1, b1, w2, uemb, lat_a, lat_b, unc_a, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index = fctx.saved_tensors
+        start, stop, p, seed, zero_latent = fctx.scalars
+        need = tuple(fctx.needs_input_grad[:7])
+        with torch.cuda.device(pos_a.device):
+            grads = fctx.ddk.eemb_latent_backward(pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, lat_a, lat_b, grad_emb,
+                                                  zero_latent, unc_a, uemb, p, seed, fctx.graph, need)
+        out = tuple(None if (g is None or m is None) else g.reshape(m[0]).to(m[1]) for g, m in zip(grads, fctx.meta))
+        return out + (None,) * 14
+
+
 def _smearing_range(expansion):
     """(start, stop) of a GaussianSmearing of 32 Gaussians whose ``offset`` and ``coeff`` are what the kernels restate from them (include/ddk.h); read
     back once per buffer and kept on the module"""
@@ -442,7 +474,8 @@ def _smearing_range(expansion):
     return cached[1]
 
 
-def fused_edge_embedding(mlp, expansion, pos_a, pos_b, edge_index, sig, sig_index, feat=None, seed=None):
+def fused_edge_embedding(mlp, expansion, pos_a, pos_b, edge_index, sig, sig_index, feat=None, seed=None, latent_a=None, latent_b=None, zero_latent=False,
+                         unconditional=None, unconditional_embedding=None, graph=None):
     """One edge group of the reference's embed in front of the conv stack (models/score_model.py:191-225) as one differentiable op:
     ``edge_emb = mlp(torch.cat([feat, sig[sig_index[edge_index[0]]], expansion(|vec|)], 1))`` and ``edge_sh`` = the first-order spherical harmonics of
     ``vec = pos_b[edge_index[1]] - pos_a[edge_index[0]]`` (component normalisation: ``[1 | sqrt3 vec / |vec|]``).  ``mlp``: the reference's
@@ -451,14 +484,39 @@ def fused_edge_embedding(mlp, expansion, pos_a, pos_b, edge_index, sig, sig_inde
     score matching: one that requires it raises.  Nothing wider than the outputs is stored per edge, forward or backward; the four parameters of ``mlp``
     get the same gradient bits on every run (no atomics).  Dropout: rate ``mlp[2].p`` while that module is in training mode, else none; the mask is a
     pure function of (``seed``, edge position, column), DDK_EEMB_MASK_LAYOUT of include/ddk.h; ``seed=None`` takes one draw from torch's default CPU
-    generator.  Returns (edge_emb [E, 24], edge_sh [E, 4]), fp32."""
+    generator.  Returns (edge_emb [E, 24], edge_sh [E, 4]), fp32.
+
+    The latent-conditioned (DisCo) model: ``latent_a`` [Na, L] and ``latent_b`` [Nb, L], 1 <= L <= 4, append ``[latent_a[edge_index[0]] |
+    latent_b[edge_index[1]]]`` to the row (the first Linear then takes K + 2 L columns); they may be one tensor and may require grad: their gradient is a
+    fixed-order sum over a node's edges (no atomics), the source sum + the destination sum where both are one tensor.  ``zero_latent=True`` (the cross
+    group, models/score_model.py:401) appends 2 L zero columns instead; it takes ``latent_a`` for L alone (or an int).  ``unconditional`` [Na] (no
+    gradient) with ``unconditional_embedding`` [1, 24] or [24] (a parameter) adds ``unconditional[edge_index[0]][:, None] * unconditional_embedding``.
+    ``graph``: ``Context.conv_graph(edge_index[0], edge_index[1], Nb, Na)`` where the caller has it (built here otherwise, when a latent needs its
+    gradient).  With none of these given the call is the plain op's, call for call."""
     if (not isinstance(mlp, nn.Sequential) or len(mlp) != 4 or not isinstance(mlp[0], nn.Linear) or not isinstance(mlp[1], nn.ReLU)
             or not isinstance(mlp[2], nn.Dropout) or not isinstance(mlp[3], nn.Linear) or mlp[0].bias is None or mlp[3].bias is None
             or mlp[0].out_features != 24 or (mlp[3].in_features, mlp[3].out_features) != (24, 24)):
         raise RuntimeError('ddk: fused_edge_embedding takes nn.Sequential(Linear(K, 24), ReLU, Dropout, Linear(24, 24)) with biases')
     K = 64 if feat is None else 68
-    if mlp[0].in_features != K:
-        raise RuntimeError(f'ddk: fused_edge_embedding: the first Linear takes {mlp[0].in_features} columns, the row has {K} (4 bond features with feat, 32 + 32)')
+    latent = latent_a is not None or latent_b is not None or zero_latent or unconditional is not None or unconditional_embedding is not None
+    L = 0
+    if latent:
+        if zero_latent:
+            L = int(latent_a) if isinstance(latent_a, int) else (latent_a.shape[1] if torch.is_tensor(latent_a) else (mlp[0].in_features - K) // 2)
+            latent_a = latent_b = None
+        else:
+            if not torch.is_tensor(latent_a) or not torch.is_tensor(latent_b) or latent_a.dim() != 2 or latent_b.dim() != 2 or latent_a.shape[1] != latent_b.shape[1]:
+                raise RuntimeError('ddk: fused_edge_embedding takes latent_a [Na, L] and latent_b [Nb, L] together (or zero_latent)')
+            L = latent_a.shape[1]
+        if not 1 <= L <= 4:
+            raise RuntimeError(f'ddk: fused_edge_embedding takes 1..4 latent columns per node; got {L}')
+        if (unconditional is None) != (unconditional_embedding is None):
+            raise RuntimeError('ddk: fused_edge_embedding takes unconditional and unconditional_embedding together')
+        if unconditional is not None and unconditional.requires_grad:
+            raise RuntimeError('ddk: fused_edge_embedding has no gradient for unconditional (a mask of graphs); detach it')
+    if mlp[0].in_features != K + 2 * L:
+        raise RuntimeError(f'ddk: fused_edge_embedding: the first Linear takes {mlp[0].in_features} columns, the row has {K + 2 * L} (4 bond features with feat, 32 + 32'
+                           + (f', 2 x {L} latent columns)' if L else ')'))
     if not pos_a.is_cuda:
         raise RuntimeError('ddk fused_edge_embedding runs on the GPU only (no CPU fallback)')
     if pos_a.requires_grad or pos_b.requires_grad:
@@ -477,9 +535,83 @@ def fused_edge_embedding(mlp, expansion, pos_a, pos_b, edge_index, sig, sig_inde
     operands = (pos_a.detach().float().contiguous(), pos_b.detach().float().contiguous(), idx_a, idx_b, None if feat is None else feat.float().contiguous(),
                 sig.float().contiguous(), sig_index.to(torch.int32).contiguous())
     w1, b1, w2, b2 = mlp[0].weight, mlp[0].bias, mlp[3].weight, mlp[3].bias
+    if latent:
+        uemb = None if unconditional_embedding is None else unconditional_embedding.reshape(-1)
+        unc = None if unconditional is None else unconditional.detach().float().reshape(-1).contiguous()
+        la, lb = latent_a, latent_b      # (one tensor on both sides: autograd adds the source sum and the destination sum, a commutative fp32 add)
+        diff = [t for t in (w1, b1, w2, b2, uemb, la, lb) if t is not None]
+        if torch.is_grad_enabled() and any(t.requires_grad for t in diff):
+            if graph is None and la is not None and (la.requires_grad or lb.requires_grad) and idx_a.shape[0] > 0:
+                graph = Context.conv_graph(idx_a, idx_b, pos_b.shape[0], pos_a.shape[0])
+            return _LatentEdgeEmbeddingFunction.apply(w1, b1, w2, b2, uemb, la, lb, unc, *operands, start, stop, p, int(seed), bool(zero_latent), graph)
+        return _ctx_of(pos_a).eemb_latent_forward(*operands, start, stop, w1, b1, w2, b2, la, lb, bool(zero_latent), unc, uemb, p, int(seed))
     if torch.is_grad_enabled() and any(t.requires_grad for t in (w1, b1, w2, b2)):
         return _EdgeEmbeddingFunction.apply(w1, b1, w2, b2, *operands, start, stop, p, int(seed))
     return _ctx_of(pos_a).eemb_forward(*operands, start, stop, w1, b1, w2, b2, p, int(seed))
+
+
+class _RaggedGumbelFunction(torch.autograd.Function):
+    """ddk_gumbel_softmax_batch with ddk_gumbel_softmax_batch_backward as its vector-Jacobian product; saved: the soft y of both sides and the two pointer
+    tables.  No atomics: the same bits on every run."""
+
+    @staticmethod
+    def forward(fctx, logit_l, logit_r, lig_ptr, rec_ptr, T, seed, stream_ids, sample, draw):
+        ctx = _ctx_of(logit_l)
+        out_l, out_r, y_l, y_r = ctx.gumbel_softmax(logit_l, logit_r, lig_ptr, rec_ptr, T, seed, stream_ids, sample, draw)
+        fctx.save_for_backward(y_l, y_r, lig_ptr, rec_ptr)
+        fctx.ddk, fctx.T = ctx, T
+        fctx.meta = [(t.shape, t.dtype) for t in (logit_l, logit_r)]
+        return out_l, out_r
+
+    @staticmethod
+    @once_differentiable
+    def backward(fctx, grad_l, grad_r):
+        y_l, y_r, lig_ptr, rec_ptr = fctx.saved_tensors
+        with torch.cuda.device(y_l.device):
+            grads = fctx.ddk.gumbel_softmax_backward(y_l, y_r, lig_ptr, rec_ptr, fctx.T, grad_l, grad_r)
+        return _grads_like(grads, fctx.meta) + (None,) * 7
+
+
+def _graph_ptrs(batches, G):
+    """the [G + 1] int64 prefixes of node-to-graph vectors whose nodes are grouped by graph in ascending order, and ONE read-back for all of them: per
+    vector (the largest descent between neighbours, the first entry, the last entry), as ``Context.conv_graph`` reads the extremes of its indices"""
+    ptrs, probes = [], []
+    for batch in batches:
+        batch = batch.long()
+        ptr = torch.zeros(G + 1, dtype=torch.int64, device=batch.device)
+        if batch.numel():
+            ptr[1:] = torch.cumsum(torch.bincount(batch.clamp(0, max(G - 1, 0)), minlength=G)[:G], 0)
+            descent = (batch[:-1] - batch[1:]).max() if batch.numel() > 1 else torch.zeros((), dtype=torch.int64, device=batch.device)
+            probes.append(torch.stack([descent, batch[0], batch[-1]]))
+        else:
+            probes.append(torch.zeros(3, dtype=torch.int64, device=batch.device))
+        ptrs.append(ptr)
+    return ptrs, torch.stack(probes).tolist()
+
+
+def ragged_gumbel_softmax(logit_l, logit_r, lig_batch, rec_batch, temperature, seed, stream_ids, sample=0, draw=0):
+    """The reference's per-graph straight-through Gumbel softmax over a graph's ligand and receptor nodes (latent_encoder.py:328-335,
+    pretrained_score_encoder.py:74-81 over models/layers.py:152-181: ``gumbel_softmax(cat([logit_l[lig_batch == g], logit_r[rec_batch == g]]).T, hard=True)``)
+    for the whole collated batch in one launch and with one read-back (the check of the two batch vectors), none per graph: ``logit_l`` [N_lig, D], ``logit_r`` [N_rec, D], D <= 4, ->
+    (latent_l [N_lig, D], latent_r [N_rec, D]): per graph and latent dimension a one-hot over the graph's nodes that carries the soft sample's gradient.
+    ``lig_batch`` / ``rec_batch``: the graph of a node, sorted; ``stream_ids`` [G]: ``runtime.stream_id`` of each graph's complex.  The noise is a pure
+    function of (``seed``, complex, ``sample``, ``draw``, d, node position), DDK_GUMBEL_LAYOUT of include/ddk.h: a graph draws the same noise in any
+    batch.  Differentiable in both logit tables, without atomics: the same bits on every run."""
+    if not logit_l.is_cuda:
+        raise RuntimeError('ddk ragged_gumbel_softmax runs on the GPU only (no CPU fallback)')
+    G = len(stream_ids)
+    if lig_batch.shape[0] != logit_l.shape[0] or rec_batch.shape[0] != logit_r.shape[0]:
+        raise RuntimeError('ddk: ragged_gumbel_softmax takes one batch entry per row of its logit tables')
+    (lig_ptr, rec_ptr), probes = _graph_ptrs((lig_batch.to(logit_l.device), rec_batch.to(logit_l.device)), G)      # the call's one read-back
+    for what, (descent, first, last) in zip(('lig_batch', 'rec_batch'), probes):
+        if descent > 0 or first < 0 or last >= G:
+            raise RuntimeError(f'ddk: ragged_gumbel_softmax takes {what} sorted by graph with entries in [0, {G})')
+    if not torch.is_tensor(stream_ids):
+        stream_ids = torch.from_numpy(np.array([int(v) & 0xFFFFFFFFFFFFFFFF for v in stream_ids], dtype=np.uint64).view(np.int64)).to(logit_l.device)
+    args = (logit_l, logit_r, lig_ptr, rec_ptr, float(temperature), int(seed), stream_ids, int(sample), int(draw))
+    if torch.is_grad_enabled() and (logit_l.requires_grad or logit_r.requires_grad):
+        return _RaggedGumbelFunction.apply(*args)
+    return _ctx_of(logit_l).gumbel_softmax(*args)[:2]
 
 
 class _HeadConvFunction(torch.autograd.Function):

@@ -9,7 +9,13 @@ checkpoint loads with ``strict=True`` and what was trained here loads into the i
 statistics and running buffers and switch dropout, as in the layers; in training every parameter gets the same gradient bits on every run for one seed.
 The inference class stays the fast path for sampling: this module is for fine-tuning.
 
-Not covered: the latent-conditioned (``latent_dim > 0``) DisCo and AR models, ``confidence_mode``, the all-atom model, any other ns / nv / sh_lmax."""
+The latent-conditioned DisCo score model (``latent_dim`` in 1..4, ``latent_vocab=1``, ``latent_droprate >= 0``) reads ``data['ligand' |
+'receptor'].latent_h`` (and ``.unconditional`` with a drop rate): the latent is appended to every node row and, as [source | destination], to every ligand
+and receptor edge row (zeros on cross edges), inside ``fused_edge_embedding``; its gradient reaches whatever made it (``LatentModelWrapper`` puts an encoder
+and ``ragged_gumbel_softmax`` in front), again without atomics.
+
+Not covered: the oracle latent encoder (TPEncoder), the AR predictor, ``latent_vocab > 1``, ``latent_cross_attention``, ``confidence_mode``, the all-atom
+model, any other ns / nv / sh_lmax."""
 import torch
 from torch import nn
 
@@ -81,12 +87,12 @@ class AtomEncoder(nn.Module):
     """models/layers.py:119-149 (the new AtomEncoder): one embedding table per categorical feature, summed, then a Linear over [sum | scalar features |
     sigma embedding].  The tables are read through ``gather_rows``: their gradient is a fixed-order segmented sum, not index_add_'s atomics."""
 
-    def __init__(self, emb_dim, feature_dims, sigma_embed_dim, lm_embedding_type=None):
+    def __init__(self, emb_dim, feature_dims, sigma_embed_dim, lm_embedding_type=None, latent_dim=0):
         super().__init__()
         self.atom_embedding_list = nn.ModuleList()
         self.num_categorical_features = len(feature_dims[0])
         lm = 1280 if lm_embedding_type == 'esm' else 0
-        self.additional_features_dim = feature_dims[1] + sigma_embed_dim + lm
+        self.additional_features_dim = feature_dims[1] + sigma_embed_dim + lm + latent_dim      # (the latent rides behind the sigma embedding: plain torch, autograd)
         for dim in feature_dims[0]:
             emb = nn.Embedding(dim, emb_dim)
             nn.init.xavier_uniform_(emb.weight.data)
@@ -106,7 +112,7 @@ class AtomEncoder(nn.Module):
 
 class TrainableScoreModel(nn.Module):
     """Constructor keywords follow ``score_model.TensorProductScoreModel`` (models/score_model.py:15-24 plus ``embedding_scale`` and ``sigma_limits``).
-    Supported: sh_lmax=1, ns=24, nv=6, latent_dim=0, the new AtomEncoder, 32-wide sigma and distance embeddings, batch_norm / no_torsion /
+    Supported: sh_lmax=1, ns=24, nv=6, latent_dim 0..4 with latent_vocab=1 and latent_droprate in [0, 1), the new AtomEncoder, 32-wide sigma and distance embeddings, batch_norm / no_torsion /
     dynamic_max_cross on or off, lm_embedding_type None or 'esm', 3..16 conv layers; anything else raises and names the option."""
 
     def __init__(self, t_to_sigma=None, device=None, timestep_emb_func=None, in_lig_edge_features=4, sigma_embed_dim=32, sh_lmax=2, ns=16, nv=4,
@@ -117,8 +123,10 @@ class TrainableScoreModel(nn.Module):
                  confidence_dropout=0, confidence_no_batchnorm=False, num_confidence_outputs=1, new_cross_attention=False, **unused):
         super().__init__()
         refused = [('sh_lmax', sh_lmax != 1, 'must be 1'), ('ns', ns != 24, 'must be 24'), ('nv', nv != 6, 'must be 6'),
-                   ('latent_dim', latent_dim != 0, 'must be 0: the latent-conditioned DisCo and AR models are not assembled'),
-                   ('latent_droprate', latent_droprate != 0, 'must be 0'), ('latent_cross_attention', bool(latent_cross_attention), 'is not implemented'),
+                   ('latent_dim', not 0 <= latent_dim <= 4, 'must be in 0..4'),
+                   ('latent_vocab', latent_dim > 0 and latent_vocab != 1, 'must be 1 whenever latent_dim > 0: the equivariant one-hot-over-nodes latent only'),
+                   ('latent_droprate', not 0.0 <= float(latent_droprate) < 1.0 or (latent_droprate > 0 and latent_dim == 0),
+                    'must be in [0, 1), and > 0 needs latent_dim > 0'), ('latent_cross_attention', bool(latent_cross_attention), 'is not implemented'),
                    ('new_cross_attention', bool(new_cross_attention), 'is not implemented'),
                    ('use_old_atom_encoder', bool(use_old_atom_encoder), 'is not implemented: the new AtomEncoder only'),
                    ('use_second_order_repr', bool(use_second_order_repr), 'is not implemented'),
@@ -140,13 +148,19 @@ class TrainableScoreModel(nn.Module):
         self.lig_max_radius, self.cross_max_distance = float(lig_max_radius), float(cross_max_distance)
         self.tr_sigma_min, self.tr_sigma_max = lim['tr_sigma_min'], lim['tr_sigma_max']
         self.timestep_emb_func = get_timestep_embedding('sinusoidal', sigma_embed_dim, embedding_scale)
+        self.latent_dim, self.latent_droprate = int(latent_dim), float(latent_droprate)
+        lat_e = 2 * self.latent_dim      # an edge row carries the latent of its source and of its destination (zeros on cross edges)
 
-        self.lig_node_embedding = AtomEncoder(ns, (LIG_FEATURE_DIMS, 0), sigma_embed_dim)
-        self.lig_edge_embedding = nn.Sequential(nn.Linear(in_lig_edge_features + sigma_embed_dim + distance_embed_dim, ns), nn.ReLU(), nn.Dropout(dropout),
+        self.lig_node_embedding = AtomEncoder(ns, (LIG_FEATURE_DIMS, 0), sigma_embed_dim, latent_dim=self.latent_dim)
+        self.lig_edge_embedding = nn.Sequential(nn.Linear(in_lig_edge_features + sigma_embed_dim + distance_embed_dim + lat_e, ns), nn.ReLU(), nn.Dropout(dropout),
                                                 nn.Linear(ns, ns))
-        self.rec_node_embedding = AtomEncoder(ns, (REC_RESIDUE_FEATURE_DIMS, 0), sigma_embed_dim, lm_embedding_type)
-        self.rec_edge_embedding = nn.Sequential(nn.Linear(sigma_embed_dim + distance_embed_dim, ns), nn.ReLU(), nn.Dropout(dropout), nn.Linear(ns, ns))
-        self.cross_edge_embedding = nn.Sequential(nn.Linear(sigma_embed_dim + cross_distance_embed_dim, ns), nn.ReLU(), nn.Dropout(dropout), nn.Linear(ns, ns))
+        self.rec_node_embedding = AtomEncoder(ns, (REC_RESIDUE_FEATURE_DIMS, 0), sigma_embed_dim, lm_embedding_type, latent_dim=self.latent_dim)
+        self.rec_edge_embedding = nn.Sequential(nn.Linear(sigma_embed_dim + distance_embed_dim + lat_e, ns), nn.ReLU(), nn.Dropout(dropout), nn.Linear(ns, ns))
+        self.cross_edge_embedding = nn.Sequential(nn.Linear(sigma_embed_dim + cross_distance_embed_dim + lat_e, ns), nn.ReLU(), nn.Dropout(dropout),
+                                                  nn.Linear(ns, ns))
+        if self.latent_droprate > 0:      # models/score_model.py:97-101: zeros at init
+            for k in ('lig_node', 'rec_node', 'lig_edge', 'rec_edge', 'cross_edge'):
+                setattr(self, f'{k}_unconditional_embedding', nn.Parameter(torch.zeros(1, ns)))
         self.rec_distance_expansion = GaussianSmearing(0.0, rec_max_radius, distance_embed_dim)
         self.cross_distance_expansion = GaussianSmearing(0.0, cross_max_distance, cross_distance_embed_dim)
 
@@ -209,18 +223,64 @@ class TrainableScoreModel(nn.Module):
             seed = _draw_seed()
         seeds = [None if seed is None else _layer_seed(seed, len(self.conv_layers) + g) for g in range(3)]      # (the conv layers take 0 .. L - 1)
 
-        lig_node_attr = self.lig_node_embedding(lig.x.to(dev).long(), sig[lig_batch])
-        rec_node_attr = self.rec_node_embedding(rec_x[:, :n_cat].long(), torch.cat([rec_x[:, n_cat:].float(), sig[rec_batch]], 1))
-        lig_emb, lig_sh = fused_edge_embedding(self.lig_edge_embedding, self.lig_distance_expansion, lig_pos, lig_pos, lig_ei, sig, lig_idx, feat=feat,
-                                               seed=seeds[0])
-        lr_emb, lr_sh = fused_edge_embedding(self.cross_edge_embedding, self.cross_distance_expansion, lig_pos, rec_pos, cross_ei, sig, lig_idx, seed=seeds[1])
-        rec_emb, rec_sh = fused_edge_embedding(self.rec_edge_embedding, self.rec_distance_expansion, rec_pos, rec_pos, rec_ei, sig, rec_idx, seed=seeds[2])
+        if self.latent_dim:
+            lig_node_attr, rec_node_attr, (lig_emb, lig_sh), (lr_emb, lr_sh), (rec_emb, rec_sh) = self._embed_latent(
+                data, sig, lig_pos, rec_pos, lig_batch, rec_batch, lig_idx, rec_idx, lig_ei, cross_ei, rec_ei, feat, rec_x, n_cat, seeds)
+        else:
+            lig_node_attr = self.lig_node_embedding(lig.x.to(dev).long(), sig[lig_batch])
+            rec_node_attr = self.rec_node_embedding(rec_x[:, :n_cat].long(), torch.cat([rec_x[:, n_cat:].float(), sig[rec_batch]], 1))
+            lig_emb, lig_sh = fused_edge_embedding(self.lig_edge_embedding, self.lig_distance_expansion, lig_pos, lig_pos, lig_ei, sig, lig_idx, feat=feat,
+                                                   seed=seeds[0])
+            lr_emb, lr_sh = fused_edge_embedding(self.cross_edge_embedding, self.cross_distance_expansion, lig_pos, rec_pos, cross_ei, sig, lig_idx, seed=seeds[1])
+            rec_emb, rec_sh = fused_edge_embedding(self.rec_edge_embedding, self.rec_distance_expansion, rec_pos, rec_pos, rec_ei, sig, rec_idx, seed=seeds[2])
 
         node_attr = torch.cat([lig_node_attr, rec_node_attr], dim=0)
         edge_emb = torch.cat([lig_emb, lr_emb, rec_emb, lr_emb], dim=0)      # the cross embedding is computed once and serves both directions
         edge_sh = torch.cat([lig_sh, lr_sh, rec_sh, lr_sh], dim=0)
         node_attr = conv_stack(self.conv_layers, node_attr, edge_index, edge_emb, group_sizes, edge_sh, seed=seed)
         return node_attr[:n_lig], node_attr[n_lig:]
+
+    def _latent_inputs(self, data, dev):
+        """(latent_l [N_lig, L], latent_r [N_rec, L], unconditional_l [N_lig, 1] or None, unconditional_r) of a batch; a missing one raises by name"""
+        out = []
+        for side in ('ligand', 'receptor'):
+            h = getattr(data[side], 'latent_h', None)
+            if h is None:
+                raise RuntimeError(f"ddk: TrainableScoreModel(latent_dim={self.latent_dim}) reads data['{side}'].latent_h; the batch has none")
+            h = h.to(dev).float()
+            if h.dim() != 2 or h.shape != (data[side].pos.shape[0], self.latent_dim):
+                raise RuntimeError(f"ddk: data['{side}'].latent_h must be [nodes, latent_dim] = {(data[side].pos.shape[0], self.latent_dim)}; got {tuple(h.shape)}")
+            out.append(h)
+        for side in ('ligand', 'receptor'):
+            u = None
+            if self.latent_droprate > 0:
+                u = getattr(data[side], 'unconditional', None)
+                if u is None:
+                    raise RuntimeError(f"ddk: TrainableScoreModel(latent_droprate={self.latent_droprate}) reads data['{side}'].unconditional; the batch has none")
+                u = u.to(dev).float().detach().reshape(-1, 1)
+                if u.shape[0] != data[side].pos.shape[0]:
+                    raise RuntimeError(f"ddk: data['{side}'].unconditional must hold one value per node; got {tuple(u.shape)}")
+            out.append(u)
+        return out
+
+    def _embed_latent(self, data, sig, lig_pos, rec_pos, lig_batch, rec_batch, lig_idx, rec_idx, lig_ei, cross_ei, rec_ei, feat, rec_x, n_cat, seeds):
+        """the node and edge embeddings of the latent-conditioned model (models/score_model.py:191-215, 310-408 with latent_h): node rows
+        [x | sig | latent] (+ unconditional * node_unconditional_embedding), edge rows with [latent[src] | latent[dst]] inside the fused op"""
+        dev = lig_pos.device
+        lat_l, lat_r, unc_l, unc_r = self._latent_inputs(data, dev)
+        lig_node_attr = self.lig_node_embedding(data['ligand'].x.to(dev).long(), torch.cat([sig[lig_batch], lat_l], 1))
+        rec_node_attr = self.rec_node_embedding(rec_x[:, :n_cat].long(), torch.cat([rec_x[:, n_cat:].float(), sig[rec_batch], lat_r], 1))
+        unc = lambda u, name: {} if u is None else dict(unconditional=u.reshape(-1), unconditional_embedding=getattr(self, f'{name}_unconditional_embedding'))
+        if unc_l is not None:
+            lig_node_attr = lig_node_attr + unc_l * self.lig_node_unconditional_embedding
+            rec_node_attr = rec_node_attr + unc_r * self.rec_node_unconditional_embedding
+        lig = fused_edge_embedding(self.lig_edge_embedding, self.lig_distance_expansion, lig_pos, lig_pos, lig_ei, sig, lig_idx, feat=feat, seed=seeds[0],
+                                   latent_a=lat_l, latent_b=lat_l, **unc(unc_l, 'lig_edge'))
+        cross = fused_edge_embedding(self.cross_edge_embedding, self.cross_distance_expansion, lig_pos, rec_pos, cross_ei, sig, lig_idx, seed=seeds[1],
+                                     latent_a=self.latent_dim, zero_latent=True, **unc(unc_l, 'cross_edge'))
+        rec = fused_edge_embedding(self.rec_edge_embedding, self.rec_distance_expansion, rec_pos, rec_pos, rec_ei, sig, rec_idx, seed=seeds[2],
+                                   latent_a=lat_r, latent_b=lat_r, **unc(unc_r, 'rec_edge'))
+        return lig_node_attr, rec_node_attr, lig, cross, rec
 
     def forward(self, data, seed=None):
         """``data``: a collated batch in the reference's layout (``data['ligand'].x / .pos / .batch / .edge_mask``, ``data['ligand', 'ligand'].edge_index /
@@ -233,3 +293,50 @@ class TrainableScoreModel(nn.Module):
         complex_t = {k: data.complex_t[k].to(dev).float() for k in ('tr', 'rot', 'tor')}
         edge_mask = None if self.no_torsion else lig.edge_mask.to(dev)
         return self._heads(lig_node_attr, lig.pos, lig.batch.to(dev), data['ligand', 'ligand'].edge_index.to(dev), edge_mask, complex_t)
+
+
+class LatentModelWrapper(nn.Module):
+    """The tuple branch of the reference's ``ModelWrapper.forward`` (models/model_classes.py:62-85) for training: ``encoder(data)`` -> (latent_l [N_lig, L],
+    latent_r [N_rec, L]) (any module; ``tensor_layers.ragged_gumbel_softmax`` is the sampling step the reference's encoders end in), the per-graph keep mask
+    of classifier-free guidance, then the score model on the batch with ``latent_h`` and ``unconditional`` set:
+
+        latent *= keep[batch][:, None]        unconditional = 1 - keep[batch]            keep [B] in {0, 1}; latent_droprate == 0: all ones, no unconditional
+
+    ``forward(data, seed=None, keep=None)``: ``keep`` as given (``training.draw_latent_keep`` makes a seeded one, ``training.train_epoch`` passes it), else
+    drawn with ``torch.bernoulli(1 - latent_droprate)`` as the reference does, in ``.train()`` and in ``.eval()`` alike (pass ``keep=torch.ones(B)``
+    for a conditional evaluation).  ``training_latent_temperature`` is set on the encoder as
+    ``encoder.latent_temperature`` before every call, as the reference does.  ``ctx`` / ``no_torsion`` are the score model's, so ``training.noise_batch`` and ``loss_function`` take the
+    wrapper where they take the model."""
+
+    def __init__(self, encoder, score_model, training_latent_temperature=1.0, latent_droprate=0.0):
+        super().__init__()
+        if not isinstance(score_model, TrainableScoreModel) or score_model.latent_dim < 1:
+            raise RuntimeError('ddk: LatentModelWrapper takes a TrainableScoreModel with latent_dim > 0')
+        if float(latent_droprate) != score_model.latent_droprate:
+            raise RuntimeError(f'ddk: LatentModelWrapper: latent_droprate = {latent_droprate}, the score model was built with {score_model.latent_droprate}')
+        self.encoder, self.score_model = encoder, score_model
+        self.training_latent_temperature, self.latent_droprate = float(training_latent_temperature), float(latent_droprate)
+
+    @property
+    def ctx(self):
+        return self.score_model.ctx
+
+    @property
+    def no_torsion(self):
+        return self.score_model.no_torsion
+
+    def forward(self, data, seed=None, keep=None):
+        self.encoder.latent_temperature = self.training_latent_temperature      # (as the reference hands it over)
+        latent_l, latent_r = self.encoder(data)
+        dev, B = latent_l.device, int(data.num_graphs)
+        lig_batch, rec_batch = data['ligand'].batch.to(dev).long(), data['receptor'].batch.to(dev).long()
+        if self.latent_droprate > 0:
+            if keep is None:
+                keep = torch.bernoulli(torch.full((B,), 1.0 - self.latent_droprate))      # (in .eval() too, as the reference's wrapper)
+            keep = torch.as_tensor(keep, dtype=torch.float32).reshape(-1).to(dev)
+            if keep.shape[0] != B:
+                raise RuntimeError(f'ddk: LatentModelWrapper takes keep [B] = {B} values; got {keep.shape[0]}')
+            latent_l, latent_r = latent_l * keep[lig_batch][:, None], latent_r * keep[rec_batch][:, None]
+            data['ligand'].unconditional, data['receptor'].unconditional = (1 - keep[lig_batch])[:, None], (1 - keep[rec_batch])[:, None]
+        data['ligand'].latent_h, data['receptor'].latent_h = latent_l, latent_r
+        return self.score_model(data, seed=seed)

@@ -107,6 +107,24 @@ def draw_times(names, seed, draw, alpha=1, beta=1):
     return _host_ctx().forward_times(seed, [stream_id(n) for n in names], draw=draw)
 
 
+def draw_latent_keep(complexes, rate, seed, draw, samples=None):
+    """The keep flags of the latent dropout (classifier-free guidance training, models/model_classes.py:70-76) for one batch: a float32 host array [G] of
+    1.0 / 0.0, complex g kept iff the uniform of generator purpose 12 for (seed, stream_id(name_g), samples[g], draw) is at or above ``rate``
+    (ddk_rng_latent_keep; computed on the host): a pure function of (name, seed, draw, sample), whatever the batch."""
+    names = [c.get('name') if hasattr(c, 'get') else c for c in complexes]
+    if any(n is None for n in names):
+        raise ValueError('ddk: draw_latent_keep needs complexes with a name (the stream id is runtime.stream_id(name))')
+    samples = [0] * len(names) if samples is None else [int(s) for s in samples]
+    if len(samples) != len(names):
+        raise ValueError(f'ddk: draw_latent_keep: samples must hold one index per complex ({len(names)}), got {len(samples)}')
+    ctx = _host_ctx()
+    out = np.empty(len(names), np.float32)
+    for s in sorted(set(samples)):      # (one call per distinct sample index: usually one)
+        at = [i for i, v in enumerate(samples) if v == s]
+        out[at] = ctx.latent_keep(seed, [stream_id(names[i]) for i in at], rate, draw=draw, sample=s)
+    return out
+
+
 def _splitmix64(x):
     x = (x + 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
     z = x
@@ -410,11 +428,14 @@ def train_epoch(model, complexes, optimizer, batch_size, seed, epoch, ema=None, 
     visited in the order ``epoch_permutation(len(complexes), seed, epoch)`` in batches of ``batch_size``; complex i is noised at ``draw_times(names, seed,
     draw=epoch)[i]`` with draw = epoch, so every epoch sees every complex at a new time and a new noise, and the whole epoch is a pure function of (the
     model's state, complexes, seed, epoch).  Per batch: ``noise_batch`` -> ``model(data, seed=...)`` -> ``loss_function`` -> ``backward`` ->
-    ``optimizer.step()`` -> ``ema.update``.  A batch of one graph is skipped, as in the reference (BatchNorm needs two).  The seven meters are added up on
+    ``optimizer.step()`` -> ``ema.update``.  A ``train_model.LatentModelWrapper`` with a drop rate gets ``keep=draw_latent_keep(batch, rate, seed, epoch)``.
+    A batch of one graph is skipped, as in the reference (BatchNorm needs two).  The seven meters are added up on
     the device and read back ONCE at the end; returns the reference's summary, {'loss', 'tr_loss', ...: the mean over the batches run} (NaN if none ran).
     The reference's out-of-memory loop, which retries a batch at 0.8 of its size, is not reproduced: an out-of-memory error is raised."""
     ctx = _ctx_of(model)
     model.train()
+    from .train_model import LatentModelWrapper      # (here: train_model imports the layers, which import nothing of this module)
+    latent = isinstance(model, LatentModelWrapper) and model.latent_droprate > 0
     order = epoch_permutation(len(complexes), seed, epoch)
     times = draw_times([c.get('name') if hasattr(c, 'get') else None for c in complexes], seed, epoch) if complexes else np.zeros(0, np.float32)
     total, ran = torch.zeros(len(TRAIN_METERS), dtype=torch.float64, device=torch.device('cuda', ctx.device)), 0
@@ -427,7 +448,10 @@ def train_epoch(model, complexes, optimizer, batch_size, seed, epoch, ema=None, 
         step_seed = _step_seed(seed, epoch, step)
         with torch.random.fork_rng(devices=[ctx.device]):      # the heads' nn.Dropout layers draw from torch's generators: seeded per step, then put back
             torch.manual_seed(step_seed)
-            tr_pred, rot_pred, tor_pred = model(data, seed=step_seed)
+            if latent:
+                tr_pred, rot_pred, tor_pred = model(data, seed=step_seed, keep=draw_latent_keep([complexes[i] for i in ids], model.latent_droprate, seed, epoch))
+            else:
+                tr_pred, rot_pred, tor_pred = model(data, seed=step_seed)
         out = loss_function(tr_pred, rot_pred, tor_pred, targets, model, tr_weight=tr_weight, rot_weight=rot_weight, tor_weight=tor_weight)
         out[0].sum().backward()
         optimizer.step()

@@ -298,6 +298,70 @@ int ddk_eemb_backward(ddk_ctx* ctx, const float* pos_a, int64_t n_a, const float
 /* Bytes of ddk_eemb_backward's workspace: a function of its arguments alone; -1 for K other than 64 and 68, E < 0 or E >= 2^31.  Host function, no context. */
 int64_t ddk_eemb_workspace(int64_t E, int32_t K);
 
+/* ---- The edge embeddings of the latent-conditioned (DisCo) score model, latent_dim = L in 1..4, latent_vocab = 1 (models/score_model.py:352-408 of the
+ *      reference): ddk_eemb_forward with 2 L more columns behind the smearing and the unconditional embedding added to the output.  With ia = idx_a[e],
+ *      ib = idx_b[e]:
+ *        row       = [ feat[e] | sig[sig_index[ia]] | smearing(d) | lat_a[ia, 0:L] | lat_b[ib, 0:L] ]                K = F + 64 + 2 L;  w1 [24, K]
+ *        hid, emb  as ddk_eemb_forward: the pre-activation's fmaf chain runs on over the 2 L new columns in ascending order; the mask is DDK_EEMB_MASK_LAYOUT's
+ *        emb[e, o] = fmaf(unc_a[ia], uemb[o], emb[e, o])                                                             only where unc_a != NULL
+ *      lat_a [n_a, L], lat_b [n_b, L]: node tables (they may be one table), unc_a [n_a]: the node's `unconditional` value (any float), uemb [24]: DEVICE,
+ *      fp32, contiguous, the two tables 16-byte aligned.  zero_latent != 0 (the cross group): the row holds zeros in the 2 L columns, lat_a and lat_b are not
+ *      read and may be NULL.  unc_a != NULL needs uemb.  Everything else as ddk_eemb_forward; with all-zero latents and no unconditional term emb has the
+ *      bits of ddk_eemb_forward with w1[:, 0:K - 2 L] (fmaf(w, 0, acc) == acc for finite w). */
+int ddk_eemb_latent_forward(ddk_ctx* ctx, const float* pos_a, int64_t n_a, const float* pos_b, int64_t n_b, const int32_t* idx_a, const int32_t* idx_b,
+                            const float* feat, int32_t F, const float* sig, int64_t n_sig, const int32_t* sig_index, float start, float stop, int32_t n_gauss,
+                            const float* w1, const float* b1, const float* w2, const float* b2, float p, uint64_t seed, const float* lat_a, const float* lat_b,
+                            int32_t L, int32_t zero_latent, const float* unc_a, const float* uemb, int64_t E, float* emb, float* sh, void* stream);
+
+/* VJP of ddk_eemb_latent_forward: the four parameter gradients of ddk_eemb_backward (grad_w1 [24, K] with the 2 L latent columns; exact zeros there with
+ * zero_latent), and because the latent DOES carry a gradient (the straight-through Gumbel softmax in front of it):
+ *   grad_uemb [24]      = sum_e unc_a[ia] grad_emb[e, :], one more column of the slice images: an fmaf chain over the slice's edges in ascending order, the
+ *                         images added in slice order; zeros where unc_a == NULL
+ *   glat[e, j]          = fmaf chain over c ascending, from 0, of gpre[e, c] w1[c, F + 64 + j], j < 2 L: per-edge rows in the workspace, two planes [E, L]
+ *   grad_lat_a [n_a, L] = the rows glat[e, 0:L] of the edges with idx_a[e] == n, added in ascending e (the first row starts the sum); grad_lat_b [n_b, L] the
+ *                         same over glat[e, L:2 L] and idx_b.  order_a / ptr_a and order_b / ptr_b: the node-sorted edge lists of idx_a and idx_b (int32 [E],
+ *                         int64 [n + 1], as ddk_seg_sum takes them; TRUSTED; needed only for the side whose gradient is asked for).  A node without edges
+ *                         gets 0; with zero_latent both get zeros.  Where lat_a and lat_b are one table its gradient is grad_lat_a + grad_lat_b.
+ * Each of the seven outputs may be NULL (not computed); all NULL is DDK_ERR_INVALID.  Everything is recomputed from the coordinates and the seed; the bits do
+ * not depend on the subset asked for.  workspace: ddk_eemb_latent_workspace(E, K, L) bytes, needed when E > 0: the images, the [E, 2 L] rows, nothing wider.
+ * E == 0: the outputs asked for are written as zeros, no kernel is launched.  No atomics. */
+int ddk_eemb_latent_backward(ddk_ctx* ctx, const float* pos_a, int64_t n_a, const float* pos_b, int64_t n_b, const int32_t* idx_a, const int32_t* idx_b,
+                             const float* feat, int32_t F, const float* sig, int64_t n_sig, const int32_t* sig_index, float start, float stop, int32_t n_gauss,
+                             const float* w1, const float* b1, const float* w2, const float* b2, float p, uint64_t seed, const float* lat_a, const float* lat_b,
+                             int32_t L, int32_t zero_latent, const float* unc_a, const float* uemb, const int32_t* order_a, const int64_t* ptr_a,
+                             const int32_t* order_b, const int64_t* ptr_b, const float* grad_emb, int64_t E, float* grad_w1, float* grad_b1, float* grad_w2,
+                             float* grad_b2, float* grad_uemb, float* grad_lat_a, float* grad_lat_b, void* workspace, void* stream);
+
+/* Bytes of ddk_eemb_latent_backward's workspace; -1 for L outside 1..4, K other than 64 + 2 L and 68 + 2 L, E < 0 or E >= 2^31.  Host function, no context. */
+int64_t ddk_eemb_latent_workspace(int64_t E, int32_t K, int32_t L);
+
+/* ---- The ragged straight-through Gumbel softmax that makes the latent of a collated batch (latent_encoder.py:328-335 and pretrained_score_encoder.py:74-81
+ *      of the reference, over models/layers.py:152-181): per graph g and latent dimension d, over the graph's ligand nodes followed by its receptor nodes
+ *      (position pos = 0 .. n_g - 1):
+ *        gum = -logf(-logf(u + 1e-20f) + 1e-20f)     z = (logit + gum) / T     y = softmax(z) (maximum subtracted)     out = (hard - y) + y in fp32,
+ *        hard = 1 at the LOWEST position of the maximum of y, else 0.  The sum of the softmax in a fixed order: thread t of 256 adds the positions of the quads
+ *        t, t + 256, ... (four positions each) in ascending order from 0, the partials by a halving tree.
+ *      logit_l / y_l / out_l [n_lig, D], logit_r / y_r / out_r [n_rec, D]: DEVICE, fp32, contiguous; lig_ptr, rec_ptr: DEVICE int64 [G + 1], graph g owns the
+ *      rows ptr[g] .. ptr[g + 1] - 1 (a pair that is no range of its table: the graph is left unwritten); stream_id: DEVICE uint64 [G].  y is saved for the
+ *      backward:  grad_logit = y * (grad_out - sum grad_out y) / T  with the sum in the same order.  One launch each, one workgroup per (g, d), no atomics.
+ *      THE NOISE is a layout contract: for a given DDK_GUMBEL_LAYOUT it never changes.  Generator purpose 13 of DDK_RNG_LAYOUT 1 with counter (stream_id[g],
+ *      sample, 13 << 28 | draw << 8 | d) yields four words; words 0 and 1 are the KEY of a second Philox4x32-10 whose counter (pos / 4, 0, 0, DDK_GUMBEL_TAG)
+ *      gives position pos the word pos % 4; u = (word >> 8) * 2^-24.  A graph's noise is a pure function of (seed, complex, sample, draw, d, pos), whatever
+ *      the batch; no existing purpose is touched; no node limit.  Limits: 1 <= G <= 65536, 1 <= D <= 4, 0 <= draw < 2^20, sample >= 0, T > 0 and finite.
+ *
+ *      ddk_rng_latent_keep: the per-complex keep flag of the latent dropout (classifier-free guidance training), keep_out[i] = (u >= rate) as 1.0f / 0.0f with u
+ *      the uniform of purpose 12 for (seed, stream_id[i], sample, draw), block 0, word 0.  A HOST function as ddk_rng_forward_times. */
+#define DDK_GUMBEL_LAYOUT 1
+#define DDK_GUMBEL_TAG 0x47554D42u      /* "GUMB" */
+int ddk_gumbel_softmax_batch(ddk_ctx* ctx, int32_t G, int32_t D, const float* logit_l, int64_t n_lig, const float* logit_r, int64_t n_rec,
+                             const int64_t* lig_ptr, const int64_t* rec_ptr, float T, uint64_t seed, const uint64_t* stream_id /* DEVICE [G] */, int32_t sample,
+                             int32_t draw, float* y_l, float* y_r, float* out_l, float* out_r, void* stream);
+int ddk_gumbel_softmax_batch_backward(ddk_ctx* ctx, int32_t G, int32_t D, const float* y_l, int64_t n_lig, const float* y_r, int64_t n_rec,
+                                      const int64_t* lig_ptr, const int64_t* rec_ptr, float T, const float* grad_out_l, const float* grad_out_r,
+                                      float* grad_logit_l, float* grad_logit_r, void* stream);
+int ddk_rng_latent_keep(ddk_ctx* ctx, uint64_t seed, int32_t n, const uint64_t* stream_id /* HOST [n] */, int32_t sample, int32_t draw, float rate,
+                        float* keep_out /* HOST [n] */);
+
 /* The fixed-order segmented sum the radial conv and the head convs add a node's rows with (rtp_seg_kernel of csrc/k_rtp.hip), on its own: the backward of
  * a gather x[index].  nodes[n, :] = rows[order[ptr[n]], :] + rows[order[ptr[n] + 1], :] + ... + rows[order[ptr[n + 1] - 1], :], added in that order, one
  * thread per (node, column); a node without rows: exact zeros.  rows [*, D], nodes [n_nodes, D]: DEVICE, fp32, contiguous, 1 <= D <= 128; order: int32,
@@ -577,6 +641,8 @@ int ddk_ligand_transformation_mask(ddk_ctx* ctx, int32_t n_lig, const int32_t* b
  *                                                      word 2 -> the forced crossover index, word 3 OF MEMBER 0 -> the island's mutation factor;
  *                                                      the crossover uniform of component d is word d % 4 of block 1 + d / 4
  *                11 forward time (ddk_rng_forward_times below)   step = the draw index, block 0, word 0: t = the uniform u
+ *                12 latent keep (ddk_rng_latent_keep above)      step = the draw index, block 0, word 0: keep iff u >= rate
+ *                13 Gumbel noise (DDK_GUMBEL_LAYOUT above)       step = the draw index, block = the latent dimension d: words 0, 1 key the per-node generator
  *      Words -> draws, in fp32, every operation as written:
  *        uniform      u = (x >> 8) * 2^-24: in [0, 1), exact
  *        torsion      (float)pi * (2u - 1): the inner term is exact, one rounding
