@@ -219,34 +219,54 @@ static int check_launchable(ddk_ctx* ctx, int32_t layer) {
   return DDK_OK;
 }
 
-// what the four tensor-product entries check first: a context that can launch, and a layer that has one of the kernels' shapes (a guard: ddk_create
-// admits ns = 24, nv = 6 only).  Asked BEFORE the launch, so that an invalid-value error of the launch itself is reported as what it is
-static int check_tp_launchable(ddk_ctx* ctx, const char* who, int32_t layer) {
+// what the six tensor-product entries check first: a context that can launch, and a `layer` that names one of the kernels' shapes: conv layer `layer` of
+// the context (ddk_create admits ns = 24, nv = 6 only), or DDK_TP_NV4 + l, layer l of the ns = 24 / nv = 4 family, which no context holds: its
+// ConvLayerDev is the static shape-only table of k_tp_shape.h.  *L: the layer to launch on.  Asked BEFORE the launch, so that an invalid-value error of
+// the launch itself is reported as what it is
+static const char* const TP_FAMILIES = "0 .. num_conv_layers - 1 of the context (24x0e [+ 6x1o [+ 6x1e [+ 24x0o]]] -> the next entry) or DDK_TP_NV4 + 0..4 "
+                                       "(24x0e [+ 4x1o [+ 4x1e [+ 24x0o]]] -> the next entry)";
+static int check_tp_launchable(ddk_ctx* ctx, const char* who, int32_t layer, const ConvLayerDev** L) {
+  if (tp_is_nv4_id(layer)) {
+    int rc = check_launchable(ctx, 0);
+    if (rc) return rc;
+    // a context that holds a conv layer of this index (more than eight layers) ran ITS layer under this id before the second family existed: refused, not reinterpreted
+    if (layer < (int)ctx->conv.size())
+      return fail(ctx, DDK_ERR_INVALID, std::string(who) + ": this context has a conv layer " + std::to_string(layer) + ", and the id is DDK_TP_NV4 + " +
+                  std::to_string(layer - TP_NV4) + " of the nv = 4 family: ask for layer 3, which has the shape of every later layer, or use a context "
+                  "with at most eight conv layers for the nv = 4 shapes");
+    *L = &tp_family_layer(layer);
+    return DDK_OK;
+  }
+  if (ctx && !ctx->host_only && ctx->finalized && (layer < 0 || layer >= (int)ctx->conv.size()))
+    return fail(ctx, DDK_ERR_INVALID, std::string(who) + ": layer out of range: it is " + TP_FAMILIES);
   int rc = check_launchable(ctx, layer);
   if (rc) return rc;
   if (tp_shape_index(ctx->conv[layer]) < 0)
-    return fail(ctx, DDK_ERR_INVALID, std::string(who) + ": the layer's irreps are not one of the four conv-layer shapes of this model family (24x0e [+ 6x1o [+ 6x1e [+ 24x0o]]] -> the next entry)");
+    return fail(ctx, DDK_ERR_INVALID, std::string(who) + ": the layer's irreps are not one of the conv-layer shapes of the two families: " + TP_FAMILIES);
+  *L = &ctx->conv[layer];
   return DDK_OK;
 }
 
 int ddk_tp_forward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float* sh, const float* w, int64_t E,
                    float* out, void* stream) {
-  int rc = check_tp_launchable(ctx, "ddk_tp_forward", layer);
+  const ConvLayerDev* L = nullptr;
+  int rc = check_tp_launchable(ctx, "ddk_tp_forward", layer, &L);
   if (rc) return rc;
-  hipError_t e = launch_tp_forward(ctx->conv[layer], x_dst, sh, w, E, out, (hipStream_t)stream);
+  hipError_t e = launch_tp_forward(*L, x_dst, sh, w, E, out, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(ctx, e, "tp_forward launch");
   return DDK_OK;
 }
 
 int ddk_tp_backward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float* sh, const float* w, const float* grad_out, int64_t E,
                     float* grad_x, float* grad_sh, float* grad_w, void* stream) {
-  int rc = check_tp_launchable(ctx, "ddk_tp_backward", layer);
+  const ConvLayerDev* L = nullptr;
+  int rc = check_tp_launchable(ctx, "ddk_tp_backward", layer, &L);
   if (rc) return rc;
   if (!grad_x && !grad_sh && !grad_w) return fail(ctx, DDK_ERR_INVALID, "ddk_tp_backward: no gradient requested (grad_x, grad_sh and grad_w are all null)");
   if (E < 0) return fail(ctx, DDK_ERR_INVALID, "ddk_tp_backward: negative edge count");
   if (E > 0 && (!x_dst || !sh || !grad_out || (!w && (grad_x || grad_sh))))
     return fail(ctx, DDK_ERR_INVALID, "ddk_tp_backward: null operand (w may be null only when grad_w alone is requested)");
-  hipError_t e = launch_tp_backward(ctx->conv[layer], x_dst, sh, w, grad_out, E, grad_x, grad_sh, grad_w, (hipStream_t)stream);
+  hipError_t e = launch_tp_backward(*L, x_dst, sh, w, grad_out, E, grad_x, grad_sh, grad_w, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(ctx, e, "tp_backward launch");
   return DDK_OK;
 }
@@ -277,20 +297,21 @@ static int check_conv_graph(ddk_ctx* ctx, const char* who, const RconvGraph& gr,
 }
 
 // the checks the two radial-tensor-product entries share: layer, group table, edge count
-static int rtp_check(ddk_ctx* ctx, const char* who, int32_t layer, const int64_t* go, int32_t n_groups, int64_t E) {
-  int rc = check_tp_launchable(ctx, who, layer);
+static int rtp_check(ddk_ctx* ctx, const char* who, int32_t layer, const int64_t* go, int32_t n_groups, int64_t E, const ConvLayerDev** L) {
+  int rc = check_tp_launchable(ctx, who, layer, L);
   if (rc) return rc;
-  if (layer > 4) return fail(ctx, DDK_ERR_INVALID, std::string(who) + ": layer out of range (0..4)");
+  if (layer > 4 && !tp_is_nv4_id(layer)) return fail(ctx, DDK_ERR_INVALID, std::string(who) + ": layer out of range (0..4, or DDK_TP_NV4 + 0..4)");
   return check_group_table(ctx, who, go, n_groups, E);
 }
 
 int ddk_rtp_forward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float* sh, const float* h, const int64_t* group_offsets, int32_t n_groups,
                     const float* w2, const float* b2, int64_t E, float* out, void* stream) {
-  int rc = rtp_check(ctx, "ddk_rtp_forward", layer, group_offsets, n_groups, E);
+  const ConvLayerDev* L = nullptr;
+  int rc = rtp_check(ctx, "ddk_rtp_forward", layer, group_offsets, n_groups, E, &L);
   if (rc) return rc;
   if (E == 0) return DDK_OK;
   if (!x_dst || !sh || !h || !w2 || !b2 || !out) return fail(ctx, DDK_ERR_INVALID, "ddk_rtp_forward: null operand");
-  hipError_t e = launch_rtp_forward(ctx->conv[layer], x_dst, sh, h, group_offsets, n_groups, w2, b2, out, (hipStream_t)stream);
+  hipError_t e = launch_rtp_forward(*L, x_dst, sh, h, group_offsets, n_groups, w2, b2, out, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(ctx, e, "rtp_forward launch");
   return DDK_OK;
 }
@@ -298,7 +319,8 @@ int ddk_rtp_forward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float
 int ddk_rtp_backward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float* sh, const float* h, const int64_t* group_offsets, int32_t n_groups,
                      const float* w2, const float* b2, const float* grad_out, int64_t E, float* grad_x, float* grad_sh, float* grad_h, float* grad_w2,
                      float* grad_b2, void* workspace, void* stream) {
-  int rc = rtp_check(ctx, "ddk_rtp_backward", layer, group_offsets, n_groups, E);
+  const ConvLayerDev* L = nullptr;
+  int rc = rtp_check(ctx, "ddk_rtp_backward", layer, group_offsets, n_groups, E, &L);
   if (rc) return rc;
   if (!grad_x && !grad_sh && !grad_h && !grad_w2 && !grad_b2)
     return fail(ctx, DDK_ERR_INVALID, "ddk_rtp_backward: no gradient requested (grad_x, grad_sh, grad_h, grad_w2 and grad_b2 are all null)");
@@ -310,7 +332,7 @@ int ddk_rtp_backward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const floa
     if (params && !workspace) return fail(ctx, DDK_ERR_INVALID, "ddk_rtp_backward: grad_w2 / grad_b2 need the workspace of ddk_rtp_backward_workspace");
   }
   if (E == 0 && !params) return DDK_OK;
-  hipError_t e = launch_rtp_backward(ctx->conv[layer], x_dst, sh, h, group_offsets, n_groups, w2, b2, grad_out, grad_x, grad_sh, grad_h, grad_w2, grad_b2,
+  hipError_t e = launch_rtp_backward(*L, x_dst, sh, h, group_offsets, n_groups, w2, b2, grad_out, grad_x, grad_sh, grad_h, grad_w2, grad_b2,
                                      (float*)workspace, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(ctx, e, "rtp_backward launch");
   return DDK_OK;
@@ -320,8 +342,8 @@ int64_t ddk_rtp_backward_workspace(int32_t layer, int64_t E, int32_t n_groups) {
 
 // the checks the two radial-conv entries share on top of rtp_check: node counts, and with edges the graph tables and the per-edge operands
 static int rconv_check(ddk_ctx* ctx, const char* who, int32_t layer, const int64_t* go, int32_t n_groups, int64_t E, const RconvGraph& gr, bool backward,
-                       const float* x_nodes, const float* sh, const float* h, const void* workspace) {
-  int rc = rtp_check(ctx, who, layer, go, n_groups, E);
+                       const float* x_nodes, const float* sh, const float* h, const void* workspace, const ConvLayerDev** L) {
+  int rc = rtp_check(ctx, who, layer, go, n_groups, E, L);
   if (!rc) rc = check_conv_graph(ctx, who, gr, E, backward);
   if (rc || E == 0) return rc;
   const std::string w(who);
@@ -334,11 +356,12 @@ int ddk_rconv_forward(ddk_ctx* ctx, int32_t layer, const float* x_nodes, int64_t
                       const int32_t* src_order, const int64_t* src_ptr, const float* sh, const float* h, const int64_t* group_offsets, int32_t n_groups,
                       const float* w2, const float* b2, int64_t E, float* out_nodes, void* workspace, void* stream) {
   const RconvGraph gr{n_in, n_out, edge_src, edge_dst, src_order, src_ptr, nullptr, nullptr};
-  int rc = rconv_check(ctx, "ddk_rconv_forward", layer, group_offsets, n_groups, E, gr, false, x_nodes, sh, h, workspace);
+  const ConvLayerDev* L = nullptr;
+  int rc = rconv_check(ctx, "ddk_rconv_forward", layer, group_offsets, n_groups, E, gr, false, x_nodes, sh, h, workspace, &L);
   if (rc) return rc;
   if (n_out > 0 && !out_nodes) return fail(ctx, DDK_ERR_INVALID, "ddk_rconv_forward: null out_nodes");
   if (E > 0 && (!w2 || !b2)) return fail(ctx, DDK_ERR_INVALID, "ddk_rconv_forward: null w2 or b2");
-  hipError_t e = launch_rconv_forward(ctx->conv[layer], gr, x_nodes, sh, h, group_offsets, n_groups, w2, b2, out_nodes, (float*)workspace, (hipStream_t)stream);
+  hipError_t e = launch_rconv_forward(*L, gr, x_nodes, sh, h, group_offsets, n_groups, w2, b2, out_nodes, (float*)workspace, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(ctx, e, "rconv_forward launch");
   return DDK_OK;
 }
@@ -348,7 +371,8 @@ int ddk_rconv_backward(ddk_ctx* ctx, int32_t layer, const float* x_nodes, int64_
                        const int64_t* group_offsets, int32_t n_groups, const float* w2, const float* b2, const float* grad_out_nodes, int64_t E,
                        float* grad_x_nodes, float* grad_sh, float* grad_h, float* grad_w2, float* grad_b2, void* workspace, void* stream) {
   const RconvGraph gr{n_in, n_out, edge_src, edge_dst, src_order, src_ptr, dst_order, dst_ptr};
-  int rc = rconv_check(ctx, "ddk_rconv_backward", layer, group_offsets, n_groups, E, gr, true, x_nodes, sh, h, workspace);
+  const ConvLayerDev* L = nullptr;
+  int rc = rconv_check(ctx, "ddk_rconv_backward", layer, group_offsets, n_groups, E, gr, true, x_nodes, sh, h, workspace, &L);
   if (rc) return rc;
   if (!grad_x_nodes && !grad_sh && !grad_h && !grad_w2 && !grad_b2)
     return fail(ctx, DDK_ERR_INVALID, "ddk_rconv_backward: no gradient requested (grad_x_nodes, grad_sh, grad_h, grad_w2 and grad_b2 are all null)");
@@ -358,7 +382,7 @@ int ddk_rconv_backward(ddk_ctx* ctx, int32_t layer, const float* x_nodes, int64_
       return fail(ctx, DDK_ERR_INVALID, "ddk_rconv_backward: null w2 (it may be null only when grad_x_nodes, grad_sh and grad_h are all null)");
     if ((grad_x_nodes || grad_sh) && !b2) return fail(ctx, DDK_ERR_INVALID, "ddk_rconv_backward: null b2 (grad_x_nodes and grad_sh need w = w2 h + b2)");
   }
-  hipError_t e = launch_rconv_backward(ctx->conv[layer], gr, x_nodes, sh, h, group_offsets, n_groups, w2, b2, grad_out_nodes, grad_x_nodes, grad_sh, grad_h,
+  hipError_t e = launch_rconv_backward(*L, gr, x_nodes, sh, h, group_offsets, n_groups, w2, b2, grad_out_nodes, grad_x_nodes, grad_sh, grad_h,
                                        grad_w2, grad_b2, (float*)workspace, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(ctx, e, "rconv_backward launch");
   return DDK_OK;

@@ -5,7 +5,7 @@
 // (bitwise an fmaf chain), no atomics anywhere, the same bits run to run and whichever subset of the outputs is asked for (compiled with -ffp-contract=off).
 //
 // TILES.  The weight row is cut into tiles of 32 SLOTS = 4 rows x 8 columns of one weight block; slot i of a tile is row 4 rg + ((i>>2)&1) + 2 (i>>4) and
-// column 8 cg + (i&3) + 4 ((i>>3)&1).  A scalar block (24 columns) has 3 column groups, a vector block (6 columns) one with two idle columns; rows past the
+// column 8 cg + (i&3) + 4 ((i>>3)&1).  A scalar block (24 columns) has 3 column groups, a vector block (nv = 6 or 4 columns) one with two or four idle columns; rows past the
 // block's end are idle slots (zero operands).  Layer 3: 24 + 9 + 9 + 24 = 66 tiles for 58.5 tiles' worth of weights.  The slot order is chosen for the
 // accumulator map of the MFMA (row = (reg&3) + 8 (reg>>2) + 4 (lane>>5)): in EVERY tile a lane's 16 registers hold the same 8 columns, known at compile time,
 // and two rows (4 rg + (lane>>5) and that + 2), so the contraction with U or g indexes registers statically and needs two rows of U per lane and tile.
@@ -63,7 +63,7 @@ struct RtpT {      // the tiles of a shape: row groups and column groups of bloc
   static constexpr int NCG(int k) { return S::vec(k) ? 1 : 3; }
   static constexpr int T0(int k) { return k <= 0 ? 0 : T0(k - 1) + NRG(k - 1) * NCG(k - 1); }
   static constexpr int NT = T0(4);
-  static_assert(S::O0 == 24 && (S::O3 == 0 || S::O3 == 24) && (S::O1 == 0 || S::O1 == 6) && (S::O2 == 0 || S::O2 == 6), "three column groups of 8, or one of 6");
+  static_assert(S::O0 == 24 && (S::O3 == 0 || S::O3 == 24) && S::O1 <= 8 && S::O2 <= 8, "three column groups of 8, or one of up to 8 (nv = 6: two idle columns, nv = 4: four)");
 };
 
 struct RtpSlot { int blk, r, c, p; bool valid; };
@@ -265,7 +265,7 @@ struct RtpEdge {
 #pragma unroll
           for (int t = 0; t < 16; ++t) {
             const int cl = (t & 3) + 4 * ((t >> 2) & 1), m = t >> 3;
-            if (VEC && cl >= 6) continue;
+            if (VEC && cl >= Ok) continue;
             const int c = 8 * cg + cl;
             if constexpr (FWD) {
               if constexpr (VEC) { o[3 * c] += u[m][0] * acc[t]; o[3 * c + 1] += u[m][1] * acc[t]; o[3 * c + 2] += u[m][2] * acc[t]; }
@@ -281,7 +281,7 @@ struct RtpEdge {
             for (int s = 0; s < 16; ++s) {
               const int cl = (s & 3) + 4 * ((s >> 2) & 1), m = s >> 3, c = 8 * cg + cl;
               float gw = 0.f;
-              if constexpr (VEC) { if (cl < 6) gw = u[m][0] * gr[3 * c] + u[m][1] * gr[3 * c + 1] + u[m][2] * gr[3 * c + 2]; } else gw = u[m][0] * gr[c];
+              if constexpr (VEC) { if (cl < Ok) gw = u[m][0] * gr[3 * c] + u[m][1] * gr[3 * c + 1] + u[m][2] * gr[3 * c + 2]; } else gw = u[m][0] * gr[c];
               const int brow = (s & 3) + 8 * (s >> 2) + 4 * hh;
 #pragma unroll
               for (int n = 0; n < 3; ++n) {
@@ -564,6 +564,10 @@ static hipError_t rtp_launch(const RtpArgs& a, bool fwd, hipStream_t s) {
 }
 
 int64_t rtp_backward_workspace(int32_t layer, int64_t E, int32_t n_groups) {
+  if (tp_is_nv4_id(layer)) {
+    if (E < 0 || E >= (int64_t)1 << 31 || n_groups < 1 || n_groups > 4) return -1;
+    return slice_bound(E, n_groups) * TP_LAYER_NV4_W[layer - TP_NV4 < 3 ? layer - TP_NV4 : 3] * RTP_IMG * (int64_t)sizeof(float);
+  }
   if (layer < 0 || layer > 4 || E < 0 || E >= (int64_t)1 << 31 || n_groups < 1 || n_groups > 4) return -1;
   return slice_bound(E, n_groups) * TP_LAYER_W[layer < 3 ? layer : 3] * RTP_IMG * (int64_t)sizeof(float);
 }
@@ -595,10 +599,12 @@ hipError_t launch_rtp_backward(const ConvLayerDev& L, const float* x_dst, const 
 // ---- the radial conv ---------------------------------------------------------------------------------------------------------------------------------------------
 int64_t rconv_workspace(int32_t layer, int64_t E, int32_t n_groups, int64_t n_in, int64_t n_out, int32_t backward) {
   const int64_t lim = (int64_t)1 << 31;
-  if (layer < 0 || layer > 4 || E < 0 || E >= lim || n_groups < 1 || n_groups > 4 || n_in < 0 || n_in >= lim || n_out < 0 || n_out >= lim) return -1;
-  const int l = layer < 3 ? layer : 3;
+  const bool nv4 = tp_is_nv4_id(layer);
+  if ((!nv4 && (layer < 0 || layer > 4)) || E < 0 || E >= lim || n_groups < 1 || n_groups > 4 || n_in < 0 || n_in >= lim || n_out < 0 || n_out >= lim) return -1;
+  const int l = nv4 ? (layer - TP_NV4 < 3 ? layer - TP_NV4 : 3) : (layer < 3 ? layer : 3);
   int din = 0, dout = 0;
-  switch (l) {
+  if (nv4) { din = TP_LAYER_NV4_DIN[l]; dout = TP_LAYER_NV4_DOUT[l]; }
+  else switch (l) {
     case 0: din = TpLayerShape<0>::DIN; dout = TpLayerShape<0>::DOUT; break;
     case 1: din = TpLayerShape<1>::DIN; dout = TpLayerShape<1>::DOUT; break;
     case 2: din = TpLayerShape<2>::DIN; dout = TpLayerShape<2>::DOUT; break;

@@ -42,8 +42,9 @@ __device__ __forceinline__ void tpf_request(const TpFArgs& a, int64_t e, int lan
 }
 
 // Rows in flight per wave and waves per SIMD as measured on MI355X (profiles/r06_tp_boundary_kernel_stats.md): the W = 1872 row (8 16-B pieces per
-// lane) wants its registers (2 waves per SIMD requested, 3 fit), the shorter rows want the occupancy
-template <class S> constexpr int TP_COL_WPE = S::NV >= 8 ? 2 : 4;
+// lane) wants its registers (2 waves per SIMD requested, 3 fit), the shorter rows want the occupancy.  The W = 1600 row of the nv = 4 family (7 pieces)
+// spills 11 registers at 4 waves (128 registers) and asks for 3 (168); not measured against 2
+template <class S> constexpr int TP_COL_WPE = S::NV >= 8 ? 2 : (S::NV == 7 ? 3 : 4);
 
 template <class S, int D, int WPE>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void tp_col_kernel(TpFArgs a) {

@@ -20,8 +20,8 @@
 //    scalar block is one row times four neighbouring columns (1 ds_read_b32 + 1 ds_read_b128); a piece of a vector block is four 3-vector dot products
 //    (8 ds_read_b128 from tables padded to 16 B per row and per column).  A wave instruction's 64 pieces are all of one kind except at the two block edges.
 //  * The G sums read the weight row, parked flat in LDS, one block ROW per lane: scalar blocks 6 ds_read_b128 at a row stride of 24 floats, vector blocks
-//    3 ds_read_b64 at a stride of 6 floats.  Bank mapping: 6-float rows read 8 B per lane are conflict-free (banks 6 r mod 64, all even and distinct over
-//    32 rows).  24-float rows start on banks 24 r mod 64 = 8 (3 r mod 8): eight starts, and rows r, r + 8 of a ds_read_b128 lane group would meet.  The
+//    3 ds_read_b64 at a stride of 6 floats (nv = 4: 2 at a stride of 4).  Bank mapping: 6-float rows read 8 B per lane are conflict-free (banks 6 r mod 64, all
+//    even and distinct over 32 rows; 4-float rows repeat after 16 rows: rows r and r + 16 meet, not measured apart).  24-float rows start on banks 24 r mod 64 = 8 (3 r mod 8): eight starts, and rows r, r + 8 of a ds_read_b128 lane group would meet.  The
 //    lane groups of ds_read_b128 take lanes of two neighbouring octets from each half of a 32-lane window ({0-3, 12-15, 20-27}, ...), so reading the six
 //    16-B pieces of a row in the order j ^ 1 in lanes 16-31 and 48-63 moves those lanes to the odd 4-bank slots; the column operand g follows the same order.
 #include <stdlib.h>
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(64) void tp_bwd_kernel(TpBArgs a) {
   using M = TpbLds<S, NX>;
   static_assert(S::O0 > 0 && S::O0 % 4 == 0 && (S::O3 == 0 || S::O3 == S::O0) && S::B1 % 4 == 0 && S::B2 % 4 == 0 && S::B3 % 4 == 0, "a 16-B piece of a scalar block is one row");
   static_assert(S::O3 == 0 || (S::O0 + 3 * S::O1 + 3 * S::O2) % 4 == 0, "g of block 0o is read 16 B at a time");
-  static_assert((S::O1 == 0 || S::O1 == 6) && (S::O2 == 0 || S::O2 == 6) && S::O1 + S::O2 <= 16, "vector rows are read as three 8-B pairs");
+  static_assert(S::O1 % 2 == 0 && S::O2 % 2 == 0 && S::O1 + S::O2 <= 16, "vector rows are read as 8-B pairs (nv = 6: three, nv = 4: two)");
   static_assert(S::A + S::P + S::Q + S::C <= 64 && S::R0 + S::R3 <= 64 && S::R1 <= 64 && S::A + S::R2 <= 64 && S::DOUT <= 128, "one lane per input irrep and per block row");
   static_assert(S::R0 == S::A + S::P, "block 0o's rows follow block 0e's in the lane order");
   __shared__ float4 smem4[M::BYTES / 16];

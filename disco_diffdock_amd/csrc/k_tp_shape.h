@@ -1,4 +1,5 @@
-// The four FasterTensorProduct shapes of the score model's conv layers (models/tensor_layers.py:56-61) and what the three files that run them share
+// The FasterTensorProduct shapes of the conv layers (models/tensor_layers.py:56-61), two families of four: ns = 24 / nv = 6 (the score model) and
+// ns = 24 / nv = 4 (the DisCo latent encoder, models/latent_encoder.py; training ops only), and what the three files that run them share
 // (k_tp.hip: the forward, k_tp_bwd.hip: its vector-Jacobian product, k_rtp.hip: the fused radial tensor product): input multiplicities A, P, Q, C of
 // 0e, 1o, 1e, 0o, output multiplicities O0 .. O3, the weight blocks' row counts R0 .. R3 and their offsets B0 .. B3 in the flat weight row of W floats;
 // the match of a ConvLayerDev against the shapes and the dispatch on it; the few device helpers that are the same text in more than one kernel.
@@ -40,6 +41,22 @@ template <> struct TpLayer<3> { using type = TpShape<24, 6, 6, 24, 24, 6, 6, 24>
 template <int I> using TpLayerShape = typename TpLayer<I>::type;
 constexpr int TP_LAYER_W[4] = {TpLayerShape<0>::W, TpLayerShape<1>::W, TpLayerShape<2>::W, TpLayerShape<3>::W};
 
+// The second family (ns = 24, nv = 4: get_irrep_seq(24, 4, False)), the same sequence with four vectors per entry.  The kernels are the same templates on
+// these types: nothing in them is written for a multiplicity, only for "a vector block has at most 8 columns" (k_rtp.hip) and "an even number" (k_tp_bwd.hip).
+// In the C ABI the family's layer l is the id DDK_TP_NV4 + l (include/ddk.h); no context holds such a layer, tp_family_layer below is its ConvLayerDev.
+template <int I> struct TpLayerNv4;
+template <> struct TpLayerNv4<0> { using type = TpShape<24, 0, 0, 0, 24, 4, 0, 0>; };
+template <> struct TpLayerNv4<1> { using type = TpShape<24, 4, 0, 0, 24, 4, 4, 0>; };
+template <> struct TpLayerNv4<2> { using type = TpShape<24, 4, 4, 0, 24, 4, 4, 24>; };
+template <> struct TpLayerNv4<3> { using type = TpShape<24, 4, 4, 24, 24, 4, 4, 24>; };
+template <int I> using TpLayerNv4Shape = typename TpLayerNv4<I>::type;
+constexpr int TP_NV4 = 8;            // DDK_TP_NV4
+constexpr int TP_NV4_LAYERS = 5;     // ids TP_NV4 .. TP_NV4 + 4, as layers 0..4 of the first family
+constexpr int TP_LAYER_NV4_W[4] = {TpLayerNv4Shape<0>::W, TpLayerNv4Shape<1>::W, TpLayerNv4Shape<2>::W, TpLayerNv4Shape<3>::W};
+constexpr int TP_LAYER_NV4_DIN[4] = {TpLayerNv4Shape<0>::DIN, TpLayerNv4Shape<1>::DIN, TpLayerNv4Shape<2>::DIN, TpLayerNv4Shape<3>::DIN};
+constexpr int TP_LAYER_NV4_DOUT[4] = {TpLayerNv4Shape<0>::DOUT, TpLayerNv4Shape<1>::DOUT, TpLayerNv4Shape<2>::DOUT, TpLayerNv4Shape<3>::DOUT};
+inline bool tp_is_nv4_id(int32_t layer) { return layer >= TP_NV4 && layer < TP_NV4 + TP_NV4_LAYERS; }
+
 // ---- host: which shape a layer has ----------------------------------------------------------------------------------------------------------------------
 template <class S>
 inline bool tp_shape_matches(const ConvLayerDev& L) {
@@ -47,9 +64,27 @@ inline bool tp_shape_matches(const ConvLayerDev& L) {
   return memcmp(L.in_mul, in, sizeof(in)) == 0 && memcmp(L.out_mul, out, sizeof(out)) == 0;
 }
 
-inline int tp_shape_index(const ConvLayerDev& L) {      // 0..3, or -1: not a FasterTensorProduct of this model family (ddk_create refuses other ns / nv)
+inline int tp_shape_index(const ConvLayerDev& L) {      // 0..3 (nv = 6), 4..7 (nv = 4), or -1: not a FasterTensorProduct of either family
   return tp_shape_matches<TpLayerShape<0>>(L) ? 0 : (tp_shape_matches<TpLayerShape<1>>(L) ? 1 : (tp_shape_matches<TpLayerShape<2>>(L) ? 2 :
-         (tp_shape_matches<TpLayerShape<3>>(L) ? 3 : -1)));
+         (tp_shape_matches<TpLayerShape<3>>(L) ? 3 : (tp_shape_matches<TpLayerNv4Shape<0>>(L) ? 4 : (tp_shape_matches<TpLayerNv4Shape<1>>(L) ? 5 :
+         (tp_shape_matches<TpLayerNv4Shape<2>>(L) ? 6 : (tp_shape_matches<TpLayerNv4Shape<3>>(L) ? 7 : -1)))))));
+}
+
+// the ConvLayerDev of id TP_NV4 + l: multiplicities alone (what tp_dispatch reads), no weights, the same for every context
+template <class S>
+inline ConvLayerDev tp_shape_only_layer() {
+  ConvLayerDev L;
+  const int in[4] = {S::A, S::P, S::Q, S::C}, out[4] = {S::O0, S::O1, S::O2, S::O3};
+  memcpy(L.in_mul, in, sizeof(in));
+  memcpy(L.out_mul, out, sizeof(out));
+  L.W = S::W; L.din = S::DIN; L.dout = S::DOUT;
+  return L;
+}
+inline const ConvLayerDev& tp_family_layer(int32_t id) {      // id: tp_is_nv4_id
+  static const ConvLayerDev table[4] = {tp_shape_only_layer<TpLayerNv4Shape<0>>(), tp_shape_only_layer<TpLayerNv4Shape<1>>(),
+                                        tp_shape_only_layer<TpLayerNv4Shape<2>>(), tp_shape_only_layer<TpLayerNv4Shape<3>>()};
+  const int l = id - TP_NV4;
+  return table[l < 3 ? l : 3];
 }
 
 // f(S{}) with the layer's shape type S, e.g. [&](auto shape) { using S = decltype(shape); ... }; hipErrorInvalidValue for a layer without one (the C
@@ -61,6 +96,10 @@ inline hipError_t tp_dispatch(const ConvLayerDev& L, F&& f) {
     case 1: return f(TpLayerShape<1>{});
     case 2: return f(TpLayerShape<2>{});
     case 3: return f(TpLayerShape<3>{});
+    case 4: return f(TpLayerNv4Shape<0>{});
+    case 5: return f(TpLayerNv4Shape<1>{});
+    case 6: return f(TpLayerNv4Shape<2>{});
+    case 7: return f(TpLayerNv4Shape<3>{});
   }
   return hipErrorInvalidValue;
 }

@@ -54,3 +54,42 @@ def get_ar_model(args, score_model_args, device, training=True):
                                 latent_dropout=args.latent_dropout, latent_hidden_dim=args.latent_hidden_dim,
                                 input_latent_dim=score_model_args.latent_dim, apply_gumbel_softmax=True)
     return ar.to(device)
+
+
+def get_trainable_model(args, device, t_to_sigma=None):
+    """utils/model_utils.py:25-101 (get_model) for TRAINING: ``train_model.TrainableScoreModel``, and with ``args.latent_dim > 0`` (``latent_vocab == 1``)
+    ``latent_encoder.TPEncoder`` in front of it in a ``train_model.LatentModelWrapper``, whose state_dict has the ``encoder.`` / ``score_model.`` keys of
+    the reference's ``ModelWrapper`` checkpoints.  The encoder reads ``encoder_ns``, ``encoder_nv``, ``encoder_num_conv_layers``,
+    ``encoder_cross_max_distance``, ``encoder_no_esm``, ``latent_*`` and ``training_latent_temperature`` as lines 70-94 there do."""
+    from .latent_encoder import TPEncoder
+    from .train_model import LatentModelWrapper, TrainableScoreModel
+    g = lambda k, d: getattr(args, k, d)
+    if getattr(args, 'all_atoms', False):
+        raise RuntimeError('ddk: get_trainable_model: all_atoms is not implemented (the coarse-grained score model trains)')
+    latent_dim = int(g('latent_dim', 0))
+    if latent_dim > 0 and g('latent_vocab', 0) != 1:
+        raise RuntimeError('ddk: get_trainable_model: latent_vocab must be 1 whenever latent_dim > 0 (the equivariant-latent models only)')
+    lm = 'esm' if g('esm_embeddings_path', None) is not None else None
+    sh_lmax = g('sh_lmax', 2)
+    score_model = TrainableScoreModel(
+        t_to_sigma=t_to_sigma, device=device, no_torsion=args.no_torsion, num_conv_layers=args.num_conv_layers, lig_max_radius=args.max_radius,
+        scale_by_sigma=args.scale_by_sigma, sigma_embed_dim=args.sigma_embed_dim, ns=args.ns, nv=args.nv, distance_embed_dim=args.distance_embed_dim,
+        cross_distance_embed_dim=args.cross_distance_embed_dim, batch_norm=not args.no_batch_norm, dropout=args.dropout, sh_lmax=sh_lmax,
+        use_second_order_repr=args.use_second_order_repr, cross_max_distance=args.cross_max_distance, dynamic_max_cross=args.dynamic_max_cross,
+        lm_embedding_type=lm, use_old_atom_encoder=g('use_old_atom_encoder', True), latent_dim=latent_dim, latent_vocab=g('latent_vocab', 0),
+        latent_cross_attention=g('latent_cross_attention', False), new_cross_attention=g('new_cross_attention', False),
+        latent_droprate=g('latent_droprate', 0), embedding_scale=args.embedding_scale,
+        sigma_limits=dict(tr_sigma_min=args.tr_sigma_min, tr_sigma_max=args.tr_sigma_max, rot_sigma_min=args.rot_sigma_min,
+                          rot_sigma_max=args.rot_sigma_max, tor_sigma_min=args.tor_sigma_min, tor_sigma_max=args.tor_sigma_max))
+    if latent_dim == 0:
+        return score_model.to(device)
+    encoder = TPEncoder(device=device, no_torsion=args.no_torsion, num_conv_layers=args.encoder_num_conv_layers, lig_max_radius=args.max_radius,
+                        ns=args.encoder_ns, nv=args.encoder_nv, distance_embed_dim=args.distance_embed_dim,
+                        cross_distance_embed_dim=args.cross_distance_embed_dim, batch_norm=not args.no_batch_norm, dropout=args.dropout, sh_lmax=sh_lmax,
+                        use_second_order_repr=args.use_second_order_repr, cross_max_distance=args.encoder_cross_max_distance,
+                        lm_embedding_type=None if g('encoder_no_esm', False) else lm, latent_dim=latent_dim, latent_vocab=args.latent_vocab,
+                        latent_no_batchnorm=g('latent_no_batchnorm', False), latent_dropout=g('latent_dropout', 0.0),
+                        latent_hidden_dim=g('latent_hidden_dim', 128), latent_virtual_nodes=g('latent_virtual_nodes', False),
+                        latent_nodes_residual=g('latent_nodes_residual', False))
+    return LatentModelWrapper(encoder, score_model, training_latent_temperature=g('training_latent_temperature', 1.0),
+                              latent_droprate=g('latent_droprate', 0)).to(device)

@@ -159,6 +159,17 @@ def tp_layer_shape(layer, ns=24, nv=6):
     return dict(A=A, P=P, Q=Q, C=C, O=O, R=R, B=B, W=B[4], din=A + 3 * P + 3 * Q + C, dout=O[0] + 3 * O[1] + 3 * O[2] + O[3])
 
 
+TP_NV4 = 8      # DDK_TP_NV4 of include/ddk.h: the `layer` argument TP_NV4 + l of the tensor-product ops is layer l of the ns = 24 / nv = 4 family
+
+
+def tp_id_shape(layer, ns=24, nv=6):
+    """``tp_layer_shape`` of a `layer` argument of the tensor-product ops: TP_NV4 + l (l in 0..4) is layer l of the ns = 24 / nv = 4 family whatever the
+    context's nv; anything else is conv layer ``layer`` of a model with (``ns``, ``nv``)"""
+    if TP_NV4 <= layer < TP_NV4 + 5:
+        return tp_layer_shape(layer - TP_NV4, 24, 4)
+    return tp_layer_shape(layer, ns, nv)
+
+
 HEAD_CENTER, HEAD_TORSION = 0, 1      # DDK_HEAD_CENTER, DDK_HEAD_TORSION of include/ddk.h
 
 
@@ -472,7 +483,7 @@ class Context:
             raise RuntimeError('ddk: the radial conv takes a ConvGraph (Context.conv_graph): its kernels trust the indices')
         ops = self._rtp_operands(layer, x_nodes, sh, h, group_offsets, w2, b2, E=graph.E)
         x_nodes = ops[0]
-        if x_nodes.dim() != 2 or x_nodes.shape != (graph.n_in, tp_layer_shape(layer, self.cfg.ns, self.cfg.nv)['din']):
+        if x_nodes.dim() != 2 or x_nodes.shape != (graph.n_in, tp_id_shape(layer, self.cfg.ns, self.cfg.nv)['din']):
             raise RuntimeError(f'ddk: the radial conv takes x_nodes [n_in, Din] for a graph of {graph.n_in} input nodes; got {tuple(x_nodes.shape)}')
         if graph.src.device != x_nodes.device:
             raise RuntimeError('ddk: the radial conv takes a ConvGraph on the device of its operands')
@@ -487,7 +498,7 @@ class Context:
         x_nodes, sh, h, offs, G, w2, b2, E, W = self._rconv_operands(layer, graph, x_nodes, sh, h, group_offsets, w2, b2)
         if w2 is None or b2 is None:
             raise RuntimeError('ddk: rconv_forward needs w2 and b2')
-        dout = tp_layer_shape(layer, self.cfg.ns, self.cfg.nv)['dout']
+        dout = tp_id_shape(layer, self.cfg.ns, self.cfg.nv)['dout']
         out = torch.empty((graph.n_out, dout), dtype=torch.float32, device=x_nodes.device)
         g = graph
         ws = _workspace(self.L.ddk_rconv_workspace(layer, g.E, G, g.n_in, g.n_out, 0),
@@ -900,7 +911,7 @@ class Context:
 
     def tp_weight_numel(self, layer):
         """W of conv layer ``layer``: the length of a FasterTensorProduct weight row (tensor_layers.py:56-63)."""
-        return tp_layer_shape(layer, self.cfg.ns, self.cfg.nv)['W']
+        return tp_id_shape(layer, self.cfg.ns, self.cfg.nv)['W']
 
     def conv_forward(self, layer, x, edge_src, edge_dst, group_offsets, edge_attr, sh, dout):
         x, edge_attr, sh = x.contiguous().float(), edge_attr.contiguous().float(), sh.contiguous().float()

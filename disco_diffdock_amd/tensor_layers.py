@@ -21,16 +21,17 @@ parity tests read like tests of the reference modules:
 * ``fused_edge_embedding(mlp, expansion, pos_a, pos_b, edge_index, sig, sig_index, feat=None, seed=None)``: one edge group of the embed in front of the
   conv stack (score_model.py:191-225): the edge embedding [E, ns] and the spherical harmonics from the coordinates, nothing kept per edge
 
-Only the configurations the shipped score models use are implemented on the device (ns=24, nv=6, sh_lmax=1, 2-layer ReLU radial MLP): the conv layers
-(faster=True, edge_groups=4, residual=True) and the two heads (faster=False, edge_groups=1, residual=False); anything else raises.
+Only the configurations the shipped models use are implemented on the device (ns=24, sh_lmax=1, 2-layer ReLU radial MLP; nv=6, the score model, and for the
+conv layers nv=4, the DisCo latent encoder): the conv layers (faster=True, edge_groups=4, residual=True) and the two heads (nv=6; faster=False,
+edge_groups=1, residual=False); anything else raises.
 
 ``TensorProductConvLayer`` trains: in ``.train()`` its forward is ``fused_radial_conv``, e3nn's BatchNorm on the batch
 statistics (plain torch, ``_BatchNormParams.forward``) and the padded residual.  In ``.eval()`` it is the fused inference
-kernel (``ddk_conv_forward``), unchanged.  ``conv_stack`` trains the whole stack of them from the edge embedding with the
+kernel (``ddk_conv_forward``), unchanged; an nv=4 layer has no inference kernel and evaluates with the training ops.  ``conv_stack`` trains the whole stack of them from the edge embedding with the
 same bits on every run.  In a head configuration the layer is ``fused_head_conv`` plus BatchNorm in training and in evaluation
 (``heads.ScoreHeads`` is the module on top); ``train_model.TrainableScoreModel`` assembles the whole model.  The latent-conditioned (DisCo) score model trains
-through ``fused_edge_embedding``'s latent columns and ``ragged_gumbel_softmax``.  What still does not train: the AR predictor, the all-atom / confidence
-irreps, any other ns / nv.
+through ``fused_edge_embedding``'s latent columns and ``ragged_gumbel_softmax``; ``latent_encoder.TPEncoder`` is the encoder in front.  What still does not
+train: the AR predictor, the all-atom / confidence irreps, any other ns / nv.
 """
 import math
 
@@ -39,7 +40,7 @@ import torch
 from torch import nn
 from torch.autograd.function import once_differentiable
 
-from .runtime import HEAD_CENTER, HEAD_TORSION, Context, head_tp_shape, tp_layer_shape
+from .runtime import HEAD_CENTER, HEAD_TORSION, TP_NV4, Context, head_tp_shape, tp_id_shape, tp_layer_shape
 
 _ORDER = ('0e', '1o', '1e', '0o')
 _DIM = {'0e': 1, '1o': 3, '1e': 3, '0o': 1}
@@ -84,14 +85,19 @@ def irrep_to_size(irreps):
     return sum(m * _DIM[k] for k, m in parse_irreps(irreps).items())
 
 
-def layer_index(in_irreps, out_irreps, ns=24, nv=6):
-    """Which conv layer of the score model has these irreps (get_irrep_seq, tensor_layers.py:12-27)."""
+def layer_index(in_irreps, out_irreps, ns=24, nv=None):
+    """The `layer` argument of the tensor-product ops for these irreps (get_irrep_seq, tensor_layers.py:12-27): 0..3 for the score model's family
+    (nv = 6), ``TP_NV4 + l`` for the latent encoder's (nv = 4).  ``nv``: one family alone (None: both are searched)."""
     i, o = tuple(parse_irreps(in_irreps).values()), tuple(parse_irreps(out_irreps).values())
-    for l in range(4):
-        s = tp_layer_shape(l, ns, nv)
-        if (s['A'], s['P'], s['Q'], s['C']) == i and s['O'] == o:
-            return l
-    raise RuntimeError(f'ddk: no fused kernel for irreps {in_irreps} -> {out_irreps} (ns={ns}, nv={nv})')
+    for fam_nv, base in ((6, 0), (4, TP_NV4)):
+        if nv not in (None, fam_nv) or ns != 24:
+            continue
+        for l in range(4):
+            s = tp_layer_shape(l, ns, fam_nv)
+            if (s['A'], s['P'], s['Q'], s['C']) == i and s['O'] == o:
+                return base + l
+    raise RuntimeError(f'ddk: no fused kernel for irreps {in_irreps} -> {out_irreps} (ns=24 with nv=6 or nv=4 are compiled in'
+                       + (f'; asked for ns={ns}, nv={nv})' if nv is not None or ns != 24 else ')'))
 
 
 _shape_ctx = {}
@@ -158,7 +164,7 @@ class FasterTensorProduct(nn.Module):
             raise AssertionError("sh_irreps don't look like 1st order spherical harmonics")
         self.in_irreps, self.out_irreps = str(in_irreps), str(out_irreps)
         self.layer = layer_index(in_irreps, out_irreps)
-        s = tp_layer_shape(self.layer)
+        s = tp_id_shape(self.layer)
         self.weight_shapes = dict(zip(_ORDER, zip(s['R'], s['O'])))      # (every block of these layers that has rows has columns)
         self.weight_numel, self.out_size = s['W'], s['dout']
 
@@ -386,9 +392,9 @@ def conv_stack(conv_layers, node_attr, edge_index, edge_emb, group_sizes, edge_s
     In training the whole stack runs without atomics: two passes from one state and one seed give the same bits.  Returns ``node_attr``."""
     layers = list(conv_layers)
     graph = None
-    if any(layer.training for layer in layers) and edge_index.shape[1] > 0:
+    if any(layer.training or getattr(layer, 'layer', 0) >= TP_NV4 for layer in layers) and edge_index.shape[1] > 0:      # (an nv = 4 layer evaluates with the training ops)
         graph = Context.conv_graph(edge_index[0], edge_index[1], node_attr.shape[0], node_attr.shape[0])
-        if seed is None:
+        if seed is None and any(layer.training for layer in layers):
             seed = _draw_seed()
     for l, layer in enumerate(layers):
         node_attr = layer.forward_embedded(node_attr, edge_index, edge_emb, group_sizes, edge_sh, graph=graph,
@@ -480,7 +486,8 @@ def fused_edge_embedding(mlp, expansion, pos_a, pos_b, edge_index, sig, sig_inde
     ``edge_emb = mlp(torch.cat([feat, sig[sig_index[edge_index[0]]], expansion(|vec|)], 1))`` and ``edge_sh`` = the first-order spherical harmonics of
     ``vec = pos_b[edge_index[1]] - pos_a[edge_index[0]]`` (component normalisation: ``[1 | sqrt3 vec / |vec|]``).  ``mlp``: the reference's
     ``nn.Sequential(Linear(K, 24), ReLU, Dropout, Linear(24, 24))``, K = 64, or 68 with ``feat`` [E, 4]; ``expansion``: a ``GaussianSmearing`` of 32
-    Gaussians; ``sig`` [T, 32]: the sigma embedding per graph, ``sig_index`` [Na] the graph of a node of ``pos_a``.  The positions carry no gradient in
+    Gaussians; ``sig`` [T, 32]: the sigma embedding per graph, ``sig_index`` [Na] the graph of a node of ``pos_a``; ``sig=None, sig_index=None``: a row without the
+    sigma block (K = 32, or 36 with ``feat``: the latent encoder's), run by the same kernels on ``W1`` padded with 32 zero columns.  The positions carry no gradient in
     score matching: one that requires it raises.  Nothing wider than the outputs is stored per edge, forward or backward; the four parameters of ``mlp``
     get the same gradient bits on every run (no atomics).  Dropout: rate ``mlp[2].p`` while that module is in training mode, else none; the mask is a
     pure function of (``seed``, edge position, column), DDK_EEMB_MASK_LAYOUT of include/ddk.h; ``seed=None`` takes one draw from torch's default CPU
@@ -497,7 +504,8 @@ def fused_edge_embedding(mlp, expansion, pos_a, pos_b, edge_index, sig, sig_inde
             or not isinstance(mlp[2], nn.Dropout) or not isinstance(mlp[3], nn.Linear) or mlp[0].bias is None or mlp[3].bias is None
             or mlp[0].out_features != 24 or (mlp[3].in_features, mlp[3].out_features) != (24, 24)):
         raise RuntimeError('ddk: fused_edge_embedding takes nn.Sequential(Linear(K, 24), ReLU, Dropout, Linear(24, 24)) with biases')
-    K = 64 if feat is None else 68
+    F_ = 0 if feat is None else 4
+    K = F_ + (32 if sig is not None else 0) + 32
     latent = latent_a is not None or latent_b is not None or zero_latent or unconditional is not None or unconditional_embedding is not None
     L = 0
     if latent:
@@ -515,12 +523,21 @@ def fused_edge_embedding(mlp, expansion, pos_a, pos_b, edge_index, sig, sig_inde
         if unconditional is not None and unconditional.requires_grad:
             raise RuntimeError('ddk: fused_edge_embedding has no gradient for unconditional (a mask of graphs); detach it')
     if mlp[0].in_features != K + 2 * L:
-        raise RuntimeError(f'ddk: fused_edge_embedding: the first Linear takes {mlp[0].in_features} columns, the row has {K + 2 * L} (4 bond features with feat, 32 + 32'
+        raise RuntimeError(f'ddk: fused_edge_embedding: the first Linear takes {mlp[0].in_features} columns, the row has {K + 2 * L} (4 bond features with feat, 32 + 32 (32 with sig=None)'
                            + (f', 2 x {L} latent columns)' if L else ')'))
     if not pos_a.is_cuda:
         raise RuntimeError('ddk fused_edge_embedding runs on the GPU only (no CPU fallback)')
     if pos_a.requires_grad or pos_b.requires_grad:
         raise RuntimeError('ddk: fused_edge_embedding has no gradient for the positions (they carry none in score matching); detach them')
+    w1 = mlp[0].weight
+    if sig is None:
+        # no sigma block (the latent encoder): 32 zero columns where the kernel reads it, a one-row zero table that every node points at.  The zero columns
+        # add exact zeros to each fmaf chain, and the cat's backward drops their gradient
+        if sig_index is not None:
+            raise RuntimeError('ddk: fused_edge_embedding takes sig and sig_index together (both None: a row without a sigma block)')
+        w1 = torch.cat([w1[:, :F_], w1.new_zeros((w1.shape[0], 32)), w1[:, F_:]], 1)
+        sig = torch.zeros((1, 32), dtype=torch.float32, device=pos_a.device)
+        sig_index = torch.zeros(pos_a.shape[0], dtype=torch.int32, device=pos_a.device)
     if sig.requires_grad or (feat is not None and feat.requires_grad):
         raise RuntimeError('ddk: fused_edge_embedding has no gradient for sig or feat (times and bond types carry none); detach them')
     if edge_index.dim() != 2 or edge_index.shape[0] != 2:
@@ -534,7 +551,7 @@ def fused_edge_embedding(mlp, expansion, pos_a, pos_b, edge_index, sig, sig_inde
     idx_a, idx_b = edge_index[0].to(torch.int32).contiguous(), edge_index[1].to(torch.int32).contiguous()
     operands = (pos_a.detach().float().contiguous(), pos_b.detach().float().contiguous(), idx_a, idx_b, None if feat is None else feat.float().contiguous(),
                 sig.float().contiguous(), sig_index.to(torch.int32).contiguous())
-    w1, b1, w2, b2 = mlp[0].weight, mlp[0].bias, mlp[3].weight, mlp[3].bias
+    b1, w2, b2 = mlp[0].bias, mlp[3].weight, mlp[3].bias
     if latent:
         uemb = None if unconditional_embedding is None else unconditional_embedding.reshape(-1)
         unc = None if unconditional is None else unconditional.detach().float().reshape(-1).contiguous()
@@ -848,7 +865,7 @@ class TensorProductConvLayer(nn.Module):
     def forward(self, node_attr, edge_index, edge_attr, edge_sh, out_nodes=None, reduce='mean'):
         if self.head is not None:
             return self._forward_head(node_attr, edge_index, edge_attr, edge_sh, out_nodes, reduce)
-        if self.training:
+        if self.training or self.layer >= TP_NV4:      # the fused inference kernel is nv = 6 only: an nv = 4 layer evaluates with the training ops
             return self._forward_training(node_attr, edge_index, edge_attr, edge_sh, out_nodes, reduce)
         if reduce != 'mean' or (out_nodes is not None and out_nodes != node_attr.shape[0]):
             raise RuntimeError("ddk: conv layers aggregate with reduce='mean' onto all nodes")
@@ -864,7 +881,8 @@ class TensorProductConvLayer(nn.Module):
 
     def _forward_training(self, node_attr, edge_index, edge_attr, edge_sh, out_nodes, reduce):
         """The reference's forward (models/tensor_layers.py:147-168) in training: fused_radial_conv, BatchNorm on the batch statistics, the padded
-        residual.  Without edges: zeros and no BatchNorm, as there."""
+        residual.  Without edges: zeros and no BatchNorm, as there.  An nv = 4 layer runs this in evaluation too: the modules' own mode then gives
+        dropout rate 0 and BatchNorm on its running buffers."""
         if reduce != 'mean':
             raise RuntimeError("ddk: conv layers aggregate with reduce='mean'")
         if not node_attr.is_cuda:
@@ -882,14 +900,15 @@ class TensorProductConvLayer(nn.Module):
         ``edge_attr = [edge_emb | node_attr[edge_index[0], :ns] | node_attr[edge_index[1], :ns]]`` cut into groups of ``group_sizes`` edges.  In
         training the row [E, 72] is never built: ``fused_radial_hidden`` -> ``fused_radial_conv(hidden=...)`` -> BatchNorm -> residual, without
         atomics.  ``graph``: the ``ConvGraph`` of ``edge_index`` over the nodes, built here otherwise; ``seed``: of the dropout mask
-        (``fused_radial_hidden``).  In evaluation the cat is built and ``forward`` runs the inference kernel, unchanged."""
+        (``fused_radial_hidden``).  In evaluation the cat is built and ``forward`` runs the inference kernel, unchanged; an nv = 4 layer, which has no inference
+        kernel, runs the training ops there too (dropout rate 0, BatchNorm on its running buffers)."""
         if self.head is not None:
             raise RuntimeError('ddk: forward_embedded is a step of the conv stack; a head layer has forward alone')
         sizes = [int(n) for n in group_sizes]
         E = edge_index.shape[1]
         if len(sizes) != self.edge_groups or any(n < 0 for n in sizes) or sum(sizes) != E or edge_emb.shape[0] != E:
             raise RuntimeError(f'ddk: forward_embedded takes {self.edge_groups} group sizes that add up to the {E} edges of edge_index and edge_emb')
-        if not self.training:
+        if not self.training and self.layer < TP_NV4:
             ns = edge_emb.shape[1]
             edge_attr = torch.cat([edge_emb, node_attr[edge_index[0], :ns], node_attr[edge_index[1], :ns]], -1)
             return self.forward(node_attr, edge_index, list(torch.split(edge_attr, sizes)), edge_sh)

@@ -14,8 +14,10 @@ The latent-conditioned DisCo score model (``latent_dim`` in 1..4, ``latent_vocab
 and receptor edge row (zeros on cross edges), inside ``fused_edge_embedding``; its gradient reaches whatever made it (``LatentModelWrapper`` puts an encoder
 and ``ragged_gumbel_softmax`` in front), again without atomics.
 
-Not covered: the oracle latent encoder (TPEncoder), the AR predictor, ``latent_vocab > 1``, ``latent_cross_attention``, ``confidence_mode``, the all-atom
+The oracle latent encoder is ``latent_encoder.TPEncoder``.  Not covered: the AR predictor, ``latent_vocab > 1``, ``latent_cross_attention``, ``confidence_mode``, the all-atom
 model, any other ns / nv / sh_lmax."""
+import inspect
+
 import torch
 from torch import nn
 
@@ -85,7 +87,7 @@ def combine_edges(lig_ei, cross_ei, rec_ei, n_lig):
 
 class AtomEncoder(nn.Module):
     """models/layers.py:119-149 (the new AtomEncoder): one embedding table per categorical feature, summed, then a Linear over [sum | scalar features |
-    sigma embedding].  The tables are read through ``gather_rows``: their gradient is a fixed-order segmented sum, not index_add_'s atomics."""
+    sigma embedding] where there are any such columns (the latent encoder's ligand side, and its receptor side without ESM, have none: the sum is the output).  The tables are read through ``gather_rows``: their gradient is a fixed-order segmented sum, not index_add_'s atomics."""
 
     def __init__(self, emb_dim, feature_dims, sigma_embed_dim, lm_embedding_type=None, latent_dim=0):
         super().__init__()
@@ -97,7 +99,8 @@ class AtomEncoder(nn.Module):
             emb = nn.Embedding(dim, emb_dim)
             nn.init.xavier_uniform_(emb.weight.data)
             self.atom_embedding_list.append(emb)
-        self.additional_features_embedder = nn.Linear(self.additional_features_dim + emb_dim, emb_dim)
+        if self.additional_features_dim > 0:      # (models/layers.py:137: without additional features the sum of the tables is the output, and there is no such key)
+            self.additional_features_embedder = nn.Linear(self.additional_features_dim + emb_dim, emb_dim)
 
     def forward(self, x_cat, x_scalar):
         """``x_cat`` [N, categorical features] (integers), ``x_scalar`` [N, additional features] (floats)"""
@@ -107,6 +110,8 @@ class AtomEncoder(nn.Module):
         emb = 0
         for i, table in enumerate(self.atom_embedding_list):
             emb = emb + gather_rows(table.weight, x_cat[:, i])
+        if self.additional_features_dim == 0:
+            return emb
         return self.additional_features_embedder(torch.cat([emb, x_scalar], dim=1))
 
 
@@ -302,7 +307,8 @@ class LatentModelWrapper(nn.Module):
 
         latent *= keep[batch][:, None]        unconditional = 1 - keep[batch]            keep [B] in {0, 1}; latent_droprate == 0: all ones, no unconditional
 
-    ``forward(data, seed=None, keep=None)``: ``keep`` as given (``training.draw_latent_keep`` makes a seeded one, ``training.train_epoch`` passes it), else
+    ``forward(data, seed=None, keep=None)``: ``seed`` goes to the score model and, where its ``forward`` has a ``seed`` parameter (``latent_encoder.TPEncoder``), to
+    the encoder; ``keep`` as given (``training.draw_latent_keep`` makes a seeded one, ``training.train_epoch`` passes it), else
     drawn with ``torch.bernoulli(1 - latent_droprate)`` as the reference does, in ``.train()`` and in ``.eval()`` alike (pass ``keep=torch.ones(B)``
     for a conditional evaluation).  ``training_latent_temperature`` is set on the encoder as
     ``encoder.latent_temperature`` before every call, as the reference does.  ``ctx`` / ``no_torsion`` are the score model's, so ``training.noise_batch`` and ``loss_function`` take the
@@ -315,6 +321,7 @@ class LatentModelWrapper(nn.Module):
         if float(latent_droprate) != score_model.latent_droprate:
             raise RuntimeError(f'ddk: LatentModelWrapper: latent_droprate = {latent_droprate}, the score model was built with {score_model.latent_droprate}')
         self.encoder, self.score_model = encoder, score_model
+        self._encoder_takes_seed = 'seed' in inspect.signature(encoder.forward).parameters
         self.training_latent_temperature, self.latent_droprate = float(training_latent_temperature), float(latent_droprate)
 
     @property
@@ -327,7 +334,10 @@ class LatentModelWrapper(nn.Module):
 
     def forward(self, data, seed=None, keep=None):
         self.encoder.latent_temperature = self.training_latent_temperature      # (as the reference hands it over)
-        latent_l, latent_r = self.encoder(data)
+        if self._encoder_takes_seed:      # (latent_encoder.TPEncoder: its dropout masks and Gumbel noise follow the step's seed, on sub-seeds of its own)
+            latent_l, latent_r = self.encoder(data, seed=seed)
+        else:
+            latent_l, latent_r = self.encoder(data)
         dev, B = latent_l.device, int(data.num_graphs)
         lig_batch, rec_batch = data['ligand'].batch.to(dev).long(), data['receptor'].batch.to(dev).long()
         if self.latent_droprate > 0:

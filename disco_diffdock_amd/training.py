@@ -168,8 +168,8 @@ def noise_batch(model, complexes, t, seed, draw=0, samples=None):
     returns (data, :data:`BatchTargets`).  ``complexes``: the dicts ``runtime.Complex`` takes, with 'name', 'lig_pos', 'edge_mask', 'mask_rotate'; ``t``:
     G host floats in [0, 1]; ``samples``: G global sample indices (default 0).  Graph g is sample ``samples[g]`` of stream ``stream_id(name_g)`` under
     ``seed`` and ``draw``, so its pose and targets do not depend on the rest of the batch, and a complex may appear twice with different samples.
-    ``data`` is a ``data.collate`` batch on the model's device in the layout ``TrainableScoreModel.forward`` documents, with the noised ``data['ligand'].pos``
-    and ``data.complex_t`` (set_time's graph-level part).  Every per-graph table goes up in ONE copy; then ddk_rng_perturbation_batch and
+    ``data`` is a ``data.collate`` batch on the model's device in the layout ``TrainableScoreModel.forward`` documents, with the noised ``data['ligand'].pos``,
+    the true poses in ``data['ligand'].orig_pos_torch`` and ``data.complex_t`` (set_time's graph-level part).  Every per-graph table goes up in ONE copy; then ddk_rng_perturbation_batch and
     ddk_modify_conformer_batch, one launch each (the IGSO(3) table is computed once per context).  Nothing is read back: what the device would report as a
     status (a bond outside its ligand, a coordinate that is not finite, a ligand over a limit) is checked here on the host first and raises."""
     ctx = _ctx_of(model)
@@ -230,6 +230,7 @@ def noise_batch(model, complexes, t, seed, draw=0, samples=None):
     noised = ctx.modify_conformer_batch(d_pos, d_node, d_bonds, d_masks, d_mask_ptr, d_tor, p.tr_update, p.rot_update, p.tor_update if T else None, T=T)
     batch = _data.collate([_data.from_arrays(c) for c in complexes]).to(dev)
     batch['ligand'].pos = noised
+    batch['ligand'].orig_pos_torch = d_pos      # the true poses, as uploaded: what the oracle latent encoder reads (latent_encoder.TPEncoder)
     batch.complex_t = {k: d_t for k in ('tr', 'rot', 'tor')}
     targets = BatchTargets(p.tr_score, p.rot_score, None if no_torsion else p.tor_score, d_tr_sigma, d_rot_sigma, d_tor_sigma, d_t, d_tor, p.tr_update,
                            p.rot_update, p.tor_update, d_so3_norm, d_torus_norm2, tuple(rotors))

@@ -106,7 +106,14 @@ int ddk_set_score_norm_tables(ddk_ctx* ctx, const double* so3_exp_score_norms, i
 
 /* ---- a12: FasterTensorProduct.forward(in_, sh, weight)  models/tensor_layers.py:65-116.
  *      x_dst [E, Din] (already gathered node_attr[edge_dst]), sh [E,4], w [E, W] -> out [E, Dout]
- *      with the irreps of conv layer `layer` (0..num_conv_layers-1).  HBM-bound (streams w). */
+ *      with the irreps of conv layer `layer` (0..num_conv_layers-1).  HBM-bound (streams w).
+ *
+ *      THE SECOND SHAPE FAMILY.  `layer` of the six tensor-product entries (ddk_tp_*, ddk_rtp_*, ddk_rconv_*) and of ddk_rtp_backward_workspace /
+ *      ddk_rconv_workspace also takes DDK_TP_NV4 + l, l in 0..4: conv layer l of the ns = 24 / nv = 4 irreps sequence (get_irrep_seq(24, 4, False), the DisCo
+ *      latent encoder's; 24x0e [+ 4x1o [+ 4x1e [+ 24x0o]]] -> the next entry; W = 672 / 800 / 928 / 1600 / 1600).  These ids name a shape, not a layer of
+ *      the context: any finalised device context serves them, with or without weights.  A context with more than eight conv layers refuses the ids that
+ *      are also indices of its own layers (DDK_ERR_INVALID; those layers have the shape of layer 3): an id is never reinterpreted.  The fused inference kernel (ddk_conv_forward) has no such ids. */
+#define DDK_TP_NV4 8
 int ddk_tp_forward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float* sh, const float* w,
                    int64_t E, float* out, void* stream);
 
@@ -115,7 +122,7 @@ int ddk_tp_forward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float*
 int ddk_tp_backward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float* sh, const float* w, const float* grad_out, int64_t E,
                     float* grad_x, float* grad_sh, float* grad_w, void* stream);
 
-/* ---- The radial tensor product of conv-layer shape `layer` (0..4): out[e] = FasterTensorProduct(x_dst[e], sh[e], w2[g(e)] h[e] + b2[g(e)]), the per-edge
+/* ---- The radial tensor product of conv-layer shape `layer` (0..4, or DDK_TP_NV4 + 0..4): out[e] = FasterTensorProduct(x_dst[e], sh[e], w2[g(e)] h[e] + b2[g(e)]), the per-edge
  *      weights [E, W] never stored (models/tensor_layers.py:154-156 without the last Linear's output and the cat).  x_dst [E, Din], sh [E, 4], h [E, 72] (the
  *      radial MLP's hidden activation), w2 [n_groups, W, 72] and b2 [n_groups, W] (fc[g][4].weight / .bias stacked), out [E, Dout]: DEVICE pointers, fp32,
  *      contiguous.  group_offsets: HOST array of n_groups + 1 entries (n_groups in 1..4), 0 = o_0 <= ... <= o_G = E; edge e belongs to group g iff
@@ -132,7 +139,7 @@ int ddk_rtp_backward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const floa
                      const float* w2, const float* b2, const float* grad_out, int64_t E, float* grad_x, float* grad_sh, float* grad_h, float* grad_w2,
                      float* grad_b2, void* workspace, void* stream);
 
-/* Bytes of ddk_rtp_backward's workspace: a function of its arguments alone (never more than 160 MB); -1 for a layer outside 0..4, n_groups outside 1..4,
+/* Bytes of ddk_rtp_backward's workspace: a function of its arguments alone (never more than 160 MB); -1 for a layer outside 0..4 and DDK_TP_NV4 + 0..4, n_groups outside 1..4,
  * E < 0 or E >= 2^31.  Host function, no context. */
 int64_t ddk_rtp_backward_workspace(int32_t layer, int64_t E, int32_t n_groups);
 
@@ -168,7 +175,7 @@ int ddk_rconv_backward(ddk_ctx* ctx, int32_t layer, const float* x_nodes, int64_
                        float* grad_x_nodes, float* grad_sh, float* grad_h, float* grad_w2, float* grad_b2, void* workspace, void* stream);
 
 /* Bytes of the workspace of ddk_rconv_forward (backward == 0) or ddk_rconv_backward (backward != 0): a function of its arguments alone, whichever outputs
- * are asked for; -1 for a layer outside 0..4, n_groups outside 1..4, E < 0 or E >= 2^31, n_in or n_out outside 0 .. 2^31 - 1.  Host function, no context. */
+ * are asked for; -1 for a layer outside 0..4 and DDK_TP_NV4 + 0..4, n_groups outside 1..4, E < 0 or E >= 2^31, n_in or n_out outside 0 .. 2^31 - 1.  Host function, no context. */
 int64_t ddk_rconv_workspace(int32_t layer, int64_t E, int32_t n_groups, int64_t n_in, int64_t n_out, int32_t backward);
 
 /* ---- The radial MLP's hidden layer from the edge embedding and the node table: the cat of the reference's embed loop (models/score_model.py:227-230) and
