@@ -70,7 +70,10 @@ __global__ __launch_bounds__(AR_H) void ar_logits_kernel(ArArgs A) {
 }
 
 // one workgroup per graph: p_i = exp(T logit_i) (NaN -> 0, inf -> FLT_MAX as torch.nan_to_num), pick = first index whose running
-// sum exceeds u * total (u: caller-supplied uniform in [0, 1)), or the first maximum for T >= 100; writes the one-hot
+// sum exceeds u * total (u: caller-supplied uniform in [0, 1)), or the first maximum for T >= 100; writes the one-hot.
+// (Sampling: a thread's starting sum comes from the shuffle scan, its predecessor's last running sum from a sequential loop; once the
+// probabilities span more than about 2^29 the two can differ in the last fp64 bit, and a target inside that one-ulp gap is claimed by
+// no thread: the pick falls to n - 1.)
 __global__ __launch_bounds__(256) void ar_decode_kernel(ArDecodeArgs A) {
   __shared__ double wsum[4];
   __shared__ float bestv[256];

@@ -1,15 +1,18 @@
 // The ragged straight-through Gumbel softmax in front of the latent-conditioned score model (include/ddk.h: ddk_gumbel_softmax_batch, DDK_GUMBEL_LAYOUT) and
 // its vector-Jacobian product: the reference's per-graph loop (latent_encoder.py:328-335, pretrained_score_encoder.py:74-81 over models/layers.py:152-181) for a
 // whole collated batch in one launch.  ONE WORKGROUP per (graph g, latent dimension d); the class axis is the graph's ligand nodes, then its receptor nodes,
-// position p = 0 .. n_lig_g + n_rec_g - 1.  Exact fp32 in a written-out order (compiled with -ffp-contract=off):
+// position p = 0 .. n_lig_g + n_rec_g - 1.  A written-out order (compiled with -ffp-contract=off):
 //   u    = (word >> 8) * 2^-24                               the word of position p: see THE NOISE below
-//   gum  = -logf(-logf(u + 1e-20f) + 1e-20f)                 the accurate library logf
-//   z    = (logit + gum) / T                                  a true division
-//   y    = expf(z - max z) / sum                              the sum: thread t adds its positions (quads t, t + 256, ... of four positions, ascending) to a
-//                                                             partial that starts from 0, then the 256 partials are added by the fixed halving tree
+//   gum  = -log(-log(u + 1e-20f) + 1e-20)                    the addition to u in fp32, the rest in fp64
+//   z    = (logit + gum) / T                                  in fp64, a true division; kept as the fp32 pair (hi, lo) with hi = fl32(z), lo = fl32(z - hi)
+//   e    = fl32(exp(z - max z))                               in fp64 from the pairs, rounded once.  z is 1 / T times a number of the order of 10: at T = 0.01
+//                                                             an fp32 z of 700 has an ulp of 6e-5, which every y under the winner's would carry as its RELATIVE
+//                                                             error (tests/test_gpu_latent_choice_adversarial.py measured 6.5e-5 against an fp32 host's 1e-5)
+//   y    = e / sum                                            in fp32.  The sum: thread t adds its positions (quads t, t + 256, ... of four positions, ascending)
+//                                                             to a partial that starts from 0, then the 256 partials are added by the fixed halving tree
 //   out  = (hard - y) + y                                     two operations as written; hard = 1 at the LOWEST position that holds the maximum of y, else 0
-// and backward, from the saved y:  grad_logit = y * (g - sum g y) / T, the sum in the same order.  No atomics; y's buffer holds z and the exponentials between the
-// passes (a thread reads back only what it wrote itself), so there is no limit on the number of nodes.
+// and backward, from the saved y:  grad_logit = y * (g - sum g y) / T in fp32, the sum in the same order.  No atomics; between the passes y's buffer holds z's hi
+// and then the exponentials, out's buffer z's lo (a thread reads back only what it wrote itself), so there is no limit on the number of nodes.
 //
 // THE NOISE (DDK_GUMBEL_LAYOUT 1): generator purpose 13 of DDK_RNG_LAYOUT 1, rng_block(seed, stream_id[g], sample, 13, draw, d), yields four words; words 0 and 1
 // are the key of a second Philox4x32-10 whose counter (p / 4, 0, 0, DDK_GUMBEL_TAG) gives position p the word p % 4.  A graph's noise is a pure function of
@@ -68,6 +71,7 @@ __device__ __forceinline__ float gumbel_tree_sum(float* red, float v) {
 
 __global__ __launch_bounds__(GUM_T) void gumbel_fwd_kernel(GumbelArgs a) {
   __shared__ float red[GUM_T];
+  __shared__ double redd[GUM_T];
   __shared__ int64_t redi[GUM_T];
   const int g = blockIdx.x, d = blockIdx.y, t = threadIdx.x;
   const GumbelGraph G = gumbel_graph(a, g);
@@ -76,8 +80,8 @@ __global__ __launch_bounds__(GUM_T) void gumbel_fwd_kernel(GumbelArgs a) {
   rng_block(rng_stream(((uint64_t)a.seed_hi << 32) | a.seed_lo, a.stream_id[g]), a.sample, RNG_GUMBEL, a.draw, (uint32_t)d, key);
   const int64_t quads = (G.n + 3) >> 2;
   bool lig;
-  // 1. z into y's buffer, the thread's maximum
-  float m = -INFINITY;
+  // 1. z as (hi, lo) into y's and out's buffers, the thread's maximum of hi + lo
+  double m = -INFINITY;
   for (int64_t q = t; q < quads; q += GUM_T) {
     const uint32_t ctr[4] = {(uint32_t)q, 0u, 0u, DDK_GUMBEL_TAG};
     uint32_t w[4];
@@ -88,21 +92,23 @@ __global__ __launch_bounds__(GUM_T) void gumbel_fwd_kernel(GumbelArgs a) {
       if (p < G.n) {
         const int64_t at = gumbel_at(G, p, a.D, d, lig);
         const float u = rng_uniform(w[i]);
-        const float gum = -logf(-logf(u + 1e-20f) + 1e-20f);
-        const float z = ((lig ? a.logit_l : a.logit_r)[at] + gum) / a.T;
-        (lig ? a.y_l : a.y_r)[at] = z;
-        m = fmaxf(m, z);
+        const double gum = -log(-log((double)(u + 1e-20f)) + 1e-20);
+        const double z = ((double)(lig ? a.logit_l : a.logit_r)[at] + gum) / (double)a.T;
+        const float hi = (float)z, lo = isinf(hi) ? 0.f : (float)(z - (double)hi);
+        (lig ? a.y_l : a.y_r)[at] = hi;
+        (lig ? a.out_l : a.out_r)[at] = lo;
+        m = fmax(m, (double)hi + (double)lo);
       }
     }
   }
   __syncthreads();
-  red[t] = m;
+  redd[t] = m;
   __syncthreads();
   for (int s = GUM_T / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] = fmaxf(red[t], red[t + s]);
+    if (t < s) redd[t] = fmax(redd[t], redd[t + s]);
     __syncthreads();
   }
-  m = red[0];
+  m = redd[0];
   // 2. the exponentials and their sum
   float part = 0.f;
   for (int64_t q = t; q < quads; q += GUM_T) {
@@ -112,7 +118,7 @@ __global__ __launch_bounds__(GUM_T) void gumbel_fwd_kernel(GumbelArgs a) {
       if (p < G.n) {
         const int64_t at = gumbel_at(G, p, a.D, d, lig);
         float* y = lig ? a.y_l : a.y_r;
-        const float e = expf(y[at] - m);
+        const float e = (float)exp(((double)y[at] + (double)(lig ? a.out_l : a.out_r)[at]) - m);
         y[at] = e;
         part += e;
       }

@@ -345,8 +345,9 @@ int64_t ddk_eemb_latent_workspace(int64_t E, int32_t K, int32_t L);
 /* ---- The ragged straight-through Gumbel softmax that makes the latent of a collated batch (latent_encoder.py:328-335 and pretrained_score_encoder.py:74-81
  *      of the reference, over models/layers.py:152-181): per graph g and latent dimension d, over the graph's ligand nodes followed by its receptor nodes
  *      (position pos = 0 .. n_g - 1):
- *        gum = -logf(-logf(u + 1e-20f) + 1e-20f)     z = (logit + gum) / T     y = softmax(z) (maximum subtracted)     out = (hard - y) + y in fp32,
- *        hard = 1 at the LOWEST position of the maximum of y, else 0.  The sum of the softmax in a fixed order: thread t of 256 adds the positions of the quads
+ *        gum = -log(-log(u + 1e-20f) + 1e-20)     z = (logit + gum) / T     e = exp(z - max z)  in fp64 (u + 1e-20f in fp32), e rounded to fp32 once: z is
+ *        1 / T times a number of the order of 10, and an fp32 z would hand its ulp (6e-5 at T = 0.01) to every y as a relative error;
+ *        y = e / sum     out = (hard - y) + y  in fp32, hard = 1 at the LOWEST position of the maximum of y, else 0.  The sum of the softmax in a fixed order: thread t of 256 adds the positions of the quads
  *        t, t + 256, ... (four positions each) in ascending order from 0, the partials by a halving tree.
  *      logit_l / y_l / out_l [n_lig, D], logit_r / y_r / out_r [n_rec, D]: DEVICE, fp32, contiguous; lig_ptr, rec_ptr: DEVICE int64 [G + 1], graph g owns the
  *      rows ptr[g] .. ptr[g + 1] - 1 (a pair that is no range of its table: the graph is left unwritten); stream_id: DEVICE uint64 [G].  y is saved for the
