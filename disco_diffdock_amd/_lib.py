@@ -54,7 +54,7 @@ _lib = None
 
 # every symbol include/ddk.h declares (tests check that the library exports all of them)
 SYMBOLS = ['ddk_create', 'ddk_destroy', 'ddk_last_error', 'ddk_version', 'ddk_load_weights', 'ddk_finalize_weights',
-           'ddk_set_score_norm_tables', 'ddk_tp_forward', 'ddk_tp_backward', 'ddk_rtp_forward', 'ddk_rtp_backward', 'ddk_rtp_backward_workspace', 'ddk_rconv_forward', 'ddk_rconv_backward', 'ddk_rconv_workspace', 'ddk_rhid_forward', 'ddk_rhid_backward', 'ddk_rhid_workspace', 'ddk_hconv_forward', 'ddk_hconv_backward', 'ddk_hconv_workspace', 'ddk_eemb_forward', 'ddk_eemb_backward', 'ddk_eemb_workspace', 'ddk_eemb_latent_forward', 'ddk_eemb_latent_backward', 'ddk_eemb_latent_workspace', 'ddk_gumbel_softmax_batch', 'ddk_gumbel_softmax_batch_backward', 'ddk_rng_latent_keep', 'ddk_seg_sum', 'ddk_conv_forward', 'ddk_complex_create', 'ddk_complex_destroy',
+           'ddk_set_score_norm_tables', 'ddk_tp_forward', 'ddk_tp_backward', 'ddk_rtp_forward', 'ddk_rtp_backward', 'ddk_rtp_backward_workspace', 'ddk_rconv_forward', 'ddk_rconv_backward', 'ddk_rconv_workspace', 'ddk_rhid_forward', 'ddk_rhid_backward', 'ddk_rhid_workspace', 'ddk_hconv_forward', 'ddk_hconv_backward', 'ddk_hconv_workspace', 'ddk_eemb_forward', 'ddk_eemb_backward', 'ddk_eemb_workspace', 'ddk_eemb_latent_forward', 'ddk_eemb_latent_backward', 'ddk_eemb_latent_workspace', 'ddk_gumbel_softmax_batch', 'ddk_gumbel_softmax_batch_backward', 'ddk_rng_latent_keep', 'ddk_node_cross_entropy_batch', 'ddk_node_cross_entropy_batch_backward', 'ddk_rng_decoding_index', 'ddk_seg_sum', 'ddk_conv_forward', 'ddk_complex_create', 'ddk_complex_destroy',
            'ddk_score_forward', 'ddk_se3_update', 'ddk_sample', 'ddk_last_graph_stats', 'ddk_last_node_features',
            'ddk_profile_enable', 'ddk_profile_read', 'ddk_profile_read_forwards', 'ddk_set_latents', 'ddk_set_guidance',
            'ddk_set_keep_receptor_features', 'ddk_randomize_position', 'ddk_complex_set_atoms',
@@ -66,7 +66,7 @@ SYMBOLS = ['ddk_create', 'ddk_destroy', 'ddk_last_error', 'ddk_version', 'ddk_lo
            'ddk_rng_noise', 'ddk_rng_initial', 'ddk_rng_uniform',
            'ddk_so3_rows', 'ddk_torus_score', 'ddk_rng_perturbation', 'ddk_score_matching_loss',
            'ddk_conformer_match_workspace', 'ddk_conformer_rmsd', 'ddk_conformer_match',
-           'ddk_rng_perturbation_batch', 'ddk_rng_forward_times', 'ddk_modify_conformer_batch', 'ddk_score_matching_loss_batch',
+           'ddk_rng_perturbation_batch', 'ddk_rng_forward_times', 'ddk_modify_conformer_batch', 'ddk_randomize_position_batch', 'ddk_score_matching_loss_batch',
            'ddk_score_matching_loss_batch_backward']
 
 # test hooks (include/ddk_debug.h): not part of the drop-in boundary
@@ -132,6 +132,10 @@ def lib():
     L.ddk_gumbel_softmax_batch.argtypes = gumbel + [C.c_uint64, vp, i32, i32, vp, vp, vp, vp, vp]
     L.ddk_gumbel_softmax_batch_backward.argtypes = gumbel + [vp, vp, vp, vp, vp]
     L.ddk_rng_latent_keep.argtypes = [vp, C.c_uint64, i32, vp, i32, i32, f32, vp]
+    node_ce = [vp, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, i32]      # ctx, G, D, the logit pair with its node counts, lig_ptr, rec_ptr, the teacher pair, column, soft
+    L.ddk_node_cross_entropy_batch.argtypes = node_ce + [vp, vp, vp, vp, vp]
+    L.ddk_node_cross_entropy_batch_backward.argtypes = node_ce + [vp, vp, vp, vp, vp, vp]
+    L.ddk_rng_decoding_index.argtypes = [vp, C.c_uint64, i32, vp, i32, i32, i32, vp]
     L.ddk_seg_sum.argtypes = [vp, vp, vp, vp, vp, i64, i32, vp]
     L.ddk_conv_forward.argtypes = [vp, i32, vp, i64, vp, vp, C.POINTER(i64), vp, vp, vp, vp]
     L.ddk_complex_create.argtypes = [vp, C.POINTER(ddk_complex_desc), i32, C.POINTER(vp)]
@@ -167,6 +171,7 @@ def lib():
     L.ddk_rng_perturbation_batch.argtypes = [vp, u64, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, C.POINTER(ddk_perturbation), vp]
     L.ddk_rng_forward_times.argtypes = [vp, u64, i32, vp, i32, i32, vp]
     L.ddk_modify_conformer_batch.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.ddk_randomize_position_batch.argtypes = [vp, u64, i32, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, f32, vp, vp, vp]
     L.ddk_score_matching_loss_batch.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.ddk_score_matching_loss_batch_backward.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.ddk_conformer_match_workspace.argtypes = [i32, i32, i32, i32]

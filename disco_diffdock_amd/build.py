@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libddk.so')
-SOURCES = ['ddk_capi.hip', 'conv_pack.hip', 'conv_launch.hip', 'k_conv.hip', 'k_tp.hip', 'k_tp_bwd.hip', 'k_rtp.hip', 'k_rhid.hip', 'k_hconv.hip', 'k_eemb.hip', 'k_gumbel.hip', 'k_reduce.hip', 'k_graph.hip', 'k_heads.hip', 'k_se3.hip', 'model.hip', 'conf.hip', 'k_conv_x.hip', 'k_conv_x2.hip', 'k_ar.hip', 'k_pairs.hip', 'k_autos.hip', 'k_build.hip', 'k_rng.hip', 'k_so3.hip', 'k_noising.hip', 'k_match.hip']
+SOURCES = ['ddk_capi.hip', 'conv_pack.hip', 'conv_launch.hip', 'k_conv.hip', 'k_tp.hip', 'k_tp_bwd.hip', 'k_rtp.hip', 'k_rhid.hip', 'k_hconv.hip', 'k_eemb.hip', 'k_gumbel.hip', 'k_node_ce.hip', 'k_reduce.hip', 'k_graph.hip', 'k_heads.hip', 'k_se3.hip', 'model.hip', 'conf.hip', 'k_conv_x.hip', 'k_conv_x2.hip', 'k_ar.hip', 'k_pairs.hip', 'k_autos.hip', 'k_build.hip', 'k_rng.hip', 'k_so3.hip', 'k_noising.hip', 'k_match.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics', '-mllvm', '-amdgpu-mfma-vgpr-form', '-Wall', '-Wno-unused-function', '-Wno-unused-value', '-Wno-unused-result']
 
 
@@ -23,7 +23,7 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-ato
 # forward's hidden layer with the forward's expressions; k_reduce: the slice reduction and the segmented sum that close these ops, separate adds in a fixed order
 FILE_FLAGS = {'k_conv_x.hip': ['-fno-slp-vectorize'], 'k_conv_x2.hip': ['-fno-slp-vectorize'], 'k_tp_bwd.hip': ['-ffp-contract=off'], 'k_rtp.hip': ['-ffp-contract=off'],
               'k_rhid.hip': ['-ffp-contract=off', '-fno-slp-vectorize'], 'k_hconv.hip': ['-ffp-contract=off', '-fno-slp-vectorize'],
-              'k_eemb.hip': ['-ffp-contract=off', '-fno-slp-vectorize'], 'k_gumbel.hip': ['-ffp-contract=off'], 'k_reduce.hip': ['-ffp-contract=off']}
+              'k_eemb.hip': ['-ffp-contract=off', '-fno-slp-vectorize'], 'k_gumbel.hip': ['-ffp-contract=off'], 'k_node_ce.hip': ['-ffp-contract=off'], 'k_reduce.hip': ['-ffp-contract=off']}
 # sources that are #included by another source (besides the headers): part of that object's content stamp
 INCLUDED_SOURCES = {'k_conv_x2.hip': ['k_conv_x.hip']}
 

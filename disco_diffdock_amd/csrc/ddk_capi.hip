@@ -675,6 +675,66 @@ int ddk_rng_latent_keep(ddk_ctx* ctx, uint64_t seed, int32_t n, const uint64_t* 
   return DDK_OK;
 }
 
+int ddk_rng_decoding_index(ddk_ctx* ctx, uint64_t seed, int32_t n, const uint64_t* stream_id, int32_t sample, int32_t draw, int32_t D, int32_t* idx_out) {
+  if (!ctx) return DDK_ERR_INVALID;
+  if (n < 0) return fail(ctx, DDK_ERR_INVALID, "ddk_rng_decoding_index: n must be >= 0");
+  if (sample < 0) return fail(ctx, DDK_ERR_INVALID, "ddk_rng_decoding_index: sample must be >= 0");
+  if (draw < 0 || draw >= RNG_MAX_STEPS) return fail(ctx, DDK_ERR_INVALID, "ddk_rng_decoding_index: draw must be in [0, " + std::to_string(RNG_MAX_STEPS) + ")");
+  if (D < 1 || D > 4) return fail(ctx, DDK_ERR_INVALID, "ddk_rng_decoding_index: D must be in 1..4");
+  if (n > 0 && (!stream_id || !idx_out)) return fail(ctx, DDK_ERR_INVALID, "ddk_rng_decoding_index: null argument");
+  for (int32_t i = 0; i < n; ++i) {
+    uint32_t w[4];
+    rng_block(rng_stream(seed, stream_id[i]), (uint32_t)sample, 14u /* decoding index: DDK_RNG_LAYOUT 1 */, (uint32_t)draw, 0, w);
+    idx_out[i] = (int32_t)(((w[0] >> 8) * (uint32_t)D) >> 24);      // (a 24-bit number times D <= 4 fits 32 bits)
+  }
+  return DDK_OK;
+}
+
+// the checks the two node cross-entropy entries share
+static int node_ce_check(ddk_ctx* ctx, const char* who, int32_t G, int32_t D, int64_t n_lig, int64_t n_rec, const int64_t* lig_ptr, const int64_t* rec_ptr,
+                         const int32_t* column, int32_t soft) {
+  int rc = check_launchable(ctx, 0);
+  if (rc) return rc;
+  const std::string w(who);
+  if (G < 1 || G > 65536) return fail(ctx, DDK_ERR_INVALID, w + ": G must be in [1, 65536]");
+  if (D < 1 || D > 4) return fail(ctx, DDK_ERR_INVALID, w + ": D must be in 1..4");
+  if (n_lig < 0 || n_rec < 0 || n_lig >= (int64_t)1 << 31 || n_rec >= (int64_t)1 << 31) return fail(ctx, DDK_ERR_INVALID, w + ": node count out of range");
+  if (soft != 0 && soft != 1) return fail(ctx, DDK_ERR_INVALID, w + ": soft must be 0 or 1");
+  if (!lig_ptr || !rec_ptr || !column) return fail(ctx, DDK_ERR_INVALID, w + ": null lig_ptr, rec_ptr or column");
+  return DDK_OK;
+}
+
+int ddk_node_cross_entropy_batch(ddk_ctx* ctx, int32_t G, int32_t D, const float* logit_l, int64_t n_lig, const float* logit_r, int64_t n_rec,
+                                 const int64_t* lig_ptr, const int64_t* rec_ptr, const float* teacher_l, const float* teacher_r, const int32_t* column,
+                                 int32_t soft, float* loss, int64_t* pick, int64_t* target, double* saved, void* stream) {
+  int rc = node_ce_check(ctx, "ddk_node_cross_entropy_batch", G, D, n_lig, n_rec, lig_ptr, rec_ptr, column, soft);
+  if (rc) return rc;
+  if ((n_lig > 0 && (!logit_l || !teacher_l)) || (n_rec > 0 && (!logit_r || !teacher_r)))
+    return fail(ctx, DDK_ERR_INVALID, "ddk_node_cross_entropy_batch: null operand (logit, teacher of a side that has nodes)");
+  if (!loss || !pick || !target || !saved) return fail(ctx, DDK_ERR_INVALID, "ddk_node_cross_entropy_batch: null output (loss, pick, target, saved)");
+  if (n_lig + n_rec == 0) return DDK_OK;
+  const NodeCeArgs a{logit_l, logit_r, teacher_l, teacher_r, lig_ptr, rec_ptr, column, loss, pick, target, saved, n_lig, n_rec, D, soft};
+  hipError_t e = launch_node_ce_forward(a, G, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "node_cross_entropy_batch launch");
+  return DDK_OK;
+}
+
+int ddk_node_cross_entropy_batch_backward(ddk_ctx* ctx, int32_t G, int32_t D, const float* logit_l, int64_t n_lig, const float* logit_r, int64_t n_rec,
+                                          const int64_t* lig_ptr, const int64_t* rec_ptr, const float* teacher_l, const float* teacher_r,
+                                          const int32_t* column, int32_t soft, const float* grad, const int64_t* target, const double* saved,
+                                          float* grad_logit_l, float* grad_logit_r, void* stream) {
+  int rc = node_ce_check(ctx, "ddk_node_cross_entropy_batch_backward", G, D, n_lig, n_rec, lig_ptr, rec_ptr, column, soft);
+  if (rc) return rc;
+  if ((n_lig > 0 && (!logit_l || !grad_logit_l || (soft && !teacher_l))) || (n_rec > 0 && (!logit_r || !grad_logit_r || (soft && !teacher_r))))
+    return fail(ctx, DDK_ERR_INVALID, "ddk_node_cross_entropy_batch_backward: null operand (logit, grad_logit, and with soft = 1 teacher, of a side that has nodes)");
+  if (!grad || !target || !saved) return fail(ctx, DDK_ERR_INVALID, "ddk_node_cross_entropy_batch_backward: null argument (grad, target, saved)");
+  if (n_lig + n_rec == 0) return DDK_OK;
+  const NodeCeBwdArgs a{logit_l, logit_r, teacher_l, teacher_r, lig_ptr, rec_ptr, column, grad, target, saved, grad_logit_l, grad_logit_r, n_lig, n_rec, D, soft};
+  hipError_t e = launch_node_ce_backward(a, G, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "node_cross_entropy_batch_backward launch");
+  return DDK_OK;
+}
+
 int ddk_seg_sum(ddk_ctx* ctx, const float* rows, const int32_t* order, const int64_t* ptr, float* nodes, int64_t n_nodes, int32_t D, void* stream) {
   int rc = check_launchable(ctx, 0);
   if (rc) return rc;

@@ -454,4 +454,24 @@ hipError_t launch_gumbel_forward(const GumbelOperands& o, const float* logit_l, 
                                  uint32_t draw, float* y_l, float* y_r, float* out_l, float* out_r, hipStream_t s);
 hipError_t launch_gumbel_backward(const GumbelOperands& o, const float* y_l, const float* y_r, const float* gout_l, const float* gout_r, float* grad_l,
                                   float* grad_r, hipStream_t s);
+// k_node_ce.hip: the AR model's ragged cross-entropy over a graph's ligand and receptor nodes and its gradient (include/ddk.h: ddk_node_cross_entropy_batch /
+// ddk_node_cross_entropy_batch_backward).  s_*: the student's logits [n], t_*: the teacher's tables [n, D]; lig_ptr / rec_ptr [G + 1] and column [G]: device
+// tables, checked per graph in the kernels; saved [G, 2] = (lse_s, lse_t)
+struct NodeCeArgs {
+  const float* s_l; const float* s_r; const float* t_l; const float* t_r;
+  const int64_t* lig_ptr; const int64_t* rec_ptr; const int32_t* column;
+  float* loss; int64_t* pick; int64_t* target; double* saved;
+  int64_t n_lig, n_rec;
+  int D, soft;
+};
+struct NodeCeBwdArgs {
+  const float* s_l; const float* s_r; const float* t_l; const float* t_r;
+  const int64_t* lig_ptr; const int64_t* rec_ptr; const int32_t* column;
+  const float* grad; const int64_t* target; const double* saved;
+  float* grad_l; float* grad_r;
+  int64_t n_lig, n_rec;
+  int D, soft;
+};
+hipError_t launch_node_ce_forward(const NodeCeArgs& a, int G, hipStream_t s);
+hipError_t launch_node_ce_backward(const NodeCeBwdArgs& a, int G, hipStream_t s);
 }  // namespace ddk

@@ -13,6 +13,7 @@
 #include "model.h"
 #include "k_geom.h"
 #include "k_head_finish.h"
+#include "k_philox.h"
 
 namespace ddk {
 
@@ -346,6 +347,143 @@ hipError_t launch_randomize(const RandPosArgs& A, hipStream_t s) {
   return hipGetLastError();
 }
 
+// randomize_position for a RAGGED batch of G different ligands, one workgroup per graph (include/ddk.h: ddk_randomize_position_batch): graph g is the global
+// sample sample[g] of stream stream_id[g]; its tables are found through node_ptr / tor_ptr / mask_ptr as in modify_conformer_batch_kernel, with that kernel's
+// checks and status codes (a sample < 0 counts as a bad table entry).  The workgroup makes the graph's draws itself, with rng_initial_kernel's expressions
+// (k_rng.hip; purposes 1, 2, 3 of DDK_RNG_LAYOUT 1) into LDS, and then runs randomize_kernel's arithmetic on them, statement for statement, so a graph gets the
+// bits ddk_rng_initial + ddk_randomize_position give the same ligand alone.  Each draw goes through LDS before it is used: a product formed here is rounded
+// as the one rng_initial_kernel stores, never fused into the addition that consumes it.
+// rng_rotation (k_philox.h) with every multiply-add WRITTEN OUT as rng_initial_kernel's code object evaluates it: there the contraction of the quaternion's
+// products was left to the compiler, which fuses some of them and not others, and a second kernel that inlines the same source need not get the same choice
+// (this one did not).  The chains below are read off that code object: the norm starts from the unfused sum of the first two squares; R[3], R[7] and
+// R[8] add rounded products; the other six fuse one product.  Doubling is exact either way.  Do not reorder them: the bit-for-bit contract with
+// ddk_rng_initial rests on them (tests/test_gpu_randomize_batch.py).
+__device__ __forceinline__ void rotation_as_rng_initial(const float q[4], float* R) {
+#pragma clang fp contract(off)
+  const float s01 = q[0] * q[0] + q[1] * q[1];
+  const float n2 = fmaf(q[3], q[3], fmaf(q[2], q[2], s01));
+  if (!(n2 >= 0x1p-60f)) {
+    R[0] = 1.f; R[1] = 0.f; R[2] = 0.f; R[3] = 0.f; R[4] = 1.f; R[5] = 0.f; R[6] = 0.f; R[7] = 0.f; R[8] = 1.f;
+    return;
+  }
+  const float inv = 1.0f / sqrtf(n2);
+  const float x = q[0] * inv, y = q[1] * inv, z = q[2] * inv, w = q[3] * inv;
+  const float x2 = x * x, y2 = y * y, z2 = z * z, w2 = w * w;
+  const float xy = x * y, zw = z * w, yw = y * w, xw = x * w, yz = y * z;
+  const float r1 = fmaf(x, y, -zw), r2 = fmaf(x, z, yw), r3 = xy + zw, r5 = fmaf(y, z, -xw), r6 = fmaf(x, z, -yw), r7 = yz + xw;
+  R[0] = fmaf(w, w, (x2 - y2) - z2); R[1] = r1 + r1;                     R[2] = r2 + r2;
+  R[3] = r3 + r3;                     R[4] = fmaf(w, w, (y2 - x2) - z2); R[5] = r5 + r5;
+  R[6] = r6 + r6;                     R[7] = r7 + r7;                     R[8] = (z2 + (-x2 - y2)) + w2;
+}
+
+__global__ __launch_bounds__(256) void randomize_batch_kernel(RandPosBatchArgs A) {
+  __shared__ float p[MAX_LIG * 3];
+  __shared__ float tor[NOISE_BATCH_MAX_ROT];
+  __shared__ float Rt[9], piv[3], ctr[3], M[9], trv[3];
+  __shared__ int skip;
+  const int g = blockIdx.x, tid = threadIdx.x;
+  const int n0 = A.node_ptr[g], n = A.node_ptr[g + 1] - n0;
+  bool tables_ok = n0 >= 0 && n >= 1 && n <= MAX_LIG && n0 <= A.N - n && A.sample[g] >= 0;
+  int R = 0, t0 = 0, m0 = 0;
+  if (A.tor_ptr != nullptr) {
+    t0 = A.tor_ptr[g]; R = A.tor_ptr[g + 1] - t0; m0 = A.mask_ptr[g];
+    tables_ok = tables_ok && t0 >= 0 && R >= 0 && R <= NOISE_BATCH_MAX_ROT && t0 <= A.T - R && m0 >= 0 && A.mask_ptr[g + 1] - m0 == R * n &&
+                m0 <= A.mask_bytes - R * n;
+  }
+  if (!tables_ok) {      // (the same in every thread: the block leaves as one)
+    if (tid == 0) A.status_out[g] = 4;
+    return;
+  }
+  const float* pos = A.pos + (size_t)n0 * 3;
+  const int32_t* bonds = A.rot_bonds + (size_t)t0 * 2;
+  const uint8_t* mask = A.mask_rotate + m0;
+  int bad_pos = 0, bad_bond = 0;
+  for (int i = tid; i < n * 3; i += 256) {
+    const float v = pos[i];
+    p[i] = v;
+    bad_pos |= !isfinite(v);
+  }
+  for (int r = tid; r < R; r += 256) {
+    const int u = bonds[2 * r], v = bonds[2 * r + 1];
+    bad_bond |= u < 0 || u >= n || v < 0 || v >= n || u == v;
+  }
+  bad_pos = __syncthreads_or(bad_pos);
+  bad_bond = __syncthreads_or(bad_bond);
+  if (bad_pos || bad_bond) {
+    if (tid == 0) A.status_out[g] = bad_bond ? 2 : 3;
+    return;
+  }
+  if (tid == 0) A.status_out[g] = 0;
+  // the draws: item j < n_tor_blk the torsion block j, j = n_tor_blk the rotation, j = n_tor_blk + 1 the translation
+  const RngStream S = rng_stream(((uint64_t)A.seed_hi << 32) | A.seed_lo, A.stream_id[g]);
+  const uint32_t sample = (uint32_t)A.sample[g];
+  const int n_tor_blk = (R + 3) >> 2;
+  for (int j = tid; j < n_tor_blk + 2; j += 256) {
+    uint32_t w[4];
+    if (j < n_tor_blk) {
+      rng_block(S, sample, RNG_INIT_TORSION, 0, (uint32_t)j, w);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int r = 4 * j + q;
+        if (r < R) tor[r] = rng_torsion(w[q]);
+      }
+    } else if (j == n_tor_blk) {
+      float q[4];
+      rng_block(S, sample, RNG_INIT_ROTATION, 0, 0, w);
+      rng_normals(w, q);
+      rotation_as_rng_initial(q, M);
+    } else {
+      float z[4];
+      rng_block(S, sample, RNG_INIT_TRANSLATION, 0, 0, w);
+      rng_normals(w, z);
+#pragma unroll
+      for (int e = 0; e < 3; ++e) trv[e] = A.tr_sigma * z[e];
+    }
+  }
+  __syncthreads();
+  for (int r = 0; r < R; ++r) {
+    if (tid == 0) {      // thread 0 builds the rotor, all apply it
+      const float th = tor[r];
+      skip = th == 0.0f;
+      bond_rotor(p, bonds[2 * r], bonds[2 * r + 1], th, Rt, piv);
+    }
+    __syncthreads();
+    if (!skip && tid < n && mask[(size_t)r * n + tid]) {
+      float x = p[3 * tid], y = p[3 * tid + 1], z = p[3 * tid + 2];
+      rotate_about(Rt, piv, x, y, z);
+      p[3 * tid] = x; p[3 * tid + 1] = y; p[3 * tid + 2] = z;
+    }
+    __syncthreads();
+  }
+  if (tid < 64) {
+    const double s = component_sum_wave0(p, n, tid);
+    if (tid < 3) ctr[tid] = (float)(s / (double)n);
+  }
+  __syncthreads();
+  if (tid < n) {
+    const float x = p[3 * tid] - ctr[0], y = p[3 * tid + 1] - ctr[1], z = p[3 * tid + 2] - ctr[2];
+    float ox, oy, oz;
+    {
+      // randomize_kernel's three rows with every multiply-add WRITTEN OUT as that kernel's code object evaluates them (its contraction was left to the
+      // compiler, which packs rows 0 and 1 and leaves row 2 on its own: row 1 starts from its middle product, row 2 adds its last product unfused).
+      // These chains are what the bit-for-bit contract with ddk_randomize_position rests on (tests/test_gpu_randomize_batch.py): do not reorder them.
+#pragma clang fp contract(off)
+      ox = fmaf(M[2], z, fmaf(M[1], y, M[0] * x));
+      oy = fmaf(M[5], z, fmaf(M[3], x, M[4] * y));
+      const float oz_xy = fmaf(M[6], x, M[7] * y), oz_z = M[8] * z;
+      oz = oz_xy + oz_z;
+      ox += trv[0]; oy += trv[1]; oz += trv[2];
+    }
+    float* o = A.pos_out + ((size_t)n0 + tid) * 3;
+    o[0] = ox; o[1] = oy; o[2] = oz;
+  }
+}
+
+hipError_t launch_randomize_batch(const RandPosBatchArgs& A, hipStream_t s) {
+  hipLaunchKernelGGL(randomize_batch_kernel, dim3(A.G), dim3(256), 0, s, A);
+  return hipGetLastError();
+}
+
 // pose metrics of evaluate.py:297-338, one workgroup per pose (see include/ddk.h: ddk_pose_metrics)
 __global__ __launch_bounds__(256) void pose_metrics_kernel(const float* pos, const float* ref, const uint8_t* mask, const int32_t* perms, int n_perms,
                                                            const float* rec_pos, int n_lig, int n_rec, float* out) {
@@ -475,5 +613,32 @@ extern "C" int ddk_modify_conformer_batch(ddk_ctx* ctx, int32_t G, int32_t N, co
   ConformerBatchArgs A{pos, node_ptr, tor_ptr, mask_ptr, rot_bonds, mask_rotate, tr_update, rot_update, tor_update, G, N, T, mask_bytes, pos_out, status_out};
   hipError_t e = launch_modify_conformer_batch(A, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(ctx, e, "modify_conformer_batch launch");
+  return DDK_OK;
+}
+
+extern "C" int ddk_randomize_position_batch(ddk_ctx* ctx, uint64_t seed, int32_t G, int32_t N, const float* pos, const int32_t* node_ptr, int32_t T,
+                                            const int32_t* rot_bonds, const uint8_t* mask_rotate, const int32_t* mask_ptr, int32_t mask_bytes,
+                                            const int32_t* tor_ptr, const uint64_t* stream_id, const int32_t* sample, float tr_sigma_max, float* pos_out,
+                                            int32_t* status_out, void* stream) {
+  using namespace ddk;
+  if (!ctx) return DDK_ERR_INVALID;
+  if (ctx->host_only) return fail(ctx, DDK_ERR_STATE, "host-only context (device < 0) cannot launch kernels");
+  if (G < 1 || G > NOISE_BATCH_MAX_GRAPHS)
+    return fail(ctx, DDK_ERR_INVALID, "ddk_randomize_position_batch: G must be in [1, " + std::to_string(NOISE_BATCH_MAX_GRAPHS) + "]");
+  if (N < G || (int64_t)N > (int64_t)G * MAX_LIG)
+    return fail(ctx, DDK_ERR_INVALID, "ddk_randomize_position_batch: N must be in [G, G * " + std::to_string(MAX_LIG) + "] (n_lig of a graph is in [1, " +
+                                          std::to_string(MAX_LIG) + "])");
+  if (T < 0 || (int64_t)T > (int64_t)G * NOISE_BATCH_MAX_ROT)
+    return fail(ctx, DDK_ERR_INVALID, "ddk_randomize_position_batch: T must be in [0, G * " + std::to_string(NOISE_BATCH_MAX_ROT) + "]");
+  if (mask_bytes < 0) return fail(ctx, DDK_ERR_INVALID, "ddk_randomize_position_batch: mask_bytes must be >= 0");
+  if (!(tr_sigma_max >= 0.f) || !(tr_sigma_max < INFINITY)) return fail(ctx, DDK_ERR_INVALID, "ddk_randomize_position_batch: tr_sigma_max must be finite and >= 0");
+  if (!pos || !node_ptr || !stream_id || !sample) return fail(ctx, DDK_ERR_INVALID, "ddk_randomize_position_batch: null argument (pos, node_ptr, stream_id, sample)");
+  if (!pos_out || !status_out) return fail(ctx, DDK_ERR_INVALID, "ddk_randomize_position_batch: null output (pos_out, status_out)");
+  if (tor_ptr && (!mask_ptr || (T > 0 && (!rot_bonds || !mask_rotate))))
+    return fail(ctx, DDK_ERR_INVALID, "ddk_randomize_position_batch: tor_ptr without the rotor tables (mask_ptr, and with T > 0 rot_bonds, mask_rotate)");
+  RandPosBatchArgs A{pos, node_ptr, tor_ptr, mask_ptr, rot_bonds, mask_rotate, stream_id, sample, (uint32_t)seed, (uint32_t)(seed >> 32), tr_sigma_max,
+                     G, N, T, mask_bytes, pos_out, status_out};
+  hipError_t e = launch_randomize_batch(A, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "randomize_position_batch launch");
   return DDK_OK;
 }

@@ -368,6 +368,21 @@ struct ConformerBatchArgs {
   int32_t* status_out;            // [G]
 };
 hipError_t launch_modify_conformer_batch(const ConformerBatchArgs& A, hipStream_t s);
+// the ragged batch form of randomize_position (ddk_randomize_position_batch): the tables of ConformerBatchArgs, and per graph the generator's stream and sample
+struct RandPosBatchArgs {
+  const float* pos;               // [N, 3]
+  const int32_t *node_ptr, *tor_ptr, *mask_ptr;      // [G + 1] each; tor_ptr null: no torsions are drawn (no_torsion)
+  const int32_t* rot_bonds;       // [T, 2] graph-local (u, v)
+  const uint8_t* mask_rotate;     // the graphs' [R_g, n_g] blocks, graph g at mask_ptr[g]
+  const uint64_t* stream_id;      // [G]
+  const int32_t* sample;          // [G]
+  uint32_t seed_lo, seed_hi;
+  float tr_sigma;
+  int G, N, T, mask_bytes;
+  float* pos_out;                 // [N, 3]
+  int32_t* status_out;            // [G]
+};
+hipError_t launch_randomize_batch(const RandPosBatchArgs& A, hipStream_t s);
 
 int conf_model_finalize(ddk_ctx* ctx);   // conf.hip (all-atom confidence model)
 void conf_complex_free(ddk_complex* cx);

@@ -41,12 +41,23 @@ def get_ar_model(args, score_model_args, device, training=True):
     """utils/model_utils.py:104-152 for `use_pretrained_score: true` AR models (the shipped disco_diffdockS_ar_model).
     The checkpoint of the ORIGINAL score model (args.original_model_dir/args.ckpt) is not needed at inference: the AR
     checkpoint overwrites it (evaluate.py:179-180), so it is only loaded when present."""
-    if training:
-        raise RuntimeError('ddk: AR model training is outside the accelerated hot path (training=False only)')
     if not ('use_pretrained_score' in args and args.use_pretrained_score):
         raise RuntimeError('ddk: only AR models built on the pretrained score model (use_pretrained_score) are implemented')
-    from .pretrained_score_encoder import PretrainedScoreEncoder
+    from .pretrained_score_encoder import PretrainedScoreEncoder, TrainablePretrainedScoreEncoder
     t_to_sigma = partial(t_to_sigma_compl, args=score_model_args)
+    if training:      # utils/model_utils.py:104-152 with training=True: the trainable classes, logits out (apply_gumbel_softmax=False)
+        import os
+        model = _trainable_score_model(score_model_args, device, t_to_sigma)
+        ckpt = os.path.join(str(getattr(args, 'original_model_dir', '')), str(getattr(args, 'ckpt', '')))
+        if getattr(args, 'original_model_dir', None) and getattr(args, 'ckpt', None) and os.path.exists(ckpt):
+            state = torch.load(ckpt, map_location='cpu')
+            wrapped = any(k.startswith('score_model.') for k in state)      # a ModelWrapper checkpoint: the score model's part (the encoder is not used)
+            model.load_state_dict({k[len('score_model.'):]: v for k, v in state.items() if k.startswith('score_model.')} if wrapped else state, strict=True)
+        ar = TrainablePretrainedScoreEncoder(pretrained_score_model=model, ns=args.ns, latent_dim=1, latent_vocab=score_model_args.latent_vocab,
+                                             latent_no_batchnorm=args.latent_no_batchnorm, latent_dropout=args.latent_dropout,
+                                             latent_hidden_dim=args.latent_hidden_dim, input_latent_dim=score_model_args.latent_dim,
+                                             apply_gumbel_softmax=False)
+        return ar.to(device)
     model = get_model(score_model_args, device, t_to_sigma)
     score_model = getattr(model, 'score_model', model)
     ar = PretrainedScoreEncoder(pretrained_score_model=score_model, ns=args.ns, latent_dim=1,
@@ -56,13 +67,9 @@ def get_ar_model(args, score_model_args, device, training=True):
     return ar.to(device)
 
 
-def get_trainable_model(args, device, t_to_sigma=None):
-    """utils/model_utils.py:25-101 (get_model) for TRAINING: ``train_model.TrainableScoreModel``, and with ``args.latent_dim > 0`` (``latent_vocab == 1``)
-    ``latent_encoder.TPEncoder`` in front of it in a ``train_model.LatentModelWrapper``, whose state_dict has the ``encoder.`` / ``score_model.`` keys of
-    the reference's ``ModelWrapper`` checkpoints.  The encoder reads ``encoder_ns``, ``encoder_nv``, ``encoder_num_conv_layers``,
-    ``encoder_cross_max_distance``, ``encoder_no_esm``, ``latent_*`` and ``training_latent_temperature`` as lines 70-94 there do."""
-    from .latent_encoder import TPEncoder
-    from .train_model import LatentModelWrapper, TrainableScoreModel
+def _trainable_score_model(args, device, t_to_sigma=None):
+    """the ``train_model.TrainableScoreModel`` of a model_parameters.yml Namespace (the score model of ``get_trainable_model`` and of the trainable AR model)"""
+    from .train_model import TrainableScoreModel
     g = lambda k, d: getattr(args, k, d)
     if getattr(args, 'all_atoms', False):
         raise RuntimeError('ddk: get_trainable_model: all_atoms is not implemented (the coarse-grained score model trains)')
@@ -70,17 +77,30 @@ def get_trainable_model(args, device, t_to_sigma=None):
     if latent_dim > 0 and g('latent_vocab', 0) != 1:
         raise RuntimeError('ddk: get_trainable_model: latent_vocab must be 1 whenever latent_dim > 0 (the equivariant-latent models only)')
     lm = 'esm' if g('esm_embeddings_path', None) is not None else None
-    sh_lmax = g('sh_lmax', 2)
-    score_model = TrainableScoreModel(
+    return TrainableScoreModel(
         t_to_sigma=t_to_sigma, device=device, no_torsion=args.no_torsion, num_conv_layers=args.num_conv_layers, lig_max_radius=args.max_radius,
         scale_by_sigma=args.scale_by_sigma, sigma_embed_dim=args.sigma_embed_dim, ns=args.ns, nv=args.nv, distance_embed_dim=args.distance_embed_dim,
-        cross_distance_embed_dim=args.cross_distance_embed_dim, batch_norm=not args.no_batch_norm, dropout=args.dropout, sh_lmax=sh_lmax,
+        cross_distance_embed_dim=args.cross_distance_embed_dim, batch_norm=not args.no_batch_norm, dropout=args.dropout, sh_lmax=g('sh_lmax', 2),
         use_second_order_repr=args.use_second_order_repr, cross_max_distance=args.cross_max_distance, dynamic_max_cross=args.dynamic_max_cross,
         lm_embedding_type=lm, use_old_atom_encoder=g('use_old_atom_encoder', True), latent_dim=latent_dim, latent_vocab=g('latent_vocab', 0),
         latent_cross_attention=g('latent_cross_attention', False), new_cross_attention=g('new_cross_attention', False),
         latent_droprate=g('latent_droprate', 0), embedding_scale=args.embedding_scale,
         sigma_limits=dict(tr_sigma_min=args.tr_sigma_min, tr_sigma_max=args.tr_sigma_max, rot_sigma_min=args.rot_sigma_min,
-                          rot_sigma_max=args.rot_sigma_max, tor_sigma_min=args.tor_sigma_min, tor_sigma_max=args.tor_sigma_max))
+                          rot_sigma_max=args.rot_sigma_max, tor_sigma_min=args.tor_sigma_min, tor_sigma_max=args.tor_sigma_max)).to(device)
+
+
+def get_trainable_model(args, device, t_to_sigma=None):
+    """utils/model_utils.py:25-101 (get_model) for TRAINING: ``train_model.TrainableScoreModel``, and with ``args.latent_dim > 0`` (``latent_vocab == 1``)
+    ``latent_encoder.TPEncoder`` in front of it in a ``train_model.LatentModelWrapper``, whose state_dict has the ``encoder.`` / ``score_model.`` keys of
+    the reference's ``ModelWrapper`` checkpoints.  The encoder reads ``encoder_ns``, ``encoder_nv``, ``encoder_num_conv_layers``,
+    ``encoder_cross_max_distance``, ``encoder_no_esm``, ``latent_*`` and ``training_latent_temperature`` as lines 70-94 there do."""
+    from .latent_encoder import TPEncoder
+    from .train_model import LatentModelWrapper
+    g = lambda k, d: getattr(args, k, d)
+    score_model = _trainable_score_model(args, device, t_to_sigma)
+    latent_dim = int(g('latent_dim', 0))
+    lm = 'esm' if g('esm_embeddings_path', None) is not None else None
+    sh_lmax = g('sh_lmax', 2)
     if latent_dim == 0:
         return score_model.to(device)
     encoder = TPEncoder(device=device, no_torsion=args.no_torsion, num_conv_layers=args.encoder_num_conv_layers, lig_max_radius=args.max_radius,

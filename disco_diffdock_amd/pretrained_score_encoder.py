@@ -4,6 +4,8 @@
 unconditional = 1 and the partially decoded input latents is the ordinary score-model forward of the AR checkpoint's own
 score-model copy (its own ddk context), the two predictor MLPs with BatchNorm1d(eval) are ``ddk_ar_logits`` and the per-graph
 pick + one-hot write is ``ddk_ar_decode`` (csrc/k_ar.hip).  ``encode_ar`` never reads the device back."""
+import collections
+
 import torch
 from torch import nn
 
@@ -125,4 +127,115 @@ class PretrainedScoreEncoder(GenericEncoder):
         return lg[:, None, :]
 
     def forward(self, data):
-        raise RuntimeError('ddk: use encode_ar() / logits(); the Gumbel-softmax training path is outside the hot path')
+        raise RuntimeError('ddk: use encode_ar() / logits(); the trainable class is TrainablePretrainedScoreEncoder (model_utils.get_ar_model(training=True))')
+
+
+# what ``TrainablePretrainedScoreEncoder.forward`` returns with apply_gumbel_softmax=False: the per-node logits [N_lig, 1], [N_rec, 1] and the int64 [G + 1]
+# prefixes of the graphs' rows, all on the device (what ``tensor_layers.ragged_node_cross_entropy`` takes)
+ARLogits = collections.namedtuple('ARLogits', ('logit_l', 'logit_r', 'lig_ptr', 'rec_ptr'))
+
+AR_GUMBEL_SEED_INDEX = 24      # the sub-seed of the AR model's Gumbel draw: the score model takes 0 .. num_conv_layers + 2 (at most 18), an oracle encoder 32 and up
+
+
+class TrainablePretrainedScoreEncoder(nn.Module):
+    """The reference's ``PretrainedScoreEncoder`` (models/pretrained_score_encoder.py) for training: a ``train_model.TrainableScoreModel`` with
+    ``latent_dim >= 1`` and at least three conv layers under ``pretrained_score_model``, and the two predictors as real ``nn.Sequential`` modules under the
+    reference's keys.  ``state_dict()`` has the keys of the inference class (the score model's under ``pretrained_score_model.`` plus
+    ``PretrainedScoreEncoder.predictor_spec()``), so what is trained here loads into ``model_utils.get_ar_model(training=False)`` with ``strict=True`` and
+    an AR checkpoint loads here.  ``ns``: the AR settings' (the predictors read ``[x[:, :ns] | x[:, -ns:]]`` of the score model's node rows; it may be
+    smaller than the score model's 24).  Supported: latent_vocab=1, latent_dim=1 (one logit per node); anything else raises and names the argument."""
+
+    def __init__(self, pretrained_score_model, ns, latent_dim, latent_vocab, latent_no_batchnorm=False, latent_dropout=0.0, latent_hidden_dim=128,
+                 input_latent_dim=0, apply_gumbel_softmax=True):
+        super().__init__()
+        from .latent_encoder import _predictor
+        from .train_model import TrainableScoreModel
+        sm = pretrained_score_model
+        if not isinstance(sm, TrainableScoreModel) or sm.latent_dim < 1:
+            raise RuntimeError('ddk: TrainablePretrainedScoreEncoder: pretrained_score_model must be a TrainableScoreModel with latent_dim >= 1')
+        refused = [('latent_vocab', latent_vocab != 1, 'must be 1: the equivariant one-hot-over-nodes latent only'),
+                   ('latent_dim', latent_dim != 1, 'must be 1: the AR predictors emit one logit per node (utils/model_utils.py:133-139)'),
+                   ('num_conv_layers', len(sm.conv_layers) < 3, 'of the score model must be >= 3: the predictors read [x[:, :ns] | x[:, -ns:]] of the full rows'),
+                   ('input_latent_dim', int(input_latent_dim) != sm.latent_dim, f"must be the score model's latent_dim ({sm.latent_dim})"),
+                   ('ns', not 1 <= int(ns) <= sm.ns, f"must be in 1..{sm.ns}, the score model's ns"),
+                   ('latent_dropout', not 0.0 <= float(latent_dropout) < 1.0, 'must be in [0, 1)'),
+                   ('latent_hidden_dim', int(latent_hidden_dim) < 1, 'must be positive')]
+        for name, bad, why in refused:
+            if bad:
+                raise RuntimeError(f'ddk: TrainablePretrainedScoreEncoder: {name} {why}')
+        self.ns, self.latent_dim, self.latent_vocab = int(ns), 1, 1
+        self.latent_temperature = 1.0
+        self.input_latent_dim = int(input_latent_dim)
+        self.apply_gumbel_softmax = bool(apply_gumbel_softmax)
+        self.pretrained_score_model = sm
+        self.latent_s_predictor = _predictor(2 * self.ns, int(latent_hidden_dim), 1, not latent_no_batchnorm, latent_dropout)
+        self.latent_r_predictor = _predictor(2 * self.ns, int(latent_hidden_dim), 1, not latent_no_batchnorm, latent_dropout)
+
+    # what ``ar_training.ar_batch`` and ``training``'s helpers read off the model they are handed
+    @property
+    def ctx(self):
+        return self.pretrained_score_model.ctx
+
+    @property
+    def no_torsion(self):
+        return self.pretrained_score_model.no_torsion
+
+    @property
+    def tr_sigma_max(self):
+        return self.pretrained_score_model.tr_sigma_max
+
+    def logits(self, data, seed=None):
+        """models/pretrained_score_encoder.py:56-72: ``latent_h = input_latent``, ``unconditional = 1`` and ``complex_t = 1`` for every graph, the score
+        model's ``embed`` and the two predictors: :data:`ARLogits`.  The pointer tables are ``data.lig_ptr`` / ``data.rec_ptr`` where the batch has them
+        (``ar_training.ar_batch`` sets them); otherwise they are made from the batch vectors, with one read-back that checks those."""
+        from .tensor_layers import _graph_ptrs
+        sm = self.pretrained_score_model
+        lig, rec = data['ligand'], data['receptor']
+        if not lig.pos.is_cuda:
+            raise RuntimeError('ddk TrainablePretrainedScoreEncoder runs on the GPU only (no CPU fallback)')
+        dev, B = lig.pos.device, int(data.num_graphs)
+        for side in (lig, rec):
+            if getattr(side, 'input_latent', None) is None:
+                raise RuntimeError("ddk: TrainablePretrainedScoreEncoder reads data['ligand' | 'receptor'].input_latent; the batch has none "
+                                   '(ar_training.ar_batch sets it)')
+            side.latent_h = side.input_latent.to(dev).float()
+            side.unconditional = torch.ones((side.latent_h.shape[0], 1), device=dev)
+        data.complex_t = {k: torch.ones(B, device=dev) for k in ('tr', 'rot', 'tor')}
+        lig_attr, rec_attr = sm.embed(data, seed)
+        ns = self.ns
+        logit_l = self.latent_s_predictor(torch.cat([lig_attr[:, :ns], lig_attr[:, -ns:]], dim=1))
+        logit_r = self.latent_r_predictor(torch.cat([rec_attr[:, :ns], rec_attr[:, -ns:]], dim=1))
+        lig_ptr, rec_ptr = getattr(data, 'lig_ptr', None), getattr(data, 'rec_ptr', None)
+        if lig_ptr is None or rec_ptr is None:
+            (lig_ptr, rec_ptr), probes = _graph_ptrs((lig.batch.to(dev), rec.batch.to(dev)), B)
+            for what, (descent, first, last) in zip(("data['ligand'].batch", "data['receptor'].batch"), probes):
+                if descent > 0 or first < 0 or last >= B:
+                    raise RuntimeError(f'ddk: TrainablePretrainedScoreEncoder takes {what} sorted by graph with entries in [0, {B})')
+        return ARLogits(logit_l, logit_r, lig_ptr, rec_ptr)
+
+    @staticmethod
+    def logit_list(pred):
+        """:data:`ARLogits` -> the reference's list of per-graph [1, 1, n_lig_g + n_rec_g] tensors (one read-back of the two pointer tables)"""
+        n_l, n_r = ((p[1:] - p[:-1]).tolist() for p in (pred.lig_ptr, pred.rec_ptr))
+        return [torch.cat([l, r], dim=0).T.unsqueeze(0) for l, r in zip(torch.split(pred.logit_l, n_l), torch.split(pred.logit_r, n_r))]
+
+    def forward(self, data, seed=None):
+        """``apply_gumbel_softmax=False`` (training, as ``get_ar_model`` builds it): :data:`ARLogits`; True: (latent_l [N_lig, 1], latent_r [N_rec, 1]), per
+        graph a straight-through one-hot over its nodes at ``self.latent_temperature`` (``ragged_gumbel_softmax``; the graphs' names in ``data.name``).
+        ``seed``: of the device ops' dropout masks and the Gumbel noise (None: one draw from torch's default CPU generator where one is needed)."""
+        from .runtime import stream_id
+        from .tensor_layers import _draw_seed, _layer_seed, ragged_gumbel_softmax
+        if seed is None and (self.training or self.apply_gumbel_softmax):
+            seed = _draw_seed()
+        pred = self.logits(data, seed)
+        if not self.apply_gumbel_softmax:
+            return pred
+        B = int(data.num_graphs)
+        names = getattr(data, 'name', None)
+        names = [names] if isinstance(names, str) else names
+        if names is None or len(names) != B:
+            raise RuntimeError(f"ddk: TrainablePretrainedScoreEncoder takes the complexes' names in data.name ({B} of them): the Gumbel noise of a graph "
+                               'is drawn from runtime.stream_id(name)')
+        dev = pred.logit_l.device
+        return ragged_gumbel_softmax(pred.logit_l, pred.logit_r, data['ligand'].batch.to(dev), data['receptor'].batch.to(dev), self.latent_temperature,
+                                     _layer_seed(seed, AR_GUMBEL_SEED_INDEX), [stream_id(n) for n in names])

@@ -59,6 +59,8 @@ RNG_TIME_PURPOSE = 11
 # the latent of the DisCo score model: the keep flag of a complex (ddk_rng_latent_keep) and the Gumbel noise (DDK_GUMBEL_LAYOUT: step = the draw index, block = d)
 RNG_LATENT_KEEP_PURPOSE, RNG_GUMBEL_PURPOSE = 12, 13
 GUMBEL_LAYOUT, GUMBEL_TAG = 1, 0x47554D42
+# the decoding index of an AR training item (ddk_rng_decoding_index): step = the draw index, block 0, word 0
+RNG_DECODING_INDEX_PURPOSE = 14
 # the ragged batch forms (ddk_rng_perturbation_batch, ddk_modify_conformer_batch, ddk_score_matching_loss_batch): limits (csrc/model.h) and status words
 NOISE_BATCH_MAX_GRAPHS, NOISE_BATCH_MAX_LIG, NOISE_BATCH_MAX_ROT = 65536, 256, 1024
 CONFORMER_BATCH_STATUS = ('done', None, 'a bond index outside the graph, or u == v', 'a coordinate that is not finite', 'a node_ptr / tor_ptr / mask_ptr entry out of range')
@@ -909,6 +911,89 @@ class Context:
                                                out.ctypes.data_as(C.c_void_p)), 'ddk_rng_latent_keep')
         return out
 
+    def decoding_index(self, seed, streams, D, draw=0, sample=0):
+        """the decoding index in 0 .. D - 1 (int32 host array) of each complex of ``streams`` for draw ``draw``: purpose RNG_DECODING_INDEX_PURPOSE, in
+        integer arithmetic (ddk_rng_decoding_index; computed on the host, no kernel)"""
+        for k, v in dict(draw=draw, sample=sample, D=D).items():
+            if not -(1 << 31) <= int(v) < 1 << 31:
+                raise ValueError(f'ddk: {k} = {v} does not fit an int32')
+        st = np.ascontiguousarray([_u64(v, 'rng_stream') for v in streams], dtype=np.uint64)
+        out = np.empty(st.size, dtype=np.int32)
+        self._check(self.L.ddk_rng_decoding_index(self.h, C.c_uint64(_u64(seed, 'seed')), st.size, st.ctypes.data_as(C.c_void_p), int(sample), int(draw), int(D),
+                                                  out.ctypes.data_as(C.c_void_p)), 'ddk_rng_decoding_index')
+        return out
+
+    # ---- the AR model's ragged node cross-entropy ------------------------------------------------------
+    @staticmethod
+    def _node_ce_operands(logit_l, logit_r, lig_ptr, rec_ptr, teacher_l, teacher_r, column, soft, who):
+        """everything the host can see of the operands of the two node cross-entropy calls: shapes, dtypes, D, G, contiguity, the device"""
+        for name, t in (('logit_l', logit_l), ('logit_r', logit_r), ('teacher_l', teacher_l), ('teacher_r', teacher_r)):
+            if not torch.is_tensor(t) or not t.is_cuda:
+                raise RuntimeError(f'ddk: {who} takes {name} as a tensor on the GPU (no CPU fallback)')
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise RuntimeError(f'ddk: {who} takes {name} as a contiguous float32 tensor; got {t.dtype}, contiguous = {t.is_contiguous()}')
+        dev = logit_l.device
+        for name, t, rows in (('logit_l', logit_l, teacher_l.shape[0]), ('logit_r', logit_r, teacher_r.shape[0])):
+            if not (t.dim() == 1 or (t.dim() == 2 and t.shape[1] == 1)) or t.shape[0] != rows:
+                raise RuntimeError(f'ddk: {who} takes {name} as one logit per row of its teacher table ([{rows}] or [{rows}, 1]); got {tuple(t.shape)}')
+        if teacher_l.dim() != 2 or teacher_r.dim() != 2 or teacher_l.shape[1] != teacher_r.shape[1] or not 1 <= teacher_l.shape[1] <= 4:
+            raise RuntimeError(f'ddk: {who} takes the teacher tables [N_lig, D] and [N_rec, D] with D in 1..4; got {tuple(teacher_l.shape)} and '
+                               f'{tuple(teacher_r.shape)}')
+        for name, t in (('lig_ptr', lig_ptr), ('rec_ptr', rec_ptr)):
+            if not torch.is_tensor(t) or t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous() or t.shape != lig_ptr.shape:
+                raise RuntimeError(f'ddk: {who} takes {name} as a contiguous int64 vector [G + 1]')
+        G = lig_ptr.shape[0] - 1
+        if not 1 <= G <= 65536:
+            raise RuntimeError(f'ddk: {who} takes 1..65536 graphs; got {G}')
+        if not torch.is_tensor(column) or column.dtype != torch.int32 or column.shape != (G,) or not column.is_contiguous():
+            raise RuntimeError(f'ddk: {who} takes column as a contiguous int32 vector [G] = [{G}]')
+        for name, t in (('logit_r', logit_r), ('teacher_l', teacher_l), ('teacher_r', teacher_r), ('lig_ptr', lig_ptr), ('rec_ptr', rec_ptr), ('column', column)):
+            if t.device != dev:
+                raise RuntimeError(f'ddk: {who} takes every operand on one device; {name} is on {t.device}, logit_l on {dev}')
+        if soft not in (0, 1, False, True):
+            raise RuntimeError(f'ddk: {who} takes soft as 0 or 1; got {soft!r}')
+        return G, teacher_l.shape[1]
+
+    def node_cross_entropy(self, logit_l, logit_r, lig_ptr, rec_ptr, teacher_l, teacher_r, column, soft=False, out=None):
+        """The cross-entropy of every graph over its ligand nodes followed by its receptor nodes (ddk_node_cross_entropy_batch): (loss [G] float32, pick [G],
+        target [G] int64, saved [G, 2] float64 = what ``node_cross_entropy_backward`` reads).  ``out``: the four tensors to write into (a graph with a bad
+        pointer pair or column is left unwritten); default: fresh ones, loss NaN and the indices -1 where nothing is written."""
+        G, D = self._node_ce_operands(logit_l, logit_r, lig_ptr, rec_ptr, teacher_l, teacher_r, column, soft, 'node_cross_entropy')
+        dev = logit_l.device
+        if out is None:
+            out = (torch.full((G,), float('nan'), dtype=torch.float32, device=dev), torch.full((G,), -1, dtype=torch.int64, device=dev),
+                   torch.full((G,), -1, dtype=torch.int64, device=dev), torch.zeros((G, 2), dtype=torch.float64, device=dev))
+        loss, pick, target, saved = out
+        for name, t, dtype, shape in (('loss', loss, torch.float32, (G,)), ('pick', pick, torch.int64, (G,)), ('target', target, torch.int64, (G,)),
+                                      ('saved', saved, torch.float64, (G, 2))):
+            if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+                raise RuntimeError(f'ddk: node_cross_entropy takes out.{name} as a contiguous {dtype} tensor {shape} on the device of the logits')
+        self._check(self.L.ddk_node_cross_entropy_batch(self.h, G, D, _ptr(logit_l), logit_l.shape[0], _ptr(logit_r), logit_r.shape[0], _ptr(lig_ptr),
+                                                        _ptr(rec_ptr), _ptr(teacher_l), _ptr(teacher_r), _ptr(column), int(bool(soft)), _ptr(loss), _ptr(pick),
+                                                        _ptr(target), _ptr(saved), _stream()), 'ddk_node_cross_entropy_batch')
+        return loss, pick, target, saved
+
+    def node_cross_entropy_backward(self, grad, logit_l, logit_r, lig_ptr, rec_ptr, teacher_l, teacher_r, column, target, saved, soft=False, out=None):
+        """(grad_logit_l, grad_logit_r) = grad_g (softmax(s) - label) per graph from the saved log-sum-exps (ddk_node_cross_entropy_batch_backward).  ``out``:
+        the two tables to write into; default: zeros (rows of no valid graph stay zero)."""
+        G, D = self._node_ce_operands(logit_l, logit_r, lig_ptr, rec_ptr, teacher_l, teacher_r, column, soft, 'node_cross_entropy_backward')
+        dev = logit_l.device
+        grad = _need_cuda(grad).contiguous().float()
+        if tuple(grad.shape) != (G,) or grad.device != dev:
+            raise RuntimeError(f'ddk: node_cross_entropy_backward takes grad [G] = [{G}] on the device of the logits; got {tuple(grad.shape)}')
+        if target.dtype != torch.int64 or tuple(target.shape) != (G,) or saved.dtype != torch.float64 or tuple(saved.shape) != (G, 2) or \
+                not target.is_contiguous() or not saved.is_contiguous() or target.device != dev or saved.device != dev:
+            raise RuntimeError('ddk: node_cross_entropy_backward takes target (int64 [G]) and saved (float64 [G, 2]) as node_cross_entropy returned them')
+        g_l, g_r = (torch.zeros_like(logit_l), torch.zeros_like(logit_r)) if out is None else out
+        for name, t, like in (('grad_logit_l', g_l, logit_l), ('grad_logit_r', g_r, logit_r)):
+            if t.dtype != torch.float32 or t.shape != like.shape or not t.is_contiguous() or t.device != dev:
+                raise RuntimeError(f'ddk: node_cross_entropy_backward takes out.{name} as a contiguous float32 tensor of the shape of its logits')
+        self._check(self.L.ddk_node_cross_entropy_batch_backward(self.h, G, D, _ptr(logit_l), logit_l.shape[0], _ptr(logit_r), logit_r.shape[0], _ptr(lig_ptr),
+                                                                 _ptr(rec_ptr), _ptr(teacher_l), _ptr(teacher_r), _ptr(column), int(bool(soft)), _ptr(grad),
+                                                                 _ptr(target), _ptr(saved), _ptr(g_l), _ptr(g_r), _stream()),
+                    'ddk_node_cross_entropy_batch_backward')
+        return g_l, g_r
+
     def tp_weight_numel(self, layer):
         """W of conv layer ``layer``: the length of a FasterTensorProduct weight row (tensor_layers.py:56-63)."""
         return tp_id_shape(layer, self.cfg.ns, self.cfg.nv)['W']
@@ -1290,6 +1375,46 @@ class Context:
         self._check(self.L.ddk_modify_conformer_batch(self.h, G, N, _ptr(pos), _ptr(node_ptr), T or 0, _ptr(rb), _ptr(mr), _ptr(mp), mask_bytes, _ptr(tp),
                                                       _ptr(tr_update), _ptr(rot_update), _ptr(tor), _ptr(out), _ptr(status), _stream()),
                     'ddk_modify_conformer_batch')
+        return (out, status) if return_status else out
+
+    def randomize_position_batch(self, seed, pos, node_ptr, rot_bonds, mask_rotate, mask_ptr, tor_ptr, streams, samples, tr_sigma_max, T=None,
+                                 no_torsion=False, return_status=False):
+        """randomize_position for a ragged batch of different ligands (ddk_randomize_position_batch): the tables of :meth:`modify_conformer_batch`, and per
+        graph the stream id (uint64 bit patterns, int64 [G]) and the global sample index (int32 [G]); graph g's pose is bit for bit what
+        :meth:`rng_initial` + ``Complex.randomize_position`` give that ligand alone at (seed, stream, sample).  ``no_torsion``: no torsions are drawn and
+        the rotor tables are not read.  Returns pos_out [N, 3]; with ``return_status`` also the int32 status [G] (CONFORMER_BATCH_STATUS; a graph with a
+        status other than 0 is not written).  Host arrays are uploaded; nothing is read back."""
+        dev = torch.device('cuda', self.device)
+        pos = self._dev(pos, torch.float32).reshape(-1, 3)
+        self._check_ptr('node_ptr', node_ptr, pos.shape[0], 'the nodes must be grouped by graph')
+        node_ptr = self._dev(node_ptr, torch.int32)
+        G, N = node_ptr.numel() - 1, pos.shape[0]
+        st = streams if torch.is_tensor(streams) else np.asarray([_u64(v, 'rng_stream') for v in streams], dtype=np.uint64).view(np.int64)
+        st, samples = self._dev(st, torch.int64), self._dev(samples, torch.int32)
+        for name, t in (('streams', st), ('samples', samples)):
+            if t.numel() != G:
+                raise ValueError(f'ddk: {name} must hold {G} entries for {G} graphs, got {t.numel()} (the library reads it through a raw pointer)')
+        rb = mr = mp = tp = None
+        mask_bytes = 0
+        if no_torsion:
+            T = 0
+        else:
+            rb = self._dev(rot_bonds, torch.int32).reshape(-1, 2)
+            T = rb.shape[0] if T is None else int(T)
+            mr = self._dev(mask_rotate, torch.uint8).reshape(-1)
+            self._check_ptr('tor_ptr', tor_ptr, T, 'the rotor counts of the graphs')
+            self._check_ptr('mask_ptr', mask_ptr, None, 'the mask blocks of the graphs')
+            mp, tp = self._dev(mask_ptr, torch.int32), self._dev(tor_ptr, torch.int32)
+            mask_bytes = mr.numel()
+            for name, t, n in (('rot_bonds', rb, 2 * T), ('mask_ptr', mp, G + 1), ('tor_ptr', tp, G + 1)):
+                if t.numel() != n:
+                    raise ValueError(f'ddk: {name} must hold {n} entries (G = {G}, T = {T}), got {t.numel()} (the library reads it through a raw pointer)')
+        out = torch.empty_like(pos)
+        status = torch.empty(max(G, 1), dtype=torch.int32, device=dev)
+        s, _, _ = self._rng_args(seed, 0, dict(G=G, N=N, T=T, mask_bytes=mask_bytes))
+        self._check(self.L.ddk_randomize_position_batch(self.h, s, G, N, _ptr(pos), _ptr(node_ptr), T, _ptr(rb), _ptr(mr), _ptr(mp), mask_bytes, _ptr(tp),
+                                                        _ptr(st), _ptr(samples), float(tr_sigma_max), _ptr(out), _ptr(status), _stream()),
+                    'ddk_randomize_position_batch')
         return (out, status) if return_status else out
 
     def _loss_batch_args(self, tr_pred, rot_pred, tor_pred, tr_score, rot_score, tor_score, tr_sigma, so3_score_norm, torus_score_norm2, tor_ptr, T):

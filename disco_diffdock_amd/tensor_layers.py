@@ -631,6 +631,46 @@ def ragged_gumbel_softmax(logit_l, logit_r, lig_batch, rec_batch, temperature, s
     return _ctx_of(logit_l).gumbel_softmax(*args)[:2]
 
 
+class _RaggedNodeCrossEntropyFunction(torch.autograd.Function):
+    """ddk_node_cross_entropy_batch with ddk_node_cross_entropy_batch_backward as its vector-Jacobian product, for the two logit tables only; saved: the
+    operands and per GRAPH the two log-sum-exps and the target.  No atomics: the same bits on every run."""
+
+    @staticmethod
+    def forward(fctx, logit_l, logit_r, lig_ptr, rec_ptr, teacher_l, teacher_r, column, soft):
+        ctx = _ctx_of(logit_l)
+        loss, pick, target, saved = ctx.node_cross_entropy(logit_l, logit_r, lig_ptr, rec_ptr, teacher_l, teacher_r, column, soft)
+        fctx.save_for_backward(logit_l, logit_r, lig_ptr, rec_ptr, teacher_l, teacher_r, column, target, saved)
+        fctx.ddk, fctx.soft = ctx, soft
+        fctx.mark_non_differentiable(pick, target)
+        return loss, pick, target
+
+    @staticmethod
+    @once_differentiable
+    def backward(fctx, grad, _pick, _target):
+        logit_l, logit_r, lig_ptr, rec_ptr, teacher_l, teacher_r, column, target, saved = fctx.saved_tensors
+        with torch.cuda.device(logit_l.device):
+            g_l, g_r = fctx.ddk.node_cross_entropy_backward(grad, logit_l, logit_r, lig_ptr, rec_ptr, teacher_l, teacher_r, column, target, saved, fctx.soft)
+        need = fctx.needs_input_grad
+        return (g_l if need[0] else None, g_r if need[1] else None) + (None,) * 6
+
+
+def ragged_node_cross_entropy(logit_l, logit_r, lig_ptr, rec_ptr, teacher_l, teacher_r, column, soft=False):
+    """The AR model's loss: per graph, the cross-entropy of the student's logits over the graph's ligand nodes followed by its receptor nodes against
+    column ``column[g]`` of the teacher's tables, the reference's loop of one ``F.cross_entropy`` per graph (autoregressive/train_ar.py:116-127, 152-177)
+    in one launch and without a read-back.  ``logit_l`` [N_lig] or [N_lig, 1], ``logit_r`` [N_rec] or [N_rec, 1] (float32, contiguous); ``lig_ptr`` /
+    ``rec_ptr``: int64 [G + 1] prefixes of the graphs' rows; ``teacher_l`` [N_lig, D], ``teacher_r`` [N_rec, D], D in 1..4; ``column``: int32 [G];
+    all on one device.  ``soft=False``: the label is the teacher column's argmax (the sampled one-hot labels); ``soft=True``: softmax of the teacher
+    column (``--no_sampling``).  Returns (loss [G], pick [G], target [G]): the student's and the teacher's argmax, the lowest position on a tie.  A graph
+    with a pointer pair that is no range of its table or a column outside 0 .. D - 1 gets loss NaN, indices -1 and no gradient.  Differentiable in the
+    two logit tables only; with neither asking for a gradient nothing is saved and no gradient is computed.  No atomics."""
+    if not (torch.is_tensor(logit_l) and logit_l.is_cuda):
+        raise RuntimeError('ddk ragged_node_cross_entropy runs on the GPU only (no CPU fallback)')
+    args = (logit_l, logit_r, lig_ptr, rec_ptr, teacher_l, teacher_r, column, bool(soft))
+    if torch.is_grad_enabled() and (logit_l.requires_grad or logit_r.requires_grad):
+        return _RaggedNodeCrossEntropyFunction.apply(*args)
+    return _ctx_of(logit_l).node_cross_entropy(*args)[:3]
+
+
 class _HeadConvFunction(torch.autograd.Function):
     """ddk_hconv_forward with ddk_hconv_backward as its vector-Jacobian product: node features to receiver rows through a head's
     FullyConnectedTensorProduct.  Saved for the backward: the node table, sh, h, the graph, and w2 / b2 where a requested gradient reads them; never the

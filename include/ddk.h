@@ -370,6 +370,36 @@ int ddk_gumbel_softmax_batch_backward(ddk_ctx* ctx, int32_t G, int32_t D, const 
 int ddk_rng_latent_keep(ddk_ctx* ctx, uint64_t seed, int32_t n, const uint64_t* stream_id /* HOST [n] */, int32_t sample, int32_t draw, float rate,
                         float* keep_out /* HOST [n] */);
 
+/* ---- The AR latent model's loss: cross-entropy over a graph's ligand nodes followed by its receptor nodes (position p = 0 .. n_g - 1), the reference's loop
+ *      of one F.cross_entropy per graph (autoregressive/train_ar.py:116-127, 152-177) for a collated batch in one launch, one workgroup of 256 threads per
+ *      graph.  s_p: the student's logit, logit_l [n_lig] / logit_r [n_rec] (the AR predictors emit one column); t_p: column c = column[g] of the teacher's
+ *      tables teacher_l [n_lig, D] / teacher_r [n_rec, D], 1 <= D <= 4.  The arithmetic, every reduction in fp64 and every operation as written:
+ *        pick   = the LOWEST p that holds max s_p        target = the LOWEST p that holds max t_p     (no p above -inf: position 0)
+ *        lse_s  = m_s + log(sum exp(s_p - m_s)), m_s = max s_p.  The sum in a fixed order: thread t of 256 adds the positions of the quads t, t + 256, ...
+ *                 (four positions each) in ascending order to a partial that starts from 0, the partials are added by a halving tree
+ *        soft = 0 (the reference's sampled labels):  q = target, loss = fl32(lse_s - s_q)
+ *        soft = 1 (its --no_sampling: the label is softmax of the encoder's logits):  lse_t as lse_s, p_t = exp(t_p - lse_t),
+ *                 loss = fl32(lse_s - sum p_t s_p), summed in the same order
+ *      out, [G] each: loss (fp32), pick, target (int64), and saved [G, 2] = (lse_s, lse_t) in fp64, which with target is all the backward needs: nothing
+ *      is saved per node.  The backward takes grad [G] and writes, element-wise in fp32,
+ *        grad_logit_p = grad_g * (fl32(exp(s_p - lse_s)) - target_p),   target_p = [p == q] (soft = 0) or fl32(exp(t_p - lse_t)) (soft = 1)
+ *      for EVERY row of a graph with valid tables, rows whose gradient is zero included; with soft = 0 it reads no teacher table (they may be NULL).
+ *      lig_ptr / rec_ptr: DEVICE int64 [G + 1], graph g owns the rows ptr[g] .. ptr[g + 1] - 1; column: DEVICE int32 [G].  A graph whose pointer pair is no
+ *      range of its table, whose column is outside 0 .. D - 1, or that has no node is left alone: none of its outputs is written, in either direction.
+ *      All tables DEVICE, fp32, contiguous.  One launch each, no atomics, no scratch, no node limit.  Limits: 1 <= G <= 65536, 1 <= D <= 4, soft 0 or 1. */
+int ddk_node_cross_entropy_batch(ddk_ctx* ctx, int32_t G, int32_t D, const float* logit_l, int64_t n_lig, const float* logit_r, int64_t n_rec,
+                                 const int64_t* lig_ptr, const int64_t* rec_ptr, const float* teacher_l, const float* teacher_r, const int32_t* column,
+                                 int32_t soft, float* loss, int64_t* pick, int64_t* target, double* saved /* [G, 2] */, void* stream);
+int ddk_node_cross_entropy_batch_backward(ddk_ctx* ctx, int32_t G, int32_t D, const float* logit_l, int64_t n_lig, const float* logit_r, int64_t n_rec,
+                                          const int64_t* lig_ptr, const int64_t* rec_ptr, const float* teacher_l, const float* teacher_r,
+                                          const int32_t* column, int32_t soft, const float* grad /* [G] */, const int64_t* target, const double* saved,
+                                          float* grad_logit_l, float* grad_logit_r, void* stream);
+/* ddk_rng_decoding_index: the decoding index of an AR training item (autoregressive/dataset_ar.py:83 draws it from an unseeded host generator),
+ * idx_out[i] = ((word >> 8) * D) >> 24 in integer arithmetic, in 0 .. D - 1, with `word` word 0 of block 0 of purpose 14 for (seed, stream_id[i], sample, draw).
+ * A HOST function as ddk_rng_latent_keep; 1 <= D <= 4. */
+int ddk_rng_decoding_index(ddk_ctx* ctx, uint64_t seed, int32_t n, const uint64_t* stream_id /* HOST [n] */, int32_t sample, int32_t draw, int32_t D,
+                           int32_t* idx_out /* HOST [n] */);
+
 /* The fixed-order segmented sum the radial conv and the head convs add a node's rows with (rtp_seg_kernel of csrc/k_rtp.hip), on its own: the backward of
  * a gather x[index].  nodes[n, :] = rows[order[ptr[n]], :] + rows[order[ptr[n] + 1], :] + ... + rows[order[ptr[n + 1] - 1], :], added in that order, one
  * thread per (node, column); a node without rows: exact zeros.  rows [*, D], nodes [n_nodes, D]: DEVICE, fp32, contiguous, 1 <= D <= 128; order: int32,
@@ -651,6 +681,7 @@ int ddk_ligand_transformation_mask(ddk_ctx* ctx, int32_t n_lig, const int32_t* b
  *                11 forward time (ddk_rng_forward_times below)   step = the draw index, block 0, word 0: t = the uniform u
  *                12 latent keep (ddk_rng_latent_keep above)      step = the draw index, block 0, word 0: keep iff u >= rate
  *                13 Gumbel noise (DDK_GUMBEL_LAYOUT above)       step = the draw index, block = the latent dimension d: words 0, 1 key the per-node generator
+ *                14 AR decoding index (ddk_rng_decoding_index above)   step = the draw index, block 0, word 0: idx = ((word >> 8) * D) >> 24
  *      Words -> draws, in fp32, every operation as written:
  *        uniform      u = (x >> 8) * 2^-24: in [0, 1), exact
  *        torsion      (float)pi * (2u - 1): the inner term is exact, one rounding
@@ -802,6 +833,21 @@ int ddk_modify_conformer_batch(ddk_ctx* ctx, int32_t G, int32_t N, const float* 
                                const int32_t* rot_bonds /* [T, 2] */, const uint8_t* mask_rotate /* [mask_bytes] */, const int32_t* mask_ptr /* [G + 1] */,
                                int32_t mask_bytes, const int32_t* tor_ptr /* [G + 1] */, const float* tr_update, const float* rot_update /* [G, 3] */,
                                const float* tor_update /* [T] or NULL */, float* pos_out /* [N, 3] */, int32_t* status_out /* [G] */, void* stream);
+/* ddk_randomize_position_batch: randomize_position(..., unbatched=True) (utils/sampling.py:12-34) for G DIFFERENT ligands in one collated table, the start
+ *   poses of an AR training batch.  pos / pos_out, node_ptr, rot_bonds, mask_rotate, mask_ptr, mask_bytes, tor_ptr and T as ddk_modify_conformer_batch takes
+ *   them; stream_id [G] (uint64) and sample [G] (int32): graph g is the global sample sample[g] of stream stream_id[g] under `seed`.  The workgroup of graph g
+ *   makes the draws of ddk_rng_initial itself (DDK_RNG_LAYOUT 1, purposes 1, 2 and 3: R_g torsion angles, the rotation, tr_sigma_max * z) and applies
+ *   ddk_randomize_position's arithmetic: the torsion rotations in bond order (axis pos_u - pos_v, pivot pos_v, a zero angle skipped), then
+ *   (pos - centroid) R^T + tr.  pos_out of graph g is BIT FOR BIT what ddk_rng_initial(seed, stream_id[g], sample0 = sample[g], B = 1, n_rot = R_g,
+ *   tr_sigma_max) followed by ddk_randomize_position gives that ligand alone, whatever else is in the batch and wherever the graph stands in it.
+ *   tor_ptr = NULL: no torsions are drawn (no_torsion; the rotor tables may then be NULL).  status_out [G] and the rule that a graph with a status other
+ *   than 0 is not written are ddk_modify_conformer_batch's; a sample < 0 is status 4.  Limits: those of ddk_modify_conformer_batch; tr_sigma_max finite and
+ *   >= 0.  One launch, one workgroup per graph, no draw array in memory. */
+int ddk_randomize_position_batch(ddk_ctx* ctx, uint64_t seed, int32_t G, int32_t N, const float* pos /* [N, 3] */, const int32_t* node_ptr /* [G + 1] */,
+                                 int32_t T, const int32_t* rot_bonds /* [T, 2] */, const uint8_t* mask_rotate /* [mask_bytes] */,
+                                 const int32_t* mask_ptr /* [G + 1] */, int32_t mask_bytes, const int32_t* tor_ptr /* [G + 1] or NULL */,
+                                 const uint64_t* stream_id /* DEVICE [G] */, const int32_t* sample /* DEVICE [G] */, float tr_sigma_max,
+                                 float* pos_out /* [N, 3] */, int32_t* status_out /* [G] */, void* stream);
 int ddk_score_matching_loss_batch(ddk_ctx* ctx, int32_t G, const int32_t* tor_ptr /* [G + 1] */, int32_t T, const float* tr_pred, const float* rot_pred,
                                   const float* tor_pred, const float* tr_score, const float* rot_score, const float* tor_score,
                                   const float* tr_sigma, const float* so3_score_norm, const float* torus_score_norm2 /* DEVICE [G] each */,
