@@ -54,7 +54,7 @@ _lib = None
 
 # every symbol include/ddk.h declares (tests check that the library exports all of them)
 SYMBOLS = ['ddk_create', 'ddk_destroy', 'ddk_last_error', 'ddk_version', 'ddk_load_weights', 'ddk_finalize_weights',
-           'ddk_set_score_norm_tables', 'ddk_tp_forward', 'ddk_tp_backward', 'ddk_rtp_forward', 'ddk_rtp_backward', 'ddk_rtp_backward_workspace', 'ddk_rconv_forward', 'ddk_rconv_backward', 'ddk_rconv_workspace', 'ddk_rhid_forward', 'ddk_rhid_backward', 'ddk_rhid_workspace', 'ddk_hconv_forward', 'ddk_hconv_backward', 'ddk_hconv_workspace', 'ddk_eemb_forward', 'ddk_eemb_backward', 'ddk_eemb_workspace', 'ddk_eemb_latent_forward', 'ddk_eemb_latent_backward', 'ddk_eemb_latent_workspace', 'ddk_gumbel_softmax_batch', 'ddk_gumbel_softmax_batch_backward', 'ddk_rng_latent_keep', 'ddk_node_cross_entropy_batch', 'ddk_node_cross_entropy_batch_backward', 'ddk_rng_decoding_index', 'ddk_seg_sum', 'ddk_conv_forward', 'ddk_complex_create', 'ddk_complex_destroy',
+           'ddk_set_score_norm_tables', 'ddk_tp_forward', 'ddk_tp_backward', 'ddk_rtp_forward', 'ddk_rtp_backward', 'ddk_rtp_backward_workspace', 'ddk_rconv_forward', 'ddk_rconv_backward', 'ddk_rconv_workspace', 'ddk_rhid_forward', 'ddk_rhid_backward', 'ddk_rhid_workspace', 'ddk_hconv_forward', 'ddk_hconv_backward', 'ddk_hconv_workspace', 'ddk_eemb_forward', 'ddk_eemb_backward', 'ddk_eemb_workspace', 'ddk_eemb_latent_forward', 'ddk_eemb_latent_backward', 'ddk_eemb_latent_workspace', 'ddk_gumbel_softmax_batch', 'ddk_gumbel_softmax_batch_backward', 'ddk_gumbel_pick_samples', 'ddk_rng_latent_keep', 'ddk_node_cross_entropy_batch', 'ddk_node_cross_entropy_batch_backward', 'ddk_rng_decoding_index', 'ddk_seg_sum', 'ddk_conv_forward', 'ddk_complex_create', 'ddk_complex_destroy',
            'ddk_score_forward', 'ddk_se3_update', 'ddk_sample', 'ddk_last_graph_stats', 'ddk_last_node_features',
            'ddk_profile_enable', 'ddk_profile_read', 'ddk_profile_read_forwards', 'ddk_set_latents', 'ddk_set_guidance',
            'ddk_set_keep_receptor_features', 'ddk_randomize_position', 'ddk_complex_set_atoms',
@@ -131,6 +131,8 @@ def lib():
     gumbel = [vp, i32, i32, vp, i64, vp, i64, vp, vp, f32]      # ctx, G, D, a table pair with its node counts, lig_ptr, rec_ptr, T
     L.ddk_gumbel_softmax_batch.argtypes = gumbel + [C.c_uint64, vp, i32, i32, vp, vp, vp, vp, vp]
     L.ddk_gumbel_softmax_batch_backward.argtypes = gumbel + [vp, vp, vp, vp, vp]
+    # ctx, B, D, logit_l, n_lig, logit_r, n_rec, T, seed, stream_id, sample0, draw, lig_latent, rec_latent, choices, stream
+    L.ddk_gumbel_pick_samples.argtypes = [vp, i32, i32, vp, i64, vp, i64, f32, C.c_uint64, C.c_uint64, i32, i32, vp, vp, vp, vp]
     L.ddk_rng_latent_keep.argtypes = [vp, C.c_uint64, i32, vp, i32, i32, f32, vp]
     node_ce = [vp, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, i32]      # ctx, G, D, the logit pair with its node counts, lig_ptr, rec_ptr, the teacher pair, column, soft
     L.ddk_node_cross_entropy_batch.argtypes = node_ce + [vp, vp, vp, vp, vp]

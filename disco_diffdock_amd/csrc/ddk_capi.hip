@@ -159,6 +159,7 @@ void ddk_destroy(ddk_ctx* ctx) {
     if (ctx->ws.xpad) ctx_free(ctx, ctx->ws.xpad);
     if (ctx->ws.sum) ctx_free(ctx, ctx->ws.sum);
     if (ctx->ws.deg) ctx_free(ctx, ctx->ws.deg);
+    if (ctx->ws.gumbel_y) ctx_free(ctx, ctx->ws.gumbel_y);
   }
   delete ctx;
 }
@@ -643,6 +644,30 @@ int ddk_gumbel_softmax_batch(ddk_ctx* ctx, int32_t G, int32_t D, const float* lo
   const GumbelOperands o{lig_ptr, rec_ptr, n_lig, n_rec, G, D, T};
   hipError_t e = launch_gumbel_forward(o, logit_l, logit_r, seed, stream_id, (uint32_t)sample, (uint32_t)draw, y_l, y_r, out_l, out_r, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(ctx, e, "gumbel_softmax_batch launch");
+  return DDK_OK;
+}
+
+int ddk_gumbel_pick_samples(ddk_ctx* ctx, int32_t B, int32_t D, const float* logit_l, int64_t n_lig, const float* logit_r, int64_t n_rec, float T, uint64_t seed,
+                            uint64_t stream_id, int32_t sample0, int32_t draw, float* lig_latent, float* rec_latent, int32_t* choices, void* stream) {
+  const char* who = "ddk_gumbel_pick_samples";
+  int rc = check_launchable(ctx, 0);
+  if (rc) return rc;
+  const std::string w(who);
+  if (B < 1 || B > 65536) return fail(ctx, DDK_ERR_INVALID, w + ": B must be in [1, 65536]");
+  if (D < 1 || D > 4) return fail(ctx, DDK_ERR_INVALID, w + ": D must be in 1..4");
+  if (n_lig < 0 || n_rec < 0 || n_lig >= (int64_t)1 << 31 || n_rec >= (int64_t)1 << 31 || n_lig + n_rec >= (int64_t)1 << 31)
+    return fail(ctx, DDK_ERR_INVALID, w + ": node count out of range (n_lig, n_rec >= 0, n_lig + n_rec < 2^31)");
+  if (!(T > 0.f) || !(T < INFINITY)) return fail(ctx, DDK_ERR_INVALID, w + ": the temperature must be positive and finite");
+  if (sample0 < 0 || (int64_t)sample0 + B - 1 > INT32_MAX) return fail(ctx, DDK_ERR_INVALID, w + ": sample0 must be >= 0 and sample0 + B - 1 < 2^31");
+  if (draw < 0 || draw >= (1 << 20)) return fail(ctx, DDK_ERR_INVALID, w + ": draw must be in [0, 2^20)");
+  if ((n_lig > 0 && (!logit_l || !lig_latent)) || (n_rec > 0 && (!logit_r || !rec_latent)))
+    return fail(ctx, DDK_ERR_INVALID, w + ": null operand (logit, latent of a side that has nodes)");
+  if (n_lig + n_rec == 0) return DDK_OK;
+  Workspace& ws = ctx->ws;
+  if ((rc = ensure(ctx, (void**)&ws.gumbel_y, &ws.gumbel_y_cap, (size_t)B * (size_t)(n_lig + n_rec) * D * sizeof(float)))) return rc;
+  hipError_t e = launch_gumbel_pick(B, D, logit_l, n_lig, logit_r, n_rec, T, seed, stream_id, (uint32_t)sample0, (uint32_t)draw, ws.gumbel_y, lig_latent,
+                                    rec_latent, choices, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "gumbel_pick_samples launch");
   return DDK_OK;
 }
 

@@ -203,6 +203,8 @@ struct Workspace {     // per-launch scratch of the fused conv entry point
   float* sum = nullptr;
   int32_t* deg = nullptr;
   size_t xpad_cap = 0, sum_cap = 0, deg_cap = 0;
+  float* gumbel_y = nullptr;      // ddk_gumbel_pick_samples: the soft y of every sample
+  size_t gumbel_y_cap = 0;
 };
 
 }  // namespace ddk
@@ -452,6 +454,9 @@ int64_t eemb_latent_workspace(int64_t E, int32_t K, int32_t NL);
 struct GumbelOperands { const int64_t* lig_ptr; const int64_t* rec_ptr; int64_t n_lig, n_rec; int G, D; float T; };
 hipError_t launch_gumbel_forward(const GumbelOperands& o, const float* logit_l, const float* logit_r, uint64_t seed, const uint64_t* stream_id, uint32_t sample,
                                  uint32_t draw, float* y_l, float* y_r, float* out_l, float* out_r, hipStream_t s);
+hipError_t launch_gumbel_pick(int B, int D, const float* logit_l, int64_t n_lig, const float* logit_r, int64_t n_rec, float T, uint64_t seed, uint64_t stream_id,
+                              uint32_t sample0, uint32_t draw, float* y /* [B (n_lig + n_rec), D] scratch */, float* out_l, float* out_r, int32_t* choices,
+                              hipStream_t s);      // ddk_gumbel_pick_samples: B samples of one complex from one table of logits
 hipError_t launch_gumbel_backward(const GumbelOperands& o, const float* y_l, const float* y_r, const float* gout_l, const float* gout_r, float* grad_l,
                                   float* grad_r, hipStream_t s);
 // k_node_ce.hip: the AR model's ragged cross-entropy over a graph's ligand and receptor nodes and its gradient (include/ddk.h: ddk_node_cross_entropy_batch /

@@ -1,4 +1,4 @@
-// The ragged straight-through Gumbel softmax in front of the latent-conditioned score model (include/ddk.h: ddk_gumbel_softmax_batch, DDK_GUMBEL_LAYOUT) and
+// The ragged straight-through Gumbel softmax in front of the latent-conditioned score model (include/ddk.h: ddk_gumbel_softmax_batch, ddk_gumbel_pick_samples, DDK_GUMBEL_LAYOUT) and
 // its vector-Jacobian product: the reference's per-graph loop (latent_encoder.py:328-335, pretrained_score_encoder.py:74-81 over models/layers.py:152-181) for a
 // whole collated batch in one launch.  ONE WORKGROUP per (graph g, latent dimension d); the class axis is the graph's ligand nodes, then its receptor nodes,
 // position p = 0 .. n_lig_g + n_rec_g - 1.  A written-out order (compiled with -ffp-contract=off):
@@ -69,15 +69,15 @@ __device__ __forceinline__ float gumbel_tree_sum(float* red, float v) {
   return red[0];
 }
 
-__global__ __launch_bounds__(GUM_T) void gumbel_fwd_kernel(GumbelArgs a) {
+// The forward of one (graph, latent dimension), the whole workgroup: the one body of gumbel_fwd_kernel and gumbel_pick_kernel.  The logits are read at the rows
+// of ``in``, y and out are written at the rows of ``G`` (the same node counts; the ragged op passes one graph twice, the per-sample op the shared table and
+// sample b's block of the outputs).  ``key``: rng_block's four words for (complex, sample, draw, d).  Returns the position of the one (n > 0 is the caller's).
+__device__ __forceinline__ int64_t gumbel_forward_body(const float* logit_l, const float* logit_r, float* y_l, float* y_r, float* out_l, float* out_r,
+                                                       const GumbelGraph& in, const GumbelGraph& G, int D, int d, float T, const uint32_t* key) {
   __shared__ float red[GUM_T];
   __shared__ double redd[GUM_T];
   __shared__ int64_t redi[GUM_T];
-  const int g = blockIdx.x, d = blockIdx.y, t = threadIdx.x;
-  const GumbelGraph G = gumbel_graph(a, g);
-  if (G.n <= 0) return;
-  uint32_t key[4];
-  rng_block(rng_stream(((uint64_t)a.seed_hi << 32) | a.seed_lo, a.stream_id[g]), a.sample, RNG_GUMBEL, a.draw, (uint32_t)d, key);
+  const int t = threadIdx.x;
   const int64_t quads = (G.n + 3) >> 2;
   bool lig;
   // 1. z as (hi, lo) into y's and out's buffers, the thread's maximum of hi + lo
@@ -90,13 +90,13 @@ __global__ __launch_bounds__(GUM_T) void gumbel_fwd_kernel(GumbelArgs a) {
     for (int i = 0; i < 4; ++i) {
       const int64_t p = 4 * q + i;
       if (p < G.n) {
-        const int64_t at = gumbel_at(G, p, a.D, d, lig);
+        const int64_t at = gumbel_at(G, p, D, d, lig);
         const float u = rng_uniform(w[i]);
         const double gum = -log(-log((double)(u + 1e-20f)) + 1e-20);
-        const double z = ((double)(lig ? a.logit_l : a.logit_r)[at] + gum) / (double)a.T;
+        const double z = ((double)(lig ? logit_l : logit_r)[gumbel_at(in, p, D, d, lig)] + gum) / (double)T;
         const float hi = (float)z, lo = isinf(hi) ? 0.f : (float)(z - (double)hi);
-        (lig ? a.y_l : a.y_r)[at] = hi;
-        (lig ? a.out_l : a.out_r)[at] = lo;
+        (lig ? y_l : y_r)[at] = hi;
+        (lig ? out_l : out_r)[at] = lo;
         m = fmax(m, (double)hi + (double)lo);
       }
     }
@@ -116,9 +116,9 @@ __global__ __launch_bounds__(GUM_T) void gumbel_fwd_kernel(GumbelArgs a) {
     for (int i = 0; i < 4; ++i) {
       const int64_t p = 4 * q + i;
       if (p < G.n) {
-        const int64_t at = gumbel_at(G, p, a.D, d, lig);
-        float* y = lig ? a.y_l : a.y_r;
-        const float e = (float)exp(((double)y[at] + (double)(lig ? a.out_l : a.out_r)[at]) - m);
+        const int64_t at = gumbel_at(G, p, D, d, lig);
+        float* y = lig ? y_l : y_r;
+        const float e = (float)exp(((double)y[at] + (double)(lig ? out_l : out_r)[at]) - m);
         y[at] = e;
         part += e;
       }
@@ -133,8 +133,8 @@ __global__ __launch_bounds__(GUM_T) void gumbel_fwd_kernel(GumbelArgs a) {
     for (int i = 0; i < 4; ++i) {
       const int64_t p = 4 * q + i;
       if (p < G.n) {
-        const int64_t at = gumbel_at(G, p, a.D, d, lig);
-        float* y = lig ? a.y_l : a.y_r;
+        const int64_t at = gumbel_at(G, p, D, d, lig);
+        float* y = lig ? y_l : y_r;
         const float v = y[at] / sum;
         y[at] = v;
         if (v > best) { best = v; where = p; }      // (ascending p: the first of equals stays)
@@ -159,13 +159,46 @@ __global__ __launch_bounds__(GUM_T) void gumbel_fwd_kernel(GumbelArgs a) {
     for (int i = 0; i < 4; ++i) {
       const int64_t p = 4 * q + i;
       if (p < G.n) {
-        const int64_t at = gumbel_at(G, p, a.D, d, lig);
-        const float y = (lig ? a.y_l : a.y_r)[at];
+        const int64_t at = gumbel_at(G, p, D, d, lig);
+        const float y = (lig ? y_l : y_r)[at];
         const float hard = p == where ? 1.f : 0.f;
-        (lig ? a.out_l : a.out_r)[at] = (hard - y) + y;
+        (lig ? out_l : out_r)[at] = (hard - y) + y;
       }
     }
   }
+  return where;
+}
+
+__global__ __launch_bounds__(GUM_T) void gumbel_fwd_kernel(GumbelArgs a) {
+  const int g = blockIdx.x, d = blockIdx.y;
+  const GumbelGraph G = gumbel_graph(a, g);
+  if (G.n <= 0) return;
+  uint32_t key[4];
+  rng_block(rng_stream(((uint64_t)a.seed_hi << 32) | a.seed_lo, a.stream_id[g]), a.sample, RNG_GUMBEL, a.draw, (uint32_t)d, key);
+  gumbel_forward_body(a.logit_l, a.logit_r, a.y_l, a.y_r, a.out_l, a.out_r, G, G, a.D, d, a.T, key);
+}
+
+// ddk_gumbel_pick_samples: workgroup (b, d) is sample ``sample + b`` of ONE complex; every sample reads the one table of logits (rows 0 .. n - 1) and writes
+// rows b n .. (b + 1) n - 1 of y (the context's scratch) and out.  stream_id is the complex id itself, by value; choices (or null) [B, D] takes the position of the
+// one, ligand nodes first (-1 where no y compares: NaN logits).
+struct GumbelPickArgs {
+  const float* logit_l; const float* logit_r;
+  float* y_l; float* y_r; float* out_l; float* out_r;
+  int32_t* choices;
+  int64_t n_lig, n_rec;
+  uint64_t stream_id;
+  int D;
+  float T;
+  uint32_t seed_lo, seed_hi, sample, draw;
+};
+
+__global__ __launch_bounds__(GUM_T) void gumbel_pick_kernel(GumbelPickArgs a) {
+  const int b = blockIdx.x, d = blockIdx.y;
+  const GumbelGraph in{0, 0, a.n_lig, a.n_lig + a.n_rec}, to{(int64_t)b * a.n_lig, (int64_t)b * a.n_rec, a.n_lig, a.n_lig + a.n_rec};
+  uint32_t key[4];
+  rng_block(rng_stream(((uint64_t)a.seed_hi << 32) | a.seed_lo, a.stream_id), a.sample + (uint32_t)b, RNG_GUMBEL, a.draw, (uint32_t)d, key);
+  const int64_t where = gumbel_forward_body(a.logit_l, a.logit_r, a.y_l, a.y_r, a.out_l, a.out_r, in, to, a.D, d, a.T, key);
+  if (a.choices && threadIdx.x == 0) a.choices[(int64_t)b * a.D + d] = (int32_t)where;
 }
 
 __global__ __launch_bounds__(GUM_T) void gumbel_bwd_kernel(GumbelBwdArgs a) {
@@ -208,6 +241,16 @@ hipError_t launch_gumbel_forward(const GumbelOperands& o, const float* logit_l, 
   a.n_lig = o.n_lig; a.n_rec = o.n_rec; a.D = o.D; a.T = o.T;
   a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.sample = sample; a.draw = draw;
   hipLaunchKernelGGL(gumbel_fwd_kernel, dim3((unsigned)o.G, (unsigned)o.D), dim3(GUM_T), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_gumbel_pick(int B, int D, const float* logit_l, int64_t n_lig, const float* logit_r, int64_t n_rec, float T, uint64_t seed, uint64_t stream_id,
+                              uint32_t sample0, uint32_t draw, float* y, float* out_l, float* out_r, int32_t* choices, hipStream_t s) {
+  GumbelPickArgs a{};
+  a.logit_l = logit_l; a.logit_r = logit_r; a.y_l = y; a.y_r = y + (int64_t)B * n_lig * D; a.out_l = out_l; a.out_r = out_r; a.choices = choices;
+  a.n_lig = n_lig; a.n_rec = n_rec; a.stream_id = stream_id; a.D = D; a.T = T;
+  a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.sample = sample0; a.draw = draw;
+  hipLaunchKernelGGL(gumbel_pick_kernel, dim3((unsigned)B, (unsigned)D), dim3(GUM_T), 0, s, a);
   return hipGetLastError();
 }
 

@@ -6,7 +6,8 @@
           -> ``latent_s_predictor`` / ``latent_r_predictor`` (plain torch) -> per-node logits [N_lig, D], [N_rec, D]
           -> ``ragged_gumbel_softmax`` (``apply_gumbel_softmax=True``) or the per-graph logit list (False: the AR model's targets)
 
-The oracle encoder reads the ground-truth pose, so it runs in training (and to make AR targets) only: it has no inference engine behind the C ABI.  Its conv
+The oracle encoder reads the ground-truth pose: it runs in training, to make AR targets, and in front of the sampler (``sampling.oracle_latents``: once per
+batch of copies of a complex, through ``logits`` in ``.eval()``).  It has no inference engine of its own behind the C ABI.  Its conv
 layers are the ns = 24 / nv = 4 (or nv = 6) family of the tensor-product ops; an nv = 4 layer has no fused inference kernel and evaluates with the
 training ops (``tensor_layers.TensorProductConvLayer``).
 

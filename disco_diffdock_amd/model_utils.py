@@ -33,8 +33,30 @@ def get_model(args, device, t_to_sigma, no_parallel=False, confidence_mode=False
         sigma_limits=dict(tr_sigma_min=args.tr_sigma_min, tr_sigma_max=args.tr_sigma_max, rot_sigma_min=args.rot_sigma_min,
                           rot_sigma_max=args.rot_sigma_max, tor_sigma_min=args.tor_sigma_min, tor_sigma_max=args.tor_sigma_max))
     if hasattr(args, 'latent_vocab'):
-        return ModelWrapper(encoder=None, score_model=score_model)   # model_utils.py:93-94
+        # model_utils.py:93-94; the oracle encoder is built when a checkpoint brings its keys (ModelWrapper.load_state_dict), from these args
+        factory = partial(_oracle_encoder_on, args, device) if g('latent_dim', 0) > 0 else None      # (a partial of a module function: the model stays picklable)
+        return ModelWrapper(encoder=None, score_model=score_model, encoder_factory=factory)
     return score_model
+
+
+def _oracle_encoder_on(args, device):
+    return _oracle_encoder(args, device).to(device)
+
+
+def _oracle_encoder(args, device):
+    """utils/model_utils.py:70-94: the ``latent_encoder.TPEncoder`` of a model_parameters.yml Namespace (``encoder_ns``, ``encoder_nv``,
+    ``encoder_num_conv_layers``, ``encoder_cross_max_distance``, ``encoder_no_esm``, ``latent_*``); what it does not implement raises by name"""
+    from .latent_encoder import TPEncoder
+    g = lambda k, d: getattr(args, k, d)
+    lm = 'esm' if g('esm_embeddings_path', None) is not None else None
+    return TPEncoder(device=device, no_torsion=args.no_torsion, num_conv_layers=args.encoder_num_conv_layers, lig_max_radius=args.max_radius,
+                     ns=args.encoder_ns, nv=args.encoder_nv, distance_embed_dim=args.distance_embed_dim,
+                     cross_distance_embed_dim=args.cross_distance_embed_dim, batch_norm=not args.no_batch_norm, dropout=args.dropout, sh_lmax=g('sh_lmax', 2),
+                     use_second_order_repr=args.use_second_order_repr, cross_max_distance=args.encoder_cross_max_distance,
+                     lm_embedding_type=None if g('encoder_no_esm', False) else lm, latent_dim=int(g('latent_dim', 0)), latent_vocab=args.latent_vocab,
+                     latent_no_batchnorm=g('latent_no_batchnorm', False), latent_dropout=g('latent_dropout', 0.0),
+                     latent_hidden_dim=g('latent_hidden_dim', 128), latent_virtual_nodes=g('latent_virtual_nodes', False),
+                     latent_nodes_residual=g('latent_nodes_residual', False))
 
 
 def get_ar_model(args, score_model_args, device, training=True):
@@ -94,22 +116,12 @@ def get_trainable_model(args, device, t_to_sigma=None):
     ``latent_encoder.TPEncoder`` in front of it in a ``train_model.LatentModelWrapper``, whose state_dict has the ``encoder.`` / ``score_model.`` keys of
     the reference's ``ModelWrapper`` checkpoints.  The encoder reads ``encoder_ns``, ``encoder_nv``, ``encoder_num_conv_layers``,
     ``encoder_cross_max_distance``, ``encoder_no_esm``, ``latent_*`` and ``training_latent_temperature`` as lines 70-94 there do."""
-    from .latent_encoder import TPEncoder
     from .train_model import LatentModelWrapper
     g = lambda k, d: getattr(args, k, d)
     score_model = _trainable_score_model(args, device, t_to_sigma)
     latent_dim = int(g('latent_dim', 0))
-    lm = 'esm' if g('esm_embeddings_path', None) is not None else None
-    sh_lmax = g('sh_lmax', 2)
     if latent_dim == 0:
         return score_model.to(device)
-    encoder = TPEncoder(device=device, no_torsion=args.no_torsion, num_conv_layers=args.encoder_num_conv_layers, lig_max_radius=args.max_radius,
-                        ns=args.encoder_ns, nv=args.encoder_nv, distance_embed_dim=args.distance_embed_dim,
-                        cross_distance_embed_dim=args.cross_distance_embed_dim, batch_norm=not args.no_batch_norm, dropout=args.dropout, sh_lmax=sh_lmax,
-                        use_second_order_repr=args.use_second_order_repr, cross_max_distance=args.encoder_cross_max_distance,
-                        lm_embedding_type=None if g('encoder_no_esm', False) else lm, latent_dim=latent_dim, latent_vocab=args.latent_vocab,
-                        latent_no_batchnorm=g('latent_no_batchnorm', False), latent_dropout=g('latent_dropout', 0.0),
-                        latent_hidden_dim=g('latent_hidden_dim', 128), latent_virtual_nodes=g('latent_virtual_nodes', False),
-                        latent_nodes_residual=g('latent_nodes_residual', False))
+    encoder = _oracle_encoder(args, device)
     return LatentModelWrapper(encoder, score_model, training_latent_temperature=g('training_latent_temperature', 1.0),
                               latent_droprate=g('latent_droprate', 0)).to(device)

@@ -888,6 +888,32 @@ class Context:
                                                     _ptr(out_r), _stream()), 'ddk_gumbel_softmax_batch')
         return out_l, out_r, y_l, y_r
 
+    def gumbel_pick_samples(self, logit_l, logit_r, B, temperature, seed, stream, sample0=0, draw=0):
+        """The one-hot latents of ``B`` samples of ONE complex from its one pair of logit tables [n_lig, D], [n_rec, D] (ddk_gumbel_pick_samples, one launch):
+        (lig_latent [B n_lig, D], rec_latent [B n_rec, D], choices int32 [B, D]).  Sample b's rows are, bit for bit, ``gumbel_softmax``'s ``out`` for the one
+        graph with ``sample = sample0 + b`` and the same seed, ``stream`` (the complex's 64-bit id), draw and temperature; ``choices`` holds the position of
+        the one, ligand nodes first, then n_lig + the receptor index."""
+        logit_l, logit_r = (_need_cuda(x).contiguous().float() for x in (logit_l, logit_r))
+        dev = logit_l.device
+        if logit_l.dim() != 2 or logit_r.dim() != 2 or logit_l.shape[1] != logit_r.shape[1] or not 1 <= logit_l.shape[1] <= 4 or logit_r.device != dev:
+            raise RuntimeError('ddk: gumbel_pick_samples takes two tables [n_lig, D] and [n_rec, D] with D in 1..4 on one device; got '
+                               f'{tuple(logit_l.shape)} and {tuple(logit_r.shape)}')
+        B, D, T = int(B), logit_l.shape[1], float(temperature)
+        if not 1 <= B <= 65536:
+            raise RuntimeError(f'ddk: gumbel_pick_samples takes 1..65536 samples; got {B}')
+        if not (T > 0 and T < float('inf')):
+            raise RuntimeError(f'ddk: gumbel_pick_samples takes a positive finite temperature; got {temperature}')
+        for k, v in dict(draw=draw, sample0=sample0).items():
+            if not 0 <= int(v) < 1 << 31:
+                raise RuntimeError(f'ddk: gumbel_pick_samples: {k} = {v} must be a non-negative int32')
+        n_l, n_r = logit_l.shape[0], logit_r.shape[0]
+        lat_l, lat_r = torch.empty((B * n_l, D), device=dev), torch.empty((B * n_r, D), device=dev)
+        choices = torch.empty((B, D), dtype=torch.int32, device=dev)
+        self._check(self.L.ddk_gumbel_pick_samples(self.h, B, D, _ptr(logit_l), n_l, _ptr(logit_r), n_r, T, C.c_uint64(_u64(seed, 'seed')),
+                                                   C.c_uint64(_u64(stream, 'rng_stream')), int(sample0), int(draw), _ptr(lat_l), _ptr(lat_r), _ptr(choices),
+                                                   _stream()), 'ddk_gumbel_pick_samples')
+        return lat_l, lat_r, choices
+
     def gumbel_softmax_backward(self, y_l, y_r, lig_ptr, rec_ptr, temperature, grad_out_l, grad_out_r):
         """(grad_logit_l, grad_logit_r) = y (g - sum g y) / T per graph and latent dimension from the saved ``y`` (ddk_gumbel_softmax_batch_backward)"""
         y_l, y_r, G, D, T = self._gumbel_operands(y_l, y_r, lig_ptr, rec_ptr, temperature, 'gumbel_softmax_backward')

@@ -4,8 +4,9 @@ SDE perturbation, SE(3)/torsion update, Kabsch re-alignment - runs inside libddk
 host synchronisation; this file only prepares the per-step host scalars exactly as the reference computes them.
 ``visualization_list`` works as in the reference (:224-228: the poses after every batch), and the extra keyword ``trajectory=[]``
 collects what the loop did step by step - poses, scores, perturbations, edge counts - recorded on the device by the launches the
-sampler makes anyway (``ddk_sample_trajectory``).  The one option outside the accelerated path (the oracle latent encoder) raises
-instead of silently doing something else."""
+sampler makes anyway (``ddk_sample_trajectory``).  With ``ar_model=None`` a latent-conditioned model samples with ORACLE latents
+(``oracle_latents``: the encoder of ``model.encoder`` on the true pose, once per batch, then one ``ddk_gumbel_pick_samples`` launch for the batch's
+samples); ``compute_ar_accuracy`` compares them with the AR model's picks."""
 import collections
 
 import numpy as np
@@ -133,7 +134,7 @@ class _Bookkeeping:
     can exceed); it stays as a guard of the other edge groups' worst-case capacities: a batch that raised it would carry NaN confidences (conf_head_kernel),
     returned as -1000 like the reference's nan_to_num, and the warning below."""
 
-    def __init__(self, graphs, choices, flat, len_lig, latent_dim, conf_cx):
+    def __init__(self, graphs, choices, flat, len_lig, latent_dim, conf_cx, ar_accuracy=None):
         import weakref
         self.graphs = [weakref.ref(g) for g in graphs]
         self.name = getattr(graphs[0], 'name', None) if graphs else None
@@ -141,13 +142,16 @@ class _Bookkeeping:
         self.done = False
         self._resolving = False
         self.bound = False       # the graphs carry this object as ``_lazy`` (our HeteroData): a graph a later call re-used is skipped
-        self.choices = self.flat = None
+        self.choices = self.flat = self.ar_accuracy = None
         self.conf_status = conf_cx.confidence_status_async() if conf_cx is not None else None
         if choices is not None:
             self.choices = torch.empty(choices.shape, dtype=choices.dtype, pin_memory=True)
             self.choices.copy_(choices, non_blocking=True)
             self.flat = torch.empty(flat.shape, dtype=flat.dtype, pin_memory=True)
             self.flat.copy_(flat.detach(), non_blocking=True)
+        if ar_accuracy is not None:      # [1] on the device (utils/sampling.py:90-101): it comes back with the picks
+            self.ar_accuracy = torch.empty(ar_accuracy.shape, dtype=ar_accuracy.dtype, pin_memory=True)
+            self.ar_accuracy.copy_(ar_accuracy, non_blocking=True)
         self.event = torch.cuda.Event()
         self.event.record()
 
@@ -176,6 +180,7 @@ class _Bookkeeping:
         if self.choices is None:
             return
         ch, n = self.choices.tolist(), self.len_lig
+        accuracy = None if self.ar_accuracy is None else float(self.ar_accuracy.reshape(-1)[0])
         for i, ref in enumerate(self.graphs):
             d_i = ref()
             if d_i is None or (self.bound and d_i.__dict__.get('_lazy') is not self):      # collected, or re-used by a later sampling() call
@@ -196,7 +201,9 @@ class _Bookkeeping:
             d_i.__dict__.pop('_lazy', None)
             d_i.latent_str = lat_str
             d_i.latent_pos = torch.cat(lat_pos, dim=0)
-        self.choices = self.flat = None      # the pinned buffers go back to the allocator
+            if accuracy is not None:
+                d_i.ar_accuracy = accuracy
+        self.choices = self.flat = self.ar_accuracy = None      # the pinned buffers go back to the allocator
 
 
 def _poll_pending():
@@ -205,6 +212,68 @@ def _poll_pending():
     for bk in list(_pending):
         if bk.event.query():
             bk.resolve()
+
+
+_NO_ENCODER = ('ddk: sampling with oracle latents (ar_model=None, or compute_ar_accuracy) needs model.encoder, and the checkpoint loaded into this model '
+               'had no encoder.* keys (ModelWrapper.load_state_dict builds the encoder from them; ModelWrapper.attach_encoder takes a live TPEncoder); '
+               'pass ar_model= to sample with the AR model\'s latents instead')
+
+
+def oracle_latents(model, batch, temperature=0.01, seed=None, rng_stream=None, sample0=0):
+    """The oracle latents of a sampling() batch, utils/sampling.py:69-76: ``batch`` is a ``data.collate`` batch of b copies of ONE complex, whose true
+    pose the encoder reads and nothing else, so ``model.encoder.logits`` runs ONCE, on the batch's first graph (the reference runs it on all b copies),
+    and ONE ``ddk_gumbel_pick_samples`` launch draws the b samples' one-hot latents from that table: (latent_l [b n_lig, D], latent_r [b n_rec, D],
+    choices int32 [b, D]) on the device, ``choices`` the picked position, ligand nodes first, then n_lig + the receptor index.  Graph i is global sample
+    ``sample0 + i`` of the complex ``rng_stream`` (default: runtime.stream_id of the first graph's name) under ``seed`` (None: one draw from torch's
+    default CPU generator, as the encoder makes itself), draw 0, DDK_GUMBEL_LAYOUT: a sample's latents do not depend on the batch it is in.  The first
+    graph needs the true centred pose in ``['ligand'].orig_pos_torch`` and a name.  The encoder takes that graph from the host, not from the sampler's
+    cached complex: its receptor features go up once per batch ([n_rec, 1281] floats with ESM columns, 1.5 MB at 300 residues), inside the 5 ms the
+    encoder's forward takes (profiles/oracle_latents_kernel_stats.md).  ``encoder.latent_temperature`` is set to ``temperature``, as the
+    reference does; the encoder runs in ``.eval()`` and is left in the mode it was in."""
+    from .data import collate
+    from .tensor_layers import _draw_seed
+    wrapper = model.module if hasattr(model, 'module') else model
+    encoder = getattr(wrapper, 'encoder', None)
+    if encoder is None:
+        raise RuntimeError(_NO_ENCODER)
+    ctx = getattr(wrapper, 'score_model', wrapper).ctx
+    dev = torch.device('cuda', ctx.device)
+    b = int(batch.num_graphs)
+    first = getattr(batch, 'first', None)
+    if first is None:
+        if b != 1:
+            raise RuntimeError('ddk: oracle_latents takes a data.collate batch (it reads the first graph through batch.first)')
+        first = batch
+    lig = first['ligand']
+    name = getattr(first, 'name', None)
+    while isinstance(name, (list, tuple)) and len(name):
+        name = name[0]
+    pose = getattr(lig, 'orig_pos_torch', None) if 'orig_pos_torch' in lig else None
+    if pose is None or not isinstance(name, str):
+        raise RuntimeError("ddk: oracle latents need the complex's true centred pose in data['ligand'].orig_pos_torch ([n_lig, 3], the frame of "
+                           "data['receptor'].pos) and its name in data.name (the stream of its Gumbel noise); the first graph of the batch has "
+                           + ('neither' if pose is None and not isinstance(name, str) else 'no orig_pos_torch' if pose is None else 'no name'))
+    pose = torch.as_tensor(np.asarray(pose, np.float32) if not torch.is_tensor(pose) else pose).float().reshape(-1, 3)
+    if pose.shape[0] != lig.pos.shape[0]:
+        raise RuntimeError(f"ddk: data['ligand'].orig_pos_torch must hold one row per ligand atom ({lig.pos.shape[0]}); got {pose.shape[0]}")
+    one = first if first is batch else collate([first])
+    kept = lig.orig_pos_torch
+    one['ligand'].orig_pos_torch = h2d_async(pose, dev)
+    encoder.latent_temperature = temperature
+    was = encoder.training
+    encoder.eval()
+    try:
+        with torch.no_grad():
+            logit_l, logit_r, _, _ = encoder.logits(one)
+    finally:
+        encoder.train(was)
+        if one is first:      # (a lone graph handed in as it is: the caller's pose stays the caller's tensor)
+            lig.orig_pos_torch = kept
+    if seed is None:
+        seed = _draw_seed()
+    if rng_stream is None:
+        rng_stream = stream_id(name)
+    return ctx.gumbel_pick_samples(logit_l, logit_r, b, temperature, seed, rng_stream, sample0=sample0, draw=0)
 
 
 def draw_noise(inference_steps, b, R_total, R, nc, device):
@@ -298,7 +367,13 @@ def sampling(data_list, model, inference_steps, tr_schedule, rot_schedule, tor_s
              gumbel_latent_temperature=0.01, ar_model=None, ar_args=None, temp_sampling=1.0, temp_psi=0.0, temp_sigma_data=0.5,
              classifier_free_guidance_weight=0.0, softmax_latent_temperature=1.0, cfg_start=1.0, cfg_end=0.0,
              compute_ar_accuracy=False, noise=None, trajectory=None, seed=None, rng_stream=None, sample_offset=0):
-    """``noise`` (extra, optional): list with one tensor [steps, b, 6+R] per batch of N(0,1) draws (tr xyz, rot xyz,
+    """``ar_model=None`` on a latent-conditioned model (utils/sampling.py:69-78, ``evaluate.py --oracle``): the latents are ORACLE latents, ``model.encoder``
+    on the true pose (every graph's ``['ligand'].orig_pos_torch``) once per batch and one draw per sample at ``gumbel_latent_temperature``
+    (:func:`oracle_latents`); with ``seed`` graph i draws as global sample ``sample_offset + i``, whatever the batch.  ``compute_ar_accuracy=True`` with an
+    ``ar_model`` runs both, samples with the AR latents and stores ``ar_accuracy`` on every graph of a batch: the share of its samples whose AR pick for
+    latent dimension 0 is the oracle's (filled with ``latent_str`` / ``latent_pos`` from the one read-back).
+
+    ``noise`` (extra, optional): list with one tensor [steps, b, 6+R] per batch of N(0,1) draws (tr xyz, rot xyz,
     torsions) to replace the device generator - used by the parity tests (the reference never seeds its RNGs).
 
     ``seed`` (extra, optional): None draws as above, from torch's device generator.  With a seed every draw of the call - the step noise and the AR picks -
@@ -338,9 +413,9 @@ def sampling(data_list, model, inference_steps, tr_schedule, rot_schedule, tor_s
     latent_model = use_latent and getattr(model_args, 'latent_dim', 0) > 0
     if classifier_free_guidance_weight != 0.0 and not latent_model:
         raise RuntimeError('ddk: classifier-free guidance needs the latent-conditioned model (sampling.py:119-135)')
-    if latent_model and (ar_model is None or compute_ar_accuracy):
-        raise RuntimeError('ddk: latent-conditioned sampling needs ar_model (the oracle encoder needs the ground-truth pose and is '
-                           'outside the hot path)')
+    oracle = latent_model and (ar_model is None or compute_ar_accuracy)      # utils/sampling.py:70
+    if oracle and getattr(model.module if hasattr(model, 'module') else model, 'encoder', None) is None:
+        raise RuntimeError(_NO_ENCODER)
     device = torch.device(device)
     if device.type != 'cuda':
         raise RuntimeError('ddk sampling runs on the GPU only (no CPU fallback)')
@@ -356,8 +431,12 @@ def sampling(data_list, model, inference_steps, tr_schedule, rot_schedule, tor_s
             if b != min(batch_size, N):
                 raise RuntimeError('ragged last batch: the reference draws noise of size min(batch_size, N) (sampling.py:146-153)')
             cx, _ = complex_for_batch(batch, device, ctx=score_model.ctx)
-            latent_h = None
-            if latent_model:   # utils/sampling.py:69-103: AR decoding on the ar_pos pose, then the latents condition every step
+            latent_h = ar_accuracy = None
+            if oracle:         # utils/sampling.py:70-78: the encoder on the true pose, once for the batch, then the b samples' draws in one launch
+                true_l, true_r, choices = oracle_latents(model, batch, gumbel_latent_temperature, seed, rng_stream, sample_offset + batch_id * batch_size)
+                latent_h = (true_l, true_r)
+            if latent_model and ar_model is not None:   # utils/sampling.py:80-85: AR decoding on the ar_pos pose
+                true_choices = choices if oracle else None
                 lig_st = batch['ligand']      # only the poses go to the device: the encoder's score-model copy takes everything else
                 lig_st.pos = h2d_async(lig_st.pos, device)      # from the cached ddk_complex (a batch.to(device) moved 61 MB of ESM features)
                 if 'ar_pos' in lig_st:
@@ -370,9 +449,12 @@ def sampling(data_list, model, inference_steps, tr_schedule, rot_schedule, tor_s
                 else:
                     latent_h = ar_model.encode_ar(batch, softmax_latent_temperature, rng=(seed, rng_stream, sample_offset + batch_id * batch_size))
                 batch['ligand'].pos = temp_lig_pos
+                choices = ar_model.last_choices          # [b, latent_dim] picked nodes (device): read back ONCE, after the sampler is enqueued
+                if true_choices is not None:             # utils/sampling.py:90-101: the share of the samples whose FIRST latent is the oracle's
+                    ar_accuracy = (choices[:, 0].long() == true_choices[:, 0].long()).double().mean().reshape(1)
+            if latent_model:   # utils/sampling.py:87-88: the latents condition every step
                 batch['ligand'].latent_h, batch['receptor'].latent_h = latent_h
                 cx.set_latents(latent_h[0], latent_h[1], 0.0)
-                choices = ar_model.last_choices          # [b, latent_dim] picked nodes (device): read back ONCE, after the sampler is enqueued
                 cx.set_guidance(classifier_free_guidance_weight, cfg_start, cfg_end)
             elif score_model.cfg['latent_dim'] > 0:
                 raise RuntimeError('ddk: a latent-conditioned score model was given but use_latent / model_args.latent_dim disable the latents')
@@ -425,11 +507,13 @@ def sampling(data_list, model, inference_steps, tr_schedule, rot_schedule, tor_s
                 # sampler and not awaited here (the reference synchronises 6x per pose)
                 from .data import HeteroData
                 bk = _Bookkeeping(graphs, choices if latent_model else None, flat, len_lig, getattr(model_args, 'latent_dim', 0),
-                                  conf_checks.pop() if conf_checks else None)
+                                  conf_checks.pop() if conf_checks else None, ar_accuracy=ar_accuracy)
                 if latent_model and all(isinstance(d_i, HeteroData) for d_i in graphs):
                     for d_i in graphs:
                         d_i.__dict__.pop('latent_str', None)
                         d_i.__dict__.pop('latent_pos', None)
+                        if ar_accuracy is not None:
+                            d_i.__dict__.pop('ar_accuracy', None)
                         d_i.__dict__['_lazy'] = bk
                     bk.bound = True
                     _pending.append(bk)

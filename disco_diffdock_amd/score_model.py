@@ -196,6 +196,10 @@ class TensorProductScoreModel(nn.Module):
         if extra:
             self.ctx.load_state_dict(extra, finalize=False)
         self.ctx.load_state_dict({k: have[k] for k in spec})
+        # a cached Complex of this context holds node embeddings made with the weights of its day: after a (re)load every complex is set up anew
+        if self._loaded:      # (a first load finds none: a complex needs finalised weights)
+            for k in [k for k in _complex_cache if k[0] == id(self.ctx)]:
+                del _complex_cache[k]
         self._loaded = True
         return torch.nn.modules.module._IncompatibleKeys(missing, unexpected)
 
@@ -256,25 +260,50 @@ class TensorProductScoreModel(nn.Module):
 
 
 class ModelWrapper(nn.Module):
-    """models/model_classes.py:53-85 as far as inference needs it: ``model.score_model`` and ``model.encoder``."""
+    """models/model_classes.py:53-85 as far as inference needs it: ``model.score_model`` and ``model.encoder``.  ``encoder`` is the oracle latent
+    encoder (``latent_encoder.TPEncoder`` in ``.eval()``) that ``sampling(ar_model=None)`` runs in front of the sampler, or None: a checkpoint with
+    ``encoder.*`` keys builds one (``encoder_factory``, which ``model_utils.get_model`` sets from its ``args``), ``attach_encoder`` takes a live one."""
 
-    def __init__(self, encoder, score_model):
+    def __init__(self, encoder, score_model, encoder_factory=None):
         super().__init__()
         self.encoder = encoder
         self.score_model = score_model
+        self.encoder_factory = encoder_factory
 
     def forward(self, data):
         return self.score_model(data)
 
+    def attach_encoder(self, encoder):
+        """use ``encoder`` (a live ``latent_encoder.TPEncoder``, shared with its owner, not copied) as the oracle encoder; it is put in ``.eval()``"""
+        from .latent_encoder import TPEncoder
+        if not isinstance(encoder, TPEncoder):
+            raise RuntimeError(f'ddk: ModelWrapper.attach_encoder takes a latent_encoder.TPEncoder; got {type(encoder).__name__}')
+        if encoder.latent_dim != self.score_model.cfg['latent_dim']:
+            raise RuntimeError(f'ddk: ModelWrapper.attach_encoder: the encoder has latent_dim = {encoder.latent_dim}, the score model '
+                               f"{self.score_model.cfg['latent_dim']}")
+        self.encoder = encoder.eval()
+        return self
+
     def load_state_dict(self, state_dict, strict=True):
-        """evaluate.py:164-171 loads either the wrapper's state_dict (keys ``score_model.*`` / ``encoder.*``) or the bare
-        score model's; the (oracle) latent encoder is outside the hot path, so its keys are reported as unexpected."""
+        """evaluate.py:164-171 loads either the wrapper's state_dict (keys ``score_model.*`` / ``encoder.*``) or the bare score model's.  ``encoder.*``
+        keys go to the oracle encoder with the caller's ``strict``; where the wrapper has none yet it is built first, in ``.eval()``, from the ``args``
+        ``get_model`` was called with (a configuration ``TPEncoder`` refuses raises and names the argument).  A state dict without them loads as the
+        bare score model does and leaves ``self.encoder`` as it is (None after ``get_model``)."""
         wrapped = any(k.startswith('score_model.') for k in state_dict)
         inner = {k[len('score_model.'):]: v for k, v in state_dict.items() if k.startswith('score_model.')} if wrapped else dict(state_dict)
-        extra = [k for k in state_dict if wrapped and not k.startswith('score_model.')]
-        if strict and extra and self.encoder is None:
-            enc = [k for k in extra if not k.startswith('encoder.')]
-            if enc:
-                raise RuntimeError(f'ddk: unexpected keys {enc}')
+        enc = {k[len('encoder.'):]: v for k, v in state_dict.items() if wrapped and k.startswith('encoder.')}
+        extra = [k for k in state_dict if wrapped and not k.startswith('score_model.') and not k.startswith('encoder.')]
+        if strict and extra:
+            raise RuntimeError(f'ddk: unexpected keys {extra}')
+        missing, unexpected = [], list(extra)
+        if enc:
+            if self.encoder is None:
+                if self.encoder_factory is None:
+                    raise RuntimeError('ddk: the state dict holds encoder.* keys and this ModelWrapper cannot build the encoder (model_utils.get_model '
+                                       'keeps what it needs; or attach_encoder a live one)')
+                self.encoder = self.encoder_factory().eval()
+            res_e = self.encoder.load_state_dict(enc, strict=strict)
+            missing += ['encoder.' + k for k in res_e.missing_keys]
+            unexpected += ['encoder.' + k for k in res_e.unexpected_keys]
         res = self.score_model.load_state_dict(inner, strict=strict)
-        return torch.nn.modules.module._IncompatibleKeys(list(res.missing_keys), list(res.unexpected_keys) + extra)
+        return torch.nn.modules.module._IncompatibleKeys(list(res.missing_keys) + missing, list(res.unexpected_keys) + unexpected)

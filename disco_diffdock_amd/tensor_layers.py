@@ -392,7 +392,7 @@ def conv_stack(conv_layers, node_attr, edge_index, edge_emb, group_sizes, edge_s
     In training the whole stack runs without atomics: two passes from one state and one seed give the same bits.  Returns ``node_attr``."""
     layers = list(conv_layers)
     graph = None
-    if any(layer.training or getattr(layer, 'layer', 0) >= TP_NV4 for layer in layers) and edge_index.shape[1] > 0:      # (an nv = 4 layer evaluates with the training ops)
+    if any(layer.training or getattr(layer, 'layer', 0) >= TP_NV4 or getattr(layer, 'eval_with_training_ops', False) for layer in layers) and edge_index.shape[1] > 0:      # (an nv = 4 layer evaluates with the training ops)
         graph = Context.conv_graph(edge_index[0], edge_index[1], node_attr.shape[0], node_attr.shape[0])
         if seed is None and any(layer.training for layer in layers):
             seed = _draw_seed()
@@ -857,6 +857,9 @@ class TensorProductConvLayer(nn.Module):
                                          activation) for _ in range(edge_groups)])
         self.batch_norm = _BatchNormParams(out_irreps) if batch_norm else None
         self._ctx, self._ctx_key = None, None
+        # evaluation runs the fused inference kernel, whose scatter is an fp32 atomic add: the last bits of an evaluation forward then differ from run to
+        # run.  True: evaluate with the training ops instead (no atomics; dropout rate 0 and BatchNorm on its running buffers, as an nv = 4 layer does)
+        self.eval_with_training_ops = False
 
     @staticmethod
     def _head_configuration(in_irreps, sh_irreps, out_irreps, n_edge_features, residual, hidden_features, faster, edge_groups, tp_weights_layers,
@@ -905,7 +908,7 @@ class TensorProductConvLayer(nn.Module):
     def forward(self, node_attr, edge_index, edge_attr, edge_sh, out_nodes=None, reduce='mean'):
         if self.head is not None:
             return self._forward_head(node_attr, edge_index, edge_attr, edge_sh, out_nodes, reduce)
-        if self.training or self.layer >= TP_NV4:      # the fused inference kernel is nv = 6 only: an nv = 4 layer evaluates with the training ops
+        if self.training or self.layer >= TP_NV4 or self.eval_with_training_ops:      # the fused inference kernel is nv = 6 only: an nv = 4 layer evaluates with the training ops
             return self._forward_training(node_attr, edge_index, edge_attr, edge_sh, out_nodes, reduce)
         if reduce != 'mean' or (out_nodes is not None and out_nodes != node_attr.shape[0]):
             raise RuntimeError("ddk: conv layers aggregate with reduce='mean' onto all nodes")
@@ -948,7 +951,7 @@ class TensorProductConvLayer(nn.Module):
         E = edge_index.shape[1]
         if len(sizes) != self.edge_groups or any(n < 0 for n in sizes) or sum(sizes) != E or edge_emb.shape[0] != E:
             raise RuntimeError(f'ddk: forward_embedded takes {self.edge_groups} group sizes that add up to the {E} edges of edge_index and edge_emb')
-        if not self.training and self.layer < TP_NV4:
+        if not self.training and self.layer < TP_NV4 and not self.eval_with_training_ops:
             ns = edge_emb.shape[1]
             edge_attr = torch.cat([edge_emb, node_attr[edge_index[0], :ns], node_attr[edge_index[1], :ns]], -1)
             return self.forward(node_attr, edge_index, list(torch.split(edge_attr, sizes)), edge_sh)

@@ -1,10 +1,12 @@
 """The forward half of the diffusion, the score-matching loss and the training loop: the reference's validation pass (test_epoch, utils/training.py) for a
-loaded checkpoint, and its training pass (train_epoch) for a ``train_model.TrainableScoreModel``: ``noise_batch`` is NoiseTransform.apply_noise per complex
+loaded checkpoint (``validation_loss``) and for the trainable classes (``test_epoch``), its sampling validation (``inference_epoch`` through
+``inference_engine``), and its training pass (train_epoch) for a ``train_model.TrainableScoreModel``: ``noise_batch`` is NoiseTransform.apply_noise per complex
 at its own time followed by collation, ``draw_times`` the times, ``train_epoch`` utils/training.py:96-135, ``ExponentialMovingAverage`` utils/utils.py:117-.
 ``noise_complex`` is NoiseTransform.apply_noise (datasets_utils/pdbbind.py:40-57) for B copies of a complex at a common t, ``loss_function`` is
 utils/training.py:14-61, ``validation_loss`` runs noise -> score model -> loss over complexes and noise levels.  Every draw comes from the counter-based generator (ddk_rng_perturbation), so a validation number is a pure function of (checkpoint, complexes, seed).
 All compute is in libddk.so (csrc/k_so3.hip, csrc/k_noising.hip and the score model); the host holds scalars."""
 import collections
+import contextlib
 import os
 
 import numpy as np
@@ -462,3 +464,126 @@ def train_epoch(model, complexes, optimizer, batch_size, seed, epoch, ema=None, 
         ran += 1
     values = (total / ran).tolist() if ran else [float('nan')] * len(TRAIN_METERS)      # the one read-back
     return dict(zip(TRAIN_METERS, values))
+
+
+def _names(complexes):
+    return [c.get('name') if hasattr(c, 'get') else None for c in complexes]
+
+
+@contextlib.contextmanager
+def reproducible_evaluation(model):
+    """inside: the model's conv layers evaluate with the training ops (``TensorProductConvLayer.eval_with_training_ops``), which use no atomics"""
+    layers = [m for m in model.modules() if hasattr(m, 'eval_with_training_ops')]
+    was = [m.eval_with_training_ops for m in layers]
+    for m in layers:
+        m.eval_with_training_ops = True
+    try:
+        yield
+    finally:
+        for m, w in zip(layers, was):
+            m.eval_with_training_ops = w
+
+
+def test_epoch(model, complexes, batch_size, seed, epoch=0, test_sigma_intervals=False):
+    """The validation loss of a ``TrainableScoreModel`` or ``train_model.LatentModelWrapper`` over ``complexes`` (dicts as ``noise_batch`` takes):
+    utils/training.py:138-177.  The model is put in ``.eval()`` (and left there, as in the reference; ``train_epoch`` sets ``.train()`` itself) and runs under
+    ``torch.no_grad()``.  The complexes are taken in list order in batches of ``batch_size``; complex i is noised at ``draw_times(names, seed,
+    draw=epoch)[i]`` with draw = epoch; step k's forward gets ``_step_seed(seed, epoch, k)`` (the oracle encoder's Gumbel noise) and, for a wrapper with a
+    drop rate, ``keep=draw_latent_keep(batch, rate, seed, epoch)`` (the reference's wrapper drops latents in evaluation too, from torch's generator; here
+    the flags follow the seed), then ``loss_function(apply_mean=False)``.  A batch of one graph is run: evaluation needs no batch statistics.  The conv
+    layers evaluate with the training ops (dropout off, BatchNorm on its running buffers): the fused inference kernel they would otherwise run scatters
+    with fp32 atomics (``ddk_conv_forward`` at the op boundary never takes the deterministic scatter), and the last bits of a loss would differ from
+    run to run.  The trade: this is not the forward ``model.eval()`` alone gives; ``TensorProductConvLayer`` reads one more flag
+    (``eval_with_training_ops``, at three places in tensor_layers.py, off outside this function), and the validation pass runs the training ops, which
+    are slower than the inference kernel (their [E, 72] hidden rows and node-sorted edge lists are built as in training).  What it buys is a number that is
+    the same on every run, so ``best_model.pt`` does not flip on an atomic's order.  The two routes agree to 8e-8 relative on every meter where measured
+    (tests/test_gpu_validation_epochs.py holds them to 1e-5).  The
+    result is a pure function of (the model's state, complexes, seed, epoch) at a given ``batch_size``.  The per-complex values of the seven meters stay
+    on the device ([n, 7], fp64) and are read back ONCE; returned: the reference's unpooled means over the complexes, {'loss', 'tr_loss', ...} (NaN
+    for an empty list), formed on the host in fp64 in list order.  (The sums themselves are not formed on the device: its scatter-add is an atomic
+    and would give the mean's last bits an order of its own.)
+
+    ``test_sigma_intervals``: also 'int{i}_{name}', i = 0 .. 9, the means over the complexes with floor(10 t) == i, NaN for an interval without one.
+    The reference creates this second meter and never adds to it (its summary is 0 / 0 everywhere); here it is filled as described.
+
+    The reference's out-of-memory branch, which skips a batch, is not reproduced: the error is raised."""
+    ctx = _ctx_of(model)
+    model.eval()
+    from .train_model import LatentModelWrapper
+    latent = isinstance(model, LatentModelWrapper) and model.latent_droprate > 0
+    n, bs = len(complexes), int(batch_size)
+    if bs < 1:
+        raise ValueError(f'ddk: test_epoch: batch_size must be positive, got {batch_size}')
+    times = draw_times(_names(complexes), seed, epoch) if n else np.zeros(0, np.float32)
+    rows = torch.zeros((n, len(TRAIN_METERS)), dtype=torch.float64, device=torch.device('cuda', ctx.device))
+    with torch.no_grad(), reproducible_evaluation(model):
+        for step, at in enumerate(range(0, n, bs)):
+            part = complexes[at:at + bs]
+            data, targets = noise_batch(model, part, times[at:at + bs], seed, draw=epoch)
+            step_seed = _step_seed(seed, epoch, step)
+            if latent:
+                tr_pred, rot_pred, tor_pred = model(data, seed=step_seed, keep=draw_latent_keep(part, model.latent_droprate, seed, epoch))
+            else:
+                tr_pred, rot_pred, tor_pred = model(data, seed=step_seed)
+            out = loss_function(tr_pred, rot_pred, tor_pred, targets, model, apply_mean=False)
+            rows[at:at + len(part)] = torch.stack([v.detach().double().reshape(-1) for v in out], dim=1)
+    host = rows.cpu().numpy()      # the one read-back
+    mean = lambda a: a.mean(axis=0).tolist() if len(a) else [float('nan')] * len(TRAIN_METERS)
+    result = dict(zip(TRAIN_METERS, mean(host)))
+    if test_sigma_intervals:
+        interval = np.floor(10.0 * np.asarray(times, np.float64)).astype(np.int64)
+        for i in range(10):
+            result.update({f'int{i}_{k}': v for k, v in zip(TRAIN_METERS, mean(host[interval == i]))})
+    return result
+
+
+def inference_engine(model, args, engine=None):
+    """The inference model of a trainable one: ``model_utils.get_model(args, ...)`` (built once: pass the returned object back as ``engine`` and only the
+    weights are loaded again, into the same context) with ``model.state_dict()`` loaded ``strict=True`` - for a ``train_model.LatentModelWrapper`` both
+    halves, the oracle encoder included.  ``args``: the model_parameters.yml Namespace the model was built from.  A reload drops the engine's cached
+    complexes (their node embeddings were made with the old weights).  The packed weights of the loads before stay allocated until the context goes
+    (``ddk_finalize_weights`` packs anew and frees nothing): measured 18.8 MB of device memory per reload for five conv layers with latent_dim 2, so a run
+    that validates 80 times on one engine ends 1.5 GB up.  An engine that is dropped gives everything back; make a new one (``engine=None``) every few
+    dozen reloads where that matters."""
+    from functools import partial
+    from .model_utils import get_model
+    if engine is None:
+        engine = get_model(args, torch.device('cuda', _ctx_of(model).device), partial(t_to_sigma, args=args), no_parallel=True)
+    engine.load_state_dict(model.state_dict(), strict=True)
+    return engine
+
+
+def inference_epoch(model, complexes, args, seed, epoch=0, engine=None):
+    """utils/training.py:180-231: sample ONE pose per complex with the model as it is now and count the poses under 2 and 5 A.  ``complexes``: dicts as
+    ``train_epoch`` takes ('lig_pos' is the true pose in the receptor-centred frame); ``args``: the model's Namespace with ``inference_steps`` and, for a
+    latent model, ``sampling_latent_temperature``; ``engine``: what ``inference_engine(model, args)`` returned earlier (the weights are loaded again), None:
+    a new one.  Per complex i, with s = ``_step_seed(seed, epoch, i)``: ``sampling.randomize_position(seed=s)``, ``sampling.sampling(batch_size=1,
+    ar_model=None, seed=s)`` - a latent model samples with ORACLE latents at ``args.sampling_latent_temperature`` - and the heavy-atom RMSD
+    (``lig_x[:, 0] != 0``) to the true pose, on the device.  One read-back at the end.  Returns {'rmsds_lt2', 'rmsds_lt5'} in percent and the RMSDs
+    themselves, a float64 array, under 'rmsds': a pure function of (the model's state, complexes, seed, epoch) on a deterministic context.  Without
+    latents (``latent_dim`` 0) the same minus the encoder.  The reference retries a complex whose Kabsch SVD "failed to converge"; there is no SVD on
+    this path (the alignment is closed-form on the device), so there is nothing to retry."""
+    from functools import partial
+    from .diffusion_utils import get_t_schedule
+    from .sampling import randomize_position, sampling
+    engine = inference_engine(model, args, engine)
+    dev = torch.device('cuda', _ctx_of(model).device)
+    sched = get_t_schedule(inference_steps=args.inference_steps)
+    use_latent = int(getattr(args, 'latent_dim', 0)) > 0
+    rmsds = torch.zeros(len(complexes), dtype=torch.float64, device=dev)
+    for i, c in enumerate(complexes):
+        s = _step_seed(seed, epoch, i)
+        true = np.asarray(c['lig_pos'], np.float32).reshape(-1, 3)
+        g = _data.from_arrays(c)
+        g['ligand'].orig_pos_torch = torch.from_numpy(true.copy())
+        graphs = [g]
+        randomize_position(graphs, args.no_torsion, False, args.tr_sigma_max, device=dev, seed=s)
+        graphs, _ = sampling(graphs, engine, args.inference_steps, sched, sched, sched, dev, partial(t_to_sigma, args=args), args, batch_size=1,
+                             use_latent=use_latent, ar_model=None, seed=s, gumbel_latent_temperature=getattr(args, 'sampling_latent_temperature', 0.01))
+        heavy = (np.asarray(c['lig_x'])[:, 0] != 0).astype(np.float32)
+        ref = h2d_async(torch.from_numpy(np.concatenate([true, heavy[:, None]], axis=1)), dev)      # one copy: the true pose and the heavy-atom flags
+        d2 = ((graphs[0]['ligand'].pos.detach().float() - ref[:, :3]) ** 2).sum(dim=1)
+        rmsds[i] = ((d2 * ref[:, 3]).sum() / ref[:, 3].sum()).sqrt()
+    host = rmsds.cpu().numpy()      # the one read-back
+    n = max(len(host), 1)
+    return {'rmsds_lt2': 100.0 * float((host < 2).sum()) / n, 'rmsds_lt5': 100.0 * float((host < 5).sum()) / n, 'rmsds': host}

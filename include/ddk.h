@@ -357,6 +357,16 @@ int64_t ddk_eemb_latent_workspace(int64_t E, int32_t K, int32_t L);
  *      gives position pos the word pos % 4; u = (word >> 8) * 2^-24.  A graph's noise is a pure function of (seed, complex, sample, draw, d, pos), whatever
  *      the batch; no existing purpose is touched; no node limit.  Limits: 1 <= G <= 65536, 1 <= D <= 4, 0 <= draw < 2^20, sample >= 0, T > 0 and finite.
  *
+ *      ddk_gumbel_pick_samples: the one-hot latents of B samples of ONE complex from ONE table of logits (the oracle encoder in front of the sampler reads only
+ *      the true pose, so its logits are the same for every copy of the complex in a batch).  Rows b n .. (b + 1) n - 1 of lig_latent [B n_lig, D] and rec_latent
+ *      [B n_rec, D] are, BIT FOR BIT, out_l and out_r of ddk_gumbel_softmax_batch called with G = 1, stream id ``stream_id``, sample = sample0 + b and the same
+ *      seed, draw and T (one device body serves both kernels): the noise is the same DDK_GUMBEL_LAYOUT, no new number.  choices (DEVICE int32 [B, D], or NULL):
+ *      the position of the one, ligand nodes first, then n_lig + the receptor index (the convention of ddk_ar_decode); -1 where no y compares (NaN logits).
+ *      One launch, one workgroup of 256 threads per (b, d), no atomics; the soft y lives in a grow-only scratch buffer of the context (B (n_lig + n_rec) D
+ *      floats).  stream_id is passed by value.  Limits: 1 <= B <= 65536, 1 <= D <= 4, T > 0 and finite, 0 <= draw < 2^20, sample0 >= 0 and
+ *      sample0 + B - 1 < 2^31, n_lig + n_rec < 2^31; a violation or a null pointer of a side that has nodes is DDK_ERR_INVALID before any launch, and the
+ *      outputs stay untouched.  n_lig + n_rec == 0 writes nothing.
+ *
  *      ddk_rng_latent_keep: the per-complex keep flag of the latent dropout (classifier-free guidance training), keep_out[i] = (u >= rate) as 1.0f / 0.0f with u
  *      the uniform of purpose 12 for (seed, stream_id[i], sample, draw), block 0, word 0.  A HOST function as ddk_rng_forward_times. */
 #define DDK_GUMBEL_LAYOUT 1
@@ -367,6 +377,9 @@ int ddk_gumbel_softmax_batch(ddk_ctx* ctx, int32_t G, int32_t D, const float* lo
 int ddk_gumbel_softmax_batch_backward(ddk_ctx* ctx, int32_t G, int32_t D, const float* y_l, int64_t n_lig, const float* y_r, int64_t n_rec,
                                       const int64_t* lig_ptr, const int64_t* rec_ptr, float T, const float* grad_out_l, const float* grad_out_r,
                                       float* grad_logit_l, float* grad_logit_r, void* stream);
+int ddk_gumbel_pick_samples(ddk_ctx* ctx, int32_t B, int32_t D, const float* logit_l /* [n_lig, D] */, int64_t n_lig, const float* logit_r /* [n_rec, D] */,
+                            int64_t n_rec, float T, uint64_t seed, uint64_t stream_id, int32_t sample0, int32_t draw, float* lig_latent /* [B*n_lig, D] */,
+                            float* rec_latent /* [B*n_rec, D] */, int32_t* choices /* [B, D] or NULL */, void* stream);
 int ddk_rng_latent_keep(ddk_ctx* ctx, uint64_t seed, int32_t n, const uint64_t* stream_id /* HOST [n] */, int32_t sample, int32_t draw, float rate,
                         float* keep_out /* HOST [n] */);
 
