@@ -617,32 +617,47 @@ int ddk_eemb_latent_backward(ddk_ctx* ctx, const float* pos_a, int64_t n_a, cons
 
 int64_t ddk_eemb_latent_workspace(int64_t E, int32_t K, int32_t L) { return eemb_latent_workspace(E, K, L); }
 
-// the checks the two Gumbel-softmax entries share
-static int gumbel_check(ddk_ctx* ctx, const char* who, int32_t G, int32_t D, int64_t n_lig, int64_t n_rec, const int64_t* lig_ptr, const int64_t* rec_ptr, float T) {
+// The checks every entry over a graph's ligand nodes followed by its receptor nodes shares (RaggedTables).  ``samples``: ddk_gumbel_pick_samples, whose count is
+// B samples of one graph, which has no pointer tables and whose rows b n + p must fit 31 bits
+static int ragged_check(ddk_ctx* ctx, const char* who, int32_t G, int32_t D, int64_t n_lig, int64_t n_rec, const int64_t* lig_ptr, const int64_t* rec_ptr,
+                        bool samples = false) {
   int rc = check_launchable(ctx, 0);
   if (rc) return rc;
   const std::string w(who);
-  if (G < 1 || G > 65536) return fail(ctx, DDK_ERR_INVALID, w + ": G must be in [1, 65536]");
+  if (G < 1 || G > 65536) return fail(ctx, DDK_ERR_INVALID, w + (samples ? ": B must be in [1, 65536]" : ": G must be in [1, 65536]"));
   if (D < 1 || D > 4) return fail(ctx, DDK_ERR_INVALID, w + ": D must be in 1..4");
-  if (n_lig < 0 || n_rec < 0 || n_lig >= (int64_t)1 << 31 || n_rec >= (int64_t)1 << 31) return fail(ctx, DDK_ERR_INVALID, w + ": node count out of range");
+  if (n_lig < 0 || n_rec < 0 || n_lig >= (int64_t)1 << 31 || n_rec >= (int64_t)1 << 31 || (samples && n_lig + n_rec >= (int64_t)1 << 31))
+    return fail(ctx, DDK_ERR_INVALID, w + ": node count out of range (n_lig, n_rec in [0, 2^31); for samples of one graph n_lig + n_rec < 2^31)");
+  if (!samples && (!lig_ptr || !rec_ptr)) return fail(ctx, DDK_ERR_INVALID, w + ": null lig_ptr or rec_ptr");
+  return DDK_OK;
+}
+// a side that has nodes passes every one of its operands
+static int ragged_sides(ddk_ctx* ctx, const char* who, int64_t n_lig, int64_t n_rec, std::initializer_list<const void*> lig, std::initializer_list<const void*> rec,
+                        const char* what) {
+  bool null = false;
+  for (const void* p : lig) null |= n_lig > 0 && !p;
+  for (const void* p : rec) null |= n_rec > 0 && !p;
+  return null ? fail(ctx, DDK_ERR_INVALID, std::string(who) + ": null operand (" + what + " of a side that has nodes)") : DDK_OK;
+}
+static int temperature_draw_check(ddk_ctx* ctx, const char* who, float T, int32_t draw) {
+  const std::string w(who);
   if (!(T > 0.f) || !(T < INFINITY)) return fail(ctx, DDK_ERR_INVALID, w + ": the temperature must be positive and finite");
-  if (!lig_ptr || !rec_ptr) return fail(ctx, DDK_ERR_INVALID, w + ": null lig_ptr or rec_ptr");
+  if (draw < 0 || draw >= (1 << 20)) return fail(ctx, DDK_ERR_INVALID, w + ": draw must be in [0, 2^20)");
   return DDK_OK;
 }
 
 int ddk_gumbel_softmax_batch(ddk_ctx* ctx, int32_t G, int32_t D, const float* logit_l, int64_t n_lig, const float* logit_r, int64_t n_rec,
                              const int64_t* lig_ptr, const int64_t* rec_ptr, float T, uint64_t seed, const uint64_t* stream_id, int32_t sample, int32_t draw,
                              float* y_l, float* y_r, float* out_l, float* out_r, void* stream) {
-  int rc = gumbel_check(ctx, "ddk_gumbel_softmax_batch", G, D, n_lig, n_rec, lig_ptr, rec_ptr, T);
-  if (rc) return rc;
+  const char* who = "ddk_gumbel_softmax_batch";
+  int rc = ragged_check(ctx, who, G, D, n_lig, n_rec, lig_ptr, rec_ptr);
+  if (rc || (rc = temperature_draw_check(ctx, who, T, draw))) return rc;
   if (sample < 0) return fail(ctx, DDK_ERR_INVALID, "ddk_gumbel_softmax_batch: sample must be >= 0");
-  if (draw < 0 || draw >= (1 << 20)) return fail(ctx, DDK_ERR_INVALID, "ddk_gumbel_softmax_batch: draw must be in [0, 2^20)");
   if (!stream_id) return fail(ctx, DDK_ERR_INVALID, "ddk_gumbel_softmax_batch: null stream_id");
-  if ((n_lig > 0 && (!logit_l || !y_l || !out_l)) || (n_rec > 0 && (!logit_r || !y_r || !out_r)))
-    return fail(ctx, DDK_ERR_INVALID, "ddk_gumbel_softmax_batch: null operand (logit, y, out of a side that has nodes)");
+  if ((rc = ragged_sides(ctx, who, n_lig, n_rec, {logit_l, y_l, out_l}, {logit_r, y_r, out_r}, "logit, y, out"))) return rc;
   if (n_lig + n_rec == 0) return DDK_OK;
-  const GumbelOperands o{lig_ptr, rec_ptr, n_lig, n_rec, G, D, T};
-  hipError_t e = launch_gumbel_forward(o, logit_l, logit_r, seed, stream_id, (uint32_t)sample, (uint32_t)draw, y_l, y_r, out_l, out_r, (hipStream_t)stream);
+  hipError_t e = launch_gumbel_forward(RaggedTables{lig_ptr, rec_ptr, n_lig, n_rec, G, D}, T, logit_l, logit_r, seed, stream_id, (uint32_t)sample, (uint32_t)draw,
+                                       y_l, y_r, out_l, out_r, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(ctx, e, "gumbel_softmax_batch launch");
   return DDK_OK;
 }
@@ -650,18 +665,10 @@ int ddk_gumbel_softmax_batch(ddk_ctx* ctx, int32_t G, int32_t D, const float* lo
 int ddk_gumbel_pick_samples(ddk_ctx* ctx, int32_t B, int32_t D, const float* logit_l, int64_t n_lig, const float* logit_r, int64_t n_rec, float T, uint64_t seed,
                             uint64_t stream_id, int32_t sample0, int32_t draw, float* lig_latent, float* rec_latent, int32_t* choices, void* stream) {
   const char* who = "ddk_gumbel_pick_samples";
-  int rc = check_launchable(ctx, 0);
-  if (rc) return rc;
-  const std::string w(who);
-  if (B < 1 || B > 65536) return fail(ctx, DDK_ERR_INVALID, w + ": B must be in [1, 65536]");
-  if (D < 1 || D > 4) return fail(ctx, DDK_ERR_INVALID, w + ": D must be in 1..4");
-  if (n_lig < 0 || n_rec < 0 || n_lig >= (int64_t)1 << 31 || n_rec >= (int64_t)1 << 31 || n_lig + n_rec >= (int64_t)1 << 31)
-    return fail(ctx, DDK_ERR_INVALID, w + ": node count out of range (n_lig, n_rec >= 0, n_lig + n_rec < 2^31)");
-  if (!(T > 0.f) || !(T < INFINITY)) return fail(ctx, DDK_ERR_INVALID, w + ": the temperature must be positive and finite");
-  if (sample0 < 0 || (int64_t)sample0 + B - 1 > INT32_MAX) return fail(ctx, DDK_ERR_INVALID, w + ": sample0 must be >= 0 and sample0 + B - 1 < 2^31");
-  if (draw < 0 || draw >= (1 << 20)) return fail(ctx, DDK_ERR_INVALID, w + ": draw must be in [0, 2^20)");
-  if ((n_lig > 0 && (!logit_l || !lig_latent)) || (n_rec > 0 && (!logit_r || !rec_latent)))
-    return fail(ctx, DDK_ERR_INVALID, w + ": null operand (logit, latent of a side that has nodes)");
+  int rc = ragged_check(ctx, who, B, D, n_lig, n_rec, nullptr, nullptr, true);
+  if (rc || (rc = temperature_draw_check(ctx, who, T, draw))) return rc;
+  if (sample0 < 0 || (int64_t)sample0 + B - 1 > INT32_MAX) return fail(ctx, DDK_ERR_INVALID, "ddk_gumbel_pick_samples: sample0 must be >= 0 and sample0 + B - 1 < 2^31");
+  if ((rc = ragged_sides(ctx, who, n_lig, n_rec, {logit_l, lig_latent}, {logit_r, rec_latent}, "logit, latent"))) return rc;
   if (n_lig + n_rec == 0) return DDK_OK;
   Workspace& ws = ctx->ws;
   if ((rc = ensure(ctx, (void**)&ws.gumbel_y, &ws.gumbel_y_cap, (size_t)B * (size_t)(n_lig + n_rec) * D * sizeof(float)))) return rc;
@@ -674,13 +681,13 @@ int ddk_gumbel_pick_samples(ddk_ctx* ctx, int32_t B, int32_t D, const float* log
 int ddk_gumbel_softmax_batch_backward(ddk_ctx* ctx, int32_t G, int32_t D, const float* y_l, int64_t n_lig, const float* y_r, int64_t n_rec,
                                       const int64_t* lig_ptr, const int64_t* rec_ptr, float T, const float* grad_out_l, const float* grad_out_r,
                                       float* grad_logit_l, float* grad_logit_r, void* stream) {
-  int rc = gumbel_check(ctx, "ddk_gumbel_softmax_batch_backward", G, D, n_lig, n_rec, lig_ptr, rec_ptr, T);
-  if (rc) return rc;
-  if ((n_lig > 0 && (!y_l || !grad_out_l || !grad_logit_l)) || (n_rec > 0 && (!y_r || !grad_out_r || !grad_logit_r)))
-    return fail(ctx, DDK_ERR_INVALID, "ddk_gumbel_softmax_batch_backward: null operand (y, grad_out, grad_logit of a side that has nodes)");
+  const char* who = "ddk_gumbel_softmax_batch_backward";
+  int rc = ragged_check(ctx, who, G, D, n_lig, n_rec, lig_ptr, rec_ptr);
+  if (rc || (rc = temperature_draw_check(ctx, who, T, 0))) return rc;
+  if ((rc = ragged_sides(ctx, who, n_lig, n_rec, {y_l, grad_out_l, grad_logit_l}, {y_r, grad_out_r, grad_logit_r}, "y, grad_out, grad_logit"))) return rc;
   if (n_lig + n_rec == 0) return DDK_OK;
-  const GumbelOperands o{lig_ptr, rec_ptr, n_lig, n_rec, G, D, T};
-  hipError_t e = launch_gumbel_backward(o, y_l, y_r, grad_out_l, grad_out_r, grad_logit_l, grad_logit_r, (hipStream_t)stream);
+  hipError_t e = launch_gumbel_backward(RaggedTables{lig_ptr, rec_ptr, n_lig, n_rec, G, D}, T, y_l, y_r, grad_out_l, grad_out_r, grad_logit_l, grad_logit_r,
+                                        (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(ctx, e, "gumbel_softmax_batch_backward launch");
   return DDK_OK;
 }
@@ -715,31 +722,24 @@ int ddk_rng_decoding_index(ddk_ctx* ctx, uint64_t seed, int32_t n, const uint64_
   return DDK_OK;
 }
 
-// the checks the two node cross-entropy entries share
-static int node_ce_check(ddk_ctx* ctx, const char* who, int32_t G, int32_t D, int64_t n_lig, int64_t n_rec, const int64_t* lig_ptr, const int64_t* rec_ptr,
-                         const int32_t* column, int32_t soft) {
-  int rc = check_launchable(ctx, 0);
-  if (rc) return rc;
-  const std::string w(who);
-  if (G < 1 || G > 65536) return fail(ctx, DDK_ERR_INVALID, w + ": G must be in [1, 65536]");
-  if (D < 1 || D > 4) return fail(ctx, DDK_ERR_INVALID, w + ": D must be in 1..4");
-  if (n_lig < 0 || n_rec < 0 || n_lig >= (int64_t)1 << 31 || n_rec >= (int64_t)1 << 31) return fail(ctx, DDK_ERR_INVALID, w + ": node count out of range");
-  if (soft != 0 && soft != 1) return fail(ctx, DDK_ERR_INVALID, w + ": soft must be 0 or 1");
-  if (!lig_ptr || !rec_ptr || !column) return fail(ctx, DDK_ERR_INVALID, w + ": null lig_ptr, rec_ptr or column");
+// what the two node cross-entropy entries check on top of ragged_check
+static int column_soft_check(ddk_ctx* ctx, const char* who, const int32_t* column, int32_t soft) {
+  if (soft != 0 && soft != 1) return fail(ctx, DDK_ERR_INVALID, std::string(who) + ": soft must be 0 or 1");
+  if (!column) return fail(ctx, DDK_ERR_INVALID, std::string(who) + ": null column");
   return DDK_OK;
 }
 
 int ddk_node_cross_entropy_batch(ddk_ctx* ctx, int32_t G, int32_t D, const float* logit_l, int64_t n_lig, const float* logit_r, int64_t n_rec,
                                  const int64_t* lig_ptr, const int64_t* rec_ptr, const float* teacher_l, const float* teacher_r, const int32_t* column,
                                  int32_t soft, float* loss, int64_t* pick, int64_t* target, double* saved, void* stream) {
-  int rc = node_ce_check(ctx, "ddk_node_cross_entropy_batch", G, D, n_lig, n_rec, lig_ptr, rec_ptr, column, soft);
-  if (rc) return rc;
-  if ((n_lig > 0 && (!logit_l || !teacher_l)) || (n_rec > 0 && (!logit_r || !teacher_r)))
-    return fail(ctx, DDK_ERR_INVALID, "ddk_node_cross_entropy_batch: null operand (logit, teacher of a side that has nodes)");
+  const char* who = "ddk_node_cross_entropy_batch";
+  int rc = ragged_check(ctx, who, G, D, n_lig, n_rec, lig_ptr, rec_ptr);
+  if (rc || (rc = column_soft_check(ctx, who, column, soft))) return rc;
+  if ((rc = ragged_sides(ctx, who, n_lig, n_rec, {logit_l, teacher_l}, {logit_r, teacher_r}, "logit, teacher"))) return rc;
   if (!loss || !pick || !target || !saved) return fail(ctx, DDK_ERR_INVALID, "ddk_node_cross_entropy_batch: null output (loss, pick, target, saved)");
   if (n_lig + n_rec == 0) return DDK_OK;
-  const NodeCeArgs a{logit_l, logit_r, teacher_l, teacher_r, lig_ptr, rec_ptr, column, loss, pick, target, saved, n_lig, n_rec, D, soft};
-  hipError_t e = launch_node_ce_forward(a, G, (hipStream_t)stream);
+  const NodeCeArgs a{{lig_ptr, rec_ptr, n_lig, n_rec, G, D}, logit_l, logit_r, teacher_l, teacher_r, column, loss, pick, target, saved, soft};
+  hipError_t e = launch_node_ce_forward(a, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(ctx, e, "node_cross_entropy_batch launch");
   return DDK_OK;
 }
@@ -748,14 +748,17 @@ int ddk_node_cross_entropy_batch_backward(ddk_ctx* ctx, int32_t G, int32_t D, co
                                           const int64_t* lig_ptr, const int64_t* rec_ptr, const float* teacher_l, const float* teacher_r,
                                           const int32_t* column, int32_t soft, const float* grad, const int64_t* target, const double* saved,
                                           float* grad_logit_l, float* grad_logit_r, void* stream) {
-  int rc = node_ce_check(ctx, "ddk_node_cross_entropy_batch_backward", G, D, n_lig, n_rec, lig_ptr, rec_ptr, column, soft);
-  if (rc) return rc;
-  if ((n_lig > 0 && (!logit_l || !grad_logit_l || (soft && !teacher_l))) || (n_rec > 0 && (!logit_r || !grad_logit_r || (soft && !teacher_r))))
-    return fail(ctx, DDK_ERR_INVALID, "ddk_node_cross_entropy_batch_backward: null operand (logit, grad_logit, and with soft = 1 teacher, of a side that has nodes)");
+  const char* who = "ddk_node_cross_entropy_batch_backward";
+  int rc = ragged_check(ctx, who, G, D, n_lig, n_rec, lig_ptr, rec_ptr);
+  if (rc || (rc = column_soft_check(ctx, who, column, soft))) return rc;
+  // (hard mode reads no teacher table)
+  if ((rc = ragged_sides(ctx, who, n_lig, n_rec, {logit_l, grad_logit_l, soft ? teacher_l : logit_l}, {logit_r, grad_logit_r, soft ? teacher_r : logit_r},
+                         "logit, grad_logit, and with soft = 1 teacher,")))
+    return rc;
   if (!grad || !target || !saved) return fail(ctx, DDK_ERR_INVALID, "ddk_node_cross_entropy_batch_backward: null argument (grad, target, saved)");
   if (n_lig + n_rec == 0) return DDK_OK;
-  const NodeCeBwdArgs a{logit_l, logit_r, teacher_l, teacher_r, lig_ptr, rec_ptr, column, grad, target, saved, grad_logit_l, grad_logit_r, n_lig, n_rec, D, soft};
-  hipError_t e = launch_node_ce_backward(a, G, (hipStream_t)stream);
+  const NodeCeBwdArgs a{{lig_ptr, rec_ptr, n_lig, n_rec, G, D}, logit_l, logit_r, teacher_l, teacher_r, column, grad, target, saved, grad_logit_l, grad_logit_r, soft};
+  hipError_t e = launch_node_ce_backward(a, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(ctx, e, "node_cross_entropy_batch_backward launch");
   return DDK_OK;
 }

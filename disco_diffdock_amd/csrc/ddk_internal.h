@@ -449,34 +449,35 @@ hipError_t launch_eemb_latent_backward(const EembOperands& o, const EembLatent& 
                                        float* grad_b1, float* grad_w2, float* grad_b2, float* grad_uemb, float* grad_lat_a, float* grad_lat_b,
                                        float* workspace, hipStream_t s);
 int64_t eemb_latent_workspace(int64_t E, int32_t K, int32_t NL);
-// k_gumbel.hip: the ragged straight-through Gumbel softmax over a graph's ligand and receptor nodes and its vector-Jacobian product (include/ddk.h:
-// ddk_gumbel_softmax_batch / ddk_gumbel_softmax_batch_backward).  lig_ptr / rec_ptr [G + 1]: device tables, range-checked per graph in the kernels
-struct GumbelOperands { const int64_t* lig_ptr; const int64_t* rec_ptr; int64_t n_lig, n_rec; int G, D; float T; };
-hipError_t launch_gumbel_forward(const GumbelOperands& o, const float* logit_l, const float* logit_r, uint64_t seed, const uint64_t* stream_id, uint32_t sample,
-                                 uint32_t draw, float* y_l, float* y_r, float* out_l, float* out_r, hipStream_t s);
+// The operands every op over a graph's ligand nodes followed by its receptor nodes takes (k_ragged.h): the node counts of the two tables, D columns, and
+// lig_ptr / rec_ptr [G + 1], device tables that the kernels range-check per graph (a graph whose pair is no range of its table is left alone)
+struct RaggedTables { const int64_t* lig_ptr; const int64_t* rec_ptr; int64_t n_lig, n_rec; int G, D; };
+// k_gumbel.hip: the ragged straight-through Gumbel softmax and its vector-Jacobian product (include/ddk.h: ddk_gumbel_softmax_batch /
+// ddk_gumbel_softmax_batch_backward), and B samples of one complex from one table of logits (ddk_gumbel_pick_samples)
+hipError_t launch_gumbel_forward(const RaggedTables& o, float T, const float* logit_l, const float* logit_r, uint64_t seed, const uint64_t* stream_id,
+                                 uint32_t sample, uint32_t draw, float* y_l, float* y_r, float* out_l, float* out_r, hipStream_t s);
 hipError_t launch_gumbel_pick(int B, int D, const float* logit_l, int64_t n_lig, const float* logit_r, int64_t n_rec, float T, uint64_t seed, uint64_t stream_id,
                               uint32_t sample0, uint32_t draw, float* y /* [B (n_lig + n_rec), D] scratch */, float* out_l, float* out_r, int32_t* choices,
-                              hipStream_t s);      // ddk_gumbel_pick_samples: B samples of one complex from one table of logits
-hipError_t launch_gumbel_backward(const GumbelOperands& o, const float* y_l, const float* y_r, const float* gout_l, const float* gout_r, float* grad_l,
+                              hipStream_t s);
+hipError_t launch_gumbel_backward(const RaggedTables& o, float T, const float* y_l, const float* y_r, const float* gout_l, const float* gout_r, float* grad_l,
                                   float* grad_r, hipStream_t s);
-// k_node_ce.hip: the AR model's ragged cross-entropy over a graph's ligand and receptor nodes and its gradient (include/ddk.h: ddk_node_cross_entropy_batch /
-// ddk_node_cross_entropy_batch_backward).  s_*: the student's logits [n], t_*: the teacher's tables [n, D]; lig_ptr / rec_ptr [G + 1] and column [G]: device
-// tables, checked per graph in the kernels; saved [G, 2] = (lse_s, lse_t)
+// k_node_ce.hip: the AR model's ragged cross-entropy and its gradient (include/ddk.h: ddk_node_cross_entropy_batch / ddk_node_cross_entropy_batch_backward).
+// s_*: the student's logits [n], t_*: the teacher's tables [n, D]; column [G]: a device table, checked per graph in the kernels; saved [G, 2] = (lse_s, lse_t)
 struct NodeCeArgs {
+  RaggedTables r;
   const float* s_l; const float* s_r; const float* t_l; const float* t_r;
-  const int64_t* lig_ptr; const int64_t* rec_ptr; const int32_t* column;
+  const int32_t* column;
   float* loss; int64_t* pick; int64_t* target; double* saved;
-  int64_t n_lig, n_rec;
-  int D, soft;
+  int soft;
 };
 struct NodeCeBwdArgs {
+  RaggedTables r;
   const float* s_l; const float* s_r; const float* t_l; const float* t_r;
-  const int64_t* lig_ptr; const int64_t* rec_ptr; const int32_t* column;
+  const int32_t* column;
   const float* grad; const int64_t* target; const double* saved;
   float* grad_l; float* grad_r;
-  int64_t n_lig, n_rec;
-  int D, soft;
+  int soft;
 };
-hipError_t launch_node_ce_forward(const NodeCeArgs& a, int G, hipStream_t s);
-hipError_t launch_node_ce_backward(const NodeCeBwdArgs& a, int G, hipStream_t s);
+hipError_t launch_node_ce_forward(const NodeCeArgs& a, hipStream_t s);
+hipError_t launch_node_ce_backward(const NodeCeBwdArgs& a, hipStream_t s);
 }  // namespace ddk

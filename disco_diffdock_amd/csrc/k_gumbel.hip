@@ -1,7 +1,8 @@
 // The ragged straight-through Gumbel softmax in front of the latent-conditioned score model (include/ddk.h: ddk_gumbel_softmax_batch, ddk_gumbel_pick_samples, DDK_GUMBEL_LAYOUT) and
 // its vector-Jacobian product: the reference's per-graph loop (latent_encoder.py:328-335, pretrained_score_encoder.py:74-81 over models/layers.py:152-181) for a
 // whole collated batch in one launch.  ONE WORKGROUP per (graph g, latent dimension d); the class axis is the graph's ligand nodes, then its receptor nodes,
-// position p = 0 .. n_lig_g + n_rec_g - 1.  A written-out order (compiled with -ffp-contract=off):
+// position p = 0 .. n_lig_g + n_rec_g - 1: the pointer-pair rule, the walk over the positions and the halving trees are k_ragged.h's, shared with
+// k_node_ce.hip.  A written-out order (compiled with -ffp-contract=off):
 //   u    = (word >> 8) * 2^-24                               the word of position p: see THE NOISE below
 //   gum  = -log(-log(u + 1e-20f) + 1e-20)                    the addition to u in fp32, the rest in fp64
 //   z    = (logit + gum) / T                                  in fp64, a true division; kept as the fp32 pair (hi, lo) with hi = fl32(z), lo = fl32(z - hi)
@@ -19,10 +20,10 @@
 // (seed, complex, sample, draw, d, position): the batch it sits in and its place there do not matter.
 #include "ddk_internal.h"
 #include "k_philox.h"
+#include "k_ragged.h"
 
 namespace ddk {
 
-constexpr int GUM_T = 256;
 constexpr uint32_t RNG_GUMBEL = 13;      // DDK_RNG_LAYOUT 1, beside RngPurpose
 
 struct GumbelArgs {      // the forward
@@ -43,135 +44,68 @@ struct GumbelBwdArgs {      // the backward: the saved y and grad_out in, grad_l
   float T;
 };
 
-// the graph's nodes on both sides, or n < 0 where a pointer pair is no range of its table (the graph is then left alone)
-struct GumbelGraph { int64_t l0, r0, nl, n; };
-template <class Args>
-__device__ __forceinline__ GumbelGraph gumbel_graph(const Args& a, int g) {
-  const int64_t l0 = a.lig_ptr[g], l1 = a.lig_ptr[g + 1], r0 = a.rec_ptr[g], r1 = a.rec_ptr[g + 1];
-  const bool ok = l0 >= 0 && l0 <= l1 && l1 <= a.n_lig && r0 >= 0 && r0 <= r1 && r1 <= a.n_rec;
-  return GumbelGraph{l0, r0, l1 - l0, ok ? (l1 - l0) + (r1 - r0) : -1};
-}
-// element (position p, column d) of a pair of node tables
-__device__ __forceinline__ int64_t gumbel_at(const GumbelGraph& G, int64_t p, int D, int d, bool& lig) {
-  lig = p < G.nl;
-  return (lig ? G.l0 + p : G.r0 + (p - G.nl)) * D + d;
-}
-
-__device__ __forceinline__ float gumbel_tree_sum(float* red, float v) {
-  const int t = threadIdx.x;
-  __syncthreads();      // (the tile may still be read from the reduction before)
-  red[t] = v;
-  __syncthreads();
-  for (int s = GUM_T / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] = red[t] + red[t + s];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 // The forward of one (graph, latent dimension), the whole workgroup: the one body of gumbel_fwd_kernel and gumbel_pick_kernel.  The logits are read at the rows
 // of ``in``, y and out are written at the rows of ``G`` (the same node counts; the ragged op passes one graph twice, the per-sample op the shared table and
-// sample b's block of the outputs).  ``key``: rng_block's four words for (complex, sample, draw, d).  Returns the position of the one (n > 0 is the caller's).
+// sample b's block of the outputs).  ``key``: rng_block's four words for (complex, sample, draw, d).  Returns the position of the one (n > 0 is the caller's),
+// INT64_MAX where no y compares.
 __device__ __forceinline__ int64_t gumbel_forward_body(const float* logit_l, const float* logit_r, float* y_l, float* y_r, float* out_l, float* out_r,
-                                                       const GumbelGraph& in, const GumbelGraph& G, int D, int d, float T, const uint32_t* key) {
-  __shared__ float red[GUM_T];
-  __shared__ double redd[GUM_T];
-  __shared__ int64_t redi[GUM_T];
-  const int t = threadIdx.x;
-  const int64_t quads = (G.n + 3) >> 2;
+                                                       const RaggedGraph& in, const RaggedGraph& G, int D, int d, float T, const uint32_t* key) {
+  __shared__ float red[RAGGED_T];
+  __shared__ double redd[RAGGED_T];
+  __shared__ int64_t redi[RAGGED_T];
   bool lig;
   // 1. z as (hi, lo) into y's and out's buffers, the thread's maximum of hi + lo
   double m = -INFINITY;
-  for (int64_t q = t; q < quads; q += GUM_T) {
-    const uint32_t ctr[4] = {(uint32_t)q, 0u, 0u, DDK_GUMBEL_TAG};
-    uint32_t w[4];
-    philox4x32_10(ctr, key, w);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int64_t p = 4 * q + i;
-      if (p < G.n) {
-        const int64_t at = gumbel_at(G, p, D, d, lig);
-        const float u = rng_uniform(w[i]);
-        const double gum = -log(-log((double)(u + 1e-20f)) + 1e-20);
-        const double z = ((double)(lig ? logit_l : logit_r)[gumbel_at(in, p, D, d, lig)] + gum) / (double)T;
-        const float hi = (float)z, lo = isinf(hi) ? 0.f : (float)(z - (double)hi);
-        (lig ? y_l : y_r)[at] = hi;
-        (lig ? out_l : out_r)[at] = lo;
-        m = fmax(m, (double)hi + (double)lo);
-      }
+  uint32_t w[4];
+  ragged_for_each(G, [&](int64_t q, int i, int64_t p) {
+    if (i == 0) {      // (one Philox block per quad)
+      const uint32_t ctr[4] = {(uint32_t)q, 0u, 0u, DDK_GUMBEL_TAG};
+      philox4x32_10(ctr, key, w);
     }
-  }
-  __syncthreads();
-  redd[t] = m;
-  __syncthreads();
-  for (int s = GUM_T / 2; s > 0; s >>= 1) {
-    if (t < s) redd[t] = fmax(redd[t], redd[t + s]);
-    __syncthreads();
-  }
-  m = redd[0];
+    const int64_t at = ragged_row(G, p, lig) * D + d;
+    const float u = rng_uniform(w[i]);
+    const double gum = -log(-log((double)(u + 1e-20f)) + 1e-20);
+    const double z = ((double)(lig ? logit_l : logit_r)[ragged_row(in, p, lig) * D + d] + gum) / (double)T;
+    const float hi = (float)z, lo = isinf(hi) ? 0.f : (float)(z - (double)hi);
+    (lig ? y_l : y_r)[at] = hi;
+    (lig ? out_l : out_r)[at] = lo;
+    m = fmax(m, (double)hi + (double)lo);
+  });
+  m = ragged_tree_fmax(redd, m);
   // 2. the exponentials and their sum
   float part = 0.f;
-  for (int64_t q = t; q < quads; q += GUM_T) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int64_t p = 4 * q + i;
-      if (p < G.n) {
-        const int64_t at = gumbel_at(G, p, D, d, lig);
-        float* y = lig ? y_l : y_r;
-        const float e = (float)exp(((double)y[at] + (double)(lig ? out_l : out_r)[at]) - m);
-        y[at] = e;
-        part += e;
-      }
-    }
-  }
-  const float sum = gumbel_tree_sum(red, part);
+  ragged_for_each(G, [&](int64_t, int, int64_t p) {
+    const int64_t at = ragged_row(G, p, lig) * D + d;
+    float* y = lig ? y_l : y_r;
+    const float e = (float)exp(((double)y[at] + (double)(lig ? out_l : out_r)[at]) - m);
+    y[at] = e;
+    part += e;
+  });
+  const float sum = ragged_tree_sum(red, part);
   // 3. y and the lowest position of its maximum
   float best = -INFINITY;
   int64_t where = INT64_MAX;
-  for (int64_t q = t; q < quads; q += GUM_T) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int64_t p = 4 * q + i;
-      if (p < G.n) {
-        const int64_t at = gumbel_at(G, p, D, d, lig);
-        float* y = lig ? y_l : y_r;
-        const float v = y[at] / sum;
-        y[at] = v;
-        if (v > best) { best = v; where = p; }      // (ascending p: the first of equals stays)
-      }
-    }
-  }
-  __syncthreads();
-  red[t] = best; redi[t] = where;
-  __syncthreads();
-  for (int s = GUM_T / 2; s > 0; s >>= 1) {
-    if (t < s) {
-      const float o = red[t + s];
-      const int64_t oi = redi[t + s];
-      if (o > red[t] || (o == red[t] && oi < redi[t])) { red[t] = o; redi[t] = oi; }
-    }
-    __syncthreads();
-  }
-  where = redi[0];
+  ragged_for_each(G, [&](int64_t, int, int64_t p) {
+    const int64_t at = ragged_row(G, p, lig) * D + d;
+    float* y = lig ? y_l : y_r;
+    const float v = y[at] / sum;
+    y[at] = v;
+    if (v > best) { best = v; where = p; }      // (ascending p: the first of equals stays)
+  });
+  ragged_tree_argmax(red, redi, best, where);
   // 4. the straight-through output
-  for (int64_t q = t; q < quads; q += GUM_T) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int64_t p = 4 * q + i;
-      if (p < G.n) {
-        const int64_t at = gumbel_at(G, p, D, d, lig);
-        const float y = (lig ? y_l : y_r)[at];
-        const float hard = p == where ? 1.f : 0.f;
-        (lig ? out_l : out_r)[at] = (hard - y) + y;
-      }
-    }
-  }
+  ragged_for_each(G, [&](int64_t, int, int64_t p) {
+    const int64_t at = ragged_row(G, p, lig) * D + d;
+    const float y = (lig ? y_l : y_r)[at];
+    const float hard = p == where ? 1.f : 0.f;
+    (lig ? out_l : out_r)[at] = (hard - y) + y;
+  });
   return where;
 }
 
-__global__ __launch_bounds__(GUM_T) void gumbel_fwd_kernel(GumbelArgs a) {
+__global__ __launch_bounds__(RAGGED_T) void gumbel_fwd_kernel(GumbelArgs a) {
   const int g = blockIdx.x, d = blockIdx.y;
-  const GumbelGraph G = gumbel_graph(a, g);
+  const RaggedGraph G = ragged_graph(a.lig_ptr, a.rec_ptr, a.n_lig, a.n_rec, g);
   if (G.n <= 0) return;
   uint32_t key[4];
   rng_block(rng_stream(((uint64_t)a.seed_hi << 32) | a.seed_lo, a.stream_id[g]), a.sample, RNG_GUMBEL, a.draw, (uint32_t)d, key);
@@ -192,55 +126,42 @@ struct GumbelPickArgs {
   uint32_t seed_lo, seed_hi, sample, draw;
 };
 
-__global__ __launch_bounds__(GUM_T) void gumbel_pick_kernel(GumbelPickArgs a) {
+__global__ __launch_bounds__(RAGGED_T) void gumbel_pick_kernel(GumbelPickArgs a) {
   const int b = blockIdx.x, d = blockIdx.y;
-  const GumbelGraph in{0, 0, a.n_lig, a.n_lig + a.n_rec}, to{(int64_t)b * a.n_lig, (int64_t)b * a.n_rec, a.n_lig, a.n_lig + a.n_rec};
+  const RaggedGraph in{0, 0, a.n_lig, a.n_lig + a.n_rec}, to{(int64_t)b * a.n_lig, (int64_t)b * a.n_rec, a.n_lig, a.n_lig + a.n_rec};
   uint32_t key[4];
   rng_block(rng_stream(((uint64_t)a.seed_hi << 32) | a.seed_lo, a.stream_id), a.sample + (uint32_t)b, RNG_GUMBEL, a.draw, (uint32_t)d, key);
   const int64_t where = gumbel_forward_body(a.logit_l, a.logit_r, a.y_l, a.y_r, a.out_l, a.out_r, in, to, a.D, d, a.T, key);
   if (a.choices && threadIdx.x == 0) a.choices[(int64_t)b * a.D + d] = (int32_t)where;
 }
 
-__global__ __launch_bounds__(GUM_T) void gumbel_bwd_kernel(GumbelBwdArgs a) {
-  __shared__ float red[GUM_T];
-  const int g = blockIdx.x, d = blockIdx.y, t = threadIdx.x;
-  const GumbelGraph G = gumbel_graph(a, g);
+__global__ __launch_bounds__(RAGGED_T) void gumbel_bwd_kernel(GumbelBwdArgs a) {
+  __shared__ float red[RAGGED_T];
+  const int g = blockIdx.x, d = blockIdx.y;
+  const RaggedGraph G = ragged_graph(a.lig_ptr, a.rec_ptr, a.n_lig, a.n_rec, g);
   if (G.n <= 0) return;
-  const int64_t quads = (G.n + 3) >> 2;
   bool lig;
   float part = 0.f;
-  for (int64_t q = t; q < quads; q += GUM_T) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int64_t p = 4 * q + i;
-      if (p < G.n) {
-        const int64_t at = gumbel_at(G, p, a.D, d, lig);
-        part += (lig ? a.gout_l : a.gout_r)[at] * (lig ? a.y_l : a.y_r)[at];
-      }
-    }
-  }
-  const float dot = gumbel_tree_sum(red, part);
-  for (int64_t q = t; q < quads; q += GUM_T) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int64_t p = 4 * q + i;
-      if (p < G.n) {
-        const int64_t at = gumbel_at(G, p, a.D, d, lig);
-        const float y = (lig ? a.y_l : a.y_r)[at], go = (lig ? a.gout_l : a.gout_r)[at];
-        (lig ? a.grad_l : a.grad_r)[at] = y * (go - dot) / a.T;
-      }
-    }
-  }
+  ragged_for_each(G, [&](int64_t, int, int64_t p) {
+    const int64_t at = ragged_row(G, p, lig) * a.D + d;
+    part += (lig ? a.gout_l : a.gout_r)[at] * (lig ? a.y_l : a.y_r)[at];
+  });
+  const float dot = ragged_tree_sum(red, part);
+  ragged_for_each(G, [&](int64_t, int, int64_t p) {
+    const int64_t at = ragged_row(G, p, lig) * a.D + d;
+    const float y = (lig ? a.y_l : a.y_r)[at], go = (lig ? a.gout_l : a.gout_r)[at];
+    (lig ? a.grad_l : a.grad_r)[at] = y * (go - dot) / a.T;
+  });
 }
 
-hipError_t launch_gumbel_forward(const GumbelOperands& o, const float* logit_l, const float* logit_r, uint64_t seed, const uint64_t* stream_id, uint32_t sample,
+hipError_t launch_gumbel_forward(const RaggedTables& o, float T, const float* logit_l, const float* logit_r, uint64_t seed, const uint64_t* stream_id, uint32_t sample,
                                  uint32_t draw, float* y_l, float* y_r, float* out_l, float* out_r, hipStream_t s) {
   GumbelArgs a{};
   a.logit_l = logit_l; a.logit_r = logit_r; a.lig_ptr = o.lig_ptr; a.rec_ptr = o.rec_ptr; a.stream_id = stream_id;
   a.y_l = y_l; a.y_r = y_r; a.out_l = out_l; a.out_r = out_r;
-  a.n_lig = o.n_lig; a.n_rec = o.n_rec; a.D = o.D; a.T = o.T;
+  a.n_lig = o.n_lig; a.n_rec = o.n_rec; a.D = o.D; a.T = T;
   a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.sample = sample; a.draw = draw;
-  hipLaunchKernelGGL(gumbel_fwd_kernel, dim3((unsigned)o.G, (unsigned)o.D), dim3(GUM_T), 0, s, a);
+  hipLaunchKernelGGL(gumbel_fwd_kernel, dim3((unsigned)o.G, (unsigned)o.D), dim3(RAGGED_T), 0, s, a);
   return hipGetLastError();
 }
 
@@ -250,14 +171,14 @@ hipError_t launch_gumbel_pick(int B, int D, const float* logit_l, int64_t n_lig,
   a.logit_l = logit_l; a.logit_r = logit_r; a.y_l = y; a.y_r = y + (int64_t)B * n_lig * D; a.out_l = out_l; a.out_r = out_r; a.choices = choices;
   a.n_lig = n_lig; a.n_rec = n_rec; a.stream_id = stream_id; a.D = D; a.T = T;
   a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.sample = sample0; a.draw = draw;
-  hipLaunchKernelGGL(gumbel_pick_kernel, dim3((unsigned)B, (unsigned)D), dim3(GUM_T), 0, s, a);
+  hipLaunchKernelGGL(gumbel_pick_kernel, dim3((unsigned)B, (unsigned)D), dim3(RAGGED_T), 0, s, a);
   return hipGetLastError();
 }
 
-hipError_t launch_gumbel_backward(const GumbelOperands& o, const float* y_l, const float* y_r, const float* gout_l, const float* gout_r, float* grad_l,
+hipError_t launch_gumbel_backward(const RaggedTables& o, float T, const float* y_l, const float* y_r, const float* gout_l, const float* gout_r, float* grad_l,
                                   float* grad_r, hipStream_t s) {
-  const GumbelBwdArgs a{y_l, y_r, gout_l, gout_r, o.lig_ptr, o.rec_ptr, grad_l, grad_r, o.n_lig, o.n_rec, o.D, o.T};
-  hipLaunchKernelGGL(gumbel_bwd_kernel, dim3((unsigned)o.G, (unsigned)o.D), dim3(GUM_T), 0, s, a);
+  const GumbelBwdArgs a{y_l, y_r, gout_l, gout_r, o.lig_ptr, o.rec_ptr, grad_l, grad_r, o.n_lig, o.n_rec, o.D, T};
+  hipLaunchKernelGGL(gumbel_bwd_kernel, dim3((unsigned)o.G, (unsigned)o.D), dim3(RAGGED_T), 0, s, a);
   return hipGetLastError();
 }
 

@@ -218,6 +218,35 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def _ragged_tables(who, table_l, table_r, *ptrs):
+    """(G, D) of an op over a graph's ligand nodes followed by its receptor nodes, after the checks the host can make: two tables [N_lig, D], [N_rec, D] with D in
+    1..4 on one device; ``ptrs`` = (lig_ptr, rec_ptr), contiguous int64 [G + 1] there, 1..65536 graphs.  An op on one graph passes none (G is None)."""
+    dev = table_l.device
+    if table_l.dim() != 2 or table_r.dim() != 2 or table_l.shape[1] != table_r.shape[1] or not 1 <= table_l.shape[1] <= 4 or table_r.device != dev:
+        raise RuntimeError(f'ddk: {who} takes two tables [N_lig, D] and [N_rec, D] with D in 1..4 on one device; got {tuple(table_l.shape)} and {tuple(table_r.shape)}')
+    if not ptrs:
+        return None, table_l.shape[1]
+    for name, t in zip(('lig_ptr', 'rec_ptr'), ptrs):
+        if not torch.is_tensor(t) or t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous() or t.device != dev or t.shape != ptrs[0].shape:
+            raise RuntimeError(f'ddk: {who} takes {name} as a contiguous int64 vector [G + 1] on the device of the tables')
+    G = ptrs[0].shape[0] - 1
+    if not 1 <= G <= 65536:
+        raise RuntimeError(f'ddk: {who} takes 1..65536 graphs; got {G}')
+    return G, table_l.shape[1]
+
+
+def _temperature(who, temperature):
+    if not 0 < float(temperature) < float('inf'):
+        raise RuntimeError(f'ddk: {who} takes a positive finite temperature; got {temperature}')
+    return float(temperature)
+
+
+def _need_int31(who, **values):
+    for k, v in values.items():
+        if not 0 <= int(v) < 1 << 31:
+            raise RuntimeError(f'ddk: {who}: {k} = {v} must be a non-negative int32')
+
+
 def _need(need, who, four=False):
     """``need`` of a ``*_backward`` as a tuple of bools; a call that asks for no gradient (``four``: or not for four flags) is refused"""
     need = tuple(bool(n) for n in need)
@@ -850,19 +879,7 @@ class Context:
     @staticmethod
     def _gumbel_operands(a_l, a_r, lig_ptr, rec_ptr, temperature, who):
         a_l, a_r = (_need_cuda(x).contiguous().float() for x in (a_l, a_r))
-        dev = a_l.device
-        if a_l.dim() != 2 or a_r.dim() != 2 or a_l.shape[1] != a_r.shape[1] or not 1 <= a_l.shape[1] <= 4 or a_r.device != dev:
-            raise RuntimeError(f'ddk: {who} takes two tables [N_lig, D] and [N_rec, D] with D in 1..4 on one device; got {tuple(a_l.shape)} and {tuple(a_r.shape)}')
-        for name, t in (('lig_ptr', lig_ptr), ('rec_ptr', rec_ptr)):
-            if not torch.is_tensor(t) or t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous() or t.device != dev or t.shape != lig_ptr.shape:
-                raise RuntimeError(f'ddk: {who} takes {name} as a contiguous int64 vector [G + 1] on the device of the tables')
-        G = lig_ptr.shape[0] - 1
-        if not 1 <= G <= 65536:
-            raise RuntimeError(f'ddk: {who} takes 1..65536 graphs; got {G}')
-        T = float(temperature)
-        if not (T > 0 and T < float('inf')):
-            raise RuntimeError(f'ddk: {who} takes a positive finite temperature; got {temperature}')
-        return a_l, a_r, G, a_l.shape[1], T
+        return (a_l, a_r, *_ragged_tables(who, a_l, a_r, lig_ptr, rec_ptr), _temperature(who, temperature))
 
     def gumbel_softmax(self, logit_l, logit_r, lig_ptr, rec_ptr, temperature, seed, stream_ids, sample=0, draw=0):
         """The straight-through Gumbel softmax of every graph and latent dimension over the graph's ligand nodes followed by its receptor nodes
@@ -879,9 +896,7 @@ class Context:
             st = h2d_async(torch.from_numpy(np.ascontiguousarray([_u64(v, 'rng_stream') for v in stream_ids], dtype=np.uint64).view(np.int64)), dev)
             if st.shape != (G,):
                 raise RuntimeError(f'ddk: gumbel_softmax takes {G} stream ids; got {st.shape[0]}')
-        for k, v in dict(draw=draw, sample=sample).items():
-            if not 0 <= int(v) < 1 << 31:
-                raise RuntimeError(f'ddk: gumbel_softmax: {k} = {v} must be a non-negative int32')
+        _need_int31('gumbel_softmax', draw=draw, sample=sample)
         y_l, y_r, out_l, out_r = torch.empty_like(logit_l), torch.empty_like(logit_r), torch.empty_like(logit_l), torch.empty_like(logit_r)
         self._check(self.L.ddk_gumbel_softmax_batch(self.h, G, D, _ptr(logit_l), logit_l.shape[0], _ptr(logit_r), logit_r.shape[0], _ptr(lig_ptr), _ptr(rec_ptr), T,
                                                     C.c_uint64(_u64(seed, 'seed')), _ptr(st), int(sample), int(draw), _ptr(y_l), _ptr(y_r), _ptr(out_l),
@@ -895,17 +910,12 @@ class Context:
         the one, ligand nodes first, then n_lig + the receptor index."""
         logit_l, logit_r = (_need_cuda(x).contiguous().float() for x in (logit_l, logit_r))
         dev = logit_l.device
-        if logit_l.dim() != 2 or logit_r.dim() != 2 or logit_l.shape[1] != logit_r.shape[1] or not 1 <= logit_l.shape[1] <= 4 or logit_r.device != dev:
-            raise RuntimeError('ddk: gumbel_pick_samples takes two tables [n_lig, D] and [n_rec, D] with D in 1..4 on one device; got '
-                               f'{tuple(logit_l.shape)} and {tuple(logit_r.shape)}')
-        B, D, T = int(B), logit_l.shape[1], float(temperature)
+        _, D = _ragged_tables('gumbel_pick_samples', logit_l, logit_r)
+        B = int(B)
         if not 1 <= B <= 65536:
             raise RuntimeError(f'ddk: gumbel_pick_samples takes 1..65536 samples; got {B}')
-        if not (T > 0 and T < float('inf')):
-            raise RuntimeError(f'ddk: gumbel_pick_samples takes a positive finite temperature; got {temperature}')
-        for k, v in dict(draw=draw, sample0=sample0).items():
-            if not 0 <= int(v) < 1 << 31:
-                raise RuntimeError(f'ddk: gumbel_pick_samples: {k} = {v} must be a non-negative int32')
+        T = _temperature('gumbel_pick_samples', temperature)
+        _need_int31('gumbel_pick_samples', draw=draw, sample0=sample0)
         n_l, n_r = logit_l.shape[0], logit_r.shape[0]
         lat_l, lat_r = torch.empty((B * n_l, D), device=dev), torch.empty((B * n_r, D), device=dev)
         choices = torch.empty((B, D), dtype=torch.int32, device=dev)
@@ -962,23 +972,15 @@ class Context:
         for name, t, rows in (('logit_l', logit_l, teacher_l.shape[0]), ('logit_r', logit_r, teacher_r.shape[0])):
             if not (t.dim() == 1 or (t.dim() == 2 and t.shape[1] == 1)) or t.shape[0] != rows:
                 raise RuntimeError(f'ddk: {who} takes {name} as one logit per row of its teacher table ([{rows}] or [{rows}, 1]); got {tuple(t.shape)}')
-        if teacher_l.dim() != 2 or teacher_r.dim() != 2 or teacher_l.shape[1] != teacher_r.shape[1] or not 1 <= teacher_l.shape[1] <= 4:
-            raise RuntimeError(f'ddk: {who} takes the teacher tables [N_lig, D] and [N_rec, D] with D in 1..4; got {tuple(teacher_l.shape)} and '
-                               f'{tuple(teacher_r.shape)}')
-        for name, t in (('lig_ptr', lig_ptr), ('rec_ptr', rec_ptr)):
-            if not torch.is_tensor(t) or t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous() or t.shape != lig_ptr.shape:
-                raise RuntimeError(f'ddk: {who} takes {name} as a contiguous int64 vector [G + 1]')
-        G = lig_ptr.shape[0] - 1
-        if not 1 <= G <= 65536:
-            raise RuntimeError(f'ddk: {who} takes 1..65536 graphs; got {G}')
+        G, D = _ragged_tables(who, teacher_l, teacher_r, lig_ptr, rec_ptr)      # (the teacher's)
         if not torch.is_tensor(column) or column.dtype != torch.int32 or column.shape != (G,) or not column.is_contiguous():
             raise RuntimeError(f'ddk: {who} takes column as a contiguous int32 vector [G] = [{G}]')
-        for name, t in (('logit_r', logit_r), ('teacher_l', teacher_l), ('teacher_r', teacher_r), ('lig_ptr', lig_ptr), ('rec_ptr', rec_ptr), ('column', column)):
+        for name, t in (('logit_r', logit_r), ('teacher_l', teacher_l), ('column', column)):      # (the other three are on teacher_l's)
             if t.device != dev:
                 raise RuntimeError(f'ddk: {who} takes every operand on one device; {name} is on {t.device}, logit_l on {dev}')
         if soft not in (0, 1, False, True):
             raise RuntimeError(f'ddk: {who} takes soft as 0 or 1; got {soft!r}')
-        return G, teacher_l.shape[1]
+        return G, D
 
     def node_cross_entropy(self, logit_l, logit_r, lig_ptr, rec_ptr, teacher_l, teacher_r, column, soft=False, out=None):
         """The cross-entropy of every graph over its ligand nodes followed by its receptor nodes (ddk_node_cross_entropy_batch): (loss [G] float32, pick [G],

@@ -15,7 +15,7 @@ F32 = np.float32
 FLT_MAX = float(np.finfo(np.float32).max)
 
 # ------------------------------------------------------------------------------------------------------------------------------------
-# the Gumbel softmax: one workgroup of GUM_T threads per (graph, d); thread t owns the quads t, t + GUM_T, ... of four positions each
+# the Gumbel softmax: one workgroup of RAGGED_T threads (csrc/k_ragged.h; GUM_T here) per (graph, d); thread t owns the quads t, t + RAGGED_T, ... of four positions each
 # ------------------------------------------------------------------------------------------------------------------------------------
 GUM_T, QUAD = 256, 4
 GUMBEL_SEED, GUMBEL_SAMPLE, GUMBEL_DRAW = 0x1234567890ABCDEF, 3, 17

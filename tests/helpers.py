@@ -24,6 +24,13 @@ def batch_of(c, B, pos=None):
     return b
 
 
+def _bits(a):
+    """the int32 bit patterns of float32 values: of a torch tensor as a tensor (compare with torch.equal), of anything else as a numpy array"""
+    if torch.is_tensor(a):
+        return a.contiguous().view(torch.int32)
+    return np.ascontiguousarray(a, np.float32).view(np.int32)
+
+
 def rel_err(a, b):
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-30))

@@ -9,8 +9,7 @@ import pytest
 import torch
 
 import latent_embedding_ref as lref
-from helpers import rel_err
-from test_gpu_radial_conv import _bits
+from helpers import _bits, rel_err
 from test_gpu_round3 import _record_drift      # the suite's record of measured parity figures
 
 pytestmark = pytest.mark.gpu

@@ -9,12 +9,9 @@ import pytest
 import torch
 
 import oracle_latents_ref as olr
+from helpers import _bits
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
 
 
 @pytest.fixture(scope='module')

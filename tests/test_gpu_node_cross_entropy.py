@@ -15,7 +15,7 @@ import pytest
 import torch
 
 import node_cross_entropy_ref as nref
-from helpers import elem_err
+from helpers import _bits, elem_err
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -41,10 +41,6 @@ def ctx(dev):
 def _record(key, value, **extra):
     from test_gpu_round3 import _record_drift
     _record_drift(f'node_ce.{key}', value, **extra)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, F32).view(np.int32)
 
 
 _cases = {}
