@@ -7,6 +7,11 @@
 //   pre[e, c]   = fmaf(W1[c, 71], in[71], ... fmaf(W1[c, 0], in[0], b1[c]))                     k ascending, the bias first
 //   gin[e, k]   = fmaf(gpre[71], W1[71, k], ... fmaf(gpre[0], W1[0, k], 0))                     c ascending
 //   grad_W1[c, k] = the slices' partial sums added in slice order, a partial sum being fmaf(gpre[e, c], in[e, k], .) over the slice's edges ascending
+//   h[e, c]     = pre < 0 ? 0 : pre at p == 0; keep(e, c) ? (pre < 0 ? 0 : pre) * s : 0 otherwise, s = 1.0f / (1.0f - p) formed once on the host in fp32
+//   gpre[e, c]  = grad_h[e, c] * (h[e, c] != 0 ? s : 0): one product
+//   grad_b1[c]  = as grad_W1 with a separate add, acc += gpre[e, c], in place of the fmaf.  Every partial sum and every sum over the slices starts from +0
+//                 (sum = 0; sum += image[s]); a group's slices are rtp_slice_len(E) edges each, counted from the group's first edge
+//   grad_xs[n]  = (the node's src rows added in ascending edge id) + (its dst rows likewise): two segmented sums of k_reduce.hip, then one add in that order
 //
 // LAYOUT.  One LANE owns one EDGE, and a step walks FOUR COLUMNS of W1[g] (all 72 rows of them: 72 loads of 16 bytes).  Forward: the lane's 72
 // accumulators sit in registers and start from the bias, its gathered row waits in LDS and gives the step's four inputs.  Backward: the lane's gpre row
