@@ -502,24 +502,68 @@ int ddk_hconv_backward(ddk_ctx* ctx, int32_t head, const float* x_nodes, int64_t
 
 int64_t ddk_hconv_workspace(int32_t head, int64_t E, int64_t n_in, int64_t n_out, int32_t backward) { return hconv_workspace(head, E, n_in, n_out, backward); }
 
-// the checks the two edge-embedding entries share: a context that can launch, the counts and the smearing, and with edges the operands both read
-static int eemb_check(ddk_ctx* ctx, const char* who, const EembOperands& o, int64_t n_a, int64_t n_b, int32_t F, int64_t n_sig, int32_t n_gauss, int64_t E) {
+// The four edge-embedding entries are two bodies, eemb_forward and eemb_backward: l == nullptr is the plain op, and `who` is the calling entry, whose name
+// every message carries.  The checks they share: a context that can launch, the counts and the smearing, and with edges the operands both directions read
+static int eemb_check(ddk_ctx* ctx, const char* who, const EembOperands& o, const EembLatent* l, int64_t n_a, int64_t n_b, int64_t n_sig, int32_t n_gauss, int64_t E) {
   int rc = check_launchable(ctx, 0);
   if (rc) return rc;
   const std::string w(who);
   const int64_t lim = (int64_t)1 << 31;
-  if (F != 0 && F != 4) return fail(ctx, DDK_ERR_INVALID, w + ": F must be 0 or 4");
+  if (o.F != 0 && o.F != 4) return fail(ctx, DDK_ERR_INVALID, w + ": F must be 0 or 4");
   if (n_gauss != 32) return fail(ctx, DDK_ERR_INVALID, w + ": n_gauss must be 32");
   if (E < 0 || E >= lim) return fail(ctx, DDK_ERR_INVALID, w + ": edge count out of range");
   if (n_a < 0 || n_a >= lim || n_b < 0 || n_b >= lim || n_sig < 0 || n_sig >= lim) return fail(ctx, DDK_ERR_INVALID, w + ": node or graph count out of range");
   if (!(o.p >= 0.f && o.p < 1.f)) return fail(ctx, DDK_ERR_INVALID, w + ": the dropout rate p must be in [0, 1)");
   if (!(o.stop > o.start)) return fail(ctx, DDK_ERR_INVALID, w + ": the smearing needs start < stop");
+  if (E > 0) {
+    if (n_a == 0 || n_b == 0 || n_sig == 0) return fail(ctx, DDK_ERR_INVALID, w + ": edges without nodes or graphs");
+    if (!o.pos_a || !o.pos_b || !o.idx_a || !o.idx_b || !o.sig || !o.sig_index) return fail(ctx, DDK_ERR_INVALID, w + ": null operand (pos, idx, sig, sig_index)");
+    if ((o.F == 4) != (o.feat != nullptr)) return fail(ctx, DDK_ERR_INVALID, w + ": feat must be given with F == 4 and null with F == 0");
+    if (!o.w1 || !o.b1 || !o.w2) return fail(ctx, DDK_ERR_INVALID, w + ": null parameter (w1, b1, w2)");
+    if (((uintptr_t)o.feat | (uintptr_t)o.sig) & 15) return fail(ctx, DDK_ERR_INVALID, w + ": feat and sig must be 16-byte aligned");
+  }
+  if (!l) return DDK_OK;      // what the two latent entries check on top
+  if (l->NL < 1 || l->NL > 4) return fail(ctx, DDK_ERR_INVALID, w + ": L (the latent columns per node) must be in 1..4");
   if (E == 0) return DDK_OK;
-  if (n_a == 0 || n_b == 0 || n_sig == 0) return fail(ctx, DDK_ERR_INVALID, w + ": edges without nodes or graphs");
-  if (!o.pos_a || !o.pos_b || !o.idx_a || !o.idx_b || !o.sig || !o.sig_index) return fail(ctx, DDK_ERR_INVALID, w + ": null operand (pos, idx, sig, sig_index)");
-  if ((F == 4) != (o.feat != nullptr)) return fail(ctx, DDK_ERR_INVALID, w + ": feat must be given with F == 4 and null with F == 0");
-  if (!o.w1 || !o.b1 || !o.w2) return fail(ctx, DDK_ERR_INVALID, w + ": null parameter (w1, b1, w2)");
-  if (((uintptr_t)o.feat | (uintptr_t)o.sig) & 15) return fail(ctx, DDK_ERR_INVALID, w + ": feat and sig must be 16-byte aligned");
+  if (!l->zero_latent && (!l->lat_a || !l->lat_b)) return fail(ctx, DDK_ERR_INVALID, w + ": null latent table (lat_a, lat_b; they may be null only with zero_latent)");
+  if (!l->zero_latent && (((uintptr_t)l->lat_a | (uintptr_t)l->lat_b) & 15)) return fail(ctx, DDK_ERR_INVALID, w + ": lat_a and lat_b must be 16-byte aligned");
+  if (l->unc_a && !l->uemb) return fail(ctx, DDK_ERR_INVALID, w + ": unc_a without uemb");
+  return DDK_OK;
+}
+
+static int eemb_forward(ddk_ctx* ctx, const char* who, const EembOperands& o, const EembLatent* l, int64_t n_a, int64_t n_b, int64_t n_sig, int32_t n_gauss,
+                        int64_t E, float* emb, float* sh, void* stream) {
+  int rc = eemb_check(ctx, who, o, l, n_a, n_b, n_sig, n_gauss, E);
+  if (rc) return rc;
+  if (E == 0) return DDK_OK;
+  const std::string w(who);
+  if (!o.b2 || !emb || !sh) return fail(ctx, DDK_ERR_INVALID, w + ": null operand (b2, emb, sh)");
+  if (((uintptr_t)emb | (uintptr_t)sh) & 15) return fail(ctx, DDK_ERR_INVALID, w + ": emb and sh must be 16-byte aligned");
+  hipError_t e = launch_eemb_forward(o, l, E, emb, sh, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, (w.substr(4) + " launch").c_str());      // (the entry's name without "ddk_")
+  return DDK_OK;
+}
+
+// the plain entry passes null for grad_uemb, grad_lat_a, grad_lat_b and the node-sorted lists of gr
+static int eemb_backward(ddk_ctx* ctx, const char* who, const EembOperands& o, const EembLatent* l, const EembLatentGraph& gr, int64_t n_sig, int32_t n_gauss,
+                         const float* grad_emb, int64_t E, float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2, float* grad_uemb, float* grad_lat_a,
+                         float* grad_lat_b, void* workspace, void* stream) {
+  int rc = eemb_check(ctx, who, o, l, gr.n_a, gr.n_b, n_sig, n_gauss, E);
+  if (rc) return rc;
+  const std::string w(who);
+  if (!grad_w1 && !grad_b1 && !grad_w2 && !grad_b2 && !grad_uemb && !grad_lat_a && !grad_lat_b)
+    return fail(ctx, DDK_ERR_INVALID, w + (l ? ": no gradient requested (all seven outputs are null)"
+                                             : ": no gradient requested (grad_w1, grad_b1, grad_w2 and grad_b2 are all null)"));
+  if (E > 0) {
+    if (!grad_emb) return fail(ctx, DDK_ERR_INVALID, w + ": null grad_emb");
+    if (!workspace) return fail(ctx, DDK_ERR_INVALID, w + ": null workspace (" + (l ? "ddk_eemb_latent_workspace" : "ddk_eemb_workspace") + " bytes)");
+    if (((uintptr_t)grad_emb | (uintptr_t)workspace) & 15) return fail(ctx, DDK_ERR_INVALID, w + ": grad_emb and the workspace must be 16-byte aligned");
+    if (l && !l->zero_latent && ((grad_lat_a && (!gr.order_a || !gr.ptr_a)) || (grad_lat_b && (!gr.order_b || !gr.ptr_b))))
+      return fail(ctx, DDK_ERR_INVALID, w + ": null node-sorted edge list (grad_lat_a needs order_a and ptr_a, grad_lat_b order_b and ptr_b)");
+  }
+  hipError_t e = launch_eemb_backward(o, l, gr, grad_emb, E, grad_w1, grad_b1, grad_w2, grad_b2, grad_uemb, grad_lat_a, grad_lat_b, (float*)workspace,
+                                      (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, (w.substr(4) + " launch").c_str());
   return DDK_OK;
 }
 
@@ -528,14 +572,7 @@ int ddk_eemb_forward(ddk_ctx* ctx, const float* pos_a, int64_t n_a, const float*
                      const float* w1, const float* b1, const float* w2, const float* b2, float p, uint64_t seed, int64_t E, float* emb, float* sh,
                      void* stream) {
   const EembOperands o{pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, b2, p, seed, F};
-  int rc = eemb_check(ctx, "ddk_eemb_forward", o, n_a, n_b, F, n_sig, n_gauss, E);
-  if (rc) return rc;
-  if (E == 0) return DDK_OK;
-  if (!b2 || !emb || !sh) return fail(ctx, DDK_ERR_INVALID, "ddk_eemb_forward: null operand (b2, emb, sh)");
-  if (((uintptr_t)emb | (uintptr_t)sh) & 15) return fail(ctx, DDK_ERR_INVALID, "ddk_eemb_forward: emb and sh must be 16-byte aligned");
-  hipError_t e = launch_eemb_forward(o, E, emb, sh, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(ctx, e, "eemb_forward launch");
-  return DDK_OK;
+  return eemb_forward(ctx, "ddk_eemb_forward", o, nullptr, n_a, n_b, n_sig, n_gauss, E, emb, sh, stream);
 }
 
 int ddk_eemb_backward(ddk_ctx* ctx, const float* pos_a, int64_t n_a, const float* pos_b, int64_t n_b, const int32_t* idx_a, const int32_t* idx_b,
@@ -543,32 +580,12 @@ int ddk_eemb_backward(ddk_ctx* ctx, const float* pos_a, int64_t n_a, const float
                       const float* w1, const float* b1, const float* w2, const float* b2, float p, uint64_t seed, const float* grad_emb, int64_t E,
                       float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2, void* workspace, void* stream) {
   const EembOperands o{pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, b2, p, seed, F};
-  int rc = eemb_check(ctx, "ddk_eemb_backward", o, n_a, n_b, F, n_sig, n_gauss, E);
-  if (rc) return rc;
-  if (!grad_w1 && !grad_b1 && !grad_w2 && !grad_b2)
-    return fail(ctx, DDK_ERR_INVALID, "ddk_eemb_backward: no gradient requested (grad_w1, grad_b1, grad_w2 and grad_b2 are all null)");
-  if (E > 0) {
-    if (!grad_emb) return fail(ctx, DDK_ERR_INVALID, "ddk_eemb_backward: null grad_emb");
-    if (!workspace) return fail(ctx, DDK_ERR_INVALID, "ddk_eemb_backward: null workspace (ddk_eemb_workspace bytes)");
-    if (((uintptr_t)grad_emb | (uintptr_t)workspace) & 15) return fail(ctx, DDK_ERR_INVALID, "ddk_eemb_backward: grad_emb and the workspace must be 16-byte aligned");
-  }
-  hipError_t e = launch_eemb_backward(o, grad_emb, E, grad_w1, grad_b1, grad_w2, grad_b2, (float*)workspace, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(ctx, e, "eemb_backward launch");
-  return DDK_OK;
+  const EembLatentGraph gr{n_a, n_b, nullptr, nullptr, nullptr, nullptr};
+  return eemb_backward(ctx, "ddk_eemb_backward", o, nullptr, gr, n_sig, n_gauss, grad_emb, E, grad_w1, grad_b1, grad_w2, grad_b2, nullptr, nullptr, nullptr,
+                       workspace, stream);
 }
 
-int64_t ddk_eemb_workspace(int64_t E, int32_t K) { return eemb_workspace(E, K); }
-
-// what the two latent entries check on top of eemb_check
-static int eemb_latent_check(ddk_ctx* ctx, const char* who, const EembLatent& l, int64_t E) {
-  const std::string w(who);
-  if (l.NL < 1 || l.NL > 4) return fail(ctx, DDK_ERR_INVALID, w + ": L (the latent columns per node) must be in 1..4");
-  if (E == 0) return DDK_OK;
-  if (!l.zero_latent && (!l.lat_a || !l.lat_b)) return fail(ctx, DDK_ERR_INVALID, w + ": null latent table (lat_a, lat_b; they may be null only with zero_latent)");
-  if (!l.zero_latent && (((uintptr_t)l.lat_a | (uintptr_t)l.lat_b) & 15)) return fail(ctx, DDK_ERR_INVALID, w + ": lat_a and lat_b must be 16-byte aligned");
-  if (l.unc_a && !l.uemb) return fail(ctx, DDK_ERR_INVALID, w + ": unc_a without uemb");
-  return DDK_OK;
-}
+int64_t ddk_eemb_workspace(int64_t E, int32_t K) { return eemb_workspace(E, K, 0); }
 
 int ddk_eemb_latent_forward(ddk_ctx* ctx, const float* pos_a, int64_t n_a, const float* pos_b, int64_t n_b, const int32_t* idx_a, const int32_t* idx_b,
                             const float* feat, int32_t F, const float* sig, int64_t n_sig, const int32_t* sig_index, float start, float stop, int32_t n_gauss,
@@ -576,15 +593,7 @@ int ddk_eemb_latent_forward(ddk_ctx* ctx, const float* pos_a, int64_t n_a, const
                             int32_t L, int32_t zero_latent, const float* unc_a, const float* uemb, int64_t E, float* emb, float* sh, void* stream) {
   const EembOperands o{pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, b2, p, seed, F};
   const EembLatent l{lat_a, lat_b, unc_a, uemb, L, zero_latent != 0};
-  int rc = eemb_check(ctx, "ddk_eemb_latent_forward", o, n_a, n_b, F, n_sig, n_gauss, E);
-  if (!rc) rc = eemb_latent_check(ctx, "ddk_eemb_latent_forward", l, E);
-  if (rc) return rc;
-  if (E == 0) return DDK_OK;
-  if (!b2 || !emb || !sh) return fail(ctx, DDK_ERR_INVALID, "ddk_eemb_latent_forward: null operand (b2, emb, sh)");
-  if (((uintptr_t)emb | (uintptr_t)sh) & 15) return fail(ctx, DDK_ERR_INVALID, "ddk_eemb_latent_forward: emb and sh must be 16-byte aligned");
-  hipError_t e = launch_eemb_latent_forward(o, l, E, emb, sh, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(ctx, e, "eemb_latent_forward launch");
-  return DDK_OK;
+  return eemb_forward(ctx, "ddk_eemb_latent_forward", o, &l, n_a, n_b, n_sig, n_gauss, E, emb, sh, stream);
 }
 
 int ddk_eemb_latent_backward(ddk_ctx* ctx, const float* pos_a, int64_t n_a, const float* pos_b, int64_t n_b, const int32_t* idx_a, const int32_t* idx_b,
@@ -595,27 +604,13 @@ int ddk_eemb_latent_backward(ddk_ctx* ctx, const float* pos_a, int64_t n_a, cons
                              float* grad_b2, float* grad_uemb, float* grad_lat_a, float* grad_lat_b, void* workspace, void* stream) {
   const EembOperands o{pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, b2, p, seed, F};
   const EembLatent l{lat_a, lat_b, unc_a, uemb, L, zero_latent != 0};
-  int rc = eemb_check(ctx, "ddk_eemb_latent_backward", o, n_a, n_b, F, n_sig, n_gauss, E);
-  if (!rc) rc = eemb_latent_check(ctx, "ddk_eemb_latent_backward", l, E);
-  if (rc) return rc;
-  if (!grad_w1 && !grad_b1 && !grad_w2 && !grad_b2 && !grad_uemb && !grad_lat_a && !grad_lat_b)
-    return fail(ctx, DDK_ERR_INVALID, "ddk_eemb_latent_backward: no gradient requested (all seven outputs are null)");
-  if (E > 0) {
-    if (!grad_emb) return fail(ctx, DDK_ERR_INVALID, "ddk_eemb_latent_backward: null grad_emb");
-    if (!workspace) return fail(ctx, DDK_ERR_INVALID, "ddk_eemb_latent_backward: null workspace (ddk_eemb_latent_workspace bytes)");
-    if (((uintptr_t)grad_emb | (uintptr_t)workspace) & 15)
-      return fail(ctx, DDK_ERR_INVALID, "ddk_eemb_latent_backward: grad_emb and the workspace must be 16-byte aligned");
-    if (!zero_latent && ((grad_lat_a && (!order_a || !ptr_a)) || (grad_lat_b && (!order_b || !ptr_b))))
-      return fail(ctx, DDK_ERR_INVALID, "ddk_eemb_latent_backward: null node-sorted edge list (grad_lat_a needs order_a and ptr_a, grad_lat_b order_b and ptr_b)");
-  }
   const EembLatentGraph gr{n_a, n_b, order_a, ptr_a, order_b, ptr_b};
-  hipError_t e = launch_eemb_latent_backward(o, l, gr, grad_emb, E, grad_w1, grad_b1, grad_w2, grad_b2, grad_uemb, grad_lat_a, grad_lat_b, (float*)workspace,
-                                             (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(ctx, e, "eemb_latent_backward launch");
-  return DDK_OK;
+  return eemb_backward(ctx, "ddk_eemb_latent_backward", o, &l, gr, n_sig, n_gauss, grad_emb, E, grad_w1, grad_b1, grad_w2, grad_b2, grad_uemb, grad_lat_a,
+                       grad_lat_b, workspace, stream);
 }
 
-int64_t ddk_eemb_latent_workspace(int64_t E, int32_t K, int32_t L) { return eemb_latent_workspace(E, K, L); }
+// (the latent entries refuse L = 0, the plain op's layout, like every L outside 1..4)
+int64_t ddk_eemb_latent_workspace(int64_t E, int32_t K, int32_t L) { return L < 1 ? -1 : eemb_workspace(E, K, L); }
 
 // The checks every entry over a graph's ligand nodes followed by its receptor nodes shares (RaggedTables).  ``samples``: ddk_gumbel_pick_samples, whose count is
 // B samples of one graph, which has no pointer tables and whose rows b n + p must fit 31 bits

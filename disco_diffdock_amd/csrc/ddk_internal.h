@@ -426,8 +426,9 @@ hipError_t launch_hconv_backward(int head, const RconvGraph& gr, const float* x_
                                  const float* grad_out_nodes, int64_t E, float* grad_x_nodes, float* grad_h, float* grad_w2, float* grad_b2, float* workspace,
                                  hipStream_t s);
 int64_t hconv_workspace(int32_t head, int64_t E, int64_t n_in, int64_t n_out, int32_t backward);
-// k_eemb.hip: one edge group's embedding in front of the conv stack, emb = W2 dropout(relu(W1 [feat | sig[graph] | smearing(|vec|)] + b1)) + b2 and the edge's
-// first-order spherical harmonics, and its vector-Jacobian product for the four parameter tensors (include/ddk.h: ddk_eemb_forward / ddk_eemb_backward).
+// k_eemb.hip: one edge group's embedding in front of the conv stack, emb = W2 dropout(relu(W1 [feat | sig[graph] | smearing(|vec|) | latent] + b1)) + b2 and the
+// edge's first-order spherical harmonics, and its vector-Jacobian product (include/ddk.h: ddk_eemb_* and ddk_eemb_latent_*).  One launcher per direction:
+// l == nullptr is the plain op (no latent columns, no unconditional term, gradients for the four parameter tensors alone), which is the latent op with NL = 0.
 // What both directions read: trusted index tables, feat null for F = 0; a null output of the backward is not computed
 struct EembOperands {
   const float* pos_a; const float* pos_b; const int32_t* idx_a; const int32_t* idx_b; const float* feat; const float* sig; const int32_t* sig_index;
@@ -436,19 +437,15 @@ struct EembOperands {
   float p; uint64_t seed;
   int F;      // bond-feature columns: 0 (feat null) or 4
 };
-hipError_t launch_eemb_forward(const EembOperands& o, int64_t E, float* emb, float* sh, hipStream_t s);
-hipError_t launch_eemb_backward(const EembOperands& o, const float* grad_emb, int64_t E, float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2,
-                                float* workspace, hipStream_t s);
-int64_t eemb_workspace(int64_t E, int32_t K);
-// the latent variant (include/ddk.h: ddk_eemb_latent_*): node tables lat_a [n_a, NL] / lat_b [n_b, NL] (not read with zero_latent), unc_a [n_a] and uemb [24]
-// (unc_a null: no unconditional term); the node-sorted lists of idx_a and idx_b that the latent's gradient is summed along (trusted, read only for grad_lat_*)
+// the latent part: node tables lat_a [n_a, NL] / lat_b [n_b, NL] (not read with zero_latent), unc_a [n_a] and uemb [24] (unc_a null: no unconditional term);
+// the node counts and the node-sorted lists of idx_a and idx_b that the latent's gradient is summed along (trusted, read only for grad_lat_*)
 struct EembLatent { const float* lat_a; const float* lat_b; const float* unc_a; const float* uemb; int NL, zero_latent; };
 struct EembLatentGraph { int64_t n_a, n_b; const int32_t* order_a; const int64_t* ptr_a; const int32_t* order_b; const int64_t* ptr_b; };
-hipError_t launch_eemb_latent_forward(const EembOperands& o, const EembLatent& l, int64_t E, float* emb, float* sh, hipStream_t s);
-hipError_t launch_eemb_latent_backward(const EembOperands& o, const EembLatent& l, const EembLatentGraph& gr, const float* grad_emb, int64_t E, float* grad_w1,
-                                       float* grad_b1, float* grad_w2, float* grad_b2, float* grad_uemb, float* grad_lat_a, float* grad_lat_b,
-                                       float* workspace, hipStream_t s);
-int64_t eemb_latent_workspace(int64_t E, int32_t K, int32_t NL);
+hipError_t launch_eemb_forward(const EembOperands& o, const EembLatent* l, int64_t E, float* emb, float* sh, hipStream_t s);
+hipError_t launch_eemb_backward(const EembOperands& o, const EembLatent* l, const EembLatentGraph& gr, const float* grad_emb, int64_t E, float* grad_w1,
+                                float* grad_b1, float* grad_w2, float* grad_b2, float* grad_uemb, float* grad_lat_a, float* grad_lat_b, float* workspace,
+                                hipStream_t s);
+int64_t eemb_workspace(int64_t E, int32_t K, int32_t NL);      // NL = 0: the plain op's (the slice images alone)
 // The operands every op over a graph's ligand nodes followed by its receptor nodes takes (k_ragged.h): the node counts of the two tables, D columns, and
 // lig_ptr / rec_ptr [G + 1], device tables that the kernels range-check per graph (a graph whose pair is no range of its table is left alone)
 struct RaggedTables { const int64_t* lig_ptr; const int64_t* rec_ptr; int64_t n_lig, n_rec; int G, D; };

@@ -357,15 +357,17 @@ __global__ __launch_bounds__(EE_PT) void eemb_param_kernel(EembKernelArgs<LAT> a
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------------------------------------
-int64_t eemb_workspace(int64_t E, int32_t K) {
-  if (E < 0 || E >= (int64_t)1 << 31 || (K != EE_S + EE_D && K != EE_KMAX)) return -1;
-  return slice_bound(E, 1) * eemb_img(K) * (int64_t)sizeof(float);
+// The plain op is the latent op with NL = 0 and no unconditional term: l == nullptr below.  It runs the <false> instantiations on the EembArgs part of the
+// arguments.  workspace: [slices][eemb_img(K)], and with NL > 0 behind it [slices][24] (grad_uemb) | glat_a [E][NL] | glat_b [E][NL], every part on 16 bytes
+int64_t eemb_workspace(int64_t E, int32_t K, int32_t NL) {
+  if (E < 0 || E >= (int64_t)1 << 31 || NL < 0 || NL > EE_NLMAX || (K != EE_S + EE_D + 2 * NL && K != EE_KMAX + 2 * NL)) return -1;
+  const int64_t ns = slice_bound(E, 1);
+  return (NL ? ws_pad(ns * eemb_img(K)) + ws_pad(ns * EE_H) + 2 * ws_pad(E * NL) : ns * eemb_img(K)) * (int64_t)sizeof(float);
 }
 
 // offset as torch.linspace(start, stop, 32) makes it in fp32 (one fused multiply-add per centre, the upper half counted down from stop), coeff as GaussianSmearing: -0.5 / (offset[1] - offset[0])^2
-template <class Args = EembArgs>
-static Args eemb_args(const EembOperands& o, int64_t E) {
-  Args a{};
+static EembLatArgs eemb_args(const EembOperands& o, const EembLatent* l, int64_t E) {
+  EembLatArgs a{};
   a.pos_a = o.pos_a; a.pos_b = o.pos_b; a.idx_a = o.idx_a; a.idx_b = o.idx_b; a.feat = o.feat; a.sig = o.sig; a.sig_index = o.sig_index;
   a.w1 = o.w1; a.b1 = o.b1; a.w2 = o.w2; a.b2 = o.b2;
   a.E = E; a.L = rtp_slice_len(E);
@@ -377,69 +379,33 @@ static Args eemb_args(const EembOperands& o, int64_t E) {
   a.p = o.p;
   a.s = o.p > 0.f ? 1.0f / (1.0f - o.p) : 1.0f;
   a.seed_lo = (uint32_t)o.seed; a.seed_hi = (uint32_t)(o.seed >> 32);
-  return a;
-}
-
-hipError_t launch_eemb_forward(const EembOperands& o, int64_t E, float* emb, float* sh, hipStream_t s) {
-  if (E == 0) return hipSuccess;
-  EembArgs a = eemb_args(o, E);
-  a.emb = emb; a.sh = sh;
-  hipLaunchKernelGGL(eemb_fwd_kernel<false>, dim3((unsigned)((E + EE_EPB - 1) / EE_EPB)), dim3(EE_EPB), 0, s, a);      // E < 2^31: fewer than 2^31 workgroups
-  return hipGetLastError();
-}
-
-hipError_t launch_eemb_backward(const EembOperands& o, const float* grad_emb, int64_t E, float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2,
-                                float* workspace, hipStream_t s) {
-  const int K = o.F + EE_S + EE_D;
-  if (E == 0) {
-    hipError_t e = zero_async(grad_w1, EE_H * K, s);
-    if (e == hipSuccess) e = zero_async(grad_b1, EE_H, s);
-    if (e == hipSuccess) e = zero_async(grad_w2, EE_H * EE_H, s);
-    if (e == hipSuccess) e = zero_async(grad_b2, EE_H, s);
-    return e;
+  if (l) {
+    a.K += 2 * l->NL;
+    a.lat_a = l->lat_a; a.lat_b = l->lat_b; a.unc_a = l->unc_a; a.uemb = l->uemb;
+    a.NL = l->NL; a.zero_latent = l->zero_latent;
   }
-  EembArgs a = eemb_args(o, E);
-  a.gemb = grad_emb; a.img = workspace;
-  const int64_t n_slices = (E + a.L - 1) / a.L;      // at most 241
-  hipLaunchKernelGGL(eemb_param_kernel<false>, dim3((unsigned)n_slices), dim3(EE_PT), 0, s, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  return launch_slice_reduce(workspace, group_table(E), a.L, ReducePart{grad_w1, grad_b1, EE_H, K}, ReducePart{grad_w2, grad_b2, EE_H, EE_H}, s);
-}
-
-// ---- host: the latent variant ------------------------------------------------------------------------------------------------------------------------------
-// workspace: [slices][eemb_img(K)] | [slices][24] (grad_uemb) | glat_a [E][NL] | glat_b [E][NL], every part on 16 bytes
-int64_t eemb_latent_workspace(int64_t E, int32_t K, int32_t NL) {
-  if (E < 0 || E >= (int64_t)1 << 31 || NL < 1 || NL > EE_NLMAX || (K != EE_S + EE_D + 2 * NL && K != EE_KMAX + 2 * NL)) return -1;
-  const int64_t ns = slice_bound(E, 1);
-  return (ws_pad(ns * eemb_img(K)) + ws_pad(ns * EE_H) + 2 * ws_pad(E * NL)) * (int64_t)sizeof(float);
-}
-
-static EembLatArgs eemb_latent_args(const EembOperands& o, const EembLatent& l, int64_t E) {
-  EembLatArgs a = eemb_args<EembLatArgs>(o, E);
-  a.K += 2 * l.NL;
-  a.lat_a = l.lat_a; a.lat_b = l.lat_b; a.unc_a = l.unc_a; a.uemb = l.uemb;
-  a.NL = l.NL; a.zero_latent = l.zero_latent;
   return a;
 }
 
-hipError_t launch_eemb_latent_forward(const EembOperands& o, const EembLatent& l, int64_t E, float* emb, float* sh, hipStream_t s) {
+hipError_t launch_eemb_forward(const EembOperands& o, const EembLatent* l, int64_t E, float* emb, float* sh, hipStream_t s) {
   if (E == 0) return hipSuccess;
-  EembLatArgs a = eemb_latent_args(o, l, E);
+  EembLatArgs a = eemb_args(o, l, E);
   a.emb = emb; a.sh = sh;
-  hipLaunchKernelGGL(eemb_fwd_kernel<true>, dim3((unsigned)((E + EE_EPB - 1) / EE_EPB)), dim3(EE_EPB), 0, s, a);
+  const dim3 grid((unsigned)((E + EE_EPB - 1) / EE_EPB));      // E < 2^31: fewer than 2^31 workgroups
+  if (l) hipLaunchKernelGGL(eemb_fwd_kernel<true>, grid, dim3(EE_EPB), 0, s, a);
+  else hipLaunchKernelGGL(eemb_fwd_kernel<false>, grid, dim3(EE_EPB), 0, s, static_cast<const EembArgs&>(a));
   return hipGetLastError();
 }
 
-hipError_t launch_eemb_latent_backward(const EembOperands& o, const EembLatent& l, const EembLatentGraph& gr, const float* grad_emb, int64_t E, float* grad_w1,
-                                       float* grad_b1, float* grad_w2, float* grad_b2, float* grad_uemb, float* grad_lat_a, float* grad_lat_b,
-                                       float* workspace, hipStream_t s) {
-  const int K = o.F + EE_S + EE_D + 2 * l.NL;
-  const bool nodes = !l.zero_latent && E > 0 && (grad_lat_a || grad_lat_b);
+hipError_t launch_eemb_backward(const EembOperands& o, const EembLatent* l, const EembLatentGraph& gr, const float* grad_emb, int64_t E, float* grad_w1,
+                                float* grad_b1, float* grad_w2, float* grad_b2, float* grad_uemb, float* grad_lat_a, float* grad_lat_b, float* workspace,
+                                hipStream_t s) {
+  const int NL = l ? l->NL : 0, K = o.F + EE_S + EE_D + 2 * NL;
+  const bool nodes = l && !l->zero_latent && E > 0 && (grad_lat_a || grad_lat_b);
   hipError_t e = hipSuccess;
-  if (!nodes) {      // no edges, or the cross group: the latent gets zeros
-    e = zero_async(grad_lat_a, gr.n_a * l.NL, s);
-    if (e == hipSuccess) e = zero_async(grad_lat_b, gr.n_b * l.NL, s);
+  if (!nodes) {      // no edges, or the cross group: the latent gets zeros (the plain op has no such output)
+    e = zero_async(grad_lat_a, gr.n_a * NL, s);
+    if (e == hipSuccess) e = zero_async(grad_lat_b, gr.n_b * NL, s);
   }
   if (E == 0) {
     if (e == hipSuccess) e = zero_async(grad_w1, EE_H * K, s);
@@ -450,22 +416,27 @@ hipError_t launch_eemb_latent_backward(const EembOperands& o, const EembLatent& 
     return e;
   }
   if (e != hipSuccess) return e;
-  EembLatArgs a = eemb_latent_args(o, l, E);
-  const int64_t ns = slice_bound(E, 1);
+  EembLatArgs a = eemb_args(o, l, E);
   a.gemb = grad_emb; a.img = workspace;
-  a.img_u = workspace + ws_pad(ns * eemb_img(K));
-  float* glat_a = a.img_u + ws_pad(ns * EE_H);
-  float* glat_b = glat_a + ws_pad(E * l.NL);
-  a.glat_a = nodes ? glat_a : nullptr; a.glat_b = nodes ? glat_b : nullptr;
-  const int64_t n_slices = (E + a.L - 1) / a.L;      // at most 241
-  hipLaunchKernelGGL(eemb_param_kernel<true>, dim3((unsigned)n_slices), dim3(EE_PT), 0, s, a);
+  const dim3 grid((unsigned)((E + a.L - 1) / a.L));      // the slices: at most 241
+  float* glat_a = nullptr; float* glat_b = nullptr;
+  if (l) {
+    const int64_t ns = slice_bound(E, 1);
+    a.img_u = workspace + ws_pad(ns * eemb_img(K));
+    glat_a = a.img_u + ws_pad(ns * EE_H);
+    glat_b = glat_a + ws_pad(E * NL);
+    a.glat_a = nodes ? glat_a : nullptr; a.glat_b = nodes ? glat_b : nullptr;
+    hipLaunchKernelGGL(eemb_param_kernel<true>, grid, dim3(EE_PT), 0, s, a);
+  } else {
+    hipLaunchKernelGGL(eemb_param_kernel<false>, grid, dim3(EE_PT), 0, s, static_cast<const EembArgs&>(a));
+  }
   if ((e = hipGetLastError()) != hipSuccess) return e;
   const EdgeGroupTable t = group_table(E);
   if (grad_w1 || grad_b1 || grad_w2 || grad_b2)
     e = launch_slice_reduce(workspace, t, a.L, ReducePart{grad_w1, grad_b1, EE_H, K}, ReducePart{grad_w2, grad_b2, EE_H, EE_H}, s);
   if (e == hipSuccess && grad_uemb) e = launch_slice_reduce(a.img_u, t, a.L, ReducePart{nullptr, grad_uemb, EE_H, 0}, ReducePart{nullptr, nullptr, 0, 0}, s);
-  if (e == hipSuccess && nodes && grad_lat_a) e = launch_seg_sum(glat_a, gr.order_a, gr.ptr_a, grad_lat_a, gr.n_a, l.NL, s);
-  if (e == hipSuccess && nodes && grad_lat_b) e = launch_seg_sum(glat_b, gr.order_b, gr.ptr_b, grad_lat_b, gr.n_b, l.NL, s);
+  if (e == hipSuccess && nodes && grad_lat_a) e = launch_seg_sum(glat_a, gr.order_a, gr.ptr_a, grad_lat_a, gr.n_a, NL, s);
+  if (e == hipSuccess && nodes && grad_lat_b) e = launch_seg_sum(glat_b, gr.order_b, gr.ptr_b, grad_lat_b, gr.n_b, NL, s);
   return e;
 }
 

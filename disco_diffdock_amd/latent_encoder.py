@@ -23,8 +23,8 @@ from torch import nn
 
 from .runtime import stream_id
 from .synthetic import LIG_FEATURE_DIMS, REC_RESIDUE_FEATURE_DIMS
-from .tensor_layers import GaussianSmearing, TensorProductConvLayer, _draw_seed, _layer_seed, conv_stack, fused_edge_embedding, ragged_gumbel_softmax
-from .train_model import AtomEncoder, build_conv_edges, combine_edges
+from .tensor_layers import GaussianSmearing, TensorProductConvLayer, _draw_seed, _layer_seed, conv_stack, ragged_gumbel_softmax
+from .train_model import AtomEncoder, embed_edge_groups
 
 ENCODER_SEED_BASE = 32      # the encoder's sub-seeds start here: a score model takes 0 .. num_conv_layers + 2 (at most 18) of the same seed
 
@@ -125,13 +125,7 @@ class TPEncoder(nn.Module):
             lig_batch, rec_batch = lig.batch.to(dev).long(), rec.batch.to(dev).long()
             if lig_pos.shape[0] != lig_batch.shape[0]:
                 raise RuntimeError(f"ddk: data['ligand'].orig_pos_torch must hold one row per ligand atom ({lig_batch.shape[0]}); got {lig_pos.shape[0]}")
-            bonds = data['ligand', 'ligand']
-            lig_ei, cross_ei, rec_ei, n_bond = build_conv_edges(lig_pos, lig_batch, rec_pos, rec_batch, bonds.edge_index.to(dev),
-                                                                data['receptor', 'receptor'].edge_index.to(dev), B, self.lig_max_radius,
-                                                                self.cross_max_distance)
-            feat = torch.cat([bonds.edge_attr.to(dev).float(), torch.zeros((lig_ei.shape[1] - n_bond, 4), device=dev)], 0)
             n_lig = lig_pos.shape[0]
-            edge_index, group_sizes = combine_edges(lig_ei, cross_ei, rec_ei, n_lig)
             n_cat = self.rec_node_embedding.num_categorical_features
             rec_x = rec.x.to(dev)
         if seed is None and self.training:
@@ -147,14 +141,10 @@ class TPEncoder(nn.Module):
             sizes = torch.stack([torch.bincount(lig_batch, minlength=B)[:B], torch.bincount(rec_batch, minlength=B)[:B]]).tolist()      # (one read-back)
         lig_node_attr = _rows_by_graph(self.lig_node_embedding, sizes and sizes[0], lig.x.to(dev).long(), lig_pos.new_zeros((n_lig, 0)))
         rec_node_attr = _rows_by_graph(self.rec_node_embedding, sizes and sizes[1], rec_x[:, :n_cat].long(), rec_x[:, n_cat:].float())
-        lig_emb, lig_sh = fused_edge_embedding(self.lig_edge_embedding, self.lig_distance_expansion, lig_pos, lig_pos, lig_ei, None, None, feat=feat,
-                                               seed=emb_seeds[0])
-        lr_emb, lr_sh = fused_edge_embedding(self.cross_edge_embedding, self.cross_distance_expansion, lig_pos, rec_pos, cross_ei, None, None, seed=emb_seeds[1])
-        rec_emb, rec_sh = fused_edge_embedding(self.rec_edge_embedding, self.rec_distance_expansion, rec_pos, rec_pos, rec_ei, None, None, seed=emb_seeds[2])
-
+        edge_index, group_sizes, edge_emb, edge_sh = embed_edge_groups(self, lig_pos, lig_batch, rec_pos, rec_batch, data['ligand', 'ligand'],
+                                                                       data['receptor', 'receptor'].edge_index, B, self.cross_max_distance, None,
+                                                                       emb_seeds)      # (sig None: the encoder has no sigma block)
         node_attr = torch.cat([lig_node_attr, rec_node_attr], dim=0)
-        edge_emb = torch.cat([lig_emb, lr_emb, rec_emb, lr_emb], dim=0)      # the cross embedding is computed once and serves both directions
-        edge_sh = torch.cat([lig_sh, lr_sh, rec_sh, lr_sh], dim=0)
         node_attr = conv_stack(self.conv_layers, node_attr, edge_index, edge_emb, group_sizes, edge_sh, seed=stack_seed)
         ns = self.ns
         scalar = torch.cat([node_attr[:, :ns], node_attr[:, -ns:]], dim=1) if self.num_conv_layers >= 3 else node_attr[:, :ns]

@@ -710,8 +710,18 @@ class Context:
         return tuple(outs)      # (ws goes back to torch's allocator, which orders its reuse after these launches on the current stream)
 
     # ---- the edge embeddings in front of the conv stack -------------------------------------------------
-    def _eemb_operands(self, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, b2, p):
-        """checked operands of the edge embedding: the tensors as the entries take them, (n_a, n_b, F, n_sig, E) and the scalars"""
+    # The plain op is the latent op with L = 0 and no unconditional term: one operand checker and one caller serve both pairs of entries.
+    def _eemb_operands(self, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, b2, p, latent=None):
+        """checked operands of the edge embedding: the tensors as the entries take them, (n_a, n_b, F, n_sig, E), the scalars and the latent part
+        (lat_a, lat_b, L, zero_latent, unc_a, uemb).  ``latent``: None for the plain op (L = 0, everything None), else (lat_a, lat_b, zero_latent, unc_a,
+        uemb) with w1 [24, F + 64 + 2 L]"""
+        F, L = 0 if feat is None else 4, 0
+        if latent is not None:
+            if not torch.is_tensor(w1) or w1.dim() != 2:
+                raise RuntimeError('ddk: the latent edge embedding takes w1 [24, F + 64 + 2 L]')
+            if w1.shape[1] - F - 64 not in (2, 4, 6, 8):
+                raise RuntimeError(f'ddk: the latent edge embedding takes w1 [24, {F + 64} + 2 L] with L in 1..4; got {tuple(w1.shape)}')
+            L = (w1.shape[1] - F - 64) // 2
         pos_a, pos_b, sig, w1, b1, w2 = (_need_cuda(t).contiguous().float() for t in (pos_a, pos_b, sig, w1, b1, w2))
         dev = pos_a.device
         if pos_a.dim() != 2 or pos_a.shape[1] != 3 or pos_b.dim() != 2 or pos_b.shape[1] != 3:
@@ -725,14 +735,11 @@ class Context:
             raise RuntimeError(f'ddk: the edge embedding takes idx_a and idx_b [E] and sig_index [Na]; got {E}, {idx_b.shape[0]} and {sig_index.shape[0]} for Na = {n_a}')
         if sig.dim() != 2 or sig.shape[1] != 32 or sig.device != dev:
             raise RuntimeError(f'ddk: the edge embedding takes sig [T, 32] on the device of pos_a; got {tuple(sig.shape)}')
-        F = 0
         if feat is not None:
             feat = _need_cuda(feat).contiguous().float()
             if feat.shape != (E, 4) or feat.device != dev:
                 raise RuntimeError(f'ddk: the edge embedding takes feat [E, 4] = {(E, 4)} on the device of pos_a; got {tuple(feat.shape)}')
-            F = 4
-        K = F + 64
-        for name, t, shape in (('w1', w1, (24, K)), ('b1', b1, (24,)), ('w2', w2, (24, 24))):
+        for name, t, shape in (('w1', w1[:, :F + 64] if L else w1, (24, F + 64)), ('b1', b1, (24,)), ('w2', w2, (24, 24))):      # (w1's latent columns were counted above)
             if t.shape != shape or t.device != dev:
                 raise RuntimeError(f'ddk: the edge embedding takes {name} {list(shape)} on the device of pos_a; got {tuple(t.shape)}')
         if b2 is not None:
@@ -746,60 +753,10 @@ class Context:
             raise RuntimeError(f'ddk: the distance expansion needs start < stop; got {start}, {stop}')
         if E and (n_a == 0 or n_b == 0 or sig.shape[0] == 0):
             raise RuntimeError('ddk: the edge embedding has edges without nodes or graphs')
-        return (pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, w1, b1, w2, b2), (n_a, n_b, F, sig.shape[0], E), (start, stop, p)
-
-    def _eemb_call(self, fn, t, n, sc, seed, tail, who):
-        pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, w1, b1, w2, b2 = t
-        n_a, n_b, F, T, E = n
-        start, stop, p = sc
-        self._check(fn(self.h, _ptr(pos_a), n_a, _ptr(pos_b), n_b, _ptr(idx_a), _ptr(idx_b), _ptr(feat), F, _ptr(sig), T, _ptr(sig_index), start, stop, 32,
-                       _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), p, _u64(seed, 'seed'), *tail, _stream()), who)
-
-    def eemb_forward(self, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, b2, p=0.0, seed=0):
-        """One edge group's embedding and spherical harmonics (ddk_eemb_forward): (emb [E, 24], sh [E, 4]) with
-        ``emb = w2 dropout_p(relu(w1 [feat | sig[sig_index[idx_a]] | smearing(|pos_b[idx_b] - pos_a[idx_a]|)] + b1)) + b2`` and ``sh = [1 | sqrt3 unit vector]``.
-        ``idx_a``, ``idx_b`` [E], ``sig_index`` [Na]: int32, trusted; ``feat`` [E, 4] or None; ``start``, ``stop``: of the 32 Gaussians.  The mask is a pure
-        function of (seed, edge position, column) (DDK_EEMB_MASK_LAYOUT of include/ddk.h); nothing per edge is kept for the backward."""
-        t, n, sc = self._eemb_operands(pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, b2, p)
-        if t[-1] is None:
-            raise RuntimeError('ddk: eemb_forward needs b2')
-        E, dev = n[4], t[0].device
-        emb, sh = torch.empty((E, 24), dtype=torch.float32, device=dev), torch.empty((E, 4), dtype=torch.float32, device=dev)
-        if E:
-            self._eemb_call(self.L.ddk_eemb_forward, t, n, sc, seed, (E, _ptr(emb), _ptr(sh)), 'ddk_eemb_forward')
-        return emb, sh
-
-    def eemb_backward(self, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, grad_emb, p=0.0, seed=0, need=(True, True, True, True)):
-        """The vector-Jacobian product of ``eemb_forward`` for its parameters (ddk_eemb_backward): (grad_w1 [24, K], grad_b1 [24], grad_w2 [24, 24],
-        grad_b2 [24]), None where ``need`` is false.  The hidden layer and the mask are recomputed from the coordinates and ``seed``; the workspace holds
-        the slice images alone, comes from torch's allocator and is released on return.  No atomics: the same bits from call to call."""
-        need = _need(need, 'eemb_backward', four=True)
-        t, n, sc = self._eemb_operands(pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, None, p)
-        F, E, dev = n[2], n[4], t[0].device
-        grad_emb = _need_cuda(grad_emb).contiguous().float()
-        if grad_emb.shape != (E, 24) or grad_emb.device != dev:
-            raise RuntimeError(f'ddk: eemb_backward takes grad_emb [E, 24] = {(E, 24)} on the device of pos_a; got {tuple(grad_emb.shape)}')
-        outs, _ = _outputs(need, ((24, F + 64), (24,), (24, 24), (24,)), dev)      # (never empty)
-        ws = _workspace(self.L.ddk_eemb_workspace(E, F + 64), f'no edge-embedding workspace for E = {E}, K = {F + 64}', dev)
-        self._eemb_call(self.L.ddk_eemb_backward, t, n, sc, seed, (_ptr(grad_emb) if E else None, E, *[_ptr(o) for o in outs], _ptr(ws)), 'ddk_eemb_backward')
-        return tuple(outs)      # (ws goes back to torch's allocator, which orders its reuse after these launches on the current stream)
-
-    # ---- the edge embeddings of the latent-conditioned (DisCo) model ------------------------------------
-    def _eemb_latent_operands(self, ops, lat_a, lat_b, zero_latent, unc_a, uemb, b2=None):
-        """checked operands of the latent edge embedding: those of ``_eemb_operands`` (``ops``: its arguments with w1 [24, F + 64 + 2 L]) and
-        (lat_a, lat_b, L, zero_latent, unc_a, uemb)"""
-        pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, p = ops
-        if not torch.is_tensor(w1) or w1.dim() != 2:
-            raise RuntimeError('ddk: the latent edge embedding takes w1 [24, F + 64 + 2 L]')
-        F = 0 if feat is None else 4
-        L2 = w1.shape[1] - F - 64
-        if L2 not in (2, 4, 6, 8):
-            raise RuntimeError(f'ddk: the latent edge embedding takes w1 [24, {F + 64} + 2 L] with L in 1..4; got {tuple(w1.shape)}')
-        L = L2 // 2
-        w1 = _need_cuda(w1).contiguous().float()
-        t, n, sc = self._eemb_operands(pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1[:, :F + 64], b1, w2, b2, p)
-        t = t[:7] + (w1,) + t[8:]
-        dev, n_a, n_b = t[0].device, n[0], n[1]
+        t, n, sc = (pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, w1, b1, w2, b2), (n_a, n_b, F, sig.shape[0], E), (start, stop, p)
+        if latent is None:
+            return t, n, sc, (None, None, 0, False, None, None)
+        lat_a, lat_b, zero_latent, unc_a, uemb = latent
         zero_latent = bool(zero_latent)
         if zero_latent:
             lat_a = lat_b = None
@@ -819,29 +776,65 @@ class Context:
                                    f'{tuple(uemb.shape)}')
         return t, n, sc, (lat_a, lat_b, L, zero_latent, unc_a, uemb)
 
-    def _eemb_latent_call(self, fn, t, n, sc, seed, lat, tail, who):
+    def _eemb_call(self, direction, t, n, sc, seed, lat, tail):
+        """``ddk_eemb_<direction>`` for L == 0, ``ddk_eemb_latent_<direction>`` with the latent arguments behind the seed otherwise; ``tail``: what follows"""
         pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, w1, b1, w2, b2 = t
         n_a, n_b, F, T, E = n
         start, stop, p = sc
         lat_a, lat_b, L, zero, unc_a, uemb = lat
-        self._check(fn(self.h, _ptr(pos_a), n_a, _ptr(pos_b), n_b, _ptr(idx_a), _ptr(idx_b), _ptr(feat), F, _ptr(sig), T, _ptr(sig_index), start, stop, 32,
-                       _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), p, _u64(seed, 'seed'), _ptr(lat_a), _ptr(lat_b), L, int(zero), _ptr(unc_a), _ptr(uemb),
-                       *tail, _stream()), who)
+        who = ('ddk_eemb_latent_' if L else 'ddk_eemb_') + direction
+        latent = (_ptr(lat_a), _ptr(lat_b), L, int(zero), _ptr(unc_a), _ptr(uemb)) if L else ()
+        self._check(getattr(self.L, who)(self.h, _ptr(pos_a), n_a, _ptr(pos_b), n_b, _ptr(idx_a), _ptr(idx_b), _ptr(feat), F, _ptr(sig), T, _ptr(sig_index),
+                                         start, stop, 32, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), p, _u64(seed, 'seed'), *latent, *tail, _stream()), who)
+
+    def eemb_forward(self, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, b2, p=0.0, seed=0):
+        """One edge group's embedding and spherical harmonics (ddk_eemb_forward): (emb [E, 24], sh [E, 4]) with
+        ``emb = w2 dropout_p(relu(w1 [feat | sig[sig_index[idx_a]] | smearing(|pos_b[idx_b] - pos_a[idx_a]|)] + b1)) + b2`` and ``sh = [1 | sqrt3 unit vector]``.
+        ``idx_a``, ``idx_b`` [E], ``sig_index`` [Na]: int32, trusted; ``feat`` [E, 4] or None; ``start``, ``stop``: of the 32 Gaussians.  The mask is a pure
+        function of (seed, edge position, column) (DDK_EEMB_MASK_LAYOUT of include/ddk.h); nothing per edge is kept for the backward."""
+        t, n, sc, lat = self._eemb_operands(pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, b2, p)
+        if t[-1] is None:
+            raise RuntimeError('ddk: eemb_forward needs b2')
+        return self._eemb_outputs(t, n, sc, seed, lat)
+
+    def _eemb_outputs(self, t, n, sc, seed, lat):
+        """(emb [E, 24], sh [E, 4]) of checked operands"""
+        E, dev = n[4], t[0].device
+        emb, sh = torch.empty((E, 24), dtype=torch.float32, device=dev), torch.empty((E, 4), dtype=torch.float32, device=dev)
+        if E:
+            self._eemb_call('forward', t, n, sc, seed, lat, (E, _ptr(emb), _ptr(sh)))
+        return emb, sh
+
+    def eemb_backward(self, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, grad_emb, p=0.0, seed=0, need=(True, True, True, True)):
+        """The vector-Jacobian product of ``eemb_forward`` for its parameters (ddk_eemb_backward): (grad_w1 [24, K], grad_b1 [24], grad_w2 [24, 24],
+        grad_b2 [24]), None where ``need`` is false.  The hidden layer and the mask are recomputed from the coordinates and ``seed``; the workspace holds
+        the slice images alone, comes from torch's allocator and is released on return.  No atomics: the same bits from call to call."""
+        need = _need(need, 'eemb_backward', four=True)
+        t, n, sc, lat = self._eemb_operands(pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, None, p)
+        F, E, dev = n[2], n[4], t[0].device
+        grad_emb = self._eemb_grad_emb('eemb_backward', grad_emb, E, dev)
+        outs, _ = _outputs(need, ((24, F + 64), (24,), (24, 24), (24,)), dev)      # (never empty)
+        ws = _workspace(self.L.ddk_eemb_workspace(E, F + 64), f'no edge-embedding workspace for E = {E}, K = {F + 64}', dev)
+        self._eemb_call('backward', t, n, sc, seed, lat, (_ptr(grad_emb) if E else None, E, *[_ptr(o) for o in outs], _ptr(ws)))
+        return tuple(outs)      # (ws goes back to torch's allocator, which orders its reuse after these launches on the current stream)
+
+    @staticmethod
+    def _eemb_grad_emb(who, grad_emb, E, dev):
+        grad_emb = _need_cuda(grad_emb).contiguous().float()
+        if grad_emb.shape != (E, 24) or grad_emb.device != dev:
+            raise RuntimeError(f'ddk: {who} takes grad_emb [E, 24] = {(E, 24)} on the device of pos_a; got {tuple(grad_emb.shape)}')
+        return grad_emb
 
     def eemb_latent_forward(self, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, b2, lat_a, lat_b, zero_latent=False, unc_a=None,
                             uemb=None, p=0.0, seed=0):
         """``eemb_forward`` with the latent columns (ddk_eemb_latent_forward): the row is ``[feat | sig | smearing | lat_a[idx_a] | lat_b[idx_b]]``, ``w1``
         [24, F + 64 + 2 L], and ``emb += unc_a[idx_a][:, None] * uemb`` where ``unc_a`` [Na] and ``uemb`` [24] are given.  ``zero_latent``: the 2 L columns
         hold zeros and the tables are not read (the cross group).  Returns (emb [E, 24], sh [E, 4])."""
-        t, n, sc, lat = self._eemb_latent_operands((pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, p), lat_a, lat_b, zero_latent,
-                                                   unc_a, uemb, b2)
+        t, n, sc, lat = self._eemb_operands(pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, b2, p,
+                                            (lat_a, lat_b, zero_latent, unc_a, uemb))
         if t[-1] is None:
             raise RuntimeError('ddk: eemb_latent_forward needs b2')
-        E, dev = n[4], t[0].device
-        emb, sh = torch.empty((E, 24), dtype=torch.float32, device=dev), torch.empty((E, 4), dtype=torch.float32, device=dev)
-        if E:
-            self._eemb_latent_call(self.L.ddk_eemb_latent_forward, t, n, sc, seed, lat, (E, _ptr(emb), _ptr(sh)), 'ddk_eemb_latent_forward')
-        return emb, sh
+        return self._eemb_outputs(t, n, sc, seed, lat)
 
     def eemb_latent_backward(self, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, lat_a, lat_b, grad_emb, zero_latent=False,
                              unc_a=None, uemb=None, p=0.0, seed=0, graph=None, need=(True,) * 7):
@@ -852,27 +845,24 @@ class Context:
         need = tuple(bool(x) for x in need)
         if len(need) != 7 or not any(need):
             raise RuntimeError('ddk: eemb_latent_backward needs at least one of its seven gradients to compute')
-        t, n, sc, lat = self._eemb_latent_operands((pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, p), lat_a, lat_b, zero_latent,
-                                                   unc_a, uemb)
+        t, n, sc, lat = self._eemb_operands(pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, None, p,
+                                            (lat_a, lat_b, zero_latent, unc_a, uemb))
         n_a, n_b, F, _, E = n
         dev, L = t[0].device, lat[2]
         K = F + 64 + 2 * L
-        grad_emb = _need_cuda(grad_emb).contiguous().float()
-        if grad_emb.shape != (E, 24) or grad_emb.device != dev:
-            raise RuntimeError(f'ddk: eemb_latent_backward takes grad_emb [E, 24] = {(E, 24)} on the device of pos_a; got {tuple(grad_emb.shape)}')
+        grad_emb = self._eemb_grad_emb('eemb_latent_backward', grad_emb, E, dev)
         tables = (None,) * 4
         if E and not lat[3] and (need[5] or need[6]):
             if not isinstance(graph, ConvGraph) or graph.E != E or graph.n_out != n_a or graph.n_in != n_b or graph.src.device != dev:
                 raise RuntimeError('ddk: eemb_latent_backward takes graph = Context.conv_graph(idx_a, idx_b, Nb, Na) on the device of pos_a for the latent gradients')
             tables = (graph.src_order, graph.src_ptr, graph.dst_order, graph.dst_ptr)
-        outs, live = _outputs(need, ((24, K), (24,), (24, 24), (24,), (24,), (n_a, L), (n_b, L)), dev)
+        shapes = ((24, K), (24,), (24, 24), (24,), (24,), (n_a, L), (n_b, L))
+        outs, live = _outputs(need, shapes, dev)
         if not live:
             return tuple(outs)
         outs = [o if o is None or o.numel() else None for o in outs]      # (an empty node table has no address)
         ws = _workspace(self.L.ddk_eemb_latent_workspace(E, K, L), f'no latent edge-embedding workspace for E = {E}, K = {K}, L = {L}', dev)
-        self._eemb_latent_call(self.L.ddk_eemb_latent_backward, t, n, sc, seed, lat,
-                               (*[_ptr(x) for x in tables], _ptr(grad_emb) if E else None, E, *[_ptr(o) for o in outs], _ptr(ws)), 'ddk_eemb_latent_backward')
-        shapes = ((24, K), (24,), (24, 24), (24,), (24,), (n_a, L), (n_b, L))
+        self._eemb_call('backward', t, n, sc, seed, lat, (*[_ptr(x) for x in tables], _ptr(grad_emb) if E else None, E, *[_ptr(o) for o in outs], _ptr(ws)))
         return tuple(torch.zeros(s, dtype=torch.float32, device=dev) if (on and o is None) else o for on, o, s in zip(need, outs, shapes))
 
     # ---- the ragged straight-through Gumbel softmax ------------------------------------------------------

@@ -402,61 +402,48 @@ def conv_stack(conv_layers, node_attr, edge_index, edge_emb, group_sizes, edge_s
     return node_attr
 
 
+def _edge_embedding_forward(scalars, w1, b1, w2, b2, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, *lat):
+    """(emb, sh) of one edge group from the device op, without autograd.  ``scalars``: (start, stop, p, seed, zero_latent, graph); ``lat``: nothing for
+    the plain op (ddk_eemb_forward), (uemb, lat_a, lat_b, unc_a) for the latent one (ddk_eemb_latent_forward)"""
+    start, stop, p, seed, zero_latent, _ = scalars
+    ctx, ops = _ctx_of(pos_a), (pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, b2)
+    if lat:
+        uemb, lat_a, lat_b, unc_a = lat
+        return ctx.eemb_latent_forward(*ops, lat_a, lat_b, zero_latent, unc_a, uemb, p, seed)
+    return ctx.eemb_forward(*ops, p, seed)
+
+
 class _EdgeEmbeddingFunction(torch.autograd.Function):
-    """ddk_eemb_forward with ddk_eemb_backward as its vector-Jacobian product: one edge group's embedding [E, 24] and spherical harmonics [E, 4] from the
-    coordinates.  Saved for the backward: the operands it was given (positions, index tensors, bond features, the sigma table, the four parameters);
-    nothing per edge that the op made itself.  The backward recomputes the hidden layer and the mask from the seed.  Gradients: the four parameters
-    alone, without atomics: the same bits on every run."""
+    """``_edge_embedding_forward`` with ddk_eemb_backward / ddk_eemb_latent_backward as its vector-Jacobian product: one edge group's embedding [E, 24]
+    and spherical harmonics [E, 4] from the coordinates.  Saved for the backward: the operands it was given (positions, index tensors, bond features,
+    the sigma table, the parameters without b2; the latent op's four tensors behind them, its node-sorted edge lists in ``scalars``); nothing per edge
+    that the op made itself.  The plain op has no latent inputs: it takes and saves no more than it did.  The backward recomputes the hidden layer and
+    the mask from the seed.  Gradients: the four parameters, and for the latent op ``uemb`` and the two latent tables (where both are one tensor the
+    caller adds the two), all without atomics: the same bits on every run."""
 
     @staticmethod
-    def forward(fctx, w1, b1, w2, b2, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, p, seed):
-        ctx = _ctx_of(pos_a)
-        emb, sh = ctx.eemb_forward(pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, b2, p, seed)
-        fctx.save_for_backward(w1, b1, w2, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index)      # (b2 is not read by the backward)
-        fctx.ddk, fctx.scalars = ctx, (start, stop, p, seed)
-        fctx.meta = [(t.shape, t.dtype) for t in (w1, b1, w2, b2)]
+    def forward(fctx, scalars, w1, b1, w2, b2, *rest):      # rest: the seven geometry operands, then ``lat``
+        emb, sh = _edge_embedding_forward(scalars, w1, b1, w2, b2, *rest)
+        fctx.save_for_backward(w1, b1, w2, *rest)      # (b2 is not read by the backward)
+        fctx.ddk, fctx.scalars = _ctx_of(rest[0]), scalars
+        fctx.meta = [None if t is None else (t.shape, t.dtype) for t in (w1, b1, w2, b2, *rest[7:10])]
         fctx.mark_non_differentiable(sh)
         return emb, sh
 
     @staticmethod
     @once_differentiable
     def backward(fctx, grad_emb, _grad_sh):
-        w1, b1, w2, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index = fctx.saved_tensors
-        start, stop, p, seed = fctx.scalars
-        need = tuple(fctx.needs_input_grad[:4])
-        with torch.cuda.device(pos_a.device):
-            grads = fctx.ddk.eemb_backward(pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, grad_emb, p, seed, need)
-        return _grads_like(grads, fctx.meta) + (None,) * 11
-
-
-class _LatentEdgeEmbeddingFunction(torch.autograd.Function):
-    """ddk_eemb_latent_forward with ddk_eemb_latent_backward as its vector-Jacobian product: ``_EdgeEmbeddingFunction`` with the latent columns and the
-    unconditional embedding.  Saved for the backward: the operands it was given, the two latent tables and the node-sorted edge lists among them; nothing
-    per edge that the op made itself.  Gradients: the four parameters, ``uemb`` and the two latent tables (where both are one tensor the caller adds the
-    two), all without atomics: the same bits on every run."""
-
-    @staticmethod
-    def forward(fctx, w1, b1, w2, b2, uemb, lat_a, lat_b, unc_a, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, p, seed, zero_latent, graph):
-        ctx = _ctx_of(pos_a)
-        emb, sh = ctx.eemb_latent_forward(pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, b2, lat_a, lat_b, zero_latent, unc_a,
-                                          uemb, p, seed)
-        fctx.save_for_backward(w1, b1, w2, uemb, lat_a, lat_b, unc_a, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index)      # (b2 is not read by the backward)
-        fctx.ddk, fctx.scalars, fctx.graph = ctx, (start, stop, p, seed, zero_latent), graph
-        fctx.meta = [None if t is None else (t.shape, t.dtype) for t in (w1, b1, w2, b2, uemb, lat_a, lat_b)]
-        fctx.mark_non_differentiable(sh)
-        return emb, sh
-
-    @staticmethod
-    @once_differentiable
-    def backward(fctx, grad_emb, _grad_sh):
-        w1, b1, w2, uemb, lat_a, lat_b, unc_a, pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index = fctx.saved_tensors
-        start, stop, p, seed, zero_latent = fctx.scalars
-        need = tuple(fctx.needs_input_grad[:7])
-        with torch.cuda.device(pos_a.device):
-            grads = fctx.ddk.eemb_latent_backward(pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop, w1, b1, w2, lat_a, lat_b, grad_emb,
-                                                  zero_latent, unc_a, uemb, p, seed, fctx.graph, need)
+        w1, b1, w2, *rest = fctx.saved_tensors
+        start, stop, p, seed, zero_latent, graph = fctx.scalars
+        ops, lat, need = (*rest[:7], start, stop, w1, b1, w2), rest[7:], fctx.needs_input_grad
+        with torch.cuda.device(rest[0].device):
+            if lat:
+                uemb, lat_a, lat_b, unc_a = lat
+                grads = fctx.ddk.eemb_latent_backward(*ops, lat_a, lat_b, grad_emb, zero_latent, unc_a, uemb, p, seed, graph, need[1:5] + need[12:15])
+            else:
+                grads = fctx.ddk.eemb_backward(*ops, grad_emb, p, seed, need[1:5])
         out = tuple(None if (g is None or m is None) else g.reshape(m[0]).to(m[1]) for g, m in zip(grads, fctx.meta))
-        return out + (None,) * 14
+        return (None,) + out[:4] + (None,) * 7 + out[4:] + ((None,) if lat else ())
 
 
 def _smearing_range(expansion):
@@ -552,19 +539,15 @@ def fused_edge_embedding(mlp, expansion, pos_a, pos_b, edge_index, sig, sig_inde
     operands = (pos_a.detach().float().contiguous(), pos_b.detach().float().contiguous(), idx_a, idx_b, None if feat is None else feat.float().contiguous(),
                 sig.float().contiguous(), sig_index.to(torch.int32).contiguous())
     b1, w2, b2 = mlp[0].bias, mlp[3].weight, mlp[3].bias
+    lat = ()      # (latent_a and latent_b may be one tensor: autograd adds the source sum and the destination sum, a commutative fp32 add)
     if latent:
-        uemb = None if unconditional_embedding is None else unconditional_embedding.reshape(-1)
-        unc = None if unconditional is None else unconditional.detach().float().reshape(-1).contiguous()
-        la, lb = latent_a, latent_b      # (one tensor on both sides: autograd adds the source sum and the destination sum, a commutative fp32 add)
-        diff = [t for t in (w1, b1, w2, b2, uemb, la, lb) if t is not None]
-        if torch.is_grad_enabled() and any(t.requires_grad for t in diff):
-            if graph is None and la is not None and (la.requires_grad or lb.requires_grad) and idx_a.shape[0] > 0:
-                graph = Context.conv_graph(idx_a, idx_b, pos_b.shape[0], pos_a.shape[0])
-            return _LatentEdgeEmbeddingFunction.apply(w1, b1, w2, b2, uemb, la, lb, unc, *operands, start, stop, p, int(seed), bool(zero_latent), graph)
-        return _ctx_of(pos_a).eemb_latent_forward(*operands, start, stop, w1, b1, w2, b2, la, lb, bool(zero_latent), unc, uemb, p, int(seed))
-    if torch.is_grad_enabled() and any(t.requires_grad for t in (w1, b1, w2, b2)):
-        return _EdgeEmbeddingFunction.apply(w1, b1, w2, b2, *operands, start, stop, p, int(seed))
-    return _ctx_of(pos_a).eemb_forward(*operands, start, stop, w1, b1, w2, b2, p, int(seed))
+        lat = (None if unconditional_embedding is None else unconditional_embedding.reshape(-1), latent_a, latent_b,
+               None if unconditional is None else unconditional.detach().float().reshape(-1).contiguous())
+    differentiable = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (w1, b1, w2, b2, *lat[:3]))
+    if differentiable and latent and graph is None and latent_a is not None and (latent_a.requires_grad or latent_b.requires_grad) and idx_a.shape[0] > 0:
+        graph = Context.conv_graph(idx_a, idx_b, pos_b.shape[0], pos_a.shape[0])
+    args = ((start, stop, p, int(seed), bool(zero_latent), graph if latent else None), w1, b1, w2, b2, *operands, *lat)
+    return _EdgeEmbeddingFunction.apply(*args) if differentiable else _edge_embedding_forward(*args)
 
 
 class _RaggedGumbelFunction(torch.autograd.Function):

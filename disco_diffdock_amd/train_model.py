@@ -85,6 +85,31 @@ def combine_edges(lig_ei, cross_ei, rec_ei, n_lig):
     return edge_index, (lig_ei.shape[1], lr.shape[1], rec_ei.shape[1], lr.shape[1])
 
 
+def embed_edge_groups(model, lig_pos, lig_batch, rec_pos, rec_batch, bonds, rec_edge_index, B, cross_cutoff, sig, seeds, latent=None):
+    """What the score model and the latent encoder do alike between their node embeddings and ``conv_stack``: the three edge lists
+    (``build_conv_edges`` at ``model.lig_max_radius`` and ``cross_cutoff``), the bond features padded with zero rows for the radius edges,
+    ``combine_edges``, and one ``fused_edge_embedding`` per group through ``model``'s ``{lig,cross,rec}_edge_embedding`` / ``_distance_expansion``.
+    ``bonds``: the batch's ``data['ligand', 'ligand']``; ``sig`` [B, 32] or None (a row without the sigma block); ``seeds``: of the three groups;
+    ``latent``: per group the latent keywords of ``fused_edge_embedding`` (None: the plain op in all three).  Returns (edge_index [2, E], the four group sizes, edge_emb [E, 24],
+    edge_sh [E, 4]) in the order of ``combine_edges``."""
+    dev, latent = lig_pos.device, latent or ({}, {}, {})
+    with torch.no_grad():
+        lig_ei, cross_ei, rec_ei, n_bond = build_conv_edges(lig_pos, lig_batch, rec_pos, rec_batch, bonds.edge_index.to(dev), rec_edge_index.to(dev), B,
+                                                            model.lig_max_radius, cross_cutoff)
+        feat = torch.cat([bonds.edge_attr.to(dev).float(), torch.zeros((lig_ei.shape[1] - n_bond, 4), device=dev)], 0)
+        edge_index, group_sizes = combine_edges(lig_ei, cross_ei, rec_ei, lig_pos.shape[0])
+        lig_idx, rec_idx = (None, None) if sig is None else (lig_batch.to(torch.int32), rec_batch.to(torch.int32))
+    lig_emb, lig_sh = fused_edge_embedding(model.lig_edge_embedding, model.lig_distance_expansion, lig_pos, lig_pos, lig_ei, sig, lig_idx, feat=feat,
+                                           seed=seeds[0], **latent[0])
+    lr_emb, lr_sh = fused_edge_embedding(model.cross_edge_embedding, model.cross_distance_expansion, lig_pos, rec_pos, cross_ei, sig, lig_idx, seed=seeds[1],
+                                         **latent[1])
+    rec_emb, rec_sh = fused_edge_embedding(model.rec_edge_embedding, model.rec_distance_expansion, rec_pos, rec_pos, rec_ei, sig, rec_idx, seed=seeds[2],
+                                           **latent[2])
+    edge_emb = torch.cat([lig_emb, lr_emb, rec_emb, lr_emb], dim=0)      # the cross embedding is computed once and serves both directions
+    edge_sh = torch.cat([lig_sh, lr_sh, rec_sh, lr_sh], dim=0)
+    return edge_index, group_sizes, edge_emb, edge_sh
+
+
 class AtomEncoder(nn.Module):
     """models/layers.py:119-149 (the new AtomEncoder): one embedding table per categorical feature, summed, then a Linear over [sum | scalar features |
     sigma embedding] where there are any such columns (the latent encoder's ligand side, and its receptor side without ESM, have none: the sum is the output).  The tables are read through ``gather_rows``: their gradient is a fixed-order segmented sum, not index_add_'s atomics."""
@@ -204,7 +229,9 @@ class TrainableScoreModel(nn.Module):
         return tr_sigma * 3 + 20
 
     def embed(self, data, seed=None):
-        """models/score_model.py:169-257: (lig_node_attr [N_lig, 84], rec_node_attr [N_rec, 84]) after the conv stack, for a collated batch"""
+        """models/score_model.py:169-257: (lig_node_attr [N_lig, 84], rec_node_attr [N_rec, 84]) after the conv stack, for a collated batch.  With
+        ``latent_dim`` (models/score_model.py:191-215, 310-408 with latent_h) the node rows are [x | sig | latent] (+ unconditional *
+        node_unconditional_embedding) and the edge rows carry [latent[src] | latent[dst]] inside the fused op"""
         lig, rec = data['ligand'], data['receptor']
         if not lig.pos.is_cuda:
             raise RuntimeError('ddk TrainableScoreModel runs on the GPU only (no CPU fallback)')
@@ -214,14 +241,7 @@ class TrainableScoreModel(nn.Module):
             lig_pos, rec_pos = lig.pos.detach().float(), rec.pos.detach().float()
             lig_batch, rec_batch = lig.batch.to(dev).long(), rec.batch.to(dev).long()
             sig = self.timestep_emb_func(complex_t['tr'])      # [B, 32]: a node's sigma embedding is its graph's
-            bonds = data['ligand', 'ligand']
-            lig_ei, cross_ei, rec_ei, n_bond = build_conv_edges(lig_pos, lig_batch, rec_pos, rec_batch, bonds.edge_index.to(dev),
-                                                                data['receptor', 'receptor'].edge_index.to(dev), B, self.lig_max_radius,
-                                                                self._cross_cutoff(complex_t))
-            feat = torch.cat([bonds.edge_attr.to(dev).float(), torch.zeros((lig_ei.shape[1] - n_bond, 4), device=dev)], 0)
             n_lig = lig_pos.shape[0]
-            edge_index, group_sizes = combine_edges(lig_ei, cross_ei, rec_ei, n_lig)
-            lig_idx, rec_idx = lig_batch.to(torch.int32), rec_batch.to(torch.int32)
             n_cat = self.rec_node_embedding.num_categorical_features
             rec_x = rec.x.to(dev)
         if self.training and seed is None:
@@ -229,19 +249,15 @@ class TrainableScoreModel(nn.Module):
         seeds = [None if seed is None else _layer_seed(seed, len(self.conv_layers) + g) for g in range(3)]      # (the conv layers take 0 .. L - 1)
 
         if self.latent_dim:
-            lig_node_attr, rec_node_attr, (lig_emb, lig_sh), (lr_emb, lr_sh), (rec_emb, rec_sh) = self._embed_latent(
-                data, sig, lig_pos, rec_pos, lig_batch, rec_batch, lig_idx, rec_idx, lig_ei, cross_ei, rec_ei, feat, rec_x, n_cat, seeds)
+            lig_node_attr, rec_node_attr, latent = self._embed_latent(data, sig, lig_batch, rec_batch, rec_x, n_cat)
         else:
             lig_node_attr = self.lig_node_embedding(lig.x.to(dev).long(), sig[lig_batch])
             rec_node_attr = self.rec_node_embedding(rec_x[:, :n_cat].long(), torch.cat([rec_x[:, n_cat:].float(), sig[rec_batch]], 1))
-            lig_emb, lig_sh = fused_edge_embedding(self.lig_edge_embedding, self.lig_distance_expansion, lig_pos, lig_pos, lig_ei, sig, lig_idx, feat=feat,
-                                                   seed=seeds[0])
-            lr_emb, lr_sh = fused_edge_embedding(self.cross_edge_embedding, self.cross_distance_expansion, lig_pos, rec_pos, cross_ei, sig, lig_idx, seed=seeds[1])
-            rec_emb, rec_sh = fused_edge_embedding(self.rec_edge_embedding, self.rec_distance_expansion, rec_pos, rec_pos, rec_ei, sig, rec_idx, seed=seeds[2])
-
+            latent = None
+        edge_index, group_sizes, edge_emb, edge_sh = embed_edge_groups(self, lig_pos, lig_batch, rec_pos, rec_batch, data['ligand', 'ligand'],
+                                                                       data['receptor', 'receptor'].edge_index, B, self._cross_cutoff(complex_t), sig,
+                                                                       seeds, latent)
         node_attr = torch.cat([lig_node_attr, rec_node_attr], dim=0)
-        edge_emb = torch.cat([lig_emb, lr_emb, rec_emb, lr_emb], dim=0)      # the cross embedding is computed once and serves both directions
-        edge_sh = torch.cat([lig_sh, lr_sh, rec_sh, lr_sh], dim=0)
         node_attr = conv_stack(self.conv_layers, node_attr, edge_index, edge_emb, group_sizes, edge_sh, seed=seed)
         return node_attr[:n_lig], node_attr[n_lig:]
 
@@ -268,10 +284,10 @@ class TrainableScoreModel(nn.Module):
             out.append(u)
         return out
 
-    def _embed_latent(self, data, sig, lig_pos, rec_pos, lig_batch, rec_batch, lig_idx, rec_idx, lig_ei, cross_ei, rec_ei, feat, rec_x, n_cat, seeds):
-        """the node and edge embeddings of the latent-conditioned model (models/score_model.py:191-215, 310-408 with latent_h): node rows
-        [x | sig | latent] (+ unconditional * node_unconditional_embedding), edge rows with [latent[src] | latent[dst]] inside the fused op"""
-        dev = lig_pos.device
+    def _embed_latent(self, data, sig, lig_batch, rec_batch, rec_x, n_cat):
+        """what the latent-conditioned model embeds differently (models/score_model.py:191-215, 310-408 with latent_h): the node rows [x | sig | latent]
+        (+ unconditional * node_unconditional_embedding), and per edge group the latent keywords of ``fused_edge_embedding``"""
+        dev = sig.device
         lat_l, lat_r, unc_l, unc_r = self._latent_inputs(data, dev)
         lig_node_attr = self.lig_node_embedding(data['ligand'].x.to(dev).long(), torch.cat([sig[lig_batch], lat_l], 1))
         rec_node_attr = self.rec_node_embedding(rec_x[:, :n_cat].long(), torch.cat([rec_x[:, n_cat:].float(), sig[rec_batch], lat_r], 1))
@@ -279,13 +295,9 @@ class TrainableScoreModel(nn.Module):
         if unc_l is not None:
             lig_node_attr = lig_node_attr + unc_l * self.lig_node_unconditional_embedding
             rec_node_attr = rec_node_attr + unc_r * self.rec_node_unconditional_embedding
-        lig = fused_edge_embedding(self.lig_edge_embedding, self.lig_distance_expansion, lig_pos, lig_pos, lig_ei, sig, lig_idx, feat=feat, seed=seeds[0],
-                                   latent_a=lat_l, latent_b=lat_l, **unc(unc_l, 'lig_edge'))
-        cross = fused_edge_embedding(self.cross_edge_embedding, self.cross_distance_expansion, lig_pos, rec_pos, cross_ei, sig, lig_idx, seed=seeds[1],
-                                     latent_a=self.latent_dim, zero_latent=True, **unc(unc_l, 'cross_edge'))
-        rec = fused_edge_embedding(self.rec_edge_embedding, self.rec_distance_expansion, rec_pos, rec_pos, rec_ei, sig, rec_idx, seed=seeds[2],
-                                   latent_a=lat_r, latent_b=lat_r, **unc(unc_r, 'rec_edge'))
-        return lig_node_attr, rec_node_attr, lig, cross, rec
+        return lig_node_attr, rec_node_attr, (dict(latent_a=lat_l, latent_b=lat_l, **unc(unc_l, 'lig_edge')),
+                                              dict(latent_a=self.latent_dim, zero_latent=True, **unc(unc_l, 'cross_edge')),
+                                              dict(latent_a=lat_r, latent_b=lat_r, **unc(unc_r, 'rec_edge')))
 
     def forward(self, data, seed=None):
         """``data``: a collated batch in the reference's layout (``data['ligand'].x / .pos / .batch / .edge_mask``, ``data['ligand', 'ligand'].edge_index /

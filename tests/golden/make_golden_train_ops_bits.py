@@ -19,6 +19,8 @@ THE CASES.  rtp_slice_len is 512 for these sizes.
     rhid           both group tables, p = 0 and p = 0.25, forward and all four gradients
     hconv          the centre head with E = 1300 onto 3 receivers; the torsion head with E = 700 onto 17 receivers, one of them without edges
     eemb           E = 1300, F = 0 and F = 4, p = 0 and p = 0.25, forward and all four gradients
+    eemb, latent   the same edges and operands with a last node on either side that has no edge, unc_a / uemb given: L = 1 with F = 0 and L = 4 with
+                   F = 4, each at p = 0 and p = 0.25, and zero_latent with L = 2 (F = 0, p = 0.25); forward and all seven gradients
     seg_sum        D = 1 and D = 128 (column 0 of the latter is all -0: the first row starts the sum, so -0 stays -0)
 """
 import argparse
@@ -125,6 +127,19 @@ def outputs(ctx, dev):
             ops = (pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop)
             out += named(tag, ('emb', 'sh'), ctx.eemb_forward(*ops, w1, b1, w2, b2, p, 0xBEEF))
             out += named(tag, ('grad_w1', 'grad_b1', 'grad_w2', 'grad_b2'), ctx.eemb_backward(*ops, w1, b1, w2, g, p, 0xBEEF))
+        # the latent op on the same edges (drawn behind everything above, which keeps its bits).  Either node table gains a last node that no edge names
+        pos_a, pos_b, sig_index = torch.cat([pos_a, f(1, 3)]), torch.cat([pos_b, f(1, 3)]), torch.cat([sig_index, i32(T, 1)])
+        graph = ctx.conv_graph(idx_a, idx_b, n_b + 1, n_a + 1)
+        assert int(graph.src_ptr[-1] - graph.src_ptr[-2]) == 0 and int(graph.dst_ptr[-1] - graph.dst_ptr[-2]) == 0
+        unc_a, uemb = torch.from_numpy((rng.random(n_a + 1) < 0.5).astype(np.float32)).to(dev), f(24)
+        ops = (pos_a, pos_b, idx_a, idx_b, feat, sig, sig_index, start, stop)
+        for L, zero, ps in ((1 if F == 0 else 4, False, (0.0, 0.25)),) + (((2, True, (0.25,)),) if F == 0 else ()):
+            w1l, lat_a, lat_b = torch.cat([w1, f(24, 2 * L) / 8], 1), f(n_a + 1, L), f(n_b + 1, L)
+            for p in ps:
+                tag = f'eemb.F{F}.L{L}.p{p}' + ('.zero_latent' if zero else '')
+                out += named(tag, ('emb', 'sh'), ctx.eemb_latent_forward(*ops, w1l, b1, w2, b2, lat_a, lat_b, zero, unc_a, uemb, p, 0xBEEF))
+                out += named(tag, ('grad_w1', 'grad_b1', 'grad_w2', 'grad_b2', 'grad_uemb', 'grad_lat_a', 'grad_lat_b'),
+                             ctx.eemb_latent_backward(*ops, w1l, b1, w2, lat_a, lat_b, g, zero, unc_a, uemb, p, 0xBEEF, graph))
 
     graph = graphs['g4']
     for D in (1, 128):
@@ -153,8 +168,13 @@ def main():
     build.build(verbose=False)
     from disco_diffdock_amd.tensor_layers import _shape_context
     d = digests(_shape_context(0), torch.device('cuda:0'))
+    earlier = []      # where the file was generated before: kept, oldest first
+    if os.path.exists(PATH):
+        with open(PATH) as f:
+            old = json.load(f)
+        earlier = old.get('earlier', []) + [{k: old[k] for k in ('generated_at_commit', 'hip')}]
     with open(PATH, 'w') as f:
-        json.dump({'generated_at_commit': a.commit, 'hip': torch.version.hip, 'sha256': d}, f, indent=1, sort_keys=True)
+        json.dump({'generated_at_commit': a.commit, 'hip': torch.version.hip, 'earlier': earlier, 'sha256': d}, f, indent=1, sort_keys=True)
         f.write('\n')
     print(f'{PATH}: {len(d)} digests')
 
