@@ -24,6 +24,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "k_node.h"
 #include "model.h"
 
 namespace ddk {
@@ -669,8 +670,7 @@ __global__ void conf_finalize_kernel(ConfFinalizeArgs A) {
         const uint8_t* nf = A.need[(type == 1 ? 0 : 2) + (s == 2 ? 1 : 0)];
         if (nf[node - (type == 1 ? A.atom0 : A.rec0)]) nd = node;
       }
-      const float m = A.sum3[(nd * 3 + s) * XW + c] / (float)(d > 1 ? d : 1);
-      v += (m - A.bn_mean[g * XW + c]) * A.bn_scale[g * XW + c] + A.bn_bias[g * XW + c];
+      v += node_finalize_value(A.sum3[(nd * 3 + s) * XW + c], d, A.bn_mean[g * XW + c], A.bn_scale[g * XW + c], A.bn_bias[g * XW + c]);
     }
   }
   A.x_out[i] = v;

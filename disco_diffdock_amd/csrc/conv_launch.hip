@@ -5,9 +5,10 @@
 // conv_prepare_device opts every entry in to its dynamic LDS, launch_conv_fused looks one entry up by key and launches it through the stored address -
 // an instantiation cannot be launched without being opted in.  Which key a (layer, launch) pair maps to, and which pairs are refused, is conv_select.
 //
-// Around a launch: conv_setup / conv_one_group (group tables of the explicit-boundary entry points), pad_rows, count_deg, node_finalize (mean, BatchNorm,
-// residual: tensor_layers.py:159-166), node_finalize_pre (the same fused with the next layer's per-node GEMM1 terms, k_node.h) and, in deterministic
-// mode, conv_det_fix behind the launch.
+// Around a launch: conv_setup / conv_one_group (group tables of the explicit-boundary entry points), pad_rows, count_deg, the node stage and, in
+// deterministic mode, conv_det_fix behind the launch.  The node stage is node_finalize (mean, BatchNorm, residual: the last layer and ddk_conv_forward) or
+// node_finalize_pre (the same fused with the next layer's per-node GEMM1 terms); both take their arithmetic from k_node.h and their arguments from one
+// block, NodeFinalizeArgs, which is the front of NodePreArgs (ddk_internal.h).
 #include "k_conv_common.h"
 #include "k_node.h"
 #include "model.h"
@@ -48,11 +49,10 @@ __global__ void count_deg_kernel(const int32_t* src, int64_t E, int32_t* deg) {
   if (i < E) atomicAdd(deg + src[i], 1);
 }
 
-// scatter 'mean' divisor, e3nn BatchNorm (eval) and the residual of tensor_layers.py:159-166:
-//   out = ((sum/max(deg,1) - mean) * scale + bias) + pad(x_in)
-// (clear_sum: every accumulator that is read is zeroed behind the read, so the next layer / forward finds a clean buffer without a
-// hipMemsetAsync of [N, 84] per layer; zero_extra: a second buffer to clear - the shared layer-0 rec-rec rows, read by every sample
-// of layer 0's finalize and therefore cleared one launch later)
+// scatter 'mean' divisor, e3nn BatchNorm (eval) and the residual of tensor_layers.py:159-166, one thread per output element:
+//   out = node_finalize_value(sum, deg, mean, scale, bias) + pad(x_in)
+// The parameters are NodeFinalizeArgs' members (launch_node_finalize), n = its n_lig_total + n_rec_total.  rr0_mask is NodePreArgs' member: the plain kernel
+// gets none (the masked shared rows belong to a layer 0 that is followed by another layer, which the fused kernel finalizes).
 __global__ void node_finalize_kernel(float* sum, const int32_t* deg, const float* x_in, const float* bn_mean,
                                      const float* bn_scale, const float* bn_bias, int64_t n, int dout, int out_stride,
                                      float* out, const float* sum_rr0, int64_t n_lig_total, int n_rec, int clear_sum,
@@ -72,8 +72,7 @@ __global__ void node_finalize_kernel(float* sum, const int32_t* deg, const float
     }
     if (sum_rr0 != nullptr && r >= n_lig_total && !(rr0_mask != nullptr && rr0_mask[r - n_lig_total]))
       sv += sum_rr0[((r - n_lig_total) % n_rec) * XW + c];   // shared layer-0 rec-rec messages
-    v = sv / (float)(d > 1 ? d : 1);
-    v = (v - bn_mean[c]) * bn_scale[c] + bn_bias[c];
+    v = node_finalize_value(sv, d, bn_mean[c], bn_scale[c], bn_bias[c]);
   }
   if (x_in != nullptr && c < XW) v += x_in[r * XW + c];
   out[i] = v;
@@ -120,15 +119,14 @@ hipError_t launch_count_deg(const int32_t* src, int64_t E, int32_t* deg, hipStre
   return hipGetLastError();
 }
 
-hipError_t launch_node_finalize(float* sum, const int32_t* deg, const float* x_in, const float* bn_mean,
-                                const float* bn_scale, const float* bn_bias, int64_t n, int dout, int out_stride,
-                                float* out, hipStream_t s, const float* sum_rr0, int64_t n_lig_total, int n_rec, int clear_sum,
-                                float* zero_extra, int64_t n_extra, int n_slots, const uint8_t* rr0_mask) {
-  int64_t tot = n * out_stride;
-  if (zero_extra != nullptr && n_extra > tot) tot = n_extra;
+hipError_t launch_node_finalize(const NodeFinalizeArgs& a, hipStream_t s) {
+  const int64_t n = (int64_t)a.n_lig_total + a.n_rec_total;
+  int64_t tot = n * a.out_stride;
+  if (a.zero_extra != nullptr && a.n_extra > tot) tot = a.n_extra;
   if (tot == 0) return hipSuccess;
-  hipLaunchKernelGGL(node_finalize_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, sum, deg, x_in, bn_mean,
-                     bn_scale, bn_bias, n, dout, out_stride, out, sum_rr0, n_lig_total, n_rec, clear_sum, zero_extra, n_extra, n_slots, rr0_mask);
+  hipLaunchKernelGGL(node_finalize_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, a.sum, a.deg, a.x_in, a.bn_mean, a.bn_scale, a.bn_bias, n,
+                     a.dout, a.out_stride, a.x_out, a.sum_rr0, (int64_t)a.n_lig_total, a.n_rec, a.clear_sum, a.zero_extra, a.n_extra, a.n_slots,
+                     static_cast<const uint8_t*>(nullptr));
   return hipGetLastError();
 }
 

@@ -782,7 +782,7 @@ int ddk_conv_forward(ddk_ctx* ctx, int32_t layer, const float* x, int64_t N, con
   if (rc) return rc;
   if (!go || go[0] != 0 || go[1] < go[0] || go[2] < go[1] || go[3] < go[2] || go[4] < go[3])
     return fail(ctx, DDK_ERR_INVALID, "group_offsets must be a non-decreasing prefix starting at 0");
-  if (go[4] >= (int64_t)1 << 31 || N * XW >= (int64_t)1 << 40) return fail(ctx, DDK_ERR_INVALID, "graph too large");
+  if (go[4] >= (int64_t)1 << 31 || N >= (int64_t)1 << 31) return fail(ctx, DDK_ERR_INVALID, "graph too large");      // (edge_src holds int32 node ids)
   hipStream_t s = (hipStream_t)stream;
   const ConvLayerDev& L = ctx->conv[layer];
   if (!L.has_weights) return fail(ctx, DDK_ERR_STATE, "conv layer has no weights loaded");
@@ -806,16 +806,13 @@ int ddk_conv_forward(ddk_ctx* ctx, int32_t layer, const float* x, int64_t N, con
     }
     CK(launch_conv_fused(L, a, ctx->n_cu, s), "conv_fused");
   }
-  if (aa) {
-    CK(launch_node_finalize(ws.sum, ws.deg, nullptr, L.bn_mean + conv_k * XW, L.bn_scale + conv_k * XW, L.bn_bias + conv_k * XW, N, L.dout, L.dout, out, s),
-       "node_finalize");
-    return DDK_OK;
-  }
-  // with no edges the reference returns zeros + residual (tensor_layers.py:149-151): BatchNorm is skipped
-  if (E > 0)
-    CK(launch_node_finalize(ws.sum, ws.deg, ws.xpad, L.bn_mean, L.bn_scale, L.bn_bias, N, L.dout, L.dout, out, s), "node_finalize");
-  else
-    CK(launch_node_finalize(ws.sum, ws.deg, ws.xpad, nullptr, nullptr, nullptr, N, 0, L.dout, out, s), "node_finalize");
+  // the node stage on rows of dout floats (ws.sum was zeroed above: nothing is cleared behind the read)
+  NodeFinalizeArgs FA = {};
+  FA.sum = ws.sum; FA.deg = ws.deg; FA.n_lig_total = (int)N; FA.out_stride = L.dout; FA.x_out = out;
+  FA.x_in = aa ? nullptr : ws.xpad;      // one conv of an all-atom layer: no residual, its own BatchNorm (conv_k = 0 elsewhere)
+  // with no edges the reference returns zeros + residual (tensor_layers.py:149-151): BatchNorm is skipped, dout stays 0
+  if (aa || E > 0) { FA.bn_mean = L.bn_mean + conv_k * XW; FA.bn_scale = L.bn_scale + conv_k * XW; FA.bn_bias = L.bn_bias + conv_k * XW; FA.dout = L.dout; }
+  CK(launch_node_finalize(FA, s), "node_finalize");
   return DDK_OK;
 }
 

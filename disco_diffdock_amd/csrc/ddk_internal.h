@@ -308,10 +308,26 @@ hipError_t launch_conv_setup(int32_t* tile_info, const int64_t* group_offsets_ho
 hipError_t launch_conv_one_group(int32_t* gt, int n_groups, int k, int64_t E, hipStream_t s);
 hipError_t launch_pad_rows(const float* x, int64_t n, int din, float* xpad, hipStream_t s);
 hipError_t launch_count_deg(const int32_t* src, int64_t E, int32_t* deg, hipStream_t s);
+// The node stage behind a conv launch (k_node.h): x_out = ((sum / max(deg, 1) - mean) * scale + bias) + pad(x_in) on rows [0, n_lig_total + n_rec_total).
+// launch_node_finalize takes this block; it is also the front of NodePreArgs, whose kernels read it as one kernel argument: the members keep the order and
+// the offsets that argument has always had (out_stride and clear_sum, which only the plain kernel reads, sit where it had padding).
+struct NodeFinalizeArgs {
+  float* sum;                    // [N, n_slots, XW] accumulators, added in slot order (deterministic mode: one per (node, receiving group))
+  const int32_t* deg;            // [N]
+  const float* x_in;             // [N, XW] or null: no residual
+  const float *bn_mean, *bn_scale, *bn_bias;      // [XW]; not read when dout == 0
+  int dout;                      // columns below dout get the finalize value; 0: the residual alone (a layer without edges skips BatchNorm)
+  int out_stride = XW;           // floats per row of x_out (plain kernel; the fused kernels write XW)
+  float* x_out;
+  const float* sum_rr0 = nullptr;      // [n_rec, XW] layer 0's rec-rec messages shared by all samples: added to the rows from n_lig_total on, or null
+  int n_lig_total, n_rec_total = 0, n_rec = 1;
+  int clear_sum = 0;             // plain kernel: zero every accumulator behind its read (the fused kernels always do), so that the next forward needs no memset
+  float* zero_extra = nullptr; int64_t n_extra = 0;      // a second buffer to clear: the shared rows, read by every sample of layer 0's finalize, one launch later
+  int n_slots = 1;
+};
+hipError_t launch_node_finalize(const NodeFinalizeArgs& a, hipStream_t s);
 // node_finalize of layer l fused with the node terms of layer l+1's GEMM1 (x_in == null, sum == null: the node terms of `x_out` alone)
-struct NodePreArgs {
-  float* sum; const int32_t* deg; const float* x_in; const float* bn_mean; const float* bn_scale; const float* bn_bias;
-  int dout; float* x_out; const float* sum_rr0; int n_lig_total, n_rec_total, n_rec; float* zero_extra; int64_t n_extra; int n_slots;
+struct NodePreArgs : NodeFinalizeArgs {
   const float* wn; const float* bnp; float* pre;
   int lig_roles, rec_roles;                  // bit r: role slot r (ConvLayerDev::wn) is needed by the layer the terms are for
   const uint8_t* rr0_mask = nullptr;         // [n_rec_total] 1: this residue row takes no shared layer-0 rec-rec row (its messages came per sample)
@@ -319,11 +335,6 @@ struct NodePreArgs {
 };
 struct NodeEmbedArgs;      // model.h
 hipError_t launch_node_finalize_pre(const NodePreArgs& a, bool finalize, hipStream_t s, const NodeEmbedArgs* embed = nullptr);      // embed != null (finalize false): the node embedding first
-hipError_t launch_node_finalize(float* sum, const int32_t* deg, const float* x_in /*[N,XW] or null*/,
-                                const float* bn_mean, const float* bn_scale, const float* bn_bias, int64_t n, int dout,
-                                int out_stride, float* out, hipStream_t s, const float* sum_rr0 = nullptr,
-                                int64_t n_lig_total = 0, int n_rec = 1, int clear_sum = 0, float* zero_extra = nullptr,
-                                int64_t n_extra = 0, int n_slots = 1, const uint8_t* rr0_mask = nullptr);
 // k_tp.hip
 hipError_t launch_tp_forward(const ConvLayerDev& L, const float* x_dst, const float* sh, const float* w, int64_t E,
                              float* out, hipStream_t s);

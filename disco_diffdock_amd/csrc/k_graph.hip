@@ -677,30 +677,6 @@ __global__ __launch_bounds__(PRE_W) void edge_features_node_kernel(EdgeFeatArgs 
   if (threadIdx.x < 256) edge_features_body(A, (int)blockIdx.x - node_blocks, (int)threadIdx.x);
 }
 
-// node embeddings: static part (categorical embeddings, ESM projection, bias) + the per-step sigma part
-// (AtomEncoder, models/layers.py:140-149), written zero-padded to XW floats per node
-__global__ void node_embed_kernel(NodeEmbedArgs A) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t n_l = (int64_t)A.B * A.n_lig, n = n_l + (int64_t)A.B * A.n_rec;
-  if (i >= n * XW) return;
-  const int64_t node = i / XW;
-  const int c = (int)(i % XW);
-  float v = 0.0f;
-  if (c < NS) {
-    const bool lig = node < n_l;
-    if (lig) v = A.lig_static[(node % A.n_lig) * NS + c] + A.sp.lig_node_sig[c];
-    else v = A.rec_static[((node - n_l) % A.n_rec) * NS + c] + A.sp.rec_node_sig[c];
-    if (A.latent_dim > 0) {   // latent columns of the AtomEncoder Linear + unconditional embedding (score_model.py:211-212)
-      const float* lat = lig ? A.lig_latent + node * A.latent_dim : A.rec_latent + (node - n_l) * A.latent_dim;
-      const float* w = (lig ? A.lig_w_lat : A.rec_w_lat) + c * A.latent_dim;
-      for (int j = 0; j < A.latent_dim; ++j) v += w[j] * lat[j];
-      const float* u = lig ? A.lig_unc : A.rec_unc;
-      if (u != nullptr) v += A.unconditional * u[c];
-    }
-  }
-  A.x[i] = v;
-}
-
 // Static per-complex precompute on the upload stream (ddk_complex_create): the receptor's node embedding without its sigma columns,
 //   out[j] = W[:, :ns] . table[residue_j] + W[:, ns:ns+lm] . lm_features_j + b     (AtomEncoder, models/layers.py:140-149; 1336-wide at lm = 1280)
 // with fp64 accumulators, rounded to fp32 once.  One workgroup per residue: 10 K slices x 24 outputs (round 3 ran the 1304-long sum as ONE
@@ -888,12 +864,6 @@ hipError_t launch_edge_features_node(const EdgeFeatArgs& A, int64_t edge_cap, co
   const unsigned blocks = (unsigned)((edge_cap + 255) / 256 + 5);
   const int nb = node_pre_tiles(P);
   hipLaunchKernelGGL(edge_features_node_kernel, dim3(blocks + nb), dim3(PRE_W), 0, s, A, P, E, nb);
-  return hipGetLastError();
-}
-
-hipError_t launch_node_embed(const NodeEmbedArgs& a, hipStream_t s) {
-  const int64_t tot = (int64_t)a.B * (a.n_lig + a.n_rec) * XW;
-  hipLaunchKernelGGL(node_embed_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

@@ -1,10 +1,19 @@
-// node_finalize_pre: the body shared by k_conv.hip's kernels (one launch per conv layer) and k_graph.hip's fused edge-feature + node-embedding launch
-// (round 6: the node embedding and layer 0's node terms depend on the diffusion time only, so they ride beside the edge features instead of behind them).
+// The node stage between two conv launches, each formula stated once.
+//   node_finalize_value       scatter-mean divisor + e3nn BatchNorm (eval) of one accumulator sum: node_finalize_kernel (conv_launch.hip, scalar),
+//                             node_finalize_pre_body<1> (16-B words) and conf_finalize_kernel (conf.hip, three accumulator slots per node).  Each caller keeps its own
+//                             order of the additions around it: the score model adds the residual last, the confidence model accumulates onto x_in slot by slot.
+//   node_finalize_pre_body    <1>: finalize, <2>: the node embedding (its only statement), then the node terms of the next conv's GEMM1.  The body of
+//                             conv_launch.hip's node_finalize_pre_kernel (one launch per layer) and of the node blocks of k_graph.hip's edge_features_node_kernel.
 #pragma once
 #include "k_conv_common.h"
 #include "model.h"
 
 namespace ddk {
+
+// scatter 'mean' divisor and e3nn BatchNorm (eval) of tensor_layers.py:159-166: (sum / max(deg, 1) - mean) * scale + bias
+__device__ __forceinline__ float node_finalize_value(float sum, int deg, float mean, float scale, float bias) {
+  return (sum / (float)(deg > 1 ? deg : 1) - mean) * scale + bias;
+}
 
 // node_finalize of one layer (FINALIZE) + the per-node terms of the NEXT layer's GEMM1 (ConvLayerDev::wn): one workgroup = PRE_TILE nodes
 // of one node type, thread t = (role slot t / 72, hidden position t % 72) with its 24 weights in registers; the node scalars are read
@@ -14,8 +23,8 @@ namespace ddk {
 #define PRE_TILE_N 16      // nodes per workgroup: 16 -> 10.2 us, 32 -> 12.5 us, 64 -> 17.9 us, 8 -> 9.7 us per launch at 13 200 nodes (the phase-2 loop is a serial chain per thread)
 #endif
 constexpr int PRE_TILE = PRE_TILE_N;
-// MODE 0: the node terms of the rows of x_out; 1: node_finalize of a layer first; 2: the node embedding first (node_embed_kernel's arithmetic: layer 0's
-// terms without a launch of their own between the embedding and the first conv)
+// MODE 0: the node terms of the rows of x_out; 1: node_finalize of a layer first; 2: the node embedding first (layer 0's terms without a launch of their
+// own between the embedding and the first conv)
 template <int MODE>
 __device__ __forceinline__ void node_finalize_pre_body(const NodePreArgs& A, const NodeEmbedArgs& E, const int blk, const int nblk) {
   constexpr bool FINALIZE = MODE == 1;
@@ -61,12 +70,11 @@ __device__ __forceinline__ void node_finalize_pre_body(const NodePreArgs& A, con
       float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
       if (c < A.dout) {
         const int d = A.deg[r];
-        const float dd = (float)(d > 1 ? d : 1);
         float sv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         for (int sl = 0; sl < A.n_slots; ++sl) {
           float4* ps = reinterpret_cast<float4*>(A.sum + (r * A.n_slots + sl) * XW + c);
           const float4 t = *ps;
-          *ps = make_float4(0.0f, 0.0f, 0.0f, 0.0f);       // every accumulator that is read is cleared behind the read (see node_finalize_kernel)
+          *ps = make_float4(0.0f, 0.0f, 0.0f, 0.0f);       // every accumulator that is read is cleared behind the read (NodeFinalizeArgs::clear_sum)
           sv[0] += t.x; sv[1] += t.y; sv[2] += t.z; sv[3] += t.w;
         }
         if (A.sum_rr0 != nullptr && !lig && !(A.rr0_mask != nullptr && A.rr0_mask[r - A.n_lig_total])) {
@@ -77,14 +85,15 @@ __device__ __forceinline__ void node_finalize_pre_body(const NodePreArgs& A, con
         const float m4[4] = {bm.x, bm.y, bm.z, bm.w}, s4[4] = {bs.x, bs.y, bs.z, bs.w}, b4[4] = {bb.x, bb.y, bb.z, bb.w};
 #pragma unroll
         for (int k = 0; k < 4; ++k)
-          if (c + k < A.dout) v[k] = (sv[k] / dd - m4[k]) * s4[k] + b4[k];
+          if (c + k < A.dout) v[k] = node_finalize_value(sv[k], d, m4[k], s4[k], b4[k]);
       }
       const float4 o = make_float4(v[0] + xin.x, v[1] + xin.y, v[2] + xin.z, v[3] + xin.w);
       *reinterpret_cast<float4*>(A.x_out + r * XW + c) = o;
       if (c < NS) *reinterpret_cast<float4*>(&xs[n][c]) = o;
     }
   } else if (MODE == 2) {
-    // AtomEncoder's static part + the per-step sigma part (+ latent columns), zero padded to XW (k_graph.hip: node_embed_kernel)
+    // the node embedding, zero padded to XW: AtomEncoder's static part (categorical embeddings, ESM projection, bias: models/layers.py:140-149) + the per-step
+    // sigma part + the latent columns of its Linear and the unconditional embedding (score_model.py:211-212).  This is its only statement
     constexpr int XW4 = XW / 4;
     for (int idx = tid; idx < cnt * XW4; idx += PRE_W) {
       const int n = idx / XW4, c = 4 * (idx - n * XW4);

@@ -45,6 +45,17 @@ enum InfoSlot : int {
 enum GroupTable : int { TAB_ALL = 0, TAB_C = 1, TAB_B = 2, TAB_A = 3, TAB_SHARED = 4, N_TAB = 5 };
 constexpr int CNT_STRIDE = 6;   // counts / offs per sample: ll radius edges, lr edges, rec-rec edges of level A, B, C, (spare)
 
+// Deterministic mode: the layout of the two buffers a complex holds for it (Bm = max_batch; ddk_complex_create allocates, score_forward_impl hands out).
+//   part     partial rows of the runs that straddle 32-edge tiles: CONV_WAVES x 2 rows of XW floats per 256-edge block of a launch, one block more per sample-aligned
+//            range (7 per sample at most).  The two head launches run side by side: final_conv on the front of the buffer, tor_bond_conv behind B + 2 blocks
+//   det_rng  sample-aligned ranges (det_ranges_kernel: 4 ints each, at most 7 * Bm + 1 of them, 8 ints of tail) of the current conv layer | of the final_conv head
+constexpr int64_t det_part_floats(int64_t edge_cap, int64_t Bm) { return (edge_cap / CONV_BLOCK_EDGES + 16 + 7 * Bm + 8) * CONV_WAVES * 2 * XW; }
+constexpr int64_t det_part_head_offset(int64_t B) { return (B + 2) * CONV_WAVES * 2 * XW; }      // tor_bond_conv's part of `part`, for a batch of B <= Bm
+constexpr int64_t det_rng_head_offset(int64_t Bm) { return 4 * (7 * Bm + 1) + 8; }
+constexpr int64_t det_rng_ints(int64_t Bm) { return 2 * det_rng_head_offset(Bm); }
+// the second region starts inside its buffer: 24 + 7 Bm blocks against B + 2 <= Bm + 2 at any edge capacity, and half of det_rng by construction
+static_assert(det_part_head_offset(1) < det_part_floats(0, 1) && det_rng_head_offset(1) < det_rng_ints(1), "deterministic buffers: the heads' regions lie inside");
+
 // Everything that depends only on the diffusion time of a forward (computed on the HOST from t, which the
 // sampler knows without reading the device: utils/sampling.py:106-113, diffusion_utils.py:12-16,58-69).
 struct StepParams {
@@ -399,7 +410,6 @@ struct NodeEmbedArgs {
   const float* lig_static; const float* rec_static; StepParams sp; int B, n_lig, n_rec; float* x;
   const float *lig_latent, *rec_latent, *lig_w_lat, *rec_w_lat, *lig_unc, *rec_unc; float unconditional; int latent_dim;
 };
-hipError_t launch_node_embed(const NodeEmbedArgs& a, hipStream_t s);
 // static per-complex precompute on the device (ddk_complex_create, upload stream)
 struct RecStaticArgs { const float* rec_x; int n_rec, feat_dim, lm; const float *rec_table, *w_emb, *w_lm_t, *b; float* out; };
 hipError_t launch_complex_static(const RecStaticArgs& R, const int32_t* rr_src, const int32_t* rr_dst, const float* rec_pos, int E, const EdgeMlpDev& m,

@@ -463,7 +463,6 @@ static int score_forward_impl(ddk_ctx* ctx, ddk_complex* cx, int B, const float*
   const ddk_config& c = ctx->cfg;
   Model* M = (Model*)ctx->model;
   const int n_lig = cx->n_lig, n_rec = cx->n_rec;
-  const int64_t N = (int64_t)B * (n_lig + n_rec);
   // layer 0: the receptor's node features and rec-rec edge features are the same for every sample of the batch
   // (no latents) -> evaluate the rec-rec messages once, exact in real arithmetic
   // Latent-conditioned (DisCo) model: the latents are one-hot at a few nodes per sample, so the shared pass (on sample 0's rows) is right
@@ -507,20 +506,19 @@ static int score_forward_impl(ddk_ctx* ctx, ddk_complex* cx, int B, const float*
   NE_.lig_static = cx->lig_node_static; NE_.rec_static = cx->rec_node_static; NE_.sp = sp; NE_.B = B; NE_.n_lig = n_lig; NE_.n_rec = n_rec;
   NE_.x = xin; NE_.lig_latent = cx->lig_latent; NE_.rec_latent = cx->rec_latent; NE_.lig_w_lat = M->dev.lig_w_lat; NE_.rec_w_lat = M->dev.rec_w_lat;
   NE_.lig_unc = M->dev.lig_node_unc; NE_.rec_unc = M->dev.rec_node_unc; NE_.unconditional = cx->unconditional; NE_.latent_dim = c.latent_dim;
-  // per-node terms of layer 0's GEMM1 (ConvLayerDev::wn): one launch with the node embedding itself
-  const bool split = ctx->conv[0].wn != nullptr && cx->pre != nullptr;
+  // Every conv layer starts GEMM1 from per-node terms (ConvLayerDev::wn, cx->pre).  conv_pack.hip uploads wn with every score-model layer that has weights,
+  // whatever the conv_kernel, and ddk_complex_create allocates pre for every complex of a context with a model: what is left is a model without conv
+  // weights or a complex created before its context's model was loaded, neither of which can run a forward
+  if (ctx->conv[0].wn == nullptr || cx->pre == nullptr)
+    return fail(ctx, DDK_ERR_STATE, "score forward: the conv layers have no weights, or the complex was created before the score model was loaded");
   // the two-limb f16 kernel (conv_kernel = 0) forms the SENDER's term inside its GEMM1: its contexts need the two receiver roles only (slots 0, 1)
-  const bool recv_only = split && ctx->conv[0].sender_in_gemm1;
-  const int role_mask = recv_only ? 0x3 : 0xF;
-  if (split) {
+  const int role_mask = ctx->conv[0].sender_in_gemm1 ? 0x3 : 0xF;
+  {
     NodePreArgs PA = {};
     PA.x_out = xin; PA.n_lig_total = B * n_lig; PA.n_rec_total = B * n_rec; PA.n_rec = n_rec;
-    PA.wn = ctx->conv[0].wn; PA.bnp = ctx->conv[0].bnp; PA.pre = cx->pre; PA.n_slots = 1; PA.lig_roles = role_mask; PA.rec_roles = role_mask;
+    PA.wn = ctx->conv[0].wn; PA.bnp = ctx->conv[0].bnp; PA.pre = cx->pre; PA.lig_roles = role_mask; PA.rec_roles = role_mask;
     // ONE launch: the edge features and, beside them, the node embedding + layer 0's node terms (they depend on t and the latents only)
     CK(launch_edge_features_node(F, feat_cap, PA, NE_, s), "edge features + node embed + node_pre");
-  } else {
-    CK(launch_edge_features(F, feat_cap, s), "edge features");
-    CK(launch_node_embed(NE_, s), "node embed");
   }
   // accumulators: node_finalize zeroes what it reads, so a forward that ran to its end leaves them clean for the next one
   if (!cx->sum_clean) {
@@ -537,7 +535,7 @@ static int score_forward_impl(ddk_ctx* ctx, ddk_complex* cx, int B, const float*
     ConvLaunch a;
     a.x = xin; a.src = cx->e_src; a.dst = cx->e_dst; a.edge_attr = cx->e_emb; a.sh = cx->e_sh; a.sum = cx->sum;
     a.tile_info = cx->info; a.counter = cx->info + I_CNT + (l % 8); a.gather = 1;
-    a.pre = split ? cx->pre : nullptr;
+    a.pre = cx->pre;
     // which rec-rec messages this layer evaluates: layer 0 the shared copy (de-duplication); layers L-2, L-3, L-4 only those received by
     // the residues inside the backward receptive field of the heads (levels A, B, C of k_graph.hip); the last layer none (and no
     // rec->lig... group 3 either): only ligand rows are read downstream unless the caller asked for the receptor rows
@@ -581,13 +579,15 @@ static int score_forward_impl(ddk_ctx* ctx, ddk_complex* cx, int B, const float*
       ctx->prof_recs.push_back(pr);
     }
     const bool clear_rr0 = rr0_dirty && !shared0;     // one launch after the layer whose finalize read the shared rows
-    if (split && l + 1 < NL) {     // finalize fused with the node terms of the next layer's GEMM1
-      NodePreArgs PA = {};
-      PA.sum = cx->sum; PA.deg = cx->deg; PA.x_in = xin; PA.bn_mean = L.bn_mean; PA.bn_scale = L.bn_scale; PA.bn_bias = L.bn_bias;
-      PA.dout = L.dout; PA.x_out = xout; PA.sum_rr0 = shared0 ? cx->sum_rr0 : nullptr; PA.n_lig_total = B * n_lig; PA.n_rec_total = B * n_rec;
+    // the node stage behind the launch.  What both of its forms read: the last layer keeps its receptor rows only where the caller asked for them
+    NodePreArgs PA = {};
+    PA.sum = cx->sum; PA.deg = cx->deg; PA.x_in = xin; PA.bn_mean = L.bn_mean; PA.bn_scale = L.bn_scale; PA.bn_bias = L.bn_bias;
+    PA.dout = L.dout; PA.x_out = xout; PA.sum_rr0 = shared0 ? cx->sum_rr0 : nullptr;
+    PA.n_lig_total = B * n_lig; PA.n_rec_total = lig_only ? 0 : B * n_rec; PA.n_rec = n_rec; PA.clear_sum = 1;
+    PA.zero_extra = clear_rr0 ? cx->sum_rr0 : nullptr; PA.n_extra = clear_rr0 ? (int64_t)n_rec * XW : 0; PA.n_slots = c.deterministic ? 2 : 1;
+    if (l + 1 < NL) {     // finalize fused with the node terms of the next layer's GEMM1
       PA.rr0_mask = (shared0 && patched) ? cx->rr_mask : nullptr;
-      PA.n_rec = n_rec; PA.zero_extra = clear_rr0 ? cx->sum_rr0 : nullptr; PA.n_extra = clear_rr0 ? (int64_t)n_rec * XW : 0;
-      PA.wn = ctx->conv[l + 1].wn; PA.bnp = ctx->conv[l + 1].bnp; PA.pre = cx->pre; PA.n_slots = c.deterministic ? 2 : 1;
+      PA.wn = ctx->conv[l + 1].wn; PA.bnp = ctx->conv[l + 1].bnp; PA.pre = cx->pre;
       // rows nothing downstream reads (the same receptive-field argument as for the rec-rec messages) are neither finalised nor given node terms
       // the last layer evaluates groups 0 and 1 only (unless the receptor rows were asked for): ligand atoms receive in both and send in group 0,
       // residues only send in group 1 -> 3 of 4 resp. 1 of 4 role slots
@@ -595,10 +595,9 @@ static int score_forward_impl(ddk_ctx* ctx, ddk_complex* cx, int B, const float*
       PA.lig_roles = (next_lig_only ? 0x7 : 0xF) & role_mask; PA.rec_roles = (next_lig_only ? 0x4 : 0xF) & role_mask;
       PA.levels = prune ? cx->levels : nullptr; PA.max_level = l == NL - 2 ? 0 : (l == NL - 3 ? 1 : (l == NL - 4 ? 2 : 3));
       CK(launch_node_finalize_pre(PA, true, s), "node_finalize_pre");
-    } else
-    CK(launch_node_finalize(cx->sum, cx->deg, xin, L.bn_mean, L.bn_scale, L.bn_bias, lig_only ? (int64_t)B * n_lig : N, L.dout, XW, xout, s,
-                            shared0 ? cx->sum_rr0 : nullptr, (int64_t)B * n_lig, n_rec, 1, clear_rr0 ? cx->sum_rr0 : nullptr,
-                            clear_rr0 ? (int64_t)n_rec * XW : 0, c.deterministic ? 2 : 1, (shared0 && patched) ? cx->rr_mask : nullptr), "node_finalize");
+    } else {
+      CK(launch_node_finalize(PA, s), "node_finalize");
+    }
     if (clear_rr0) rr0_dirty = false;
     float* t = xin; xin = xout; xout = t;
   }
@@ -625,7 +624,7 @@ static int score_forward_impl(ddk_ctx* ctx, ddk_complex* cx, int B, const float*
   // per bond already); built on the caller's stream before the fork
   int32_t* head_rng = nullptr;
   if (c.deterministic) {
-    head_rng = cx->det_rng + (4 * (7 * (size_t)cx->max_batch + 1) + 8);
+    head_rng = cx->det_rng + det_rng_head_offset(cx->max_batch);
     GraphArgs Gd = {};
     Gd.B = B;
     CK(launch_det_ranges(Gd, 6, n_lig, head_rng, s), "deterministic ranges (head)");
@@ -642,7 +641,7 @@ static int score_forward_impl(ddk_ctx* ctx, ddk_complex* cx, int B, const float*
     a.gbeg = cx->info + I_HEAD + (hd == 1 ? 0 : 2); a.gend = a.gbeg + 1;
     if (c.deterministic) {     // (the two head launches run side by side: each its own part of the partial-row buffer)
       const int64_t eh = (int64_t)B * (n_lig + (int64_t)cx->R * BOND_CAP);
-      a.part = cx->part + (hd == 1 ? 0 : ((size_t)B + 2) * CONV_WAVES * 2 * XW); a.edge_bound = eh;
+      a.part = cx->part + (hd == 1 ? 0 : det_part_head_offset(B)); a.edge_bound = eh;
       if (hd == 1) { a.det_rng = head_rng; a.det_nr = B; }
     }
     CK(launch_conv_fused(ctx->head[hd], a, ctx->n_cu, (hd == 1 && torsion) ? ctx->head_stream : s), "conv_fused (head)");
@@ -803,8 +802,8 @@ int ddk_complex_create(ddk_ctx* ctx, const ddk_complex_desc* d, int32_t max_batc
   const int det = c.deterministic ? 1 : 0;
   cx->sum = cx_upload<float>(cx, nullptr, N * XW * (det ? 2 : 1));      // deterministic: one accumulator per (node, receiving group)
   if (det) {      // partial rows of the runs that straddle 32-edge tiles (one block more per sample-aligned range: 7 per sample at most) + the ranges themselves
-    cx->part = cx_upload<float>(cx, nullptr, (cx->edge_cap / CONV_BLOCK_EDGES + 16 + 7 * Bm + 8) * CONV_WAVES * 2 * XW);
-    cx->det_rng = cx_upload<int32_t>(cx, nullptr, 2 * (4 * (7 * Bm + 1) + 8));      // [conv layers | final_conv head]
+    cx->part = cx_upload<float>(cx, nullptr, det_part_floats(cx->edge_cap, Bm));
+    cx->det_rng = cx_upload<int32_t>(cx, nullptr, det_rng_ints(Bm));      // [conv layers | final_conv head]
   }
   cx->sum_rr0 = cx_upload<float>(cx, nullptr, (int64_t)n_rec * XW);
   if (has_model) cx->pre = cx_upload<float>(cx, nullptr, N * PRE_W);
