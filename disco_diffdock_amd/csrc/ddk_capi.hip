@@ -222,11 +222,26 @@ static int check_launchable(ddk_ctx* ctx, int32_t layer) {
 
 // what the six tensor-product entries check first: a context that can launch, and a `layer` that names one of the kernels' shapes: conv layer `layer` of
 // the context (ddk_create admits ns = 24, nv = 6 only), or DDK_TP_NV4 + l, layer l of the ns = 24 / nv = 4 family, which no context holds: its
-// ConvLayerDev is the static shape-only table of k_tp_shape.h.  *L: the layer to launch on.  Asked BEFORE the launch, so that an invalid-value error of
+// ConvLayerDev is the static shape-only table of k_tp_shape.h; or, where `aa_ok` (the radial tensor product and the radial conv), DDK_TP_AA + l, layer l of
+// the all-atom family (e3nn's FullyConnectedTensorProduct with sh_lmax = 2), a shape-only layer too.  *L: the layer to launch on.  Asked BEFORE the launch, so that an invalid-value error of
 // the launch itself is reported as what it is
-static const char* const TP_FAMILIES = "0 .. num_conv_layers - 1 of the context (24x0e [+ 6x1o [+ 6x1e [+ 24x0o]]] -> the next entry) or DDK_TP_NV4 + 0..4 "
-                                       "(24x0e [+ 4x1o [+ 4x1e [+ 24x0o]]] -> the next entry)";
-static int check_tp_launchable(ddk_ctx* ctx, const char* who, int32_t layer, const ConvLayerDev** L) {
+static const char* const TP_FAMILIES = "0 .. num_conv_layers - 1 of the context (24x0e [+ 6x1o [+ 6x1e [+ 24x0o]]] -> the next entry), DDK_TP_NV4 + 0..4 "
+                                       "(24x0e [+ 4x1o [+ 4x1e [+ 24x0o]]] -> the next entry) or, for the radial tensor product and the radial conv, "
+                                       "DDK_TP_AA + 0..4 (the all-atom family: the first family's irreps with sh = 1x0e + 1x1o + 1x2e)";
+static int check_tp_launchable(ddk_ctx* ctx, const char* who, int32_t layer, const ConvLayerDev** L, bool aa_ok = false) {
+  if (tp_is_aa_id(layer)) {
+    int rc = check_launchable(ctx, 0);
+    if (rc) return rc;
+    // the ids name a shape, not a context's layer: a context that holds a conv layer of this index (the all-atom inference context has 45) is refused
+    if (layer < (int)ctx->conv.size())
+      return fail(ctx, DDK_ERR_INVALID, std::string(who) + ": this context has a conv layer " + std::to_string(layer) + ", and the id is DDK_TP_AA + " +
+                  std::to_string(layer - TP_AA) + " of the all-atom family: use a context with at most 16 conv layers for the all-atom shapes");
+    if (!aa_ok)
+      return fail(ctx, DDK_ERR_INVALID, std::string(who) + ": DDK_TP_AA + " + std::to_string(layer - TP_AA) + " names a shape of the all-atom family, which has no "
+                  "per-edge weight form [E, W]: its ops are ddk_rtp_* and ddk_rconv_*");
+    *L = &tp_family_layer(layer);
+    return DDK_OK;
+  }
   if (tp_is_nv4_id(layer)) {
     int rc = check_launchable(ctx, 0);
     if (rc) return rc;
@@ -299,9 +314,10 @@ static int check_conv_graph(ddk_ctx* ctx, const char* who, const RconvGraph& gr,
 
 // the checks the two radial-tensor-product entries share: layer, group table, edge count
 static int rtp_check(ddk_ctx* ctx, const char* who, int32_t layer, const int64_t* go, int32_t n_groups, int64_t E, const ConvLayerDev** L) {
-  int rc = check_tp_launchable(ctx, who, layer, L);
+  int rc = check_tp_launchable(ctx, who, layer, L, true);
   if (rc) return rc;
-  if (layer > 4 && !tp_is_nv4_id(layer)) return fail(ctx, DDK_ERR_INVALID, std::string(who) + ": layer out of range (0..4, or DDK_TP_NV4 + 0..4)");
+  if (layer > 4 && !tp_is_nv4_id(layer) && !tp_is_aa_id(layer))
+    return fail(ctx, DDK_ERR_INVALID, std::string(who) + ": layer out of range (0..4, DDK_TP_NV4 + 0..4, or DDK_TP_AA + 0..4 of the all-atom family)");
   return check_group_table(ctx, who, go, n_groups, E);
 }
 
@@ -323,6 +339,8 @@ int ddk_rtp_backward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const floa
   const ConvLayerDev* L = nullptr;
   int rc = rtp_check(ctx, "ddk_rtp_backward", layer, group_offsets, n_groups, E, &L);
   if (rc) return rc;
+  if (tp_is_aa_id(layer) && grad_sh)
+    return fail(ctx, DDK_ERR_INVALID, "ddk_rtp_backward: grad_sh is not implemented for the all-atom family (DDK_TP_AA ids): pass NULL");
   if (!grad_x && !grad_sh && !grad_h && !grad_w2 && !grad_b2)
     return fail(ctx, DDK_ERR_INVALID, "ddk_rtp_backward: no gradient requested (grad_x, grad_sh, grad_h, grad_w2 and grad_b2 are all null)");
   const bool per_edge = grad_x || grad_sh || grad_h, params = grad_w2 || grad_b2;
@@ -375,6 +393,8 @@ int ddk_rconv_backward(ddk_ctx* ctx, int32_t layer, const float* x_nodes, int64_
   const ConvLayerDev* L = nullptr;
   int rc = rconv_check(ctx, "ddk_rconv_backward", layer, group_offsets, n_groups, E, gr, true, x_nodes, sh, h, workspace, &L);
   if (rc) return rc;
+  if (tp_is_aa_id(layer) && grad_sh)
+    return fail(ctx, DDK_ERR_INVALID, "ddk_rconv_backward: grad_sh is not implemented for the all-atom family (DDK_TP_AA ids): pass NULL");
   if (!grad_x_nodes && !grad_sh && !grad_h && !grad_w2 && !grad_b2)
     return fail(ctx, DDK_ERR_INVALID, "ddk_rconv_backward: no gradient requested (grad_x_nodes, grad_sh, grad_h, grad_w2 and grad_b2 are all null)");
   if (E > 0) {

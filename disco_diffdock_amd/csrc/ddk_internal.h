@@ -183,6 +183,7 @@ struct ConvLayerDev {          // device copies for one TensorProductConvLayer w
   // block shapes of the FasterTensorProduct (tensor_layers.py:58-63), order 0e,1o,1e,0o
   int n_in[4] = {}, n_out[4] = {}, blk_off[4] = {};
   int in_mul[4] = {}, out_mul[4] = {};   // 0e,1o,1e,0o multiplicities of the layer's in/out irreps
+  bool tp_aa = false;          // a shape-only layer of the all-atom family (k_tp_shape.h: ids DDK_TP_AA + l); never set on a context's layer
 };
 
 constexpr int PRE_W = 4 * NE;   // floats of node pre-activations per node: 4 roles x 72 hidden units

@@ -35,6 +35,10 @@
 // node-sorted edge list, one thread per (node, column): the scatter-mean of the forward ([E, Dout] rows over src) and the backward of the gather ([E, Din]
 // rows of grad_x over dst); rtp_node_scale_kernel makes gn = grad_out / max(count, 1) once per node, so that the backward gathers plain rows.  No atomics
 // here either.  The indices, orderings and pointer tables are trusted: Context.conv_graph (Python) builds and range-checks them.
+//
+// THE ALL-ATOM FAMILY (S::AA, k_tp_shape.h: the confidence model's conv layers, e3nn's FullyConnectedTensorProduct with sh_lmax = 2).  The same two kernels:
+// sh rows have 9 floats, blocks 1 and 2 end in the rows of the kind RTP_V2 (vector (x) Y2 -> vector), a slot's place in the weight row is e3nn's
+// (S::WROW), and there is no grad_sh.  Everything the family adds stands under `if constexpr (S::AA)`, so the other shapes compile to what they were.
 #include <stdlib.h>
 
 #include "ddk_internal.h"
@@ -82,12 +86,13 @@ __device__ __forceinline__ RtpSlot rtp_slot(int T, int i) {      // slot i of ti
   s.r = 4 * rg + ((i >> 2) & 1) + 2 * (i >> 4);
   s.c = 8 * cg + (i & 3) + 4 * ((i >> 3) & 1);
   s.valid = s.r < Rk && s.c < Ok;
-  s.p = s.valid ? Bk + s.r * Ok + s.c : 0;
+  if constexpr (S::AA) s.p = s.valid ? S::WROW(s.blk, s.r) + s.c : 0;      // e3nn's instruction order: a compile-time table of the shape
+  else s.p = s.valid ? Bk + s.r * Ok + s.c : 0;
   return s;
 }
 
 // what makes row r of block k: the kind of product and where its input sits in the node row
-enum { RTP_SS = 0, RTP_SV = 1, RTP_VS = 2, RTP_VX = 3, RTP_VD = 4, RTP_NONE = 5 };      // scalar s0, scalar (x) v, vector s0, (vector x v)/sqrt2, (vector . v)/sqrt3
+enum { RTP_SS = 0, RTP_SV = 1, RTP_VS = 2, RTP_VX = 3, RTP_VD = 4, RTP_NONE = 5, RTP_V2 = 6 };      // scalar s0, scalar (x) v, vector s0, (vector x v)/sqrt2, (vector . v)/sqrt3; all-atom family: sqrt(3/10) M(Y2) vector
 struct RtpRow { int kind, xoff, xstep; };
 
 template <class S>
@@ -101,10 +106,12 @@ __device__ __forceinline__ RtpRow rtp_row(int k, int r) {
     if (r < A) o = RtpRow{RTP_SV, r, 0};
     else if (r < A + P) o = RtpRow{RTP_VS, XP + 3 * (r - A), 1};
     else if (r < A + P + Q) o = RtpRow{RTP_VX, XQ + 3 * (r - A - P), 1};
+    else if (S::AA && r < A + P + Q + P) o = RtpRow{RTP_V2, XP + 3 * (r - A - P - Q), 1};      // 1o (x) 2e -> 1o
   } else if (k == 2) {
     if (r < P) o = RtpRow{RTP_VX, XP + 3 * r, 1};
     else if (r < P + Q) o = RtpRow{RTP_VS, XQ + 3 * (r - P), 1};
     else if (r < P + Q + C) o = RtpRow{RTP_SV, XC + (r - P - Q), 0};
+    else if (S::AA && r < P + Q + C + Q) o = RtpRow{RTP_V2, XQ + 3 * (r - P - Q - C), 1};      // 1e (x) 2e -> 1e
   } else {
     if (r < Q) o = RtpRow{RTP_VD, XQ + 3 * r, 1};
     else if (r < Q + C) o = RtpRow{RTP_SS, XC + (r - Q), 0};
@@ -129,6 +136,17 @@ __device__ __forceinline__ void rtp_u(int kind, const float* i, float s0, float 
   u[0] *= rs; u[1] *= rs; u[2] *= rs;
 }
 
+// The all-atom family's row kind, vector (x) Y2 -> vector: u = rs sqrt(3/10) M i, with M the symmetric traceless matrix of the five Y2 components
+// y = sh[4..8] (e3nn's order: xz, xy, y^2 - (x^2 + z^2)/2, yz, (z^2 - x^2)/2, each times its normalisation) that w3j(1, 2, 1) defines:
+//   M = [[-y2/sqrt3 - y4, y1, y0], [y1, 2 y2/sqrt3, y3], [y0, y3, -y2/sqrt3 + y4]].
+// M is its own adjoint, so the same product with c = 1 folds a G row into grad_x (rtp_fold_aa)
+__device__ __forceinline__ void rtp_m2(const float* y, const float* i, float c, float* u) {
+  const float d = y[2] * TP_INV_S3;
+  u[0] = ((y[1] * i[1] + y[0] * i[2]) - (d + y[4]) * i[0]) * c;
+  u[1] = ((y[1] * i[0] + y[3] * i[2]) + (d + d) * i[1]) * c;
+  u[2] = ((y[0] * i[0] + y[3] * i[1]) + (y[4] - d) * i[2]) * c;
+}
+
 // the adjoint of rtp_u without rs: a G row (scalar blocks: G[0]) into the edge's grad_x image (stride 32 floats per column) and grad_sh
 __device__ __forceinline__ void rtp_fold(const RtpRow& rk, const float* i, const float* G, float s0, float vx, float vy, float vz, float* gxl, bool want_gx, float* gs) {
   float d0 = 0.f, d1 = 0.f, d2 = 0.f;
@@ -149,6 +167,28 @@ __device__ __forceinline__ void rtp_fold(const RtpRow& rk, const float* i, const
   }
 }
 
+// rtp_u of the all-atom family (y: the edge's Y2 components, rs = sqrt(1 / R_k): with the constants of rtp_u and TP_S3_10 a path's scale is e3nn's
+// sqrt(dim_out / R_k) times the Frobenius-normalised w3j)
+__device__ __forceinline__ void rtp_u_aa(int kind, const float* i, float s0, float vx, float vy, float vz, const float* y, float rs, float* u) {
+  rtp_u(kind, i, s0, vx, vy, vz, rs, u);
+  if (kind == RTP_V2) rtp_m2(y, i, TP_S3_10 * rs, u);
+}
+
+// rtp_fold of the all-atom family: grad_x alone (grad_sh is not implemented for it: poses are data where it trains)
+__device__ __forceinline__ void rtp_fold_aa(const RtpRow& rk, const float* i, const float* G, float s0, float vx, float vy, float vz, const float* y, float* gxl) {
+  float d[3] = {0.f, 0.f, 0.f};
+  if (rk.kind == RTP_SS) { d[0] = s0 * G[0]; }
+  else if (rk.kind == RTP_SV) { d[0] = vx * G[0] + vy * G[1] + vz * G[2]; }
+  else if (rk.kind == RTP_VS) { d[0] = s0 * G[0]; d[1] = s0 * G[1]; d[2] = s0 * G[2]; }
+  else if (rk.kind == RTP_VX) { d[0] = (vy * G[2] - vz * G[1]) * TP_INV_S2; d[1] = (vz * G[0] - vx * G[2]) * TP_INV_S2; d[2] = (vx * G[1] - vy * G[0]) * TP_INV_S2; }
+  else if (rk.kind == RTP_VD) { const float k3 = G[0] * TP_INV_S3; d[0] = vx * k3; d[1] = vy * k3; d[2] = vz * k3; }
+  else if (rk.kind == RTP_V2) { rtp_m2(y, G, TP_S3_10, d); }
+  if (rk.kind != RTP_NONE) {
+    gxl[32 * rk.xoff] += d[0];
+    if (rk.xstep) { gxl[32 * (rk.xoff + 1)] += d[1]; gxl[32 * (rk.xoff + 2)] += d[2]; }
+  }
+}
+
 // ---- forward and backward pass 2 ---------------------------------------------------------------------------------------------------------------------------
 // The compile-time flag IDX of the edge and parameter kernels, carried by the shape type so that the kernels of the plain shapes keep their symbols and
 // their code: with S = RtpIdx<shape>, x and g are NODE tables and edge e reads rows a.xi[e] / a.gi[e] of them (the radial conv); sh, h and every output row
@@ -157,8 +197,11 @@ template <class S> struct RtpIdx : S {};
 template <class S> struct RtpIsIdx { static constexpr bool value = false; };
 template <class S> struct RtpIsIdx<RtpIdx<S>> { static constexpr bool value = true; };
 
+template <bool AA> struct RtpY2 {};                         // the lane's Y2 components: the all-atom family alone holds them
+template <> struct RtpY2<true> { float y2[5]; };
+
 template <class S, bool FWD, bool NX, bool NH>
-struct RtpEdge {
+struct RtpEdge : RtpY2<S::AA> {
   using TT = RtpT<S>;
   static constexpr bool IDX = RtpIsIdx<S>::value;
   static constexpr bool G1 = FWD || NX;      // GEMM 1 (w_tile) runs
@@ -238,7 +281,8 @@ struct RtpEdge {
         rk[m] = r < Rk ? rtp_row<S>(K, r) : RtpRow{RTP_NONE, 0, 0};
 #pragma unroll
         for (int k = 0; k < 3; ++k) in[m][k] = (ev && rk[m].kind != RTP_NONE) ? a.x[xrow() * S::DIN + rk[m].xoff + k * rk[m].xstep] : 0.f;
-        if constexpr (FWD || NH) rtp_u(rk[m].kind, in[m], s0, vx, vy, vz, rs, u[m]);
+        if constexpr (S::AA) { if constexpr (FWD || NH) rtp_u_aa(rk[m].kind, in[m], s0, vx, vy, vz, this->y2, rs, u[m]); }
+        else if constexpr (FWD || NH) rtp_u(rk[m].kind, in[m], s0, vx, vy, vz, rs, u[m]);
         G[m][0] = 0.f; G[m][1] = 0.f; G[m][2] = 0.f;
       }
 #pragma unroll
@@ -300,7 +344,8 @@ struct RtpEdge {
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
           G[m][0] *= rs; G[m][1] *= rs; G[m][2] *= rs;
-          rtp_fold(rk[m], in[m], G[m], s0, vx, vy, vz, gxl, a.gx != nullptr, gs);
+          if constexpr (S::AA) rtp_fold_aa(rk[m], in[m], G[m], s0, vx, vy, vz, this->y2, gxl);
+          else rtp_fold(rk[m], in[m], G[m], s0, vx, vy, vz, gxl, a.gx != nullptr, gs);
         }
       }
     }
@@ -345,7 +390,11 @@ struct RtpEdge {
       }
     }
     s0 = 0.f; vx = 0.f; vy = 0.f; vz = 0.f;
-    if (ev) {
+    if constexpr (S::AA) {      // rows of 9 floats: [Y0 | Y1 | Y2]
+#pragma unroll
+      for (int k = 0; k < 5; ++k) this->y2[k] = ev ? a.sh[e * 9 + 4 + k] : 0.f;
+      if (ev) { s0 = a.sh[e * 9]; vx = a.sh[e * 9 + 1]; vy = a.sh[e * 9 + 2]; vz = a.sh[e * 9 + 3]; }
+    } else if (ev) {
       const tp_f4 v = *reinterpret_cast<const tp_f4*>(a.sh + e * 4);
       s0 = v.x; vx = v.y; vy = v.z; vz = v.w;
     }
@@ -432,6 +481,11 @@ __global__ __launch_bounds__(256) void rtp_param_kernel(RtpArgs a) {
   __shared__ float hs[32 * RTP_H];
   __shared__ float4 shs4[32];
   float* shs = reinterpret_cast<float*>(shs4);
+  [[maybe_unused]] float* shy = nullptr;      // the all-atom family: the staged edges' Y2 components, [32][5] (shs4 keeps [Y0 | Y1])
+  if constexpr (S::AA) {
+    __shared__ float shy_buf[32 * 5];
+    shy = shy_buf;
+  }
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, hh = lane >> 5;
   const int chunk = blockIdx.x % NCH;
   const int64_t slice = blockIdx.x / NCH;
@@ -486,7 +540,13 @@ __global__ __launch_bounds__(256) void rtp_param_kernel(RtpArgs a) {
       for (int f = tid; f < 32 * S::DOUT; f += 256) gsm[f] = f < n_e * S::DOUT ? a.g[eb * S::DOUT + f] : 0.f;
     }
     for (int f = tid; f < 32 * RTP_H; f += 256) hs[f] = f < n_e * RTP_H ? a.h[eb * RTP_H + f] : 0.f;
-    if (tid < 128) shs[tid] = tid < n_e * 4 ? a.sh[eb * 4 + tid] : 0.f;
+    if constexpr (S::AA) {
+      for (int f = tid; f < 32 * 9; f += 256) {
+        const int r = f / 9, k = f - 9 * r;
+        const float v = r < n_e ? a.sh[eb * 9 + f] : 0.f;
+        if (k < 4) shs[4 * r + k] = v; else shy[5 * r + k - 4] = v;
+      }
+    } else if (tid < 128) shs[tid] = tid < n_e * 4 ? a.sh[eb * 4 + tid] : 0.f;
     __syncthreads();
     if (active) {
 #pragma unroll 4
@@ -496,7 +556,8 @@ __global__ __launch_bounds__(256) void rtp_param_kernel(RtpArgs a) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) in[k] = xs[el * S::DIN + rk.xoff + k * rk.xstep];
         const float4 sv = shs4[el];
-        rtp_u(rk.kind, in, sv.x, sv.y, sv.z, sv.w, rs, u);
+        if constexpr (S::AA) rtp_u_aa(rk.kind, in, sv.x, sv.y, sv.z, sv.w, shy + 5 * el, rs, u);
+        else rtp_u(rk.kind, in, sv.x, sv.y, sv.z, sv.w, rs, u);
         const float g0 = gsm[el * S::DOUT + goff], g1 = gsm[el * S::DOUT + goff + gstep], g2 = gsm[el * S::DOUT + goff + 2 * gstep];
         const float gw = vec ? u[0] * g0 + u[1] * g1 + u[2] * g2 : u[0] * g0;
 #pragma unroll
@@ -564,6 +625,10 @@ static hipError_t rtp_launch(const RtpArgs& a, bool fwd, hipStream_t s) {
 }
 
 int64_t rtp_backward_workspace(int32_t layer, int64_t E, int32_t n_groups) {
+  if (tp_is_aa_id(layer)) {
+    if (E < 0 || E >= (int64_t)1 << 31 || n_groups < 1 || n_groups > 4) return -1;
+    return slice_bound(E, n_groups) * TP_LAYER_AA_W[layer - TP_AA < 3 ? layer - TP_AA : 3] * RTP_IMG * (int64_t)sizeof(float);
+  }
   if (tp_is_nv4_id(layer)) {
     if (E < 0 || E >= (int64_t)1 << 31 || n_groups < 1 || n_groups > 4) return -1;
     return slice_bound(E, n_groups) * TP_LAYER_NV4_W[layer - TP_NV4 < 3 ? layer - TP_NV4 : 3] * RTP_IMG * (int64_t)sizeof(float);
@@ -585,7 +650,7 @@ hipError_t launch_rtp_forward(const ConvLayerDev& L, const float* x_dst, const f
                               const float* w2, const float* b2, float* out, hipStream_t s) {
   RtpArgs a = rtp_args(x_dst, sh, h, group_offsets, n_groups, w2, b2);
   a.out = out;
-  return tp_dispatch(L, [&](auto shape) { return rtp_launch<decltype(shape)>(a, true, s); });
+  return tp_dispatch_aa(L, [&](auto shape) { return rtp_launch<decltype(shape)>(a, true, s); });
 }
 
 hipError_t launch_rtp_backward(const ConvLayerDev& L, const float* x_dst, const float* sh, const float* h, const int64_t* group_offsets, int n_groups,
@@ -593,13 +658,15 @@ hipError_t launch_rtp_backward(const ConvLayerDev& L, const float* x_dst, const 
                                float* grad_b2, float* workspace, hipStream_t s) {
   RtpArgs a = rtp_args(x_dst, sh, h, group_offsets, n_groups, w2, b2);
   a.g = grad_out; a.gx = grad_x; a.gsh = grad_sh; a.gh = grad_h; a.gw2 = grad_w2; a.gb2 = grad_b2; a.ws = workspace;
-  return tp_dispatch(L, [&](auto shape) { return rtp_launch<decltype(shape)>(a, false, s); });
+  return tp_dispatch_aa(L, [&](auto shape) { return rtp_launch<decltype(shape)>(a, false, s); });
 }
 
 // ---- the radial conv ---------------------------------------------------------------------------------------------------------------------------------------------
 int64_t rconv_workspace(int32_t layer, int64_t E, int32_t n_groups, int64_t n_in, int64_t n_out, int32_t backward) {
   const int64_t lim = (int64_t)1 << 31;
-  const bool nv4 = tp_is_nv4_id(layer);
+  const bool aa = tp_is_aa_id(layer);      // (node rows of the first family's widths)
+  if (aa) layer -= TP_AA;
+  const bool nv4 = !aa && tp_is_nv4_id(layer);
   if ((!nv4 && (layer < 0 || layer > 4)) || E < 0 || E >= lim || n_groups < 1 || n_groups > 4 || n_in < 0 || n_in >= lim || n_out < 0 || n_out >= lim) return -1;
   const int l = nv4 ? (layer - TP_NV4 < 3 ? layer - TP_NV4 : 3) : (layer < 3 ? layer : 3);
   int din = 0, dout = 0;
@@ -612,12 +679,12 @@ int64_t rconv_workspace(int32_t layer, int64_t E, int32_t n_groups, int64_t n_in
   }
   if (!backward) return ws_pad(E * dout) * (int64_t)sizeof(float);      // the tensor product's rows
   // gn [n_out, Dout], the per-edge rows of grad_x [E, Din], the parameter images
-  return (ws_pad(n_out * dout) + ws_pad(E * din)) * (int64_t)sizeof(float) + rtp_backward_workspace(layer, E, n_groups);
+  return (ws_pad(n_out * dout) + ws_pad(E * din)) * (int64_t)sizeof(float) + rtp_backward_workspace(aa ? TP_AA + layer : layer, E, n_groups);
 }
 
 hipError_t launch_rconv_forward(const ConvLayerDev& L, const RconvGraph& gr, const float* x_nodes, const float* sh, const float* h, const int64_t* group_offsets,
                                 int n_groups, const float* w2, const float* b2, float* out_nodes, float* workspace, hipStream_t s) {
-  return tp_dispatch(L, [&](auto shape) {
+  return tp_dispatch_aa(L, [&](auto shape) {
     using S = decltype(shape);
     if (group_offsets[n_groups] == 0) return zero_async(out_nodes, gr.n_out * S::DOUT, s);
     RtpArgs a = rtp_args(x_nodes, sh, h, group_offsets, n_groups, w2, b2);
@@ -632,7 +699,7 @@ hipError_t launch_rconv_forward(const ConvLayerDev& L, const RconvGraph& gr, con
 hipError_t launch_rconv_backward(const ConvLayerDev& L, const RconvGraph& gr, const float* x_nodes, const float* sh, const float* h, const int64_t* group_offsets,
                                  int n_groups, const float* w2, const float* b2, const float* grad_out_nodes, float* grad_x_nodes, float* grad_sh, float* grad_h,
                                  float* grad_w2, float* grad_b2, float* workspace, hipStream_t s) {
-  return tp_dispatch(L, [&](auto shape) {
+  return tp_dispatch_aa(L, [&](auto shape) {
     using S = decltype(shape);
     const int64_t E = group_offsets[n_groups];
     if (E == 0) {

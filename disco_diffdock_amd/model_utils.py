@@ -111,12 +111,18 @@ def _trainable_score_model(args, device, t_to_sigma=None):
                           rot_sigma_max=args.rot_sigma_max, tor_sigma_min=args.tor_sigma_min, tor_sigma_max=args.tor_sigma_max)).to(device)
 
 
-def get_trainable_model(args, device, t_to_sigma=None):
+def get_trainable_model(args, device, t_to_sigma=None, confidence_mode=False):
     """utils/model_utils.py:25-101 (get_model) for TRAINING: ``train_model.TrainableScoreModel``, and with ``args.latent_dim > 0`` (``latent_vocab == 1``)
     ``latent_encoder.TPEncoder`` in front of it in a ``train_model.LatentModelWrapper``, whose state_dict has the ``encoder.`` / ``score_model.`` keys of
     the reference's ``ModelWrapper`` checkpoints.  The encoder reads ``encoder_ns``, ``encoder_nv``, ``encoder_num_conv_layers``,
-    ``encoder_cross_max_distance``, ``encoder_no_esm``, ``latent_*`` and ``training_latent_temperature`` as lines 70-94 there do."""
+    ``encoder_cross_max_distance``, ``encoder_no_esm``, ``latent_*`` and ``training_latent_temperature`` as lines 70-94 there do.
+    ``confidence_mode=True`` with ``all_atoms`` args: ``confidence.TrainableConfidenceModel``, the all-atom ranking model."""
     from .train_model import LatentModelWrapper
+    if confidence_mode:
+        if not getattr(args, 'all_atoms', False):
+            raise RuntimeError('ddk: get_trainable_model: the confidence model that trains is the all-atom model (all_atoms: true)')
+        from .confidence import TrainableConfidenceModel
+        return TrainableConfidenceModel(args, device)
     g = lambda k, d: getattr(args, k, d)
     score_model = _trainable_score_model(args, device, t_to_sigma)
     latent_dim = int(g('latent_dim', 0))

@@ -2,6 +2,7 @@
 PyTorch is used only for device memory and streams; all compute happens in libddk.so."""
 import collections
 import ctypes as C
+import math
 import os
 import warnings
 from types import SimpleNamespace
@@ -161,15 +162,58 @@ def tp_layer_shape(layer, ns=24, nv=6):
     return dict(A=A, P=P, Q=Q, C=C, O=O, R=R, B=B, W=B[4], din=A + 3 * P + 3 * Q + C, dout=O[0] + 3 * O[1] + 3 * O[2] + O[3])
 
 
+def tp_layer_shape_aa(layer, ns=24, nv=6):
+    """Conv layer ``layer`` of the all-atom (confidence) model (all_atom_score_model.py:26, 112-133): e3nn's ``FullyConnectedTensorProduct(in, '1x0e + 1x1o +
+    1x2e', out)`` on the irreps of ``tp_layer_shape``; the table of csrc/k_tp_shape.h and csrc/k_rtp.hip.  The keys of ``tp_layer_shape`` (R: a block's
+    fan-in, B: None, the blocks are not adjacent in the weight row) and ``paths``: e3nn's instructions in its order, each a dict of ``ir_in``, ``ir_sh``,
+    ``ir_out`` (names), ``offset`` and ``mul_in``, ``mul_out`` of its [mul_in, mul_out] matrix in the flat weight row, ``xoff`` / ``ooff`` (where the input and
+    the output irrep start in a node row), ``block`` k and ``row0`` (its first row in weight block k, the order the kernels walk), ``kind`` (the product of one
+    input with the sh row [Y0 | Y1 | Y2]: 'ss' i Y0, 'sv' i Y1, 'vs' i Y0, 'vd' i . Y1, 'vx' i x Y1, 'v2' M(Y2) i with M = [[-y2/sqrt3 - y4, y1, y0],
+    [y1, 2 y2/sqrt3, y3], [y0, y3, -y2/sqrt3 + y4]]) and ``scale`` = sqrt(dim_out / R_k) times the amplitude of the Frobenius-normalised w3j in that form
+    (1, 1/sqrt3, 1/sqrt3, 1/sqrt3, 1/sqrt6, 1/sqrt10).  Instructions without floats (an absent irrep) are left out."""
+    s = tp_layer_shape(layer, ns, nv)
+    A, P, Q, C, O = s['A'], s['P'], s['Q'], s['C'], s['O']
+    R = [r if o else 0 for r, o in zip((A + P, A + P + Q + P, P + Q + C + Q, Q + C), O)]
+    xoff = {'0e': 0, '1o': A, '1e': A + 3 * P, '0o': A + 3 * P + 3 * Q}
+    ooff = {'0e': 0, '1o': O[0], '1e': O[0] + 3 * O[1], '0o': O[0] + 3 * O[1] + 3 * O[2]}
+    mul_in, blk = {'0e': A, '1o': P, '1e': Q, '0o': C}, {'0e': 0, '1o': 1, '1e': 2, '0o': 3}
+    amp = {'ss': 1.0, 'sv': 3 ** -0.5, 'vs': 3 ** -0.5, 'vd': 3 ** -0.5, 'vx': 6 ** -0.5, 'v2': 10 ** -0.5}
+    # (input, sh, output, kind, first row in the output's block), in e3nn's order: input irrep, then sh irrep, then output irrep
+    order = [('0e', '0e', '0e', 'ss', 0), ('0e', '1o', '1o', 'sv', 0), ('1o', '0e', '1o', 'vs', A), ('1o', '1o', '0e', 'vd', A), ('1o', '1o', '1e', 'vx', 0),
+             ('1o', '2e', '1o', 'v2', A + P + Q), ('1e', '0e', '1e', 'vs', P), ('1e', '1o', '1o', 'vx', A + P), ('1e', '1o', '0o', 'vd', 0),
+             ('1e', '2e', '1e', 'v2', P + Q + C), ('0o', '0e', '0o', 'ss', Q), ('0o', '1o', '1e', 'sv', P + Q)]
+    paths, off = [], 0
+    for ir_in, ir_sh, ir_out, kind, row0 in order:
+        k = blk[ir_out]
+        mi, mo = mul_in[ir_in], O[k]
+        if mi * mo == 0:
+            continue
+        dim_out = 3 if k in (1, 2) else 1
+        paths.append(dict(ir_in=ir_in, ir_sh=ir_sh, ir_out=ir_out, kind=kind, offset=off, mul_in=mi, mul_out=mo, xoff=xoff[ir_in], ooff=ooff[ir_out],
+                          block=k, row0=row0, scale=math.sqrt(dim_out / R[k]) * amp[kind]))
+        off += mi * mo
+    return dict(s, R=R, B=None, W=off, paths=paths, sh_dim=9)
+
+
 TP_NV4 = 8      # DDK_TP_NV4 of include/ddk.h: the `layer` argument TP_NV4 + l of the tensor-product ops is layer l of the ns = 24 / nv = 4 family
+
+
+TP_AA = 16      # DDK_TP_AA: TP_AA + l is conv layer l of the all-atom (confidence) family, sh_lmax = 2 (the radial tensor product and the radial conv only)
 
 
 def tp_id_shape(layer, ns=24, nv=6):
     """``tp_layer_shape`` of a `layer` argument of the tensor-product ops: TP_NV4 + l (l in 0..4) is layer l of the ns = 24 / nv = 4 family whatever the
-    context's nv; anything else is conv layer ``layer`` of a model with (``ns``, ``nv``)"""
+    context's nv, TP_AA + l is ``tp_layer_shape_aa(l)``; anything else is conv layer ``layer`` of a model with (``ns``, ``nv``)"""
     if TP_NV4 <= layer < TP_NV4 + 5:
         return tp_layer_shape(layer - TP_NV4, 24, 4)
+    if TP_AA <= layer < TP_AA + 5:
+        return tp_layer_shape_aa(layer - TP_AA)
     return tp_layer_shape(layer, ns, nv)
+
+
+def tp_sh_dim(layer):
+    """floats of an sh row of the tensor-product ops for this `layer` argument: 9 = [Y0 | Y1 | Y2] for the all-atom family, else 4"""
+    return 9 if TP_AA <= layer < TP_AA + 5 else 4
 
 
 HEAD_CENTER, HEAD_TORSION = 0, 1      # DDK_HEAD_CENTER, DDK_HEAD_TORSION of include/ddk.h
@@ -432,8 +476,8 @@ class Context:
         G, E, W = len(offs) - 1, x_dst.shape[0] if E is None else E, self.tp_weight_numel(layer)
         if not 1 <= G <= 4:
             raise RuntimeError(f'ddk: the radial tensor product takes 1..4 edge groups; got {G}')
-        if sh.shape != (E, 4) or h.shape != (E, 72):
-            raise RuntimeError('ddk: the radial tensor product takes sh [E, 4] and h [E, 72]')
+        if sh.shape != (E, tp_sh_dim(layer)) or h.shape != (E, 72):
+            raise RuntimeError(f'ddk: the radial tensor product takes sh [E, {tp_sh_dim(layer)}] and h [E, 72]' + (' (the all-atom family: [Y0 | Y1 | Y2])' if tp_sh_dim(layer) == 9 else ''))
         if w2 is not None:
             w2 = _need_cuda(w2).contiguous().float()
             if w2.shape != (G, W, 72):
@@ -467,7 +511,7 @@ class Context:
         grad_out = _need_cuda(grad_out).contiguous().float()
         if grad_out.dim() != 2 or grad_out.shape[0] != E:
             raise RuntimeError('ddk: rtp_backward takes grad_out [E, Dout]')
-        outs, live = _outputs(need, ((E, x_dst.shape[1]), (E, 4), (E, 72), (G, W, 72), (G, W)), x_dst.device)
+        outs, live = _outputs(need, ((E, x_dst.shape[1]), (E, tp_sh_dim(layer)), (E, 72), (G, W, 72), (G, W)), x_dst.device)
         if not live:
             return tuple(outs)
         ws = None
@@ -552,7 +596,7 @@ class Context:
         grad_out_nodes = _need_cuda(grad_out_nodes).contiguous().float()
         if grad_out_nodes.dim() != 2 or grad_out_nodes.shape[0] != g.n_out:
             raise RuntimeError('ddk: rconv_backward takes grad_out_nodes [n_out, Dout]')
-        outs, live = _outputs(need, ((g.n_in, x_nodes.shape[1]), (E, 4), (E, 72), (G, W, 72), (G, W)), x_nodes.device)
+        outs, live = _outputs(need, ((g.n_in, x_nodes.shape[1]), (E, tp_sh_dim(layer)), (E, 72), (G, W, 72), (G, W)), x_nodes.device)
         if not live:
             return tuple(outs)
         ws = _workspace(self.L.ddk_rconv_workspace(layer, E, G, g.n_in, g.n_out, 1),

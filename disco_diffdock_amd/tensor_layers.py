@@ -31,7 +31,9 @@ kernel (``ddk_conv_forward``), unchanged; an nv=4 layer has no inference kernel 
 same bits on every run.  In a head configuration the layer is ``fused_head_conv`` plus BatchNorm in training and in evaluation
 (``heads.ScoreHeads`` is the module on top); ``train_model.TrainableScoreModel`` assembles the whole model.  The latent-conditioned (DisCo) score model trains
 through ``fused_edge_embedding``'s latent columns and ``ragged_gumbel_softmax``; ``latent_encoder.TPEncoder`` is the encoder in front.  What still does not
-train: the AR predictor, the all-atom / confidence irreps, any other ns / nv.
+train: the AR predictor, the all-atom SCORE model, any other ns / nv.  The all-atom CONFIDENCE model's conv layer (sh_lmax = 2, e3nn's
+FullyConnectedTensorProduct: ``FullyConnectedTensorProduct``, ``sh_second_order``, ``TensorProductConvLayer`` with second-order sh_irreps) trains on the third
+shape family of the radial ops; ``confidence.TrainableConfidenceModel`` is the model on top.
 """
 import math
 
@@ -40,7 +42,7 @@ import torch
 from torch import nn
 from torch.autograd.function import once_differentiable
 
-from .runtime import HEAD_CENTER, HEAD_TORSION, TP_NV4, Context, head_tp_shape, tp_id_shape, tp_layer_shape
+from .runtime import HEAD_CENTER, HEAD_TORSION, TP_AA, TP_NV4, Context, head_tp_shape, tp_id_shape, tp_layer_shape
 
 _ORDER = ('0e', '1o', '1e', '0o')
 _DIM = {'0e': 1, '1o': 3, '1e': 3, '0o': 1}
@@ -85,10 +87,24 @@ def irrep_to_size(irreps):
     return sum(m * _DIM[k] for k, m in parse_irreps(irreps).items())
 
 
-def layer_index(in_irreps, out_irreps, ns=24, nv=None):
+SH_SECOND_ORDER = '1x0e+1x1o+1x2e'      # o3.Irreps.spherical_harmonics(2): the sh irreps of the all-atom (confidence) model
+
+
+def _is_second_order_sh(sh_irreps):
+    return sh_irreps is not None and str(sh_irreps).replace(' ', '') == SH_SECOND_ORDER
+
+
+def layer_index(in_irreps, out_irreps, ns=24, nv=None, sh_irreps=None):
     """The `layer` argument of the tensor-product ops for these irreps (get_irrep_seq, tensor_layers.py:12-27): 0..3 for the score model's family
-    (nv = 6), ``TP_NV4 + l`` for the latent encoder's (nv = 4).  ``nv``: one family alone (None: both are searched)."""
+    (nv = 6), ``TP_NV4 + l`` for the latent encoder's (nv = 4).  ``nv``: one family alone (None: both are searched).  ``sh_irreps`` = '1x0e + 1x1o + 1x2e'
+    names the all-atom family (e3nn's FullyConnectedTensorProduct on the nv = 6 irreps): ``TP_AA + l``."""
     i, o = tuple(parse_irreps(in_irreps).values()), tuple(parse_irreps(out_irreps).values())
+    if _is_second_order_sh(sh_irreps):
+        for l in range(4):
+            s = tp_layer_shape(l, 24, 6)
+            if ns == 24 and nv in (None, 6) and (s['A'], s['P'], s['Q'], s['C']) == i and s['O'] == o:
+                return TP_AA + l
+        raise RuntimeError(f'ddk: no fused kernel for irreps {in_irreps} (x) {sh_irreps} -> {out_irreps} (the all-atom family is compiled in for ns=24, nv=6)')
     for fam_nv, base in ((6, 0), (4, TP_NV4)):
         if nv not in (None, fam_nv) or ns != 24:
             continue
@@ -180,6 +196,49 @@ class FasterTensorProduct(nn.Module):
         return out.reshape(lead + (self.out_size,))
 
 
+class FullyConnectedTensorProduct(nn.Module):
+    """The holder of a conv layer's tensor product in the all-atom (confidence) model, e3nn's ``o3.FullyConnectedTensorProduct(in_irreps, '1x0e + 1x1o +
+    1x2e', out_irreps, shared_weights=False)`` (all_atom_score_model.py:26), as ``FasterTensorProduct`` is for its families: ``.layer`` (``TP_AA + l``),
+    ``.weight_numel`` and ``.out_size``, with the weights in e3nn's instruction order and normalisation (``runtime.tp_layer_shape_aa``).  It has no
+    per-edge-weight form: ``fused_radial_tp`` / ``fused_radial_conv`` run it with the weights formed inside the kernels."""
+
+    def __init__(self, in_irreps, sh_irreps, out_irreps, shared_weights=False, **kwargs):
+        super().__init__()
+        if shared_weights:
+            raise RuntimeError('ddk: FullyConnectedTensorProduct takes per-edge weights from a radial MLP (shared_weights=False)')
+        if not _is_second_order_sh(sh_irreps):
+            raise RuntimeError(f'ddk: FullyConnectedTensorProduct is the all-atom family\'s, sh_irreps {SH_SECOND_ORDER}; got {sh_irreps} (the score heads are fused_head_conv)')
+        self.in_irreps, self.sh_irreps, self.out_irreps = str(in_irreps), str(sh_irreps), str(out_irreps)
+        self.layer = layer_index(in_irreps, out_irreps, sh_irreps=sh_irreps)
+        s = tp_id_shape(self.layer)
+        self.weight_numel, self.out_size = s['W'], s['dout']
+
+    def forward(self, in_, sh, weight):
+        raise RuntimeError(f'ddk: the all-atom family has no per-edge weight form [E, {self.weight_numel}]: use fused_radial_tp or fused_radial_conv, which form '
+                           'the weights inside the kernels')
+
+
+def sh_second_order(sh4):
+    """The sh rows [E, 9] = [Y0 | Y1 | Y2] of the all-atom family (e3nn's component order and 'component' normalisation, normalize=True) from
+    ``fused_edge_embedding``'s rows [E, 4] = [1 | sqrt3 u]: Y2 is a polynomial of the unit vector u that Y1 carries.  A zero-length edge (Y1 = 0: a C-alpha
+    atom and its own residue) gives Y2 = 0, as e3nn does.  Plain torch, no gradient."""
+    with torch.no_grad():
+        sh4 = sh4.detach().float()
+        x, y, z = (sh4[:, 1:4] * (3 ** -0.5)).unbind(-1)
+        s15 = 15 ** 0.5
+        y2 = torch.stack([s15 * x * z, s15 * x * y, (5 ** 0.5) * (y * y - 0.5 * (x * x + z * z)), s15 * y * z, (0.5 * s15) * (z * z - x * x)], -1)
+        return torch.cat([sh4, y2], -1).contiguous()
+
+
+def _fc_parts(blk):
+    """(first Linear, ReLU, Dropout, last Linear) of a radial MLP: an FCBlock (Linear, Identity, ReLU, Dropout, Linear: keys 0 and 4) or the all-atom
+    layer's ``Sequential(Linear, ReLU, Dropout, Linear)`` (keys 0 and 3); None for anything else"""
+    if not isinstance(blk, nn.Sequential) or len(blk) not in (4, 5):
+        return None
+    parts = (blk[0], blk[-3], blk[-2], blk[-1])
+    return parts if all(isinstance(m, t) for m, t in zip(parts, (nn.Linear, nn.ReLU, nn.Dropout, nn.Linear))) else None
+
+
 class _RadialTPFunction(torch.autograd.Function):
     """ddk_rtp_forward with ddk_rtp_backward as its vector-Jacobian product: the tensor product with its weights w2[g] h + b2[g] formed inside the
     kernels, so that neither the per-edge weights [E, W] nor their gradient exist.  Inputs keep their shapes and dtypes: the gradients come back in them."""
@@ -187,7 +246,7 @@ class _RadialTPFunction(torch.autograd.Function):
     @staticmethod
     def forward(fctx, in_, sh, h, w2, b2, layer, offsets, out_size):
         ctx = _ctx_of(in_)
-        x, s, hh = _as_rows(in_, in_.shape[-1]), _as_rows(sh, 4), _as_rows(h, h.shape[-1])
+        x, s, hh = _as_rows(in_, in_.shape[-1]), _as_rows(sh, sh.shape[-1]), _as_rows(h, h.shape[-1])
         w, b = w2.contiguous().float(), b2.contiguous().float()
         out = ctx.rtp_forward(layer, x, s, hh, offsets, w, b, out_size)
         ng = fctx.needs_input_grad
@@ -211,8 +270,8 @@ def _radial_operands(who, tp, fc, x, edge_attr, hidden=None):
     """What fused_radial_tp and fused_radial_conv share: the checks on ``tp`` and ``fc``, then ``fc[i][0..3]`` in torch.  Returns the group offsets, the
     hidden activation [E, 72] and the last Linears stacked, w2 [G, W, 72] and b2 [G, W].  With ``hidden`` given (fused_radial_hidden's output)
     ``fc[i][0..3]`` do not run, and ``edge_attr`` gives the groups alone: G + 1 integer offsets, or one tensor per group whose rows are counted."""
-    if not isinstance(tp, FasterTensorProduct):
-        raise RuntimeError(f'ddk: {who} takes a FasterTensorProduct')
+    if not isinstance(tp, (FasterTensorProduct, FullyConnectedTensorProduct)):
+        raise RuntimeError(f'ddk: {who} takes a FasterTensorProduct (or the all-atom family\'s FullyConnectedTensorProduct)')
     if not x.is_cuda:
         raise RuntimeError(f'ddk {who} runs on the GPU only (no CPU fallback)')
     if hidden is not None and not torch.is_tensor(edge_attr) and len(edge_attr) and not torch.is_tensor(edge_attr[0]):
@@ -232,15 +291,15 @@ def _radial_operands(who, tp, fc, x, edge_attr, hidden=None):
             offs.append(offs[-1] + ea.shape[0])
     if not 1 <= len(fc) <= 4:
         raise RuntimeError(f'ddk: {who} takes one edge_attr tensor per FCBlock, 1..4 of them')
-    for blk in fc:
-        if len(blk) != 5 or not isinstance(blk[4], nn.Linear) or blk[4].in_features != 72 or blk[4].out_features != tp.weight_numel or blk[4].bias is None:
+    for blk in fc:      # an FCBlock, or the all-atom layer's Sequential(Linear, ReLU, Dropout, Linear): the last module is the Linear the kernels run
+        if len(blk) not in (4, 5) or not isinstance(blk[-1], nn.Linear) or blk[-1].in_features != 72 or blk[-1].out_features != tp.weight_numel or blk[-1].bias is None:
             raise RuntimeError(f'ddk: {who} takes 2-layer FCBlocks whose last Linear maps 72 -> weight_numel')
     if hidden is not None:
         if hidden.dim() != 2 or hidden.shape != (offs[-1], 72):
             raise RuntimeError(f'ddk: {who} takes hidden [E, 72] with E = {offs[-1]}, the total of the edge groups; got {tuple(hidden.shape)}')
     else:
-        hidden = torch.cat([blk[:4](ea) for blk, ea in zip(fc, edge_attr)], dim=0) if len(fc) > 1 else fc[0][:4](edge_attr[0])
-    w2, b2 = torch.stack([blk[4].weight for blk in fc]), torch.stack([blk[4].bias for blk in fc])
+        hidden = torch.cat([blk[:-1](ea) for blk, ea in zip(fc, edge_attr)], dim=0) if len(fc) > 1 else fc[0][:-1](edge_attr[0])
+    w2, b2 = torch.stack([blk[-1].weight for blk in fc]), torch.stack([blk[-1].bias for blk in fc])
     return offs, hidden, w2, b2
 
 
@@ -256,7 +315,7 @@ def fused_radial_tp(tp, fc, x_dst, edge_sh, edge_attr):
     if torch.is_grad_enabled() and any(t.requires_grad for t in (x_dst, edge_sh, hidden, w2, b2)):
         return _RadialTPFunction.apply(x_dst, edge_sh, hidden, w2, b2, tp.layer, tuple(offs), tp.out_size)
     ctx = _ctx_of(x_dst)
-    return ctx.rtp_forward(tp.layer, x_dst, edge_sh.reshape(-1, 4), hidden, offs, w2, b2, tp.out_size)
+    return ctx.rtp_forward(tp.layer, x_dst, edge_sh.reshape(-1, edge_sh.shape[-1]), hidden, offs, w2, b2, tp.out_size)
 
 
 class _RadialConvFunction(torch.autograd.Function):
@@ -267,7 +326,7 @@ class _RadialConvFunction(torch.autograd.Function):
     @staticmethod
     def forward(fctx, node_attr, sh, h, w2, b2, layer, offsets, graph):
         ctx = _ctx_of(node_attr)
-        x, s, hh = _as_rows(node_attr, node_attr.shape[-1]), _as_rows(sh, 4), _as_rows(h, h.shape[-1])
+        x, s, hh = _as_rows(node_attr, node_attr.shape[-1]), _as_rows(sh, sh.shape[-1]), _as_rows(h, h.shape[-1])
         w, b = w2.contiguous().float(), b2.contiguous().float()
         out = ctx.rconv_forward(layer, graph, x, s, hh, offsets, w, b)
         ng = fctx.needs_input_grad
@@ -308,7 +367,7 @@ def fused_radial_conv(tp, fc, node_attr, edge_index, edge_sh, edge_attr, out_nod
     if torch.is_grad_enabled() and any(t.requires_grad for t in (node_attr, edge_sh, hidden, w2, b2)):
         return _RadialConvFunction.apply(node_attr, edge_sh, hidden, w2, b2, tp.layer, tuple(offs), graph)
     ctx = _ctx_of(node_attr)
-    return ctx.rconv_forward(tp.layer, graph, node_attr, edge_sh.reshape(-1, 4), hidden, offs, w2, b2)
+    return ctx.rconv_forward(tp.layer, graph, node_attr, edge_sh.reshape(-1, edge_sh.shape[-1]), hidden, offs, w2, b2)
 
 
 class _RadialHiddenFunction(torch.autograd.Function):
@@ -357,11 +416,12 @@ def fused_radial_hidden(fc, node_attr, edge_emb, group_offsets, graph, seed=None
     if not 1 <= len(fc) <= 4 or len(offs) != len(fc) + 1:
         raise RuntimeError('ddk: fused_radial_hidden takes 1..4 FCBlocks and one more group offset than blocks')
     for blk in fc:
-        if (len(blk) != 5 or not isinstance(blk[4], nn.Linear) or blk[4].in_features != 72 or blk[4].bias is None or not isinstance(blk[0], nn.Linear)
-                or blk[0].in_features != 72 or blk[0].out_features != 72 or blk[0].bias is None or not isinstance(blk[2], nn.ReLU)
-                or not isinstance(blk[3], nn.Dropout)):
-            raise RuntimeError('ddk: fused_radial_hidden takes 2-layer FCBlocks: Linear(72, 72) with bias, Identity, ReLU, Dropout, Linear(72, .)')
-    rates = {float(blk[3].p) if blk[3].training else 0.0 for blk in fc}
+        parts = _fc_parts(blk)
+        if (parts is None or parts[3].in_features != 72 or parts[3].bias is None or parts[0].in_features != 72 or parts[0].out_features != 72
+                or parts[0].bias is None):
+            raise RuntimeError('ddk: fused_radial_hidden takes 2-layer FCBlocks: Linear(72, 72) with bias, Identity, ReLU, Dropout, Linear(72, .) '
+                               '(or the all-atom layer\'s Sequential without the Identity)')
+    rates = {float(_fc_parts(blk)[2].p) if _fc_parts(blk)[2].training else 0.0 for blk in fc}
     if len(rates) != 1:
         raise RuntimeError(f'ddk: fused_radial_hidden takes one dropout rate for all groups; got {sorted(rates)}')
     p = rates.pop()
@@ -813,6 +873,8 @@ class _BatchNormParams(nn.Module):
 
 
 class TensorProductConvLayer(nn.Module):
+    all_atom = False      # True on a conv layer of the all-atom (confidence) model: sh_irreps of second order
+
     def __init__(self, in_irreps, sh_irreps, out_irreps, n_edge_features, residual=True, batch_norm=True, dropout=0.0,
                  hidden_features=None, faster=False, edge_groups=1, tp_weights_layers=2, activation='relu'):
         super().__init__()
@@ -824,6 +886,21 @@ class TensorProductConvLayer(nn.Module):
             self.in_irreps, self.out_irreps, self.sh_irreps = str(in_irreps), str(out_irreps), sh_irreps
             self.residual, self.edge_groups, self.out_size = residual, edge_groups, s['dout']
             self.fc = FCBlock(n_edge_features, s['K'], s['W'], tp_weights_layers, dropout, activation)      # a plain FCBlock: keys fc.0.weight, fc.4.bias
+            self.batch_norm = _BatchNormParams(out_irreps) if batch_norm else None
+            return
+        self.all_atom = _is_second_order_sh(sh_irreps)
+        if self.all_atom:
+            # a conv layer of the all-atom (confidence) model (all_atom_score_model.py:15-50): e3nn's FullyConnectedTensorProduct with sh_lmax = 2, one radial
+            # MLP WITHOUT the FCBlock's Identity (keys fc.0.*, fc.3.*), no residual, senders and receivers possibly different node tables
+            if faster or edge_groups != 1 or residual or tp_weights_layers != 2 or activation != 'relu':
+                raise RuntimeError('ddk: an all-atom conv layer (sh_irreps 1x0e + 1x1o + 1x2e) is faster=False, edge_groups=1, residual=False with a 2-layer ReLU radial MLP')
+            if n_edge_features != 72 or hidden_features not in (None, 72):
+                raise RuntimeError('ddk: radial MLP width must be 3*ns = 72')
+            self.in_irreps, self.out_irreps, self.sh_irreps = str(in_irreps), str(out_irreps), sh_irreps
+            self.residual, self.edge_groups = residual, edge_groups
+            self.tp = FullyConnectedTensorProduct(in_irreps, sh_irreps, out_irreps)
+            self.layer, self.out_size = self.tp.layer, self.tp.out_size
+            self.fc = nn.Sequential(nn.Linear(72, 72), nn.ReLU(), nn.Dropout(dropout), nn.Linear(72, self.tp.weight_numel))
             self.batch_norm = _BatchNormParams(out_irreps) if batch_norm else None
             return
         if not faster or edge_groups != 4 or not residual:
@@ -888,9 +965,54 @@ class TensorProductConvLayer(nn.Module):
             self._ctx, self._ctx_key = ctx, key
         return self._ctx
 
+    def _forward_all_atom(self, node_attr, edge_index, edge_attr, edge_sh, out_nodes, reduce, graph=None, hidden=None):
+        """The all-atom layer's forward (all_atom_score_model.py:36-50): ``BN(scatter_mean(tp(node_attr[edge_dst], edge_sh, fc(edge_attr)), edge_src,
+        out_nodes))`` through fused_radial_conv; ``edge_sh`` [E, 9].  BatchNorm is applied ALWAYS: a conv without edges gives BatchNorm of zeros (and moves
+        the running buffers in training), where the score model's layer returns the zeros.  Training and evaluation run the same kernels (the modules' own
+        mode gives dropout rate 0 and BatchNorm on its running buffers)."""
+        if reduce != 'mean':
+            raise RuntimeError("ddk: conv layers aggregate with reduce='mean'")
+        if not node_attr.is_cuda:
+            raise RuntimeError('ddk TensorProductConvLayer runs on the GPU only (no CPU fallback)')
+        n_out = int(out_nodes or node_attr.shape[0])
+        if edge_index.shape[1] == 0:
+            out = torch.zeros((n_out, self.out_size), dtype=torch.float32, device=node_attr.device)
+        elif hidden is not None:
+            out = fused_radial_conv(self.tp, self.fc, node_attr, edge_index, edge_sh, [0, edge_index.shape[1]], out_nodes=n_out, graph=graph, hidden=hidden)
+        else:
+            out = fused_radial_conv(self.tp, self.fc, node_attr, edge_index, edge_sh, edge_attr, out_nodes=n_out, graph=graph)
+        return self.batch_norm(out) if self.batch_norm is not None else out
+
+    def forward_embedded_all_atom(self, recv_attr, send_attr, edge_index, edge_emb, edge_sh, graph=None, hidden_graph=None, seed=None):
+        """One conv of the all-atom model's loop (all_atom_score_model.py:232-268) from the edge EMBEDDING [E, ns]: what ``forward(send_attr, edge_index,
+        [edge_emb | recv_attr[edge_index[0], :ns] | send_attr[edge_index[1], :ns]], edge_sh, out_nodes=recv_attr.shape[0])`` returns, without the row
+        [E, 72]: ``fused_radial_hidden`` on the two scalar tables concatenated (receivers first, the senders' index shifted; torch's cat has a deterministic
+        backward) -> ``fused_radial_conv(hidden=...)`` -> BatchNorm.  ``recv_attr is send_attr``: one table (ll, aa, rr).  ``graph``: the ``ConvGraph`` of
+        ``edge_index`` from the senders to the receivers; ``hidden_graph``: that of the shifted index over the concatenated table (``graph`` itself for one
+        table); both built here otherwise.  ``seed``: of the dropout mask."""
+        if not self.all_atom:
+            raise RuntimeError('ddk: forward_embedded_all_atom is a step of the all-atom model; this layer has forward_embedded')
+        E, n_recv, n_send = edge_index.shape[1], recv_attr.shape[0], send_attr.shape[0]
+        if edge_emb.shape[0] != E:
+            raise RuntimeError(f'ddk: forward_embedded_all_atom takes one edge_emb row per edge; got {edge_emb.shape[0]} for {E} edges')
+        if E == 0:
+            return self._forward_all_atom(send_attr, edge_index, None, edge_sh, n_recv, 'mean')
+        if graph is None:
+            graph = Context.conv_graph(edge_index[0], edge_index[1], n_send, n_recv)
+        if recv_attr is send_attr:
+            table, hidden_graph = recv_attr, graph
+        else:
+            table = torch.cat([recv_attr[:, :24], send_attr[:, :24]], 0)
+            if hidden_graph is None:
+                hidden_graph = Context.conv_graph(edge_index[0], edge_index[1] + n_recv, n_recv + n_send, n_recv + n_send)
+        hidden = fused_radial_hidden(self.fc, table, edge_emb, [0, E], hidden_graph, seed=seed)
+        return self._forward_all_atom(send_attr, edge_index, None, edge_sh, n_recv, 'mean', graph=graph, hidden=hidden)
+
     def forward(self, node_attr, edge_index, edge_attr, edge_sh, out_nodes=None, reduce='mean'):
         if self.head is not None:
             return self._forward_head(node_attr, edge_index, edge_attr, edge_sh, out_nodes, reduce)
+        if self.all_atom:
+            return self._forward_all_atom(node_attr, edge_index, edge_attr, edge_sh, out_nodes, reduce)
         if self.training or self.layer >= TP_NV4 or self.eval_with_training_ops:      # the fused inference kernel is nv = 6 only: an nv = 4 layer evaluates with the training ops
             return self._forward_training(node_attr, edge_index, edge_attr, edge_sh, out_nodes, reduce)
         if reduce != 'mean' or (out_nodes is not None and out_nodes != node_attr.shape[0]):
@@ -928,8 +1050,9 @@ class TensorProductConvLayer(nn.Module):
         atomics.  ``graph``: the ``ConvGraph`` of ``edge_index`` over the nodes, built here otherwise; ``seed``: of the dropout mask
         (``fused_radial_hidden``).  In evaluation the cat is built and ``forward`` runs the inference kernel, unchanged; an nv = 4 layer, which has no inference
         kernel, runs the training ops there too (dropout rate 0, BatchNorm on its running buffers)."""
-        if self.head is not None:
-            raise RuntimeError('ddk: forward_embedded is a step of the conv stack; a head layer has forward alone')
+        if self.head is not None or self.all_atom:
+            raise RuntimeError('ddk: forward_embedded is a step of the conv stack; a head layer has forward alone' if self.head is not None else
+                               'ddk: forward_embedded is a step of the score model\'s conv stack; an all-atom layer has forward_embedded_all_atom')
         sizes = [int(n) for n in group_sizes]
         E = edge_index.shape[1]
         if len(sizes) != self.edge_groups or any(n < 0 for n in sizes) or sum(sizes) != E or edge_emb.shape[0] != E:

@@ -114,6 +114,22 @@ int ddk_set_score_norm_tables(ddk_ctx* ctx, const double* so3_exp_score_norms, i
  *      the context: any finalised device context serves them, with or without weights.  A context with more than eight conv layers refuses the ids that
  *      are also indices of its own layers (DDK_ERR_INVALID; those layers have the shape of layer 3): an id is never reinterpreted.  The fused inference kernel (ddk_conv_forward) has no such ids. */
 #define DDK_TP_NV4 8
+/*      THE THIRD SHAPE FAMILY (the all-atom confidence model, sh_lmax = 2).  `layer` of ddk_rtp_*, ddk_rconv_*, ddk_rtp_backward_workspace and
+ *      ddk_rconv_workspace also takes DDK_TP_AA + l, l in 0..4: conv layer l of models/all_atom_score_model.py, e3nn's
+ *      FullyConnectedTensorProduct(in, 1x0e + 1x1o + 1x2e, out) on the irreps of the first family (Din 24 / 42 / 60 / 84, Dout 42 / 60 / 84 / 84;
+ *      W = 720 / 972 / 1224 / 1944 / 1944).  For these ids
+ *        - sh has 9 floats per edge, [Y0 | Y1 (3) | Y2 (5)] in e3nn's component order and 'component' normalisation (no alignment is asked of it); the
+ *          op is bilinear in (x, sh, w) for any sh row;
+ *        - a weight row is e3nn's: one [mul_in, mul_out] matrix per instruction, the instructions in the order (input irrep, sh irrep, output irrep),
+ *          each path scaled by sqrt(dim_out / fan-in of its output) times the Frobenius-normalised Wigner 3j (layer 3: (0e,0e,0e) @ 0, (0e,1o,1o) @ 576,
+ *          (1o,0e,1o) @ 720, (1o,1o,0e) @ 756, (1o,1o,1e) @ 900, (1o,2e,1o) @ 936, (1e,0e,1e) @ 972, (1e,1o,1o) @ 1008, (1e,1o,0o) @ 1044,
+ *          (1e,2e,1e) @ 1188, (0o,0e,0o) @ 1224, (0o,1o,1e) @ 1800);
+ *        - grad_sh is not implemented (poses are data where this model trains): a non-NULL grad_sh is DDK_ERR_INVALID;
+ *        - ddk_tp_forward / ddk_tp_backward (per-edge weights [E, W]) refuse the ids by name: nothing in this model's training holds [E, 1944].
+ *      Like DDK_TP_NV4 + l the ids name a shape, not a layer of the context (a context holds at most 16 conv layers, indices 0..15, so none of its own
+ *      layers has such an index; one that did would be refused, not reinterpreted).  The same exact fp32 chains, no atomics, the same bits from run to
+ *      run and whichever outputs are asked for. */
+#define DDK_TP_AA 16
 int ddk_tp_forward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float* sh, const float* w,
                    int64_t E, float* out, void* stream);
 
@@ -122,7 +138,7 @@ int ddk_tp_forward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float*
 int ddk_tp_backward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const float* sh, const float* w, const float* grad_out, int64_t E,
                     float* grad_x, float* grad_sh, float* grad_w, void* stream);
 
-/* ---- The radial tensor product of conv-layer shape `layer` (0..4, or DDK_TP_NV4 + 0..4): out[e] = FasterTensorProduct(x_dst[e], sh[e], w2[g(e)] h[e] + b2[g(e)]), the per-edge
+/* ---- The radial tensor product of conv-layer shape `layer` (0..4, DDK_TP_NV4 + 0..4, or DDK_TP_AA + 0..4 with sh [E, 9]: see DDK_TP_AA): out[e] = FasterTensorProduct(x_dst[e], sh[e], w2[g(e)] h[e] + b2[g(e)]), the per-edge
  *      weights [E, W] never stored (models/tensor_layers.py:154-156 without the last Linear's output and the cat).  x_dst [E, Din], sh [E, 4], h [E, 72] (the
  *      radial MLP's hidden activation), w2 [n_groups, W, 72] and b2 [n_groups, W] (fc[g][4].weight / .bias stacked), out [E, Dout]: DEVICE pointers, fp32,
  *      contiguous.  group_offsets: HOST array of n_groups + 1 entries (n_groups in 1..4), 0 = o_0 <= ... <= o_G = E; edge e belongs to group g iff
@@ -139,7 +155,7 @@ int ddk_rtp_backward(ddk_ctx* ctx, int32_t layer, const float* x_dst, const floa
                      const float* w2, const float* b2, const float* grad_out, int64_t E, float* grad_x, float* grad_sh, float* grad_h, float* grad_w2,
                      float* grad_b2, void* workspace, void* stream);
 
-/* Bytes of ddk_rtp_backward's workspace: a function of its arguments alone (never more than 160 MB); -1 for a layer outside 0..4 and DDK_TP_NV4 + 0..4, n_groups outside 1..4,
+/* Bytes of ddk_rtp_backward's workspace: a function of its arguments alone (never more than 160 MB); -1 for a layer outside 0..4, DDK_TP_NV4 + 0..4 and DDK_TP_AA + 0..4, n_groups outside 1..4,
  * E < 0 or E >= 2^31.  Host function, no context. */
 int64_t ddk_rtp_backward_workspace(int32_t layer, int64_t E, int32_t n_groups);
 
@@ -175,7 +191,7 @@ int ddk_rconv_backward(ddk_ctx* ctx, int32_t layer, const float* x_nodes, int64_
                        float* grad_x_nodes, float* grad_sh, float* grad_h, float* grad_w2, float* grad_b2, void* workspace, void* stream);
 
 /* Bytes of the workspace of ddk_rconv_forward (backward == 0) or ddk_rconv_backward (backward != 0): a function of its arguments alone, whichever outputs
- * are asked for; -1 for a layer outside 0..4 and DDK_TP_NV4 + 0..4, n_groups outside 1..4, E < 0 or E >= 2^31, n_in or n_out outside 0 .. 2^31 - 1.  Host function, no context. */
+ * are asked for; -1 for a layer outside 0..4, DDK_TP_NV4 + 0..4 and DDK_TP_AA + 0..4, n_groups outside 1..4, E < 0 or E >= 2^31, n_in or n_out outside 0 .. 2^31 - 1.  Host function, no context. */
 int64_t ddk_rconv_workspace(int32_t layer, int64_t E, int32_t n_groups, int64_t n_in, int64_t n_out, int32_t backward);
 
 /* ---- The radial MLP's hidden layer from the edge embedding and the node table: the cat of the reference's embed loop (models/score_model.py:227-230) and
